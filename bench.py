@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W          # N > 1: starts its own N rank processes
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      # or under a launcher
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # + DIR/<name>.npy: what the last timed step computed
 
 One "step" = Trainer.iteration's per-batch body (src/trainers.py:100-107) on one batch of the
 ML-1M-shaped synthetic workload (C1 of SURVEY 8d: V=3417, L=50, d=64, 2 layers, 2 heads, c=3,
@@ -24,6 +25,7 @@ sys.path.insert(0, ROOT)
 FP32_MFMA_PEAK_TFLOPS = 157.3        # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense, spec
 BF16_MFMA_PEAK_TFLOPS = 2500.0       # MI355X_MICROARCH.md: bf16 MFMA, dense (not the 2:1-sparse headline)
 PMC_PROFILE = os.path.join("profiles", "r03_pmc_C1.csv")     # committed rocprofv3 --pmc passes of this round's library
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: every file of DIR together, .npy headers included
 
 
 def model_args(a):
@@ -77,6 +79,37 @@ def cpu_baseline(a, budget_s=12.0):
                                    f"{r['cores']} cores): port {r['port_seq_per_s']} vs imported reference {r['reference_seq_per_s']} seq/s; "
                                    "reference-equivalent CPU rate on this host ~= value / ref_ratio")
     return out
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write every tensor of ``arrays`` (name -> tensor) as ``out_dir/<name>.npy``: float64 stays float64, everything else
+    is written as float32.  The files stay within ``limit`` bytes: from the smallest array up, an array is written whole
+    when it fits in an equal split of the budget still left, otherwise as a fixed sample of that size -- its flat elements
+    at ``unique(default_rng(0).integers(0, numel, share))``, sorted -- so that two runs of the same arguments, and two
+    builds of the project, write the same elements.  Returns a summary."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    item = {k: 8 if t.dtype == torch.float64 else 4 for k, t in arrays.items()}
+    budget = limit - 256 * len(arrays)                  # room for the .npy headers
+    keep = {}
+    for i, name in enumerate(sorted(arrays, key=lambda k: arrays[k].numel() * item[k])):
+        share = budget // (len(arrays) - i)
+        keep[name] = min(arrays[name].numel(), max(1, share // item[name]))
+        budget -= keep[name] * item[name]
+    written, sampled = 0, []
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        if keep[name] < n:
+            idx = np.unique(np.random.default_rng(0).integers(0, n, size=keep[name]))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            sampled.append(name)
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy())
+        written += os.path.getsize(path)
+    assert written <= limit, (written, limit)
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": written, "sampled": sampled}
 
 
 def fused_shape(a):
@@ -265,7 +298,12 @@ def main():
     ap.add_argument("--exchange", choices=["auto", "rccl", "rccl_bucketed", "p2p"], default="auto",
                     help="gradient exchange of the data-parallel step: RCCL all-reduce(s), or the one-shot peer-to-peer read-reduce "
                          "fused into Adam (IPC-mapped peer arenas over xGMI)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed -- its loss and the parameters after its "
+                         "Adam update -- as DIR/<name>.npy (rank 0; at most 64 MB in all, a fixed sample of larger outputs)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus > 1 and world == 1 and "RANK" not in os.environ:
@@ -409,6 +447,12 @@ def main():
         dt = float(t.item())
     final_loss = float(loss.item())
     assert np.isfinite(final_loss), "training diverged"
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # before anything below runs more steps on this model (the roofline's eager steps)
+        arrays = {"loss": loss.reshape(1)}
+        arrays.update(model.state_dict())
+        dumped = dump_outputs(a.dump_outputs, arrays)
 
     pruned = fused_shape(a) and a.layers >= 2 and not model._plan(B).options["no_prune_top"]
     out = {
@@ -424,6 +468,8 @@ def main():
                              (f"; data-parallel exchange: {trainer.exchange_desc()}" if pg is not None else ""),
                    "final_loss": round(final_loss, 4)},
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     if a.dtype == "bf16":
         out["config"]["precision"] = ("bf16 storage of the saved activations and of a bf16 shadow of the Linear weights, bf16 MFMA "
                                       "with fp32 accumulation; fp32 master weights, LayerNorm, softmax, loss and Adam (config C2's "

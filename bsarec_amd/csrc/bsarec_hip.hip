@@ -177,6 +177,7 @@ struct bsarec_plan {
     long long* stamps = nullptr;             // diagnostic stamp buffer (bsarec_debug_stamps)
     bsarec_hook_t dense_hook = nullptr; void* dense_hook_user = nullptr;   // bsarec_plan_set_dense_grad_hook
     float* lookup_grad = nullptr;            // target of the embedding scatter when the dense dE is exchanged early
+    unsigned long long* lookup_acc = nullptr;  // [V][d] fixed-point sum of the scatter (kernels.h), zero between steps
 };
 static ProfState* prof_of(bsarec_plan* p) { return &p->prof; }
 static bool bf_products_of(const bsarec_plan* p) { return p->bf_products; }
@@ -296,6 +297,7 @@ static void carve(bsarec_plan& p, char* base, size_t* total) {
     p.pos_slices = cdiv(B, 64);
     p.part_pos = cv.take<float>((long)p.pos_slices * L * d);
     p.trash = cv.take<float>(1024);
+    p.lookup_acc = cv.take<unsigned long long>((long)c.item_size * d);
     p.part_kvb = cv.take<float>(2 * B * d);
     for (int l = 0; l < N; ++l) p.part_cwL[l] = c.filter_kind == 1 ? cv.take<float>(B * c.cutoff_bins * d * 2) : nullptr;
     // pruned top block: its last-row gradient operands and the rank-1 key / value operands live in their own compact
@@ -353,6 +355,9 @@ extern "C" int bsarec_plan_create(bsarec_plan_t** out, const bsarec_config_t* cf
     size_t total = 0;
     carve(*p, p->ws, &total);
     if (total > workspace_bytes) { delete p; return -12; }
+    if (hipMemset(p->lookup_acc, 0, (size_t)cfg->item_size * cfg->hidden * sizeof(unsigned long long)) != hipSuccess) {
+        delete p; return -12;
+    }
 
     // reduction job table: per layer 19 jobs (state_dict order), then the 2 embedding LayerNorm jobs
     const long d = cfg->hidden;
@@ -1049,6 +1054,9 @@ static bool can_fuse_adam(const bsarec_plan& p, const bsarec_adam_t& a) {
 static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, const bsarec_adam_t* fuse_adam) {
     if (!p) return -10;
     if (!p->G.item_emb) return -13;
+    // fused Adam reads the item table's gradient from the arena, where the lookup sum must land: refuse before anything is
+    // launched (an early return after the scatter would leave its sums in lookup_acc for the next step)
+    if (fuse_adam && p->lookup_grad) return -21;
     PlanScope scope(p);
     hipStream_t s = (hipStream_t)stream;
     const bsarec_config_t& c = p->cfg;
@@ -1310,11 +1318,11 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
                     ScatterP sc;                       // ... and so does the embedding-gradient scatter (block 0's launch: dz is complete)
                     memset(&sc, 0, sizeof(sc));
                     if (p->scatter_in_block && l == 0) {
-                        sc.de = p->dz; sc.ids32 = p->ids32; sc.T = T; sc.dE = p->lookup_grad ? p->lookup_grad : p->G.item_emb;
+                        sc.de = p->dz; sc.ids32 = p->ids32; sc.T = T; sc.dA = p->lookup_acc;
                         sc.nblocks = cdiv(T, SCATTER_FLOATS / 64);
                     }
                     for (int i = 0; i < dw_np; ++i) if (!dw_problem_ok(DW.P[i])) return -21;
-                    if (sc.nblocks && (!sc.de || !sc.ids32 || !sc.dE)) return -21;
+                    if (sc.nblocks && (!sc.de || !sc.ids32 || !sc.dA)) return -21;
                     ProfScope prof(BSAREC_K_DW1, s);
                     const dim3 dw_grid(8 * cdiv(ns, 8) * (dw_nu - DW.nsmall) + DW.nsmall * DW.small_slabs + sc.nblocks + (tk_here.state ? 1 : 0));
                     LAUNCH(dw_direct_kernel, dw_grid, dim3(256), 0, s, DW, tk_here, sc);
@@ -1365,7 +1373,7 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
         if (!p->scatter_in_block)
         DISPATCH_LPR(d, {
             constexpr int CHUNK = SCATTER_FLOATS / (LPR * 4);
-            constexpr size_t smem = SCATTER_FLOATS * 4 + 2 * CHUNK * 4;
+            constexpr size_t smem = SCATTER_FLOATS * 8 + 2 * CHUNK * 4;
             static bool attr = false;
             if (!attr) {
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(embed_bwd_kernel<LPR>),
@@ -1374,11 +1382,15 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
             }
             const int sb = cdiv(T, CHUNK);
             LAUNCH(embed_bwd_kernel<LPR>, dim3(sb + L * p->pos_slices), dim3(ROW_THREADS), smem, se, p->dz, p->ids32, B, L, d,
-                   p->lookup_grad ? p->lookup_grad : p->G.item_emb, p->part_pos, sb);
+                   p->lookup_acc, p->part_pos, sb);
             HIPCHK(hipGetLastError());
         });
         // ---- ONE deterministic second-stage reduction for every split-K slab and LayerNorm / beta partial
         // (no empty blocks: flat block map); its extra last block closes the optimisation step when asked to
+        // (the lookup-path sum of the item-table gradient joins its target here: after every scatter block has finished)
+        LookupAcc la;
+        la.acc = p->lookup_acc; la.dst = p->lookup_grad ? p->lookup_grad : p->G.item_emb; la.n4 = (long)c.item_size * d / 4;
+        la.nblocks = (int)std::min<long>(cdiv(la.n4, ROW_THREADS), 1024);
         if (fuse_adam) {
             const bsarec_adam_t& a = *fuse_adam;
             AdamFuseP A;
@@ -1386,14 +1398,14 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
             A.w = a.params; A.g = const_cast<float*>(a.grads); A.m = a.exp_avg; A.v = a.exp_avg_sq;
             A.b1 = a.beta1; A.b2 = a.beta2; A.eps = a.eps; A.wd = a.weight_decay;
             A.shadow = (unsigned short*)a.shadow_bf16; A.shadow_from = a.shadow_bf16 ? a.shadow_from : a.n;
-            A.item_off = p->G.item_emb - a.grads; A.item_n4 = (long)c.item_size * d / 4;
+            A.item_off = p->G.item_emb - a.grads; A.item_n4 = (long)c.item_size * d / 4; A.lookup_acc = la.acc;
             int ab = cdiv(A.item_n4, ROW_THREADS);
             if (ab > 1024) ab = 1024;
             LAUNCH(reduce_adam_kernel, dim3(p->red_blocks + ab), dim3(ROW_THREADS), 0, s, p->pruned ? p->jobs_pruned : p->jobs,
                    p->blockmap, p->red_blocks, (const uint64_t*)p->state, A);
         } else
-        LAUNCH(multi_reduce_flat_kernel, dim3(p->red_blocks + (tick.state ? 1 : 0)), dim3(ROW_THREADS), 0, s,
-               p->pruned ? p->jobs_pruned : p->jobs, p->blockmap, p->red_blocks, tick);
+        LAUNCH(multi_reduce_flat_kernel, dim3(p->red_blocks + la.nblocks + (tick.state ? 1 : 0)), dim3(ROW_THREADS), 0, s,
+               p->pruned ? p->jobs_pruned : p->jobs, p->blockmap, p->red_blocks, tick, la);
         HIPCHK(hipGetLastError());
     }
     return 0;

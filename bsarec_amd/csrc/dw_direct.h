@@ -335,19 +335,19 @@ __device__ __forceinline__ void dw_wg_body(const DwProblem& Q, int m0, int n0, i
 // sc.nblocks > 0: the lookup-path scatter of the item-table gradient (embed_scatter_block, 64-token chunks) rides here
 // too, as the workgroups after the weight-gradient ones: light, latency-bound blocks that fill the slots the big
 // workgroups leave free instead of a launch of their own (11.6 us + a launch boundary at C1).
-struct ScatterP { const float* de; const int* ids32; int T; float* dE; int nblocks; };
+struct ScatterP { const float* de; const int* ids32; int T; unsigned long long* dA; int nblocks; };
 // (One instantiation for fp32 and bf16-storage plans: with the bf16 loop compiled in, the fp32 path of this kernel measured 0.5 %
 // of the step FASTER than an fp32-only instantiation -- 0.1568 against 0.1575 ms, three A/B pairs on one box; scheduling luck,
 // kept because it is measured.  The logits backward below is the opposite case and has two.)
 __global__ void __launch_bounds__(256)
 dw_direct_kernel(const DwP G, const TickP tk, const ScatterP sc) {
     __shared__ __attribute__((aligned(16))) float red[3][66][64];      // accumulators (64) + bias sums (2) of waves 1..3
-    static_assert(sizeof(red) >= (SCATTER_FLOATS + 2 * (SCATTER_FLOATS / 64)) * 4, "scatter scratch fits the reduction scratch");
+    static_assert(sizeof(red) >= (2 * SCATTER_FLOATS + 2 * (SCATTER_FLOATS / 64)) * 4, "scatter scratch fits the reduction scratch");
     {
         const int nmain = 8 * ((G.nslab + 7) >> 3) * (G.nunits - G.nsmall) + G.nsmall * G.small_slabs;
         if ((int)blockIdx.x >= nmain) {
             const int x = blockIdx.x - nmain;
-            if (x < sc.nblocks) embed_scatter_block<16>(sc.de, sc.ids32, sc.T, 64, sc.dE, x, &red[0][0][0]);
+            if (x < sc.nblocks) embed_scatter_block<16>(sc.de, sc.ids32, sc.T, 64, sc.dA, x, &red[0][0][0]);
             else if (tk.state) tick_body(tk, &red[0][0][0]);
             return;
         }

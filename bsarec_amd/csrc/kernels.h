@@ -491,20 +491,45 @@ dlast_kernel(const float* __restrict__ slabs, int nsplit, long slab_stride, int 
 
 // =============================================================================================
 // embedding-gradient tail: dPos[t] = sum_b de[b,t]  (deterministic), dE[ids] += de for ids != 0
-// (padding_idx = 0 suppresses only the lookup gradient, src/model/_abstract_model.py:10).  The dense
-// logits-path dE is already in place; rows are added with full-row (>= 64 B contiguous) f32 atomics.
+// (padding_idx = 0 suppresses only the lookup gradient, src/model/_abstract_model.py:10).  The lookup rows are summed as
+// 64-bit fixed point (2^-40 units) with integer atomics -- LDS inside a chunk, then one global row add per chunk leader
+// into the plan's accumulator -- so the sum does not depend on the order in which tokens and chunks arrive: a step gives
+// the same gradient bit for bit on every run.  The final reduction kernel of the backward adds the accumulator once onto
+// the dense logits-path dE and zeroes it (LookupAcc).
 // =============================================================================================
+#define LOOKUP_FIX_ONE 0x1p40f         // fixed-point unit: |sum| < 2^23 representable, resolution 2^-40
+__device__ __forceinline__ unsigned long long lookup_fix(float x) {
+    return (unsigned long long)(long long)rintf(fminf(fmaxf(x * LOOKUP_FIX_ONE, -0x1p62f), 0x1p62f));
+}
+__device__ __forceinline__ float lookup_unfix(unsigned long long a) { return (float)((double)(long long)a * 0x1p-40); }
+// accumulator -> float: dst[i] += acc[i], acc[i] = 0 (float4 group i4).  Items no token of the step looked up hold zero:
+// nothing to add, nothing to write back.
+struct LookupAcc { unsigned long long* acc; float* dst; long n4; int nblocks; };
+__device__ __forceinline__ bool lookup_take(unsigned long long* acc, long i4, f32x4& add) {
+    ulonglong2* a = reinterpret_cast<ulonglong2*>(acc + 4 * i4);
+    const ulonglong2 x = a[0], y = a[1];
+    if (!(x.x | x.y | y.x | y.y)) return false;
+    a[0] = make_ulonglong2(0ull, 0ull); a[1] = make_ulonglong2(0ull, 0ull);
+    add = f32x4{lookup_unfix(x.x), lookup_unfix(x.y), lookup_unfix(y.x), lookup_unfix(y.y)};
+    return true;
+}
+__device__ __forceinline__ void lookup_flush(const LookupAcc& la, long first, long stride) {
+    f32x4 add;
+    for (long i = first; i < la.n4; i += stride)
+        if (lookup_take(la.acc, i, add)) st4(la.dst + 4 * i, ld4(la.dst + 4 * i) + add);
+}
 #ifndef SCATTER_FLOATS
 #define SCATTER_FLOATS 4096           // LDS row accumulators per block: chunk = 4096 / (4*LPR) tokens (64 at d = 64:
                                       // 200 blocks at C1; 128-token chunks measured 18.2 us, 64- and 32-token chunks 11.6 us)
 #endif
-// One scatter block: CHUNK tokens starting at chunk * CHUNK.  esm: SCATTER_FLOATS floats + 2 * CHUNK ints of LDS.
+// One scatter block: CHUNK tokens starting at chunk * CHUNK into the fixed-point accumulator dA ([V][d]).
+// esm: SCATTER_FLOATS 64-bit words + 2 * CHUNK ints of LDS.
 template <int LPR>
 __device__ __forceinline__ void embed_scatter_block(const float* __restrict__ de, const int* __restrict__ ids32, int T, int d,
-                                                    float* __restrict__ dE, int chunk, float* __restrict__ esm) {
+                                                    unsigned long long* __restrict__ dA, int chunk, float* __restrict__ esm) {
     constexpr int RPP = ROW_THREADS / LPR, W = LPR * 4, CHUNK = SCATTER_FLOATS / W;
-    float* acc = esm;                                   // [CHUNK][W]
-    int* sid = reinterpret_cast<int*>(esm + SCATTER_FLOATS);      // [CHUNK]
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(esm);     // [CHUNK][W]
+    int* sid = reinterpret_cast<int*>(esm + 2 * SCATTER_FLOATS);  // [CHUNK]
     int* lead = sid + CHUNK;                                      // [CHUNK]
     const int lr = threadIdx.x / LPR, lc = (threadIdx.x % LPR) << 2;
     const bool colok = lc < d;
@@ -516,7 +541,7 @@ __device__ __forceinline__ void embed_scatter_block(const float* __restrict__ de
         const int t0 = chunk * CHUNK;
         const int n = min(CHUNK, T - t0);
         for (int i = threadIdx.x; i < CHUNK; i += ROW_THREADS) sid[i] = i < n ? ids32[t0 + i] : 0;
-        for (int i = threadIdx.x; i < SCATTER_FLOATS / 4; i += ROW_THREADS) st4(acc + 4 * i, f32x4{0, 0, 0, 0});
+        for (int i = threadIdx.x; i < SCATTER_FLOATS; i += ROW_THREADS) acc[i] = 0ull;
         __syncthreads();
         constexpr int NP = CHUNK / RPP;                   // rows per thread group, loads issued together
         f32x4 g[NP];
@@ -543,13 +568,14 @@ __device__ __forceinline__ void embed_scatter_block(const float* __restrict__ de
         for (int p = 0; p < NP; ++p) {
             const int j = lr + p * RPP;
             if (colok && j < n && sid[j] != 0) {          // padding_idx = 0: no lookup gradient for id 0
-                float* a = acc + lead[j] * W + lc;
-                atomicAdd(a + 0, g[p].x); atomicAdd(a + 1, g[p].y); atomicAdd(a + 2, g[p].z); atomicAdd(a + 3, g[p].w);
+                unsigned long long* a = acc + lead[j] * W + lc;
+                atomicAdd(a + 0, lookup_fix(g[p].x)); atomicAdd(a + 1, lookup_fix(g[p].y));
+                atomicAdd(a + 2, lookup_fix(g[p].z)); atomicAdd(a + 3, lookup_fix(g[p].w));
             }
         }
         __syncthreads();
-        // one leader row per wave-instruction: lane = column, so every global_atomic_add_f32 covers 256 contiguous
-        // bytes (the full-rate shape; 4-byte pieces at a 16-byte stride run ~17x slower)
+        // one leader row per wave-instruction: lane = column, so every global 64-bit atomic add covers 512 contiguous
+        // bytes (contiguous rows: 4-byte pieces at a 16-byte stride ran ~17x slower as float atomics)
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
         constexpr int PW = CHUNK / (ROW_THREADS / 64);      // tokens owned by one wave (<= 64)
         const int j0 = wv * PW, myj = j0 + lane;
@@ -560,7 +586,7 @@ __device__ __forceinline__ void embed_scatter_block(const float* __restrict__ de
             todo &= todo - 1;
             const long row = (long)sid[j] * d;
             for (int c0 = 0; c0 < d; c0 += 64)
-                if (c0 + lane < d) unsafeAtomicAdd(dE + row + c0 + lane, acc[j * W + c0 + lane]);
+                if (c0 + lane < d) atomicAdd(dA + row + c0 + lane, acc[j * W + c0 + lane]);
         }
     }
 }
@@ -568,13 +594,13 @@ __device__ __forceinline__ void embed_scatter_block(const float* __restrict__ de
 template <int LPR>
 __global__ void __launch_bounds__(ROW_THREADS)
 embed_bwd_kernel(const float* __restrict__ de, const int* __restrict__ ids32, int B, int L, int d,
-                 float* __restrict__ dE, float* __restrict__ dPos, int scatter_blocks) {
+                 unsigned long long* __restrict__ dA, float* __restrict__ dPos, int scatter_blocks) {
     constexpr int RPP = ROW_THREADS / LPR, W = LPR * 4;
     extern __shared__ __attribute__((aligned(16))) float esm[];
     const int lr = threadIdx.x / LPR, lc = (threadIdx.x % LPR) << 2;
     const bool colok = lc < d;
     if ((int)blockIdx.x < scatter_blocks) {
-        embed_scatter_block<LPR>(de, ids32, B * L, d, dE, blockIdx.x, esm);
+        embed_scatter_block<LPR>(de, ids32, B * L, d, dA, blockIdx.x, esm);
         return;
     }
     float (*red)[W] = reinterpret_cast<float (*)[W]>(esm);
@@ -718,9 +744,14 @@ __global__ void __launch_bounds__(ROW_THREADS) adam_tick_kernel(TickP tk) {
 }
 
 __global__ void __launch_bounds__(ROW_THREADS)
-multi_reduce_flat_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ blockmap, int nblocks, TickP tk) {
+multi_reduce_flat_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ blockmap, int nblocks, TickP tk,
+                         const LookupAcc la) {
     __shared__ float red[ROW_THREADS];
-    if ((int)blockIdx.x >= nblocks) { tick_body(tk, red); return; }
+    if ((int)blockIdx.x >= nblocks + la.nblocks) { tick_body(tk, red); return; }
+    if ((int)blockIdx.x >= nblocks) {
+        lookup_flush(la, (long)(blockIdx.x - nblocks) * ROW_THREADS + threadIdx.x, (long)la.nblocks * ROW_THREADS);
+        return;
+    }
     const int bm = blockmap[blockIdx.x];
     reduce_chunk(jobs[bm >> 16], bm & 0xFFFF, reinterpret_cast<float(*)[64]>(red));
 }
@@ -789,6 +820,7 @@ struct AdamFuseP {
     float *w, *g, *m, *v; float b1, b2, eps, wd;
     unsigned short* shadow; long shadow_from;
     long item_off, item_n4;            // the item table inside the flat arena: element offset, float4 count
+    unsigned long long* lookup_acc;    // the lookup-path sum of the item-table gradient (fixed point), added here once
 };
 __global__ void __launch_bounds__(ROW_THREADS)
 reduce_adam_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ blockmap, int nblocks,
@@ -836,6 +868,11 @@ reduce_adam_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ b
     for (long i = (long)(blockIdx.x - nblocks) * ROW_THREADS + threadIdx.x; i < A.item_n4; i += nb * ROW_THREADS) {
         const long o = A.item_off + 4 * i;
         f32x4 wi = ld4(A.w + o), gi = ld4(A.g + o), mi = ld4(A.m + o), vi = ld4(A.v + o);
+        f32x4 add;
+        if (A.lookup_acc && lookup_take(A.lookup_acc, i, add)) {
+            gi += add;
+            st4(A.g + o, gi);
+        }
         if (A.wd != 0.f) gi += A.wd * wi;
         mi = A.b1 * mi + (1.0f - A.b1) * gi;
         vi = A.b2 * vi + (1.0f - A.b2) * gi * gi;

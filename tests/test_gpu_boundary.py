@@ -15,7 +15,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import E2E_CASES, GOLDEN, load_e2e
+from conftest import E2E_CASES, GOLDEN, ROOT, load_e2e
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -266,11 +266,45 @@ def test_bench_command_of_the_driver_builds_no_graph_on_the_clock():
     assert fd2.pos // 32 == 25 and ran > 25
     fd2.run(ran - 25)
     torch.cuda.synchronize()
-    # (float atomics in the embedding scatter: arrival order differs run to run, Adam turns a sign flip of a ~0 gradient
-    #  into a +-lr step -- compare up to a small fraction of such elements, as the graph-vs-eager test does)
+    # (a tolerance from when the embedding scatter summed with float atomics: Adam turns a sign flip of a ~0 gradient into
+    #  a +-lr step -- compare up to a small fraction of such elements, as the graph-vs-eager test does)
     bad = (arena_g - tr2.model._arena).abs() > 5e-5
     print("graph vs eager after", ran, "steps: fraction off", bad.float().mean().item())
     assert bad.float().mean().item() <= 1e-2
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """`bench.py --steps K --dump-outputs DIR`, run twice with the same arguments: the result line counts exactly K timed steps
+    and holds ms_per_step; DIR holds the last step's loss and the parameters after its Adam update (the state_dict keys) in
+    float32.  Same inputs and a step without order-dependent float sums: the two runs write the same bits -- also when the
+    second one goes on to the roofline section, whose extra eager steps on the same model must come after the dump."""
+    import subprocess
+    import sys
+    from bsarec_amd import BSARecModel
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--batch", "32",
+           "--item_size", "301", "--no-secondary", "--no-cpu-baseline"]
+    lines = []
+    for i, extra in enumerate((["--no-roofline"], [])):
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / f"run{i}")], capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    for line in lines:
+        assert line["steps"] == 7 and line["ms_per_step"] > 0
+        assert line["dump_outputs"]["sampled"] == [] and line["dump_outputs"]["bytes"] <= 64 << 20
+    assert "roofline" not in lines[0] and "roofline" in lines[1]
+    import bench
+    a = argparse.Namespace(item_size=301, hidden=64, seq_len=50, batch=32, layers=2, heads=2, dtype="f32")
+    params = BSARecModel(bench.model_args(a)).state_dict()
+    assert sorted(os.listdir(tmp_path / "run0")) == sorted([f"{k}.npy" for k in params] + ["loss.npy"])
+    l0, l1 = (np.load(tmp_path / f"run{i}" / "loss.npy") for i in range(2))
+    assert l0.dtype == np.float32 and l0.shape == (1,)
+    assert all(abs(float(l0[0]) - line["config"]["final_loss"]) <= 1e-4 for line in lines)
+    assert np.array_equal(l0, l1)
+    for k, t in params.items():
+        p0, p1 = (np.load(tmp_path / f"run{i}" / f"{k}.npy") for i in range(2))
+        assert p0.dtype == np.float32 and p0.shape == tuple(t.shape), k
+        assert np.array_equal(p0, p1), k
 
 
 @pytest.mark.parametrize("V,B,k", [(3417, 64, 20), (20034, 33, 20), (40, 5, 20), (100003, 3, 10)])

@@ -153,7 +153,7 @@ def test_full_size_properties_batch_equivariance_and_normalisation():
 
 def test_trainer_loop_graph_replay_equals_eager_and_learns():
     """Trainer.iteration(train=True): hipGraph replay (incl. several steps per graph launch) and eager launches give the
-    same parameters bit for bit (same Philox stream, deterministic reductions except the atomic scatter -> allow 1e-6), the
+    same parameters (same Philox stream, deterministic reductions; the tolerance below dates from the float-atomic scatter), the
     short last batch goes through its own plan, and the loss goes down."""
     from bsarec_amd import BSARecModel, data as D
     from bsarec_amd.trainer import Trainer
@@ -173,8 +173,8 @@ def test_trainer_loop_graph_replay_equals_eager_and_learns():
             assert any(k[0] == "indexed_multi" for k in tr._graphs if isinstance(k, tuple)), "multi-step graph not exercised"
         res[mode] = (losses, {k: v.detach().cpu().numpy().copy() for k, v in model.state_dict().items()})
         assert losses[-1] < losses[0]
-    # the embedding scatter uses float atomics (arrival order varies run to run, last-bit differences in dE), and Adam
-    # turns a sign flip of a ~0 gradient into a +-lr step: compare up to a tiny fraction of such elements
+    # (tolerance from when the embedding scatter used float atomics -- last-bit differences in dE, which Adam turns into a
+    #  +-lr step where the gradient is ~0 -- kept: compare up to a tiny fraction of such elements)
     np.testing.assert_allclose(res["graph"][0], res["eager"][0], atol=2e-4)
     for k in res["graph"][1]:
         bad = np.abs(res["graph"][1][k] - res["eager"][1][k]) > 2e-5

@@ -360,3 +360,38 @@ def test_code_object_has_no_packed_fp32_vector_instructions(tmp_path):
     packed = re.findall(r"^\s*(v_pk_(?:fma|mul|add)_f32)\b", dis, re.M)
     assert not packed, f"{len(packed)} packed fp32 instructions in the code object (build flags lost?)"
     assert "v_mfma_f32_32x32x16_bf16" in dis and "v_mfma_f32_32x32x2_f32" in dis      # (it is the right code object)
+
+
+def test_bench_dump_outputs_stays_under_its_limit_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: arrays are written whole while the set fits; past the limit each array keeps its share of the
+    elements, the same elements on every call (two builds of the project are compared file for file); float64 stays float64."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"loss": torch.tensor([1.5]), "big": torch.randn(300, 64, generator=g), "small": torch.randn(7, generator=g),
+              "wide": torch.randn(5000, generator=g, dtype=torch.float64)}
+    whole = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert whole["sampled"] == [] and whole["arrays"] == 4
+    for k, t in arrays.items():
+        v = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert v.dtype == (np.float64 if k == "wide" else np.float32) and v.shape == tuple(t.shape)
+        assert np.array_equal(v, t.numpy())
+    limit = 48 << 10
+    runs = [bench.dump_outputs(str(tmp_path / f"cut{i}"), arrays, limit=limit) for i in range(2)]
+    assert runs[0]["sampled"] == ["big", "wide"] and runs[0]["bytes"] <= limit
+    assert sum(os.path.getsize(tmp_path / "cut0" / f) for f in os.listdir(tmp_path / "cut0")) <= limit
+    for k, t in arrays.items():
+        a, b = (np.load(tmp_path / f"cut{i}" / f"{k}.npy") for i in range(2))
+        assert np.array_equal(a, b)
+        flat = t.reshape(-1).numpy()
+        assert np.isin(a, flat).all()                         # elements of the array, not of another one
+        if k in ("loss", "small"):
+            assert np.array_equal(a.reshape(-1), flat)
+        else:
+            assert 0 < a.size < flat.size
+
+
+def test_bench_rejects_zero_steps():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
