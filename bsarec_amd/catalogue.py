@@ -256,19 +256,26 @@ class ShardedCatalogue:
             ok = (seen_all.view(Bg, S) >= 0) & (loc >= 0) & (loc < self.Vs)
             rows = torch.arange(Bg, device=self.device).view(Bg, 1).expand(Bg, S)
             scores[rows[ok], loc[ok]] = 0.0
-        kk = min(k, max(self.Vs, 1))
-        cand_v = torch.full((Bg, k), -float("inf"), device=self.device)
+        if not 1 <= k <= min(L.TOPK_MAX, self.V):
+            raise ValueError(f"topk: k = {k} outside 1 .. min(BSAREC_TOPK_MAX = {L.TOPK_MAX}, items = {self.V})")
+        # rank r contributes its min(k, Vs_r) best; the gathered blocks are padded to k, and the merge reads only the real
+        # candidates, in rank order: equal scores then stand in global id order (shards are contiguous id ranges and each
+        # block is in ascending id order among its ties), so the merge's "smaller column first" is the full table's order
+        n_r = [min(k, max(0, min(self.rows_per, self.V - r * self.rows_per))) for r in range(W)]
+        kk = n_r[self.rank]
+        cand_v = torch.zeros(Bg, k, device=self.device)
         cand_i = torch.zeros(Bg, k, dtype=torch.int64, device=self.device)
-        if self.Vs:
+        if kk:
             v, i = self._topk_rows(scores, self.logits.stride(0), kk)
             cand_v[:, :kk], cand_i[:, :kk] = v, i + self.lo
         all_v = torch.empty(W, Bg, k, device=self.device)
         all_i = torch.empty(W, Bg, k, dtype=torch.int64, device=self.device)
         dist.all_gather(list(all_v.unbind(0)), cand_v, group=g)
         dist.all_gather(list(all_i.unbind(0)), cand_i, group=g)
-        mv = all_v.permute(1, 0, 2).reshape(Bg, W * k)
-        mi = all_i.permute(1, 0, 2).reshape(Bg, W * k)
-        top_v, sel = self._topk_rows(mv.contiguous(), W * k, k)
+        real = torch.cat([torch.arange(r * k, r * k + n, device=self.device) for r, n in enumerate(n_r) if n])
+        mv = all_v.permute(1, 0, 2).reshape(Bg, W * k)[:, real].contiguous()
+        mi = all_i.permute(1, 0, 2).reshape(Bg, W * k)[:, real]
+        top_v, sel = self._topk_rows(mv, mv.shape[1], k)
         top_i = torch.gather(mi, 1, sel)
         r0 = self.rank * B
         return top_v[r0:r0 + B].clone(), top_i[r0:r0 + B].clone()
@@ -284,17 +291,20 @@ class ShardedCatalogue:
         return val, idx
 
     @torch.no_grad()
-    def full_sort_scores(self, batches, epoch: int = 0, k: int = 20):
+    def full_sort_scores(self, batches, epoch: int = 0, k: int = 20, extra_ks=()):
         """The reference's evaluation bookkeeping (src/trainers.py:118-158 + get_full_sort_score, :70-83) over the SHARDED
         table: ``batches`` yields this rank's (input_ids [B, L], answers [B], seen [B, S] or None) per step (every rank the
-        same number of steps); the top-20 of each sequence comes from :meth:`topk`, hits and DCG sums are all-reduced, so
-        every rank returns the metrics of the GLOBAL evaluation set: ([HR@5, NDCG@5, HR@10, NDCG@10, HR@20, NDCG@20], str)."""
+        same number of steps); the top-max(k, *extra_ks) of each sequence comes from :meth:`topk`, hits and DCG sums are
+        all-reduced, so every rank returns the metrics of the GLOBAL evaluation set: ([HR@5, NDCG@5, HR@10, NDCG@10, HR@20,
+        NDCG@20] + [HR@e, NDCG@e for e in extra_ks], str)."""
         import torch.distributed as dist
         from .trainer import ndcg_at_k, recall_at_k
-        ks = (5, 10, 20)
+        extra = tuple(extra_ks or ())
+        ks = (5, 10, 20) + extra
+        depth = max((k,) + extra)
         sums = torch.zeros(2 * len(ks) + 1, dtype=torch.float64, device=self.device)
         for ids, answers, seen in batches:
-            _, top_i = self.topk(ids, k=k, seen=seen)
+            _, top_i = self.topk(ids, k=depth, seen=seen)
             hit = top_i == answers.to(device=self.device, dtype=torch.int64).view(-1, 1)
             n = hit.shape[0]
             for j, kk in enumerate(ks):
@@ -303,9 +313,9 @@ class ShardedCatalogue:
             sums[-1] += n
         dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.group)
         vals = (sums[:-1] / sums[-1].clamp(min=1)).tolist()
-        post_fix = {"Epoch": epoch, "HR@5": '{:.4f}'.format(vals[0]), "NDCG@5": '{:.4f}'.format(vals[1]),
-                    "HR@10": '{:.4f}'.format(vals[2]), "NDCG@10": '{:.4f}'.format(vals[3]),
-                    "HR@20": '{:.4f}'.format(vals[4]), "NDCG@20": '{:.4f}'.format(vals[5])}
+        post_fix = {"Epoch": epoch}
+        for j, kk in enumerate(ks):
+            post_fix[f"HR@{kk}"], post_fix[f"NDCG@{kk}"] = '{:.4f}'.format(vals[2 * j]), '{:.4f}'.format(vals[2 * j + 1])
         return vals, str(post_fix)
 
     def close(self):

@@ -1521,7 +1521,8 @@ extern "C" int bsarec_mask_seen(float* scores, long ld, int B, const int64_t* us
 
 extern "C" int bsarec_topk_seen(float* scores, long ld, int B, int V, const int64_t* users, const int64_t* indptr,
                                 const int64_t* indices, int k, int64_t* out_idx, float* out_val, void* stream) {
-    if (!scores || !out_idx || B < 1 || V < 1 || ld < V || k < 1 || k > TOPK_MAX || k > V) return -10;
+    static_assert(BSAREC_TOPK_MAX == TOPK_MAX && ROW_THREADS == 256, "topk_seen_kernel: one thread per digit bin");
+    if (!scores || !out_idx || B < 1 || V < 1 || ld < V || k < 1 || k > BSAREC_TOPK_MAX || k > V) return -10;
     if (indptr && (!users || !indices)) return -10;
     hipLaunchKernelGGL(topk_seen_kernel, dim3(B), dim3(ROW_THREADS), 0, (hipStream_t)stream, scores, ld, V, users, indptr, indices, k,
                        out_idx, out_val);

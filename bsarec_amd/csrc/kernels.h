@@ -1013,57 +1013,120 @@ grad_join_kernel(float* __restrict__ y, const float* __restrict__ x, long n4, in
     }
 }
 
-// Top-k of every score row with the seen items zeroed first: the body of the reference's evaluation loop for one batch
-// (src/trainers.py:134-149: rating_pred[train_matrix[user] > 0] = 0, np.argpartition(..., -20), argsort of the 20) in ONE
-// launch, one workgroup per user.  (1) the CSR row of the user is written as zeros into the score row (as the reference
-// does -- the caller may still read the masked scores); (2) every thread keeps the best k of its strided share of the row
-// as a sorted list in LDS (one compare rejects almost every candidate); (3) k rounds of a workgroup arg-max over the 256
-// list heads produce the result in descending order.  Ties (exact equal scores, e.g. the zeros of seen items when fewer
-// than k scores are positive) go to the smaller item id; the reference's argpartition leaves their order unspecified and
-// they cannot change HR / NDCG (the answer is never a seen item).  k <= TOPK_MAX (48 KB of list storage in LDS).
-#define TOPK_MAX 24
-__device__ __forceinline__ bool topk_better(float v, long i, float w, long j) { return v > w || (v == w && i < j); }
+// Order of the top-k (bsarec_topk_seen, include/bsarec_hip.h): a TOTAL order on (score, column) -- score descending with
+// every NaN equal to each other and above +inf, -0 equal to +0; among equal scores the smaller column first.  topk_key maps
+// a score to a 32-bit key whose unsigned order is that score order (canonical NaN / +0 first, then the usual sign flip); a
+// real score's key is >= topk_key(-inf) = 0x007fffff, so key 0 sorts below every score.
+__device__ __forceinline__ unsigned topk_key(float v) {
+    unsigned u = __float_as_uint(v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) u = 0x7fc00000u;          // any NaN -> one quiet NaN (key 0xffc00000 > +inf's)
+    if (u == 0x80000000u) u = 0u;                                   // -0 -> +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// Seen-item masking of bsarec_topk_seen: the CSR row of the user is written as zeros into the score row (as the reference does
+// -- the caller may still read the masked scores).  Ends with a barrier: the scan that follows reads the zeros.
+__device__ __forceinline__ void topk_mask_seen(float* row, int V, const int64_t* users, const int64_t* indptr, const int64_t* indices) {
+    if (!indptr) return;
+    const long u = users[blockIdx.x];
+    const long j0 = indptr[u], j1 = indptr[u + 1];
+    for (long j = j0 + threadIdx.x; j < j1; j += ROW_THREADS) { const long it = indices[j]; if (it >= 0 && it < V) row[it] = 0.f; }
+    __syncthreads();
+}
+
+// Top-k of every score row with the seen items zeroed first, 1 <= k <= TOPK_MAX: the body of the reference's evaluation loop
+// for one batch (src/trainers.py:134-149: rating_pred[train_matrix[user] > 0] = 0, np.argpartition(..., -20), argsort of the
+// 20) in ONE launch, one workgroup per user.  (1) topk_mask_seen; (2) radix select of the k-th largest key, 8-bit digits from
+// the most significant one: each pass histograms the digit of the keys that match the prefix chosen so far (per-wave LDS
+// histograms), a workgroup scan over the 256 bins (descending digit) picks the bin that holds the k-th key; it stops early
+// once that bin is taken whole.  The result is a (prefix, mask) threshold: `rem` keys with key & mask == prefix are still
+// needed, k - rem keys lie above it.  (3) one ORDERED compaction pass over the row in 256-column chunks: keys above the
+// threshold take slots [0, k - rem) through an LDS counter; keys on the threshold are ranked by column (ballot + workgroup
+// prefix of the wave counts) and the first rem of them fill slots [k - rem, k) -- exact ties at the k-th place (e.g.
+// thousands of seen-item zeros) go to the smaller columns.  (4) bitonic sort (descending) of the k composites
+// key << 32 | ~column in LDS, padded with 0 (below every real key) to a power of two.  Every pass re-reads the row from
+// global memory (L2-resident at these row lengths); LDS: 4 KB of histograms + 8 KB of candidates.
+#define TOPK_MAX 1024
 __global__ void __launch_bounds__(ROW_THREADS)
 topk_seen_kernel(float* __restrict__ scores, long ld, int V, const int64_t* __restrict__ users, const int64_t* __restrict__ indptr,
                  const int64_t* __restrict__ indices, int k, int64_t* __restrict__ out_idx, float* __restrict__ out_val) {
-    __shared__ float lv[TOPK_MAX][ROW_THREADS];          // [rank][thread]: conflict-free for "every thread touches its rank r"
-    __shared__ int li[TOPK_MAX][ROW_THREADS];
-    __shared__ float rv[ROW_THREADS / 64];
-    __shared__ int ri[ROW_THREADS / 64], rt[ROW_THREADS / 64];
-    const int tid = threadIdx.x;
+    constexpr int NW = ROW_THREADS / 64;
+    __shared__ unsigned hist[NW][256];
+    __shared__ unsigned long long cand[TOPK_MAX];
+    __shared__ unsigned wscan[NW], wcnt[2][NW], sel[3], ngt;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float* row = scores + (long)blockIdx.x * ld;
-    if (indptr) {
-        const long u = users[blockIdx.x];
-        const long j0 = indptr[u], j1 = indptr[u + 1];
-        for (long j = j0 + tid; j < j1; j += ROW_THREADS) { const long it = indices[j]; if (it >= 0 && it < V) row[it] = 0.f; }
-        __syncthreads();                                 // (drains the stores: the scan below reads the zeros)
-    }
-    for (int r = 0; r < k; ++r) { lv[r][tid] = -INFINITY; li[r][tid] = 0x7fffffff; }
-    float vmin = -INFINITY; int imin = 0x7fffffff;       // this thread's current k-th best
-    for (int j = tid; j < V; j += ROW_THREADS) {
-        const float v = row[j];
-        if (!topk_better(v, j, vmin, imin)) continue;
-        int r = k - 1;                                   // insertion into the sorted list (descending)
-        while (r > 0 && topk_better(v, j, lv[r - 1][tid], li[r - 1][tid])) { lv[r][tid] = lv[r - 1][tid]; li[r][tid] = li[r - 1][tid]; --r; }
-        lv[r][tid] = v; li[r][tid] = j;
-        vmin = lv[k - 1][tid]; imin = li[k - 1][tid];
-    }
-    int head = 0;                                        // next unused rank of this thread's list
-    for (int r = 0; r < k; ++r) {
-        float v = head < k ? lv[head][tid] : -INFINITY;
-        int i = head < k ? li[head][tid] : 0x7fffffff, t = tid;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {        // wave arg-max (value desc, item id asc)
-            const float v2 = __shfl_xor(v, off, 64); const int i2 = __shfl_xor(i, off, 64), t2 = __shfl_xor(t, off, 64);
-            if (topk_better(v2, i2, v, i)) { v = v2; i = i2; t = t2; }
+    topk_mask_seen(row, V, users, indptr, indices);
+    // ---- (2) radix select
+    unsigned prefix = 0u, mask = 0u;
+    int rem = k;                                         // keys still to take among those matching the prefix
+    if (tid == 0) ngt = 0u;
+    for (int i = tid; i < TOPK_MAX; i += ROW_THREADS) cand[i] = 0ull;   // (the sort's padding; the barriers below order it)
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int i = tid; i < NW * 256; i += ROW_THREADS) (&hist[0][0])[i] = 0u;
+        __syncthreads();
+#pragma unroll 4
+        for (int c = tid; c < V; c += ROW_THREADS) {
+            const unsigned key = topk_key(row[c]);
+            if ((key & mask) == prefix) atomicAdd(&hist[wave][(key >> shift) & 255u], 1u);
         }
-        if ((tid & 63) == 0) { rv[tid >> 6] = v; ri[tid >> 6] = i; rt[tid >> 6] = t; }
         __syncthreads();
-        float bv = rv[0]; int bi = ri[0], bt = rt[0];
+        const int bin = 255 - tid;                       // thread t owns digit 255 - t: the scan runs from the top digit down
+        unsigned cnt = 0u;
 #pragma unroll
-        for (int w = 1; w < ROW_THREADS / 64; ++w) if (topk_better(rv[w], ri[w], bv, bi)) { bv = rv[w]; bi = ri[w]; bt = rt[w]; }
-        if (tid == bt) ++head;
-        if (tid == 0) { out_idx[(long)blockIdx.x * k + r] = bi; if (out_val) out_val[(long)blockIdx.x * k + r] = bv; }
+        for (int w = 0; w < NW; ++w) cnt += hist[w][bin];
+        unsigned incl = cnt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const unsigned y = __shfl_up(incl, off, 64); if (lane >= off) incl += y; }
+        if (lane == 63) wscan[wave] = incl;
         __syncthreads();
+        for (int w = 0; w < wave; ++w) incl += wscan[w];
+        const unsigned above = incl - cnt;               // matching keys with a larger digit
+        if (above < (unsigned)rem && incl >= (unsigned)rem) { sel[0] = bin; sel[1] = above; sel[2] = cnt; }   // exactly one thread
+        __syncthreads();
+        rem -= (int)sel[1];
+        prefix |= sel[0] << shift;
+        mask |= 255u << shift;
+        if (sel[2] == (unsigned)rem) break;              // the bin is taken whole: no finer digit needed
+    }
+    // ---- (3) ordered compaction
+    const int n_gt = k - rem;
+    int taken = 0;                                       // threshold keys ranked so far (the same in every thread)
+    for (int c0 = 0, par = 0; c0 < V; c0 += ROW_THREADS, par ^= 1) {
+        const int c = c0 + tid;
+        const unsigned key = c < V ? topk_key(row[c]) : 0u;
+        const unsigned long long comp = ((unsigned long long)key << 32) | (unsigned)~c;
+        if (c < V && (key & mask) > prefix) cand[atomicAdd(&ngt, 1u)] = comp;
+        if (taken < rem) {
+            const bool eq = c < V && (key & mask) == prefix;
+            const unsigned long long bal = __ballot(eq);
+            if (lane == 0) wcnt[par][wave] = (unsigned)__popcll(bal);
+            __syncthreads();                             // (wcnt is double-buffered: the next chunk writes the other half)
+            int before = taken;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) { const int n = (int)wcnt[par][w]; if (w < wave) before += n; taken += n; }
+            if (eq) {
+                const int r = before + __popcll(bal & ((1ull << lane) - 1ull));
+                if (r < rem) cand[n_gt + r] = comp;
+            }
+        }
+    }
+    // ---- (4) bitonic sort of the k survivors, descending
+    int n = 1;
+    while (n < k) n <<= 1;
+    __syncthreads();
+    for (int size = 2; size <= n; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < (n >> 1); i += ROW_THREADS) {
+                const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+                const unsigned long long a = cand[lo], b = cand[hi];
+                if (((lo & size) == 0) == (a < b)) { cand[lo] = b; cand[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int r = tid; r < k; r += ROW_THREADS) {
+        const int c = (int)~(unsigned)cand[r];            // (a slot left empty would read -1: never a load out of the row)
+        out_idx[(long)blockIdx.x * k + r] = c;
+        if (out_val) out_val[(long)blockIdx.x * k + r] = c >= 0 && c < V ? row[c] : __builtin_nanf("");
     }
 }

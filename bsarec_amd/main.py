@@ -26,6 +26,24 @@ from .model import MODEL_DICT
 from .trainer import Trainer
 
 
+def cutoff_list(text: str) -> tuple:
+    """--extra_ks: comma list of evaluation cutoffs in 1 .. BSAREC_TOPK_MAX (duplicates dropped, order kept)."""
+    from ._lib import TOPK_MAX
+    out = []
+    for tok in (t.strip() for t in text.split(",")):
+        if not tok:
+            continue
+        try:
+            k = int(tok)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not an integer cutoff: {tok!r}") from None
+        if not 1 <= k <= TOPK_MAX:
+            raise argparse.ArgumentTypeError(f"cutoff {k} outside 1..{TOPK_MAX}")
+        if k not in out:
+            out.append(k)
+    return tuple(out)
+
+
 def parse_args(argv=None):
     """The reference's flag names and defaults (src/utils.py:53-96); BSARec-specific --c / --alpha included."""
     p = argparse.ArgumentParser()
@@ -58,6 +76,8 @@ def parse_args(argv=None):
     p.add_argument("--initializer_range", default=0.02, type=float)
     p.add_argument("--c", default=3, type=int)
     p.add_argument("--alpha", default=0.9, type=float)
+    # not a reference flag: HR@k / NDCG@k at these cutoffs too, logged after the reference's six metrics
+    p.add_argument("--extra_ks", default=(), type=cutoff_list, help="extra evaluation cutoffs, e.g. 50,100 (<= 1024)")
     # DuoRec's flags (src/utils.py:106-111)
     p.add_argument("--tau", default=1.0, type=float)
     p.add_argument("--lmd", default=0.1, type=float)
@@ -65,6 +85,14 @@ def parse_args(argv=None):
     p.add_argument("--ssl", default="us_x", type=str)
     p.add_argument("--sim", default="dot", type=str)
     return p.parse_args(argv)
+
+
+NDCG20 = 5        # position of NDCG@20 in the evaluation scores; extra cutoffs come after the reference's six values
+
+
+def monitored_score(scores) -> np.ndarray:
+    """What early stopping monitors: NDCG@20 (src/main.py:57), whatever extra cutoffs follow it."""
+    return np.array(scores[NDCG20:NDCG20 + 1])
 
 
 class EarlyStopping:
@@ -124,7 +152,7 @@ def run(args, user_seq, logger=None, checkpoint_path=None):
     for epoch in range(args.epochs):
         trainer.train(epoch)
         scores, _ = trainer.valid(epoch)
-        stopper(np.array(scores[-1:]), trainer.model)               # monitors NDCG@20 (src/main.py:57)
+        stopper(monitored_score(scores), trainer.model)             # monitors NDCG@20 (src/main.py:57)
         epochs = epoch + 1
         if stopper.early_stop:
             logger.info("Early stopping")

@@ -26,7 +26,7 @@ class _NullLogger:
 
 
 def recall_at_k(hit: torch.Tensor, k: int) -> float:
-    """src/metrics.py:3-13 for single-target lists: hit is bool[n, 20]."""
+    """src/metrics.py:3-13 for single-target lists: hit is bool[n, K], K >= k."""
     return float(hit[:, :k].any(1).double().mean().item())
 
 
@@ -34,6 +34,11 @@ def ndcg_at_k(hit: torch.Tensor, k: int) -> float:
     """src/metrics.py:15-31: one relevant item -> idcg = 1, dcg = 1/log2(rank + 2)."""
     w = 1.0 / torch.log2(torch.arange(k, device=hit.device, dtype=torch.float64) + 2.0)
     return float((hit[:, :k].double() * w).sum(1).mean().item())
+
+
+def extra_cutoffs(args) -> tuple:
+    """Evaluation cutoffs beyond the reference's 5 / 10 / 20 (``--extra_ks``; none by default)."""
+    return tuple(getattr(args, "extra_ks", None) or ())
 
 
 def graph_sizes(k: int):
@@ -197,10 +202,14 @@ class Trainer:
         """src/trainers.py:62-68 (kept for API parity; evaluation uses model.full_logits)."""
         return torch.matmul(seq_out, self.model.item_embeddings.weight.transpose(0, 1))
 
-    def get_full_sort_score(self, epoch, answers, pred_list):
-        """src/trainers.py:70-83: answers int[n], pred_list int[n, 20] (device tensors or numpy)."""
+    def get_full_sort_score(self, epoch, answers, pred_list, extra_ks=None):
+        """src/trainers.py:70-83: answers int[n], pred_list int[n, K] (device tensors or numpy), K >= 20.  ``extra_ks``
+        (default: args.extra_ks) appends HR@k, NDCG@k of every extra cutoff after the reference's six values (K >= k)."""
+        extra = extra_cutoffs(self.args) if extra_ks is None else tuple(extra_ks)
         ans = torch.as_tensor(answers, device=self.device).view(-1, 1)
         pred = torch.as_tensor(pred_list, device=self.device)
+        if extra and pred.shape[1] < max(extra):
+            raise ValueError(f"get_full_sort_score: lists of {pred.shape[1]} items, extra cutoffs up to {max(extra)}")
         hit = pred == ans
         recall = [recall_at_k(hit, k) for k in (5, 10, 15, 20)]
         ndcg = [ndcg_at_k(hit, k) for k in (5, 10, 15, 20)]
@@ -210,8 +219,13 @@ class Trainer:
             "HR@10": '{:.4f}'.format(recall[1]), "NDCG@10": '{:.4f}'.format(ndcg[1]),
             "HR@20": '{:.4f}'.format(recall[3]), "NDCG@20": '{:.4f}'.format(ndcg[3]),
         }
+        scores = [recall[0], ndcg[0], recall[1], ndcg[1], recall[3], ndcg[3]]
+        for k in extra:
+            hr, nd = recall_at_k(hit, k), ndcg_at_k(hit, k)
+            post_fix[f"HR@{k}"], post_fix[f"NDCG@{k}"] = '{:.4f}'.format(hr), '{:.4f}'.format(nd)
+            scores += [hr, nd]
         self.logger.info(post_fix)
-        return [recall[0], ndcg[0], recall[1], ndcg[1], recall[3], ndcg[3]], str(post_fix)
+        return scores, str(post_fix)
 
     # ---- one optimisation step --------------------------------------------------------------------
     def _exchange_and_adam(self):
@@ -533,17 +547,19 @@ class Trainer:
         # ---- evaluation (src/trainers.py:118-158), all on the device
         self.model.eval()
         preds, answers_all = [], []
+        depth = max((20,) + extra_cutoffs(self.args))
         for batch in dataloader:
             batch = tuple(t.to(self.device, non_blocking=True) for t in batch)
             user_ids, input_ids, answers, _, _ = batch
-            preds.append(self.topk_after_seen(user_ids, input_ids))
+            preds.append(self.topk_after_seen(user_ids, input_ids, k=depth))
             answers_all.append(answers)
         return self.get_full_sort_score(epoch, torch.cat(answers_all), torch.cat(preds))
 
     def topk_after_seen(self, user_ids, input_ids, k: int = 20, return_scores: bool = False):
         """The body of the reference's eval loop for one batch (src/trainers.py:126-149): full-catalogue scores of the
         last position (HIP), then ONE launch that sets the seen items' scores to 0 -- not -inf -- from the device CSR and
-        takes the k best ids in descending score order (``bsarec_topk_seen``; no host round trip, no torch.topk)."""
+        takes the k best ids in descending score order (``bsarec_topk_seen``; no host round trip, no torch.topk).
+        1 <= k <= BSAREC_TOPK_MAX (1024) and k <= item_size; equal scores go to the smaller id, NaN ranks above +inf."""
         from . import _lib as L
         scores = self.model.full_logits(input_ids).clone()           # a copy: the plan's logits buffer stays intact
         indptr, indices = self._seen_csr()

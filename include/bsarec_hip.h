@@ -31,7 +31,7 @@ extern "C" {
 #endif
 
 #define BSAREC_MAX_LAYERS 16
-#define BSAREC_ABI_VERSION 8
+#define BSAREC_ABI_VERSION 9
 
 /* Hyper-parameters the reference model reads from `args`
  * (src/utils.py:83-96; src/model/bsarec.py:71-88; src/model/_modules.py:79-87). */
@@ -267,9 +267,12 @@ int bsarec_mask_seen(float *scores, long ld, int B, const int64_t *users, const 
                      const int64_t *indices, void *stream);
 
 /* The same masking AND the reference's top-k (src/trainers.py:134-149: argpartition of the 20 best + argsort) in one
- * launch, one workgroup per user: scores[b][seen items] = 0, then out_idx[b][0..k) = item ids of the k largest scores of
- * scores[b][0..V) in descending order (equal scores: smaller id first), out_val (nullable) their scores.  indptr == NULL:
- * no masking.  k <= 24, k <= V <= ld. */
+ * launch, one workgroup per user: scores[b][seen items] = 0 (written back), then out_idx[b][0..k) = the columns of the k
+ * best scores of scores[b][0..V) in descending order, out_val (nullable) their scores exactly as stored.  Columns [V, ld)
+ * are never read.  indptr == NULL: no masking.  1 <= k <= BSAREC_TOPK_MAX, k <= V <= ld.
+ * The order is total: NaN ranks above +inf and all NaNs are equal, -0.0 equals +0.0, and among equal scores the smaller
+ * column comes first -- a stable descending sort with NaN as the largest value; every index is < V. */
+#define BSAREC_TOPK_MAX 1024
 int bsarec_topk_seen(float *scores, long ld, int B, int V, const int64_t *users, const int64_t *indptr,
                      const int64_t *indices, int k, int64_t *out_idx, float *out_val, void *stream);
 
