@@ -5,8 +5,10 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BSAREC_LIB") or os.path.join(HERE, "libbsarec_hip.so")   # BSAREC_LIB: another build of the same ABI
 MAX_LAYERS = 16
-ABI_VERSION = 9
+ABI_VERSION = 10
 TOPK_MAX = 1024                                  # BSAREC_TOPK_MAX: the largest k of bsarec_topk_seen
+NEG_MAX = 1024                                   # BSAREC_NEG_MAX: the most negatives per row of bsarec_sampled_rank
+NEG_MAX_DRAWS = 1 << 20                          # BSAREC_NEG_MAX_DRAWS: draws examined before a row fails
 
 (BUF_LAYER_OUT, BUF_LOGITS, BUF_LOSS, BUF_DSP, BUF_HMIX, BUF_PROBS, BUF_DLAYER_IN, BUF_LOSS_ROWS, BUF_CTX,
  BUF_DLOGITS) = range(10)
@@ -152,6 +154,8 @@ EXPORTS = {
     "bsarec_mask_seen": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_topk_seen": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "bsarec_sampled_rank": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 +
+                            [C.c_int, C.c_uint64, C.c_uint32] + [C.c_void_p] * 4),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

@@ -9,6 +9,7 @@
 #include "fused_chain.h"
 #include "comm.h"
 #include "catalogue_shard.h"
+#include "sampled_rank.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -1526,6 +1527,19 @@ extern "C" int bsarec_topk_seen(float* scores, long ld, int B, int V, const int6
     if (indptr && (!users || !indices)) return -10;
     hipLaunchKernelGGL(topk_seen_kernel, dim3(B), dim3(ROW_THREADS), 0, (hipStream_t)stream, scores, ld, V, users, indptr, indices, k,
                        out_idx, out_val);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_sampled_rank(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* users,
+                                   const int64_t* answers, const int64_t* indptr, const int64_t* indices, const int64_t* pop_cum,
+                                   int n_neg, uint64_t seed, uint32_t tag, int32_t* rank_out, int64_t* cand_out, float* score_out,
+                                   void* stream) {
+    static_assert(BSAREC_NEG_MAX == NEG_MAX && BSAREC_NEG_MAX_DRAWS == NEG_MAX_DRAWS, "sampled_rank_kernel: the header's limits");
+    if (!h || !item_emb || !users || !answers || !rank_out || (indptr && !indices)) return -10;
+    if (B < 1 || V < 2 || d < 4 || d > 256 || d % 4 != 0 || ldh < d || n_neg < 1 || n_neg > BSAREC_NEG_MAX) return -10;
+    if ((uintptr_t)item_emb % 16 != 0) return -10;               // float4 row loads
+    hipLaunchKernelGGL(sampled_rank_kernel, dim3(B), dim3(ROW_THREADS), 0, (hipStream_t)stream, h, ldh, item_emb, V, d, users, answers,
+                       indptr, indices, pop_cum, n_neg, (uint32_t)seed, (uint32_t)(seed >> 32), tag, rank_out, cand_out, score_out);
     return (int)hipGetLastError();
 }
 

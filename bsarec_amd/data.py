@@ -93,6 +93,17 @@ def seen_csr(user_seqs: List[List[int]], split: str) -> Tuple[np.ndarray, np.nda
     return np.asarray(indptr, dtype=np.int64), (np.concatenate(cols) if cols else np.zeros(0, dtype=np.int64))
 
 
+def item_popularity(user_seqs: List[List[int]], item_size: int) -> np.ndarray:
+    """int64[item_size]: how often each item occurs in the training part s[:-2] of every user's sequence (item 0 gets 0).
+    One table for valid and test, so no held-out answer leaks into the popularity sampler of sampled evaluation."""
+    counts = np.zeros(item_size, dtype=np.int64)
+    parts = [np.asarray(s[:-2], dtype=np.int64) for s in user_seqs if len(s) > 2]
+    if parts:
+        counts += np.bincount(np.concatenate(parts), minlength=item_size)[:item_size]
+    counts[0] = 0
+    return counts
+
+
 class DeviceBatches:
     """Device-resident replacement of the reference's train DataLoader (RandomSampler, batch_size,
     no drop_last; src/dataset.py:209-211).  Iterating yields the reference's 5-tuples

@@ -44,6 +44,29 @@ def cutoff_list(text: str) -> tuple:
     return tuple(out)
 
 
+def negatives_count(text: str) -> int:
+    """--eval_negatives: 0 (full-catalogue ranking) .. BSAREC_NEG_MAX."""
+    from ._lib import NEG_MAX
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}") from None
+    if not 0 <= n <= NEG_MAX:
+        raise argparse.ArgumentTypeError(f"{n} outside 0..{NEG_MAX}")
+    return n
+
+
+def seed_value(text: str) -> int:
+    """--eval_seed: an unsigned 64-bit integer."""
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}") from None
+    if not 0 <= n < 1 << 64:
+        raise argparse.ArgumentTypeError(f"{n} outside 0..2^64-1")
+    return n
+
+
 def parse_args(argv=None):
     """The reference's flag names and defaults (src/utils.py:53-96); BSARec-specific --c / --alpha included."""
     p = argparse.ArgumentParser()
@@ -78,13 +101,25 @@ def parse_args(argv=None):
     p.add_argument("--alpha", default=0.9, type=float)
     # not a reference flag: HR@k / NDCG@k at these cutoffs too, logged after the reference's six metrics
     p.add_argument("--extra_ks", default=(), type=cutoff_list, help="extra evaluation cutoffs, e.g. 50,100 (<= 1024)")
+    # not reference flags: sampled-candidate evaluation (each answer against N sampled unseen items) instead of the full
+    # ranking.  Absent unless given (argparse.SUPPRESS), so that a run without them logs the same arguments as before;
+    # readers use trainer.sampled_protocol(args)
+    p.add_argument("--eval_negatives", default=argparse.SUPPRESS, type=negatives_count,
+                   help="rank each answer against this many sampled unseen items (0..1024; 0 = full ranking, the default)")
+    p.add_argument("--eval_sampler", default=argparse.SUPPRESS, choices=("uniform", "popularity"),
+                   help="how the negatives are drawn: uniform over the catalogue (default) or by training-set popularity")
+    p.add_argument("--eval_seed", default=argparse.SUPPRESS, type=seed_value, help="seed of the negative draws (default: --seed)")
     # DuoRec's flags (src/utils.py:106-111)
     p.add_argument("--tau", default=1.0, type=float)
     p.add_argument("--lmd", default=0.1, type=float)
     p.add_argument("--lmd_sem", default=0.1, type=float)
     p.add_argument("--ssl", default="us_x", type=str)
     p.add_argument("--sim", default="dot", type=str)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    n = getattr(args, "eval_negatives", 0)
+    if n > 0 and args.extra_ks and max(args.extra_ks) > n + 1:
+        p.error(f"--extra_ks: cutoff {max(args.extra_ks)} exceeds the {n + 1} candidates of --eval_negatives {n}")
+    return args
 
 
 NDCG20 = 5        # position of NDCG@20 in the evaluation scores; extra cutoffs come after the reference's six values
@@ -132,6 +167,8 @@ def run(args, user_seq, logger=None, checkpoint_path=None):
     for split in ("valid", "test"):
         indptr, cols = D.seen_csr(user_seq, split)
         setattr(args, f"{split}_rating_matrix", sp.csr_matrix((np.ones(len(cols)), cols, indptr), shape=(n_users, args.item_size)))
+    if getattr(args, "eval_negatives", 0) > 0 and getattr(args, "eval_sampler", "uniform") == "popularity":
+        args.item_popularity = D.item_popularity(user_seq, args.item_size)    # training part only: one table for both splits
     model = MODEL_DICT[args.model_type.lower()](args=args)
     if getattr(model, "needs_negatives", False):
         train_dl.enable_negatives(user_seq, args.item_size)

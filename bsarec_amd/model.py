@@ -502,6 +502,14 @@ class BSARecModel(nn.Module):
         Vp = (V + 3) // 4 * 4
         return plan.view(L.BUF_LOGITS, 0, (input_ids.shape[0], Vp))[:, :V]
 
+    def last_hidden(self, input_ids) -> torch.Tensor:
+        """Last-position hidden state of the eval forward (``bsarec_forward_last``), [B, d]: a view of row L-1 of the last
+        layer's output in the plan's workspace, valid until the next forward at this batch size.  The dropout step is not
+        advanced.  What sampled-candidate evaluation scores the candidates against (Trainer.sampled_ranks)."""
+        plan = self._run_forward(input_ids, train=False, new_step=False, last_only=True)
+        B, Lq, d = input_ids.shape[0], self.args.max_seq_length, self.args.hidden_size
+        return plan.view(L.BUF_LAYER_OUT, self.args.num_hidden_layers, (B, Lq, d))[:, Lq - 1, :]
+
     # ---- fused training step (used by bsarec_amd.trainer.Trainer) ------------------------------
     def configure_adam(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         self._require_gpu()

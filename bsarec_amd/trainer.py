@@ -41,6 +41,22 @@ def extra_cutoffs(args) -> tuple:
     return tuple(getattr(args, "extra_ks", None) or ())
 
 
+def sampled_protocol(args):
+    """Sampled-candidate evaluation settings (``--eval_negatives / --eval_sampler / --eval_seed``): (negatives per row,
+    sampler, seed); 0 negatives = the reference's full-catalogue ranking (the default)."""
+    n = int(getattr(args, "eval_negatives", 0) or 0)
+    sampler = getattr(args, "eval_sampler", None) or "uniform"
+    seed = getattr(args, "eval_seed", None)
+    return n, sampler, int(getattr(args, "seed", 0) if seed is None else seed)
+
+
+def sampled_metrics(ranks, k: int):
+    """HR@k and NDCG@k of sampled evaluation from the answers' ranks among their candidates (0 = first)."""
+    r = np.asarray(ranks, dtype=np.int64)
+    hit = r < k
+    return float(hit.mean()), float(np.where(hit, 1.0 / np.log2(r.astype(np.float64) + 2.0), 0.0).mean())
+
+
 def graph_sizes(k: int):
     """Group sizes a ``steps_per_graph = k`` trainer replays as one graph launch: k and the powers of two below it."""
     out, p = [], 1
@@ -168,10 +184,12 @@ class Trainer:
 
     def valid(self, epoch):
         self.args.train_matrix = self.args.valid_rating_matrix
+        self._eval_tag = 1                     # the Philox tag of sampled evaluation's draw stream: 1 valid, 2 test
         return self.iteration(epoch, self.eval_dataloader, train=False)
 
     def test(self, epoch):
         self.args.train_matrix = self.args.test_rating_matrix
+        self._eval_tag = 2
         return self.iteration(epoch, self.test_dataloader, train=False)
 
     def check_exchange(self):
@@ -224,6 +242,27 @@ class Trainer:
             hr, nd = recall_at_k(hit, k), ndcg_at_k(hit, k)
             post_fix[f"HR@{k}"], post_fix[f"NDCG@{k}"] = '{:.4f}'.format(hr), '{:.4f}'.format(nd)
             scores += [hr, nd]
+        self.logger.info(post_fix)
+        return scores, str(post_fix)
+
+    def get_sampled_score(self, epoch, ranks, extra_ks=None):
+        """Metrics of sampled-candidate evaluation from the answers' ranks (``sampled_ranks``): the reference's six positions
+        (HR / NDCG @ 5, 10, 20), then HR@k, NDCG@k of every extra cutoff, so early stopping reads the same position; the
+        log line gains the key "Protocol" (e.g. "uniform-100").  Extra cutoffs above N + 1 are rejected."""
+        n, sampler, _ = sampled_protocol(self.args)
+        extra = extra_cutoffs(self.args) if extra_ks is None else tuple(extra_ks)
+        if extra and max(extra) > n + 1:
+            raise ValueError(f"get_sampled_score: extra cutoffs up to {max(extra)}, but a row has only {n + 1} candidates")
+        r = torch.as_tensor(ranks).cpu().numpy()
+        if r.size and r.min() < 0:
+            raise ValueError(f"get_sampled_score: {int((r < 0).sum())} rows without {n} sampled negatives")
+        post_fix = {"Epoch": epoch}
+        scores = []
+        for k in (5, 10, 20) + extra:
+            hr, nd = sampled_metrics(r, k)
+            post_fix[f"HR@{k}"], post_fix[f"NDCG@{k}"] = '{:.4f}'.format(hr), '{:.4f}'.format(nd)
+            scores += [hr, nd]
+        post_fix["Protocol"] = f"{sampler}-{n}"
         self.logger.info(post_fix)
         return scores, str(post_fix)
 
@@ -546,6 +585,13 @@ class Trainer:
             return post_fix
         # ---- evaluation (src/trainers.py:118-158), all on the device
         self.model.eval()
+        if sampled_protocol(self.args)[0] > 0:          # opt-in: rank each answer against sampled negatives instead
+            ranks = []
+            for batch in dataloader:
+                batch = tuple(t.to(self.device, non_blocking=True) for t in batch)
+                user_ids, input_ids, answers, _, _ = batch
+                ranks.append(self.sampled_ranks(user_ids, input_ids, answers, tag=getattr(self, "_eval_tag", 1)))
+            return self.get_sampled_score(epoch, torch.cat(ranks))
         preds, answers_all = [], []
         depth = max((20,) + extra_cutoffs(self.args))
         for batch in dataloader:
@@ -569,6 +615,93 @@ class Trainer:
                                           indptr.data_ptr(), indices.data_ptr(), k, pred.data_ptr(), None,
                                           torch.cuda.current_stream(self.device).cuda_stream), "bsarec_topk_seen")
         return (pred, scores) if return_scores else pred
+
+    def sampled_ranks(self, user_ids, input_ids, answers, return_candidates: bool = False, tag: int = 1):
+        """Sampled-candidate evaluation of one batch: each answer against args.eval_negatives = N items the user has not seen,
+        drawn uniformly or by training popularity (args.eval_sampler; args.item_popularity, see data.item_popularity) from
+        the Philox stream of (user, tag, args.eval_seed) -- ``bsarec_sampled_rank``, one launch after the eval forward.
+        Returns the int32 ranks [B] (ties count against the model); with ``return_candidates`` also the candidates
+        [B, N + 1] (answer first) and their scores.  Raises ValueError when a row has fewer than N eligible items."""
+        from . import _lib as L
+        n, sampler, seed = sampled_protocol(self.args)
+        if not 1 <= n <= L.NEG_MAX:
+            raise ValueError(f"sampled_ranks: eval_negatives = {n}, expected 1..{L.NEG_MAX}")
+        V = int(self.args.item_size)
+        tables = self._sampling_tables(sampler, V)
+        users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
+        ans = answers.to(device=self.device, dtype=torch.int64).contiguous()
+        self._check_pool(tables, users.cpu().numpy(), ans.cpu().numpy(), n, V)
+        h = self.model.last_hidden(input_ids)
+        if h.dtype != torch.float32 or h.stride(1) != 1:
+            h = h.float().contiguous()
+        E = self.model.item_embeddings.weight.detach()
+        if not E.is_contiguous() or E.data_ptr() % 16:
+            E = E.contiguous().clone()
+        B, d = h.shape
+        indptr, indices = self._seen_csr()
+        rank = torch.empty(B, dtype=torch.int32, device=self.device)
+        cand = torch.empty(B, n + 1, dtype=torch.int64, device=self.device) if return_candidates else None
+        score = torch.empty(B, n + 1, dtype=torch.float32, device=self.device) if return_candidates else None
+        cum = tables["cum"]
+        L.check(L.load().bsarec_sampled_rank(h.data_ptr(), h.stride(0), E.data_ptr(), B, V, d, users.data_ptr(), ans.data_ptr(),
+                                             indptr.data_ptr(), indices.data_ptr(), cum.data_ptr() if cum is not None else None,
+                                             n, seed & 0xFFFFFFFFFFFFFFFF, int(tag), rank.data_ptr(),
+                                             cand.data_ptr() if cand is not None else None,
+                                             score.data_ptr() if score is not None else None,
+                                             torch.cuda.current_stream(self.device).cuda_stream), "bsarec_sampled_rank")
+        bad = torch.nonzero(rank < 0).view(-1)
+        if bad.numel():
+            raise ValueError(f"sampled_ranks: no {n} negatives within {L.NEG_MAX_DRAWS} draws for users "
+                             f"{users[bad[:5]].tolist()}")
+        return (rank, cand, score) if return_candidates else rank
+
+    def _sampling_tables(self, sampler: str, V: int):
+        """Host tables of the eligibility check and the device cumulative popularity, cached per (seen matrix, sampler):
+        keys = u * V + item over the seen CSR (sorted), seen_w[u] = the drawable items in row u, pool = all drawable items."""
+        mat = self.args.train_matrix
+        pop = getattr(self.args, "item_popularity", None) if sampler == "popularity" else None
+        key = (id(mat), sampler, id(pop), V)
+        if getattr(self, "_neg_key", None) != key:
+            if sampler == "uniform":
+                w = np.ones(V, dtype=np.int64)
+            elif sampler == "popularity":
+                if pop is None:
+                    raise ValueError("sampled_ranks: the popularity sampler needs args.item_popularity (data.item_popularity)")
+                pop = np.asarray(pop, dtype=np.int64)
+                if pop.shape != (V,) or pop.min() < 0:
+                    raise ValueError(f"sampled_ranks: item_popularity must be {V} counts >= 0")
+                w = (pop > 0).astype(np.int64)
+            else:
+                raise ValueError(f"sampled_ranks: unknown sampler {sampler!r}")
+            w[0] = 0
+            csr = mat.tocsr()
+            csr.sum_duplicates()
+            ip, ix = csr.indptr.astype(np.int64), csr.indices.astype(np.int64)
+            rows = np.repeat(np.arange(len(ip) - 1, dtype=np.int64), np.diff(ip))
+            inr = (ix >= 0) & (ix < V)
+            seen_w = np.bincount(rows[inr], weights=w[ix[inr]], minlength=len(ip) - 1).astype(np.int64)
+            cum = None
+            if sampler == "popularity":
+                c = np.cumsum(np.where(np.arange(V) == 0, 0, pop))
+                cum = torch.as_tensor(c.astype(np.int64), device=self.device)
+            self._neg_tables = {"keys": rows * V + ix, "seen_w": seen_w, "w": w, "pool": int(w.sum()), "cum": cum}
+            self._neg_key = key
+        return self._neg_tables
+
+    @staticmethod
+    def _check_pool(t, users, answers, n: int, V: int):
+        """Every row must have >= n drawable items that are neither seen nor its answer (the kernel's -1 is only a backstop)."""
+        if ((answers < 1) | (answers >= V)).any():
+            i = int(np.nonzero((answers < 1) | (answers >= V))[0][0])
+            raise ValueError(f"sampled_ranks: answer {int(answers[i])} of user {int(users[i])} outside [1, {V})")
+        q = users * V + answers
+        pos = np.minimum(np.searchsorted(t["keys"], q), max(len(t["keys"]) - 1, 0))
+        a_seen = (t["keys"][pos] == q) if len(t["keys"]) else np.zeros(len(q), dtype=bool)
+        elig = t["pool"] - t["seen_w"][users] - np.where(a_seen, 0, t["w"][answers])
+        short = np.nonzero(elig < n)[0]
+        if short.size:
+            raise ValueError(f"sampled_ranks: {n} negatives requested, but users {users[short[:5]].tolist()} have only "
+                             f"{elig[short[:5]].tolist()} eligible items")
 
     def _seen_csr(self):
         """args.train_matrix (scipy CSR, as the reference builds it in src/dataset.py:126-168) on the device --

@@ -31,7 +31,7 @@ extern "C" {
 #endif
 
 #define BSAREC_MAX_LAYERS 16
-#define BSAREC_ABI_VERSION 9
+#define BSAREC_ABI_VERSION 10
 
 /* Hyper-parameters the reference model reads from `args`
  * (src/utils.py:83-96; src/model/bsarec.py:71-88; src/model/_modules.py:79-87). */
@@ -275,6 +275,33 @@ int bsarec_mask_seen(float *scores, long ld, int B, const int64_t *users, const 
 #define BSAREC_TOPK_MAX 1024
 int bsarec_topk_seen(float *scores, long ld, int B, int V, const int64_t *users, const int64_t *indptr,
                      const int64_t *indices, int k, int64_t *out_idx, float *out_val, void *stream);
+
+/* Sampled-candidate evaluation: the protocol of the SASRec / BERT4Rec papers, opt-in beside the full ranking above.  Row b
+ * ranks its answer a = answers[b] against n_neg items drawn for user u = users[b] that u has not seen.  One launch, one
+ * workgroup per row; enqueued on `stream` and capturable.
+ *   Draw stream: Philox4x32-10 call j = 0, 1, ... has counter (j, lo32(u), hi32(u), tag), key (lo32(seed), hi32(seed)) and
+ *   returns words w0..w3.  pop_cum == NULL (uniform): draw 4j + m takes w_m, item = 1 + ((uint64)w_m * (V - 1) >> 32).
+ *   pop_cum != NULL (popularity): int64[V], non-decreasing, pop_cum[0] = 0, T = pop_cum[V - 1] >= 1; draw 2j + m takes
+ *   x = w_2m | (uint64)w_2m+1 << 32, r = the high 64 bits of the 128-bit product x * T, item = the smallest i with
+ *   pop_cum[i] > r (items of count 0 are never drawn).
+ *   Acceptance, in stream order: a draw is accepted iff its item is not in the seen set (CSR row u of indptr / indices,
+ *   sorted ascending; indptr == NULL: nothing is seen), is not a, and was not accepted before.  Sampling stops at n_neg
+ *   accepted; a row that has not got them after BSAREC_NEG_MAX_DRAWS draws has failed.  a may itself be a seen item (a
+ *   repeated item): it is still the positive.
+ *   Candidates: [a, n_1 .. n_n_neg] in acceptance order; they depend on (u, tag, seed) only.
+ *   Scores: s_c = sum_k h[b * ldh + k] * item_emb[c * d + k] in fp32, one code path for the answer and the negatives.
+ *   Rank: the number of negatives whose score is > s_a, == s_a or NaN (ties count against the model); n_neg if s_a is
+ *   NaN; -1 for a failed row or an answer outside [1, V).
+ * rank_out: int32[B].  cand_out / score_out (nullable): [B][n_neg + 1], the candidates and their scores; a failed row has
+ * a in column 0, 0 after its accepted negatives, and NaN scores.  Limits (else < 0 before any HIP call): B >= 1, V >= 2,
+ * 4 <= d <= 256, d % 4 == 0, ldh >= d, 1 <= n_neg <= BSAREC_NEG_MAX, item_emb 16-byte aligned, h / item_emb / users /
+ * answers / rank_out non-null, indices non-null when indptr is given. */
+#define BSAREC_NEG_MAX 1024
+#define BSAREC_NEG_MAX_DRAWS (1 << 20)
+int bsarec_sampled_rank(const float *h, long ldh, const float *item_emb, int B, int V, int d, const int64_t *users,
+                        const int64_t *answers, const int64_t *indptr, const int64_t *indices, const int64_t *pop_cum,
+                        int n_neg, uint64_t seed, uint32_t tag, int32_t *rank_out, int64_t *cand_out, float *score_out,
+                        void *stream);
 
 /* Stand-alone FrequencyLayer (src/model/bsarec.py:90-104) for per-op parity tests:
  * y = LN(Drop(low + beta^2 (x - low)) + x); backward given dy. */
