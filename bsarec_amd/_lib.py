@@ -9,9 +9,11 @@ ABI_VERSION = 10
 TOPK_MAX = 1024                                  # BSAREC_TOPK_MAX: the largest k of bsarec_topk_seen
 NEG_MAX = 1024                                   # BSAREC_NEG_MAX: the most negatives per row of bsarec_sampled_rank
 NEG_MAX_DRAWS = 1 << 20                          # BSAREC_NEG_MAX_DRAWS: draws examined before a row fails
+TRAIN_NEG_MAX = 8192                             # BSAREC_TRAIN_NEG_MAX: the most candidates of the sampled-softmax head
+TRAIN_NEG_SITE = 0x4E454753                      # BSAREC_TRAIN_NEG_SITE: Philox counter word 2 of its draws
 
 (BUF_LAYER_OUT, BUF_LOGITS, BUF_LOSS, BUF_DSP, BUF_HMIX, BUF_PROBS, BUF_DLAYER_IN, BUF_LOSS_ROWS, BUF_CTX,
- BUF_DLOGITS) = range(10)
+ BUF_DLOGITS, BUF_TRAIN_CAND, BUF_TRAIN_CORR, BUF_TRAIN_LOGITS, BUF_TRAIN_DLOGITS) = range(14)
 K_NONE, K_FFN1, K_FFN2, K_QKV, K_LOGITS, K_DU, K_DW1, K_FUSED_FWD, K_FUSED_BWD = range(9)
 
 LAYER_FIELDS = ["sqrt_beta", "filter_ln_w", "filter_ln_b", "query_w", "query_b", "key_w", "key_b", "value_w", "value_b",
@@ -42,7 +44,13 @@ class Config(C.Structure):
                 # per-plan options, 0 = default (include/bsarec_hip.h)
                 ("hidden_act", C.c_int), ("storage", C.c_int), ("no_fused", C.c_int), ("no_prune_top", C.c_int),
                 ("dw_tiled", C.c_int), ("splits", C.c_int), ("top_slabs", C.c_int), ("separate_embed", C.c_int),
-                ("separate_top", C.c_int), ("chain_kernels", C.c_int), ("x3_products", C.c_int)]
+                ("separate_top", C.c_int), ("chain_kernels", C.c_int), ("x3_products", C.c_int),
+                # sampled-softmax training head (0 = full-catalogue CE)
+                ("train_negatives", C.c_int), ("train_sampler", C.c_int), ("train_no_logq", C.c_int)]
+
+
+TRAIN_FIELDS = ("train_negatives", "train_sampler", "train_no_logq")
+TRAIN_SAMPLERS = {"uniform": 0, "popularity": 1}
 
 
 OPTION_FIELDS = ("storage", "no_fused", "no_prune_top", "dw_tiled", "splits", "top_slabs", "separate_embed", "separate_top", "chain_kernels", "x3_products")
@@ -129,6 +137,7 @@ EXPORTS = {
                                      C.POINTER(Tensors), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_shadow_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bsarec_plan_set_dense_grad_hook": (C.c_int, [C.c_void_p, HOOK, C.c_void_p, C.c_void_p]),
+    "bsarec_plan_set_train_sampler": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bsarec_buffer_is_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "bsarec_plan_is_fused": (C.c_int, [C.c_void_p]),
     "bsarec_config_is_fused": (C.c_int, [C.c_void_p]),

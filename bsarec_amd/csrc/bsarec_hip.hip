@@ -10,6 +10,7 @@
 #include "comm.h"
 #include "catalogue_shard.h"
 #include "sampled_rank.h"
+#include "sampled_softmax.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -162,7 +163,8 @@ struct bsarec_plan {
     ReduceJob* jobs_pruned;                    // same table with the top layer's key / value bias jobs fed from partials
     bool prune_ok;                             // the loss path may run the pruned top block (fused shape, >= 2 layers)
     bool pruned;                               // mode of the last forward
-    int loss_kind;                             // head of the last loss call: 0 = full-catalogue CE, 1 = SASRec's BCE pair
+    int loss_kind;                             // head of the last loss call: 0 = full-catalogue CE, 1 = SASRec's BCE pair,
+                                               // 2 = sampled softmax (cfg.train_negatives > 0)
     const float* ext_dy = nullptr;             // bsarec_backward_seq: upstream gradient of the last layer's output, all positions
     const float* ext_mid[BSAREC_MAX_LAYERS] = {};   // bsarec_backward_seq_multi: upstream gradients of layer outputs 0 .. N-1 (null: none)
     const int64_t *bce_pos, *bce_neg;
@@ -179,6 +181,11 @@ struct bsarec_plan {
     bsarec_hook_t dense_hook = nullptr; void* dense_hook_user = nullptr;   // bsarec_plan_set_dense_grad_hook
     float* lookup_grad = nullptr;            // target of the embedding scatter when the dense dE is exchanged early
     unsigned long long* lookup_acc = nullptr;  // [V][d] fixed-point sum of the scatter (kernels.h), zero between steps
+    // sampled-softmax head (cfg.train_negatives > 0; sampled_softmax.h)
+    int* ssm_cand = nullptr; float *ssm_corr = nullptr, *ssm_logits = nullptr, *ssm_dlogits = nullptr;
+    const int64_t* pop_cum = nullptr;          // bsarec_plan_set_train_sampler (train_sampler = 1)
+    const int64_t* ssm_answers = nullptr;      // answers of the last sampled loss (the backward reads them)
+    int ssm_nslab = 0, ssm_chunk = 0;          // split-K slabs of d(h_last) and the candidate columns per slab
 };
 static ProfState* prof_of(bsarec_plan* p) { return &p->prof; }
 static bool bf_products_of(const bsarec_plan* p) { return p->bf_products; }
@@ -212,6 +219,9 @@ static int check_cfg(const bsarec_config_t& c) {
     if (c.hidden_act < 0 || c.hidden_act > 4) return -14;
     if (c.storage < 0 || c.storage > 1) return -15;
     if (c.splits < 0 || c.splits > 1024 || c.top_slabs < 0 || c.top_slabs > 16) return -16;
+    if (c.train_negatives < 0 || c.train_negatives > BSAREC_TRAIN_NEG_MAX) return -17;
+    if (c.train_sampler < 0 || c.train_sampler > 1 || c.train_no_logq < 0 || c.train_no_logq > 1) return -17;
+    if (c.train_negatives > 0 && c.storage != 0) return -18;      // the sampled head is fp32 only
     return 0;
 }
 
@@ -257,6 +267,12 @@ static void derive(bsarec_plan& p) {
     if (vc < 64) vc = 64;
     p.vchunk = (int)vc;
     p.vsplit = cdiv(p.Vp, p.vchunk);
+    // sampled head: d(h_last) in at most vsplit (<= 32) slabs of >= 256 candidate columns, so the readers' slab count holds
+    if (c.train_negatives > 0) {
+        const int N = c.train_negatives, want = std::max(1, std::min(std::min(p.vsplit, 32), N / 256));
+        p.ssm_chunk = (int)rup(cdiv(N, want), SSM_KS);
+        p.ssm_nslab = cdiv(N, p.ssm_chunk);
+    }
 }
 
 static void carve(bsarec_plan& p, char* base, size_t* total) {
@@ -308,6 +324,11 @@ static void carve(bsarec_plan& p, char* base, size_t* total) {
     p.top_ak = cv.take<float>(B * h * d); p.top_rk = cv.take<float>(B * h * d);
     p.top_av = cv.take<float>(B * h * d); p.top_rv = cv.take<float>(B * h * d);
     p.slab_dummy = cv.take<float>((long)p.nsplit * 4 * d);
+    if (c.train_negatives > 0) {                                 // (a zero tail carves exactly what it always did)
+        const long Nn = c.train_negatives;
+        p.ssm_cand = cv.take<int>(Nn); p.ssm_corr = cv.take<float>(Nn);
+        p.ssm_logits = cv.take<float>(B * (Nn + 1)); p.ssm_dlogits = cv.take<float>(B * (Nn + 1));
+    }
     // (no guard pad: the direct weight-gradient kernels prefetch past a slice without predicates, but through buffer
     // descriptors sized to their operand -- dw_direct.h)
     *total = cv.off;
@@ -449,6 +470,7 @@ extern "C" long bsarec_buffer_offset(const bsarec_plan_t* p, int buffer, int lay
     if (!p) return -1;
     const int N = p->cfg.layers;
     const void* ptr = nullptr;
+    if (buffer >= BSAREC_BUF_TRAIN_CAND && p->cfg.train_negatives == 0) return -1;
     switch (buffer) {
         case BSAREC_BUF_LAYER_OUT: if (layer < 0 || layer > N) return -1; ptr = p->X[layer]; break;
         case BSAREC_BUF_LOGITS: ptr = p->logits; break;
@@ -460,6 +482,10 @@ extern "C" long bsarec_buffer_offset(const bsarec_plan_t* p, int buffer, int lay
         case BSAREC_BUF_PROBS: if (layer < 0 || layer >= N) return -1; ptr = p->lb[layer].probs; break;
         case BSAREC_BUF_CTX: if (layer < 0 || layer >= N) return -1; ptr = p->lb[layer].ctx; break;
         case BSAREC_BUF_DLAYER_IN: if (layer < 0 || layer > N) return -1; ptr = (layer & 1) ? p->dXb : p->dXa; break;
+        case BSAREC_BUF_TRAIN_CAND: ptr = p->ssm_cand; break;
+        case BSAREC_BUF_TRAIN_CORR: ptr = p->ssm_corr; break;
+        case BSAREC_BUF_TRAIN_LOGITS: ptr = p->ssm_logits; break;
+        case BSAREC_BUF_TRAIN_DLOGITS: ptr = p->ssm_dlogits; break;
         default: return -1;
     }
     return (long)((const char*)ptr - p->ws);
@@ -467,9 +493,28 @@ extern "C" long bsarec_buffer_offset(const bsarec_plan_t* p, int buffer, int lay
 
 extern "C" int bsarec_plan_set_dense_grad_hook(bsarec_plan_t* p, bsarec_hook_t hook, void* user, float* lookup_grad) {
     if (!p) return -10;
+    if (p->cfg.train_negatives > 0 && (hook || lookup_grad)) return -22;     // the sampled head has no dense part to exchange early
     p->dense_hook = hook; p->dense_hook_user = user; p->lookup_grad = lookup_grad;
     return 0;
 }
+
+extern "C" int bsarec_plan_set_train_sampler(bsarec_plan_t* p, const int64_t* pop_cum) {
+    if (!p) return -10;
+    if (p->cfg.train_negatives == 0 || p->cfg.train_sampler != 1) return -22;
+    p->pop_cum = pop_cum;
+    return 0;
+}
+
+// The sampled head's refusals, checked by every entry point that runs the loss before it launches anything.
+static int sampled_refusal(const bsarec_plan& p) {
+    if (p.cfg.train_negatives == 0) return 0;
+    if (p.dense_hook || p.lookup_grad) return -22;
+    if (p.cfg.train_sampler == 1 && !p.pop_cum && !g_dry) return -23;
+    return 0;
+}
+
+// split-K slabs of d(h_last) the head's backward leaves for the top block
+static int head_nsplit(const bsarec_plan& p) { return p.loss_kind == 1 ? 1 : (p.loss_kind == 2 ? p.ssm_nslab : p.vsplit); }
 
 extern "C" int bsarec_plan_is_fused(const bsarec_plan_t* p) { return p && p->fused ? 1 : 0; }
 extern "C" int bsarec_config_is_fused(const bsarec_config_t* cfg) {
@@ -681,7 +726,7 @@ static int launch_fused_bwd(bsarec_plan& p, int l, bool tr, const float* dY, flo
     F.a_g = w.attn_ln_w; F.w1 = wm.ffn1_w; F.w2 = wm.ffn2_w; F.ff_g = w.ffn_ln_w; F.tw = p.twiddle;
     F.xhat_f = b.xhat_f; F.rstd_f = b.rstd_f; F.q = b.q; F.k = b.k; F.v = b.v; F.probs = b.probs;
     F.xhat_a = b.xhat_a; F.rstd_a = b.rstd_a; F.u = b.gp; F.xhat_ff = b.xhat_ff; F.rstd_ff = b.rstd_ff;
-    if (top) { F.dh_slabs = p.dlast_slab; F.dh_nsplit = p.loss_kind == 1 ? 1 : p.vsplit; F.dh_stride = (long)c.batch * d; }
+    if (top) { F.dh_slabs = p.dlast_slab; F.dh_nsplit = head_nsplit(p); F.dh_stride = (long)c.batch * d; }
     if (l == 0) {       // the embedding front-end's backward (Drop + LayerNorm) rides in the bottom block's epilogue
         F.e_dz = p.dz; F.e_xhat = p.xhat0; F.e_rstd = p.rstd0; F.e_g = p.P.ln_w;
         F.e_pg = p.part_ln0; F.e_pb = p.part_ln0 + nb * d; F.e_drop = make_drop(p, c.p_hidden, 0, tr);
@@ -772,7 +817,7 @@ static void fill_top_bwd(bsarec_plan& p, int l, bool tr, float* dXout, TopBwdP& 
     F.a_g = w.attn_ln_w; F.w1 = w.ffn1_w; F.w2 = w.ffn2_w; F.ff_g = w.ffn_ln_w; F.tw = p.twiddle;
     F.xhat_f = b.xhat_f; F.rstd_f = b.rstd_f; F.q = b.q; F.k = b.k; F.v = b.v; F.probs = b.probs;
     F.xhat_a = b.xhat_a; F.rstd_a = b.rstd_a; F.u = b.u; F.xhat_ff = b.xhat_ff; F.rstd_ff = b.rstd_ff; F.low = b.dsp;
-    F.dh_slabs = p.dlast_slab; F.dh_nsplit = p.loss_kind == 1 ? 1 : p.vsplit; F.dh_stride = (long)c.batch * d;
+    F.dh_slabs = p.dlast_slab; F.dh_nsplit = head_nsplit(p); F.dh_stride = (long)c.batch * d;
     F.dT = p.top_dT; F.dU = p.top_dU; F.dO = p.top_dO; F.dq = p.top_dq;
     F.ak = p.top_ak; F.rk = p.top_rk; F.av = p.top_av; F.rv = p.top_rv;
     F.pbk = p.part_kvb; F.pbv = p.part_kvb + (long)c.batch * d;
@@ -957,9 +1002,36 @@ extern "C" int bsarec_logits(bsarec_plan_t* p, void* stream) {
     return launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_LOGITS, true);
 }
 
+static SsmP ssm_params(const bsarec_plan& p, const int64_t* answers) {
+    const bsarec_config_t& c = p.cfg;
+    SsmP P;
+    memset(&P, 0, sizeof(P));
+    P.H = p.X[c.layers] + (long)(c.seq_len - 1) * c.hidden; P.ldh = (long)c.seq_len * c.hidden; P.E = p.P.item_emb;
+    P.answers = answers; P.pop_cum = c.train_sampler == 1 ? p.pop_cum : nullptr; P.state = p.state;
+    P.B = c.batch; P.V = c.item_size; P.d = c.hidden; P.N = c.train_negatives; P.logq = c.train_no_logq ? 0 : 1;
+    P.inv_b = 1.0f / (float)c.batch;
+    P.cand = p.ssm_cand; P.corr = p.ssm_corr; P.logits = p.ssm_logits; P.dlogits = p.ssm_dlogits; P.loss_rows = p.loss_rows;
+    P.slab = p.dlast_slab; P.nslab = p.ssm_nslab; P.chunk = p.ssm_chunk; P.acc = p.lookup_acc;
+    const int dt = cdiv(c.hidden, SSM_TILE);
+    P.tilesA = cdiv(c.train_negatives, SSM_TILE) * dt;
+    P.tilesB = p.ssm_nslab * cdiv(c.batch, SSM_TILE) * dt;
+    return P;
+}
+
 static int loss_impl(bsarec_plan_t* p, const int64_t* answers, void* stream, bool with_mean) {
     if (!p || !answers) return -10;
     hipStream_t s = (hipStream_t)stream;
+    if (p->cfg.train_negatives > 0) {          // sampled softmax (sampled_softmax.h): draws + logits, then the rows' CE
+        RET(sampled_refusal(*p));
+        p->loss_kind = 2; p->ssm_answers = answers;
+        const SsmP P = ssm_params(*p, answers);
+        LAUNCH(ssm_logits_kernel, dim3(cdiv(P.N, SSM_TILE), cdiv(P.B, SSM_TILE)), dim3(ROW_THREADS), 0, s, P);
+        HIPCHK(hipGetLastError());
+        LAUNCH(ssm_ce_kernel, dim3(P.B), dim3(ROW_THREADS), 0, s, P);
+        HIPCHK(hipGetLastError());
+        if (with_mean) LAUNCH(loss_mean_kernel, dim3(1), dim3(ROW_THREADS), 0, s, p->loss_rows, P.B, p->loss);
+        return (int)hipGetLastError();
+    }
     RET(bsarec_logits(p, stream));
     p->loss_kind = 0;
     const bsarec_config_t& c = p->cfg;
@@ -1019,6 +1091,7 @@ extern "C" int bsarec_backward(bsarec_plan_t* p, void* stream) {
 extern "C" int bsarec_backward_seq(bsarec_plan_t* p, const float* d_out, void* stream) {
     if (!p || !d_out) return -10;
     if (p->pruned) return -13;                 // the forward kept only the last row of the top block: run bsarec_forward
+    if (p->cfg.train_negatives > 0) return -22;     // a plan with the sampled head runs that head's backward only
     TickP none;
     memset(&none, 0, sizeof(none));
     p->ext_dy = d_out;
@@ -1043,7 +1116,7 @@ extern "C" int bsarec_backward_seq_multi(bsarec_plan_t* p, const float* const* d
 // launch of block 0 to host the step tick, plain single-GPU gradient sources, and every gradient tensor inside the flat
 // arena the update walks (item table + the reduction jobs' targets = the whole arena).
 static bool can_fuse_adam(const bsarec_plan& p, const bsarec_adam_t& a) {
-    if (!p.fused || !p.direct_dw || p.loss_kind != 0) return false;
+    if (!p.fused || !p.direct_dw || p.loss_kind == 1) return false;
     if (a.grads2 || a.n_grad_srcs > 0 || a.grad_scale != 1.0f) return false;
     if (!p.G.item_emb || p.G.item_emb < a.grads) return false;
     const long item = (long)p.cfg.item_size * p.cfg.hidden;
@@ -1076,6 +1149,13 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
         if (!g_dry) HIPCHK(hipMemsetAsync(p->G.item_emb, 0, (size_t)c.item_size * d * sizeof(float), s));
         LAUNCH(bce_bwd_kernel, dim3(B), dim3(64), 0, s, hlast, (long)L * d, p->P.item_emb, p->bce_pos, p->bce_neg, p->dlogits, B, d,
                c.item_size, p->dlast_slab, p->G.item_emb);
+        HIPCHK(hipGetLastError());
+    } else if (p->loss_kind == 2) {
+        // sampled softmax: candidate and answer rows of dE into the fixed-point accumulator (the item table's dense part is
+        // zero: the final reduction writes the accumulator over it), and the slabs of d(h_last)
+        SsmP P = ssm_params(*p, p->ssm_answers);
+        const int tilesC = std::max(1, std::min(cdiv((long)B * d, ROW_THREADS), 64));
+        LAUNCH(ssm_bwd_kernel, dim3(P.tilesA + P.tilesB + tilesC), dim3(ROW_THREADS), 0, s, P);
         HIPCHK(hipGetLastError());
     } else if (direct_logits) {
         // fused shape: dE = dlogits^T . h_last (K = B rows, written straight into the gradient buffer) and the split-K
@@ -1134,7 +1214,7 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
     } else
     if (!p->fused) {      // the fused top-layer backward synthesises this gradient from the slabs itself
         LAUNCH(dlast_kernel, dim3(cdiv((long)T * d / 4, ROW_THREADS)), dim3(ROW_THREADS), 0, s, p->dlast_slab,
-               p->loss_kind == 1 ? 1 : p->vsplit, (long)B * d, T, L, d, dY);
+               head_nsplit(*p), (long)B * d, T, L, d, dY);
         HIPCHK(hipGetLastError());
     }
 
@@ -1392,6 +1472,7 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
         LookupAcc la;
         la.acc = p->lookup_acc; la.dst = p->lookup_grad ? p->lookup_grad : p->G.item_emb; la.n4 = (long)c.item_size * d / 4;
         la.nblocks = (int)std::min<long>(cdiv(la.n4, ROW_THREADS), 1024);
+        la.dense_zero = (!p->ext_dy && p->loss_kind == 2) ? 1 : 0;
         if (fuse_adam) {
             const bsarec_adam_t& a = *fuse_adam;
             AdamFuseP A;
@@ -1400,6 +1481,7 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
             A.b1 = a.beta1; A.b2 = a.beta2; A.eps = a.eps; A.wd = a.weight_decay;
             A.shadow = (unsigned short*)a.shadow_bf16; A.shadow_from = a.shadow_bf16 ? a.shadow_from : a.n;
             A.item_off = p->G.item_emb - a.grads; A.item_n4 = (long)c.item_size * d / 4; A.lookup_acc = la.acc;
+            A.dense_zero = la.dense_zero;
             int ab = cdiv(A.item_n4, ROW_THREADS);
             if (ab > 1024) ab = 1024;
             LAUNCH(reduce_adam_kernel, dim3(p->red_blocks + ab), dim3(ROW_THREADS), 0, s, p->pruned ? p->jobs_pruned : p->jobs,
@@ -1477,6 +1559,7 @@ extern "C" int bsarec_train_step_indexed(bsarec_plan_t* p, const int64_t* table,
                                          int64_t* answers_buf, const bsarec_adam_t* a, void* stream) {
     if (!p) return -10;
     RET(adam_check(a));
+    RET(sampled_refusal(*p));
     hipStream_t s = (hipStream_t)stream;
     if (!table || !answers_table || !perm || !cursor || !ids_buf || !answers_buf) return -10;
     GatherP gp{table, answers_table, perm, n_samples, (const long long*)cursor, ids_buf, answers_buf};
@@ -1495,6 +1578,7 @@ extern "C" int bsarec_grad_step_indexed(bsarec_plan_t* p, const int64_t* table, 
                                         const int64_t* perm, long n_samples, void* cursor, int64_t* ids_buf,
                                         int64_t* answers_buf, float lr, float b1, float b2, void* stream) {
     if (!p || !table || !answers_table || !perm || !cursor || !ids_buf || !answers_buf) return -10;
+    RET(sampled_refusal(*p));
     GatherP gp{table, answers_table, perm, n_samples, (const long long*)cursor, ids_buf, answers_buf};
     RET(forward_impl(p, ids_buf, 1, stream, gp, true));
     RET(bsarec_loss(p, answers_buf, stream));
@@ -1506,6 +1590,7 @@ extern "C" int bsarec_train_step(bsarec_plan_t* p, const int64_t* ids, const int
                                  void* stream) {
     if (!p) return -10;
     RET(adam_check(a));
+    RET(sampled_refusal(*p));
     RET(bsarec_step_begin(p, stream));
     RET(bsarec_forward_last(p, ids, 1, stream));
     RET(bsarec_loss(p, answers, stream));

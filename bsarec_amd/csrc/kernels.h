@@ -504,7 +504,9 @@ __device__ __forceinline__ unsigned long long lookup_fix(float x) {
 __device__ __forceinline__ float lookup_unfix(unsigned long long a) { return (float)((double)(long long)a * 0x1p-40); }
 // accumulator -> float: dst[i] += acc[i], acc[i] = 0 (float4 group i4).  Items no token of the step looked up hold zero:
 // nothing to add, nothing to write back.
-struct LookupAcc { unsigned long long* acc; float* dst; long n4; int nblocks; };
+// dense_zero: the item table has no dense part this step (sampled-softmax head: its rows are in the accumulator too), so
+// dst[i] = acc[i] is written for EVERY group, zero where the accumulator is
+struct LookupAcc { unsigned long long* acc; float* dst; long n4; int nblocks; int dense_zero; };
 __device__ __forceinline__ bool lookup_take(unsigned long long* acc, long i4, f32x4& add) {
     ulonglong2* a = reinterpret_cast<ulonglong2*>(acc + 4 * i4);
     const ulonglong2 x = a[0], y = a[1];
@@ -515,8 +517,10 @@ __device__ __forceinline__ bool lookup_take(unsigned long long* acc, long i4, f3
 }
 __device__ __forceinline__ void lookup_flush(const LookupAcc& la, long first, long stride) {
     f32x4 add;
-    for (long i = first; i < la.n4; i += stride)
-        if (lookup_take(la.acc, i, add)) st4(la.dst + 4 * i, ld4(la.dst + 4 * i) + add);
+    for (long i = first; i < la.n4; i += stride) {
+        if (lookup_take(la.acc, i, add)) st4(la.dst + 4 * i, la.dense_zero ? add : ld4(la.dst + 4 * i) + add);
+        else if (la.dense_zero) st4(la.dst + 4 * i, f32x4{0, 0, 0, 0});
+    }
 }
 #ifndef SCATTER_FLOATS
 #define SCATTER_FLOATS 4096           // LDS row accumulators per block: chunk = 4096 / (4*LPR) tokens (64 at d = 64:
@@ -821,6 +825,7 @@ struct AdamFuseP {
     unsigned short* shadow; long shadow_from;
     long item_off, item_n4;            // the item table inside the flat arena: element offset, float4 count
     unsigned long long* lookup_acc;    // the lookup-path sum of the item-table gradient (fixed point), added here once
+    int dense_zero;                    // LookupAcc.dense_zero: the gradient is the accumulator alone (not read, always stored)
 };
 __global__ void __launch_bounds__(ROW_THREADS)
 reduce_adam_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ blockmap, int nblocks,
@@ -867,12 +872,13 @@ reduce_adam_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ b
     const long nb = gridDim.x - nblocks;
     for (long i = (long)(blockIdx.x - nblocks) * ROW_THREADS + threadIdx.x; i < A.item_n4; i += nb * ROW_THREADS) {
         const long o = A.item_off + 4 * i;
-        f32x4 wi = ld4(A.w + o), gi = ld4(A.g + o), mi = ld4(A.m + o), vi = ld4(A.v + o);
+        f32x4 wi = ld4(A.w + o), mi = ld4(A.m + o), vi = ld4(A.v + o);
+        f32x4 gi = A.dense_zero ? f32x4{0, 0, 0, 0} : ld4(A.g + o);
         f32x4 add;
         if (A.lookup_acc && lookup_take(A.lookup_acc, i, add)) {
-            gi += add;
+            gi = A.dense_zero ? add : gi + add;
             st4(A.g + o, gi);
-        }
+        } else if (A.dense_zero) st4(A.g + o, gi);
         if (A.wd != 0.f) gi += A.wd * wi;
         mi = A.b1 * mi + (1.0f - A.b1) * gi;
         vi = A.b2 * vi + (1.0f - A.b2) * gi * gi;

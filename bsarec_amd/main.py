@@ -56,6 +56,18 @@ def negatives_count(text: str) -> int:
     return n
 
 
+def train_negatives_count(text: str) -> int:
+    """--train_negatives: 0 (full-catalogue cross-entropy) .. BSAREC_TRAIN_NEG_MAX."""
+    from ._lib import TRAIN_NEG_MAX
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}") from None
+    if not 0 <= n <= TRAIN_NEG_MAX:
+        raise argparse.ArgumentTypeError(f"{n} outside 0..{TRAIN_NEG_MAX}")
+    return n
+
+
 def seed_value(text: str) -> int:
     """--eval_seed: an unsigned 64-bit integer."""
     try:
@@ -109,6 +121,14 @@ def parse_args(argv=None):
     p.add_argument("--eval_sampler", default=argparse.SUPPRESS, choices=("uniform", "popularity"),
                    help="how the negatives are drawn: uniform over the catalogue (default) or by training-set popularity")
     p.add_argument("--eval_seed", default=argparse.SUPPRESS, type=seed_value, help="seed of the negative draws (default: --seed)")
+    # not reference flags: the sampled-softmax training head (the answer against N candidates shared by the batch, logQ-corrected)
+    # instead of the full-catalogue cross-entropy.  Absent unless given (argparse.SUPPRESS), as the --eval_* flags are
+    p.add_argument("--train_negatives", default=argparse.SUPPRESS, type=train_negatives_count,
+                   help="train with a sampled softmax over this many candidates per step (0..8192; 0 = full CE, the default)")
+    p.add_argument("--train_sampler", default=argparse.SUPPRESS, choices=("uniform", "popularity"),
+                   help="how the training candidates are drawn: uniform over the catalogue (default) or by training popularity")
+    p.add_argument("--train_no_logq", default=argparse.SUPPRESS, action="store_true",
+                   help="no logQ correction of the sampled logits")
     # DuoRec's flags (src/utils.py:106-111)
     p.add_argument("--tau", default=1.0, type=float)
     p.add_argument("--lmd", default=0.1, type=float)
@@ -167,7 +187,8 @@ def run(args, user_seq, logger=None, checkpoint_path=None):
     for split in ("valid", "test"):
         indptr, cols = D.seen_csr(user_seq, split)
         setattr(args, f"{split}_rating_matrix", sp.csr_matrix((np.ones(len(cols)), cols, indptr), shape=(n_users, args.item_size)))
-    if getattr(args, "eval_negatives", 0) > 0 and getattr(args, "eval_sampler", "uniform") == "popularity":
+    if (getattr(args, "eval_negatives", 0) > 0 and getattr(args, "eval_sampler", "uniform") == "popularity") or \
+            (getattr(args, "train_negatives", 0) > 0 and getattr(args, "train_sampler", "uniform") == "popularity"):
         args.item_popularity = D.item_popularity(user_seq, args.item_size)    # training part only: one table for both splits
     model = MODEL_DICT[args.model_type.lower()](args=args)
     if getattr(model, "needs_negatives", False):

@@ -79,6 +79,8 @@ class _Plan:
         for k in L.OPTION_FIELDS:
             setattr(self.cfg, k, int(opts.get(k, 0)))
         self.options = {k: int(getattr(self.cfg, k)) for k in L.OPTION_FIELDS}
+        for k in L.TRAIN_FIELDS:                        # the model's training head (0: full-catalogue CE)
+            setattr(self.cfg, k, model.train_head[k])
         nbytes = lib.bsarec_workspace_bytes(C.byref(self.cfg))
         if nbytes == 0:
             raise ValueError("configuration not supported by libbsarec_hip (see include/bsarec_hip.h limits: "
@@ -105,6 +107,8 @@ class _Plan:
                                        self.ws.data_ptr(), nbytes, self.state.data_ptr(),
                                        model._twiddle.data_ptr(), stream), "bsarec_plan_create")
         self.lib = lib
+        if self.cfg.train_negatives > 0 and self.cfg.train_sampler == 1 and model._train_cum is not None:
+            model._install_train_sampler(self)
 
     def view(self, buf: int, layer: int, shape) -> torch.Tensor:
         """A workspace buffer as a tensor: fp32, or bfloat16 where the plan stores it so (cfg.storage = 1)."""
@@ -220,8 +224,24 @@ class _LossFn(torch.autograd.Function):
         return (None, None, None) + model._grads_in_param_order(g)
 
 
+def train_head_of(args) -> Dict[str, int]:
+    """The training head ``args`` select, as bsarec_config_t fields: ``train_negatives`` (0 = full-catalogue CE, else the
+    sampled-softmax head over that many candidates), ``train_sampler`` ("uniform" / "popularity") and ``train_no_logq``.
+    Absent attributes mean 0."""
+    n = int(getattr(args, "train_negatives", 0) or 0)
+    if not 0 <= n <= L.TRAIN_NEG_MAX:
+        raise ValueError(f"train_negatives = {n}, expected 0..{L.TRAIN_NEG_MAX}")
+    sampler = getattr(args, "train_sampler", "uniform") or "uniform"
+    if sampler not in L.TRAIN_SAMPLERS:
+        raise ValueError(f"train_sampler {sampler!r}: expected one of {sorted(L.TRAIN_SAMPLERS)}")
+    return {"train_negatives": n, "train_sampler": L.TRAIN_SAMPLERS[sampler] if n else 0,
+            "train_no_logq": int(bool(getattr(args, "train_no_logq", False))) if n else 0}
+
+
 class BSARecModel(nn.Module):
     """Drop-in for ``MODEL_DICT['bsarec'](args=args)`` (src/main.py:31)."""
+
+    sampled_softmax_ok = True                    # args.train_negatives > 0 selects the sampled-softmax head (train_head_of)
 
     def __init__(self, args):
         super().__init__()
@@ -235,6 +255,14 @@ class BSARecModel(nn.Module):
         self.options = dict(getattr(args, "plan_options", None) or {})
         if getattr(args, "storage", None) == "bf16":
             self.options["storage"] = 1
+        self.train_head = train_head_of(args)
+        if self.train_head["train_negatives"] > 0:
+            if not self.sampled_softmax_ok:
+                raise ValueError(f"{type(self).__name__} has its own loss head: train_negatives must be 0")
+            if self.options.get("storage", 0) or L.default_options().get("storage", 0):
+                raise ValueError("train_negatives > 0: the sampled-softmax head is fp32 only (no bf16 storage)")
+        self._train_cum = None            # cumulative popularity of the sampled head (set_train_popularity), host int64[V]
+        self._train_cum_dev = None
         self.batch_size = getattr(args, "batch_size", 256)              # stored, unused (as in the reference)
         self.cutoff_bins = min(args.c // 2 + 1, args.max_seq_length // 2 + 1)   # src/model/bsarec.py:87,96
         if getattr(args, "filter_kind", 0) == 1:
@@ -323,6 +351,31 @@ class BSARecModel(nn.Module):
         self._dense_hook = L.HOOK(lambda user, stream: fn(stream)) if fn is not None else None
         for plan in self._plans.values():
             self._install_hook(plan)
+
+    def set_train_popularity(self, counts):
+        """The popularity sampler of the sampled-softmax head (train_sampler = "popularity"): ``counts`` int64[item_size] of
+        item occurrences (data.item_popularity; item 0 and items of count 0 are never drawn).  Uploaded once as the
+        cumulative table of include/bsarec_hip.h and handed to every plan."""
+        V = int(self.args.item_size)
+        c = np.asarray(counts, dtype=np.int64)
+        if c.shape != (V,) or (c < 0).any():
+            raise ValueError(f"set_train_popularity: expected {V} counts >= 0")
+        cum = np.cumsum(np.where(np.arange(V) == 0, 0, c))
+        if cum[-1] < 1:
+            raise ValueError("set_train_popularity: every count is 0")
+        self._train_cum, self._train_cum_dev = cum, None
+        for plan in self._plans.values():
+            self._install_train_sampler(plan)
+
+    def _install_train_sampler(self, plan):
+        if plan.cfg.train_negatives == 0 or plan.cfg.train_sampler != 1:
+            return
+        dev = self._arena.device
+        if self._train_cum_dev is None or self._train_cum_dev.device != dev:
+            self._train_cum_dev = torch.as_tensor(self._train_cum, dtype=torch.int64, device=dev)
+        L.check(plan.lib.bsarec_plan_set_train_sampler(plan.handle, self._train_cum_dev.data_ptr()),
+                "bsarec_plan_set_train_sampler")
+        plan._pop_keepalive = self._train_cum_dev
 
     def _install_hook(self, plan):
         lk = self._lookup.data_ptr() if (self._lookup is not None and plan.garena is self._garena) else None
@@ -627,6 +680,7 @@ class SASRecModel(BSARecModel):
     36 keys)."""
 
     needs_negatives = True                       # Trainer: feed neg_answer (DeviceBatches.enable_negatives)
+    sampled_softmax_ok = False                   # its own (BCE) head
 
     def __init__(self, args):
         import copy
@@ -713,6 +767,7 @@ class FMLPRecModel(BSARecModel):
     + feed-forward, no attention branch); elsewhere on the generic tiled kernels."""
 
     needs_negatives = True
+    sampled_softmax_ok = False                   # its own (log-sigmoid) head
 
     def __init__(self, args):
         import copy

@@ -77,10 +77,35 @@ def graph_schedule(n: int, k: int):
     return out
 
 
+def check_train_head(model, args, train_dataloader, process_group=None):
+    """Host checks of the sampled-softmax training head (args.train_negatives > 0) before the first step: single GPU only,
+    and under the popularity sampler every training answer must have a popularity count > 0 (an answer the sampler can
+    never draw has q = 0 and an infinite logQ correction).  Installs the popularity table on the model."""
+    head = getattr(model, "train_head", None) or {}
+    if head.get("train_negatives", 0) == 0:
+        return
+    if process_group is not None:
+        raise ValueError("train_negatives > 0: data-parallel training has no sampled-softmax head")
+    if head.get("train_sampler", 0) == 1:
+        pop = getattr(args, "item_popularity", None)
+        if pop is None:
+            raise ValueError("train_sampler = popularity needs args.item_popularity (data.item_popularity)")
+        pop = np.asarray(pop, dtype=np.int64)
+        ans = getattr(train_dataloader, "answers", None)
+        if ans is not None:
+            a = torch.as_tensor(ans).detach().cpu().numpy().astype(np.int64)
+            bad = (a < 0) | (a >= pop.shape[0])
+            bad[~bad] = pop[a[~bad]] <= 0
+            if bad.any():
+                raise ValueError(f"train_sampler = popularity: {int(bad.sum())} training answers have popularity count 0")
+        model.set_train_popularity(pop)
+
+
 class Trainer:
     def __init__(self, model: BSARecModel, train_dataloader, eval_dataloader, test_dataloader, args, logger=None,
                  use_graph: bool = True, process_group=None, exchange: str = "auto"):
         self.args = args
+        check_train_head(model, args, train_dataloader, process_group)
         self.logger = logger or _NullLogger()
         if not torch.cuda.is_available() or getattr(args, "no_cuda", False):
             raise RuntimeError("bsarec_amd.Trainer needs an MI355X: there is no CPU training path "

@@ -74,6 +74,11 @@ typedef struct {
                          * matrix cores as six bf16 x bf16 partial products of the operands' exact three-way bf16 splits
                          * (fp32 accumulation; error <= 2^-26 per product, below fp32 rounding; fp32 tensors, fp32 storage).
                          * 0 (default): v_mfma_f32_32x32x2_f32.  Ignored under storage = 1 */
+    int train_negatives;  /* 0: the loss is the full-catalogue CE.  1 .. BSAREC_TRAIN_NEG_MAX: the sampled-softmax head (below) for
+                           * every entry point that runs the loss (bsarec_loss, bsarec_train_step, bsarec_train_step_indexed,
+                           * bsarec_grad_step_indexed); bsarec_logits stays full-catalogue.  fp32 only (storage = 1 is refused) */
+    int train_sampler;    /* sampled head: 0 uniform over [1, V); 1 popularity (bsarec_plan_set_train_sampler) */
+    int train_no_logq;    /* sampled head: 1 = no logQ correction */
 } bsarec_config_t;
 
 /* The 19 tensors of one BSARecBlock, in state_dict order (+ the sibling model's filter weight)
@@ -106,7 +111,12 @@ enum {
     BSAREC_BUF_DLAYER_IN = 6,  /* [B,L,d]   gradient w.r.t. layer output l (ping-pong pair: only l = 0, 1 survive backward; on the fused path l = 0 is never materialised: the bottom block emits the embedding gradient directly) */
     BSAREC_BUF_LOSS_ROWS = 7,  /* [B]       per-sequence cross-entropy */
     BSAREC_BUF_CTX = 8,        /* [B,L,d]   attention context of layer l */
-    BSAREC_BUF_DLOGITS = 9     /* [B,Vp]    d loss / d logits = (softmax - onehot(answer)) / B, pad columns = 0 (after bsarec_loss) */
+    BSAREC_BUF_DLOGITS = 9,    /* [B,Vp]    d loss / d logits = (softmax - onehot(answer)) / B, pad columns = 0 (after bsarec_loss) */
+    /* sampled-softmax head (cfg.train_negatives = N > 0 only; -1 otherwise), after the loss: */
+    BSAREC_BUF_TRAIN_CAND = 10,    /* int32 [N]     the step's candidates n_0 .. n_N-1 */
+    BSAREC_BUF_TRAIN_CORR = 11,    /* [N]           their corrections c(n_j) */
+    BSAREC_BUF_TRAIN_LOGITS = 12,  /* [B, N+1]      x_b0 (answer), x_b1 .. x_bN (candidates; -inf on an accidental hit) */
+    BSAREC_BUF_TRAIN_DLOGITS = 13  /* [B, N+1]      d loss / d x = (softmax - onehot_0) / B (exactly 0 on a hit) */
 };
 
 typedef struct bsarec_plan bsarec_plan_t;   /* host-side launch plan (no device memory of its own) */
@@ -156,6 +166,32 @@ void bsarec_plan_destroy(bsarec_plan_t *plan);
  * exchange is not disturbed; hand it to the update as bsarec_adam_t.grads2. */
 typedef void (*bsarec_hook_t)(void *user, void *stream);
 int bsarec_plan_set_dense_grad_hook(bsarec_plan_t *plan, bsarec_hook_t hook, void *user, float *lookup_grad);
+
+/* Sampled-softmax training head (cfg.train_negatives = N > 0), opt-in beside the full-catalogue CE for large catalogues
+ * (Jean et al. 2015; Yi et al. 2019).
+ *   Draws: each step draws N items with replacement, shared by all B rows.  Philox4x32-10 call j = 0, 1, ... has key
+ *   (lo32(state[0]), hi32(state[0])) -- the dropout key -- and counter (lo32(j), hi32(j), BSAREC_TRAIN_NEG_SITE, lo32(state[1]))
+ *   -- the dropout stream's layout at a site no dropout mask uses, with the step value this step's masks use (read on the
+ *   device: a captured graph replays with fresh candidates).  Uniform (train_sampler 0): draw 4j + m takes word w_m,
+ *   n = 1 + ((uint64)w_m * (V - 1) >> 32).  Popularity (1): draw 2j + m takes x = w_2m | (uint64)w_2m+1 << 32, r = the high 64
+ *   bits of x * T, n = the smallest i with pop_cum[i] > r (the table format of bsarec_sampled_rank: int64[V], non-decreasing,
+ *   pop_cum[0] = 0, T = pop_cum[V - 1] >= 1; items of count 0 are never drawn).  Candidates depend on (seed, step, N, V, table)
+ *   only.
+ *   Logits: x_b0 = h_b . E[a_b] - c(a_b), x_bj = h_b . E[n_j] - c(n_j) (j = 1 .. N, candidate n_j-1), h_b = the last layer's
+ *   output at position L-1, fp32 dot products; c(i) = log(N q_i), q_i = (pop_cum[i] - pop_cum[i-1]) / T, under popularity
+ *   sampling with logQ on, else 0 (uniform: a constant that cancels).  Accidental hit n_j == a_b: x_bj = -inf.
+ *   Loss: loss_rows[b] = logsumexp_j x_bj - x_b0 -> BSAREC_BUF_LOSS_ROWS, their mean over B -> BSAREC_BUF_LOSS.
+ *   Backward (bsarec_backward and the steps): g = (softmax(x_b) - onehot_0) / B; d(h_b) = sum_c g_bc E[c]; dE[c] += g_bc h_b for
+ *   every candidate column, the answers included, summed as 64-bit fixed point (2^-40) so that the step is bit-deterministic;
+ *   rows that are no candidate get no head gradient (the item table's gradient is then the head rows plus the lookup rows;
+ *   Adam stays dense).
+ *   Refusals (< 0 before anything is launched): storage = 1 (at plan creation); a dense-gradient hook or lookup_grad;
+ *   bsarec_backward_seq / _multi; train_sampler = 1 without a table. */
+#define BSAREC_TRAIN_NEG_MAX 8192
+#define BSAREC_TRAIN_NEG_SITE 0x4E454753u
+/* The popularity table of train_sampler = 1: int64[V] on the device, kept valid by the caller while the plan trains (null
+ * clears it).  < 0 on a plan without train_negatives > 0 and train_sampler = 1. */
+int bsarec_plan_set_train_sampler(bsarec_plan_t *plan, const int64_t *pop_cum);
 
 /* Byte offset of a named buffer inside the workspace, or -1. */
 long bsarec_buffer_offset(const bsarec_plan_t *plan, int buffer, int layer);
