@@ -46,7 +46,9 @@ class Config(C.Structure):
                 ("dw_tiled", C.c_int), ("splits", C.c_int), ("top_slabs", C.c_int), ("separate_embed", C.c_int),
                 ("separate_top", C.c_int), ("chain_kernels", C.c_int), ("x3_products", C.c_int),
                 # sampled-softmax training head (0 = full-catalogue CE)
-                ("train_negatives", C.c_int), ("train_sampler", C.c_int), ("train_no_logq", C.c_int)]
+                ("train_negatives", C.c_int), ("train_sampler", C.c_int), ("train_no_logq", C.c_int),
+                # lazy (sparse) Adam for the item table under the sampled head (0 = dense Adam)
+                ("train_lazy_adam", C.c_int)]
 
 
 TRAIN_FIELDS = ("train_negatives", "train_sampler", "train_no_logq")

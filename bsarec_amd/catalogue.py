@@ -40,8 +40,8 @@ class ShardedCatalogue:
     per-rank batch size (fixed: the staging table and the encoder plan are sized by it)."""
 
     def __init__(self, args, batch: int, group, device):
-        if int(getattr(args, "train_negatives", 0) or 0) > 0:
-            raise ValueError("ShardedCatalogue: catalogue-sharded training has no sampled-softmax head (train_negatives must be 0)")
+        if int(getattr(args, "train_negatives", 0) or 0) > 0 or getattr(args, "train_lazy_adam", False):
+            raise ValueError("ShardedCatalogue: catalogue-sharded training has no sampled-softmax head (train_negatives must be 0) and no lazy Adam")
         import torch.distributed as dist
         self.args, self.group, self.device, self.B = args, group, torch.device(device), int(batch)
         self.rank, self.W = dist.get_rank(group), dist.get_world_size(group)

@@ -11,6 +11,7 @@
 #include "catalogue_shard.h"
 #include "sampled_rank.h"
 #include "sampled_softmax.h"
+#include "lazy_adam.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -186,6 +187,9 @@ struct bsarec_plan {
     const int64_t* pop_cum = nullptr;          // bsarec_plan_set_train_sampler (train_sampler = 1)
     const int64_t* ssm_answers = nullptr;      // answers of the last sampled loss (the backward reads them)
     int ssm_nslab = 0, ssm_chunk = 0;          // split-K slabs of d(h_last) and the candidate columns per slab
+    // lazy Adam (cfg.train_lazy_adam = 1; lazy_adam.h): the touched-row marks and list, used while a step runs lazily
+    LazyRows lazy = {};
+    bool lazy_now = false;                     // set by bsarec_train_step / _indexed around their launches (LazyStep)
 };
 static ProfState* prof_of(bsarec_plan* p) { return &p->prof; }
 static bool bf_products_of(const bsarec_plan* p) { return p->bf_products; }
@@ -222,6 +226,7 @@ static int check_cfg(const bsarec_config_t& c) {
     if (c.train_negatives < 0 || c.train_negatives > BSAREC_TRAIN_NEG_MAX) return -17;
     if (c.train_sampler < 0 || c.train_sampler > 1 || c.train_no_logq < 0 || c.train_no_logq > 1) return -17;
     if (c.train_negatives > 0 && c.storage != 0) return -18;      // the sampled head is fp32 only
+    if (c.train_lazy_adam < 0 || c.train_lazy_adam > 1 || (c.train_lazy_adam && c.train_negatives == 0)) return -19;
     return 0;
 }
 
@@ -329,6 +334,11 @@ static void carve(bsarec_plan& p, char* base, size_t* total) {
         p.ssm_cand = cv.take<int>(Nn); p.ssm_corr = cv.take<float>(Nn);
         p.ssm_logits = cv.take<float>(B * (Nn + 1)); p.ssm_dlogits = cv.take<float>(B * (Nn + 1));
     }
+    if (c.train_lazy_adam) {                                     // (nothing without the flag)
+        p.lazy.cap = (int)std::min<long>(c.item_size, T + B + c.train_negatives);
+        p.lazy.d4 = (int)(d / 4);
+        p.lazy.mark = cv.take<int>(c.item_size); p.lazy.rows = cv.take<int>(p.lazy.cap); p.lazy.count = cv.take<int>(1);
+    }
     // (no guard pad: the direct weight-gradient kernels prefetch past a slice without predicates, but through buffer
     // descriptors sized to their operand -- dw_direct.h)
     *total = cv.off;
@@ -378,6 +388,10 @@ extern "C" int bsarec_plan_create(bsarec_plan_t** out, const bsarec_config_t* cf
     carve(*p, p->ws, &total);
     if (total > workspace_bytes) { delete p; return -12; }
     if (hipMemset(p->lookup_acc, 0, (size_t)cfg->item_size * cfg->hidden * sizeof(unsigned long long)) != hipSuccess) {
+        delete p; return -12;
+    }
+    if (cfg->train_lazy_adam && (hipMemset(p->lazy.mark, 0, (size_t)cfg->item_size * sizeof(int)) != hipSuccess ||
+                                 hipMemset(p->lazy.count, 0, sizeof(int)) != hipSuccess)) {
         delete p; return -12;
     }
 
@@ -1015,6 +1029,10 @@ static SsmP ssm_params(const bsarec_plan& p, const int64_t* answers) {
     const int dt = cdiv(c.hidden, SSM_TILE);
     P.tilesA = cdiv(c.train_negatives, SSM_TILE) * dt;
     P.tilesB = p.ssm_nslab * cdiv(c.batch, SSM_TILE) * dt;
+    if (p.lazy_now) {                          // lazy Adam step: reset the row count in the loss, mark T in the backward
+        P.lazy = p.lazy; P.ids32 = p.ids32; P.nids = p.T;
+        P.tilesM = (int)std::min<long>(cdiv((long)p.T + c.batch + c.train_negatives, ROW_THREADS), 64);
+    }
     return P;
 }
 
@@ -1155,7 +1173,7 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
         // zero: the final reduction writes the accumulator over it), and the slabs of d(h_last)
         SsmP P = ssm_params(*p, p->ssm_answers);
         const int tilesC = std::max(1, std::min(cdiv((long)B * d, ROW_THREADS), 64));
-        LAUNCH(ssm_bwd_kernel, dim3(P.tilesA + P.tilesB + tilesC), dim3(ROW_THREADS), 0, s, P);
+        LAUNCH(ssm_bwd_kernel, dim3(P.tilesA + P.tilesB + tilesC + P.tilesM), dim3(ROW_THREADS), 0, s, P);
         HIPCHK(hipGetLastError());
     } else if (direct_logits) {
         // fused shape: dE = dlogits^T . h_last (K = B rows, written straight into the gradient buffer) and the split-K
@@ -1470,9 +1488,15 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
         // (no empty blocks: flat block map); its extra last block closes the optimisation step when asked to
         // (the lookup-path sum of the item-table gradient joins its target here: after every scatter block has finished)
         LookupAcc la;
+        memset(&la, 0, sizeof(la));
         la.acc = p->lookup_acc; la.dst = p->lookup_grad ? p->lookup_grad : p->G.item_emb; la.n4 = (long)c.item_size * d / 4;
         la.nblocks = (int)std::min<long>(cdiv(la.n4, ROW_THREADS), 1024);
         la.dense_zero = (!p->ext_dy && p->loss_kind == 2) ? 1 : 0;
+        const bool lazy = p->lazy_now && !p->ext_dy && p->loss_kind == 2;
+        if (lazy) {                        // lazy Adam: the rows of T only, in a grid sized to the list's capacity
+            la.lazy = p->lazy;
+            la.nblocks = (int)std::min<long>(cdiv((long)p->lazy.cap * p->lazy.d4, ROW_THREADS), 1024);
+        }
         if (fuse_adam) {
             const bsarec_adam_t& a = *fuse_adam;
             AdamFuseP A;
@@ -1482,7 +1506,8 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
             A.shadow = (unsigned short*)a.shadow_bf16; A.shadow_from = a.shadow_bf16 ? a.shadow_from : a.n;
             A.item_off = p->G.item_emb - a.grads; A.item_n4 = (long)c.item_size * d / 4; A.lookup_acc = la.acc;
             A.dense_zero = la.dense_zero;
-            int ab = cdiv(A.item_n4, ROW_THREADS);
+            if (lazy) A.lazy = p->lazy;
+            int ab = lazy ? la.nblocks : cdiv(A.item_n4, ROW_THREADS);
             if (ab > 1024) ab = 1024;
             LAUNCH(reduce_adam_kernel, dim3(p->red_blocks + ab), dim3(ROW_THREADS), 0, s, p->pruned ? p->jobs_pruned : p->jobs,
                    p->blockmap, p->red_blocks, (const uint64_t*)p->state, A);
@@ -1546,6 +1571,39 @@ extern "C" int bsarec_adam_apply(const bsarec_adam_t* a, void* state, void* stre
     return adam_launch(*a, state, (hipStream_t)stream);
 }
 
+// Lazy Adam (cfg.train_lazy_adam): the flat arena must hold the item table (the rows of T are addressed through it), with
+// no data-parallel gradient sources and no bf16 shadow (the lazy head is single-GPU fp32).
+static int lazy_check(const bsarec_plan& p, const bsarec_adam_t& a) {
+    if (!p.cfg.train_lazy_adam) return 0;
+    if (a.grads2 || a.n_grad_srcs > 0 || a.shadow_bf16) return -24;
+    const long item = (long)p.cfg.item_size * p.cfg.hidden;
+    if (!p.G.item_emb || p.G.item_emb < a.grads) return -24;
+    const long off = p.G.item_emb - a.grads;
+    if (off + item > a.n || (off & 3)) return -24;
+    return 0;
+}
+
+// The plan-aware Adam of a lazy step (lazy_adam_kernel): dense over the arena without the item table, lazy over T.
+// Adam's t / bias corrections were advanced by the step's gradient reduction.
+static int lazy_adam_launch(const bsarec_plan& p, const bsarec_adam_t& a, hipStream_t s) {
+    LazyAdamP A;
+    memset(&A, 0, sizeof(A));
+    A.w = a.params; A.g = a.grads; A.m = a.exp_avg; A.v = a.exp_avg_sq;
+    A.n = a.n; A.item_off = p.G.item_emb - a.grads; A.item_n = (long)p.cfg.item_size * p.cfg.hidden;
+    A.b1 = a.beta1; A.b2 = a.beta2; A.eps = a.eps; A.wd = a.weight_decay; A.gscale = a.grad_scale;
+    A.T = p.lazy;
+    A.dense_blocks = (int)std::max<long>(1, std::min<long>(cdiv((A.n - A.item_n) / 4, ROW_THREADS), 2048));
+    const int lb = (int)std::min<long>(cdiv((long)p.lazy.cap * p.lazy.d4, ROW_THREADS), 1024);
+    LAUNCH(lazy_adam_kernel, dim3(A.dense_blocks + lb), dim3(ROW_THREADS), 0, s, (const uint64_t*)p.state, A);
+    return (int)hipGetLastError();
+}
+
+struct LazyStep {                              // a lazy plan's step runs lazily for the duration of one entry point
+    bsarec_plan* p;
+    explicit LazyStep(bsarec_plan* q) : p(q) { p->lazy_now = p->cfg.train_lazy_adam != 0; }
+    ~LazyStep() { p->lazy_now = false; }
+};
+
 extern "C" int bsarec_gather_batch(const int64_t* table, const int64_t* answers_table, const int64_t* perm, long n_samples,
                                    const void* cursor, int B, int L, int64_t* ids_out, int64_t* answers_out, void* stream) {
     if (!table || !answers_table || !perm || !cursor || !ids_out || !answers_out || B < 1 || L < 1) return -10;
@@ -1560,8 +1618,10 @@ extern "C" int bsarec_train_step_indexed(bsarec_plan_t* p, const int64_t* table,
     if (!p) return -10;
     RET(adam_check(a));
     RET(sampled_refusal(*p));
+    RET(lazy_check(*p, *a));
     hipStream_t s = (hipStream_t)stream;
     if (!table || !answers_table || !perm || !cursor || !ids_buf || !answers_buf) return -10;
+    LazyStep lazy(p);
     GatherP gp{table, answers_table, perm, n_samples, (const long long*)cursor, ids_buf, answers_buf};
     RET(forward_impl(p, ids_buf, 1, stream, gp, true));       // batch assembly rides in the embedding kernel
     RET(loss_impl(p, answers_buf, stream, false));
@@ -1571,7 +1631,7 @@ extern "C" int bsarec_train_step_indexed(bsarec_plan_t* p, const int64_t* table,
     if (can_fuse_adam(*p, *a) && !p->cfg.separate_embed)       // 7 launches: the last one reduces and updates
         return backward_impl(p, stream, tk, a);
     RET(backward_impl(p, stream, tk));
-    return adam_launch(*a, p->state, s);
+    return p->lazy_now ? lazy_adam_launch(*p, *a, s) : adam_launch(*a, p->state, s);
 }
 
 extern "C" int bsarec_grad_step_indexed(bsarec_plan_t* p, const int64_t* table, const int64_t* answers_table,
@@ -1579,6 +1639,7 @@ extern "C" int bsarec_grad_step_indexed(bsarec_plan_t* p, const int64_t* table, 
                                         int64_t* answers_buf, float lr, float b1, float b2, void* stream) {
     if (!p || !table || !answers_table || !perm || !cursor || !ids_buf || !answers_buf) return -10;
     RET(sampled_refusal(*p));
+    if (p->cfg.train_lazy_adam) return -22;    // a lazy plan's item-table update needs the step's T: its Adam runs inside the step
     GatherP gp{table, answers_table, perm, n_samples, (const long long*)cursor, ids_buf, answers_buf};
     RET(forward_impl(p, ids_buf, 1, stream, gp, true));
     RET(bsarec_loss(p, answers_buf, stream));
@@ -1591,6 +1652,18 @@ extern "C" int bsarec_train_step(bsarec_plan_t* p, const int64_t* ids, const int
     if (!p) return -10;
     RET(adam_check(a));
     RET(sampled_refusal(*p));
+    RET(lazy_check(*p, *a));
+    if (p->cfg.train_lazy_adam) {
+        // lazy: the gradient reduction's extra block advances Adam's t (as bsarec_adam_step's tick would), then the dense
+        // update of the rest of the arena and the lazy one of T in one launch
+        LazyStep lazy(p);
+        RET(bsarec_step_begin(p, stream));
+        RET(bsarec_forward_last(p, ids, 1, stream));
+        RET(bsarec_loss(p, answers, stream));
+        TickP tk = make_tick(p->state, 1, a->lr, a->beta1, a->beta2, nullptr, 0, nullptr, nullptr, 0, 0);
+        RET(backward_impl(p, stream, tk));
+        return lazy_adam_launch(*p, *a, (hipStream_t)stream);
+    }
     RET(bsarec_step_begin(p, stream));
     RET(bsarec_forward_last(p, ids, 1, stream));
     RET(bsarec_loss(p, answers, stream));

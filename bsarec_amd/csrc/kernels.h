@@ -7,6 +7,7 @@
 #include "common.h"
 
 #define ROW_THREADS 256
+#include "lazy_adam.h"
 
 // =============================================================================================
 // K1 embedding front-end: X0 = Drop(LN(E[ids] + Pos[t]))      src/model/_abstract_model.py:14-24
@@ -506,7 +507,8 @@ __device__ __forceinline__ float lookup_unfix(unsigned long long a) { return (fl
 // nothing to add, nothing to write back.
 // dense_zero: the item table has no dense part this step (sampled-softmax head: its rows are in the accumulator too), so
 // dst[i] = acc[i] is written for EVERY group, zero where the accumulator is
-struct LookupAcc { unsigned long long* acc; float* dst; long n4; int nblocks; int dense_zero; };
+// lazy.rows != null (lazy Adam, lazy_adam.h): only the rows of the step's list are flushed, dense_zero style (dst = acc)
+struct LookupAcc { unsigned long long* acc; float* dst; long n4; int nblocks; int dense_zero; LazyRows lazy; };
 __device__ __forceinline__ bool lookup_take(unsigned long long* acc, long i4, f32x4& add) {
     ulonglong2* a = reinterpret_cast<ulonglong2*>(acc + 4 * i4);
     const ulonglong2 x = a[0], y = a[1];
@@ -517,6 +519,15 @@ __device__ __forceinline__ bool lookup_take(unsigned long long* acc, long i4, f3
 }
 __device__ __forceinline__ void lookup_flush(const LookupAcc& la, long first, long stride) {
     f32x4 add;
+    if (la.lazy.rows) {
+        const int d4 = la.lazy.d4;
+        const long n = (long)min(*la.lazy.count, la.lazy.cap) * d4;
+        for (long k = first; k < n; k += stride) {
+            const long i = (long)la.lazy.rows[k / d4] * d4 + k % d4;
+            st4(la.dst + 4 * i, lookup_take(la.acc, i, add) ? add : f32x4{0, 0, 0, 0});
+        }
+        return;
+    }
     for (long i = first; i < la.n4; i += stride) {
         if (lookup_take(la.acc, i, add)) st4(la.dst + 4 * i, la.dense_zero ? add : ld4(la.dst + 4 * i) + add);
         else if (la.dense_zero) st4(la.dst + 4 * i, f32x4{0, 0, 0, 0});
@@ -826,6 +837,7 @@ struct AdamFuseP {
     long item_off, item_n4;            // the item table inside the flat arena: element offset, float4 count
     unsigned long long* lookup_acc;    // the lookup-path sum of the item-table gradient (fixed point), added here once
     int dense_zero;                    // LookupAcc.dense_zero: the gradient is the accumulator alone (not read, always stored)
+    LazyRows lazy;                     // lazy.rows != null: lazy Adam (lazy_adam.h) -- the item arm walks the rows of T only
 };
 __global__ void __launch_bounds__(ROW_THREADS)
 reduce_adam_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ blockmap, int nblocks,
@@ -870,6 +882,23 @@ reduce_adam_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ b
         return;
     }
     const long nb = gridDim.x - nblocks;
+    if (A.lazy.rows) {
+        // lazy Adam: the rows of T (marked by this step's ssm_bwd_kernel) -- their accumulator rows taken and zeroed, their
+        // gradient rows written (dense_zero: the accumulator alone), updated once, unmarked
+        const int d4 = A.lazy.d4;
+        const long n = (long)min(*A.lazy.count, A.lazy.cap) * d4;
+        for (long k = (long)(blockIdx.x - nblocks) * ROW_THREADS + threadIdx.x; k < n; k += nb * ROW_THREADS) {
+            const int r = A.lazy.rows[k / d4], q = (int)(k % d4);
+            const long i = (long)r * d4 + q, o = A.item_off + 4 * i;
+            f32x4 wi = ld4(A.w + o), mi = ld4(A.m + o), vi = ld4(A.v + o), gi = {0, 0, 0, 0};
+            if (A.lookup_acc) lookup_take(A.lookup_acc, i, gi);
+            st4(A.g + o, gi);
+            lazy_adam4(wi, mi, vi, gi, A.b1, A.b2, A.eps, A.wd, step_size, bc2s);
+            st4(A.w + o, wi); st4(A.m + o, mi); st4(A.v + o, vi);
+            if (q == 0) A.lazy.mark[r] = 0;
+        }
+        return;
+    }
     for (long i = (long)(blockIdx.x - nblocks) * ROW_THREADS + threadIdx.x; i < A.item_n4; i += nb * ROW_THREADS) {
         const long o = A.item_off + 4 * i;
         f32x4 wi = ld4(A.w + o), mi = ld4(A.m + o), vi = ld4(A.v + o);

@@ -1,0 +1,108 @@
+// Lazy (sparse) Adam for the item table under the sampled-softmax head (bsarec_config_t.train_lazy_adam, include/bsarec_hip.h).
+// A step updates only the item rows it touches -- T = the looked-up ids != 0, the answers and the N candidates -- so the
+// item table's share of the optimiser costs O(|T| d) instead of O(V d).  The pieces, all on the device (a captured step
+// replays with a fresh T):
+//   LazyRows       a per-plan int32[V] mark array (0 between steps) and a compact list of the marked rows with its count.
+//                  The count is reset by ssm_logits_kernel (the step's loss, before anything marks); ssm_bwd_kernel marks
+//                  (lazy_mark_wave: the first marker of a row appends it, one atomic per wave); the step's last item-table
+//                  pass clears the marks of the listed rows again.
+//   lookup flush   (kernels.h, LookupAcc.lazy) the fixed-point accumulator -> the gradient rows of T, not the V rows
+//   lazy Adam      reduce_adam_kernel's item arm (fused indexed step, kernels.h) or lazy_adam_kernel here (every other step
+//                  shape): the arithmetic of adam_kernel on the rows of T only (lazy_adam4)
+// Rows are listed in arbitrary order; each row's update is independent of the others, so the step stays bit-deterministic.
+// The restatement in numpy is tests/lazy_adam_ref.py.
+#pragma once
+#include "common.h"
+
+struct LazyRows {
+    int* mark;           // [V]: 1 while the row is in this step's list, else 0
+    int* rows;           // [cap]: the touched rows of the step, in arbitrary order
+    int* count;          // rows listed so far (reset once per step)
+    int cap;             // min(V, B L + B + N): no step can touch more distinct rows
+    int d4;              // float4 groups per row (d / 4)
+};
+
+// Mark row r (valid lanes only); the first marker of the step appends it to the list.  Called by all 64 lanes of a wave
+// together (the ballot): one global atomic per wave for the slots (Guideline 12: wave-aggregated atomics).
+__device__ __forceinline__ void lazy_mark_wave(const LazyRows& T, int r, bool valid) {
+    const bool first = valid && atomicExch(T.mark + r, 1) == 0;
+    const unsigned long long won = __ballot(first);
+    if (won == 0ull) return;                                      // wave-uniform
+    const int lane = threadIdx.x & 63, leader = __builtin_ctzll(won);
+    int base = 0;
+    if (lane == leader) base = atomicAdd(T.count, __popcll(won));
+    base = __shfl(base, leader);
+    if (first) {
+        const int slot = base + __popcll(won & ((1ull << lane) - 1ull));
+        if (slot < T.cap) T.rows[slot] = r;                       // (never false: at most cap distinct rows are marked)
+    }
+}
+
+// The marking role over ids32 [nids] (0 = padding, not marked), answers [B] (clamped to [0, V)) and cand [N]: element e of
+// the concatenation, grid-stride from wave-aligned starts so that every lane of a wave takes the same trips.
+__device__ __forceinline__ void lazy_mark_role(const LazyRows& T, const int* __restrict__ ids32, long nids,
+                                               const int64_t* __restrict__ answers, int B, const int* __restrict__ cand, int N,
+                                               int V, int blk, int nblk) {
+    const long total = nids + B + N, stride = (long)nblk * ROW_THREADS;
+    for (long e0 = (long)blk * ROW_THREADS + (threadIdx.x & ~63); e0 < total; e0 += stride) {
+        const long e = e0 + (threadIdx.x & 63);
+        int r = 0;
+        bool valid = e < total;
+        if (valid) {
+            if (e < nids) { r = ids32[e]; valid = r != 0; }
+            else if (e < nids + B) { const long long a = answers[e - nids]; r = a < 0 ? 0 : (a >= V ? V - 1 : (int)a); }
+            else { r = cand[e - nids - B]; r = r < 0 ? 0 : (r >= V ? V - 1 : r); }
+        }
+        lazy_mark_wave(T, r, valid);
+    }
+}
+
+// One float4 group of Adam, the arithmetic of adam_kernel / reduce_adam_kernel's item arm expression for expression.
+__device__ __forceinline__ void lazy_adam4(f32x4& wi, f32x4& mi, f32x4& vi, f32x4 gi, float b1, float b2, float eps, float wd,
+                                           float step_size, float bc2s) {
+    if (wd != 0.f) gi += wd * wi;
+    mi = b1 * mi + (1.0f - b1) * gi;
+    vi = b2 * vi + (1.0f - b2) * gi * gi;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wi[k] -= step_size * (mi[k] / (sqrtf(vi[k]) / bc2s + eps));
+}
+
+// The plan-aware Adam of a lazy step whose update is not fused into the gradient reduction: blocks [0, dense_blocks) run
+// adam_kernel's update over the arena without the item table ([0, item_off) and [item_off + item_n, n)), the others the
+// rows of T (their gradient rows were written by the lookup flush).  t / bias corrections: already advanced (state[3]).
+struct LazyAdamP {
+    float *w; const float* g; float *m, *v;
+    long n, item_off, item_n;            // arena length, the item table's element offset and length (all % 4 == 0)
+    float b1, b2, eps, wd, gscale;
+    int dense_blocks;
+    LazyRows T;
+};
+__global__ void __launch_bounds__(ROW_THREADS)
+lazy_adam_kernel(const uint64_t* __restrict__ state, const LazyAdamP A) {
+    const float* f = reinterpret_cast<const float*>(state + 3);
+    const float step_size = f[0], bc2s = f[1];
+    if ((int)blockIdx.x < A.dense_blocks) {
+        const long lo4 = A.item_off / 4, skip4 = A.item_n / 4, n4 = (A.n - A.item_n) / 4;
+        for (long j = (long)blockIdx.x * ROW_THREADS + threadIdx.x; j < n4; j += (long)A.dense_blocks * ROW_THREADS) {
+            const long o = 4 * (j < lo4 ? j : j + skip4);
+            f32x4 gi = ld4(A.g + o);
+            gi = gi * A.gscale;
+            f32x4 wi = ld4(A.w + o), mi = ld4(A.m + o), vi = ld4(A.v + o);
+            lazy_adam4(wi, mi, vi, gi, A.b1, A.b2, A.eps, A.wd, step_size, bc2s);
+            st4(A.w + o, wi); st4(A.m + o, mi); st4(A.v + o, vi);
+        }
+        return;
+    }
+    const int nb = gridDim.x - A.dense_blocks, d4 = A.T.d4;
+    const long n = (long)min(*A.T.count, A.T.cap) * d4;
+    for (long k = (long)(blockIdx.x - A.dense_blocks) * ROW_THREADS + threadIdx.x; k < n; k += (long)nb * ROW_THREADS) {
+        const int r = A.T.rows[k / d4], q = (int)(k % d4);
+        const long o = A.item_off + 4 * ((long)r * d4 + q);
+        f32x4 gi = ld4(A.g + o);
+        gi = gi * A.gscale;
+        f32x4 wi = ld4(A.w + o), mi = ld4(A.m + o), vi = ld4(A.v + o);
+        lazy_adam4(wi, mi, vi, gi, A.b1, A.b2, A.eps, A.wd, step_size, bc2s);
+        st4(A.w + o, wi); st4(A.m + o, mi); st4(A.v + o, vi);
+        if (q == 0) A.T.mark[r] = 0;                               // the last pass of the step over T: unmark
+    }
+}

@@ -33,6 +33,9 @@ struct SsmP {
     float* slab; int nslab, chunk;        // dh split-K slabs [nslab][B][d]; slab s sums candidate columns [s chunk, (s+1) chunk)
     unsigned long long* acc;              // [V][d] fixed-point item-table accumulator (kernels.h, LookupAcc)
     int tilesA, tilesB;                   // ssm_bwd_kernel: workgroups of the first two roles
+    // lazy Adam step (lazy.rows != null, lazy_adam.h): ssm_logits_kernel resets the row count, and the last tilesM workgroups
+    // of ssm_bwd_kernel mark the touched rows -- ids32 [nids] (!= 0), the answers and the candidates
+    LazyRows lazy; const int* ids32; long nids; int tilesM;
 };
 
 // draw j of the step (0 <= j < N) -> item in [1, V) (uniform) or [0, V) with count > 0 (popularity)
@@ -92,6 +95,7 @@ __global__ void __launch_bounds__(ROW_THREADS) ssm_logits_kernel(const SsmP P) {
     __shared__ float c_s[SSM_TILE];
     __shared__ long long ans_s[SSM_TILE];
     const int tid = threadIdx.x, col0 = blockIdx.x * SSM_TILE, row0 = blockIdx.y * SSM_TILE;
+    if (P.lazy.rows && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *P.lazy.count = 0;     // before ssm_bwd_kernel marks
     if (tid < SSM_TILE) {
         const uint64_t seed = P.state[0];
         const int j = col0 + tid;
@@ -167,7 +171,8 @@ __global__ void __launch_bounds__(ROW_THREADS) ssm_ce_kernel(const SsmP P) {
 }
 
 // roles by blockIdx.x: [0, tilesA) dE of candidate tiles (64 candidates x 64 dims), [tilesA, tilesA + tilesB) dh slabs
-// (64 rows x 64 dims x slab), the rest dE of the answer columns (grid-stride over B d)
+// (64 rows x 64 dims x slab), then dE of the answer columns (grid-stride over B d), and the last tilesM (0 unless a lazy Adam
+// step) mark the step's touched item rows (lazy_mark_role)
 __global__ void __launch_bounds__(ROW_THREADS) ssm_bwd_kernel(const SsmP P) {
     __shared__ __attribute__((aligned(16))) float As[SSM_KS][SSM_LDP];
     __shared__ __attribute__((aligned(16))) float Bs[SSM_KS][SSM_LDP];
@@ -234,7 +239,12 @@ __global__ void __launch_bounds__(ROW_THREADS) ssm_bwd_kernel(const SsmP P) {
         return;
     }
     blk -= P.tilesB;
-    const long n = (long)B * d, nthr = (long)(gridDim.x - P.tilesA - P.tilesB) * ROW_THREADS;
+    const int tilesC = gridDim.x - P.tilesA - P.tilesB - P.tilesM;
+    if (blk >= tilesC) {
+        lazy_mark_role(P.lazy, P.ids32, P.nids, P.answers, B, P.cand, P.N, P.V, blk - tilesC, P.tilesM);
+        return;
+    }
+    const long n = (long)B * d, nthr = (long)tilesC * ROW_THREADS;
     for (long e = (long)blk * ROW_THREADS + tid; e < n; e += nthr) {
         const int b = (int)(e / d), k = (int)(e % d);
         int a = (int)P.answers[b];

@@ -129,6 +129,8 @@ def parse_args(argv=None):
                    help="how the training candidates are drawn: uniform over the catalogue (default) or by training popularity")
     p.add_argument("--train_no_logq", default=argparse.SUPPRESS, action="store_true",
                    help="no logQ correction of the sampled logits")
+    p.add_argument("--train_lazy_adam", default=argparse.SUPPRESS, action="store_true",
+                   help="lazy (sparse) Adam for the item table: each step updates only the rows it touches (needs --train_negatives)")
     # DuoRec's flags (src/utils.py:106-111)
     p.add_argument("--tau", default=1.0, type=float)
     p.add_argument("--lmd", default=0.1, type=float)

@@ -81,6 +81,7 @@ class _Plan:
         self.options = {k: int(getattr(self.cfg, k)) for k in L.OPTION_FIELDS}
         for k in L.TRAIN_FIELDS:                        # the model's training head (0: full-catalogue CE)
             setattr(self.cfg, k, model.train_head[k])
+        self.cfg.train_lazy_adam = int(model.lazy_adam)
         nbytes = lib.bsarec_workspace_bytes(C.byref(self.cfg))
         if nbytes == 0:
             raise ValueError("configuration not supported by libbsarec_hip (see include/bsarec_hip.h limits: "
@@ -256,6 +257,13 @@ class BSARecModel(nn.Module):
         if getattr(args, "storage", None) == "bf16":
             self.options["storage"] = 1
         self.train_head = train_head_of(args)
+        # lazy (sparse) Adam for the item table: the steps update only the item rows they touch (include/bsarec_hip.h)
+        self.lazy_adam = bool(getattr(args, "train_lazy_adam", False))
+        if self.lazy_adam:
+            if not self.sampled_softmax_ok:
+                raise ValueError(f"{type(self).__name__}: train_lazy_adam needs BSARec's sampled-softmax head")
+            if self.train_head["train_negatives"] == 0:
+                raise ValueError("train_lazy_adam needs the sampled-softmax head (train_negatives > 0)")
         if self.train_head["train_negatives"] > 0:
             if not self.sampled_softmax_ok:
                 raise ValueError(f"{type(self).__name__} has its own loss head: train_negatives must be 0")
@@ -643,11 +651,16 @@ class BSARecModel(nn.Module):
     def adam_step(self, grad_scale: float = 1.0, tick: bool = True, grad_srcs=None):
         """Fused Adam over the flat arenas (after an external gradient exchange, or -- ``grad_srcs`` -- reading every
         rank's gradient arena itself)."""
+        if self.lazy_adam:
+            raise ValueError("adam_step: a lazy-Adam model updates inside train_step / train_step_indexed (a plan-less "
+                             "update cannot know which item rows the step touched)")
         ad = self._adam_struct(grad_scale, grad_srcs)
         fn = L.load().bsarec_adam_step if tick else L.load().bsarec_adam_apply
         L.check(fn(C.byref(ad), self._state.data_ptr(), self._stream()), "bsarec_adam_step" if tick else "bsarec_adam_apply")
 
     def grad_views(self) -> "OrderedDict[str, torch.Tensor]":
+        """The gradient arena per tensor.  After a lazy-Adam step (train_lazy_adam) the item table's rows the step touched
+        hold this step's gradient and every other row keeps what it held before."""
         return OrderedDict((k, self._garena[o:o + n].view(shp)) for k, (o, n, shp) in self._slices.items())
 
 

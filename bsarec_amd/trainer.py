@@ -84,6 +84,8 @@ def check_train_head(model, args, train_dataloader, process_group=None):
     head = getattr(model, "train_head", None) or {}
     if head.get("train_negatives", 0) == 0:
         return
+    if process_group is not None and getattr(model, "lazy_adam", False):
+        raise ValueError("train_lazy_adam: data-parallel training has no sampled-softmax head and no lazy Adam")
     if process_group is not None:
         raise ValueError("train_negatives > 0: data-parallel training has no sampled-softmax head")
     if head.get("train_sampler", 0) == 1:

@@ -79,6 +79,8 @@ typedef struct {
                            * bsarec_grad_step_indexed); bsarec_logits stays full-catalogue.  fp32 only (storage = 1 is refused) */
     int train_sampler;    /* sampled head: 0 uniform over [1, V); 1 popularity (bsarec_plan_set_train_sampler) */
     int train_no_logq;    /* sampled head: 1 = no logQ correction */
+    int train_lazy_adam;  /* sampled head: 1 = lazy (sparse) Adam for the item table in bsarec_train_step and
+                           * bsarec_train_step_indexed (below); 0 (default): dense Adam.  Needs train_negatives > 0 */
 } bsarec_config_t;
 
 /* The 19 tensors of one BSARecBlock, in state_dict order (+ the sibling model's filter weight)
@@ -184,11 +186,32 @@ int bsarec_plan_set_dense_grad_hook(bsarec_plan_t *plan, bsarec_hook_t hook, voi
  *   Backward (bsarec_backward and the steps): g = (softmax(x_b) - onehot_0) / B; d(h_b) = sum_c g_bc E[c]; dE[c] += g_bc h_b for
  *   every candidate column, the answers included, summed as 64-bit fixed point (2^-40) so that the step is bit-deterministic;
  *   rows that are no candidate get no head gradient (the item table's gradient is then the head rows plus the lookup rows;
- *   Adam stays dense).
+ *   Adam stays dense unless train_lazy_adam = 1).
  *   Refusals (< 0 before anything is launched): storage = 1 (at plan creation); a dense-gradient hook or lookup_grad;
  *   bsarec_backward_seq / _multi; train_sampler = 1 without a table. */
 #define BSAREC_TRAIN_NEG_MAX 8192
 #define BSAREC_TRAIN_NEG_SITE 0x4E454753u
+/* Lazy (sparse) Adam for the item table (cfg.train_lazy_adam = 1, with the sampled head), the optimiser of torch.optim.SparseAdam
+ * and of LazyAdam: a step's update of the item table costs what the rows it touches cost, not V d.
+ *   Touched set of a step: T = { ids[b][l] != 0 } u { answers[b] } u { n_0 .. n_N-1 } (BSAREC_BUF_TRAIN_CAND), at most
+ *   min(V, B L + B + N) rows; ids and answers clamped to [0, V) as the kernels read them.
+ *   Row r in T: g_r = the item-table gradient row of the sampled head (candidate and answer rows plus lookup rows, the
+ *   fixed-point sum converted to float), then the arithmetic of the dense update with the same t and bias corrections
+ *   (state[3]): g += wd w when weight_decay != 0, m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2,
+ *   w -= step_size m / (sqrt(v) / bc2s + eps).  Once per step however often r occurs in T, and even when g_r is exactly 0:
+ *   presence in T counts, not the value.
+ *   Row r not in T: w, m and v unchanged bit for bit (no weight decay), its gradient row not written.
+ *   Every other tensor of the arena: the dense update, as without the flag.
+ *   Gradient arena after a lazy step: item rows of T hold this step's gradient; other item rows keep what they held before.
+ *   T, its size and its resets live on the device: a captured step replays with a fresh T.  Steps stay bit-deterministic
+ *   (T is listed in arbitrary order; each row's update is independent of the others).
+ *   Only bsarec_train_step and bsarec_train_step_indexed update lazily; bsarec_loss / bsarec_backward on such a plan compute
+ *   and store exactly what they do without the flag.  The plan-less bsarec_adam_step / bsarec_adam_apply are unchanged.
+ *   Refusals (< 0 before anything is launched): train_lazy_adam = 1 with train_negatives = 0 (at plan creation; the workspace
+ *   size is 0); bsarec_grad_step_indexed on such a plan; a step whose bsarec_adam_t does not hold the item table inside
+ *   its flat arena, or has grads2, grad_srcs or shadow_bf16.
+ *   Workspace: int32[V] row marks + int32[min(V, B L + B + N)] row list; nothing without the flag. */
+
 /* The popularity table of train_sampler = 1: int64[V] on the device, kept valid by the caller while the plan trains (null
  * clears it).  < 0 on a plan without train_negatives > 0 and train_sampler = 1. */
 int bsarec_plan_set_train_sampler(bsarec_plan_t *plan, const int64_t *pop_cum);

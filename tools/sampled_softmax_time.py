@@ -2,6 +2,7 @@
 time of the head's loss launches alone.  One configuration per process, so that a caller can give each its own time limit:
 
     python tools/sampled_softmax_time.py --V 100003 --neg 1024      # --neg 0: full-catalogue CE
+    python tools/sampled_softmax_time.py --V 100003 --neg 1024 --lazy   # lazy Adam for the item table (train_lazy_adam)
 
 Prints one JSON line.  B = 256, d = 64, L = 50, 2 layers, 2 heads, dropout 0.5 (the bench shape); eager bsarec_train_step."""
 import argparse
@@ -22,12 +23,14 @@ def main():
     ap.add_argument("--neg", type=int, default=0)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--lazy", action="store_true", help="lazy (sparse) Adam for the item table (needs --neg > 0)")
     a = ap.parse_args()
     from bsarec_amd import BSARecModel
     B, L = 256, 50
     args = argparse.Namespace(item_size=a.V, hidden_size=64, max_seq_length=L, batch_size=B, hidden_dropout_prob=0.5,
                               attention_probs_dropout_prob=0.5, num_hidden_layers=2, num_attention_heads=2, hidden_act="gelu",
-                              initializer_range=0.02, c=3, alpha=0.9, seed=42, train_negatives=a.neg)
+                              initializer_range=0.02, c=3, alpha=0.9, seed=42, train_negatives=a.neg,
+                              train_lazy_adam=a.lazy)
     m = BSARecModel(args).cuda()
     m.configure_adam()
     m.train()
@@ -54,7 +57,7 @@ def main():
     t1.record()
     torch.cuda.synchronize()
     loss_ms = t0.elapsed_time(t1) / a.steps
-    print(json.dumps({"V": a.V, "neg": a.neg, "ms_per_step": round(step_ms, 4), "head_loss_ms": round(loss_ms, 4),
+    print(json.dumps({"V": a.V, "neg": a.neg, "lazy": a.lazy, "ms_per_step": round(step_ms, 4), "head_loss_ms": round(loss_ms, 4),
                       "head_loss_share": round(loss_ms / step_ms, 3)}), flush=True)
 
 
