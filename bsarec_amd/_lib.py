@@ -167,6 +167,9 @@ EXPORTS = {
                                    C.c_void_p, C.c_void_p]),
     "bsarec_sampled_rank": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 +
                             [C.c_int, C.c_uint64, C.c_uint32] + [C.c_void_p] * 4),
+    "bsarec_topk_full_workspace_bytes": (C.c_long, [C.c_int] * 5),
+    "bsarec_topk_full": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 +
+                         [C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

@@ -1,4 +1,5 @@
 // MI355X (gfx950) BSARec training hot path: launch plan + C ABI.  See include/bsarec_hip.h.
+#include <cmath>
 #include "../../include/bsarec_hip.h"
 #include "../../include/bsarec_shard.h"
 #include "epilogues.h"
@@ -10,6 +11,7 @@
 #include "comm.h"
 #include "catalogue_shard.h"
 #include "sampled_rank.h"
+#include "full_rank.h"
 #include "sampled_softmax.h"
 #include "lazy_adam.h"
 
@@ -1698,6 +1700,75 @@ extern "C" int bsarec_sampled_rank(const float* h, long ldh, const float* item_e
     if ((uintptr_t)item_emb % 16 != 0) return -10;               // float4 row loads
     hipLaunchKernelGGL(sampled_rank_kernel, dim3(B), dim3(ROW_THREADS), 0, (hipStream_t)stream, h, ldh, item_emb, V, d, users, answers,
                        indptr, indices, pop_cum, n_neg, (uint32_t)seed, (uint32_t)(seed >> 32), tag, rank_out, cand_out, score_out);
+    return (int)hipGetLastError();
+}
+
+// Full-catalogue top-k without the score matrix (full_rank.h).  Sizes of one call: s sampled columns per row (a function of
+// k and V only), cap list entries per row (cand_cap, or by default about 4 k V / s: expected survivors ~ k V / s = cap / 4); s ~ 4 sqrt(k V).
+struct FrShape { long s, stride, cap; };
+static bool fr_shape(int B, int V, int d, int k, int cand_cap, FrShape* out) {
+    if (B < 1 || k < 1 || k > BSAREC_TOPK_MAX || V < k || d < 4 || d > 256 || d % 4 != 0) return false;
+    if (cand_cap < 0 || (cand_cap > 0 && cand_cap < k) || cand_cap > (1 << 30)) return false;
+    const long kv = (long)k * V;
+    long s = 4 * (long)std::sqrt((double)kv);
+    if (s < 4L * k) s = 4L * k;
+    if (s > V) s = V;
+    long cap = cand_cap;
+    if (cap == 0) {
+        cap = (4 * kv + s - 1) / s;
+        cap = (cap + 255) / 256 * 256;
+        if (cap < k) cap = k;
+    }
+    out->s = s; out->stride = V / s; out->cap = cap;
+    return true;
+}
+static long fr_align(long x) { return (x + 255) / 256 * 256; }
+
+extern "C" long bsarec_topk_full_workspace_bytes(int B, int V, int d, int k, int cand_cap) {
+    FrShape f;
+    if (!fr_shape(B, V, d, k, cand_cap, &f)) return -10;
+    return fr_align((long)B * 8) + fr_align((long)B * 4) + fr_align((long)B * f.s * 4) + (long)B * f.cap * 8;
+}
+
+extern "C" int bsarec_topk_full(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* users,
+                                const int64_t* indptr, const int64_t* indices, int k, int cand_cap, void* workspace,
+                                long workspace_bytes, int64_t* out_idx, float* out_val, void* stream) {
+    static_assert(BSAREC_TOPK_MAX == TOPK_MAX && ROW_THREADS == 256 && FR_ROWS == 128, "full_rank.h: the header's limits");
+    FrShape f;
+    if (!fr_shape(B, V, d, k, cand_cap, &f)) return -10;
+    if (!h || !item_emb || !workspace || !out_idx || ldh < d || (indptr && (!users || !indices))) return -10;
+    if ((uintptr_t)h % 16 != 0 || (uintptr_t)item_emb % 16 != 0 || (uintptr_t)workspace % 16 != 0) return -10;
+    if (workspace_bytes < bsarec_topk_full_workspace_bytes(B, V, d, k, cand_cap)) return -10;
+    char* ws = (char*)workspace;
+    unsigned long long* tau = (unsigned long long*)ws;           ws += fr_align((long)B * 8);
+    unsigned* count = (unsigned*)ws;                             ws += fr_align((long)B * 4);
+    unsigned* skeys = (unsigned*)ws;                             ws += fr_align((long)B * f.s * 4);
+    unsigned long long* list = (unsigned long long*)ws;
+    const int cap = (int)f.cap;
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = (B + FR_ROWS - 1) / FR_ROWS, nblk = (V + FR_ITEMS - 1) / FR_ITEMS;
+    int groups = (1024 + tiles - 1) / tiles;                    // about 1024 workgroups over the (row tile x item) grid
+    if (groups > nblk) groups = nblk;
+    const size_t smem = (size_t)FR_ROWS * (d + 4) * sizeof(float);
+    static bool attr = false;                                    // up to 133 KB of the 160 KB LDS (d = 256)
+    if (!attr) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(full_rank_filter_kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)FR_ROWS * 260 * sizeof(float)));
+        if (e != hipSuccess) return (int)e;
+        attr = true;
+    }
+    hipLaunchKernelGGL(full_rank_sample_kernel, dim3(B), dim3(ROW_THREADS), 0, st, h, ldh, item_emb, V, d, users, indptr, indices,
+                       k, (int)f.s, (int)f.stride, skeys, tau, count);
+    for (int round = 0; round <= FR_ROUNDS; ++round) {
+        if (round > 0)
+            hipLaunchKernelGGL(full_rank_rethreshold_kernel, dim3(B), dim3(ROW_THREADS), 0, st, k, cap, tau, count, list);
+        hipLaunchKernelGGL(full_rank_filter_kernel, dim3(tiles, groups), dim3(ROW_THREADS), smem, st, h, ldh, item_emb, B, V, d, cap,
+                           tau, count, list);
+    }
+    hipLaunchKernelGGL(full_rank_select_kernel, dim3(B), dim3(ROW_THREADS), 0, st, V, k, cap, users, indptr, indices, count, list,
+                       out_idx, out_val);
+    hipLaunchKernelGGL(full_rank_fallback_kernel, dim3(B), dim3(ROW_THREADS), 0, st, h, ldh, item_emb, V, d, k, cap, users, indptr,
+                       indices, count, out_idx, out_val);
     return (int)hipGetLastError();
 }
 

@@ -121,6 +121,10 @@ def parse_args(argv=None):
     p.add_argument("--eval_sampler", default=argparse.SUPPRESS, choices=("uniform", "popularity"),
                    help="how the negatives are drawn: uniform over the catalogue (default) or by training-set popularity")
     p.add_argument("--eval_seed", default=argparse.SUPPRESS, type=seed_value, help="seed of the negative draws (default: --seed)")
+    # not a reference flag: how the full ranking is computed -- dense (full_logits + bsarec_topk_seen, the default) or fused
+    # (bsarec_topk_full: no B x V score matrix, the same lists).  Absent unless given, as the --eval_* flags above
+    p.add_argument("--eval_full_rank", default=argparse.SUPPRESS, choices=("dense", "fused"),
+                   help="full-ranking path: dense score matrix + top-k (default) or fused scoring + top-k without the matrix")
     # not reference flags: the sampled-softmax training head (the answer against N candidates shared by the batch, logQ-corrected)
     # instead of the full-catalogue cross-entropy.  Absent unless given (argparse.SUPPRESS), as the --eval_* flags are
     p.add_argument("--train_negatives", default=argparse.SUPPRESS, type=train_negatives_count,
@@ -139,6 +143,8 @@ def parse_args(argv=None):
     p.add_argument("--sim", default="dot", type=str)
     args = p.parse_args(argv)
     n = getattr(args, "eval_negatives", 0)
+    if n > 0 and hasattr(args, "eval_full_rank"):
+        p.error("--eval_full_rank: applies to the full ranking, not to --eval_negatives > 0")
     if n > 0 and args.extra_ks and max(args.extra_ks) > n + 1:
         p.error(f"--extra_ks: cutoff {max(args.extra_ks)} exceeds the {n + 1} candidates of --eval_negatives {n}")
     return args

@@ -624,7 +624,10 @@ class Trainer:
         for batch in dataloader:
             batch = tuple(t.to(self.device, non_blocking=True) for t in batch)
             user_ids, input_ids, answers, _, _ = batch
-            preds.append(self.topk_after_seen(user_ids, input_ids, k=depth))
+            if getattr(self.args, "eval_full_rank", "dense") == "fused":
+                preds.append(self.topk_full(user_ids, input_ids, k=depth))
+            else:
+                preds.append(self.topk_after_seen(user_ids, input_ids, k=depth))
             answers_all.append(answers)
         return self.get_full_sort_score(epoch, torch.cat(answers_all), torch.cat(preds))
 
@@ -642,6 +645,40 @@ class Trainer:
                                           indptr.data_ptr(), indices.data_ptr(), k, pred.data_ptr(), None,
                                           torch.cuda.current_stream(self.device).cuda_stream), "bsarec_topk_seen")
         return (pred, scores) if return_scores else pred
+
+    def topk_full(self, user_ids, input_ids, k: int = 20, return_scores: bool = False):
+        """topk_after_seen without the B x V score matrix (``--eval_full_rank fused``): ``bsarec_topk_full`` scores every item
+        from the last position's hidden state on the fly and returns the same ids (and, with ``return_scores``, the same
+        fp32 scores, 0 for seen items) in the same order.  Working memory: a cached workspace of O(B (k + candidates))."""
+        from . import _lib as L
+        V = int(self.args.item_size)
+        if not 1 <= k <= min(L.TOPK_MAX, V):
+            raise ValueError(f"topk_full: k = {k}, expected 1..{min(L.TOPK_MAX, V)}")
+        h = self.model.last_hidden(input_ids)
+        if h.dtype != torch.float32 or h.stride(1) != 1 or h.data_ptr() % 16 or h.stride(0) % 4:
+            h = h.float().contiguous()
+        E = self.model.item_embeddings.weight.detach()
+        if E.dtype != torch.float32 or not E.is_contiguous() or E.data_ptr() % 16:
+            E = E.float().contiguous().clone()
+        B, d = h.shape
+        indptr, indices = self._seen_csr()
+        users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
+        lib = L.load()
+        key = (B, V, d, k)
+        ws = getattr(self, "_full_rank_ws", {}).get(key)
+        if ws is None:
+            nbytes = lib.bsarec_topk_full_workspace_bytes(B, V, d, k, 0)
+            if nbytes < 0:
+                raise ValueError(f"topk_full: unsupported shape B={B} V={V} d={d} k={k}")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._full_rank_ws = {key: ws}
+        pred = torch.empty(B, k, dtype=torch.int64, device=self.device)
+        val = torch.empty(B, k, dtype=torch.float32, device=self.device) if return_scores else None
+        L.check(lib.bsarec_topk_full(h.data_ptr(), h.stride(0), E.data_ptr(), B, V, d, users.data_ptr(), indptr.data_ptr(),
+                                     indices.data_ptr(), k, 0, ws.data_ptr(), ws.numel(), pred.data_ptr(),
+                                     val.data_ptr() if val is not None else None,
+                                     torch.cuda.current_stream(self.device).cuda_stream), "bsarec_topk_full")
+        return (pred, val) if return_scores else pred
 
     def sampled_ranks(self, user_ids, input_ids, answers, return_candidates: bool = False, tag: int = 1):
         """Sampled-candidate evaluation of one batch: each answer against args.eval_negatives = N items the user has not seen,

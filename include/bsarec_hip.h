@@ -362,6 +362,29 @@ int bsarec_sampled_rank(const float *h, long ldh, const float *item_emb, int B, 
                         int n_neg, uint64_t seed, uint32_t tag, int32_t *rank_out, int64_t *cand_out, float *score_out,
                         void *stream);
 
+/* Full-catalogue top-k without the B x V score matrix: opt-in beside bsarec_logits + bsarec_topk_seen, same result.
+ *   Scores: s(b, j) = acc after acc = 0, acc = fmaf(h[b * ldh + i], item_emb[j * d + i], acc) for i = 0 .. d-1 in fp32 --
+ *   an fmaf chain in ascending i, which v_mfma_f32_32x32x2_f32 computes bit for bit.  A score depends only on those two rows:
+ *   not on B, V, k, cand_cap, the row's or the item's position, the workspace or the launch.
+ *   Result: the seen items of row b (CSR row users[b] of indptr / indices; indptr == NULL: none; entries outside [0, V) are
+ *   ignored) score 0.0, not -inf, exactly as in bsarec_topk_seen.  out_idx[b][0..k) = the top k under bsarec_topk_seen's total
+ *   order (NaN above +inf and all NaNs equal, -0 equal to +0, ties to the smaller column, column 0 ranked like any other);
+ *   out_val (nullable) their scores, +0.0 for a seen item.  For the same scores the lists are exactly those of
+ *   bsarec_topk_seen on the materialised matrix, for every input (ties, all-zero tables, NaN rows, heavily seen rows):
+ *   there is no approximate mode.
+ *   Execution: a fixed sequence of 8 launches on `stream`: no host synchronisation, no allocation; capturable in a graph.
+ *   Working memory: the caller's workspace of bsarec_topk_full_workspace_bytes(B, V, d, k, cand_cap) bytes, O(B (s + cap))
+ *   with s ~ 4 sqrt(k V) sampled columns and cap candidates per row, never O(B V).
+ *   Limits (else < 0 before any HIP call): B >= 1, 1 <= k <= BSAREC_TOPK_MAX, k <= V < 2^31, 4 <= d <= 256, d % 4 == 0,
+ *   ldh >= d, h / item_emb / workspace 16-byte aligned and non-null, out_idx non-null, workspace_bytes >= the query, users and
+ *   indices non-null when indptr is given.  cand_cap == 0: the default capacity; > 0: the per-row candidate capacity
+ *   (k <= cand_cap <= 2^30), for tests that force the overflow paths -- the result does not depend on it.
+ * bsarec_topk_full_workspace_bytes: host only, no HIP call; < 0 for arguments bsarec_topk_full would refuse. */
+long bsarec_topk_full_workspace_bytes(int B, int V, int d, int k, int cand_cap);
+int bsarec_topk_full(const float *h, long ldh, const float *item_emb, int B, int V, int d, const int64_t *users,
+                     const int64_t *indptr, const int64_t *indices, int k, int cand_cap, void *workspace, long workspace_bytes,
+                     int64_t *out_idx, float *out_val, void *stream);
+
 /* Stand-alone FrequencyLayer (src/model/bsarec.py:90-104) for per-op parity tests:
  * y = LN(Drop(low + beta^2 (x - low)) + x); backward given dy. */
 int bsarec_freq_layer_fwd(const float *x, const float *sqrt_beta, const float *ln_w, const float *ln_b,
