@@ -207,6 +207,24 @@ SHARD_EXPORTS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_shard_scatter_rows": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.POINTER(PTRS8), C.c_long, C.c_long, C.c_long,
                                             C.c_int, C.c_void_p, C.c_void_p]),
+    # sampled-softmax head of the sharded step, lazy Adam of the shard
+    "bsarec_shard_ssm_draw": (C.c_int, [C.c_uint64, C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "bsarec_shard_ssm_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PTRS8), C.c_int, C.c_long, C.c_long,
+                                          C.c_int, C.c_void_p, C.c_void_p]),
+    "bsarec_shard_ssm_head": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "bsarec_shard_ssm_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bsarec_shard_ssm_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),
+    "bsarec_shard_ssm_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bsarec_shard_ssm_pull": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(PTRS8), C.c_long, C.c_long,
+                                        C.c_long, C.c_int, C.c_void_p, C.c_void_p]),
+    "bsarec_shard_lazy_mark": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long,
+                                         C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bsarec_shard_lazy_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float,
+                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -22,17 +22,30 @@ sequences, Bg = W*B):
 
 The loss is the mean over the global batch: d loss / d logits carries 1 / Bg, so every gradient is already the
 global-batch one and the encoder's Adam takes the plain SUM over ranks (grad_scale = 1).
+
+Sampled-softmax head (opt-in, ``train_negatives`` N > 0 with ``train_sampler`` / ``train_no_logq`` / ``train_lazy_adam`` as on
+one GPU) -- the head rows above become, per rank:
+
+  draw             the step's N candidates, the same on every rank (key of set_seed(seed, rank=0), step = the encoder's
+                   state[1] read on the device): those of ONE BSARecModel training on the global batch
+  gather           the B answer rows and the N candidate rows out of the owners' shards
+  head             logits / loss rows / d loss / d logits (1 / Bg) of the B local rows only; all-gather of the loss rows
+  head backward    d h_last of the local rows (complete: no exchange); the head gradient rows [B + N, d] (IPC-exported)
+  encoder backward, barrier   as above
+  owner pull       every owner adds the answer rows of its items and the rank-ordered sum of the candidate partials
+  Adam             shard: dense (dE zeroed once per step), or lazy over the owned rows the step touched
 """
 from __future__ import annotations
 
 import copy
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib as L
 from .dp import PeerExchange, _as_tensor
-from .model import BSARecModel
+from .model import BSARecModel, train_head_of
 
 
 class ShardedCatalogue:
@@ -40,15 +53,25 @@ class ShardedCatalogue:
     per-rank batch size (fixed: the staging table and the encoder plan are sized by it)."""
 
     def __init__(self, args, batch: int, group, device):
-        if int(getattr(args, "train_negatives", 0) or 0) > 0 or getattr(args, "train_lazy_adam", False):
-            raise ValueError("ShardedCatalogue: catalogue-sharded training has no sampled-softmax head (train_negatives must be 0) and no lazy Adam")
+        # the training head: full-catalogue CE, or the sampled-softmax head with the single-GPU flags and limits
+        head = train_head_of(args)
+        self.N = head["train_negatives"]
+        self.popularity = head["train_sampler"] == L.TRAIN_SAMPLERS["popularity"]
+        self.logq = 0 if head["train_no_logq"] else 1
+        self.lazy = bool(getattr(args, "train_lazy_adam", False))
+        if self.lazy and self.N == 0:
+            raise ValueError("train_lazy_adam needs the sampled-softmax head (train_negatives > 0)")
+        if getattr(args, "storage", None) == "bf16":
+            raise ValueError("catalogue sharding is fp32 only")
+        if torch.device(device).type != "cuda":        # before the process group, the IPC mappings and any allocation
+            head_name = (f"sampled-softmax head, train_negatives = {self.N}" if self.N else "full-catalogue CE head")
+            raise ValueError(f"ShardedCatalogue: the catalogue-sharded step ({head_name}) runs on the GPU only, "
+                             f"not on device {str(device)!r}")
         import torch.distributed as dist
         self.args, self.group, self.device, self.B = args, group, torch.device(device), int(batch)
         self.rank, self.W = dist.get_rank(group), dist.get_world_size(group)
         if self.W > 8:
             raise ValueError("catalogue sharding runs inside one xGMI node (<= 8 ranks)")
-        if getattr(args, "storage", None) == "bf16":
-            raise ValueError("catalogue sharding is fp32 only")
         V, d, Lq = int(args.item_size), int(args.hidden_size), int(args.max_seq_length)
         self.V, self.d, self.Lq = V, d, Lq
         self.rows_per = (V + self.W - 1) // self.W
@@ -61,6 +84,7 @@ class ShardedCatalogue:
         enc_args = copy.copy(args)
         enc_args.item_size = self.n + 1
         enc_args.plan_options = dict(getattr(args, "plan_options", None) or {})
+        enc_args.train_negatives, enc_args.train_lazy_adam = 0, False      # the head runs here, not in the encoder's plan
         self.encoder = BSARecModel(enc_args).to(self.device)
         off, self.stage_n, _ = self.encoder._slices["item_embeddings.weight"]
         assert off == 0 and self.stage_n == (self.n + 1) * d
@@ -83,22 +107,67 @@ class ShardedCatalogue:
                                     weight_decay=float(getattr(args, "weight_decay", 0.0)))
         # head buffers
         self.ld = (max(self.Vs, 1) + 3) // 4 * 4
-        self.logits = torch.zeros(self.Bg, self.ld, dtype=torch.float32, device=self.device)
-        self.stats = torch.zeros(3, self.Bg, dtype=torch.float32, device=self.device)
-        self.stats_all = torch.zeros(self.W, 3, self.Bg, dtype=torch.float32, device=self.device)
-        self.h_all = torch.zeros(self.Bg, d, dtype=torch.float32, device=self.device)
+        self.logits = self.h_all = None
+        if self.N == 0:
+            self._full_head_buffers()
+            self.stats = torch.zeros(3, self.Bg, dtype=torch.float32, device=self.device)
+            self.stats_all = torch.zeros(self.W, 3, self.Bg, dtype=torch.float32, device=self.device)
+            self.dh = torch.zeros(self.Bg, d, dtype=torch.float32, device=self.device)
+            self.scratch = torch.zeros(max(1, self.lib.bsarec_shard_head_bwd_scratch_floats(self.Bg, self.Vs, d)),
+                                       dtype=torch.float32, device=self.device)
         self.ans_all = torch.zeros(self.Bg, dtype=torch.int64, device=self.device)
         self.ids_all = torch.zeros(self.W, self.n, dtype=torch.int64, device=self.device)
         self.local_ids = torch.zeros(self.B, Lq, dtype=torch.int64, device=self.device)
-        self.dh = torch.zeros(self.Bg, d, dtype=torch.float32, device=self.device)
-        self.scratch = torch.zeros(max(1, self.lib.bsarec_shard_head_bwd_scratch_floats(self.Bg, self.Vs, d)),
-                                   dtype=torch.float32, device=self.device)
         self.d_out = torch.zeros(self.B, Lq, d, dtype=torch.float32, device=self.device)
+        if self.N:
+            self._sampled_head_buffers(px)
         self.loss_rows = torch.zeros(self.Bg, dtype=torch.float32, device=self.device)
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._shards8 = L.PTRS8(*([int(p) for p in self.shard_ptrs] + [None] * (8 - self.W)))
         self._grads8 = L.PTRS8(*([int(p) for p in px.grad_srcs(0)] + [None] * (8 - self.W)))
         dist.barrier(group=group)
+
+    def _full_head_buffers(self):
+        """Partial logits of all Bg sequences against the owned rows and the gathered h_last (the full-CE step; evaluation)."""
+        self.logits = torch.zeros(self.Bg, self.ld, dtype=torch.float32, device=self.device)
+        self.h_all = torch.zeros(self.Bg, self.d, dtype=torch.float32, device=self.device)
+
+    def _sampled_head_buffers(self, px):
+        B, N, d, dev = self.B, self.N, self.d, self.device
+        # the draws' key: the one BSARecModel.set_seed(seed, rank=0) writes (the encoder replica's key is rank-decorrelated)
+        self.key = int(getattr(self.args, "seed", 42)) & 0x7FFFFFFFFFFFFFFF
+        self._cum = None                                            # set_train_popularity: device int64[V]
+        self.cand = torch.zeros(N, dtype=torch.int32, device=dev)   # the step's candidates (tests read them)
+        self.corr = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.rows = torch.zeros(B + N, d, dtype=torch.float32, device=dev)
+        self.s_logits = torch.zeros(B, N + 1, dtype=torch.float32, device=dev)
+        self.s_dlogits = torch.zeros(B, N + 1, dtype=torch.float32, device=dev)
+        self.loss_rows_local = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.s_scratch = torch.zeros(self.lib.bsarec_shard_ssm_bwd_scratch_floats(B, N, d), dtype=torch.float32, device=dev)
+        # the head gradient rows [B + N, d], read by the owners after the barrier that follows the backward
+        g_ptr, g_ptrs = px.share((B + N) * d * 4)
+        self.head_grad = _as_tensor(g_ptr, (B + N) * d, torch.float32, dev).view(B + N, d)
+        self._hgrads8 = L.PTRS8(*([int(p) for p in g_ptrs] + [None] * (8 - self.W)))
+        if self.lazy:       # the touched owned rows of a step (lazy_adam.h): marks [Vs] (0 between steps) and their list
+            self.lazy_cap = min(self.Vs, self.W * self.n + self.Bg + N)
+            self.lazy_mark = torch.zeros(max(self.Vs, 1), dtype=torch.int32, device=dev)
+            self.lazy_rows = torch.zeros(max(self.lazy_cap, 1), dtype=torch.int32, device=dev)
+            self.lazy_count = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def set_train_popularity(self, counts):
+        """The popularity sampler of the sampled-softmax head: ``counts`` int64[item_size] of item occurrences over the
+        GLOBAL catalogue, the same on every rank (checks and format of BSARecModel.set_train_popularity)."""
+        V = self.V
+        c = np.asarray(counts, dtype=np.int64)
+        if c.shape != (V,) or (c < 0).any():
+            raise ValueError(f"set_train_popularity: expected {V} counts >= 0")
+        cum = np.cumsum(np.where(np.arange(V) == 0, 0, c))
+        if cum[-1] < 1:
+            raise ValueError("set_train_popularity: every count is 0")
+        if self.N and self._cum is not None:
+            self._cum.copy_(torch.as_tensor(cum, dtype=torch.int64))   # in place: a captured step keeps its pointer
+        elif self.N:
+            self._cum = torch.as_tensor(cum, dtype=torch.int64, device=self.device)
 
     # ---- weights ---------------------------------------------------------------------------------------------------
     def load_full_state_dict(self, sd):
@@ -153,6 +222,8 @@ class ShardedCatalogue:
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
         ans = answers.to(device=self.device, dtype=torch.int64).contiguous()
         assert tuple(ids.shape) == (B, Lq) and tuple(ans.shape) == (B,)
+        if self.N and self.popularity and self._cum is None:
+            raise ValueError("ShardedCatalogue: the popularity sampler needs set_train_popularity(counts) before the first step")
         st = enc._stream()
         # peers finished the previous step: their shards are current, nobody reads my old staging gradient any more
         self.px.barrier(st)
@@ -160,6 +231,8 @@ class ShardedCatalogue:
                                              enc._arena.data_ptr(), self.local_ids.data_ptr(), st), "bsarec_shard_gather_rows")
         enc.train()
         plan = enc._run_forward(self.local_ids, train=True, new_step=True)
+        if self.N:
+            return self._sampled_step(plan, ids, ans, st)
         h_last = plan.view(L.BUF_LAYER_OUT, self.args.num_hidden_layers, (B, Lq, d))[:, Lq - 1, :].float().contiguous()
         dist.all_gather(list(self.h_all.view(W, B, d).unbind(0)), h_last, group=g)
         dist.all_gather(list(self.ans_all.view(W, B).unbind(0)), ans, group=g)
@@ -186,6 +259,54 @@ class ShardedCatalogue:
                         a["v"].data_ptr() + 4 * sn, enc._numel - sn, [p + 4 * sn for p in self.px.grad_srcs(0)])
         L.check(lib.bsarec_adam_step(C.byref(ad), enc._state.data_ptr(), st), "bsarec_adam_step")
         if self.Vs:
+            ae = self._adam(self.E.data_ptr(), self.dE.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.Vs * d)
+            L.check(lib.bsarec_adam_apply(C.byref(ae), enc._state.data_ptr(), st), "bsarec_adam_apply")
+        return self.loss[0]
+
+    def _sampled_step(self, plan, ids, ans, st) -> torch.Tensor:
+        """The rest of :meth:`train_step` under the sampled-softmax head (module docstring; include/bsarec_shard.h)."""
+        import torch.distributed as dist
+        lib, enc, g = self.lib, self.encoder, self.group
+        B, Lq, d, W, Bg, n, N = self.B, self.Lq, self.d, self.W, self.Bg, self.n, self.N
+        H = plan.view(L.BUF_LAYER_OUT, self.args.num_hidden_layers, (B, Lq, d))
+        h, ldh = H.data_ptr() + 4 * (Lq - 1) * d, Lq * d          # h_last in place: row b at position L-1
+        cum = self._cum.data_ptr() if self.popularity else None
+        dist.all_gather(list(self.ans_all.view(W, B).unbind(0)), ans, group=g)
+        dist.all_gather(list(self.ids_all.unbind(0)), ids.view(-1), group=g)
+        if not self.lazy:
+            self.dE.zero_()                 # the head adds its rows now: no dense overwrite of the owned rows any more
+        L.check(lib.bsarec_shard_ssm_draw(self.key, enc._state.data_ptr(), N, self.V, cum, self.logq, self.cand.data_ptr(),
+                                          self.corr.data_ptr(), self.lazy_count.data_ptr() if self.lazy else None, st),
+                "bsarec_shard_ssm_draw")
+        L.check(lib.bsarec_shard_ssm_gather(ans.data_ptr(), B, self.cand.data_ptr(), N, C.byref(self._shards8), W, self.rows_per,
+                                            self.V, d, self.rows.data_ptr(), st), "bsarec_shard_ssm_gather")
+        L.check(lib.bsarec_shard_ssm_head(h, ldh, B, Bg, self.rows.data_ptr(), ans.data_ptr(), self.cand.data_ptr(),
+                                          self.corr.data_ptr(), N, self.V, cum, self.logq, d, self.s_logits.data_ptr(),
+                                          self.s_dlogits.data_ptr(), self.loss_rows_local.data_ptr(), st), "bsarec_shard_ssm_head")
+        dist.all_gather(list(self.loss_rows.view(W, B).unbind(0)), self.loss_rows_local, group=g)
+        L.check(lib.bsarec_shard_ssm_loss(self.loss_rows.data_ptr(), Bg, self.loss.data_ptr(), st), "bsarec_shard_ssm_loss")
+        L.check(lib.bsarec_shard_ssm_bwd(self.s_dlogits.data_ptr(), B, N, h, ldh, self.rows.data_ptr(), d,
+                                         self.d_out.data_ptr() + 4 * (Lq - 1) * d, Lq * d, self.head_grad.data_ptr(),
+                                         self.s_scratch.data_ptr(), st), "bsarec_shard_ssm_bwd")
+        L.check(lib.bsarec_backward_seq(plan.handle, self.d_out.data_ptr(), st), "bsarec_backward_seq")
+        self.px.barrier(st)                 # every rank's gradient arena and head gradient rows are complete
+        L.check(lib.bsarec_shard_ssm_pull(self.ans_all.data_ptr(), B, W, self.cand.data_ptr(), N, C.byref(self._hgrads8), self.lo,
+                                          self.Vs, self.V, d, self.dE.data_ptr(), st), "bsarec_shard_ssm_pull")
+        L.check(lib.bsarec_shard_scatter_rows(self.ids_all.data_ptr(), n, W, C.byref(self._grads8), self.lo, self.Vs, self.V, d,
+                                              self.dE.data_ptr(), st), "bsarec_shard_scatter_rows")
+        sn, a = self.stage_n, enc._adam
+        ad = self._adam(enc._arena.data_ptr() + 4 * sn, enc._garena.data_ptr() + 4 * sn, a["m"].data_ptr() + 4 * sn,
+                        a["v"].data_ptr() + 4 * sn, enc._numel - sn, [p + 4 * sn for p in self.px.grad_srcs(0)])
+        L.check(lib.bsarec_adam_step(C.byref(ad), enc._state.data_ptr(), st), "bsarec_adam_step")
+        if self.Vs and self.lazy:
+            L.check(lib.bsarec_shard_lazy_mark(self.ids_all.data_ptr(), W * n, self.ans_all.data_ptr(), Bg, self.cand.data_ptr(), N,
+                                               self.lo, self.Vs, self.V, self.lazy_mark.data_ptr(), self.lazy_rows.data_ptr(),
+                                               self.lazy_count.data_ptr(), self.lazy_cap, st), "bsarec_shard_lazy_mark")
+            L.check(lib.bsarec_shard_lazy_adam(self.E.data_ptr(), self.dE.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), d,
+                                               a["b1"], a["b2"], a["eps"], a["wd"], self.lazy_mark.data_ptr(),
+                                               self.lazy_rows.data_ptr(), self.lazy_count.data_ptr(), self.lazy_cap,
+                                               enc._state.data_ptr(), st), "bsarec_shard_lazy_adam")
+        elif self.Vs:
             ae = self._adam(self.E.data_ptr(), self.dE.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.Vs * d)
             L.check(lib.bsarec_adam_apply(C.byref(ae), enc._state.data_ptr(), st), "bsarec_adam_apply")
         return self.loss[0]
@@ -237,6 +358,8 @@ class ShardedCatalogue:
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
         assert tuple(ids.shape) == (B, Lq)
         st = enc._stream()
+        if self.logits is None:             # sampled-softmax training: the full-catalogue buffers on the first evaluation
+            self._full_head_buffers()
         self.px.barrier(st)
         L.check(lib.bsarec_shard_gather_rows(ids.data_ptr(), n, C.byref(self._shards8), W, self.rows_per, self.V, d,
                                              enc._arena.data_ptr(), self.local_ids.data_ptr(), st), "bsarec_shard_gather_rows")

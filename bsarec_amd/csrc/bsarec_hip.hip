@@ -1976,3 +1976,132 @@ extern "C" int bsarec_shard_scatter_rows(const int64_t* ids_all, long n, int wor
            Vs, V, d4, dE);
     return (int)hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------
+// sampled-softmax head of the catalogue-sharded step (include/bsarec_shard.h; sampled_softmax.h, catalogue_shard.h,
+// lazy_adam.h)
+// ---------------------------------------------------------------------------------------------
+// dh split-K over the candidates: the single-GPU plan's rule (sampled head of bsarec_plan) without its vsplit cap
+static void shard_ssm_split(int N, int* nslab, int* chunk) {
+    const int want = std::max(1, std::min(32, N / 256));
+    *chunk = (int)rup(cdiv(N, want), SSM_KS);
+    *nslab = cdiv(N, *chunk);
+}
+
+static SsmP shard_ssm_params(const float* h, long ldh, int B, int Bg, const float* rows, const int64_t* answers, const int* cand,
+                             const float* corr, int N, long V, const int64_t* pop_cum, int logq, int d) {
+    SsmP P;
+    memset(&P, 0, sizeof(P));
+    P.H = h; P.ldh = ldh; P.E = rows; P.answers = answers; P.pop_cum = pop_cum;
+    P.B = B; P.V = (int)V; P.d = d; P.N = N; P.logq = logq ? 1 : 0; P.inv_b = 1.0f / (float)Bg;
+    P.cand = const_cast<int*>(cand); P.corr = const_cast<float*>(corr);
+    return P;
+}
+
+extern "C" int bsarec_shard_ssm_draw(uint64_t key, const uint64_t* state, int N, long V, const int64_t* pop_cum, int logq,
+                                     int* cand, float* corr, int* lazy_count, void* stream) {
+    if (!state || !cand || !corr || N < 1 || N > SSM_NEG_MAX || V < 2 || V > INT32_MAX) return -10;
+    SsmP P = shard_ssm_params(nullptr, 0, 1, 1, nullptr, nullptr, cand, corr, N, V, pop_cum, logq, 4);
+    P.state = state;
+    LAUNCH(shard_ssm_draw_kernel, dim3(cdiv(N, ROW_THREADS)), dim3(ROW_THREADS), 0, (hipStream_t)stream, P, key, lazy_count);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_shard_ssm_gather(const int64_t* answers, int B, const int* cand, int N, const float* const* shards, int world,
+                                       long rows_per, long V, int d, float* rows, void* stream) {
+    if (!answers || !cand || !rows || B < 1 || N < 1 || N > SSM_NEG_MAX || rows_per < 1 || V < 1 || d < 4 || (d & 3)) return -10;
+    if ((V + rows_per - 1) / rows_per > world) return -11;
+    ShardPtrs S;
+    RET(shard_ptrs(S, shards, world));
+    const int d4 = d / 4;
+    LAUNCH(shard_ssm_gather_kernel, dim3(cdiv(((long)B + N) * d4, 256)), dim3(256), 0, (hipStream_t)stream, answers, B, cand, N, S,
+           rows_per, V, d4, rows);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_shard_ssm_head(const float* h, long ldh, int B, int Bg, const float* rows, const int64_t* answers,
+                                     const int* cand, const float* corr, int N, long V, const int64_t* pop_cum, int logq, int d,
+                                     float* logits, float* dlogits, float* loss_rows, void* stream) {
+    if (!h || !rows || !answers || !cand || !corr || !logits || !dlogits || !loss_rows) return -10;
+    if (B < 1 || Bg < B || N < 1 || N > SSM_NEG_MAX || V < 2 || V > INT32_MAX || d < 4 || (d & 3) || ldh < d) return -10;
+    hipStream_t s = (hipStream_t)stream;
+    SsmP P = shard_ssm_params(h, ldh, B, Bg, rows, answers, cand, corr, N, V, pop_cum, logq, d);
+    P.logits = logits; P.dlogits = dlogits; P.loss_rows = loss_rows;
+    LAUNCH(shard_ssm_logits_kernel, dim3(cdiv(N, SSM_TILE), cdiv(B, SSM_TILE)), dim3(ROW_THREADS), 0, s, P);
+    HIPCHK(hipGetLastError());
+    LAUNCH(shard_ssm_ce_kernel, dim3(B), dim3(ROW_THREADS), 0, s, P);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_shard_ssm_loss(const float* loss_rows_all, int Bg, float* loss, void* stream) {
+    if (!loss_rows_all || !loss || Bg < 1) return -10;
+    LAUNCH(loss_mean_kernel, dim3(1), dim3(ROW_THREADS), 0, (hipStream_t)stream, loss_rows_all, Bg, loss);
+    return (int)hipGetLastError();
+}
+
+extern "C" long bsarec_shard_ssm_bwd_scratch_floats(int B, int N, int d) {
+    if (B < 1 || N < 1 || N > SSM_NEG_MAX || d < 4) return -10;
+    int ns, ch;
+    shard_ssm_split(N, &ns, &ch);
+    return (long)ns * B * d;
+}
+
+extern "C" int bsarec_shard_ssm_bwd(const float* dlogits, int B, int N, const float* h, long ldh, const float* rows, int d,
+                                    float* dh, long lddh, float* grad_rows, float* scratch, void* stream) {
+    if (!dlogits || !h || !rows || !dh || !grad_rows || !scratch) return -10;
+    if (B < 1 || N < 1 || N > SSM_NEG_MAX || d < 4 || (d & 3) || ldh < d || lddh < d || (lddh & 3)) return -10;
+    hipStream_t s = (hipStream_t)stream;
+    SsmP P = shard_ssm_params(h, ldh, B, B, rows, nullptr, nullptr, nullptr, N, 2, nullptr, 0, d);
+    P.dlogits = const_cast<float*>(dlogits); P.slab = scratch;
+    shard_ssm_split(N, &P.nslab, &P.chunk);
+    const int dt = cdiv(d, SSM_TILE);
+    P.tilesA = cdiv(N, SSM_TILE) * dt;
+    P.tilesB = P.nslab * cdiv(B, SSM_TILE) * dt;
+    const int tilesC = std::max(1, std::min(cdiv((long)B * d, ROW_THREADS), 64));
+    LAUNCH(shard_ssm_bwd_kernel, dim3(P.tilesA + P.tilesB + tilesC), dim3(ROW_THREADS), 0, s, P, grad_rows);
+    HIPCHK(hipGetLastError());
+    const long n4 = (long)B * d / 4;
+    LAUNCH(shard_ssm_dh_kernel, dim3(cdiv(n4, ROW_THREADS)), dim3(ROW_THREADS), 0, s, scratch, P.nslab, B, d / 4, dh, lddh);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_shard_ssm_pull(const int64_t* answers_all, int B, int world, const int* cand, int N,
+                                     const float* const* grad_rows, long lo, long Vs, long V, int d, float* dE, void* stream) {
+    if (!answers_all || !cand || B < 1 || N < 1 || N > SSM_NEG_MAX || Vs < 0 || lo < 0 || V < 1 || d < 4 || (d & 3)) return -10;
+    ShardPtrs G;
+    RET(shard_ptrs(G, grad_rows, world));
+    if (Vs == 0) return 0;
+    if (!dE) return -10;
+    const int d4 = d / 4;
+    LAUNCH(shard_ssm_pull_kernel, dim3(cdiv(((long)N + (long)world * B) * d4, 256)), dim3(256), 0, (hipStream_t)stream, answers_all,
+           B, world, cand, N, G, lo, Vs, V, d4, dE);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_shard_lazy_mark(const int64_t* ids_all, long nids, const int64_t* answers_all, int Bg, const int* cand, int N,
+                                      long lo, long Vs, long V, int* mark, int* rows, int* count, int cap, void* stream) {
+    if (!ids_all || !answers_all || !cand || nids < 0 || Bg < 1 || N < 1 || N > SSM_NEG_MAX || Vs < 0 || lo < 0 || V < 1) return -10;
+    if (Vs == 0) return 0;
+    if (!mark || !rows || !count || cap < (int)std::min<long>(Vs, nids + Bg + N)) return -10;
+    LazyRows T;
+    memset(&T, 0, sizeof(T));
+    T.mark = mark; T.rows = rows; T.count = count; T.cap = cap;
+    const int nb = (int)std::max<long>(1, std::min<long>(cdiv(nids + Bg + N, ROW_THREADS), 256));
+    LAUNCH(shard_lazy_mark_kernel, dim3(nb), dim3(ROW_THREADS), 0, (hipStream_t)stream, ids_all, nids, answers_all, Bg, cand, N, lo,
+           Vs, V, T);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_shard_lazy_adam(float* E, float* dE, float* m, float* v, int d, float b1, float b2, float eps, float wd,
+                                      int* mark, const int* rows, const int* count, int cap, const void* state, void* stream) {
+    if (!state || d < 4 || (d & 3) || cap < 0) return -10;
+    if (cap == 0) return 0;
+    if (!E || !dE || !m || !v || !mark || !rows || !count) return -10;
+    ShardLazyAdamP A;
+    memset(&A, 0, sizeof(A));
+    A.w = E; A.g = dE; A.m = m; A.v = v; A.b1 = b1; A.b2 = b2; A.eps = eps; A.wd = wd;
+    A.T.mark = mark; A.T.rows = const_cast<int*>(rows); A.T.count = const_cast<int*>(count); A.T.cap = cap; A.T.d4 = d / 4;
+    const int nb = (int)std::min<long>(cdiv((long)cap * A.T.d4, ROW_THREADS), 1024);
+    LAUNCH(shard_lazy_adam_kernel, dim3(nb), dim3(ROW_THREADS), 0, (hipStream_t)stream, (const uint64_t*)state, A);
+    return (int)hipGetLastError();
+}

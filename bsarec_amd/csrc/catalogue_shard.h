@@ -130,3 +130,68 @@ shard_slab_sum_kernel(const float* __restrict__ slabs, int nsplit, long n4, floa
     for (int s = 1; s < nsplit; ++s) a += ld4(slabs + ((long)s * n4 + i) * 4);
     st4(out + 4 * i, a);
 }
+
+// ---- sampled-softmax head of the sharded step (sampled_softmax.h, shard_ssm_*; include/bsarec_shard.h) -----------------
+
+// Rows of the head, read out of the owners' shards (system scope, as shard_gather_rows_kernel): R[b] = E[answers[b]] for
+// b < B, R[B + j] = E[cand[j]], ids clamped to [0, V).
+__global__ void __launch_bounds__(256)
+shard_ssm_gather_kernel(const int64_t* __restrict__ answers, int B, const int* __restrict__ cand, int N, const ShardPtrs S,
+                        long rows_per, long V, int d4, float* __restrict__ R) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long row = idx / d4;
+    const int c = (int)(idx - row * d4);
+    if (row >= (long)B + N) return;
+    long id = row < B ? (long)answers[row] : (long)cand[row - B];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    const long owner = id / rows_per;
+    st4(R + (row * d4 + c) * 4, ld4_sys(S.p[owner] + ((id - owner * rows_per) * d4 + c) * 4));
+}
+
+// Owner side of the head gradient: G.p[r] = rank r's head gradient [B + N][d] (rows b < B: its answer rows, rows B + j: its
+// partial candidate rows).  Lane (slot, float4): slots [0, N) are the candidates -- an owned n_j gets the W partials of row
+// B + j summed in rank order, then added to dE[n_j - lo]; slots [N, N + W B) are the answers of ans_all (rank order) -- an
+// owned answer gets its rank's row.  A row hit several times (draws with replacement, an answer that is also a candidate,
+// answers shared by sequences) takes float atomics: the order of those additions is not fixed.
+__global__ void __launch_bounds__(256)
+shard_ssm_pull_kernel(const int64_t* __restrict__ ans_all, int B, int world, const int* __restrict__ cand, int N, const ShardPtrs G,
+                      long lo, long Vs, long V, int d4, float* __restrict__ dE) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long t = idx / d4;
+    const int c = (int)(idx - t * d4);
+    if (t >= (long)N + (long)world * B) return;
+    long id = t < N ? (long)cand[t] : (long)ans_all[t - N];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    if (id < lo || id >= lo + Vs) return;
+    f32x4 g;
+    if (t < N) {
+        const long off = (((long)B + t) * d4 + c) * 4;
+        g = ld4_sys(G.p[0] + off);
+        for (int r = 1; r < world; ++r) g += ld4_sys(G.p[r] + off);
+    } else {
+        const long u = t - N, r = u / B;
+        g = ld4_sys(G.p[r] + ((u - r * B) * d4 + c) * 4);
+    }
+    float* dst = dE + ((id - lo) * d4 + c) * 4;
+    unsafeAtomicAdd(dst + 0, g.x); unsafeAtomicAdd(dst + 1, g.y); unsafeAtomicAdd(dst + 2, g.z); unsafeAtomicAdd(dst + 3, g.w);
+}
+
+// Lazy Adam of the shard: mark the owned rows of the step -- the looked-up ids_all [nids] (!= 0), ans_all [Bg] and cand [N],
+// clamped to [0, V) -- at their local index (lazy_mark_wave).  Grid-stride from wave-aligned starts (every lane of a wave
+// takes the same trips: the ballot).
+__global__ void __launch_bounds__(ROW_THREADS)
+shard_lazy_mark_kernel(const int64_t* __restrict__ ids_all, long nids, const int64_t* __restrict__ ans_all, int Bg,
+                       const int* __restrict__ cand, int N, long lo, long Vs, long V, const LazyRows T) {
+    const long total = nids + Bg + N, stride = (long)gridDim.x * ROW_THREADS;
+    for (long e0 = (long)blockIdx.x * ROW_THREADS + (threadIdx.x & ~63); e0 < total; e0 += stride) {
+        const long e = e0 + (threadIdx.x & 63);
+        long id = 0;
+        bool valid = e < total;
+        if (valid) {
+            id = e < nids ? (long)ids_all[e] : (e < nids + Bg ? (long)ans_all[e - nids] : (long)cand[e - nids - Bg]);
+            id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+            valid = (e >= nids || id != 0) && id >= lo && id < lo + Vs;
+        }
+        lazy_mark_wave(T, valid ? (int)(id - lo) : 0, valid);
+    }
+}

@@ -106,3 +106,26 @@ lazy_adam_kernel(const uint64_t* __restrict__ state, const LazyAdamP A) {
         if (q == 0) A.T.mark[r] = 0;                               // the last pass of the step over T: unmark
     }
 }
+
+// Lazy Adam of a catalogue shard (include/bsarec_shard.h, bsarec_shard_lazy_adam): the rows of T (marked by
+// shard_lazy_mark_kernel, catalogue_shard.h) of the shard's w / m / v with its gradient g, the arithmetic of lazy_adam4 and the
+// corrections of the step's tick (state[3]); the last pass of the step over T -- the gradient rows are zeroed and the marks
+// cleared.  Rows outside T are not read.
+struct ShardLazyAdamP { float *w, *g, *m, *v; float b1, b2, eps, wd; LazyRows T; };
+__global__ void __launch_bounds__(ROW_THREADS)
+shard_lazy_adam_kernel(const uint64_t* __restrict__ state, const ShardLazyAdamP A) {
+    const float* f = reinterpret_cast<const float*>(state + 3);
+    const float step_size = f[0], bc2s = f[1];
+    const int d4 = A.T.d4;
+    const long n = (long)min(*A.T.count, A.T.cap) * d4;
+    for (long k = (long)blockIdx.x * ROW_THREADS + threadIdx.x; k < n; k += (long)gridDim.x * ROW_THREADS) {
+        const int r = A.T.rows[k / d4], q = (int)(k % d4);
+        const long o = 4 * ((long)r * d4 + q);
+        const f32x4 gi = ld4(A.g + o);
+        f32x4 wi = ld4(A.w + o), mi = ld4(A.m + o), vi = ld4(A.v + o);
+        lazy_adam4(wi, mi, vi, gi, A.b1, A.b2, A.eps, A.wd, step_size, bc2s);
+        st4(A.w + o, wi); st4(A.m + o, mi); st4(A.v + o, vi);
+        st4(A.g + o, f32x4{0.f, 0.f, 0.f, 0.f});
+        if (q == 0) A.T.mark[r] = 0;
+    }
+}

@@ -131,24 +131,12 @@ __global__ void __launch_bounds__(ROW_THREADS) ssm_logits_kernel(const SsmP P) {
     }
 }
 
-// one workgroup per row: the answer's logit, then the row's cross-entropy over the N + 1 columns
-__global__ void __launch_bounds__(ROW_THREADS) ssm_ce_kernel(const SsmP P) {
-    __shared__ float red[ROW_THREADS / 64];
-    __shared__ float bc;
-    const int b = blockIdx.x, tid = threadIdx.x, n1 = P.N + 1;
-    float* row = P.logits + (long)b * n1;
-    float* drow = P.dlogits + (long)b * n1;
-    int a = (int)P.answers[b];
-    a = a < 0 ? 0 : (a >= P.V ? P.V - 1 : a);
-    // x_b0: the dot product in the same k order as the product tiles (sequential fmaf), one lane
-    if (tid == 0) {
-        const float* h = P.H + (long)b * P.ldh;
-        const float* e = P.E + (long)a * P.d;
-        float s = 0.f;
-        for (int k = 0; k < P.d; ++k) s = fmaf(h[k], e[k], s);
-        row[0] = s - ssm_corr(P, a);
-    }
-    __syncthreads();
+// The cross-entropy of one row over its n1 = N + 1 columns once the answer's logit is in row[0] (every lane has passed a
+// barrier since): logsumexp, drow = (softmax - onehot_0) * inv_b, loss_row = lse - row[0].  One 256-lane workgroup; red /
+// bc: the caller's LDS.
+__device__ __forceinline__ void ssm_ce_row(const float* row, float* drow, int n1, float inv_b, float* loss_row, float* red,
+                                           float& bc) {
+    const int tid = threadIdx.x;
     float mx = -INFINITY;
     for (int j = tid; j < n1; j += ROW_THREADS) mx = fmaxf(mx, row[j]);
     mx = group_max<64>(mx);
@@ -166,8 +154,28 @@ __global__ void __launch_bounds__(ROW_THREADS) ssm_ce_kernel(const SsmP P) {
     if (tid == 0) { float t = 0.f; for (int i = 0; i < ROW_THREADS / 64; ++i) t += red[i]; bc = mx + logf(t); }
     __syncthreads();
     const float lse = bc;
-    for (int j = tid; j < n1; j += ROW_THREADS) drow[j] = (expf(row[j] - lse) - (j == 0 ? 1.0f : 0.0f)) * P.inv_b;
-    if (tid == 0) P.loss_rows[b] = lse - row[0];
+    for (int j = tid; j < n1; j += ROW_THREADS) drow[j] = (expf(row[j] - lse) - (j == 0 ? 1.0f : 0.0f)) * inv_b;
+    if (tid == 0) *loss_row = lse - row[0];
+}
+
+// one workgroup per row: the answer's logit, then the row's cross-entropy over the N + 1 columns
+__global__ void __launch_bounds__(ROW_THREADS) ssm_ce_kernel(const SsmP P) {
+    __shared__ float red[ROW_THREADS / 64];
+    __shared__ float bc;
+    const int b = blockIdx.x, tid = threadIdx.x, n1 = P.N + 1;
+    float* row = P.logits + (long)b * n1;
+    int a = (int)P.answers[b];
+    a = a < 0 ? 0 : (a >= P.V ? P.V - 1 : a);
+    // x_b0: the dot product in the same k order as the product tiles (sequential fmaf), one lane
+    if (tid == 0) {
+        const float* h = P.H + (long)b * P.ldh;
+        const float* e = P.E + (long)a * P.d;
+        float s = 0.f;
+        for (int k = 0; k < P.d; ++k) s = fmaf(h[k], e[k], s);
+        row[0] = s - ssm_corr(P, a);
+    }
+    __syncthreads();
+    ssm_ce_row(row, P.dlogits + (long)b * n1, n1, P.inv_b, P.loss_rows + b, red, bc);
 }
 
 // roles by blockIdx.x: [0, tilesA) dE of candidate tiles (64 candidates x 64 dims), [tilesA, tilesA + tilesB) dh slabs
@@ -252,4 +260,151 @@ __global__ void __launch_bounds__(ROW_THREADS) ssm_bwd_kernel(const SsmP P) {
         const float v = P.dlogits[(long)b * n1] * P.H[(long)b * P.ldh + k];
         if (v != 0.f) atomicAdd(P.acc + (long)a * d + k, lookup_fix(v));
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same head inside the catalogue-sharded step (include/bsarec_shard.h, bsarec_shard_ssm_*): every rank draws the same
+// N candidates, gathers their rows and its B answer rows out of the owners' shards (shard_ssm_gather_kernel,
+// catalogue_shard.h) into rows R [B + N][d] (answers first), and runs the head on its own B rows only.  The product tiles,
+// the draw and the corrections are the ones above; the differences: E is R (row b = E[a_b], row B + j = E[n_j]), and the
+// gradient of the candidate columns is this rank's dense partial g^T H (no fixed-point accumulator: the owners sum the W
+// partials, shard_ssm_pull_kernel).  SsmP fields used: H, ldh, E = R, answers, pop_cum, B, V, d, N, logq, inv_b = 1 / Bg,
+// cand, corr, logits, dlogits, loss_rows, slab, nslab, chunk, tilesA, tilesB.
+
+// one lane per draw: cand[j], corr[j] of the step (key from the caller, step = state[1] read here); lane 0 resets the lazy
+// row count of the step (null: dense Adam) before anything marks
+__global__ void __launch_bounds__(ROW_THREADS) shard_ssm_draw_kernel(const SsmP P, uint64_t key, int* lazy_count) {
+    const int j = blockIdx.x * ROW_THREADS + threadIdx.x;
+    if (lazy_count && j == 0) *lazy_count = 0;
+    if (j >= P.N) return;
+    const int it = ssm_draw(P, (uint32_t)key, (uint32_t)(key >> 32), (uint32_t)P.state[1], j);
+    P.cand[j] = it;
+    P.corr[j] = ssm_corr(P, it);
+}
+
+// grid (ceil(N / 64), ceil(B / 64)): x_bj = h_b . R[B + j] - c(n_j), -inf on an accidental hit (the tiles of ssm_logits_kernel)
+__global__ void __launch_bounds__(ROW_THREADS) shard_ssm_logits_kernel(const SsmP P) {
+    __shared__ __attribute__((aligned(16))) float As[SSM_KS][SSM_LDP];
+    __shared__ __attribute__((aligned(16))) float Bs[SSM_KS][SSM_LDP];
+    __shared__ int it_s[SSM_TILE];
+    __shared__ float c_s[SSM_TILE];
+    __shared__ long long ans_s[SSM_TILE];
+    const int tid = threadIdx.x, col0 = blockIdx.x * SSM_TILE, row0 = blockIdx.y * SSM_TILE;
+    const int B = P.B, d = P.d;
+    if (tid < SSM_TILE) {
+        const int j = col0 + tid, b = row0 + tid;
+        it_s[tid] = j < P.N ? P.cand[j] : 0;
+        c_s[tid] = j < P.N ? P.corr[j] : 0.f;
+        ans_s[tid] = b < B ? (long long)P.answers[b] : -1;
+    }
+    __syncthreads();
+    float acc[4][4] = {};
+    ssm_tile<true, true>(d,
+        [&](int k, int m) { return row0 + m < B && k < d ? P.H[(long)(row0 + m) * P.ldh + k] : 0.f; },
+        [&](int k, int m) { return col0 + m < P.N && k < d ? P.E[(long)(B + col0 + m) * d + k] : 0.f; }, As, Bs, acc);
+    const int r0 = (tid >> 4) * 4, c0 = (tid & 15) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int b = row0 + r0 + i;
+        if (b >= B) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j;
+            if (col0 + c >= P.N) continue;
+            const float x = (long long)it_s[c] == ans_s[r0 + i] ? -INFINITY : acc[i][j] - c_s[c];
+            P.logits[(long)b * (P.N + 1) + 1 + col0 + c] = x;
+        }
+    }
+}
+
+// one workgroup per row: x_b0 = h_b . R[b] - c(a_b) (sequential fmaf, as ssm_ce_kernel), then the row's cross-entropy
+__global__ void __launch_bounds__(ROW_THREADS) shard_ssm_ce_kernel(const SsmP P) {
+    __shared__ float red[ROW_THREADS / 64];
+    __shared__ float bc;
+    const int b = blockIdx.x, tid = threadIdx.x, n1 = P.N + 1;
+    float* row = P.logits + (long)b * n1;
+    if (tid == 0) {
+        int a = (int)P.answers[b];
+        a = a < 0 ? 0 : (a >= P.V ? P.V - 1 : a);
+        const float* h = P.H + (long)b * P.ldh;
+        const float* e = P.E + (long)b * P.d;
+        float s = 0.f;
+        for (int k = 0; k < P.d; ++k) s = fmaf(h[k], e[k], s);
+        row[0] = s - ssm_corr(P, a);
+    }
+    __syncthreads();
+    ssm_ce_row(row, P.dlogits + (long)b * n1, n1, P.inv_b, P.loss_rows + b, red, bc);
+}
+
+// roles by blockIdx.x, as ssm_bwd_kernel: [0, tilesA) this rank's partial gradient of candidate tiles, G[B + c][k] =
+// sum_b g[b][1 + c] h_b[k] (K = B in one workgroup: a fixed order), [tilesA, tilesA + tilesB) the dh slabs (slab 0 with the
+// answer term g_b0 R[b]), then the answer rows G[b][k] = g_b0 h_b[k] (grid-stride over B d).  G [B + N][d] is overwritten.
+__global__ void __launch_bounds__(ROW_THREADS) shard_ssm_bwd_kernel(const SsmP P, float* __restrict__ G) {
+    __shared__ __attribute__((aligned(16))) float As[SSM_KS][SSM_LDP];
+    __shared__ __attribute__((aligned(16))) float Bs[SSM_KS][SSM_LDP];
+    const int tid = threadIdx.x, B = P.B, d = P.d, n1 = P.N + 1, dt = (d + SSM_TILE - 1) / SSM_TILE;
+    const int r0 = (tid >> 4) * 4, c0 = (tid & 15) * 4;
+    int blk = blockIdx.x;
+    if (blk < P.tilesA) {
+        const int cand0 = (blk / dt) * SSM_TILE, k0 = (blk % dt) * SSM_TILE;
+        float acc[4][4] = {};
+        ssm_tile<false, false>(B,
+            [&](int k, int m) { return cand0 + m < P.N ? P.dlogits[(long)k * n1 + 1 + cand0 + m] : 0.f; },
+            [&](int k, int m) { return k0 + m < d ? P.H[(long)k * P.ldh + k0 + m] : 0.f; }, As, Bs, acc);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = cand0 + r0 + i;
+            if (c >= P.N) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (k0 + c0 + j < d) G[(long)(B + c) * d + k0 + c0 + j] = acc[i][j];
+        }
+        return;
+    }
+    blk -= P.tilesA;
+    if (blk < P.tilesB) {
+        const int rt = (B + SSM_TILE - 1) / SSM_TILE;
+        const int s = blk / (rt * dt), rem = blk % (rt * dt), row0 = (rem / dt) * SSM_TILE, k0 = (rem % dt) * SSM_TILE;
+        const int cbeg = s * P.chunk, cend = min(P.N, cbeg + P.chunk);
+        float acc[4][4] = {};
+        for (int cb = cbeg; cb < cend; cb += SSM_TILE) {
+            const int cn = min(SSM_TILE, cend - cb);
+            ssm_tile<true, false>(cn,
+                [&](int k, int m) { return row0 + m < B ? P.dlogits[(long)(row0 + m) * n1 + 1 + cb + k] : 0.f; },
+                [&](int k, int m) { return k0 + m < d ? P.E[(long)(B + cb + k) * d + k0 + m] : 0.f; }, As, Bs, acc);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b = row0 + r0 + i;
+            if (b >= B) continue;
+            const float ga = s == 0 ? P.dlogits[(long)b * n1] : 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k = k0 + c0 + j;
+                if (k >= d) continue;
+                float v = acc[i][j];
+                if (s == 0) v = fmaf(ga, P.E[(long)b * d + k], v);
+                P.slab[(long)s * B * d + (long)b * d + k] = v;
+            }
+        }
+        return;
+    }
+    blk -= P.tilesB;
+    const int tilesC = gridDim.x - P.tilesA - P.tilesB;
+    const long n = (long)B * d, nthr = (long)tilesC * ROW_THREADS;
+    for (long e = (long)blk * ROW_THREADS + tid; e < n; e += nthr) {
+        const int b = (int)(e / d), k = (int)(e % d);
+        G[e] = P.dlogits[(long)b * n1] * P.H[(long)b * P.ldh + k];
+    }
+}
+
+// dh[b * lddh + k] = sum of the nslab slabs [nslab][B][d] in slab order (one float4 per lane)
+__global__ void __launch_bounds__(ROW_THREADS)
+shard_ssm_dh_kernel(const float* __restrict__ slab, int nslab, int B, int d4, float* __restrict__ dh, long lddh) {
+    const long i = (long)blockIdx.x * ROW_THREADS + threadIdx.x, n4 = (long)B * d4;
+    if (i >= n4) return;
+    f32x4 a = ld4(slab + 4 * i);
+    for (int s = 1; s < nslab; ++s) a += ld4(slab + ((long)s * n4 + i) * 4);
+    const long b = i / d4;
+    st4(dh + b * lddh + (i - b * d4) * 4, a);
 }
