@@ -188,7 +188,7 @@ struct bsarec_plan {
     int* ssm_cand = nullptr; float *ssm_corr = nullptr, *ssm_logits = nullptr, *ssm_dlogits = nullptr;
     const int64_t* pop_cum = nullptr;          // bsarec_plan_set_train_sampler (train_sampler = 1)
     const int64_t* ssm_answers = nullptr;      // answers of the last sampled loss (the backward reads them)
-    int ssm_nslab = 0, ssm_chunk = 0;          // split-K slabs of d(h_last) and the candidate columns per slab
+    int ssm_nslab = 0;                         // split-K slabs of d(h_last) (ssm_split with the cap of plan_ssm_params)
     // lazy Adam (cfg.train_lazy_adam = 1; lazy_adam.h): the touched-row marks and list, used while a step runs lazily
     LazyRows lazy = {};
     bool lazy_now = false;                     // set by bsarec_train_step / _indexed around their launches (LazyStep)
@@ -241,6 +241,14 @@ static bool fused_shape_ok(const bsarec_config_t& c) {
     return c.cutoff_bins <= FUSED_MAX_CB;
 }
 
+// sampled head: d(h_last) split-K over the candidates, at most cap (<= SSM_SLAB_MAX) slabs of >= 256 candidate columns
+#define SSM_SLAB_MAX 32
+static void ssm_split(int N, int cap, int* nslab, int* chunk) {
+    const int want = std::max(1, std::min(cap, N / 256));
+    *chunk = (int)rup(cdiv(N, want), SSM_KS);
+    *nslab = cdiv(N, *chunk);
+}
+
 static void derive(bsarec_plan& p) {
     const bsarec_config_t& c = p.cfg;
     p.fused = fused_shape_ok(c);
@@ -274,12 +282,9 @@ static void derive(bsarec_plan& p) {
     if (vc < 64) vc = 64;
     p.vchunk = (int)vc;
     p.vsplit = cdiv(p.Vp, p.vchunk);
-    // sampled head: d(h_last) in at most vsplit (<= 32) slabs of >= 256 candidate columns, so the readers' slab count holds
-    if (c.train_negatives > 0) {
-        const int N = c.train_negatives, want = std::max(1, std::min(std::min(p.vsplit, 32), N / 256));
-        p.ssm_chunk = (int)rup(cdiv(N, want), SSM_KS);
-        p.ssm_nslab = cdiv(N, p.ssm_chunk);
-    }
+    // sampled head: at most vsplit slabs, so the readers' slab count holds
+    int chunk;
+    if (c.train_negatives > 0) ssm_split(c.train_negatives, std::min(p.vsplit, SSM_SLAB_MAX), &p.ssm_nslab, &chunk);
 }
 
 static void carve(bsarec_plan& p, char* base, size_t* total) {
@@ -1018,19 +1023,29 @@ extern "C" int bsarec_logits(bsarec_plan_t* p, void* stream) {
     return launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_LOGITS, true);
 }
 
-static SsmP ssm_params(const bsarec_plan& p, const int64_t* answers) {
-    const bsarec_config_t& c = p.cfg;
+// The head's parameters (sampled_softmax.h): B of the Bg rows of the global batch against the item rows E, d(h_last) in at
+// most slab_cap slabs.  The output buffers, the gradient sink and the stream state are the caller's to add.
+static SsmP ssm_params(const float* h, long ldh, int B, int Bg, const float* E, const int64_t* answers, const int* cand,
+                       const float* corr, int N, long V, const int64_t* pop_cum, int logq, int d, int slab_cap) {
     SsmP P;
     memset(&P, 0, sizeof(P));
-    P.H = p.X[c.layers] + (long)(c.seq_len - 1) * c.hidden; P.ldh = (long)c.seq_len * c.hidden; P.E = p.P.item_emb;
-    P.answers = answers; P.pop_cum = c.train_sampler == 1 ? p.pop_cum : nullptr; P.state = p.state;
-    P.B = c.batch; P.V = c.item_size; P.d = c.hidden; P.N = c.train_negatives; P.logq = c.train_no_logq ? 0 : 1;
-    P.inv_b = 1.0f / (float)c.batch;
-    P.cand = p.ssm_cand; P.corr = p.ssm_corr; P.logits = p.ssm_logits; P.dlogits = p.ssm_dlogits; P.loss_rows = p.loss_rows;
-    P.slab = p.dlast_slab; P.nslab = p.ssm_nslab; P.chunk = p.ssm_chunk; P.acc = p.lookup_acc;
-    const int dt = cdiv(c.hidden, SSM_TILE);
-    P.tilesA = cdiv(c.train_negatives, SSM_TILE) * dt;
-    P.tilesB = p.ssm_nslab * cdiv(c.batch, SSM_TILE) * dt;
+    P.H = h; P.ldh = ldh; P.E = E; P.answers = answers; P.pop_cum = pop_cum;
+    P.B = B; P.V = (int)V; P.d = d; P.N = N; P.logq = logq ? 1 : 0; P.inv_b = 1.0f / (float)Bg;
+    P.cand = const_cast<int*>(cand); P.corr = const_cast<float*>(corr);
+    ssm_split(N, slab_cap, &P.nslab, &P.chunk);
+    const int dt = cdiv(d, SSM_TILE);
+    P.tilesA = cdiv(N, SSM_TILE) * dt;
+    P.tilesB = P.nslab * cdiv(B, SSM_TILE) * dt;
+    return P;
+}
+
+static SsmP plan_ssm_params(const bsarec_plan& p, const int64_t* answers) {
+    const bsarec_config_t& c = p.cfg;
+    SsmP P = ssm_params(p.X[c.layers] + (long)(c.seq_len - 1) * c.hidden, (long)c.seq_len * c.hidden, c.batch, c.batch,
+                        p.P.item_emb, answers, p.ssm_cand, p.ssm_corr, c.train_negatives, c.item_size,
+                        c.train_sampler == 1 ? p.pop_cum : nullptr, !c.train_no_logq, c.hidden, std::min(p.vsplit, SSM_SLAB_MAX));
+    P.state = p.state; P.logits = p.ssm_logits; P.dlogits = p.ssm_dlogits; P.loss_rows = p.loss_rows;
+    P.slab = p.dlast_slab; P.acc = p.lookup_acc;
     if (p.lazy_now) {                          // lazy Adam step: reset the row count in the loss, mark T in the backward
         P.lazy = p.lazy; P.ids32 = p.ids32; P.nids = p.T;
         P.tilesM = (int)std::min<long>(cdiv((long)p.T + c.batch + c.train_negatives, ROW_THREADS), 64);
@@ -1044,10 +1059,10 @@ static int loss_impl(bsarec_plan_t* p, const int64_t* answers, void* stream, boo
     if (p->cfg.train_negatives > 0) {          // sampled softmax (sampled_softmax.h): draws + logits, then the rows' CE
         RET(sampled_refusal(*p));
         p->loss_kind = 2; p->ssm_answers = answers;
-        const SsmP P = ssm_params(*p, answers);
-        LAUNCH(ssm_logits_kernel, dim3(cdiv(P.N, SSM_TILE), cdiv(P.B, SSM_TILE)), dim3(ROW_THREADS), 0, s, P);
+        const SsmP P = plan_ssm_params(*p, answers);
+        LAUNCH(ssm_logits_kernel<false>, dim3(cdiv(P.N, SSM_TILE), cdiv(P.B, SSM_TILE)), dim3(ROW_THREADS), 0, s, P);
         HIPCHK(hipGetLastError());
-        LAUNCH(ssm_ce_kernel, dim3(P.B), dim3(ROW_THREADS), 0, s, P);
+        LAUNCH(ssm_ce_kernel<false>, dim3(P.B), dim3(ROW_THREADS), 0, s, P);
         HIPCHK(hipGetLastError());
         if (with_mean) LAUNCH(loss_mean_kernel, dim3(1), dim3(ROW_THREADS), 0, s, p->loss_rows, P.B, p->loss);
         return (int)hipGetLastError();
@@ -1173,9 +1188,9 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
     } else if (p->loss_kind == 2) {
         // sampled softmax: candidate and answer rows of dE into the fixed-point accumulator (the item table's dense part is
         // zero: the final reduction writes the accumulator over it), and the slabs of d(h_last)
-        SsmP P = ssm_params(*p, p->ssm_answers);
+        const SsmP P = plan_ssm_params(*p, p->ssm_answers);
         const int tilesC = std::max(1, std::min(cdiv((long)B * d, ROW_THREADS), 64));
-        LAUNCH(ssm_bwd_kernel, dim3(P.tilesA + P.tilesB + tilesC + P.tilesM), dim3(ROW_THREADS), 0, s, P);
+        LAUNCH(ssm_bwd_kernel<false>, dim3(P.tilesA + P.tilesB + tilesC + P.tilesM), dim3(ROW_THREADS), 0, s, P);
         HIPCHK(hipGetLastError());
     } else if (direct_logits) {
         // fused shape: dE = dlogits^T . h_last (K = B rows, written straight into the gradient buffer) and the split-K
@@ -1959,8 +1974,8 @@ extern "C" int bsarec_shard_head_bwd(const float* dlogits, long ld, int Bg, int 
         e.c_split = (long)Bg * d;
         RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s)));
     }
-    const long n4 = (long)Bg * d / 4;
-    LAUNCH(shard_slab_sum_kernel, dim3(cdiv(n4, ROW_THREADS)), dim3(ROW_THREADS), 0, s, scratch, ns, n4, dh);
+    LAUNCH(shard_slab_sum_kernel, dim3(cdiv((long)Bg * d / 4, ROW_THREADS)), dim3(ROW_THREADS), 0, s, scratch, ns, Bg, d / 4, dh,
+           (long)d);
     return (int)hipGetLastError();
 }
 
@@ -1981,27 +1996,10 @@ extern "C" int bsarec_shard_scatter_rows(const int64_t* ids_all, long n, int wor
 // sampled-softmax head of the catalogue-sharded step (include/bsarec_shard.h; sampled_softmax.h, catalogue_shard.h,
 // lazy_adam.h)
 // ---------------------------------------------------------------------------------------------
-// dh split-K over the candidates: the single-GPU plan's rule (sampled head of bsarec_plan) without its vsplit cap
-static void shard_ssm_split(int N, int* nslab, int* chunk) {
-    const int want = std::max(1, std::min(32, N / 256));
-    *chunk = (int)rup(cdiv(N, want), SSM_KS);
-    *nslab = cdiv(N, *chunk);
-}
-
-static SsmP shard_ssm_params(const float* h, long ldh, int B, int Bg, const float* rows, const int64_t* answers, const int* cand,
-                             const float* corr, int N, long V, const int64_t* pop_cum, int logq, int d) {
-    SsmP P;
-    memset(&P, 0, sizeof(P));
-    P.H = h; P.ldh = ldh; P.E = rows; P.answers = answers; P.pop_cum = pop_cum;
-    P.B = B; P.V = (int)V; P.d = d; P.N = N; P.logq = logq ? 1 : 0; P.inv_b = 1.0f / (float)Bg;
-    P.cand = const_cast<int*>(cand); P.corr = const_cast<float*>(corr);
-    return P;
-}
-
 extern "C" int bsarec_shard_ssm_draw(uint64_t key, const uint64_t* state, int N, long V, const int64_t* pop_cum, int logq,
                                      int* cand, float* corr, int* lazy_count, void* stream) {
     if (!state || !cand || !corr || N < 1 || N > SSM_NEG_MAX || V < 2 || V > INT32_MAX) return -10;
-    SsmP P = shard_ssm_params(nullptr, 0, 1, 1, nullptr, nullptr, cand, corr, N, V, pop_cum, logq, 4);
+    SsmP P = ssm_params(nullptr, 0, 1, 1, nullptr, nullptr, cand, corr, N, V, pop_cum, logq, 4, SSM_SLAB_MAX);
     P.state = state;
     LAUNCH(shard_ssm_draw_kernel, dim3(cdiv(N, ROW_THREADS)), dim3(ROW_THREADS), 0, (hipStream_t)stream, P, key, lazy_count);
     return (int)hipGetLastError();
@@ -2025,11 +2023,11 @@ extern "C" int bsarec_shard_ssm_head(const float* h, long ldh, int B, int Bg, co
     if (!h || !rows || !answers || !cand || !corr || !logits || !dlogits || !loss_rows) return -10;
     if (B < 1 || Bg < B || N < 1 || N > SSM_NEG_MAX || V < 2 || V > INT32_MAX || d < 4 || (d & 3) || ldh < d) return -10;
     hipStream_t s = (hipStream_t)stream;
-    SsmP P = shard_ssm_params(h, ldh, B, Bg, rows, answers, cand, corr, N, V, pop_cum, logq, d);
+    SsmP P = ssm_params(h, ldh, B, Bg, rows, answers, cand, corr, N, V, pop_cum, logq, d, SSM_SLAB_MAX);
     P.logits = logits; P.dlogits = dlogits; P.loss_rows = loss_rows;
-    LAUNCH(shard_ssm_logits_kernel, dim3(cdiv(N, SSM_TILE), cdiv(B, SSM_TILE)), dim3(ROW_THREADS), 0, s, P);
+    LAUNCH(ssm_logits_kernel<true>, dim3(cdiv(N, SSM_TILE), cdiv(B, SSM_TILE)), dim3(ROW_THREADS), 0, s, P);
     HIPCHK(hipGetLastError());
-    LAUNCH(shard_ssm_ce_kernel, dim3(B), dim3(ROW_THREADS), 0, s, P);
+    LAUNCH(ssm_ce_kernel<true>, dim3(B), dim3(ROW_THREADS), 0, s, P);
     return (int)hipGetLastError();
 }
 
@@ -2042,7 +2040,7 @@ extern "C" int bsarec_shard_ssm_loss(const float* loss_rows_all, int Bg, float* 
 extern "C" long bsarec_shard_ssm_bwd_scratch_floats(int B, int N, int d) {
     if (B < 1 || N < 1 || N > SSM_NEG_MAX || d < 4) return -10;
     int ns, ch;
-    shard_ssm_split(N, &ns, &ch);
+    ssm_split(N, SSM_SLAB_MAX, &ns, &ch);
     return (long)ns * B * d;
 }
 
@@ -2051,17 +2049,13 @@ extern "C" int bsarec_shard_ssm_bwd(const float* dlogits, int B, int N, const fl
     if (!dlogits || !h || !rows || !dh || !grad_rows || !scratch) return -10;
     if (B < 1 || N < 1 || N > SSM_NEG_MAX || d < 4 || (d & 3) || ldh < d || lddh < d || (lddh & 3)) return -10;
     hipStream_t s = (hipStream_t)stream;
-    SsmP P = shard_ssm_params(h, ldh, B, B, rows, nullptr, nullptr, nullptr, N, 2, nullptr, 0, d);
-    P.dlogits = const_cast<float*>(dlogits); P.slab = scratch;
-    shard_ssm_split(N, &P.nslab, &P.chunk);
-    const int dt = cdiv(d, SSM_TILE);
-    P.tilesA = cdiv(N, SSM_TILE) * dt;
-    P.tilesB = P.nslab * cdiv(B, SSM_TILE) * dt;
+    SsmP P = ssm_params(h, ldh, B, B, rows, nullptr, nullptr, nullptr, N, 2, nullptr, 0, d, SSM_SLAB_MAX);
+    P.dlogits = const_cast<float*>(dlogits); P.slab = scratch; P.G = grad_rows;
     const int tilesC = std::max(1, std::min(cdiv((long)B * d, ROW_THREADS), 64));
-    LAUNCH(shard_ssm_bwd_kernel, dim3(P.tilesA + P.tilesB + tilesC), dim3(ROW_THREADS), 0, s, P, grad_rows);
+    LAUNCH(ssm_bwd_kernel<true>, dim3(P.tilesA + P.tilesB + tilesC), dim3(ROW_THREADS), 0, s, P);
     HIPCHK(hipGetLastError());
-    const long n4 = (long)B * d / 4;
-    LAUNCH(shard_ssm_dh_kernel, dim3(cdiv(n4, ROW_THREADS)), dim3(ROW_THREADS), 0, s, scratch, P.nslab, B, d / 4, dh, lddh);
+    LAUNCH(shard_slab_sum_kernel, dim3(cdiv((long)B * d / 4, ROW_THREADS)), dim3(ROW_THREADS), 0, s, scratch, P.nslab, B, d / 4, dh,
+           lddh);
     return (int)hipGetLastError();
 }
 

@@ -121,17 +121,18 @@ shard_ce_grad_kernel(float* __restrict__ logits, long ld, int Vs, const int64_t*
     if (tid == 0) loss_rows[b] = lse - tgt;
 }
 
-// sum of split-K slabs [nsplit][n] -> out[n]
+// out[b * ldo + k] = sum of the nslab split-K slabs [nslab][B][d] in slab order (one float4 per lane, d4 = d / 4)
 __global__ void __launch_bounds__(ROW_THREADS)
-shard_slab_sum_kernel(const float* __restrict__ slabs, int nsplit, long n4, float* __restrict__ out) {
-    const long i = (long)blockIdx.x * ROW_THREADS + threadIdx.x;
+shard_slab_sum_kernel(const float* __restrict__ slab, int nslab, int B, int d4, float* __restrict__ out, long ldo) {
+    const long i = (long)blockIdx.x * ROW_THREADS + threadIdx.x, n4 = (long)B * d4;
     if (i >= n4) return;
-    f32x4 a = ld4(slabs + 4 * i);
-    for (int s = 1; s < nsplit; ++s) a += ld4(slabs + ((long)s * n4 + i) * 4);
-    st4(out + 4 * i, a);
+    f32x4 a = ld4(slab + 4 * i);
+    for (int s = 1; s < nslab; ++s) a += ld4(slab + ((long)s * n4 + i) * 4);
+    const long b = i / d4;
+    st4(out + b * ldo + (i - b * d4) * 4, a);
 }
 
-// ---- sampled-softmax head of the sharded step (sampled_softmax.h, shard_ssm_*; include/bsarec_shard.h) -----------------
+// ---- sampled-softmax head of the sharded step (sampled_softmax.h; include/bsarec_shard.h) ---------------------------
 
 // Rows of the head, read out of the owners' shards (system scope, as shard_gather_rows_kernel): R[b] = E[answers[b]] for
 // b < B, R[B + j] = E[cand[j]], ids clamped to [0, V).
@@ -176,22 +177,10 @@ shard_ssm_pull_kernel(const int64_t* __restrict__ ans_all, int B, int world, con
     unsafeAtomicAdd(dst + 0, g.x); unsafeAtomicAdd(dst + 1, g.y); unsafeAtomicAdd(dst + 2, g.z); unsafeAtomicAdd(dst + 3, g.w);
 }
 
-// Lazy Adam of the shard: mark the owned rows of the step -- the looked-up ids_all [nids] (!= 0), ans_all [Bg] and cand [N],
-// clamped to [0, V) -- at their local index (lazy_mark_wave).  Grid-stride from wave-aligned starts (every lane of a wave
-// takes the same trips: the ballot).
+// Lazy Adam of the shard: mark the owned rows of the step -- the looked-up ids_all [nids] (!= 0), ans_all [Bg] and cand [N]
+// -- at their local index (lazy_mark_role, lazy_adam.h).
 __global__ void __launch_bounds__(ROW_THREADS)
 shard_lazy_mark_kernel(const int64_t* __restrict__ ids_all, long nids, const int64_t* __restrict__ ans_all, int Bg,
                        const int* __restrict__ cand, int N, long lo, long Vs, long V, const LazyRows T) {
-    const long total = nids + Bg + N, stride = (long)gridDim.x * ROW_THREADS;
-    for (long e0 = (long)blockIdx.x * ROW_THREADS + (threadIdx.x & ~63); e0 < total; e0 += stride) {
-        const long e = e0 + (threadIdx.x & 63);
-        long id = 0;
-        bool valid = e < total;
-        if (valid) {
-            id = e < nids ? (long)ids_all[e] : (e < nids + Bg ? (long)ans_all[e - nids] : (long)cand[e - nids - Bg]);
-            id = id < 0 ? 0 : (id >= V ? V - 1 : id);
-            valid = (e >= nids || id != 0) && id >= lo && id < lo + Vs;
-        }
-        lazy_mark_wave(T, valid ? (int)(id - lo) : 0, valid);
-    }
+    lazy_mark_role(T, ids_all, nids, ans_all, Bg, cand, N, V, lo, Vs, blockIdx.x, gridDim.x);
 }

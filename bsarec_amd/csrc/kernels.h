@@ -520,12 +520,9 @@ __device__ __forceinline__ bool lookup_take(unsigned long long* acc, long i4, f3
 __device__ __forceinline__ void lookup_flush(const LookupAcc& la, long first, long stride) {
     f32x4 add;
     if (la.lazy.rows) {
-        const int d4 = la.lazy.d4;
-        const long n = (long)min(*la.lazy.count, la.lazy.cap) * d4;
-        for (long k = first; k < n; k += stride) {
-            const long i = (long)la.lazy.rows[k / d4] * d4 + k % d4;
+        lazy_rows_walk(la.lazy, first, stride, [&](int, int, long i) {
             st4(la.dst + 4 * i, lookup_take(la.acc, i, add) ? add : f32x4{0, 0, 0, 0});
-        }
+        });
         return;
     }
     for (long i = first; i < la.n4; i += stride) {
@@ -885,18 +882,13 @@ reduce_adam_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ b
     if (A.lazy.rows) {
         // lazy Adam: the rows of T (marked by this step's ssm_bwd_kernel) -- their accumulator rows taken and zeroed, their
         // gradient rows written (dense_zero: the accumulator alone), updated once, unmarked
-        const int d4 = A.lazy.d4;
-        const long n = (long)min(*A.lazy.count, A.lazy.cap) * d4;
-        for (long k = (long)(blockIdx.x - nblocks) * ROW_THREADS + threadIdx.x; k < n; k += nb * ROW_THREADS) {
-            const int r = A.lazy.rows[k / d4], q = (int)(k % d4);
-            const long i = (long)r * d4 + q, o = A.item_off + 4 * i;
-            f32x4 wi = ld4(A.w + o), mi = ld4(A.m + o), vi = ld4(A.v + o), gi = {0, 0, 0, 0};
-            if (A.lookup_acc) lookup_take(A.lookup_acc, i, gi);
-            st4(A.g + o, gi);
-            lazy_adam4(wi, mi, vi, gi, A.b1, A.b2, A.eps, A.wd, step_size, bc2s);
-            st4(A.w + o, wi); st4(A.m + o, mi); st4(A.v + o, vi);
-            if (q == 0) A.lazy.mark[r] = 0;
-        }
+        lazy_adam_rows(A.lazy, (long)(blockIdx.x - nblocks) * ROW_THREADS + threadIdx.x, nb * ROW_THREADS, A.w, A.m, A.v, A.item_off,
+                       A.b1, A.b2, A.eps, A.wd, step_size, bc2s, [&](long i, long o) {
+                           f32x4 gi = {0, 0, 0, 0};
+                           if (A.lookup_acc) lookup_take(A.lookup_acc, i, gi);
+                           st4(A.g + o, gi);
+                           return gi;
+                       });
         return;
     }
     for (long i = (long)(blockIdx.x - nblocks) * ROW_THREADS + threadIdx.x; i < A.item_n4; i += nb * ROW_THREADS) {

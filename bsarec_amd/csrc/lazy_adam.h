@@ -8,7 +8,7 @@
 //                  pass clears the marks of the listed rows again.
 //   lookup flush   (kernels.h, LookupAcc.lazy) the fixed-point accumulator -> the gradient rows of T, not the V rows
 //   lazy Adam      reduce_adam_kernel's item arm (fused indexed step, kernels.h) or lazy_adam_kernel here (every other step
-//                  shape): the arithmetic of adam_kernel on the rows of T only (lazy_adam4)
+//                  shape): the arithmetic of adam_kernel on the rows of T only (lazy_adam_rows, lazy_adam4)
 // Rows are listed in arbitrary order; each row's update is independent of the others, so the step stays bit-deterministic.
 // The restatement in numpy is tests/lazy_adam_ref.py.
 #pragma once
@@ -38,22 +38,35 @@ __device__ __forceinline__ void lazy_mark_wave(const LazyRows& T, int r, bool va
     }
 }
 
-// The marking role over ids32 [nids] (0 = padding, not marked), answers [B] (clamped to [0, V)) and cand [N]: element e of
-// the concatenation, grid-stride from wave-aligned starts so that every lane of a wave takes the same trips.
-__device__ __forceinline__ void lazy_mark_role(const LazyRows& T, const int* __restrict__ ids32, long nids,
+// The marking role over ids [nids] (0 = padding, not marked), answers [B] and cand [N], clamped to [0, V): element e of the
+// concatenation, grid-stride from wave-aligned starts so that every lane of a wave takes the same trips.  Only ids of the
+// owned window [lo, lo + Vs) are marked, at their local index (the plan owns [0, V)).
+template <class I>
+__device__ __forceinline__ void lazy_mark_role(const LazyRows& T, const I* __restrict__ ids, long nids,
                                                const int64_t* __restrict__ answers, int B, const int* __restrict__ cand, int N,
-                                               int V, int blk, int nblk) {
+                                               long V, long lo, long Vs, int blk, int nblk) {
     const long total = nids + B + N, stride = (long)nblk * ROW_THREADS;
     for (long e0 = (long)blk * ROW_THREADS + (threadIdx.x & ~63); e0 < total; e0 += stride) {
         const long e = e0 + (threadIdx.x & 63);
-        int r = 0;
+        long id = 0;
         bool valid = e < total;
         if (valid) {
-            if (e < nids) { r = ids32[e]; valid = r != 0; }
-            else if (e < nids + B) { const long long a = answers[e - nids]; r = a < 0 ? 0 : (a >= V ? V - 1 : (int)a); }
-            else { r = cand[e - nids - B]; r = r < 0 ? 0 : (r >= V ? V - 1 : r); }
+            id = e < nids ? (long)ids[e] : (e < nids + B ? (long)answers[e - nids] : (long)cand[e - nids - B]);
+            id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+            valid = (e >= nids || id != 0) && id >= lo && id < lo + Vs;
         }
-        lazy_mark_wave(T, r, valid);
+        lazy_mark_wave(T, valid ? (int)(id - lo) : 0, valid);
+    }
+}
+
+// The rows of T, grid-stride from `first`: fn(r, q, i) for float4 group q of listed row r, i = r d4 + q its group index
+template <class F>
+__device__ __forceinline__ void lazy_rows_walk(const LazyRows& T, long first, long stride, F fn) {
+    const int d4 = T.d4;
+    const long n = (long)min(*T.count, T.cap) * d4;
+    for (long k = first; k < n; k += stride) {
+        const int r = T.rows[k / d4], q = (int)(k % d4);
+        fn(r, q, (long)r * d4 + q);
     }
 }
 
@@ -65,6 +78,27 @@ __device__ __forceinline__ void lazy_adam4(f32x4& wi, f32x4& mi, f32x4& vi, f32x
     vi = b2 * vi + (1.0f - b2) * gi * gi;
 #pragma unroll
     for (int k = 0; k < 4; ++k) wi[k] -= step_size * (mi[k] / (sqrtf(vi[k]) / bc2s + eps));
+}
+
+// Adam of the float4 group at element offset o of w / m / v with gradient gi
+__device__ __forceinline__ void lazy_adam_at(float* w, float* m, float* v, long o, f32x4 gi, float b1, float b2, float eps, float wd,
+                                             float step_size, float bc2s) {
+    f32x4 wi = ld4(w + o), mi = ld4(m + o), vi = ld4(v + o);
+    lazy_adam4(wi, mi, vi, gi, b1, b2, eps, wd, step_size, bc2s);
+    st4(w + o, wi); st4(m + o, mi); st4(v + o, vi);
+}
+
+// The step's last pass over T: Adam of every listed row of the item table at element offset off of w / m / v, then the row's
+// mark cleared.  grad(i, o) returns the gradient of group i (element offset o = off + 4 i) and leaves the gradient row as
+// the caller wants it after the step.
+template <class FG>
+__device__ __forceinline__ void lazy_adam_rows(const LazyRows& T, long first, long stride, float* w, float* m, float* v, long off,
+                                               float b1, float b2, float eps, float wd, float step_size, float bc2s, FG grad) {
+    lazy_rows_walk(T, first, stride, [&](int r, int q, long i) {
+        const long o = off + 4 * i;
+        lazy_adam_at(w, m, v, o, grad(i, o), b1, b2, eps, wd, step_size, bc2s);
+        if (q == 0) T.mark[r] = 0;
+    });
 }
 
 // The plan-aware Adam of a lazy step whose update is not fused into the gradient reduction: blocks [0, dense_blocks) run
@@ -85,47 +119,26 @@ lazy_adam_kernel(const uint64_t* __restrict__ state, const LazyAdamP A) {
         const long lo4 = A.item_off / 4, skip4 = A.item_n / 4, n4 = (A.n - A.item_n) / 4;
         for (long j = (long)blockIdx.x * ROW_THREADS + threadIdx.x; j < n4; j += (long)A.dense_blocks * ROW_THREADS) {
             const long o = 4 * (j < lo4 ? j : j + skip4);
-            f32x4 gi = ld4(A.g + o);
-            gi = gi * A.gscale;
-            f32x4 wi = ld4(A.w + o), mi = ld4(A.m + o), vi = ld4(A.v + o);
-            lazy_adam4(wi, mi, vi, gi, A.b1, A.b2, A.eps, A.wd, step_size, bc2s);
-            st4(A.w + o, wi); st4(A.m + o, mi); st4(A.v + o, vi);
+            lazy_adam_at(A.w, A.m, A.v, o, ld4(A.g + o) * A.gscale, A.b1, A.b2, A.eps, A.wd, step_size, bc2s);
         }
         return;
     }
-    const int nb = gridDim.x - A.dense_blocks, d4 = A.T.d4;
-    const long n = (long)min(*A.T.count, A.T.cap) * d4;
-    for (long k = (long)(blockIdx.x - A.dense_blocks) * ROW_THREADS + threadIdx.x; k < n; k += (long)nb * ROW_THREADS) {
-        const int r = A.T.rows[k / d4], q = (int)(k % d4);
-        const long o = A.item_off + 4 * ((long)r * d4 + q);
-        f32x4 gi = ld4(A.g + o);
-        gi = gi * A.gscale;
-        f32x4 wi = ld4(A.w + o), mi = ld4(A.m + o), vi = ld4(A.v + o);
-        lazy_adam4(wi, mi, vi, gi, A.b1, A.b2, A.eps, A.wd, step_size, bc2s);
-        st4(A.w + o, wi); st4(A.m + o, mi); st4(A.v + o, vi);
-        if (q == 0) A.T.mark[r] = 0;                               // the last pass of the step over T: unmark
-    }
+    const long nb = gridDim.x - A.dense_blocks;
+    lazy_adam_rows(A.T, (long)(blockIdx.x - A.dense_blocks) * ROW_THREADS + threadIdx.x, nb * ROW_THREADS, A.w, A.m, A.v, A.item_off,
+                   A.b1, A.b2, A.eps, A.wd, step_size, bc2s, [&](long, long o) { return ld4(A.g + o) * A.gscale; });
 }
 
 // Lazy Adam of a catalogue shard (include/bsarec_shard.h, bsarec_shard_lazy_adam): the rows of T (marked by
-// shard_lazy_mark_kernel, catalogue_shard.h) of the shard's w / m / v with its gradient g, the arithmetic of lazy_adam4 and the
-// corrections of the step's tick (state[3]); the last pass of the step over T -- the gradient rows are zeroed and the marks
-// cleared.  Rows outside T are not read.
+// shard_lazy_mark_kernel, catalogue_shard.h) of the shard's w / m / v with its gradient g and the corrections of the step's
+// tick (state[3]); the gradient rows are zeroed.  Rows outside T are not read.
 struct ShardLazyAdamP { float *w, *g, *m, *v; float b1, b2, eps, wd; LazyRows T; };
 __global__ void __launch_bounds__(ROW_THREADS)
 shard_lazy_adam_kernel(const uint64_t* __restrict__ state, const ShardLazyAdamP A) {
     const float* f = reinterpret_cast<const float*>(state + 3);
-    const float step_size = f[0], bc2s = f[1];
-    const int d4 = A.T.d4;
-    const long n = (long)min(*A.T.count, A.T.cap) * d4;
-    for (long k = (long)blockIdx.x * ROW_THREADS + threadIdx.x; k < n; k += (long)gridDim.x * ROW_THREADS) {
-        const int r = A.T.rows[k / d4], q = (int)(k % d4);
-        const long o = 4 * ((long)r * d4 + q);
-        const f32x4 gi = ld4(A.g + o);
-        f32x4 wi = ld4(A.w + o), mi = ld4(A.m + o), vi = ld4(A.v + o);
-        lazy_adam4(wi, mi, vi, gi, A.b1, A.b2, A.eps, A.wd, step_size, bc2s);
-        st4(A.w + o, wi); st4(A.m + o, mi); st4(A.v + o, vi);
-        st4(A.g + o, f32x4{0.f, 0.f, 0.f, 0.f});
-        if (q == 0) A.T.mark[r] = 0;
-    }
+    lazy_adam_rows(A.T, (long)blockIdx.x * ROW_THREADS + threadIdx.x, (long)gridDim.x * ROW_THREADS, A.w, A.m, A.v, 0, A.b1, A.b2,
+                   A.eps, A.wd, f[0], f[1], [&](long, long o) {
+                       const f32x4 gi = ld4(A.g + o);
+                       st4(A.g + o, f32x4{0.f, 0.f, 0.f, 0.f});
+                       return gi;
+                   });
 }
