@@ -2,6 +2,7 @@
 
     python -m bsarec_amd.build          # -> bsarec_amd/libbsarec_hip.so
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -9,10 +10,9 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "bsarec_hip.hip")
-DEPS = [os.path.join(HERE, "csrc", f) for f in ("bsarec_hip.hip", "common.h", "gemm.h", "epilogues.h", "kernels.h", "fused_layer.h", "dw_direct.h", "fused_top.h", "fused_chain.h", "comm.h", "catalogue_shard.h", "sampled_rank.h", "sampled_softmax.h", "lazy_adam.h", "full_rank.h")]
-DEPS.append(os.path.join(os.path.dirname(HERE), "include", "bsarec_hip.h"))
-DEPS.append(os.path.join(os.path.dirname(HERE), "include", "bsarec_comm.h"))
-DEPS.append(os.path.join(os.path.dirname(HERE), "include", "bsarec_shard.h"))
+# every source and header of the library: a change to any of them makes the built library stale
+DEPS = sorted(glob.glob(os.path.join(HERE, "csrc", "*.hip")) + glob.glob(os.path.join(HERE, "csrc", "*.h")) +
+              glob.glob(os.path.join(os.path.dirname(HERE), "include", "*.h")))
 OUT = os.path.join(HERE, "libbsarec_hip.so")
 
 

@@ -50,86 +50,6 @@ struct ProfState {                    // per plan (bsarec_profile_select / _read
     size_t used = 0;
     ~ProfState() { for (auto& e : events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } }
 };
-static ProfState* prof_of(bsarec_plan* p);
-static bool bf_products_of(const bsarec_plan* p);     // cfg.storage = 1 on the generic tiled path: bf16 products (gemm.h)
-
-struct ProfScope {
-    hipStream_t s; bool on; hipEvent_t stop;
-    ProfScope(int kclass, hipStream_t st) : s(st), on(false) {
-        ProfState* ps = t_plan ? prof_of(t_plan) : nullptr;
-        on = ps && kclass != BSAREC_K_NONE && kclass == ps->kclass;
-        if (!on) return;
-        if (ps->used == ps->events.size()) {
-            hipEvent_t a, b;
-            (void)hipEventCreate(&a); (void)hipEventCreate(&b);
-            ps->events.push_back({a, b});
-        }
-        (void)hipEventRecord(ps->events[ps->used].first, s);
-        stop = ps->events[ps->used].second;
-        ++ps->used;
-    }
-    ~ProfScope() { if (on) (void)hipEventRecord(stop, s); }
-};
-
-// ---------------------------------------------------------------------------------------------
-// GEMM launcher
-// ---------------------------------------------------------------------------------------------
-static GemmP gemm_defaults(int M, int N, int K) {
-    GemmP P;
-    memset(&P, 0, sizeof(P));
-    P.M = M; P.N = N; P.K = K; P.Nb = N; P.Kv = K;
-    P.nseg = 1; P.nprob = 1; P.nsplit = 1; P.kchunk = K; P.nh = 1;
-    return P;
-}
-
-template <int BM, int BN, int WM, int WN, bool AKM, bool BKM, int AXF, int BXF, bool BG, bool BF, class Epi>
-static int launch_gemm_as(const GemmP& P, const XformP& X, const Epi& epi, float* bgrad, int nbatch, hipStream_t s, int kclass) {
-    auto kern = gemm_kernel<BM, BN, WM, WN, AKM, BKM, AXF, BXF, BG, BF, Epi>;
-    constexpr size_t smem = GemmSmem<BM, BN, AKM, BKM, BF>::BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (smem > 48 * 1024)
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_done = true;
-    }
-    if (P.M <= 0 || P.N <= 0) return 0;
-    dim3 grid(cdiv(P.M, BM), cdiv(P.N, BN), nbatch * P.nprob * P.nsplit);
-    if (g_dry) return 0;
-    ProfScope prof(kclass, s);
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), smem, s, P, X, epi, bgrad);
-    return (int)hipGetLastError();
-}
-
-// fp32_only: the products of the loss head (logits and their backward) stay fp32 in the bf16-product mode, as they do under
-// the fused bf16 storage
-template <int BM, int BN, int WM, int WN, bool AKM, bool BKM, int AXF, int BXF, bool BG, class Epi>
-static int launch_gemm(const GemmP& P, const XformP& X, const Epi& epi, float* bgrad, int nbatch, hipStream_t s,
-                       int kclass = BSAREC_K_NONE, bool fp32_only = false) {
-    if (!fp32_only && t_plan && bf_products_of(t_plan)) {
-        // token-parallel products (M = B L rows, one problem): a 64 x 64 tile issues ~120 instructions and 16 KB of fp32 operand
-        // loads per 0.26 MFLOP k-step, which is what bounds it once the matrix time is gone -- 128 x 128 tiles quarter that
-        if constexpr (BM == 64 && BN == 64 && !BG)
-            if (P.M >= 8192 && P.N >= 128 && nbatch == 1)
-                return launch_gemm_as<128, 128, WM, WN, AKM, BKM, AXF, BXF, BG, true, Epi>(P, X, epi, bgrad, nbatch, s, kclass);
-        return launch_gemm_as<BM, BN, WM, WN, AKM, BKM, AXF, BXF, BG, true, Epi>(P, X, epi, bgrad, nbatch, s, kclass);
-    }
-    // fp32, 256-wide tiles (LayerNorm / softmax / dS epilogues at hidden or L > 128): 8 waves as 2 x 4 -- the 92 KB of
-    // fp32 staging allow one workgroup per CU, and four waves at 344 registers left every SIMD with a single wave
-    if constexpr (BN == 256 && WM * WN == 4)
-        return launch_gemm_as<BM, BN, 2, 4, AKM, BKM, AXF, BXF, BG, false, Epi>(P, X, epi, bgrad, nbatch, s, kclass);
-    else
-        return launch_gemm_as<BM, BN, WM, WN, AKM, BKM, AXF, BXF, BG, false, Epi>(P, X, epi, bgrad, nbatch, s, kclass);
-}
-
-static XformP no_xform() { XformP X; memset(&X, 0, sizeof(X)); return X; }
-
-template <bool BIAS, bool ADD, bool GGRAD>
-static EpiLinear<BIAS, ADD, GGRAD> epi_linear(float* C, long ldc) {
-    EpiLinear<BIAS, ADD, GGRAD> e;
-    memset(&e, 0, sizeof(e));
-    e.C[0] = C; e.ldc = ldc;
-    return e;
-}
 
 // ---------------------------------------------------------------------------------------------
 // plan
@@ -159,7 +79,6 @@ struct bsarec_plan {
     // backward scratch (shared by all layers)
     float *dXa, *dXb, *dz, *dT, *dU, *dH, *dXacc, *dO, *dF, *dC, *dS, *dq, *dk, *dv, *dXtmp, *dlast_slab;
     float *slab_wL[BSAREC_MAX_LAYERS], *slab_bL[BSAREC_MAX_LAYERS], *part_lnL[BSAREC_MAX_LAYERS], *part_betaL[BSAREC_MAX_LAYERS];
-    float *slab_w, *slab_b, *part_ln, *part_beta;   // the current layer's set (selected by the backward loop)
     float *part_ln0, *part_pos, *trash;
     int pos_slices;
     ReduceJob* jobs; int jobs_per_layer;
@@ -193,14 +112,99 @@ struct bsarec_plan {
     LazyRows lazy = {};
     bool lazy_now = false;                     // set by bsarec_train_step / _indexed around their launches (LazyStep)
 };
-static ProfState* prof_of(bsarec_plan* p) { return &p->prof; }
-static bool bf_products_of(const bsarec_plan* p) { return p->bf_products; }
 struct PlanScope {                           // marks the plan a C call works on for this thread (nesting-safe)
     bsarec_plan* prev;
     explicit PlanScope(bsarec_plan* p) : prev(t_plan) { t_plan = p; }
     ~PlanScope() { t_plan = prev; }
 };
 
+struct ProfScope {
+    hipStream_t s; bool on; hipEvent_t stop;
+    ProfScope(int kclass, hipStream_t st) : s(st), on(false) {
+        ProfState* ps = t_plan ? &t_plan->prof : nullptr;
+        on = ps && kclass != BSAREC_K_NONE && kclass == ps->kclass;
+        if (!on) return;
+        if (ps->used == ps->events.size()) {
+            hipEvent_t a, b;
+            (void)hipEventCreate(&a); (void)hipEventCreate(&b);
+            ps->events.push_back({a, b});
+        }
+        (void)hipEventRecord(ps->events[ps->used].first, s);
+        stop = ps->events[ps->used].second;
+        ++ps->used;
+    }
+    ~ProfScope() { if (on) (void)hipEventRecord(stop, s); }
+};
+
+// ---------------------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------------------
+// Launch of a kernel with dynamic LDS: raises the kernel's limit when smem exceeds the 48 KiB default and the largest size
+// this instantiation has asked for so far, then launches unless this is the dry pass.  The raise must not first happen under
+// graph capture: bsarec_plan_create's dry pass walks every launch sequence a step of that plan can take.
+template <auto Kernel, class... A>
+static int launch_lds(dim3 grid, dim3 block, size_t smem, hipStream_t s, const A&... a) {
+    static size_t raised = 0;
+    if (smem > 48 * 1024 && smem > raised) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        raised = smem;
+    }
+    if (g_dry) return 0;
+    hipLaunchKernelGGL(Kernel, grid, block, smem, s, a...);
+    return (int)hipGetLastError();
+}
+
+static GemmP gemm_defaults(int M, int N, int K) {
+    GemmP P;
+    memset(&P, 0, sizeof(P));
+    P.M = M; P.N = N; P.K = K; P.Nb = N; P.Kv = K;
+    P.nseg = 1; P.nprob = 1; P.nsplit = 1; P.kchunk = K; P.nh = 1;
+    return P;
+}
+
+template <int BM, int BN, int WM, int WN, bool AKM, bool BKM, int AXF, int BXF, bool BG, bool BF, class Epi>
+static int launch_gemm_as(const GemmP& P, const XformP& X, const Epi& epi, float* bgrad, int nbatch, hipStream_t s, int kclass) {
+    if (P.M <= 0 || P.N <= 0) return 0;
+    const dim3 grid(cdiv(P.M, BM), cdiv(P.N, BN), nbatch * P.nprob * P.nsplit);
+    ProfScope prof(g_dry ? BSAREC_K_NONE : kclass, s);
+    return launch_lds<gemm_kernel<BM, BN, WM, WN, AKM, BKM, AXF, BXF, BG, BF, Epi>>(grid, dim3(64 * WM * WN),
+                                                                                  GemmSmem<BM, BN, AKM, BKM, BF>::BYTES, s, P, X, epi, bgrad);
+}
+
+// fp32_only: the products of the loss head (logits and their backward) stay fp32 in the bf16-product mode, as they do under
+// the fused bf16 storage
+template <int BM, int BN, int WM, int WN, bool AKM, bool BKM, int AXF, int BXF, bool BG, class Epi>
+static int launch_gemm(const GemmP& P, const XformP& X, const Epi& epi, float* bgrad, int nbatch, hipStream_t s,
+                       int kclass = BSAREC_K_NONE, bool fp32_only = false) {
+    if (!fp32_only && t_plan && t_plan->bf_products) {
+        // token-parallel products (M = B L rows, one problem): a 64 x 64 tile issues ~120 instructions and 16 KB of fp32 operand
+        // loads per 0.26 MFLOP k-step, which is what bounds it once the matrix time is gone -- 128 x 128 tiles quarter that
+        if constexpr (BM == 64 && BN == 64 && !BG)
+            if (P.M >= 8192 && P.N >= 128 && nbatch == 1)
+                return launch_gemm_as<128, 128, WM, WN, AKM, BKM, AXF, BXF, BG, true, Epi>(P, X, epi, bgrad, nbatch, s, kclass);
+        return launch_gemm_as<BM, BN, WM, WN, AKM, BKM, AXF, BXF, BG, true, Epi>(P, X, epi, bgrad, nbatch, s, kclass);
+    }
+    // fp32, 256-wide tiles (LayerNorm / softmax / dS epilogues at hidden or L > 128): 8 waves as 2 x 4 -- the 92 KB of
+    // fp32 staging allow one workgroup per CU, and four waves at 344 registers left every SIMD with a single wave
+    if constexpr (BN == 256 && WM * WN == 4)
+        return launch_gemm_as<BM, BN, 2, 4, AKM, BKM, AXF, BXF, BG, false, Epi>(P, X, epi, bgrad, nbatch, s, kclass);
+    else
+        return launch_gemm_as<BM, BN, WM, WN, AKM, BKM, AXF, BXF, BG, false, Epi>(P, X, epi, bgrad, nbatch, s, kclass);
+}
+
+static XformP no_xform() { XformP X; memset(&X, 0, sizeof(X)); return X; }
+
+template <bool BIAS, bool ADD, bool GGRAD>
+static EpiLinear<BIAS, ADD, GGRAD> epi_linear(float* C, long ldc) {
+    EpiLinear<BIAS, ADD, GGRAD> e;
+    memset(&e, 0, sizeof(e));
+    e.C[0] = C; e.ldc = ldc;
+    return e;
+}
+
+// ---------------------------------------------------------------------------------------------
+// plan: configuration checks, derived sizes, workspace carve, creation
+// ---------------------------------------------------------------------------------------------
 struct Carver {
     char* base; size_t off;
     explicit Carver(char* b) : base(b), off(0) {}
@@ -321,7 +325,6 @@ static void carve(bsarec_plan& p, char* base, size_t* total) {
         p.part_lnL[l] = cv.take<float>((long)p.nblk * 6 * d);        // gamma/beta partials of the 3 LayerNorms
         p.part_betaL[l] = cv.take<float>(B * d);
     }
-    p.slab_w = p.slab_wL[0]; p.slab_b = p.slab_bL[0]; p.part_ln = p.part_lnL[0]; p.part_beta = p.part_betaL[0];
     p.part_ln0 = cv.take<float>((long)p.nblk * 2 * d);
     p.pos_slices = cdiv(B, 64);
     p.part_pos = cv.take<float>((long)p.pos_slices * L * d);
@@ -363,7 +366,7 @@ extern "C" size_t bsarec_workspace_bytes(const bsarec_config_t* cfg) {
     return total;
 }
 
-// slab sub-offsets (floats) inside slab_w / slab_b, per split-K slice
+// slab sub-offsets (floats) inside a layer's slab_wL / slab_bL, per split-K slice
 struct SlabMap { long wq, wk, wv, wo, w1, w2, wtot, bq, bk, bv, bo, b1, b2, btot; };
 static SlabMap slab_map(long d) {
     SlabMap m;
@@ -373,8 +376,19 @@ static SlabMap slab_map(long d) {
 }
 
 // Split-K slabs are stored [tensor][split][elements] so that one reduce job reads a fixed stride.
-static float* slab_w_ptr(const bsarec_plan& p, long tensor_off) { return p.slab_w + tensor_off * p.nsplit; }
-static float* slab_b_ptr(const bsarec_plan& p, long tensor_off) { return p.slab_b + tensor_off * p.nsplit; }
+static float* slab_w_ptr(const bsarec_plan& p, int l, long tensor_off) { return p.slab_wL[l] + tensor_off * p.nsplit; }
+static float* slab_b_ptr(const bsarec_plan& p, int l, long tensor_off) { return p.slab_bL[l] + tensor_off * p.nsplit; }
+
+// LayerNorm gamma / beta partials, planes of [nblk][d]: six per layer in part_lnL[l] (feed-forward, attention, filter), two of
+// the embedding LayerNorm in part_ln0
+enum LnPart { LN_FF_G, LN_FF_B, LN_A_G, LN_A_B, LN_F_G, LN_F_B };
+enum Ln0Part { LN_E_G, LN_E_B };
+static float* ln_part(const bsarec_plan& p, int l, LnPart k) { return p.part_lnL[l] + (long)k * p.nblk * p.cfg.hidden; }
+static float* ln0_part(const bsarec_plan& p, Ln0Part k) { return p.part_ln0 + (long)k * p.nblk * p.cfg.hidden; }
+
+// h_last: row L-1 of every sequence of the last layer's output [B][L][d], as a [B][d] matrix of row stride L d
+static const float* h_last(const bsarec_plan& p) { return p.X[p.cfg.layers] + (long)(p.cfg.seq_len - 1) * p.cfg.hidden; }
+static long h_last_stride(const bsarec_plan& p) { return (long)p.cfg.seq_len * p.cfg.hidden; }
 
 extern "C" int bsarec_plan_create(bsarec_plan_t** out, const bsarec_config_t* cfg, const bsarec_tensors_t* params,
                                   const bsarec_tensors_t* grads, const bsarec_tensors_t* shadow, void* workspace,
@@ -413,23 +427,22 @@ extern "C" int bsarec_plan_create(bsarec_plan_t** out, const bsarec_config_t* cf
     const int ns = p->nsplit, nb = p->nblk;
     for (int l = 0; l < cfg->layers; ++l) {
         const bsarec_layer_t& g = p->G.layer[l];
-        p->slab_w = p->slab_wL[l]; p->slab_b = p->slab_bL[l]; p->part_ln = p->part_lnL[l]; p->part_beta = p->part_betaL[l];
-        add(p->part_beta, g.sqrt_beta, cfg->batch, d);
-        add(p->part_ln + 4L * nb * d, g.filter_ln_w, nb, d);
-        add(p->part_ln + 5L * nb * d, g.filter_ln_b, nb, d);
-        add(slab_w_ptr(*p, sm.wq), g.query_w, ns, d * d); add(slab_b_ptr(*p, sm.bq), g.query_b, ns, d);
-        add(slab_w_ptr(*p, sm.wk), g.key_w, ns, d * d);   add(slab_b_ptr(*p, sm.bk), g.key_b, ns, d);
-        add(slab_w_ptr(*p, sm.wv), g.value_w, ns, d * d); add(slab_b_ptr(*p, sm.bv), g.value_b, ns, d);
-        add(slab_w_ptr(*p, sm.wo), g.dense_w, ns, d * d); add(slab_b_ptr(*p, sm.bo), g.dense_b, ns, d);
-        add(p->part_ln + 2L * nb * d, g.attn_ln_w, nb, d);
-        add(p->part_ln + 3L * nb * d, g.attn_ln_b, nb, d);
-        add(slab_w_ptr(*p, sm.w1), g.ffn1_w, ns, 4 * d * d); add(slab_b_ptr(*p, sm.b1), g.ffn1_b, ns, 4 * d);
-        add(slab_w_ptr(*p, sm.w2), g.ffn2_w, ns, 4 * d * d); add(slab_b_ptr(*p, sm.b2), g.ffn2_b, ns, d);
-        add(p->part_ln + 0L * nb * d, g.ffn_ln_w, nb, d);
-        add(p->part_ln + 1L * nb * d, g.ffn_ln_b, nb, d);
+        add(p->part_betaL[l], g.sqrt_beta, cfg->batch, d);
+        add(ln_part(*p, l, LN_F_G), g.filter_ln_w, nb, d);
+        add(ln_part(*p, l, LN_F_B), g.filter_ln_b, nb, d);
+        add(slab_w_ptr(*p, l, sm.wq), g.query_w, ns, d * d); add(slab_b_ptr(*p, l, sm.bq), g.query_b, ns, d);
+        add(slab_w_ptr(*p, l, sm.wk), g.key_w, ns, d * d);   add(slab_b_ptr(*p, l, sm.bk), g.key_b, ns, d);
+        add(slab_w_ptr(*p, l, sm.wv), g.value_w, ns, d * d); add(slab_b_ptr(*p, l, sm.bv), g.value_b, ns, d);
+        add(slab_w_ptr(*p, l, sm.wo), g.dense_w, ns, d * d); add(slab_b_ptr(*p, l, sm.bo), g.dense_b, ns, d);
+        add(ln_part(*p, l, LN_A_G), g.attn_ln_w, nb, d);
+        add(ln_part(*p, l, LN_A_B), g.attn_ln_b, nb, d);
+        add(slab_w_ptr(*p, l, sm.w1), g.ffn1_w, ns, 4 * d * d); add(slab_b_ptr(*p, l, sm.b1), g.ffn1_b, ns, 4 * d);
+        add(slab_w_ptr(*p, l, sm.w2), g.ffn2_w, ns, 4 * d * d); add(slab_b_ptr(*p, l, sm.b2), g.ffn2_b, ns, d);
+        add(ln_part(*p, l, LN_FF_G), g.ffn_ln_w, nb, d);
+        add(ln_part(*p, l, LN_FF_B), g.ffn_ln_b, nb, d);
     }
-    add(p->part_ln0 + 0L * nb * d, p->G.ln_w, nb, d);
-    add(p->part_ln0 + 1L * nb * d, p->G.ln_b, nb, d);
+    add(ln0_part(*p, LN_E_G), p->G.ln_w, nb, d);
+    add(ln0_part(*p, LN_E_B), p->G.ln_b, nb, d);
     if (p->scatter_in_block) {   // the position gradient = sum over the batch of the embedding gradient rows the block kernel wrote
         ReduceJob j; j.src = p->dz; j.dst = p->G.pos_emb; j.nsplit = cfg->batch; j.len = (int)((long)cfg->seq_len * d);
         j.stride = (long)cfg->seq_len * d; j.scale = 1.f; j.pad = 0;
@@ -608,32 +621,16 @@ template <int LPR>
 static int launch_freq_fwd(const float* X, const float* sb, const float* g, const float* be, float eps, DropP drop,
                            const float* tw, int B, int L, int d, int cb, float* dsp, float* xhat, float* rstd, hipStream_t s,
                            const float* cw = nullptr) {
-    auto kern = freq_fwd_kernel<LPR>;
-    const size_t smem = freq_smem(L, d, cb, 1);
-    static size_t attr = 0;
-    if (smem > 48 * 1024 && smem > attr) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr = smem;
-    }
-    LAUNCH(kern, dim3(B), dim3(ROW_THREADS), smem, s, X, sb, g, be, eps, drop, tw, L, d, cb, dsp, xhat, rstd, cw);
-    return (int)hipGetLastError();
+    return launch_lds<freq_fwd_kernel<LPR>>(dim3(B), dim3(ROW_THREADS), freq_smem(L, d, cb, 1), s, X, sb, g, be, eps, drop, tw, L, d,
+                                            cb, dsp, xhat, rstd, cw);
 }
 
 template <int LPR>
 static int launch_freq_bwd(const float* X, const float* dF, const float* dXin, const float* sb, const float* tw, int B, int L,
                            int d, int cb, float* dX, float* pbeta, hipStream_t s, const float* cw = nullptr, float* pcw = nullptr) {
-    auto kern = freq_bwd_kernel<LPR>;
-    const size_t smem = freq_smem(L, d, cb, 2);
-    static size_t attr = 0;
-    if (smem > 48 * 1024 && smem > attr) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr = smem;
-    }
-    LAUNCH(kern, dim3(B), dim3(ROW_THREADS), smem, s, X, dF, dXin, sb, tw, L, d, cb, dX, pbeta, cw, pcw);
-    return (int)hipGetLastError();
+    return launch_lds<freq_bwd_kernel<LPR>>(dim3(B), dim3(ROW_THREADS), freq_smem(L, d, cb, 2), s, X, dF, dXin, sb, tw, L, d, cb, dX,
+                                            pbeta, cw, pcw);
 }
-
-static bool fused_ok(const bsarec_plan& p) { return p.fused; }
 
 // Host-side check of everything a direct (buffer-descriptor) kernel is about to dereference.  These kernels prefetch
 // without predicates and rely on the descriptor's range check; a descriptor whose BASE is null with a non-zero range
@@ -656,216 +653,149 @@ static bool dh_problem_ok(const DhP& h) {
     return true;
 }
 
-static void fill_top_fwd(bsarec_plan& p, int l, bool tr, TopFwdP& F);
+// head size (x storage x product mode) of the block kernels as the compile-time constants DH (, BF, X3)
+#define DISPATCH_DH(dh, ...) \
+    do { switch (dh) { case 16: { constexpr int DH = 16; __VA_ARGS__; } break; \
+                       case 32: { constexpr int DH = 32; __VA_ARGS__; } break; \
+                       default: { constexpr int DH = 64; __VA_ARGS__; } break; } } while (0)
+#define DISPATCH_BLOCK(p, ...) \
+    do { if ((p).bf) { constexpr bool BF = true, X3 = false; DISPATCH_DH((p).dh, __VA_ARGS__); } \
+         else if ((p).cfg.x3_products) { constexpr bool BF = false, X3 = true; DISPATCH_DH((p).dh, __VA_ARGS__); } \
+         else { constexpr bool BF = false, X3 = false; DISPATCH_DH((p).dh, __VA_ARGS__); } } while (0)
+
+// What the parameter structs of the four block kernels (FusedFwdP, TopFwdP, FusedBwdP, TopBwdP: same field names) share:
+// block l's weights (wm: where the Linear weights come from), saved activations, shape, dropout sites and stamp slot.
+// Everything else is zero; `u` and whatever one kernel alone reads are the caller's to set.
+template <bool FWD, class BlockP>
+static void fill_block(const bsarec_plan& p, int l, bool tr, const bsarec_layer_t& wm, BlockP& F) {
+    const bsarec_config_t& c = p.cfg;
+    const bsarec_layer_t& w = p.P.layer[l];
+    const LayerBufs& b = p.lb[l];
+    memset(&F, 0, sizeof(F));
+    F.X = p.X[l];
+    F.sqrt_beta = w.sqrt_beta; F.f_g = w.filter_ln_w; F.wq = wm.query_w; F.wk = wm.key_w; F.wv = wm.value_w; F.wo = wm.dense_w;
+    F.a_g = w.attn_ln_w; F.w1 = wm.ffn1_w; F.w2 = wm.ffn2_w; F.ff_g = w.ffn_ln_w; F.tw = p.twiddle;
+    F.xhat_f = b.xhat_f; F.rstd_f = b.rstd_f; F.q = b.q; F.k = b.k; F.v = b.v; F.probs = b.probs;
+    F.xhat_a = b.xhat_a; F.rstd_a = b.rstd_a; F.xhat_ff = b.xhat_ff; F.rstd_ff = b.rstd_ff;
+    F.L = c.seq_len; F.Lp = p.Lp; F.cb = c.cutoff_bins; F.heads = c.heads;
+    F.alpha = c.alpha; F.oma = (float)(1.0 - (double)c.alpha);
+    F.drop_f = make_drop(p, c.p_hidden, 1 + 4 * l, tr); F.drop_p = make_drop(p, c.p_attn, 2 + 4 * l, tr);
+    F.drop_o = make_drop(p, c.p_hidden, 3 + 4 * l, tr); F.drop_ff = make_drop(p, c.p_hidden, 4 + 4 * l, tr);
+    F.stamps = p.stamps ? p.stamps + 32 * (2 * l + (FWD ? 0 : 1)) : nullptr;
+    if constexpr (FWD) {       // the forward alone: the output, the biases and LayerNorm betas, the activations it saves
+        F.Xout = p.X[l + 1];
+        F.f_b = w.filter_ln_b; F.bq = w.query_b; F.bk = w.key_b; F.bv = w.value_b; F.bo = w.dense_b; F.a_b = w.attn_ln_b;
+        F.b1 = w.ffn1_b; F.b2 = w.ffn2_b; F.ff_b = w.ffn_ln_b;
+        F.ids32 = p.ids32; F.ctx = b.ctx; F.hmix = b.hmix; F.u = b.u;
+        F.eps = c.ln_eps;
+    }
+}
+
+// the backward's LayerNorm / sqrt_beta partials of block l (FusedBwdP, TopBwdP)
+template <class BlockP>
+static void fill_block_partials(const bsarec_plan& p, int l, BlockP& F) {
+    F.pg_ff = ln_part(p, l, LN_FF_G); F.pb_ff = ln_part(p, l, LN_FF_B); F.pg_a = ln_part(p, l, LN_A_G);
+    F.pb_a = ln_part(p, l, LN_A_B); F.pg_f = ln_part(p, l, LN_F_G); F.pb_f = ln_part(p, l, LN_F_B);
+    F.pbeta = p.part_betaL[l];
+}
+
+static void fill_top_fwd(bsarec_plan& p, int l, bool tr, TopFwdP& F) {
+    fill_block<true>(p, l, tr, p.P.layer[l], F);
+    F.low = p.lb[l].dsp;
+    F.wk_sh = p.S.layer[l].key_w; F.wv_sh = p.S.layer[l].value_w;
+}
 
 static int launch_fused_fwd(bsarec_plan& p, int l, bool tr, hipStream_t s, const int64_t* ids = nullptr, const GatherP* gp = nullptr,
                             bool top_tail = false /* block l + 1 is the pruned top block: run it as this launch's tail */) {
     const bsarec_config_t& c = p.cfg;
-    const bsarec_layer_t& w = p.P.layer[l];
-    const bsarec_layer_t& wm = p.bf ? p.S.layer[l] : w;      // MFMA operands: bf16 shadow of the Linear weights (storage = 1)
-    LayerBufs& b = p.lb[l];
     FusedFwdP F;
-    memset(&F, 0, sizeof(F));
-    F.X = p.X[l]; F.Xout = p.X[l + 1];
+    fill_block<true>(p, l, tr, p.bf ? p.S.layer[l] : p.P.layer[l], F);      // MFMA operands: bf16 shadow of the Linear weights (storage = 1)
     F.xout_f32 = (l == c.layers - 1);
-    F.sqrt_beta = w.sqrt_beta; F.f_g = w.filter_ln_w; F.f_b = w.filter_ln_b;
-    F.wq = wm.query_w; F.bq = w.query_b; F.wk = wm.key_w; F.bk = w.key_b; F.wv = wm.value_w; F.bv = w.value_b;
-    F.wo = wm.dense_w; F.bo = w.dense_b; F.a_g = w.attn_ln_w; F.a_b = w.attn_ln_b;
-    F.w1 = wm.ffn1_w; F.b1 = w.ffn1_b; F.w2 = wm.ffn2_w; F.b2 = w.ffn2_b; F.ff_g = w.ffn_ln_w; F.ff_b = w.ffn_ln_b;
-    F.tw = p.twiddle; F.ids32 = p.ids32;
-    F.xhat_f = b.xhat_f; F.rstd_f = b.rstd_f; F.q = b.q; F.k = b.k; F.v = b.v; F.probs = b.probs; F.ctx = b.ctx;
-    F.xhat_a = b.xhat_a; F.rstd_a = b.rstd_a; F.hmix = b.hmix; F.u = b.u; F.xhat_ff = b.xhat_ff; F.rstd_ff = b.rstd_ff;
-    F.gp = b.gp;
+    F.gp = p.lb[l].gp;
     F.dsp = nullptr;          // FrequencyLayer output stays in LDS on the fused path (BSAREC_BUF_DSP is generic-path only)
     if (l == 0 && gp) {       // the embedding front-end rides in the bottom block's phase 0
         F.e_E = p.P.item_emb; F.e_pos = p.P.pos_emb; F.e_g = p.P.ln_w; F.e_b = p.P.ln_b; F.e_ids = ids; F.e_gp = *gp;
         F.e_drop = make_drop(p, c.p_hidden, 0, tr); F.e_V = c.item_size;
         F.e_X0 = p.X[0]; F.e_xhat = p.xhat0; F.e_rstd = p.rstd0; F.e_ids32 = p.ids32;
     }
-    F.L = c.seq_len; F.Lp = p.Lp; F.cb = c.cutoff_bins; F.heads = c.heads;
-    F.alpha = c.alpha; F.oma = (float)(1.0 - (double)c.alpha); F.eps = c.ln_eps;
-    F.drop_f = make_drop(p, c.p_hidden, 1 + 4 * l, tr); F.drop_p = make_drop(p, c.p_attn, 2 + 4 * l, tr);
-    F.drop_o = make_drop(p, c.p_hidden, 3 + 4 * l, tr); F.drop_ff = make_drop(p, c.p_hidden, 4 + 4 * l, tr);
     F.trash = p.trash;
-    F.stamps = p.stamps ? p.stamps + 32 * (2 * l) : nullptr;
     TopFwdP TF;
     if (top_tail) fill_top_fwd(p, l + 1, tr, TF);
+    const dim3 grid(c.batch), block(512);
+    ProfScope prof(BSAREC_K_FUSED_FWD, s);
     if (c.filter_kind == 1) {        // FMLPRec block: whole-spectrum complex filter + feed-forward (no attention branch)
-        F.filter_cw = w.filter_cw;
-        const size_t fsm = fused_fwd_smem_bytes();
-        static bool attr_fm = false;
-        if (!attr_fm) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_layer_fwd_kernel<32, false, NoTail, false, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)fsm)); attr_fm = true; }
-        ProfScope prof(BSAREC_K_FUSED_FWD, s);
-        LAUNCH((fused_layer_fwd_kernel<32, false, NoTail, false, true>), dim3(c.batch), dim3(512), fsm, s, F, NoTail());
-        return (int)hipGetLastError();
+        F.filter_cw = p.P.layer[l].filter_cw;
+        return launch_lds<fused_layer_fwd_kernel<32, false, NoTail, false, true>>(grid, block, fused_fwd_smem_bytes(), s, F, NoTail());
     }
+    int rc = 0;
     if (!p.bf && c.chain_kernels && !c.x3_products) {
         // register-chain forward (fused_chain.h): one wave per 16-token tile, two workgroup barriers
         const size_t csm = fused_chain_fwd_smem_bytes(top_tail);
-#define CHAIN_FWD_CASE(DHV) { \
-        static bool attr = false, attr_t = false; \
-        if (!attr) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_chain_fwd_kernel<DHV, NoTail>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_chain_fwd_smem_bytes(false))); attr = true; } \
-        if (!attr_t) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_chain_fwd_kernel<DHV, TopFwdP>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_chain_fwd_smem_bytes(true))); attr_t = true; } \
-        ProfScope prof(BSAREC_K_FUSED_FWD, s); \
-        if (top_tail) LAUNCH((fused_chain_fwd_kernel<DHV, TopFwdP>), dim3(c.batch), dim3(512), csm, s, F, TF); \
-        else LAUNCH((fused_chain_fwd_kernel<DHV, NoTail>), dim3(c.batch), dim3(512), csm, s, F, NoTail()); }
-        if (p.dh == 16) CHAIN_FWD_CASE(16) else if (p.dh == 32) CHAIN_FWD_CASE(32) else CHAIN_FWD_CASE(64)
-#undef CHAIN_FWD_CASE
-        return (int)hipGetLastError();
+        DISPATCH_DH(p.dh, rc = top_tail ? launch_lds<fused_chain_fwd_kernel<DH, TopFwdP>>(grid, block, csm, s, F, TF)
+                                        : launch_lds<fused_chain_fwd_kernel<DH, NoTail>>(grid, block, csm, s, F, NoTail()));
+        return rc;
     }
     const size_t smem = fused_fwd_smem_bytes();
-#define FUSED_FWD_CASE(DHV, BFV, X3V) { \
-        static bool attr = false, attr_t = false; \
-        if (!attr) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_layer_fwd_kernel<DHV, BFV, NoTail, X3V>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); attr = true; } \
-        if (!attr_t) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_layer_fwd_kernel<DHV, BFV, TopFwdP, X3V>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); attr_t = true; } \
-        ProfScope prof(BSAREC_K_FUSED_FWD, s); \
-        if (top_tail) LAUNCH((fused_layer_fwd_kernel<DHV, BFV, TopFwdP, X3V>), dim3(c.batch), dim3(512), smem, s, F, TF); \
-        else LAUNCH((fused_layer_fwd_kernel<DHV, BFV, NoTail, X3V>), dim3(c.batch), dim3(512), smem, s, F, NoTail()); }
-    if (p.bf) { if (p.dh == 16) FUSED_FWD_CASE(16, true, false) else if (p.dh == 32) FUSED_FWD_CASE(32, true, false) else FUSED_FWD_CASE(64, true, false) }
-    else if (c.x3_products) { if (p.dh == 16) FUSED_FWD_CASE(16, false, true) else if (p.dh == 32) FUSED_FWD_CASE(32, false, true) else FUSED_FWD_CASE(64, false, true) }
-    else { if (p.dh == 16) FUSED_FWD_CASE(16, false, false) else if (p.dh == 32) FUSED_FWD_CASE(32, false, false) else FUSED_FWD_CASE(64, false, false) }
-#undef FUSED_FWD_CASE
-    return (int)hipGetLastError();
+    DISPATCH_BLOCK(p, rc = top_tail ? launch_lds<fused_layer_fwd_kernel<DH, BF, TopFwdP, X3>>(grid, block, smem, s, F, TF)
+                                    : launch_lds<fused_layer_fwd_kernel<DH, BF, NoTail, X3>>(grid, block, smem, s, F, NoTail()));
+    return rc;
 }
 
 static int launch_fused_bwd(bsarec_plan& p, int l, bool tr, const float* dY, float* dXout, hipStream_t s, bool top,
                             const TopBwdP* head = nullptr /* the pruned top block's backward runs as this launch's head */) {
     const bsarec_config_t& c = p.cfg;
-    const bsarec_layer_t& w = p.P.layer[l];
-    const bsarec_layer_t& wm = p.bf ? p.S.layer[l] : w;
-    LayerBufs& b = p.lb[l];
-    const long nb = p.nblk, d = c.hidden;
     FusedBwdP F;
-    memset(&F, 0, sizeof(F));
-    F.dY = dY; F.dX = dXout; F.X = p.X[l];
-    F.sqrt_beta = w.sqrt_beta; F.f_g = w.filter_ln_w; F.wq = wm.query_w; F.wk = wm.key_w; F.wv = wm.value_w; F.wo = wm.dense_w;
-    F.a_g = w.attn_ln_w; F.w1 = wm.ffn1_w; F.w2 = wm.ffn2_w; F.ff_g = w.ffn_ln_w; F.tw = p.twiddle;
-    F.xhat_f = b.xhat_f; F.rstd_f = b.rstd_f; F.q = b.q; F.k = b.k; F.v = b.v; F.probs = b.probs;
-    F.xhat_a = b.xhat_a; F.rstd_a = b.rstd_a; F.u = b.gp; F.xhat_ff = b.xhat_ff; F.rstd_ff = b.rstd_ff;
-    if (top) { F.dh_slabs = p.dlast_slab; F.dh_nsplit = head_nsplit(p); F.dh_stride = (long)c.batch * d; }
+    fill_block<false>(p, l, tr, p.bf ? p.S.layer[l] : p.P.layer[l], F);
+    fill_block_partials(p, l, F);
+    F.dY = dY; F.dX = dXout;
+    F.u = p.lb[l].gp;
+    if (top) { F.dh_slabs = p.dlast_slab; F.dh_nsplit = head_nsplit(p); F.dh_stride = (long)c.batch * c.hidden; }
     if (l == 0) {       // the embedding front-end's backward (Drop + LayerNorm) rides in the bottom block's epilogue
         F.e_dz = p.dz; F.e_xhat = p.xhat0; F.e_rstd = p.rstd0; F.e_g = p.P.ln_w;
-        F.e_pg = p.part_ln0; F.e_pb = p.part_ln0 + nb * d; F.e_drop = make_drop(p, c.p_hidden, 0, tr);
+        F.e_pg = ln0_part(p, LN_E_G); F.e_pb = ln0_part(p, LN_E_B); F.e_drop = make_drop(p, c.p_hidden, 0, tr);
         F.e_dx_extra = p.ext_dy ? p.ext_mid[0] : nullptr;
     }
     F.dT = p.dT; F.dU = p.dU; F.dO = p.dO; F.dq = p.dq; F.dk = p.dk; F.dv = p.dv;
-    F.pg_ff = p.part_ln + 0 * nb * d; F.pb_ff = p.part_ln + 1 * nb * d; F.pg_a = p.part_ln + 2 * nb * d;
-    F.pb_a = p.part_ln + 3 * nb * d; F.pg_f = p.part_ln + 4 * nb * d; F.pb_f = p.part_ln + 5 * nb * d;
-    F.pbeta = p.part_beta;
-    F.L = c.seq_len; F.Lp = p.Lp; F.cb = c.cutoff_bins; F.heads = c.heads;
-    F.alpha = c.alpha; F.oma = (float)(1.0 - (double)c.alpha);
-    F.drop_f = make_drop(p, c.p_hidden, 1 + 4 * l, tr); F.drop_p = make_drop(p, c.p_attn, 2 + 4 * l, tr);
-    F.drop_o = make_drop(p, c.p_hidden, 3 + 4 * l, tr); F.drop_ff = make_drop(p, c.p_hidden, 4 + 4 * l, tr);
     F.trash = p.trash;
-    F.stamps = p.stamps ? p.stamps + 32 * (2 * l + 1) : nullptr;
+    const dim3 grid(c.batch), block(512);
     const size_t smem = fused_bwd_smem_bytes();
+    ProfScope prof(BSAREC_K_FUSED_BWD, s);
     if (c.filter_kind == 1) {
-        F.filter_cw = w.filter_cw; F.pcw = p.part_cwL[l];
-        static bool attr_fm = false;
-        if (!attr_fm) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_layer_bwd_kernel<32, false, NoTail, false, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); attr_fm = true; }
-        ProfScope prof(BSAREC_K_FUSED_BWD, s);
-        LAUNCH((fused_layer_bwd_kernel<32, false, NoTail, false, true>), dim3(c.batch), dim3(512), smem, s, F, NoTail());
-        return (int)hipGetLastError();
+        F.filter_cw = p.P.layer[l].filter_cw; F.pcw = p.part_cwL[l];
+        return launch_lds<fused_layer_bwd_kernel<32, false, NoTail, false, true>>(grid, block, smem, s, F, NoTail());
     }
-#define FUSED_BWD_CASE(DHV, BFV, X3V) { \
-        static bool attr = false; \
-        if (!attr) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_layer_bwd_kernel<DHV, BFV, NoTail, X3V>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-                     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_layer_bwd_kernel<DHV, BFV, TopBwdP, X3V>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); attr = true; } \
-        ProfScope prof(BSAREC_K_FUSED_BWD, s); \
-        if (head) LAUNCH((fused_layer_bwd_kernel<DHV, BFV, TopBwdP, X3V>), dim3(c.batch), dim3(512), smem, s, F, *head); \
-        else LAUNCH((fused_layer_bwd_kernel<DHV, BFV, NoTail, X3V>), dim3(c.batch), dim3(512), smem, s, F, NoTail()); }
-    if (p.bf) { if (p.dh == 16) FUSED_BWD_CASE(16, true, false) else if (p.dh == 32) FUSED_BWD_CASE(32, true, false) else FUSED_BWD_CASE(64, true, false) }
-    else if (c.x3_products) { if (p.dh == 16) FUSED_BWD_CASE(16, false, true) else if (p.dh == 32) FUSED_BWD_CASE(32, false, true) else FUSED_BWD_CASE(64, false, true) }
-    else { if (p.dh == 16) FUSED_BWD_CASE(16, false, false) else if (p.dh == 32) FUSED_BWD_CASE(32, false, false) else FUSED_BWD_CASE(64, false, false) }
-#undef FUSED_BWD_CASE
-    return (int)hipGetLastError();
-}
-
-static void fill_top_fwd(bsarec_plan& p, int l, bool tr, TopFwdP& F) {
-    const bsarec_config_t& c = p.cfg;
-    const bsarec_layer_t& w = p.P.layer[l];
-    LayerBufs& b = p.lb[l];
-    memset(&F, 0, sizeof(F));
-    F.X = p.X[l]; F.Xout = p.X[l + 1];
-    F.sqrt_beta = w.sqrt_beta; F.f_g = w.filter_ln_w; F.f_b = w.filter_ln_b;
-    F.wq = w.query_w; F.bq = w.query_b; F.wk = w.key_w; F.bk = w.key_b; F.wv = w.value_w; F.bv = w.value_b;
-    F.wo = w.dense_w; F.bo = w.dense_b; F.a_g = w.attn_ln_w; F.a_b = w.attn_ln_b;
-    F.w1 = w.ffn1_w; F.b1 = w.ffn1_b; F.w2 = w.ffn2_w; F.b2 = w.ffn2_b; F.ff_g = w.ffn_ln_w; F.ff_b = w.ffn_ln_b;
-    F.tw = p.twiddle; F.ids32 = p.ids32;
-    F.xhat_f = b.xhat_f; F.rstd_f = b.rstd_f; F.q = b.q; F.k = b.k; F.v = b.v; F.probs = b.probs; F.ctx = b.ctx;
-    F.xhat_a = b.xhat_a; F.rstd_a = b.rstd_a; F.hmix = b.hmix; F.u = b.u; F.xhat_ff = b.xhat_ff; F.rstd_ff = b.rstd_ff;
-    F.low = b.dsp;
-    F.wk_sh = p.S.layer[l].key_w; F.wv_sh = p.S.layer[l].value_w;
-    F.L = c.seq_len; F.Lp = p.Lp; F.cb = c.cutoff_bins; F.heads = c.heads;
-    F.alpha = c.alpha; F.oma = (float)(1.0 - (double)c.alpha); F.eps = c.ln_eps;
-    F.drop_f = make_drop(p, c.p_hidden, 1 + 4 * l, tr); F.drop_p = make_drop(p, c.p_attn, 2 + 4 * l, tr);
-    F.drop_o = make_drop(p, c.p_hidden, 3 + 4 * l, tr); F.drop_ff = make_drop(p, c.p_hidden, 4 + 4 * l, tr);
-    F.stamps = p.stamps ? p.stamps + 32 * (2 * l) : nullptr;
+    int rc = 0;
+    DISPATCH_BLOCK(p, rc = head ? launch_lds<fused_layer_bwd_kernel<DH, BF, TopBwdP, X3>>(grid, block, smem, s, F, *head)
+                                : launch_lds<fused_layer_bwd_kernel<DH, BF, NoTail, X3>>(grid, block, smem, s, F, NoTail()));
+    return rc;
 }
 
 static int launch_top_fwd(bsarec_plan& p, int l, bool tr, hipStream_t s) {
-    const bsarec_config_t& c = p.cfg;
     TopFwdP F;
     fill_top_fwd(p, l, tr, F);
-    const size_t smem = top_fwd_smem_bytes();
-#define TOP_FWD_CASE(DHV, BFV) { \
-        static bool attr = false; \
-        if (!attr) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(top_fwd_kernel<DHV, BFV>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); attr = true; } \
-        LAUNCH((top_fwd_kernel<DHV, BFV>), dim3(c.batch), dim3(256), smem, s, F); }
-    if (p.bf) { if (p.dh == 16) TOP_FWD_CASE(16, true) else if (p.dh == 32) TOP_FWD_CASE(32, true) else TOP_FWD_CASE(64, true) }
-    else { if (p.dh == 16) TOP_FWD_CASE(16, false) else if (p.dh == 32) TOP_FWD_CASE(32, false) else TOP_FWD_CASE(64, false) }
-#undef TOP_FWD_CASE
-    return (int)hipGetLastError();
+    int rc = 0;
+    DISPATCH_BLOCK(p, rc = launch_lds<top_fwd_kernel<DH, BF>>(dim3(p.cfg.batch), dim3(256), top_fwd_smem_bytes(), s, F));
+    return rc;
 }
 
 static void fill_top_bwd(bsarec_plan& p, int l, bool tr, float* dXout, TopBwdP& F) {
     const bsarec_config_t& c = p.cfg;
-    const bsarec_layer_t& w = p.P.layer[l];
-    LayerBufs& b = p.lb[l];
-    const long nb = p.nblk, d = c.hidden;
-    memset(&F, 0, sizeof(F));
-    F.dX = dXout; F.X = p.X[l];
-    F.sqrt_beta = w.sqrt_beta; F.f_g = w.filter_ln_w; F.wq = w.query_w; F.wk = w.key_w; F.wv = w.value_w; F.wo = w.dense_w;
-    F.a_g = w.attn_ln_w; F.w1 = w.ffn1_w; F.w2 = w.ffn2_w; F.ff_g = w.ffn_ln_w; F.tw = p.twiddle;
-    F.xhat_f = b.xhat_f; F.rstd_f = b.rstd_f; F.q = b.q; F.k = b.k; F.v = b.v; F.probs = b.probs;
-    F.xhat_a = b.xhat_a; F.rstd_a = b.rstd_a; F.u = b.u; F.xhat_ff = b.xhat_ff; F.rstd_ff = b.rstd_ff; F.low = b.dsp;
-    F.dh_slabs = p.dlast_slab; F.dh_nsplit = head_nsplit(p); F.dh_stride = (long)c.batch * d;
+    fill_block<false>(p, l, tr, p.P.layer[l], F);
+    fill_block_partials(p, l, F);
+    F.dX = dXout;
+    F.u = p.lb[l].u; F.low = p.lb[l].dsp;
+    F.dh_slabs = p.dlast_slab; F.dh_nsplit = head_nsplit(p); F.dh_stride = (long)c.batch * c.hidden;
     F.dT = p.top_dT; F.dU = p.top_dU; F.dO = p.top_dO; F.dq = p.top_dq;
     F.ak = p.top_ak; F.rk = p.top_rk; F.av = p.top_av; F.rv = p.top_rv;
-    F.pbk = p.part_kvb; F.pbv = p.part_kvb + (long)c.batch * d;
-    F.pg_ff = p.part_ln + 0 * nb * d; F.pb_ff = p.part_ln + 1 * nb * d; F.pg_a = p.part_ln + 2 * nb * d;
-    F.pb_a = p.part_ln + 3 * nb * d; F.pg_f = p.part_ln + 4 * nb * d; F.pb_f = p.part_ln + 5 * nb * d;
-    F.pbeta = p.part_beta;
-    F.L = c.seq_len; F.Lp = p.Lp; F.cb = c.cutoff_bins; F.heads = c.heads;
-    F.alpha = c.alpha; F.oma = (float)(1.0 - (double)c.alpha);
-    F.drop_f = make_drop(p, c.p_hidden, 1 + 4 * l, tr); F.drop_p = make_drop(p, c.p_attn, 2 + 4 * l, tr);
-    F.drop_o = make_drop(p, c.p_hidden, 3 + 4 * l, tr); F.drop_ff = make_drop(p, c.p_hidden, 4 + 4 * l, tr);
-    F.stamps = p.stamps ? p.stamps + 32 * (2 * l + 1) : nullptr;
+    F.pbk = p.part_kvb; F.pbv = p.part_kvb + (long)c.batch * c.hidden;
 }
 
 static int launch_top_bwd(bsarec_plan& p, int l, bool tr, float* dXout, hipStream_t s) {
-    const bsarec_config_t& c = p.cfg;
     TopBwdP F;
-    fill_top_bwd(p, l, tr, dXout, F);      // (reads p.part_ln / p.part_beta of THIS layer: call inside the layer's iteration)
-    const size_t smem = top_bwd_smem_bytes();
-#define TOP_BWD_CASE(DHV, BFV) { \
-        static bool attr = false; \
-        if (!attr) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(top_bwd_kernel<DHV, BFV>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); attr = true; } \
-        LAUNCH((top_bwd_kernel<DHV, BFV>), dim3(c.batch), dim3(256), smem, s, F); }
-    if (p.bf) { if (p.dh == 16) TOP_BWD_CASE(16, true) else if (p.dh == 32) TOP_BWD_CASE(32, true) else TOP_BWD_CASE(64, true) }
-    else { if (p.dh == 16) TOP_BWD_CASE(16, false) else if (p.dh == 32) TOP_BWD_CASE(32, false) else TOP_BWD_CASE(64, false) }
-#undef TOP_BWD_CASE
-    return (int)hipGetLastError();
+    fill_top_bwd(p, l, tr, dXout, F);
+    int rc = 0;
+    DISPATCH_BLOCK(p, rc = launch_lds<top_bwd_kernel<DH, BF>>(dim3(p.cfg.batch), dim3(256), top_bwd_smem_bytes(), s, F));
+    return rc;
 }
 
 extern "C" int bsarec_debug_stamps(bsarec_plan_t* p, void* dev_buf) { if (!p) return -10; p->stamps = (long long*)dev_buf; return 0; }
@@ -893,18 +823,95 @@ extern "C" int bsarec_forward_last(bsarec_plan_t* p, const int64_t* ids, int tra
     return forward_impl(p, ids, train, stream, none, true);
 }
 
+// Block l on the generic path: FrequencyLayer, attention and feed-forward as tiled GEMMs with fused epilogues
+static int generic_layer_fwd(bsarec_plan& p, int l, bool tr, hipStream_t s) {
+    const bsarec_config_t& c = p.cfg;
+    const int T = p.T, d = c.hidden, L = c.seq_len, B = c.batch, h = c.heads, dh = p.dh, Lp = p.Lp;
+    const bsarec_layer_t& w = p.P.layer[l];
+    LayerBufs& b = p.lb[l];
+    const float* X = p.X[l];
+    const XformP nox = no_xform();
+    // K2 FrequencyLayer
+    DISPATCH_LPR(d, RET(launch_freq_fwd<LPR>(X, w.sqrt_beta, w.filter_ln_w, w.filter_ln_b, c.ln_eps,
+                                             make_drop(p, c.p_hidden, 1 + 4 * l, tr), p.twiddle, B, L, d,
+                                             c.cutoff_bins, b.dsp, b.xhat_f, b.rstd_f, s,
+                                             c.filter_kind == 1 ? w.filter_cw : nullptr)));
+    // K3 Q, K, V projections (one launch, 3 problems)
+    {
+        GemmP g = gemm_defaults(T, d, d);
+        g.nprob = 3; g.lda = d; g.ldb = d;
+        g.A[0] = g.A[1] = g.A[2] = X;
+        g.B[0] = w.query_w; g.B[1] = w.key_w; g.B[2] = w.value_w;
+        auto e = epi_linear<true, false, false>(b.q, d);
+        e.C[1] = b.k; e.C[2] = b.v;
+        e.bias[0] = w.query_b; e.bias[1] = w.key_b; e.bias[2] = w.value_b;
+        RET((launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_QKV)));
+    }
+    // K4a scores + mask + softmax -> probs
+    {
+        GemmP g = gemm_defaults(L, Lp, dh);
+        g.Nb = L; g.lda = d; g.ldb = d; g.nh = h;
+        g.A[0] = b.q; g.B[0] = b.k;
+        g.a_sb = (long)L * d; g.a_sh = dh; g.b_sb = (long)L * d; g.b_sh = dh;
+        EpiSoftmax e; e.ids = p.ids32; e.L = L; e.Lp = Lp; e.sqrt_dh = sqrtf((float)dh); e.P = b.probs;
+        DISPATCH_BN(Lp, RET((launch_gemm<64, BN, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, B * h, s))));
+    }
+    // K4b context = Drop(probs) . V
+    {
+        GemmP g = gemm_defaults(L, dh, Lp);
+        g.Kv = L; g.lda = Lp; g.ldb = d; g.nh = h;
+        g.A[0] = b.probs; g.B[0] = b.v;
+        g.a_sb = (long)h * L * Lp; g.a_sh = (long)L * Lp; g.b_sb = (long)L * d; g.b_sh = dh;
+        XformP xf = nox; xf.drop = make_drop(p, c.p_attn, 2 + 4 * l, tr); xf.L = L; xf.Lp = Lp;
+        auto e = epi_linear<false, false, false>(b.ctx, d);
+        e.c_sb = (long)L * d; e.c_sh = dh;
+        RET((launch_gemm<64, 64, 2, 2, false, true, XF_DROP, XF_NONE, false>(g, xf, e, nullptr, B * h, s)));
+    }
+    // K5 dense + dropout + residual + LayerNorm + alpha mix
+    {
+        GemmP g = gemm_defaults(T, d, d);
+        g.lda = d; g.ldb = d; g.A[0] = b.ctx; g.B[0] = w.dense_w;
+        EpiLN<true> e;
+        e.bias = w.dense_b; e.R = X; e.drop = make_drop(p, c.p_hidden, 3 + 4 * l, tr);
+        e.gamma = w.attn_ln_w; e.beta = w.attn_ln_b; e.eps = c.ln_eps;
+        e.Y = b.hmix; e.xhat = b.xhat_a; e.rstd = b.rstd_a;
+        e.dsp = b.dsp; e.alpha = c.alpha; e.oma = (float)(1.0 - (double)c.alpha);
+        DISPATCH_BN(d, RET((launch_gemm<64, BN, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s))));
+    }
+    // K6a dense_1
+    {
+        GemmP g = gemm_defaults(T, 4 * d, d);
+        g.lda = d; g.ldb = d; g.A[0] = b.hmix; g.B[0] = w.ffn1_w;
+        auto e = epi_linear<true, false, false>(b.u, 4 * d);
+        e.bias[0] = w.ffn1_b;
+        RET((launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_FFN1)));
+    }
+    // K6b gelu + dense_2 + dropout + residual + LayerNorm
+    {
+        GemmP g = gemm_defaults(T, d, 4 * d);
+        g.lda = 4 * d; g.ldb = 4 * d; g.A[0] = b.u; g.B[0] = w.ffn2_w;
+        EpiLN<false> e;
+        e.bias = w.ffn2_b; e.R = b.hmix; e.drop = make_drop(p, c.p_hidden, 4 + 4 * l, tr);
+        e.gamma = w.ffn_ln_w; e.beta = w.ffn_ln_b; e.eps = c.ln_eps;
+        e.Y = p.X[l + 1]; e.xhat = b.xhat_ff; e.rstd = b.rstd_ff;
+        e.dsp = nullptr; e.alpha = 0.f; e.oma = 1.f;
+        XformP xa = nox; xa.act = c.hidden_act;
+        DISPATCH_BN(d, RET((launch_gemm<64, BN, 2, 2, false, false, XF_GELU, XF_NONE, false>(g, xa, e, nullptr, 1, s, BSAREC_K_FFN2))));
+    }
+    return 0;
+}
+
 static int forward_impl(bsarec_plan_t* p, const int64_t* ids, int train, void* stream, const GatherP& gp, bool last_only) {
     if (!p || (!ids && !gp.table)) return -10;
     PlanScope scope(p);
     hipStream_t s = (hipStream_t)stream;
     const bsarec_config_t& c = p->cfg;
-    const int T = p->T, d = c.hidden, L = c.seq_len, B = c.batch, h = c.heads, dh = p->dh, Lp = p->Lp;
+    const int T = p->T, d = c.hidden, L = c.seq_len;
     const bool tr = train != 0;
     p->train = tr;
     p->pruned = last_only && p->prune_ok;
-    const XformP nox = no_xform();
 
-    const bool embed_in_block = fused_ok(*p) && p->embed_in_block;
+    const bool embed_in_block = p->fused && p->embed_in_block;
     if (!embed_in_block)
     DISPATCH_LPR(d, {
         constexpr int RPB = ROW_THREADS / LPR;
@@ -914,83 +921,11 @@ static int forward_impl(bsarec_plan_t* p, const int64_t* ids, int train, void* s
         HIPCHK(hipGetLastError());
     });
 
+    const bool tail = p->pruned && c.layers >= 2 && !c.separate_top;     // top block = tail of the launch below it
     for (int l = 0; l < c.layers; ++l) {
-        const bsarec_layer_t& w = p->P.layer[l];
-        LayerBufs& b = p->lb[l];
-        const float* X = p->X[l];
-        if (fused_ok(*p)) {
-            const bool tail = p->pruned && c.layers >= 2 && !c.separate_top;     // top block = tail of the launch below it
-            if (p->pruned && l == c.layers - 1) { if (!tail) RET(launch_top_fwd(*p, l, tr, s)); }
-            else RET(launch_fused_fwd(*p, l, tr, s, ids, (l == 0 && embed_in_block) ? &gp : nullptr, tail && l == c.layers - 2));
-            continue;
-        }
-        // K2 FrequencyLayer
-        DISPATCH_LPR(d, RET(launch_freq_fwd<LPR>(X, w.sqrt_beta, w.filter_ln_w, w.filter_ln_b, c.ln_eps,
-                                                 make_drop(*p, c.p_hidden, 1 + 4 * l, tr), p->twiddle, B, L, d,
-                                                 c.cutoff_bins, b.dsp, b.xhat_f, b.rstd_f, s,
-                                                 c.filter_kind == 1 ? w.filter_cw : nullptr)));
-        // K3 Q, K, V projections (one launch, 3 problems)
-        {
-            GemmP g = gemm_defaults(T, d, d);
-            g.nprob = 3; g.lda = d; g.ldb = d;
-            g.A[0] = g.A[1] = g.A[2] = X;
-            g.B[0] = w.query_w; g.B[1] = w.key_w; g.B[2] = w.value_w;
-            auto e = epi_linear<true, false, false>(b.q, d);
-            e.C[1] = b.k; e.C[2] = b.v;
-            e.bias[0] = w.query_b; e.bias[1] = w.key_b; e.bias[2] = w.value_b;
-            RET((launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_QKV)));
-        }
-        // K4a scores + mask + softmax -> probs
-        {
-            GemmP g = gemm_defaults(L, Lp, dh);
-            g.Nb = L; g.lda = d; g.ldb = d; g.nh = h;
-            g.A[0] = b.q; g.B[0] = b.k;
-            g.a_sb = (long)L * d; g.a_sh = dh; g.b_sb = (long)L * d; g.b_sh = dh;
-            EpiSoftmax e; e.ids = p->ids32; e.L = L; e.Lp = Lp; e.sqrt_dh = sqrtf((float)dh); e.P = b.probs;
-            DISPATCH_BN(Lp, RET((launch_gemm<64, BN, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, B * h, s))));
-        }
-        // K4b context = Drop(probs) . V
-        {
-            GemmP g = gemm_defaults(L, dh, Lp);
-            g.Kv = L; g.lda = Lp; g.ldb = d; g.nh = h;
-            g.A[0] = b.probs; g.B[0] = b.v;
-            g.a_sb = (long)h * L * Lp; g.a_sh = (long)L * Lp; g.b_sb = (long)L * d; g.b_sh = dh;
-            XformP xf = nox; xf.drop = make_drop(*p, c.p_attn, 2 + 4 * l, tr); xf.L = L; xf.Lp = Lp;
-            auto e = epi_linear<false, false, false>(b.ctx, d);
-            e.c_sb = (long)L * d; e.c_sh = dh;
-            RET((launch_gemm<64, 64, 2, 2, false, true, XF_DROP, XF_NONE, false>(g, xf, e, nullptr, B * h, s)));
-        }
-        // K5 dense + dropout + residual + LayerNorm + alpha mix
-        {
-            GemmP g = gemm_defaults(T, d, d);
-            g.lda = d; g.ldb = d; g.A[0] = b.ctx; g.B[0] = w.dense_w;
-            EpiLN<true> e;
-            e.bias = w.dense_b; e.R = X; e.drop = make_drop(*p, c.p_hidden, 3 + 4 * l, tr);
-            e.gamma = w.attn_ln_w; e.beta = w.attn_ln_b; e.eps = c.ln_eps;
-            e.Y = b.hmix; e.xhat = b.xhat_a; e.rstd = b.rstd_a;
-            e.dsp = b.dsp; e.alpha = c.alpha; e.oma = (float)(1.0 - (double)c.alpha);
-            DISPATCH_BN(d, RET((launch_gemm<64, BN, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s))));
-        }
-        // K6a dense_1
-        {
-            GemmP g = gemm_defaults(T, 4 * d, d);
-            g.lda = d; g.ldb = d; g.A[0] = b.hmix; g.B[0] = w.ffn1_w;
-            auto e = epi_linear<true, false, false>(b.u, 4 * d);
-            e.bias[0] = w.ffn1_b;
-            RET((launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_FFN1)));
-        }
-        // K6b gelu + dense_2 + dropout + residual + LayerNorm
-        {
-            GemmP g = gemm_defaults(T, d, 4 * d);
-            g.lda = 4 * d; g.ldb = 4 * d; g.A[0] = b.u; g.B[0] = w.ffn2_w;
-            EpiLN<false> e;
-            e.bias = w.ffn2_b; e.R = b.hmix; e.drop = make_drop(*p, c.p_hidden, 4 + 4 * l, tr);
-            e.gamma = w.ffn_ln_w; e.beta = w.ffn_ln_b; e.eps = c.ln_eps;
-            e.Y = p->X[l + 1]; e.xhat = b.xhat_ff; e.rstd = b.rstd_ff;
-            e.dsp = nullptr; e.alpha = 0.f; e.oma = 1.f;
-            XformP xa = nox; xa.act = c.hidden_act;
-            DISPATCH_BN(d, RET((launch_gemm<64, BN, 2, 2, false, false, XF_GELU, XF_NONE, false>(g, xa, e, nullptr, 1, s, BSAREC_K_FFN2))));
-        }
+        if (!p->fused) RET(generic_layer_fwd(*p, l, tr, s));
+        else if (p->pruned && l == c.layers - 1) { if (!tail) RET(launch_top_fwd(*p, l, tr, s)); }
+        else RET(launch_fused_fwd(*p, l, tr, s, ids, (l == 0 && embed_in_block) ? &gp : nullptr, tail && l == c.layers - 2));
     }
     return 0;
 }
@@ -1003,13 +938,13 @@ extern "C" int bsarec_logits(bsarec_plan_t* p, void* stream) {
     PlanScope scope(p);
     hipStream_t s = (hipStream_t)stream;
     const bsarec_config_t& c = p->cfg;
-    const int d = c.hidden, L = c.seq_len;
+    const int d = c.hidden;
     // hidden = 64 and a small problem: straight from global memory into the MFMA operands (dw_direct.h).  Measured on one box:
     // C1 (B = 256, V = 3,417) 0.1569 -> 0.1551 ms/step; at B = 256 x V = 12,102 and 1,024 x 20,034 the direct form LOSES (every
     // 32-row block re-reads the whole table, 4-byte stores: 0.134 -> 0.140 and 0.661 -> 0.687 ms) -- those keep the tiled GEMM
     if (p->fused && d == 64 && p->Vp <= 4096 && c.batch <= 512 && !g_dry) {
         LogitsP G;
-        G.H = p->X[c.layers] + (long)(L - 1) * d; G.ldh = (long)L * d; G.E = p->P.item_emb; G.C = p->logits;
+        G.H = h_last(*p); G.ldh = h_last_stride(*p); G.E = p->P.item_emb; G.C = p->logits;
         G.B = c.batch; G.V = c.item_size; G.Vp = p->Vp;
         const long units = (long)cdiv(c.batch, 32) * cdiv(p->Vp, 32);
         ProfScope prof(BSAREC_K_LOGITS, s);
@@ -1017,8 +952,8 @@ extern "C" int bsarec_logits(bsarec_plan_t* p, void* stream) {
         return (int)hipGetLastError();
     }
     GemmP g = gemm_defaults(c.batch, p->Vp, d);
-    g.Nb = c.item_size; g.lda = (long)L * d; g.ldb = d;
-    g.A[0] = p->X[c.layers] + (long)(L - 1) * d; g.B[0] = p->P.item_emb;
+    g.Nb = c.item_size; g.lda = h_last_stride(*p); g.ldb = d;
+    g.A[0] = h_last(*p); g.B[0] = p->P.item_emb;
     auto e = epi_linear<false, false, false>(p->logits, p->Vp);
     return launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_LOGITS, true);
 }
@@ -1041,9 +976,9 @@ static SsmP ssm_params(const float* h, long ldh, int B, int Bg, const float* E, 
 
 static SsmP plan_ssm_params(const bsarec_plan& p, const int64_t* answers) {
     const bsarec_config_t& c = p.cfg;
-    SsmP P = ssm_params(p.X[c.layers] + (long)(c.seq_len - 1) * c.hidden, (long)c.seq_len * c.hidden, c.batch, c.batch,
-                        p.P.item_emb, answers, p.ssm_cand, p.ssm_corr, c.train_negatives, c.item_size,
-                        c.train_sampler == 1 ? p.pop_cum : nullptr, !c.train_no_logq, c.hidden, std::min(p.vsplit, SSM_SLAB_MAX));
+    SsmP P = ssm_params(h_last(p), h_last_stride(p), c.batch, c.batch, p.P.item_emb, answers, p.ssm_cand, p.ssm_corr,
+                        c.train_negatives, c.item_size, c.train_sampler == 1 ? p.pop_cum : nullptr, !c.train_no_logq, c.hidden,
+                        std::min(p.vsplit, SSM_SLAB_MAX));
     P.state = p.state; P.logits = p.ssm_logits; P.dlogits = p.ssm_dlogits; P.loss_rows = p.loss_rows;
     P.slab = p.dlast_slab; P.acc = p.lookup_acc;
     if (p.lazy_now) {                          // lazy Adam step: reset the row count in the loss, mark T in the backward
@@ -1105,10 +1040,9 @@ static int loss_pair(bsarec_plan_t* p, const int64_t* pos_ids, const int64_t* ne
     if (!p || !pos_ids || !neg_ids) return -10;
     hipStream_t s = (hipStream_t)stream;
     const bsarec_config_t& c = p->cfg;
-    const int L = c.seq_len, d = c.hidden;
     p->loss_kind = 1; p->bce_pos = pos_ids; p->bce_neg = neg_ids;
-    LAUNCH(bce_rows_kernel, dim3(1), dim3(ROW_THREADS), 0, s, p->X[c.layers] + (long)(L - 1) * d, (long)L * d, p->P.item_emb,
-           pos_ids, neg_ids, c.batch, d, c.item_size, p->dlogits, p->loss, logsig);
+    LAUNCH(bce_rows_kernel, dim3(1), dim3(ROW_THREADS), 0, s, h_last(*p), h_last_stride(*p), p->P.item_emb,
+           pos_ids, neg_ids, c.batch, c.hidden, c.item_size, p->dlogits, p->loss, logsig);
     return (int)hipGetLastError();
 }
 
@@ -1146,7 +1080,6 @@ extern "C" int bsarec_backward_seq_multi(bsarec_plan_t* p, const float* const* d
     return rc;
 }
 
-
 // Can the final gradient reduction and Adam be one launch (reduce_adam_kernel)?  Needs the direct weight-gradient
 // launch of block 0 to host the step tick, plain single-GPU gradient sources, and every gradient tensor inside the flat
 // arena the update walks (item table + the reduction jobs' targets = the whole arena).
@@ -1160,6 +1093,370 @@ static bool can_fuse_adam(const bsarec_plan& p, const bsarec_adam_t& a) {
     return p.red_elems + item == a.n && p.red_lo >= a.grads && p.red_hi <= a.grads + a.n;
 }
 
+// The head's backward, by the head of the last loss call: the dense part of the item table's gradient into G.item_emb (or the
+// candidate rows into lookup_acc) and the head_nsplit(p) split-K slabs of d(h_last) into dlast_slab.  With an external
+// upstream gradient there is no head: the item table gets its lookup rows only.
+static int head_bwd(bsarec_plan& p, hipStream_t s) {
+    const bsarec_config_t& c = p.cfg;
+    const int d = c.hidden, B = c.batch;
+    const float* hlast = h_last(p);
+    const long ldh = h_last_stride(p);
+    const XformP nox = no_xform();
+    const bool direct_logits = p.fused && p.direct_dw && p.loss_kind == 0 && (long)B * p.Vp * 4 < (1L << 30) &&
+                               (long)c.item_size * d * 4 < (1L << 31);
+    if (p.ext_dy) {             // backward of forward(): no head on this path, the item table gets its lookup rows only
+        if (!g_dry) HIPCHK(hipMemsetAsync(p.G.item_emb, 0, (size_t)c.item_size * d * sizeof(float), s));
+    } else if (p.loss_kind == 1) {     // SASRec's BCE pair: two embedding rows per sequence instead of the dense logits path
+        if (!g_dry) HIPCHK(hipMemsetAsync(p.G.item_emb, 0, (size_t)c.item_size * d * sizeof(float), s));
+        LAUNCH(bce_bwd_kernel, dim3(B), dim3(64), 0, s, hlast, ldh, p.P.item_emb, p.bce_pos, p.bce_neg, p.dlogits, B, d,
+               c.item_size, p.dlast_slab, p.G.item_emb);
+        HIPCHK(hipGetLastError());
+    } else if (p.loss_kind == 2) {
+        // sampled softmax: candidate and answer rows of dE into the fixed-point accumulator (the item table's dense part is
+        // zero: the final reduction writes the accumulator over it), and the slabs of d(h_last)
+        const SsmP P = plan_ssm_params(p, p.ssm_answers);
+        const int tilesC = std::max(1, std::min(cdiv((long)B * d, ROW_THREADS), 64));
+        LAUNCH(ssm_bwd_kernel<false>, dim3(P.tilesA + P.tilesB + tilesC + P.tilesM), dim3(ROW_THREADS), 0, s, P);
+        HIPCHK(hipGetLastError());
+    } else if (direct_logits) {
+        // fused shape: dE = dlogits^T . h_last (K = B rows, written straight into the gradient buffer) and the split-K
+        // slabs of d(h_last) = dlogits . E by the direct kernels (dw_direct.h), one launch
+        DwProblem q;
+        memset(&q, 0, sizeof(q));
+        q.A = p.dlogits; q.B = hlast; q.lda = p.Vp; q.ldb = ldh; q.M = c.item_size; q.N = d; q.K = B;
+        q.kchunk = (int)rup(B, 32); q.nslab = 1; q.slab = p.G.item_emb; q.bslab = nullptr; q.gelu = 0;
+        DhP H;
+        memset(&H, 0, sizeof(H));
+        H.A = p.dlogits; H.lda = p.Vp; H.E = p.P.item_emb; H.B = B; H.V = c.item_size; H.kchunk = p.vchunk;
+        H.nsplit = p.vsplit; H.slab = p.dlast_slab;
+        const int tiles = cdiv(c.item_size, 64);
+        if (!dw_problem_ok(q) || !dh_problem_ok(H)) return -21;
+        const dim3 lb_grid(tiles + cdiv(cdiv(B, 32) * p.vsplit, 4));
+        if (p.bf) LAUNCH(logits_bwd_direct_kernel<true>, lb_grid, dim3(256), 0, s, q, tiles, H);
+        else LAUNCH(logits_bwd_direct_kernel<false>, lb_grid, dim3(256), 0, s, q, tiles, H);
+        HIPCHK(hipGetLastError());
+    } else {
+        // dE (dense, logits path) = dlogits^T . h_last  [V, d] (overwrites the gradient buffer) and the split-K slabs of
+        // d(h_last) = dlogits . E -- one launch
+        PairP G;
+        memset(&G, 0, sizeof(G));
+        G.A = gemm_defaults(c.item_size, d, B);
+        G.A.lda = p.Vp; G.A.ldb = ldh; G.A.A[0] = p.dlogits; G.A.B[0] = hlast;
+        G.EA = epi_linear<false, false, false>(p.G.item_emb, d);
+        G.B = gemm_defaults(B, d, p.Vp);
+        G.B.Kv = c.item_size; G.B.lda = p.Vp; G.B.ldb = d; G.B.A[0] = p.dlogits; G.B.B[0] = p.P.item_emb;
+        G.B.nsplit = p.vsplit; G.B.kchunk = p.vchunk;
+        G.EB = epi_linear<false, false, false>(p.dlast_slab, d);
+        G.EB.c_split = (long)B * d;
+        G.tilesA = cdiv(c.item_size, 64) * cdiv(d, 64);
+        G.tilesB_m = cdiv(B, 64);
+        if (d <= 64) {
+            constexpr size_t smem = GemmSmem<64, 64, true, true>::BYTES > GemmSmem<64, 64, false, true>::BYTES
+                                        ? GemmSmem<64, 64, true, true>::BYTES : GemmSmem<64, 64, false, true>::BYTES;
+            LAUNCH(gemm_logits_bwd_kernel, dim3(G.tilesA + G.tilesB_m * p.vsplit), dim3(GEMM_THREADS), smem, s, G);
+            HIPCHK(hipGetLastError());
+        } else {                                   // wider hidden sizes: two plain launches (N needs several tiles)
+            RET((launch_gemm<64, 64, 2, 2, true, true, XF_NONE, XF_NONE, false>(G.A, nox, G.EA, nullptr, 1, s, BSAREC_K_NONE, true)));
+            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(G.B, nox, G.EB, nullptr, 1, s, BSAREC_K_NONE, true)));
+        }
+    }
+    return 0;
+}
+
+// The upstream gradient of the top layer's output, in or instead of the loop's first buffer dY: the caller's tensor
+// (bsarec_backward_seq), or on the generic path h_last's gradient summed from the head's slabs into row L-1 of zeros.
+static int top_grad(bsarec_plan& p, float*& dY, hipStream_t s) {
+    const bsarec_config_t& c = p.cfg;
+    const int T = p.T, d = c.hidden;
+    if (p.ext_dy) {
+        if (p.bf) {      // the block kernels read inter-block gradients as bf16: convert the caller's fp32 tensor once
+            CastJobs6 J;
+            memset(&J, 0, sizeof(J));
+            J.src[0] = p.ext_dy; J.dst[0] = (unsigned short*)dY; J.n4[0] = (long)T * d / 4;
+            LAUNCH(cast_bf16_kernel, dim3(cdiv((long)T * d / 4, ROW_THREADS), 1), dim3(ROW_THREADS), 0, s, J);
+            HIPCHK(hipGetLastError());
+        } else dY = const_cast<float*>(p.ext_dy);
+    } else if (!p.fused) {      // the fused top-layer backward synthesises this gradient from the slabs itself
+        LAUNCH(dlast_kernel, dim3(cdiv((long)T * d / 4, ROW_THREADS)), dim3(ROW_THREADS), 0, s, p.dlast_slab,
+               head_nsplit(p), (long)c.batch * d, T, c.seq_len, d, dY);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+// Block l's backward on the generic path up to dXtmp: feed-forward, the two LayerNorms of the mix, attention.  Leaves the
+// weight-gradient operands (dT, dU, dO, dq, dk, dv) and dF / dXtmp for the FrequencyLayer backward that completes dX.
+static int generic_layer_bwd(bsarec_plan& p, int l, const float* dY, hipStream_t s) {
+    const bsarec_config_t& c = p.cfg;
+    const int T = p.T, d = c.hidden, L = c.seq_len, B = c.batch, h = c.heads, dh = p.dh, Lp = p.Lp, nb = p.nblk;
+    const bool tr = p.train;
+    const bsarec_layer_t& w = p.P.layer[l];
+    const LayerBufs& b = p.lb[l];
+    const XformP nox = no_xform();
+    // ---- FeedForward backward
+    {
+        LnBranch a; memset(&a, 0, sizeof(a));
+        a.xhat = b.xhat_ff; a.rstd = b.rstd_ff; a.gamma = w.ffn_ln_w; a.in_scale = 1.f;
+        a.drop = make_drop(p, c.p_hidden, 4 + 4 * l, tr); a.dT = p.dT;
+        a.pgamma = ln_part(p, l, LN_FF_G); a.pbeta = ln_part(p, l, LN_FF_B);
+        DISPATCH_LPR(d, LAUNCH((ln_bwd_kernel<LPR, 0>), dim3(nb), dim3(ROW_THREADS), 0, s, dY, a, a, p.dz, T, d, p.rows_pb));
+        HIPCHK(hipGetLastError());
+    }
+    {   // dU = (dT2 . W2) * gelu'(U)
+        GemmP g = gemm_defaults(T, 4 * d, d);
+        g.lda = d; g.ldb = 4 * d; g.A[0] = p.dT; g.B[0] = w.ffn2_w;
+        auto e = epi_linear<false, false, true>(p.dU, 4 * d);
+        e.U = b.u; e.ldu = 4 * d; e.act = c.hidden_act;
+        RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_DU)));
+    }
+    {   // dH = dU . W1 + dz
+        GemmP g = gemm_defaults(T, d, 4 * d);
+        g.lda = 4 * d; g.ldb = d; g.A[0] = p.dU; g.B[0] = w.ffn1_w;
+        auto e = epi_linear<false, true, false>(p.dH, d);
+        e.R = p.dz; e.ldr = d;
+        RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s)));
+    }
+    // ---- mix + the two LayerNorms (attention branch scaled by 1-alpha, filter branch by alpha)
+    {
+        LnBranch a; memset(&a, 0, sizeof(a));
+        a.xhat = b.xhat_a; a.rstd = b.rstd_a; a.gamma = w.attn_ln_w; a.in_scale = (float)(1.0 - (double)c.alpha);
+        a.drop = make_drop(p, c.p_hidden, 3 + 4 * l, tr); a.dT = p.dO;
+        a.pgamma = ln_part(p, l, LN_A_G); a.pbeta = ln_part(p, l, LN_A_B);
+        LnBranch f; memset(&f, 0, sizeof(f));
+        f.xhat = b.xhat_f; f.rstd = b.rstd_f; f.gamma = w.filter_ln_w; f.in_scale = c.alpha;
+        f.drop = make_drop(p, c.p_hidden, 1 + 4 * l, tr); f.dT = p.dF;
+        f.pgamma = ln_part(p, l, LN_F_G); f.pbeta = ln_part(p, l, LN_F_B);
+        DISPATCH_LPR(d, LAUNCH((ln_bwd_kernel<LPR, 1>), dim3(nb), dim3(ROW_THREADS), 0, s, p.dH, a, f, p.dXacc, T, d, p.rows_pb));
+        HIPCHK(hipGetLastError());
+    }
+    // ---- attention backward
+    {   // dC = dO . Wo
+        GemmP g = gemm_defaults(T, d, d);
+        g.lda = d; g.ldb = d; g.A[0] = p.dO; g.B[0] = w.dense_w;
+        auto e = epi_linear<false, false, false>(p.dC, d);
+        RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s)));
+    }
+    XformP xfa = nox; xfa.drop = make_drop(p, c.p_attn, 2 + 4 * l, tr); xfa.L = L; xfa.Lp = Lp;
+    {   // dS = P * (dA - rowsum(dA P)) / sqrt(dh),  dA = (dC . V^T) * keep/(1-p)
+        GemmP g = gemm_defaults(L, Lp, dh);
+        g.Nb = L; g.lda = d; g.ldb = d; g.nh = h; g.A[0] = p.dC; g.B[0] = b.v;
+        g.a_sb = (long)L * d; g.a_sh = dh; g.b_sb = (long)L * d; g.b_sh = dh;
+        EpiDS e; e.P = b.probs; e.drop = xfa.drop; e.L = L; e.Lp = Lp; e.sqrt_dh = sqrtf((float)dh); e.dS = p.dS;
+        DISPATCH_BN(Lp, RET((launch_gemm<64, BN, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, B * h, s))));
+    }
+    {   // dV = Drop(P)^T . dC
+        GemmP g = gemm_defaults(L, dh, L);
+        g.lda = Lp; g.ldb = d; g.nh = h; g.A[0] = b.probs; g.B[0] = p.dC;
+        g.a_sb = (long)h * L * Lp; g.a_sh = (long)L * Lp; g.b_sb = (long)L * d; g.b_sh = dh;
+        auto e = epi_linear<false, false, false>(p.dv, d);
+        e.c_sb = (long)L * d; e.c_sh = dh;
+        RET((launch_gemm<64, 64, 2, 2, true, true, XF_DROP, XF_NONE, false>(g, xfa, e, nullptr, B * h, s)));
+    }
+    {   // dK = dS^T . Q
+        GemmP g = gemm_defaults(L, dh, L);
+        g.lda = Lp; g.ldb = d; g.nh = h; g.A[0] = p.dS; g.B[0] = b.q;
+        g.a_sb = (long)h * L * Lp; g.a_sh = (long)L * Lp; g.b_sb = (long)L * d; g.b_sh = dh;
+        auto e = epi_linear<false, false, false>(p.dk, d);
+        e.c_sb = (long)L * d; e.c_sh = dh;
+        RET((launch_gemm<64, 64, 2, 2, true, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, B * h, s)));
+    }
+    {   // dQ = dS . K
+        GemmP g = gemm_defaults(L, dh, Lp);
+        g.Kv = L; g.lda = Lp; g.ldb = d; g.nh = h; g.A[0] = p.dS; g.B[0] = b.k;
+        g.a_sb = (long)h * L * Lp; g.a_sh = (long)L * Lp; g.b_sb = (long)L * d; g.b_sh = dh;
+        auto e = epi_linear<false, false, false>(p.dq, d);
+        e.c_sb = (long)L * d; e.c_sh = dh;
+        RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, B * h, s)));
+    }
+    {   // dXtmp = dQ.Wq + dK.Wk + dV.Wv + (dzA + dzF)
+        GemmP g = gemm_defaults(T, d, d);
+        g.lda = d; g.ldb = d; g.nseg = 3;
+        g.A[0] = p.dq; g.A[1] = p.dk; g.A[2] = p.dv;
+        g.B[0] = w.query_w; g.B[1] = w.key_w; g.B[2] = w.value_w;
+        auto e = epi_linear<false, true, false>(p.dXtmp, d);
+        e.R = p.dXacc; e.ldr = d;
+        RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s)));
+    }
+    return 0;
+}
+
+// tile size of the grouped tiled kernel (the direct kernel has its own units): 128 for bf16 products at hidden >= 128 (C3:
+// 405 -> 337 us per launch); the fp32 form needs 296 registers at 128 x 128 = one wave per SIMD and loses (765 -> 987 us)
+static int dw_tile(const bsarec_plan& p) { return (p.bf_products && p.cfg.hidden >= 128) ? 128 : 64; }
+
+// The six weight-gradient problems (and bias gradients) of block l as split-K products into the layer's slabs
+static void build_dw_problems(const bsarec_plan& p, int l, bool top_pruned, GroupedTN& G) {
+    const bsarec_config_t& c = p.cfg;
+    const int T = p.T, d = c.hidden, L = c.seq_len, B = c.batch, h = c.heads, N = c.layers, ns = p.nsplit;
+    const SlabMap sm = slab_map(d);
+    const LayerBufs& b = p.lb[l];
+    const float* X = p.X[l];
+    memset(&G, 0, sizeof(G));
+    struct Spec { const float* A; long lda; const float* B; long ldb; int M, N; long woff, boff; int gelu; };
+    const Spec sp[6] = {
+        {p.dq, d, X, d, d, d, sm.wq, sm.bq, 0},        {p.dk, d, X, d, d, d, sm.wk, sm.bk, 0},
+        {p.dv, d, X, d, d, d, sm.wv, sm.bv, 0},        {p.dO, d, b.ctx, d, d, d, sm.wo, sm.bo, 0},
+        {p.dU, 4 * d, b.hmix, d, 4 * d, d, sm.w1, sm.b1, 0},
+        // dW2 = dT2^T . act(u): the full fused forward already saved gelu(u) in `u`; elsewhere apply it while loading
+        {p.dT, d, b.u, 4 * d, d, 4 * d, sm.w2, sm.b2, (p.fused && !top_pruned) ? 0 : 1}};
+    int tiles = 0;
+    const int gts = dw_tile(p);
+    // Top block: only position L-1 of each sequence carries an upstream gradient (bsarec.py:32), so dq, dO, dU
+    // and dT2 are zero on every other row: their four products reduce over the B last positions only
+    // (row stride L*ld), exactly; dk and dv still reduce over all tokens.
+    const bool top = (l == N - 1) && !p.ext_dy;       // (an external upstream gradient has every row)
+    for (int i = 0; i < 6; ++i) {
+        const bool last_only = top && i != 1 && i != 2;
+        GemmP g = gemm_defaults(sp[i].M, sp[i].N, last_only ? B : T);
+        g.lda = sp[i].lda; g.ldb = sp[i].ldb; g.A[0] = sp[i].A; g.B[0] = sp[i].B; g.nsplit = ns; g.kchunk = p.kchunk;
+        if (last_only) {
+            // row L-1 of every sequence (element offsets: the operands are bf16 tensors under storage = 1)
+            const long esz = p.bf ? 2 : 4;
+            g.A[0] = (const float*)((const char*)g.A[0] + (long)(L - 1) * sp[i].lda * esz);
+            g.B[0] = (const float*)((const char*)g.B[0] + (long)(L - 1) * sp[i].ldb * esz);
+            g.lda *= L; g.ldb *= L;
+            g.kchunk = (int)rup(cdiv(B, ns), GEMM_BK);           // slices beyond ceil(B / kchunk) write zero slabs
+            if (top_pruned) {                                    // gradient rows come compact ([B][M]) from top_bwd_kernel
+                g.A[0] = i == 0 ? p.top_dq : i == 3 ? p.top_dO : i == 4 ? p.top_dU : p.top_dT;
+                g.lda = sp[i].M;
+                g.nsplit = std::min(p.top_slabs, ns); g.kchunk = (int)rup(cdiv(B, g.nsplit), GEMM_BK);
+            }
+        }
+        // pruned top block: dK, dV are rank-1 per (sequence, head) -> dWk = AK^T RK, dWv = AV^T RV over B*h rows
+        // (fused_top.h); their bias gradients come from per-sequence partials, the slab output is discarded
+        const bool compact = top_pruned && (i == 1 || i == 2);
+        if (compact) {
+            g = gemm_defaults(d, d, B * h);
+            g.A[0] = i == 1 ? p.top_ak : p.top_av; g.B[0] = i == 1 ? p.top_rk : p.top_rv; g.lda = d; g.ldb = d;
+            g.nsplit = std::min(p.top_slabs, ns); g.kchunk = (int)rup(cdiv(B * h, g.nsplit), GEMM_BK);
+        }
+        G.P[i] = g;
+        G.E[i] = epi_linear<false, false, false>(slab_w_ptr(p, l, sp[i].woff), sp[i].N);
+        G.E[i].c_split = (long)sp[i].M * sp[i].N;
+        G.bgrad[i] = compact ? p.slab_dummy : slab_b_ptr(p, l, sp[i].boff);
+        G.tile0[i] = tiles;
+        G.tiles_n[i] = cdiv(sp[i].N, gts);
+        G.b_gelu[i] = sp[i].gelu;
+        tiles += cdiv(sp[i].M, gts) * G.tiles_n[i];
+    }
+    G.tile0[6] = tiles; G.nprob = 6; G.act = c.hidden_act;
+}
+
+// What the layer loop carries from the pruned top block to the block below it on the direct path: the top block's six
+// (tiny) weight-gradient problems wait in DW (np problems, nu units so far) and its backward in top_head; both ride in the
+// launches of the block below.
+struct DwPending { DwP DW; int np, nu; TopBwdP top_head; bool have_head; };
+
+// Direct launch of block l's problems (and of those waiting in Q).  tick: the step tick to run in this launch (null: none).
+static int launch_dw_direct(bsarec_plan& p, int l, bool top_pruned, const GroupedTN& G, DwPending& Q, const TickP* tick,
+                            hipStream_t s) {
+    const int T = p.T, ns = p.nsplit;
+    // hidden = 64: direct split-K products, one workgroup per (problem, 64x64 tile, slab slice) -- dw_direct.h.
+    // The pruned top block's six (tiny) problems are not launched on their own: they wait in DW and ride in
+    // the next block's launch.
+    for (int i = 0; i < 6; ++i) {
+        const GemmP& g = G.P[i];
+        DwProblem& q = Q.DW.P[Q.np];
+        q.A = g.A[0]; q.B = g.B[0]; q.lda = g.lda; q.ldb = g.ldb; q.M = g.M; q.N = g.N; q.K = g.K;
+        q.kchunk = g.kchunk; q.nslab = g.nsplit; q.slab = G.E[i].C[0]; q.bslab = G.bgrad[i]; q.gelu = G.b_gelu[i];
+        q.bf16 = p.bf ? 1 : 0;
+        for (int m0 = 0; m0 < q.M; m0 += 64)
+            for (int n0 = 0; n0 < q.N; n0 += 64) Q.DW.U[Q.nu++] = DwUnit{(short)Q.np, (short)m0, (short)n0, 0};
+        ++Q.np;
+    }
+    if (top_pruned) { Q.DW.nsmall = Q.nu; Q.DW.small_slabs = std::min(p.top_slabs, ns); }
+    else {
+        Q.DW.nunits = Q.nu; Q.DW.nslab = ns;
+        TickP tk_here;                     // the step tick rides in block 0's launch when Adam is fused into the reduction
+        memset(&tk_here, 0, sizeof(tk_here));
+        if (tick) tk_here = *tick;
+        ScatterP sc;                       // ... and so does the embedding-gradient scatter (block 0's launch: dz is complete)
+        memset(&sc, 0, sizeof(sc));
+        if (p.scatter_in_block && l == 0) {
+            sc.de = p.dz; sc.ids32 = p.ids32; sc.T = T; sc.dA = p.lookup_acc;
+            sc.nblocks = cdiv(T, SCATTER_FLOATS / 64);
+        }
+        for (int i = 0; i < Q.np; ++i) if (!dw_problem_ok(Q.DW.P[i])) return -21;
+        if (sc.nblocks && (!sc.de || !sc.ids32 || !sc.dA)) return -21;
+        ProfScope prof(BSAREC_K_DW1, s);
+        const dim3 dw_grid(8 * cdiv(ns, 8) * (Q.nu - Q.DW.nsmall) + Q.DW.nsmall * Q.DW.small_slabs + sc.nblocks + (tk_here.state ? 1 : 0));
+        LAUNCH(dw_direct_kernel, dw_grid, dim3(256), 0, s, Q.DW, tk_here, sc);
+        HIPCHK(hipGetLastError());
+        Q.np = 0; Q.nu = 0; Q.DW.nsmall = 0; Q.DW.small_slabs = 0;
+    }
+    return 0;
+}
+
+// Grouped tiled launch of block l's problems
+static int launch_dw_grouped(const bsarec_plan& p, const GroupedTN& G, hipStream_t s) {
+    ProfScope prof(BSAREC_K_DW1, s);
+    const dim3 grid(G.tile0[6], p.nsplit), block(GEMM_THREADS);
+    if (!p.bf_products)
+        return launch_lds<gemm_grouped_tn_kernel<false, 64>>(grid, block, GemmSmem<64, 64, true, true, false>::BYTES, s, G);
+    if (dw_tile(p) == 128)
+        return launch_lds<gemm_grouped_tn_kernel<true, 128>>(grid, block, GemmSmem<128, 128, true, true, true>::BYTES, s, G);
+    return launch_lds<gemm_grouped_tn_kernel<true, 64>>(grid, block, GemmSmem<64, 64, true, true, true>::BYTES, s, G);
+}
+
+// Embedding front-end backward: LayerNorm + dropout into dz (fused path: done by the bottom block's backward kernel), then the
+// scatter of dz's rows into lookup_acc and the position partials (unless that rode in block 0's weight-gradient launch)
+static int embed_bwd(bsarec_plan& p, const float* dY, hipStream_t s) {
+    const bsarec_config_t& c = p.cfg;
+    const int T = p.T, d = c.hidden, L = c.seq_len, B = c.batch;
+    if (!p.fused) {
+        LnBranch a; memset(&a, 0, sizeof(a));
+        a.xhat = p.xhat0; a.rstd = p.rstd0; a.gamma = p.P.ln_w; a.in_scale = 1.f;
+        a.drop = make_drop(p, c.p_hidden, 0, p.train); a.dT = nullptr;
+        a.pgamma = ln0_part(p, LN_E_G); a.pbeta = ln0_part(p, LN_E_B);
+        DISPATCH_LPR(d, LAUNCH((ln_bwd_kernel<LPR, 2>), dim3(p.nblk), dim3(ROW_THREADS), 0, s, dY, a, a, p.dz, T, d, p.rows_pb));
+        HIPCHK(hipGetLastError());
+    }
+    if (!p.scatter_in_block)
+    DISPATCH_LPR(d, {
+        constexpr int CHUNK = SCATTER_FLOATS / (LPR * 4);
+        const int sb = cdiv(T, CHUNK);
+        RET(launch_lds<embed_bwd_kernel<LPR>>(dim3(sb + L * p.pos_slices), dim3(ROW_THREADS), SCATTER_FLOATS * 8 + 2 * CHUNK * 4, s,
+                                              p.dz, p.ids32, B, L, d, p.lookup_acc, p.part_pos, sb));
+    });
+    return 0;
+}
+
+// ONE deterministic second-stage reduction for every split-K slab and LayerNorm / beta partial (no empty blocks: flat block
+// map); its extra last block closes the optimisation step when asked to (the lookup-path sum of the item-table gradient
+// joins its target here: after every scatter block has finished).  fuse_adam: the same launch also runs Adam over the arena.
+static int final_reduce(bsarec_plan& p, const TickP& tick, const bsarec_adam_t* fuse_adam, hipStream_t s) {
+    const bsarec_config_t& c = p.cfg;
+    LookupAcc la;
+    memset(&la, 0, sizeof(la));
+    la.acc = p.lookup_acc; la.dst = p.lookup_grad ? p.lookup_grad : p.G.item_emb; la.n4 = (long)c.item_size * c.hidden / 4;
+    la.nblocks = (int)std::min<long>(cdiv(la.n4, ROW_THREADS), 1024);
+    la.dense_zero = (!p.ext_dy && p.loss_kind == 2) ? 1 : 0;
+    const bool lazy = p.lazy_now && !p.ext_dy && p.loss_kind == 2;
+    if (lazy) {                        // lazy Adam: the rows of T only, in a grid sized to the list's capacity
+        la.lazy = p.lazy;
+        la.nblocks = (int)std::min<long>(cdiv((long)p.lazy.cap * p.lazy.d4, ROW_THREADS), 1024);
+    }
+    const ReduceJob* jobs = p.pruned ? p.jobs_pruned : p.jobs;
+    if (fuse_adam) {
+        const bsarec_adam_t& a = *fuse_adam;
+        AdamFuseP A;
+        memset(&A, 0, sizeof(A));
+        A.w = a.params; A.g = const_cast<float*>(a.grads); A.m = a.exp_avg; A.v = a.exp_avg_sq;
+        A.b1 = a.beta1; A.b2 = a.beta2; A.eps = a.eps; A.wd = a.weight_decay;
+        A.shadow = (unsigned short*)a.shadow_bf16; A.shadow_from = a.shadow_bf16 ? a.shadow_from : a.n;
+        A.item_off = p.G.item_emb - a.grads; A.item_n4 = la.n4; A.lookup_acc = la.acc;
+        A.dense_zero = la.dense_zero;
+        if (lazy) A.lazy = p.lazy;
+        int ab = lazy ? la.nblocks : cdiv(A.item_n4, ROW_THREADS);
+        if (ab > 1024) ab = 1024;
+        LAUNCH(reduce_adam_kernel, dim3(p.red_blocks + ab), dim3(ROW_THREADS), 0, s, jobs, p.blockmap, p.red_blocks,
+               (const uint64_t*)p.state, A);
+    } else
+        LAUNCH(multi_reduce_flat_kernel, dim3(p.red_blocks + la.nblocks + (tick.state ? 1 : 0)), dim3(ROW_THREADS), 0, s, jobs,
+               p.blockmap, p.red_blocks, tick, la);
+    return (int)hipGetLastError();
+}
+
 static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, const bsarec_adam_t* fuse_adam) {
     if (!p) return -10;
     if (!p->G.item_emb) return -13;
@@ -1169,301 +1466,42 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
     PlanScope scope(p);
     hipStream_t s = (hipStream_t)stream;
     const bsarec_config_t& c = p->cfg;
-    const int T = p->T, d = c.hidden, L = c.seq_len, B = c.batch, h = c.heads, dh = p->dh, Lp = p->Lp, N = c.layers;
+    const int T = p->T, d = c.hidden, L = c.seq_len, B = c.batch, N = c.layers;
     const bool tr = p->train;
-    const XformP nox = no_xform();
-    const SlabMap sm = slab_map(d);
-    const int ns = p->nsplit, nb = p->nblk;
-    const float* hlast = p->X[N] + (long)(L - 1) * d;
-    const bool direct_logits = !p->ext_dy && p->fused && p->direct_dw && p->loss_kind == 0 && (long)B * p->Vp * 4 < (1L << 30) &&
-                               (long)c.item_size * d * 4 < (1L << 31);
 
-    if (p->ext_dy) {             // backward of forward(): no head on this path, the item table gets its lookup rows only
-        if (!g_dry) HIPCHK(hipMemsetAsync(p->G.item_emb, 0, (size_t)c.item_size * d * sizeof(float), s));
-    } else if (p->loss_kind == 1) {     // SASRec's BCE pair: two embedding rows per sequence instead of the dense logits path
-        if (!g_dry) HIPCHK(hipMemsetAsync(p->G.item_emb, 0, (size_t)c.item_size * d * sizeof(float), s));
-        LAUNCH(bce_bwd_kernel, dim3(B), dim3(64), 0, s, hlast, (long)L * d, p->P.item_emb, p->bce_pos, p->bce_neg, p->dlogits, B, d,
-               c.item_size, p->dlast_slab, p->G.item_emb);
-        HIPCHK(hipGetLastError());
-    } else if (p->loss_kind == 2) {
-        // sampled softmax: candidate and answer rows of dE into the fixed-point accumulator (the item table's dense part is
-        // zero: the final reduction writes the accumulator over it), and the slabs of d(h_last)
-        const SsmP P = plan_ssm_params(*p, p->ssm_answers);
-        const int tilesC = std::max(1, std::min(cdiv((long)B * d, ROW_THREADS), 64));
-        LAUNCH(ssm_bwd_kernel<false>, dim3(P.tilesA + P.tilesB + tilesC + P.tilesM), dim3(ROW_THREADS), 0, s, P);
-        HIPCHK(hipGetLastError());
-    } else if (direct_logits) {
-        // fused shape: dE = dlogits^T . h_last (K = B rows, written straight into the gradient buffer) and the split-K
-        // slabs of d(h_last) = dlogits . E by the direct kernels (dw_direct.h), one launch
-        DwProblem q;
-        memset(&q, 0, sizeof(q));
-        q.A = p->dlogits; q.B = hlast; q.lda = p->Vp; q.ldb = (long)L * d; q.M = c.item_size; q.N = d; q.K = B;
-        q.kchunk = (int)rup(B, 32); q.nslab = 1; q.slab = p->G.item_emb; q.bslab = nullptr; q.gelu = 0;
-        DhP H;
-        memset(&H, 0, sizeof(H));
-        H.A = p->dlogits; H.lda = p->Vp; H.E = p->P.item_emb; H.B = B; H.V = c.item_size; H.kchunk = p->vchunk;
-        H.nsplit = p->vsplit; H.slab = p->dlast_slab;
-        const int tiles = cdiv(c.item_size, 64);
-        if (!dw_problem_ok(q) || !dh_problem_ok(H)) return -21;
-        const dim3 lb_grid(tiles + cdiv(cdiv(B, 32) * p->vsplit, 4));
-        if (p->bf) LAUNCH(logits_bwd_direct_kernel<true>, lb_grid, dim3(256), 0, s, q, tiles, H);
-        else LAUNCH(logits_bwd_direct_kernel<false>, lb_grid, dim3(256), 0, s, q, tiles, H);
-        HIPCHK(hipGetLastError());
-    } else
-    // dE (dense, logits path) = dlogits^T . h_last  [V, d] (overwrites the gradient buffer) and the split-K slabs of
-    // d(h_last) = dlogits . E -- one launch
-    {
-        PairP G;
-        memset(&G, 0, sizeof(G));
-        G.A = gemm_defaults(c.item_size, d, B);
-        G.A.lda = p->Vp; G.A.ldb = (long)L * d; G.A.A[0] = p->dlogits; G.A.B[0] = hlast;
-        G.EA = epi_linear<false, false, false>(p->G.item_emb, d);
-        G.B = gemm_defaults(B, d, p->Vp);
-        G.B.Kv = c.item_size; G.B.lda = p->Vp; G.B.ldb = d; G.B.A[0] = p->dlogits; G.B.B[0] = p->P.item_emb;
-        G.B.nsplit = p->vsplit; G.B.kchunk = p->vchunk;
-        G.EB = epi_linear<false, false, false>(p->dlast_slab, d);
-        G.EB.c_split = (long)B * d;
-        G.tilesA = cdiv(c.item_size, 64) * cdiv(d, 64);
-        G.tilesB_m = cdiv(B, 64);
-        if (d <= 64) {
-            constexpr size_t smem = GemmSmem<64, 64, true, true>::BYTES > GemmSmem<64, 64, false, true>::BYTES
-                                        ? GemmSmem<64, 64, true, true>::BYTES : GemmSmem<64, 64, false, true>::BYTES;
-            LAUNCH(gemm_logits_bwd_kernel, dim3(G.tilesA + G.tilesB_m * p->vsplit), dim3(GEMM_THREADS), smem, s, G);
-            HIPCHK(hipGetLastError());
-        } else {                                   // wider hidden sizes: two plain launches (N needs several tiles)
-            RET((launch_gemm<64, 64, 2, 2, true, true, XF_NONE, XF_NONE, false>(G.A, nox, G.EA, nullptr, 1, s, BSAREC_K_NONE, true)));
-            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(G.B, nox, G.EB, nullptr, 1, s, BSAREC_K_NONE, true)));
-        }
-    }
+    RET(head_bwd(*p, s));
     // the dense item-table gradient is complete (enqueued): a data-parallel host may start exchanging it now
     if (p->dense_hook && !g_dry && !p->ext_dy) p->dense_hook(p->dense_hook_user, stream);
     float* dY = (N & 1) ? p->dXb : p->dXa;       // gradient w.r.t. X[l+1]; ping-pong so that dX[0] lands in dXa
-    if (p->ext_dy) {
-        if (p->bf) {      // the block kernels read inter-block gradients as bf16: convert the caller's fp32 tensor once
-            CastJobs6 J;
-            memset(&J, 0, sizeof(J));
-            J.src[0] = p->ext_dy; J.dst[0] = (unsigned short*)dY; J.n4[0] = (long)T * d / 4;
-            LAUNCH(cast_bf16_kernel, dim3(cdiv((long)T * d / 4, ROW_THREADS), 1), dim3(ROW_THREADS), 0, s, J);
-            HIPCHK(hipGetLastError());
-        } else dY = const_cast<float*>(p->ext_dy);
-    } else
-    if (!p->fused) {      // the fused top-layer backward synthesises this gradient from the slabs itself
-        LAUNCH(dlast_kernel, dim3(cdiv((long)T * d / 4, ROW_THREADS)), dim3(ROW_THREADS), 0, s, p->dlast_slab,
-               head_nsplit(*p), (long)B * d, T, L, d, dY);
-        HIPCHK(hipGetLastError());
-    }
+    RET(top_grad(*p, dY, s));
 
-    DwP DW;                       // weight-gradient problems waiting for their launch (dw_direct.h)
-    memset(&DW, 0, sizeof(DW));
-    int dw_np = 0, dw_nu = 0;
-    TopBwdP top_head;
-    bool have_head = false;
+    DwPending pend;
+    memset(&pend, 0, sizeof(pend));
     for (int l = N - 1; l >= 0; --l) {
-        const bsarec_layer_t& w = p->P.layer[l];
-        LayerBufs& b = p->lb[l];
-        const float* X = p->X[l];
         float* dXout = (dY == p->dXa) ? p->dXb : p->dXa;
-        p->slab_w = p->slab_wL[l]; p->slab_b = p->slab_bL[l]; p->part_ln = p->part_lnL[l]; p->part_beta = p->part_betaL[l];
         const bool top_pruned = p->fused && p->pruned && l == N - 1;
         if (top_pruned) {
             // rides in the next launch -- when this layer's weight-gradient products do too (the direct kernel defers them; the
             // tiled fallback launches them inside this iteration and needs the top block's operands now)
-            if (N >= 2 && !c.separate_top && p->direct_dw) { fill_top_bwd(*p, l, tr, dXout, top_head); have_head = true; }
+            if (N >= 2 && !c.separate_top && p->direct_dw) { fill_top_bwd(*p, l, tr, dXout, pend.top_head); pend.have_head = true; }
             else RET(launch_top_bwd(*p, l, tr, dXout, s));
         } else if (p->fused) {
-            RET(launch_fused_bwd(*p, l, tr, dY, dXout, s, l == N - 1 && !p->ext_dy, (have_head && l == N - 2) ? &top_head : nullptr));
-        } else {
-        // ---- FeedForward backward
-        {
-            LnBranch a; memset(&a, 0, sizeof(a));
-            a.xhat = b.xhat_ff; a.rstd = b.rstd_ff; a.gamma = w.ffn_ln_w; a.in_scale = 1.f;
-            a.drop = make_drop(*p, c.p_hidden, 4 + 4 * l, tr); a.dT = p->dT;
-            a.pgamma = p->part_ln + 0L * nb * d; a.pbeta = p->part_ln + 1L * nb * d;
-            DISPATCH_LPR(d, LAUNCH((ln_bwd_kernel<LPR, 0>), dim3(nb), dim3(ROW_THREADS), 0, s, dY, a, a, p->dz, T, d, p->rows_pb));
-            HIPCHK(hipGetLastError());
-        }
-        {   // dU = (dT2 . W2) * gelu'(U)
-            GemmP g = gemm_defaults(T, 4 * d, d);
-            g.lda = d; g.ldb = 4 * d; g.A[0] = p->dT; g.B[0] = w.ffn2_w;
-            auto e = epi_linear<false, false, true>(p->dU, 4 * d);
-            e.U = b.u; e.ldu = 4 * d; e.act = c.hidden_act;
-            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_DU)));
-        }
-        {   // dH = dU . W1 + dz
-            GemmP g = gemm_defaults(T, d, 4 * d);
-            g.lda = 4 * d; g.ldb = d; g.A[0] = p->dU; g.B[0] = w.ffn1_w;
-            auto e = epi_linear<false, true, false>(p->dH, d);
-            e.R = p->dz; e.ldr = d;
-            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s)));
-        }
-        // ---- mix + the two LayerNorms (attention branch scaled by 1-alpha, filter branch by alpha)
-        {
-            LnBranch a; memset(&a, 0, sizeof(a));
-            a.xhat = b.xhat_a; a.rstd = b.rstd_a; a.gamma = w.attn_ln_w; a.in_scale = (float)(1.0 - (double)c.alpha);
-            a.drop = make_drop(*p, c.p_hidden, 3 + 4 * l, tr); a.dT = p->dO;
-            a.pgamma = p->part_ln + 2L * nb * d; a.pbeta = p->part_ln + 3L * nb * d;
-            LnBranch f; memset(&f, 0, sizeof(f));
-            f.xhat = b.xhat_f; f.rstd = b.rstd_f; f.gamma = w.filter_ln_w; f.in_scale = c.alpha;
-            f.drop = make_drop(*p, c.p_hidden, 1 + 4 * l, tr); f.dT = p->dF;
-            f.pgamma = p->part_ln + 4L * nb * d; f.pbeta = p->part_ln + 5L * nb * d;
-            DISPATCH_LPR(d, LAUNCH((ln_bwd_kernel<LPR, 1>), dim3(nb), dim3(ROW_THREADS), 0, s, p->dH, a, f, p->dXacc, T, d, p->rows_pb));
-            HIPCHK(hipGetLastError());
-        }
-        // ---- attention backward
-        {   // dC = dO . Wo
-            GemmP g = gemm_defaults(T, d, d);
-            g.lda = d; g.ldb = d; g.A[0] = p->dO; g.B[0] = w.dense_w;
-            auto e = epi_linear<false, false, false>(p->dC, d);
-            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s)));
-        }
-        XformP xfa = nox; xfa.drop = make_drop(*p, c.p_attn, 2 + 4 * l, tr); xfa.L = L; xfa.Lp = Lp;
-        {   // dS = P * (dA - rowsum(dA P)) / sqrt(dh),  dA = (dC . V^T) * keep/(1-p)
-            GemmP g = gemm_defaults(L, Lp, dh);
-            g.Nb = L; g.lda = d; g.ldb = d; g.nh = h; g.A[0] = p->dC; g.B[0] = b.v;
-            g.a_sb = (long)L * d; g.a_sh = dh; g.b_sb = (long)L * d; g.b_sh = dh;
-            EpiDS e; e.P = b.probs; e.drop = xfa.drop; e.L = L; e.Lp = Lp; e.sqrt_dh = sqrtf((float)dh); e.dS = p->dS;
-            DISPATCH_BN(Lp, RET((launch_gemm<64, BN, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, B * h, s))));
-        }
-        {   // dV = Drop(P)^T . dC
-            GemmP g = gemm_defaults(L, dh, L);
-            g.lda = Lp; g.ldb = d; g.nh = h; g.A[0] = b.probs; g.B[0] = p->dC;
-            g.a_sb = (long)h * L * Lp; g.a_sh = (long)L * Lp; g.b_sb = (long)L * d; g.b_sh = dh;
-            auto e = epi_linear<false, false, false>(p->dv, d);
-            e.c_sb = (long)L * d; e.c_sh = dh;
-            RET((launch_gemm<64, 64, 2, 2, true, true, XF_DROP, XF_NONE, false>(g, xfa, e, nullptr, B * h, s)));
-        }
-        {   // dK = dS^T . Q
-            GemmP g = gemm_defaults(L, dh, L);
-            g.lda = Lp; g.ldb = d; g.nh = h; g.A[0] = p->dS; g.B[0] = b.q;
-            g.a_sb = (long)h * L * Lp; g.a_sh = (long)L * Lp; g.b_sb = (long)L * d; g.b_sh = dh;
-            auto e = epi_linear<false, false, false>(p->dk, d);
-            e.c_sb = (long)L * d; e.c_sh = dh;
-            RET((launch_gemm<64, 64, 2, 2, true, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, B * h, s)));
-        }
-        {   // dQ = dS . K
-            GemmP g = gemm_defaults(L, dh, Lp);
-            g.Kv = L; g.lda = Lp; g.ldb = d; g.nh = h; g.A[0] = p->dS; g.B[0] = b.k;
-            g.a_sb = (long)h * L * Lp; g.a_sh = (long)L * Lp; g.b_sb = (long)L * d; g.b_sh = dh;
-            auto e = epi_linear<false, false, false>(p->dq, d);
-            e.c_sb = (long)L * d; e.c_sh = dh;
-            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, B * h, s)));
-        }
-        {   // dXtmp = dQ.Wq + dK.Wk + dV.Wv + (dzA + dzF)
-            GemmP g = gemm_defaults(T, d, d);
-            g.lda = d; g.ldb = d; g.nseg = 3;
-            g.A[0] = p->dq; g.A[1] = p->dk; g.A[2] = p->dv;
-            g.B[0] = w.query_w; g.B[1] = w.key_w; g.B[2] = w.value_w;
-            auto e = epi_linear<false, true, false>(p->dXtmp, d);
-            e.R = p->dXacc; e.ldr = d;
-            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s)));
-        }
-        }
-        {   // all six weight gradients + bias gradients of the block: one grouped split-K launch
-            GroupedTN G;
-            memset(&G, 0, sizeof(G));
-            struct Spec { const float* A; long lda; const float* B; long ldb; int M, N; long woff, boff; int gelu; };
-            const Spec sp[6] = {
-                {p->dq, d, X, d, d, d, sm.wq, sm.bq, 0},        {p->dk, d, X, d, d, d, sm.wk, sm.bk, 0},
-                {p->dv, d, X, d, d, d, sm.wv, sm.bv, 0},        {p->dO, d, b.ctx, d, d, d, sm.wo, sm.bo, 0},
-                {p->dU, 4 * d, b.hmix, d, 4 * d, d, sm.w1, sm.b1, 0},
-                // dW2 = dT2^T . act(u): the full fused forward already saved gelu(u) in `u`; elsewhere apply it while loading
-                {p->dT, d, b.u, 4 * d, d, 4 * d, sm.w2, sm.b2, (p->fused && !top_pruned) ? 0 : 1}};
-            int tiles = 0;
-            // tile size of the grouped tiled kernel (the direct kernel has its own units): 128 for bf16 products at hidden >= 128 (C3:
-            // 405 -> 337 us per launch); the fp32 form needs 296 registers at 128 x 128 = one wave per SIMD and loses (765 -> 987 us)
-            const int gts = (p->bf_products && d >= 128) ? 128 : 64;
-            // Top block: only position L-1 of each sequence carries an upstream gradient (bsarec.py:32), so dq, dO, dU
-            // and dT2 are zero on every other row: their four products reduce over the B last positions only
-            // (row stride L*ld), exactly; dk and dv still reduce over all tokens.
-            const bool top = (l == N - 1) && !p->ext_dy;       // (an external upstream gradient has every row)
-            for (int i = 0; i < 6; ++i) {
-                const bool last_only = top && i != 1 && i != 2;
-                GemmP g = gemm_defaults(sp[i].M, sp[i].N, last_only ? B : T);
-                g.lda = sp[i].lda; g.ldb = sp[i].ldb; g.A[0] = sp[i].A; g.B[0] = sp[i].B; g.nsplit = ns; g.kchunk = p->kchunk;
-                if (last_only) {
-                    // row L-1 of every sequence (element offsets: the operands are bf16 tensors under storage = 1)
-                    const long esz = p->bf ? 2 : 4;
-                    g.A[0] = (const float*)((const char*)g.A[0] + (long)(L - 1) * sp[i].lda * esz);
-                    g.B[0] = (const float*)((const char*)g.B[0] + (long)(L - 1) * sp[i].ldb * esz);
-                    g.lda *= L; g.ldb *= L;
-                    g.kchunk = (int)rup(cdiv(B, ns), GEMM_BK);           // slices beyond ceil(B / kchunk) write zero slabs
-                    if (top_pruned) {                                    // gradient rows come compact ([B][M]) from top_bwd_kernel
-                        g.A[0] = i == 0 ? p->top_dq : i == 3 ? p->top_dO : i == 4 ? p->top_dU : p->top_dT;
-                        g.lda = sp[i].M;
-                        g.nsplit = std::min(p->top_slabs, ns); g.kchunk = (int)rup(cdiv(B, g.nsplit), GEMM_BK);
-                    }
-                }
-                // pruned top block: dK, dV are rank-1 per (sequence, head) -> dWk = AK^T RK, dWv = AV^T RV over B*h rows
-                // (fused_top.h); their bias gradients come from per-sequence partials, the slab output is discarded
-                const bool compact = top_pruned && (i == 1 || i == 2);
-                if (compact) {
-                    g = gemm_defaults(d, d, B * h);
-                    g.A[0] = i == 1 ? p->top_ak : p->top_av; g.B[0] = i == 1 ? p->top_rk : p->top_rv; g.lda = d; g.ldb = d;
-                    g.nsplit = std::min(p->top_slabs, ns); g.kchunk = (int)rup(cdiv(B * h, g.nsplit), GEMM_BK);
-                }
-                G.P[i] = g;
-                G.E[i] = epi_linear<false, false, false>(slab_w_ptr(*p, sp[i].woff), sp[i].N);
-                G.E[i].c_split = (long)sp[i].M * sp[i].N;
-                G.bgrad[i] = compact ? p->slab_dummy : slab_b_ptr(*p, sp[i].boff);
-                G.tile0[i] = tiles;
-                G.tiles_n[i] = cdiv(sp[i].N, gts);
-                G.b_gelu[i] = sp[i].gelu;
-                tiles += cdiv(sp[i].M, gts) * G.tiles_n[i];
-            }
-            G.tile0[6] = tiles; G.nprob = 6; G.act = c.hidden_act;
-            if (p->fused && p->direct_dw) {
-                // hidden = 64: direct split-K products, one workgroup per (problem, 64x64 tile, slab slice) -- dw_direct.h.
-                // The pruned top block's six (tiny) problems are not launched on their own: they wait in DW and ride in
-                // the next block's launch.
-                for (int i = 0; i < 6; ++i) {
-                    const GemmP& g = G.P[i];
-                    DwProblem& q = DW.P[dw_np];
-                    q.A = g.A[0]; q.B = g.B[0]; q.lda = g.lda; q.ldb = g.ldb; q.M = g.M; q.N = g.N; q.K = g.K;
-                    q.kchunk = g.kchunk; q.nslab = g.nsplit; q.slab = G.E[i].C[0]; q.bslab = G.bgrad[i]; q.gelu = G.b_gelu[i];
-                    q.bf16 = p->bf ? 1 : 0;
-                    for (int m0 = 0; m0 < q.M; m0 += 64)
-                        for (int n0 = 0; n0 < q.N; n0 += 64) DW.U[dw_nu++] = DwUnit{(short)dw_np, (short)m0, (short)n0, 0};
-                    ++dw_np;
-                }
-                if (top_pruned) { DW.nsmall = dw_nu; DW.small_slabs = std::min(p->top_slabs, ns); }
-                else {
-                    DW.nunits = dw_nu; DW.nslab = ns;
-                    TickP tk_here;                     // the step tick rides in block 0's launch when Adam is fused into the reduction
-                    memset(&tk_here, 0, sizeof(tk_here));
-                    if (fuse_adam && l == 0) tk_here = tick;
-                    ScatterP sc;                       // ... and so does the embedding-gradient scatter (block 0's launch: dz is complete)
-                    memset(&sc, 0, sizeof(sc));
-                    if (p->scatter_in_block && l == 0) {
-                        sc.de = p->dz; sc.ids32 = p->ids32; sc.T = T; sc.dA = p->lookup_acc;
-                        sc.nblocks = cdiv(T, SCATTER_FLOATS / 64);
-                    }
-                    for (int i = 0; i < dw_np; ++i) if (!dw_problem_ok(DW.P[i])) return -21;
-                    if (sc.nblocks && (!sc.de || !sc.ids32 || !sc.dA)) return -21;
-                    ProfScope prof(BSAREC_K_DW1, s);
-                    const dim3 dw_grid(8 * cdiv(ns, 8) * (dw_nu - DW.nsmall) + DW.nsmall * DW.small_slabs + sc.nblocks + (tk_here.state ? 1 : 0));
-                    LAUNCH(dw_direct_kernel, dw_grid, dim3(256), 0, s, DW, tk_here, sc);
-                    HIPCHK(hipGetLastError());
-                    dw_np = 0; dw_nu = 0; DW.nsmall = 0; DW.small_slabs = 0;
-                }
-            } else {
-            ProfScope prof(BSAREC_K_DW1, s);
-#define GROUPED_LAUNCH(BFV, TSV) do { \
-                constexpr size_t sm_ = GemmSmem<TSV, TSV, true, true, BFV>::BYTES; \
-                static bool attr_ = false; \
-                if (!attr_) { if (sm_ > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_grouped_tn_kernel<BFV, TSV>), \
-                                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_)); attr_ = true; } \
-                LAUNCH((gemm_grouped_tn_kernel<BFV, TSV>), dim3(tiles, ns), dim3(GEMM_THREADS), sm_, s, G); } while (0)
-            if (p->bf_products) { if (gts == 128) GROUPED_LAUNCH(true, 128); else GROUPED_LAUNCH(true, 64); }
-            else GROUPED_LAUNCH(false, 64);
-#undef GROUPED_LAUNCH
-            HIPCHK(hipGetLastError());
-            }
-        }
+            RET(launch_fused_bwd(*p, l, tr, dY, dXout, s, l == N - 1 && !p->ext_dy,
+                                 (pend.have_head && l == N - 2) ? &pend.top_head : nullptr));
+        } else RET(generic_layer_bwd(*p, l, dY, s));
+        // all six weight gradients + bias gradients of the block: one split-K launch (the step tick rides in block 0's direct
+        // launch when Adam is fused into the reduction)
+        GroupedTN G;
+        build_dw_problems(*p, l, top_pruned, G);
+        if (p->fused && p->direct_dw) RET(launch_dw_direct(*p, l, top_pruned, G, pend, (fuse_adam && l == 0) ? &tick : nullptr, s));
+        else RET(launch_dw_grouped(*p, G, s));
         // ---- FrequencyLayer backward: completes dX of this layer
-        if (!p->fused)
-            DISPATCH_LPR(d, RET(launch_freq_bwd<LPR>(X, p->dF, p->dXtmp, w.sqrt_beta, p->twiddle, B, L, d, c.cutoff_bins,
-                                                     dXout, p->part_beta, s, c.filter_kind == 1 ? w.filter_cw : nullptr,
+        if (!p->fused) {
+            const bsarec_layer_t& w = p->P.layer[l];
+            DISPATCH_LPR(d, RET(launch_freq_bwd<LPR>(p->X[l], p->dF, p->dXtmp, w.sqrt_beta, p->twiddle, B, L, d, c.cutoff_bins,
+                                                     dXout, p->part_betaL[l], s, c.filter_kind == 1 ? w.filter_cw : nullptr,
                                                      c.filter_kind == 1 ? p->part_cwL[l] : nullptr)));
+        }
         dY = dXout;
         // forward(all_sequence_output=True): layer output l may carry an upstream gradient of its own -- it joins the gradient
         // coming down from the blocks above (the fused bottom block adds output 0's inside its epilogue: its dX never
@@ -1475,65 +1513,8 @@ static int backward_impl(bsarec_plan_t* p, void* stream, const TickP& tick, cons
             HIPCHK(hipGetLastError());
         }
     }
-    // ---- embedding front-end backward
-    {
-        hipStream_t se = s;
-        LnBranch a; memset(&a, 0, sizeof(a));
-        a.xhat = p->xhat0; a.rstd = p->rstd0; a.gamma = p->P.ln_w; a.in_scale = 1.f;
-        a.drop = make_drop(*p, c.p_hidden, 0, tr); a.dT = nullptr;
-        a.pgamma = p->part_ln0 + 0L * nb * d; a.pbeta = p->part_ln0 + 1L * nb * d;
-        if (!p->fused) {                  // fused path: done by the bottom block's backward kernel
-            DISPATCH_LPR(d, LAUNCH((ln_bwd_kernel<LPR, 2>), dim3(nb), dim3(ROW_THREADS), 0, se, dY, a, a, p->dz, T, d, p->rows_pb));
-            HIPCHK(hipGetLastError());
-        }
-        if (!p->scatter_in_block)
-        DISPATCH_LPR(d, {
-            constexpr int CHUNK = SCATTER_FLOATS / (LPR * 4);
-            constexpr size_t smem = SCATTER_FLOATS * 8 + 2 * CHUNK * 4;
-            static bool attr = false;
-            if (!attr) {
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(embed_bwd_kernel<LPR>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                attr = true;
-            }
-            const int sb = cdiv(T, CHUNK);
-            LAUNCH(embed_bwd_kernel<LPR>, dim3(sb + L * p->pos_slices), dim3(ROW_THREADS), smem, se, p->dz, p->ids32, B, L, d,
-                   p->lookup_acc, p->part_pos, sb);
-            HIPCHK(hipGetLastError());
-        });
-        // ---- ONE deterministic second-stage reduction for every split-K slab and LayerNorm / beta partial
-        // (no empty blocks: flat block map); its extra last block closes the optimisation step when asked to
-        // (the lookup-path sum of the item-table gradient joins its target here: after every scatter block has finished)
-        LookupAcc la;
-        memset(&la, 0, sizeof(la));
-        la.acc = p->lookup_acc; la.dst = p->lookup_grad ? p->lookup_grad : p->G.item_emb; la.n4 = (long)c.item_size * d / 4;
-        la.nblocks = (int)std::min<long>(cdiv(la.n4, ROW_THREADS), 1024);
-        la.dense_zero = (!p->ext_dy && p->loss_kind == 2) ? 1 : 0;
-        const bool lazy = p->lazy_now && !p->ext_dy && p->loss_kind == 2;
-        if (lazy) {                        // lazy Adam: the rows of T only, in a grid sized to the list's capacity
-            la.lazy = p->lazy;
-            la.nblocks = (int)std::min<long>(cdiv((long)p->lazy.cap * p->lazy.d4, ROW_THREADS), 1024);
-        }
-        if (fuse_adam) {
-            const bsarec_adam_t& a = *fuse_adam;
-            AdamFuseP A;
-            memset(&A, 0, sizeof(A));
-            A.w = a.params; A.g = const_cast<float*>(a.grads); A.m = a.exp_avg; A.v = a.exp_avg_sq;
-            A.b1 = a.beta1; A.b2 = a.beta2; A.eps = a.eps; A.wd = a.weight_decay;
-            A.shadow = (unsigned short*)a.shadow_bf16; A.shadow_from = a.shadow_bf16 ? a.shadow_from : a.n;
-            A.item_off = p->G.item_emb - a.grads; A.item_n4 = (long)c.item_size * d / 4; A.lookup_acc = la.acc;
-            A.dense_zero = la.dense_zero;
-            if (lazy) A.lazy = p->lazy;
-            int ab = lazy ? la.nblocks : cdiv(A.item_n4, ROW_THREADS);
-            if (ab > 1024) ab = 1024;
-            LAUNCH(reduce_adam_kernel, dim3(p->red_blocks + ab), dim3(ROW_THREADS), 0, s, p->pruned ? p->jobs_pruned : p->jobs,
-                   p->blockmap, p->red_blocks, (const uint64_t*)p->state, A);
-        } else
-        LAUNCH(multi_reduce_flat_kernel, dim3(p->red_blocks + la.nblocks + (tick.state ? 1 : 0)), dim3(ROW_THREADS), 0, s,
-               p->pruned ? p->jobs_pruned : p->jobs, p->blockmap, p->red_blocks, tick, la);
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
+    RET(embed_bwd(*p, dY, s));
+    return final_reduce(*p, tick, fuse_adam, s);
 }
 
 // ---------------------------------------------------------------------------------------------
