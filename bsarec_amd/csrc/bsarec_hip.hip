@@ -268,8 +268,10 @@ static void derive(bsarec_plan& p) {
     // split-K over tokens for the weight-gradient products: 32 / 40 slab slices (below), 32-aligned chunks (the direct kernel of
     // the fused shape cuts every slice into 4 more quarters inside a workgroup)
     // fused shape, C1 (12 weight-gradient units): 32 slices = 384 workgroups leave 128 of the kernel's 512 slots to the
-    // embedding scatter blocks from the first cycle (measured with exact k-block counts, 24 / 28 / 32 / 40 slices:
-    // 0.1722 / 0.1706 / 0.1694 / 0.1745 ms per step)
+    // embedding scatter blocks from the first cycle.  Re-measured with the per-workgroup record (tools/dw_stamps.py):
+    // 40 slices (two workgroups on 224 of the 256 CUs, 10 whole k-blocks per wave) end the big workgroups 2 us sooner,
+    // but the scatter blocks then start up to 17 us into the launch and the final reduction reads 8 more slabs:
+    // 32 / 40 slices = 0.1533 / 0.1551 ms per step (three runs each, alternating), so 32 stays
     const int want_splits = c.splits > 0 ? c.splits : (p.fused ? 32 : 40);
     p.top_slabs = c.top_slabs > 0 ? c.top_slabs : 2;
     p.embed_in_block = !c.separate_embed || p.bf;     // bf16 storage: X[0] is written by the block kernel only
@@ -799,6 +801,16 @@ static int launch_top_bwd(bsarec_plan& p, int l, bool tr, float* dXout, hipStrea
 }
 
 extern "C" int bsarec_debug_stamps(bsarec_plan_t* p, void* dev_buf) { if (!p) return -10; p->stamps = (long long*)dev_buf; return 0; }
+
+#ifdef BSAREC_DW_STAMPS
+// diagnostic build only: the per-workgroup record of the last dw_direct_kernel launch (dw_direct.h), n rows of 8 words
+extern "C" int bsarec_debug_dw_stamps(long long* host_out, int n) {
+    if (!host_out || n < 1 || n > DW_STAMP_MAX) return -10;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_dw_stamps), (size_t)n * 8 * sizeof(long long)));
+    return 0;
+}
+#endif
 
 extern "C" int bsarec_step_begin(bsarec_plan_t* p, void* stream) {
     if (!p) return -10;

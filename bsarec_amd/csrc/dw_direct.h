@@ -12,9 +12,14 @@
 // MFMAs and keeps DW_STAGES k-blocks in flight in registers.
 //
 // Work decomposition: unit = (problem, 64 x 64 tile); the token axis is cut into `nslab` slab slices, each slice
-// again into 4 quarters taken by the 4 waves of a workgroup, which add their accumulators through LDS and write ONE
-// slab; the step's flat reduction sums the nslab slabs (deterministic, fixed order).  The LDS-tiled kernel this
-// replaces at the fused shape spent ~1 us per 32-deep k-step on store -> barrier -> fragment-read latency.
+// again into 4 quarters taken by the 4 waves of a workgroup, which park their accumulators in LDS, add them in wave
+// order -- each wave a quarter of the tile -- and write ONE slab; the step's flat reduction sums the nslab slabs
+// (deterministic, fixed order).  The LDS-tiled kernel this replaces at the fused shape spent ~1 us per 32-deep k-step
+// on store -> barrier -> fragment-read latency.
+// Measured per workgroup at C1 (tools/dw_stamps.py, profiles/r04_dw_stamps_*.txt): 32 slices put two big workgroups on
+// 116 CUs and one on 140, yet the doubly loaded ones last 20 us against 15.6 us, not twice as long: a workgroup's life
+// is ~1 us of set-up, a k loop paced by memory (13-14 us for 13 k-blocks, and 13 us for the 4 k-blocks of a top-block
+// problem started beside them) and the reduction.  See DESIGN 4.2 before re-balancing MFMA work across CUs.
 #pragma once
 #include "fused_layer.h"
 
@@ -226,8 +231,37 @@ __device__ __forceinline__ void dw_loop_c(__amdgpu_buffer_rsrc_t ra, __amdgpu_bu
 }
 #define DW_STAGES_M 3         // 48 token rows in flight per wave (the widening form: 5 x 8)
 
+#ifdef BSAREC_DW_STAMPS
+// Diagnostic build only (-DBSAREC_DW_STAMPS; tools/dw_stamps.py): per workgroup of the LAST dw_direct_kernel launch its
+// start and end on the constant 100 MHz clock, where it ran (HW_ID, XCC_ID) and what it was (0 big, 1 small, 2 scatter,
+// 3 tick, 4 empty).  The record is wave 0's: the four waves of a big workgroup leave the barrier together and end within
+// the shared reduction.
+#define DW_STAMP_MAX 2048
+__device__ long long g_dw_stamps[DW_STAMP_MAX][8];
+struct DwStampScope {
+    long long t0; int kind;
+    __device__ DwStampScope() : t0(wall_clock64()), kind(4) {}
+    __device__ ~DwStampScope() {
+        if (threadIdx.x == 0 && blockIdx.x < DW_STAMP_MAX) {
+            long long* r = g_dw_stamps[blockIdx.x];
+            r[0] = t0; r[1] = wall_clock64();
+            r[2] = ((long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 4);
+            r[3] = kind;
+        }
+    }
+};
+#define DW_STAMP_SCOPE DwStampScope dw_stamp_
+#define DW_STAMP_KIND(k) dw_stamp_.kind = (k)
+// phases of wave 0 inside dw_wg_body: 4 operands known, 5 k loop done, 6 past the barrier
+#define DW_STAMP_AT(i) do { if (threadIdx.x == 0 && blockIdx.x < DW_STAMP_MAX) g_dw_stamps[blockIdx.x][i] = wall_clock64(); } while (0)
+#else
+#define DW_STAMP_SCOPE
+#define DW_STAMP_KIND(k)
+#define DW_STAMP_AT(i)
+#endif
+
 // One workgroup = one (problem, 64 x 64 tile, slab slice): its 4 waves take the 4 quarters of the slice, meet in LDS,
-// wave 0 writes the slab.
+// each wave adds and writes a quarter of the slab tile.
 // STAGES = k-blocks in flight per wave = the granule the wave's k range is rounded up to: 5 for the block weight
 // gradients (10 k-blocks per wave at C1), 4 for the logits backward (8 resp. 16 k-blocks per wave: no padding MFMAs).
 // BFM: the instantiation for plans with bf16 storage -- bf16 operands go to the bf16 matrix cores (dw_loop_m); the fp32
@@ -262,6 +296,7 @@ __device__ __forceinline__ void dw_wg_body(const DwProblem& Q, int m0, int n0, i
         const int soa = kbeg * rowa, sob = kbeg * rowb;
         const int crow = kbeg + 4 * half;
         const bool full = kbeg + 8 * nkb <= kend;                            // no partial last k-block: the unmasked loop
+        DW_STAMP_AT(4);
 #define DW_RUN(BFV) \
         if (Q.gelu) { \
             if (full) dw_loop<true, false, BFV, STAGES>(ra, rb, voa, vob, soa, sob, rowa, rowb, nkb, crow, kend, acc, bs); \
@@ -290,11 +325,15 @@ __device__ __forceinline__ void dw_wg_body(const DwProblem& Q, int m0, int n0, i
         } else { DW_RUN(false) }
 #undef DW_RUN
     }
+    DW_STAMP_AT(5);
     // bias gradient: column sums of the gradient operand; the two lane halves hold different token rows
     bs.x = xor32_sum(bs.x); bs.y = xor32_sum(bs.y);
-    // the four quarters meet in LDS: waves 1..3 park their registers, wave 0 adds them in a fixed order
-    if (wv > 0) {
-        float (*mine)[64] = red[wv - 1];
+    // the four quarters meet in LDS: every wave parks its registers, then wave w finishes a quarter of the tile -- tile row
+    // parity w >> 1, registers 8 (w & 1) .. + 7 -- adding the four waves' values in wave order (the same fixed order whichever
+    // wave adds) and storing its 8 slab rows.  (One wave doing all of it kept the other three SIMDs idle for the launch's last
+    // ~3 us: DESIGN 4.2.)
+    {
+        float (*mine)[64] = red[wv];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -304,27 +343,25 @@ __device__ __forceinline__ void dw_wg_body(const DwProblem& Q, int m0, int n0, i
         mine[64][lane] = bs.x; mine[65][lane] = bs.y;
     }
     __syncthreads();
-    if (wv > 0) return;
-#pragma unroll 1
-    for (int w = 0; w < 3; ++w) {              // not unrolled: one wave's 66 values live at a time
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int jn = 0; jn < 2; ++jn)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][jn][r] += red[w][(i * 2 + jn) * 16 + r][lane];
-        bs.x += red[w][64][lane]; bs.y += red[w][65][lane];
-    }
+    DW_STAMP_AT(6);
     // slab: register r of lane (l31, half) of tile (i, jn) is C[m0 + 2 (rho(r) + 4 half) + i][n0 + 2 l31 + jn]
     float* C = Q.slab + (long)slab * Q.M * Q.N;
+    const int qi = wv >> 1, r0 = (wv & 1) * 8;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int rr = 0; rr < 8; ++rr) {
+        const int r = r0 + rr;
+        f32x2 v = {red[0][(qi * 2) * 16 + r][lane], red[0][(qi * 2 + 1) * 16 + r][lane]};
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + 2 * (rho(r) + 4 * half) + i;
-            if (m < Q.M) gst2(C + (long)m * Q.N + n0 + 2 * l31, f32x2{acc[i][0][r], acc[i][1][r]});
-        }
-    if (Q.bslab && n0 == 0 && half == 0 && m0 + 2 * l31 + 1 < Q.M) gst2(Q.bslab + (long)slab * Q.M + m0 + 2 * l31, bs);
+        for (int w = 1; w < 4; ++w) { v.x += red[w][(qi * 2) * 16 + r][lane]; v.y += red[w][(qi * 2 + 1) * 16 + r][lane]; }
+        const int m = m0 + 2 * (rho(r) + 4 * half) + qi;
+        if (m < Q.M) gst2(C + (long)m * Q.N + n0 + 2 * l31, v);
+    }
+    if (wv == 0 && Q.bslab && n0 == 0 && half == 0 && m0 + 2 * l31 + 1 < Q.M) {
+        f32x2 b = {red[0][64][lane], red[0][65][lane]};
+#pragma unroll
+        for (int w = 1; w < 4; ++w) { b.x += red[w][64][lane]; b.y += red[w][65][lane]; }
+        gst2(Q.bslab + (long)slab * Q.M + m0 + 2 * l31, b);
+    }
 }
 
 
@@ -341,12 +378,14 @@ struct ScatterP { const float* de; const int* ids32; int T; unsigned long long* 
 // kept because it is measured.  The logits backward below is the opposite case and has two.)
 __global__ void __launch_bounds__(256)
 dw_direct_kernel(const DwP G, const TickP tk, const ScatterP sc) {
-    __shared__ __attribute__((aligned(16))) float red[3][66][64];      // accumulators (64) + bias sums (2) of waves 1..3
+    __shared__ __attribute__((aligned(16))) float red[4][66][64];      // accumulators (64) + bias sums (2) of the 4 waves
     static_assert(sizeof(red) >= (2 * SCATTER_FLOATS + 2 * (SCATTER_FLOATS / 64)) * 4, "scatter scratch fits the reduction scratch");
+    DW_STAMP_SCOPE;
     {
         const int nmain = 8 * ((G.nslab + 7) >> 3) * (G.nunits - G.nsmall) + G.nsmall * G.small_slabs;
         if ((int)blockIdx.x >= nmain) {
             const int x = blockIdx.x - nmain;
+            DW_STAMP_KIND(x < sc.nblocks ? 2 : 3);
             if (x < sc.nblocks) embed_scatter_block<16>(sc.de, sc.ids32, sc.T, 64, sc.dA, x, &red[0][0][0]);
             else if (tk.state) tick_body(tk, &red[0][0][0]);
             return;
@@ -362,9 +401,11 @@ dw_direct_kernel(const DwP G, const TickP tk, const ScatterP sc) {
         slab = xcd + 8 * (j / nbig);
         if (slab >= G.nslab) return;
         ui = G.nsmall + j % nbig;
+        DW_STAMP_KIND(0);
     } else {                                              // the small ones fill the free slots and finish early
         const int bid = blockIdx.x - nbw;
         ui = bid % G.nsmall; slab = bid / G.nsmall;
+        DW_STAMP_KIND(1);
     }
     const DwUnit u = G.U[ui];
     const DwProblem& Q = G.P[u.prob];
@@ -490,7 +531,7 @@ __device__ __forceinline__ void dh_wave_body(const DhP& G, int wg) {
 template <bool BFH>
 __global__ void __launch_bounds__(256)
 logits_bwd_direct_kernel(const DwProblem Q, int tiles, const DhP H) {
-    __shared__ __attribute__((aligned(16))) float red[3][66][64];
+    __shared__ __attribute__((aligned(16))) float red[4][66][64];
     if ((int)blockIdx.x < tiles) dw_wg_body<4, false, BFH>(Q, 64 * (int)blockIdx.x, 0, 0, red);
     else dh_wave_body<4, BFH>(H, (int)blockIdx.x - tiles);
 }
