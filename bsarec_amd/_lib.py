@@ -48,19 +48,23 @@ class Config(C.Structure):
                 # sampled-softmax training head (0 = full-catalogue CE)
                 ("train_negatives", C.c_int), ("train_sampler", C.c_int), ("train_no_logq", C.c_int),
                 # lazy (sparse) Adam for the item table under the sampled head (0 = dense Adam)
-                ("train_lazy_adam", C.c_int)]
+                ("train_lazy_adam", C.c_int),
+                # fp32 fused block kernels read the Linear weights from their fragment-ordered image (csrc/wimage.h)
+                ("weight_image", C.c_int)]
 
 
 TRAIN_FIELDS = ("train_negatives", "train_sampler", "train_no_logq")
 TRAIN_SAMPLERS = {"uniform": 0, "popularity": 1}
 
 
-OPTION_FIELDS = ("storage", "no_fused", "no_prune_top", "dw_tiled", "splits", "top_slabs", "separate_embed", "separate_top", "chain_kernels", "x3_products")
+OPTION_FIELDS = ("storage", "no_fused", "no_prune_top", "dw_tiled", "splits", "top_slabs", "separate_embed", "separate_top", "chain_kernels", "x3_products",
+                 "weight_image")
 HIDDEN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "tanh": 3, "sigmoid": 4}      # src/model/_modules.py:38-45
 
 # Plan options the HOST gives to plans it creates from now on.  The C ABI has no process-wide state: these are Python
 # defaults (test / bench shims and the environment knobs of INTEGRATION.md), copied into bsarec_config_t per plan.
 _defaults = {k: 0 for k in OPTION_FIELDS}
+_defaults["weight_image"] = 1        # on wherever the library can use it (fp32 plans at the fused shape), ignored elsewhere
 
 
 def _env_defaults():
@@ -85,6 +89,8 @@ def _env_defaults():
             d[key] = int(e[env])
     if e.get("BSAREC_STORAGE") == "bf16":
         d["storage"] = 1
+    if e.get("BSAREC_WEIGHT_IMAGE") == "0":
+        d["weight_image"] = 0
     return d
 
 
@@ -120,7 +126,8 @@ class Adam(C.Structure):
     _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
                 ("n", C.c_long), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float), ("grad_scale", C.c_float), ("shadow_bf16", C.c_void_p), ("shadow_from", C.c_long),
-                ("grads2", C.c_void_p), ("grads2_n", C.c_long), ("n_grad_srcs", C.c_int), ("grad_srcs", C.c_void_p * 8)]
+                ("grads2", C.c_void_p), ("grads2_n", C.c_long), ("n_grad_srcs", C.c_int), ("grad_srcs", C.c_void_p * 8),
+                ("wimage_plan", C.c_void_p)]
 
 
 class Comm(C.Structure):
@@ -138,6 +145,9 @@ EXPORTS = {
     "bsarec_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(Config), C.POINTER(Tensors), C.POINTER(Tensors),
                                      C.POINTER(Tensors), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_shadow_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bsarec_wimage_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bsarec_wimage_floats": (C.c_long, [C.POINTER(Config)]),
+    "bsarec_wimage_offset": (C.c_long, [C.c_int] * 5),
     "bsarec_plan_set_dense_grad_hook": (C.c_int, [C.c_void_p, HOOK, C.c_void_p, C.c_void_p]),
     "bsarec_plan_set_train_sampler": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bsarec_buffer_is_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

@@ -111,6 +111,9 @@ struct bsarec_plan {
     // lazy Adam (cfg.train_lazy_adam = 1; lazy_adam.h): the touched-row marks and list, used while a step runs lazily
     LazyRows lazy = {};
     bool lazy_now = false;                     // set by bsarec_train_step / _indexed around their launches (LazyStep)
+    // fragment image of the Linear weights (cfg.weight_image; wimage.h): [layers][wimage_layer_floats(d)], the caller's
+    // memory (bsarec_plan_create); null = the block kernels read the masters
+    float* wimg = nullptr;
 };
 struct PlanScope {                           // marks the plan a C call works on for this thread (nesting-safe)
     bsarec_plan* prev;
@@ -233,7 +236,14 @@ static int check_cfg(const bsarec_config_t& c) {
     if (c.train_sampler < 0 || c.train_sampler > 1 || c.train_no_logq < 0 || c.train_no_logq > 1) return -17;
     if (c.train_negatives > 0 && c.storage != 0) return -18;      // the sampled head is fp32 only
     if (c.train_lazy_adam < 0 || c.train_lazy_adam > 1 || (c.train_lazy_adam && c.train_negatives == 0)) return -19;
+    if (c.weight_image < 0 || c.weight_image > 1) return -20;
     return 0;
+}
+
+static bool fused_shape_ok(const bsarec_config_t& c);
+// fragment image: only where the fp32 LDS-phase block kernels run (the bf16 / x3 / chain / FMLPRec variants read the masters)
+static bool wimage_wanted(const bsarec_config_t& c) {
+    return c.weight_image && fused_shape_ok(c) && c.storage == 0 && !c.x3_products && !c.chain_kernels && c.filter_kind == 0;
 }
 
 static bool fused_shape_ok(const bsarec_config_t& c) {
@@ -392,12 +402,27 @@ static float* ln0_part(const bsarec_plan& p, Ln0Part k) { return p.part_ln0 + (l
 static const float* h_last(const bsarec_plan& p) { return p.X[p.cfg.layers] + (long)(p.cfg.seq_len - 1) * p.cfg.hidden; }
 static long h_last_stride(const bsarec_plan& p) { return (long)p.cfg.seq_len * p.cfg.hidden; }
 
+// fragment image (wimage.h): one weight's F / T image of layer l, and a layer's Linear weights as their images
+static float* wimage_weight(const bsarec_plan& p, int l, int which, bool transposed) {
+    const long d = p.cfg.hidden;
+    return p.wimg + l * wimage_layer_floats(d) + (transposed ? 12 * d * d : 0) + wimage_weight_off(which, d);
+}
+static bsarec_layer_t wimage_layer(const bsarec_plan& p, int l, bool transposed) {
+    bsarec_layer_t w;
+    memset(&w, 0, sizeof(w));
+    w.query_w = wimage_weight(p, l, WIMAGE_WQ, transposed); w.key_w = wimage_weight(p, l, WIMAGE_WK, transposed);
+    w.value_w = wimage_weight(p, l, WIMAGE_WV, transposed); w.dense_w = wimage_weight(p, l, WIMAGE_WO, transposed);
+    w.ffn1_w = wimage_weight(p, l, WIMAGE_W1, transposed); w.ffn2_w = wimage_weight(p, l, WIMAGE_W2, transposed);
+    return w;
+}
+
 extern "C" int bsarec_plan_create(bsarec_plan_t** out, const bsarec_config_t* cfg, const bsarec_tensors_t* params,
                                   const bsarec_tensors_t* grads, const bsarec_tensors_t* shadow, void* workspace,
                                   size_t workspace_bytes, void* state, const float* twiddle, void* stream) {
     if (!out || !cfg || !params || !workspace || !state || !twiddle) return -10;
     RET(check_cfg(*cfg));
     if (cfg->storage == 1 && fused_shape_ok(*cfg) && !shadow) return -15;     // (the generic path rounds its operands itself)
+    if (wimage_wanted(*cfg) && (!shadow || !shadow->layer[0].query_w || ((uintptr_t)shadow->layer[0].query_w & 255))) return -15;
     if (((uintptr_t)workspace & 255) != 0) return -11;
     bsarec_plan* p = new bsarec_plan();
     p->cfg = *cfg;
@@ -406,6 +431,7 @@ extern "C" int bsarec_plan_create(bsarec_plan_t** out, const bsarec_config_t* cf
     if (shadow) p->S = *shadow; else memset(&p->S, 0, sizeof(p->S));
     p->ws = (char*)workspace; p->ws_bytes = workspace_bytes;
     p->state = (uint64_t*)state; p->twiddle = twiddle; p->train = false;
+    p->wimg = wimage_wanted(*cfg) ? shadow->layer[0].query_w : nullptr;
     derive(*p);
     size_t total = 0;
     carve(*p, p->ws, &total);
@@ -427,19 +453,26 @@ extern "C" int bsarec_plan_create(bsarec_plan_t** out, const bsarec_config_t* cf
         jobs.push_back(j);
     };
     const int ns = p->nsplit, nb = p->nblk;
+    auto add_w = [&](int l, int which, const float* src, float* dst) {       // a Linear weight: the job also names its image
+        add(src, dst, ns, (which >= WIMAGE_W1 ? 4 : 1) * d * d);
+        if (!p->wimg) return;
+        ReduceJob& j = jobs.back();
+        j.img_f = wimage_weight(*p, l, which, false); j.img_t = wimage_weight(*p, l, which, true);
+        j.wn = (int)(which == WIMAGE_W1 ? 4 * d : d); j.wk = (int)(which == WIMAGE_W2 ? 4 * d : d);
+    };
     for (int l = 0; l < cfg->layers; ++l) {
         const bsarec_layer_t& g = p->G.layer[l];
         add(p->part_betaL[l], g.sqrt_beta, cfg->batch, d);
         add(ln_part(*p, l, LN_F_G), g.filter_ln_w, nb, d);
         add(ln_part(*p, l, LN_F_B), g.filter_ln_b, nb, d);
-        add(slab_w_ptr(*p, l, sm.wq), g.query_w, ns, d * d); add(slab_b_ptr(*p, l, sm.bq), g.query_b, ns, d);
-        add(slab_w_ptr(*p, l, sm.wk), g.key_w, ns, d * d);   add(slab_b_ptr(*p, l, sm.bk), g.key_b, ns, d);
-        add(slab_w_ptr(*p, l, sm.wv), g.value_w, ns, d * d); add(slab_b_ptr(*p, l, sm.bv), g.value_b, ns, d);
-        add(slab_w_ptr(*p, l, sm.wo), g.dense_w, ns, d * d); add(slab_b_ptr(*p, l, sm.bo), g.dense_b, ns, d);
+        add_w(l, WIMAGE_WQ, slab_w_ptr(*p, l, sm.wq), g.query_w); add(slab_b_ptr(*p, l, sm.bq), g.query_b, ns, d);
+        add_w(l, WIMAGE_WK, slab_w_ptr(*p, l, sm.wk), g.key_w);   add(slab_b_ptr(*p, l, sm.bk), g.key_b, ns, d);
+        add_w(l, WIMAGE_WV, slab_w_ptr(*p, l, sm.wv), g.value_w); add(slab_b_ptr(*p, l, sm.bv), g.value_b, ns, d);
+        add_w(l, WIMAGE_WO, slab_w_ptr(*p, l, sm.wo), g.dense_w); add(slab_b_ptr(*p, l, sm.bo), g.dense_b, ns, d);
         add(ln_part(*p, l, LN_A_G), g.attn_ln_w, nb, d);
         add(ln_part(*p, l, LN_A_B), g.attn_ln_b, nb, d);
-        add(slab_w_ptr(*p, l, sm.w1), g.ffn1_w, ns, 4 * d * d); add(slab_b_ptr(*p, l, sm.b1), g.ffn1_b, ns, 4 * d);
-        add(slab_w_ptr(*p, l, sm.w2), g.ffn2_w, ns, 4 * d * d); add(slab_b_ptr(*p, l, sm.b2), g.ffn2_b, ns, d);
+        add_w(l, WIMAGE_W1, slab_w_ptr(*p, l, sm.w1), g.ffn1_w); add(slab_b_ptr(*p, l, sm.b1), g.ffn1_b, ns, 4 * d);
+        add_w(l, WIMAGE_W2, slab_w_ptr(*p, l, sm.w2), g.ffn2_w); add(slab_b_ptr(*p, l, sm.b2), g.ffn2_b, ns, d);
         add(ln_part(*p, l, LN_FF_G), g.ffn_ln_w, nb, d);
         add(ln_part(*p, l, LN_FF_B), g.ffn_ln_b, nb, d);
     }
@@ -567,6 +600,33 @@ extern "C" int bsarec_buffer_is_bf16(const bsarec_plan_t* p, int buffer, int lay
         case BSAREC_BUF_DLAYER_IN: return 1;
         default: return 0;
     }
+}
+
+extern "C" int bsarec_wimage_refresh(bsarec_plan_t* p, void* stream) {
+    if (!p) return -10;
+    if (!p->wimg) return 0;
+    WImageP W;
+    memset(&W, 0, sizeof(W));
+    for (int l = 0; l < p->cfg.layers; ++l) {
+        const bsarec_layer_t& w = p->P.layer[l];
+        const float* src[WIMAGE_NW] = {w.query_w, w.key_w, w.value_w, w.dense_w, w.ffn1_w, w.ffn2_w};
+        for (int i = 0; i < WIMAGE_NW; ++i) W.w[l][i] = src[i];
+    }
+    W.img = p->wimg; W.d = p->cfg.hidden;
+    LAUNCH(wimage_refresh_kernel, dim3(cdiv(12L * W.d * W.d, ROW_THREADS), p->cfg.layers), dim3(ROW_THREADS), 0, (hipStream_t)stream, W);
+    return g_dry ? 0 : (int)hipGetLastError();
+}
+
+extern "C" long bsarec_wimage_floats(const bsarec_config_t* cfg) {
+    if (!cfg || check_cfg(*cfg) != 0) return -10;
+    return wimage_wanted(*cfg) ? cfg->layers * wimage_layer_floats(cfg->hidden) : 0;
+}
+
+extern "C" long bsarec_wimage_offset(int which, int transposed, int d, int n, int k) {
+    if (which < 0 || which >= WIMAGE_NW || d < 32 || d % 32 || transposed < 0 || transposed > 1) return -1;
+    const int wn = which == WIMAGE_W1 ? 4 * d : d, wk = which == WIMAGE_W2 ? 4 * d : d;
+    if (n < 0 || n >= wn || k < 0 || k >= wk) return -1;
+    return (transposed ? 12L * d * d : 0) + wimage_weight_off(which, d) + (transposed ? wimage_off(k, n, wn) : wimage_off(n, k, wk));
 }
 
 extern "C" int bsarec_shadow_refresh(bsarec_plan_t* p, void* stream) {
@@ -711,7 +771,8 @@ static int launch_fused_fwd(bsarec_plan& p, int l, bool tr, hipStream_t s, const
                             bool top_tail = false /* block l + 1 is the pruned top block: run it as this launch's tail */) {
     const bsarec_config_t& c = p.cfg;
     FusedFwdP F;
-    fill_block<true>(p, l, tr, p.bf ? p.S.layer[l] : p.P.layer[l], F);      // MFMA operands: bf16 shadow of the Linear weights (storage = 1)
+    // MFMA operands: bf16 shadow of the Linear weights (storage = 1), their fragment image (cfg.weight_image), or the masters
+    fill_block<true>(p, l, tr, p.bf ? p.S.layer[l] : p.wimg ? wimage_layer(p, l, false) : p.P.layer[l], F);
     F.xout_f32 = (l == c.layers - 1);
     F.gp = p.lb[l].gp;
     F.dsp = nullptr;          // FrequencyLayer output stays in LDS on the fused path (BSAREC_BUF_DSP is generic-path only)
@@ -722,7 +783,10 @@ static int launch_fused_fwd(bsarec_plan& p, int l, bool tr, hipStream_t s, const
     }
     F.trash = p.trash;
     TopFwdP TF;
-    if (top_tail) fill_top_fwd(p, l + 1, tr, TF);
+    if (top_tail) {
+        fill_top_fwd(p, l + 1, tr, TF);
+        if (p.wimg) { TF.wk_sh = wimage_weight(p, l + 1, WIMAGE_WK, false); TF.wv_sh = wimage_weight(p, l + 1, WIMAGE_WV, false); }
+    }
     const dim3 grid(c.batch), block(512);
     ProfScope prof(BSAREC_K_FUSED_FWD, s);
     if (c.filter_kind == 1) {        // FMLPRec block: whole-spectrum complex filter + feed-forward (no attention branch)
@@ -738,6 +802,11 @@ static int launch_fused_fwd(bsarec_plan& p, int l, bool tr, hipStream_t s, const
         return rc;
     }
     const size_t smem = fused_fwd_smem_bytes();
+    if (p.wimg) {
+        DISPATCH_DH(p.dh, rc = top_tail ? launch_lds<fused_layer_fwd_kernel<DH, false, TopFwdP, false, false, true>>(grid, block, smem, s, F, TF)
+                                        : launch_lds<fused_layer_fwd_kernel<DH, false, NoTail, false, false, true>>(grid, block, smem, s, F, NoTail()));
+        return rc;
+    }
     DISPATCH_BLOCK(p, rc = top_tail ? launch_lds<fused_layer_fwd_kernel<DH, BF, TopFwdP, X3>>(grid, block, smem, s, F, TF)
                                     : launch_lds<fused_layer_fwd_kernel<DH, BF, NoTail, X3>>(grid, block, smem, s, F, NoTail()));
     return rc;
@@ -747,7 +816,7 @@ static int launch_fused_bwd(bsarec_plan& p, int l, bool tr, const float* dY, flo
                             const TopBwdP* head = nullptr /* the pruned top block's backward runs as this launch's head */) {
     const bsarec_config_t& c = p.cfg;
     FusedBwdP F;
-    fill_block<false>(p, l, tr, p.bf ? p.S.layer[l] : p.P.layer[l], F);
+    fill_block<false>(p, l, tr, p.bf ? p.S.layer[l] : p.wimg ? wimage_layer(p, l, true) : p.P.layer[l], F);
     fill_block_partials(p, l, F);
     F.dY = dY; F.dX = dXout;
     F.u = p.lb[l].gp;
@@ -767,6 +836,11 @@ static int launch_fused_bwd(bsarec_plan& p, int l, bool tr, const float* dY, flo
         return launch_lds<fused_layer_bwd_kernel<32, false, NoTail, false, true>>(grid, block, smem, s, F, NoTail());
     }
     int rc = 0;
+    if (p.wimg) {
+        DISPATCH_DH(p.dh, rc = head ? launch_lds<fused_layer_bwd_kernel<DH, false, TopBwdP, false, false, true>>(grid, block, smem, s, F, *head)
+                                    : launch_lds<fused_layer_bwd_kernel<DH, false, NoTail, false, false, true>>(grid, block, smem, s, F, NoTail()));
+        return rc;
+    }
     DISPATCH_BLOCK(p, rc = head ? launch_lds<fused_layer_bwd_kernel<DH, BF, TopBwdP, X3>>(grid, block, smem, s, F, *head)
                                 : launch_lds<fused_layer_bwd_kernel<DH, BF, NoTail, X3>>(grid, block, smem, s, F, NoTail()));
     return rc;
@@ -1433,6 +1507,16 @@ static int embed_bwd(bsarec_plan& p, const float* dY, hipStream_t s) {
     return 0;
 }
 
+// Does this Adam update the plan's own masters (same arena layout as its gradients)?  Only then do the masters change
+// under the plan's fragment image.
+static bool adam_on_masters(const bsarec_plan& p, const bsarec_adam_t& a) {
+    return p.G.item_emb && a.params + (p.G.item_emb - a.grads) == p.P.item_emb;
+}
+// after an Adam launch that does not write the image itself (adam_kernel, lazy_adam_kernel): rebuild it, one small launch
+static int wimage_after_adam(bsarec_plan& p, const bsarec_adam_t& a, hipStream_t s) {
+    return (p.wimg && !a.wimage_plan && adam_on_masters(p, a)) ? bsarec_wimage_refresh(&p, s) : 0;
+}
+
 // ONE deterministic second-stage reduction for every split-K slab and LayerNorm / beta partial (no empty blocks: flat block
 // map); its extra last block closes the optimisation step when asked to (the lookup-path sum of the item-table gradient
 // joins its target here: after every scatter block has finished).  fuse_adam: the same launch also runs Adam over the arena.
@@ -1458,6 +1542,7 @@ static int final_reduce(bsarec_plan& p, const TickP& tick, const bsarec_adam_t* 
         A.shadow = (unsigned short*)a.shadow_bf16; A.shadow_from = a.shadow_bf16 ? a.shadow_from : a.n;
         A.item_off = p.G.item_emb - a.grads; A.item_n4 = la.n4; A.lookup_acc = la.acc;
         A.dense_zero = la.dense_zero;
+        A.wimage = (p.wimg && adam_on_masters(p, a)) ? 1 : 0;
         if (lazy) A.lazy = p.lazy;
         int ab = lazy ? la.nblocks : cdiv(A.item_n4, ROW_THREADS);
         if (ab > 1024) ab = 1024;
@@ -1563,7 +1648,10 @@ static int adam_launch(const bsarec_adam_t& a, void* state, hipStream_t s) {
     LAUNCH(adam_kernel, dim3(blocks), dim3(ROW_THREADS), 0, s, a.params, a.grads, a.exp_avg, a.exp_avg_sq, n4,
            (const uint64_t*)state, a.beta1, a.beta2, a.eps, a.weight_decay, a.grad_scale, (unsigned short*)a.shadow_bf16,
            a.shadow_bf16 ? a.shadow_from / 4 : n4, S);
-    return (int)hipGetLastError();
+    HIPCHK(hipGetLastError());
+    // adam_kernel walks the arena as float4 groups without knowing its tensors: the fragment image is rebuilt by a launch of
+    // its own right behind it (same stream, so inside the same captured graph)
+    return a.wimage_plan ? bsarec_wimage_refresh(a.wimage_plan, s) : 0;
 }
 
 extern "C" int bsarec_adam_step(const bsarec_adam_t* a, void* state, void* stream) {
@@ -1641,7 +1729,8 @@ extern "C" int bsarec_train_step_indexed(bsarec_plan_t* p, const int64_t* table,
     if (can_fuse_adam(*p, *a) && !p->cfg.separate_embed)       // 7 launches: the last one reduces and updates
         return backward_impl(p, stream, tk, a);
     RET(backward_impl(p, stream, tk));
-    return p->lazy_now ? lazy_adam_launch(*p, *a, s) : adam_launch(*a, p->state, s);
+    RET(p->lazy_now ? lazy_adam_launch(*p, *a, s) : adam_launch(*a, p->state, s));
+    return wimage_after_adam(*p, *a, s);
 }
 
 extern "C" int bsarec_grad_step_indexed(bsarec_plan_t* p, const int64_t* table, const int64_t* answers_table,
@@ -1672,13 +1761,15 @@ extern "C" int bsarec_train_step(bsarec_plan_t* p, const int64_t* ids, const int
         RET(bsarec_loss(p, answers, stream));
         TickP tk = make_tick(p->state, 1, a->lr, a->beta1, a->beta2, nullptr, 0, nullptr, nullptr, 0, 0);
         RET(backward_impl(p, stream, tk));
-        return lazy_adam_launch(*p, *a, (hipStream_t)stream);
+        RET(lazy_adam_launch(*p, *a, (hipStream_t)stream));
+        return wimage_after_adam(*p, *a, (hipStream_t)stream);
     }
     RET(bsarec_step_begin(p, stream));
     RET(bsarec_forward_last(p, ids, 1, stream));
     RET(bsarec_loss(p, answers, stream));
     RET(bsarec_backward(p, stream));
-    return bsarec_adam_step(a, p->state, stream);
+    RET(bsarec_adam_step(a, p->state, stream));
+    return wimage_after_adam(*p, *a, (hipStream_t)stream);
 }
 
 extern "C" int bsarec_mask_seen(float* scores, long ld, int B, const int64_t* users, const int64_t* indptr,

@@ -15,6 +15,7 @@
 #pragma once
 #include "common.h"
 #include "kernels.h"
+#include "wimage.h"
 #include <type_traits>
 
 #define FS 68          // LDS row stride (floats) of a 64-wide tile: 16-B aligned rows, conflict-free b128 reads
@@ -247,10 +248,18 @@ __device__ __forceinline__ f32x16 mfma_x3(const Split3& a, const Split3& b, f32x
 }
 
 // "rows x weights": B[k][n] = W[n][k], lane n reads its own weight row (contiguous in k); e = element offset of
-// W[n][k0 + KH] in the fp32 master (MM = 0, 2) resp. the bf16 shadow (MM = 1) behind `base`
-template <int MM, int K>
+// W[n][k0 + KH] in the fp32 master (MM = 0, 2) resp. the bf16 shadow (MM = 1) behind `base`.
+// IMG (MM = 0 only): `base` is the weight's F image (wimage.h), KT the row length of W; e names the same element of the
+// master as without it.  One 16-byte load per k-block either way, the same values in the same registers -- from the image
+// the 64 lanes of an instruction read 1 KB contiguous instead of 32 B out of each of 32 rows.
+template <int MM, int K, int KT = 64, bool IMG = false>
 __device__ __forceinline__ void load_w(const float* __restrict__ base, long e, WFrag<MM, K>& f) {
-    if constexpr (MM == 1) {
+    static_assert(!IMG || MM == 0, "the fragment image exists for the fp32 products only");
+    if constexpr (IMG) {
+        const float* gw = base + wimage_off((int)(e / KT), (int)(e % KT), KT);
+#pragma unroll
+        for (int kb = 0; kb < K / 8; ++kb) f.w[kb] = gld4(gw + 256 * kb);
+    } else if constexpr (MM == 1) {
 #pragma unroll
         for (int s = 0; s < K / 16; ++s) f.w[s] = *reinterpret_cast<const AS_GLOBAL u32x4*>((const AS_GLOBAL char*)base + 2 * (e + 16 * s));
     } else if constexpr (MM == 2) {
@@ -262,10 +271,17 @@ __device__ __forceinline__ void load_w(const float* __restrict__ base, long e, W
     }
 }
 // "x . W": B[k][j] = W[k][j], lane j reads a weight column (stride LDW elements): coalesced dword (fp32) or
-// halfword (bf16) loads; e = element offset of W[k0 + KH][j]
-template <int MM, int K, int LDW>
+// halfword (bf16) loads; e = element offset of W[k0 + KH][j].
+// IMG (MM = 0 only): `base` is the weight's T image, NR the number of rows of W: one 16-byte load per k-block in place of
+// four dword loads a row apart.
+template <int MM, int K, int LDW, int NR = 64, bool IMG = false>
 __device__ __forceinline__ void load_wT(const float* __restrict__ base, long e, WFrag<MM, K>& f) {
-    if constexpr (MM == 1) {
+    static_assert(!IMG || MM == 0, "the fragment image exists for the fp32 products only");
+    if constexpr (IMG) {
+        const float* gw = base + wimage_off((int)(e % LDW), (int)(e / LDW), NR);
+#pragma unroll
+        for (int kb = 0; kb < K / 8; ++kb) f.w[kb] = gld4(gw + 256 * kb);
+    } else if constexpr (MM == 1) {
         const AS_GLOBAL unsigned short* g = reinterpret_cast<const AS_GLOBAL unsigned short*>((const AS_GLOBAL char*)base + 2 * e);
 #pragma unroll
         for (int s = 0; s < K / 16; ++s) {
@@ -391,7 +407,7 @@ template <int DH, bool BF, unsigned KOFF, bool HELPED>
 __device__ __forceinline__ void top_fwd_rest(const TopFwdRegs<BF>& R, const DropSeed& dseed, float* sX, float* sK, float* sV,
                                              float* sPart, float* sTab, float* sSpec, float* sVec, const int* sIds);
 template <bool BF> struct TopFwdHelpRegs;
-template <bool BF, unsigned KOFF> __device__ __forceinline__ void top_fwd_help_prefetch(TopFwdHelpRegs<BF>& H);
+template <bool BF, unsigned KOFF, bool IMG> __device__ __forceinline__ void top_fwd_help_prefetch(TopFwdHelpRegs<BF>& H);
 template <int DH, bool BF, unsigned KOFF>
 __device__ __forceinline__ void top_fwd_help(const TopFwdHelpRegs<BF>& H, const float* sX, float* sK, float* sV, float* sVec);
 template <class T> struct IsTail { static constexpr bool value = true; };
@@ -427,11 +443,13 @@ template <int DH, bool BF, unsigned KOFF> __device__ __forceinline__ void top_bw
 // TAILP = TopFwdP: the block above is the one-row top block of the loss path and runs as this kernel's tail -- the
 // output tile, the ids and the twiddle table stay in LDS, waves 4..7 exit, waves 0..3 carry on (one launch and the
 // top block's whole load phase saved).
-template <int DH, bool BF, class TAILP, bool X3 = false, bool FM = false>
+// IMG: wq .. w2 (and the tail's wk_sh / wv_sh) point at the weights' F images (wimage.h), not at the masters.
+template <int DH, bool BF, class TAILP, bool X3 = false, bool FM = false, bool IMG = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
 #define PTYPE FusedFwdP
     static_assert(!(BF && X3), "x3 products work on fp32 tensors");
+    static_assert(!IMG || (!BF && !X3 && !FM), "the fragment image feeds the fp32 products of the BSARec block");
     constexpr int MM = X3 ? 2 : (BF ? 1 : 0);       // product mode of the MFMA helpers (WFrag)
     // FM: the sibling model FMLPRec's block (src/model/fmlprec.py:78-113) -- FilterLayer with the learnable complex filter
     // y = irfft(rfft(x) * W) over ALL L/2 + 1 bins, LayerNorm(Drop(y) + x), then the same feed-forward; no attention branch
@@ -489,7 +507,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
     WFrag<MM, 64> wA, wB;
     float qkv_bias[3] = {0.f, 0.f, 0.f};
     if (!FM && grp == 1) {
-        load_w<MM, 64>(R1_wq, wrow, wA);
+        load_w<MM, 64, 64, IMG>(R1_wq, wrow, wA);
         qkv_bias[0] = gld(KARG(FusedFwdP, bq) + col); qkv_bias[1] = gld(KARG(FusedFwdP, bk) + col);
         qkv_bias[2] = gld(KARG(FusedFwdP, bv) + col);
     }
@@ -585,8 +603,8 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            if (which == 0) { load_w<MM, 64>(R2_wk, wrow, wB); mma_w<MM, 64>(sX + arow, wA, acc); }
-            else if (which == 1) { load_w<MM, 64>(R2_wv, wrow, wA); mma_w<MM, 64>(sX + arow, wB, acc); }
+            if (which == 0) { load_w<MM, 64, 64, IMG>(R2_wk, wrow, wB); mma_w<MM, 64>(sX + arow, wA, acc); }
+            else if (which == 1) { load_w<MM, 64, 64, IMG>(R2_wv, wrow, wA); mma_w<MM, 64>(sX + arow, wB, acc); }
             else mma_w<MM, 64>(sX + arow, wA, acc);
             const float bias = qkv_bias[which];
 #pragma unroll
@@ -690,7 +708,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
     }
     // dense weights for phase 4 (this group's K half), held across the attention
     WFrag<MM, 32> wO;
-    if constexpr (!FM) load_w<MM, 32>(R2_wo, wrow + 32 * grp, wO);
+    if constexpr (!FM) load_w<MM, 32, 64, IMG>(R2_wo, wrow + 32 * grp, wO);
     lds_barrier();
     if constexpr (!FM) {
     // q, k, v -> global as whole rows, 16 B per lane (per-lane dword stores are store-issue bound)
@@ -853,7 +871,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
     LnPre lnA;
     if constexpr (!FM) lnA = ln_pre(R4_bo, R4_a_g, R4_a_b, R4_drop_o, dseed, tok0);
     {
-        load_w<MM, 64>(R4_w1, (long)(128 * grp + col) * 64 + KH, wA);      // first dense_1 block of this group
+        load_w<MM, 64, 64, IMG>(R4_w1, (long)(128 * grp + col) * 64 + KH, wA);      // first dense_1 block of this group
         ffn_bias[0] = gld(KARG(FusedFwdP, b1) + 128 * grp + col); ffn_bias[1] = gld(KARG(FusedFwdP, b1) + 128 * grp + 64 + col);
         if constexpr (!FM) {
         f32x16 acc;
@@ -884,8 +902,8 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
             const int c256 = (2 * grp + i) * 64 + col;
             WFrag<MM, 64>& wcur = i ? wB : wA;
             WFrag<MM, 64>& wnxt = i ? wA : wB;
-            if (i == 0) load_w<MM, 64>(R5_w1, (long)(c256 + 64) * 64 + KH, wnxt);
-            else load_w<MM, 64>(R5_w2, (long)col * 256 + 128 * grp + KH, wnxt);     // first dense_2 chunk of this group
+            if (i == 0) load_w<MM, 64, 64, IMG>(R5_w1, (long)(c256 + 64) * 64 + KH, wnxt);
+            else load_w<MM, 64, 256, IMG>(R5_w2, (long)col * 256 + 128 * grp + KH, wnxt);     // first dense_2 chunk of this group
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -928,7 +946,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         const float* sa = sU + (wm * 32 + l31) * FU + 128 * grp + KH;
-        load_w<MM, 64>(R6_w2, (long)col * 256 + 128 * grp + 64 + KH, wB);
+        load_w<MM, 64, 256, IMG>(R6_w2, (long)col * 256 + 128 * grp + 64 + KH, wB);
         mma_w<MM, 64>(sa, wA, acc);                          // chunk 0 of this group sits in wA
         mma_w<MM, 64>(sa + 64, wB, acc);
         float* part = grp == 0 ? sX : sE;                    // sX / sE are dead: partial tiles
@@ -939,7 +957,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
     STAMP(7);
     TopFwdRegs<BF> TR;
     TopFwdHelpRegs<BF> TH;
-    if constexpr (TAIL) { if (wave < 4) top_fwd_prefetch<BF, KOFF, false>(TR); else top_fwd_help_prefetch<BF, KOFF>(TH); }
+    if constexpr (TAIL) { if (wave < 4) top_fwd_prefetch<BF, KOFF, false>(TR); else top_fwd_help_prefetch<BF, KOFF, IMG>(TH); }
     const auto R7_Xout = KARG(FusedFwdP, Xout);
     const auto R7_eps = KARG(FusedFwdP, eps);
     const auto R7_rstd_ff = KARG(FusedFwdP, rstd_ff);
@@ -1044,11 +1062,13 @@ __device__ __forceinline__ void seq_partials_64(const f32x4 (&v)[N], float* cons
 // sources of the FrequencyLayer backward run one per group.
 // HEADP = TopBwdP: the block above is the one-row top block of the loss path; its backward runs first, inside this
 // kernel, on waves 0..3 (its dX tile stays in LDS), while waves 4..7 stage this block's gelu' tile.
-template <int DH, bool BF, class HEADP, bool X3 = false, bool FM = false>
+// IMG: wq .. w2 point at the weights' T images (wimage.h); the head (TopBwdP) keeps reading the masters.
+template <int DH, bool BF, class HEADP, bool X3 = false, bool FM = false, bool IMG = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
 #define PTYPE FusedBwdP
     static_assert(!(BF && X3), "x3 products work on fp32 tensors");
+    static_assert(!IMG || (!BF && !X3 && !FM), "the fragment image feeds the fp32 products of the BSARec block");
     constexpr int MM = X3 ? 2 : (BF ? 1 : 0);
     // FM: backward of the sibling model FMLPRec's block (see the forward): stages A1..A3 (feed-forward), then its own tail
     static_assert(!FM || (!BF && !X3 && !IsTail<HEADP>::value), "the FMLPRec block runs in fp32, without a top-block head");
@@ -1140,7 +1160,7 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
     WFrag<MM, 64> wA, wB;
     WFrag<MM, 32> wk4;                              // stage D's key-weight fragments (requested at the end of stage C)
     f32x4 e_bt, e_x[2];                             // stage E's sqrt_beta / x tile rows (requested there too)
-    load_wT<MM, 64, 256>(R1_w2, (long)KH * 256 + 128 * grp + col, wA);             // first dU block of this group
+    load_wT<MM, 64, 256, 64, IMG>(R1_w2, (long)KH * 256 + 128 * grp + col, wA);             // first dU block of this group
     // stage A1's operands are requested BEFORE the u tile: loads return in issue order, so the LayerNorm row pass waits
     // only for them while the 64 KB of u are still in flight
     const f32x4 g = gld4(R1_ff_g + lc);
@@ -1229,12 +1249,12 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
         // bursts and their epilogues together (lockstep) and the matrix pipe idles during every epilogue.
         const float* sa = sT + arow;
         const int c0 = (2 * grp) * 64 + col, c1 = c0 + 64;
-        load_wT<MM, 64, 256>(R2_w2, (long)KH * 256 + c1, wB);                          // block 1's weights
+        load_wT<MM, 64, 256, 64, IMG>(R2_w2, (long)KH * 256 + c1, wB);                          // block 1's weights
         f32x16 acc0, acc1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
         mma_w<MM, 64>(sa, wA, acc0);
-        load_wT<MM, 64, 64>(R2_w1, (long)(128 * grp + KH) * 64 + col, wA);             // first dH chunk of this group
+        load_wT<MM, 64, 64, 256, IMG>(R2_w1, (long)(128 * grp + KH) * 64 + col, wA);             // first dH chunk of this group
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const f32x4 a = ld4(sa + 8 * (r >> 1));
@@ -1258,8 +1278,8 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
             const int blk = 2 * grp + i, c256 = blk * 64 + col;
             WFrag<MM, 64>& wcur = i ? wB : wA;
             WFrag<MM, 64>& wnxt = i ? wA : wB;
-            if (i == 0) load_wT<MM, 64, 256>(R2_w2, (long)KH * 256 + c256 + 64, wnxt);
-            else load_wT<MM, 64, 64>(R2_w1, (long)(128 * grp + KH) * 64 + col, wnxt);      // first dH chunk of this group
+            if (i == 0) load_wT<MM, 64, 256, 64, IMG>(R2_w2, (long)KH * 256 + c256 + 64, wnxt);
+            else load_wT<MM, 64, 64, 256, IMG>(R2_w1, (long)(128 * grp + KH) * 64 + col, wnxt);      // first dH chunk of this group
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -1291,8 +1311,8 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         const float* sa = sdU + (wm * 32 + l31) * FU + 128 * grp + KH;
-        load_wT<MM, 64, 64>(R3_w1, (long)(128 * grp + 64 + KH) * 64 + col, wB);
-        if constexpr (!FM) load_wT<MM, 32, 64>(R3_wo, (long)(32 * grp + KH) * 64 + col, wO);          // dense^T half for stage B2
+        load_wT<MM, 64, 64, 256, IMG>(R3_w1, (long)(128 * grp + 64 + KH) * 64 + col, wB);
+        if constexpr (!FM) load_wT<MM, 32, 64, 64, IMG>(R3_wo, (long)(32 * grp + KH) * 64 + col, wO);          // dense^T half for stage B2
         // stage B1's operands (q, k, v, xhat of both LayerNorms: 80 KB per sequence) are requested here, AFTER the weight
         // fragments this stage waits for (loads return in issue order), and land while the MFMAs below run
 #pragma unroll
@@ -1691,8 +1711,8 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
         // their point of use with the whole round trip exposed
         {
             const long wofs = (long)KH * 64 + col;
-            if (grp == 0) { load_wT<MM, 64, 64>(KARG(FusedBwdP, wq), wofs, wA); load_wT<MM, 32, 64>(KARG(FusedBwdP, wk), wofs, wk4); }
-            else { load_wT<MM, 32, 64>(KARG(FusedBwdP, wk), wofs + 32 * 64, wk4); load_wT<MM, 64, 64>(KARG(FusedBwdP, wv), wofs, wA); }
+            if (grp == 0) { load_wT<MM, 64, 64, 64, IMG>(KARG(FusedBwdP, wq), wofs, wA); load_wT<MM, 32, 64, 64, IMG>(KARG(FusedBwdP, wk), wofs, wk4); }
+            else { load_wT<MM, 32, 64, 64, IMG>(KARG(FusedBwdP, wk), wofs + 32 * 64, wk4); load_wT<MM, 64, 64, 64, IMG>(KARG(FusedBwdP, wv), wofs, wA); }
             const float* const pX = KARG(FusedBwdP, X);
             e_bt = gld4(KARG(FusedBwdP, sqrt_beta) + lc);
 #pragma unroll

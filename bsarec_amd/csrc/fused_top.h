@@ -23,8 +23,9 @@ struct TopFwdP {
     float alpha, oma, eps;
     DropP drop_f, drop_p, drop_o, drop_ff;
     long long* stamps;             // diagnostic: per-step shader clock of workgroup 0 (null in production)
-    // bf16 storage (BF instantiation): wk_sh / wv_sh = bf16 shadow of the key / value weights for the MFMA projections of
-    // all rows (as the full block kernel reads them); the one-row vector products keep the fp32 masters
+    // wk_sh / wv_sh = the derived copy of the key / value weights that the MFMA projections of all rows read (as the full
+    // block kernel reads its weights): the bf16 shadow (BF instantiation), or the F images of wimage.h (fused tail with
+    // IMG); the one-row vector products keep the fp32 masters
     const float *wk_sh, *wv_sh;
 };
 
@@ -376,14 +377,14 @@ struct TopFwdHelpRegs {
     WFrag<BF, 64> wA, wB;                  // K / V weight fragments of this wave's 32 x 32 tile
     float bias_k, bias_v;
 };
-template <bool BF, unsigned KOFF>
+template <bool BF, unsigned KOFF, bool IMG>
 __device__ __forceinline__ void top_fwd_help_prefetch(TopFwdHelpRegs<BF>& H) {
     const int lane = threadIdx.x & 63, hw = ((int)threadIdx.x >> 6) - 4;
     const int l31 = lane & 31, half = lane >> 5;
     const int wn = hw & 1, col = wn * 32 + l31;
     const int KH = (BF ? 8 : 4) * half;
-    load_w<BF, 64>(BF ? TP(wv_sh) : TP(wv), (long)col * 64 + KH, H.wB);
-    load_w<BF, 64>(BF ? TP(wk_sh) : TP(wk), (long)col * 64 + KH, H.wA);
+    load_w<BF, 64, 64, IMG>(BF || IMG ? TP(wv_sh) : TP(wv), (long)col * 64 + KH, H.wB);
+    load_w<BF, 64, 64, IMG>(BF || IMG ? TP(wk_sh) : TP(wk), (long)col * 64 + KH, H.wA);
     H.bias_v = gld(TP(bv) + col); H.bias_k = gld(TP(bk) + col);
 }
 template <int DH, bool BF, unsigned KOFF>

@@ -8,6 +8,7 @@
 
 #define ROW_THREADS 256
 #include "lazy_adam.h"
+#include "wimage.h"
 
 // =============================================================================================
 // K1 embedding front-end: X0 = Drop(LN(E[ids] + Pos[t]))      src/model/_abstract_model.py:14-24
@@ -645,7 +646,12 @@ embed_bwd_kernel(const float* __restrict__ de, const int* __restrict__ ids32, in
 // =============================================================================================
 // deterministic second-stage reductions: dst[i] = scale * sum_s src[s*stride + i]
 // =============================================================================================
-struct ReduceJob { const float* src; float* dst; int nsplit; int len; long stride; float scale; int pad; };
+// img_f != null (a Linear weight [wn][wk] of a plan that keeps the fragment image, wimage.h): where the fused Adam stores
+// the updated parameter a second and third time -- the weight's F and T image
+struct ReduceJob {
+    const float* src; float* dst; int nsplit; int len; long stride; float scale; int pad;
+    float* img_f = nullptr; float* img_t = nullptr; int wn = 0, wk = 0;
+};
 
 __device__ __forceinline__ void reduce_chunk(const ReduceJob& j, int chunk, float (*red)[64]) {
     const int e = threadIdx.x & 63, sg = threadIdx.x >> 6;       // element within the block, split group
@@ -835,6 +841,7 @@ struct AdamFuseP {
     unsigned long long* lookup_acc;    // the lookup-path sum of the item-table gradient (fixed point), added here once
     int dense_zero;                    // LookupAcc.dense_zero: the gradient is the accumulator alone (not read, always stored)
     LazyRows lazy;                     // lazy.rows != null: lazy Adam (lazy_adam.h) -- the item arm walks the rows of T only
+    int wimage;                        // the jobs' fragment images (ReduceJob.img_f) mirror `w`: keep them current
 };
 __global__ void __launch_bounds__(ROW_THREADS)
 reduce_adam_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ blockmap, int nblocks,
@@ -875,6 +882,7 @@ reduce_adam_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ b
             wi -= step_size * (mi / (sqrtf(vi) / bc2s + A.eps));
             A.w[o] = wi; A.m[o] = mi; A.v[o] = vi;
             if (A.shadow && o >= A.shadow_from) A.shadow[o] = (unsigned short)(adam_pk_bf16(wi, 0.f) & 0xFFFFu);
+            if (A.wimage && j.img_f) wimage_store(j.img_f, j.img_t, i / j.wk, i % j.wk, j.wn, j.wk, wi);
         }
         return;
     }
@@ -909,6 +917,21 @@ reduce_adam_kernel(const ReduceJob* __restrict__ jobs, const int* __restrict__ b
         if (A.shadow && o >= A.shadow_from)
             *reinterpret_cast<uint2*>(A.shadow + o) = make_uint2(adam_pk_bf16(wi.x, wi.y), adam_pk_bf16(wi.z, wi.w));
     }
+}
+
+// Fragment image (wimage.h) <- fp32 masters of the six Linear weights of every layer: blockIdx.y = layer, one master
+// element per thread, stored to its place in the F and in the T image.
+struct WImageP { const float* w[BSAREC_MAX_LAYERS][WIMAGE_NW]; float* img; int d; };
+__global__ void __launch_bounds__(ROW_THREADS)
+wimage_refresh_kernel(const WImageP P) {
+    const long d = P.d, dd = d * d;
+    const long i = (long)blockIdx.x * ROW_THREADS + threadIdx.x;           // element of the layer's six weights, in image order
+    if (i >= 12 * dd) return;
+    const int which = i < 4 * dd ? (int)(i / dd) : (i < 8 * dd ? WIMAGE_W1 : WIMAGE_W2);
+    const int e = (int)(i - wimage_weight_off(which, d));
+    const int wn = which == WIMAGE_W1 ? 4 * P.d : P.d, wk = which == WIMAGE_W2 ? 4 * P.d : P.d;
+    float* f = P.img + blockIdx.y * wimage_layer_floats(d) + wimage_weight_off(which, d);
+    wimage_store(f, f + 12 * dd, e / wk, e % wk, wn, wk, P.w[blockIdx.y][which][e]);
 }
 
 // fp32 -> bf16 (round to nearest even) for up to six tensors, jobs in the kernarg block: blockIdx.y = tensor

@@ -99,6 +99,11 @@ class _Plan:
         self.garena = model._garena if garena is None else garena
         pt, gt = model._tensor_struct(model._arena), model._tensor_struct(self.garena)
         st = model._tensor_struct(model._shadow_arena()) if self.bf16 else None
+        # fp32 at the fused shape (cfg.weight_image): the model's fragment image of the Linear weights (csrc/wimage.h)
+        self.wimage = lib.bsarec_wimage_floats(C.byref(self.cfg)) > 0
+        if self.wimage:
+            st = L.Tensors()
+            st.layer[0].query_w = model._wimage_arena(lib.bsarec_wimage_floats(C.byref(self.cfg))).data_ptr()
         stream = torch.cuda.current_stream(dev).cuda_stream
         # own_state: a snapshot of the model's step state (dropout seed / step) that stays put while OTHER forwards run --
         # a forward retained for autograd must regenerate ITS masks in its backward
@@ -332,6 +337,8 @@ class BSARecModel(nn.Module):
         self._adam = None
         self._shadow = None               # bf16 mirror of the arena (plans with storage = 1), allocated on first use
         self._shadow_stale = True
+        self._wimage = None               # fragment image of the Linear weights (fp32 plans at the fused shape), on first use
+        self._wimage_stale = True
         self._garena_alt = None           # second gradient arena (peer-to-peer exchange: arenas alternate by step parity)
         self._lookup = None               # [V*d] lookup-path rows of the item-table gradient (bucketed exchange)
         self._dense_hook = None
@@ -396,16 +403,34 @@ class BSARecModel(nn.Module):
             self._shadow_stale = True
         return self._shadow
 
+    def _wimage_arena(self, floats: int):
+        if self._wimage is None:
+            buf = torch.zeros(floats + 64, dtype=torch.float32, device=self._arena.device)
+            off = ((-buf.data_ptr()) % 256) // 4
+            self._wimage = buf[off:off + floats]
+            self._wimage_stale = True
+        assert self._wimage.numel() == floats
+        return self._wimage
+
     def _refresh_shadow(self, plan, force=False):
-        """bf16 storage: the MFMA products read a bf16 shadow of the Linear weights.  The fused Adam keeps it current;
-        after anything else that changes the fp32 masters (load_state_dict, init, an external optimiser) it is rebuilt."""
+        """The derived copies of the Linear weights that the MFMA products read: the bf16 shadow (bf16 storage), or the
+        fragment image (fp32 at the fused shape, csrc/wimage.h).  The training steps keep them current; after anything else
+        that changes the fp32 masters (load_state_dict, init, an external optimiser) they are rebuilt."""
         if plan.bf16 and (force or self._shadow_stale):
             L.check(plan.lib.bsarec_shadow_refresh(plan.handle, self._stream()), "bsarec_shadow_refresh")
             self._shadow_stale = False
+        if plan.wimage and (force or self._wimage_stale):
+            L.check(plan.lib.bsarec_wimage_refresh(plan.handle, self._stream()), "bsarec_wimage_refresh")
+            self._wimage_stale = False
+
+    def weights_changed(self):
+        """Call after writing the parameter arena by any means other than this module's training steps."""
+        self._shadow_stale = True
+        self._wimage_stale = True
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         out = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._shadow_stale = True
+        self.weights_changed()
         return out
 
     def _apply(self, fn, recurse=True):
@@ -504,6 +529,7 @@ class BSARecModel(nn.Module):
         # always rebuild the bf16 shadow here (storage = 1 only; one small launch per layer)
         self._refresh_shadow(plan, force=True)
         self._shadow_stale = True
+        self._wimage_stale = True
         # last_only: the caller consumes position L-1 of the last layer only (loss / logits / backward)
         fwd = lib.bsarec_forward_last if last_only else lib.bsarec_forward
         L.check(fwd(plan.handle, ids.data_ptr(), 1 if train else 0, st), "bsarec_forward")
@@ -655,8 +681,16 @@ class BSARecModel(nn.Module):
             raise ValueError("adam_step: a lazy-Adam model updates inside train_step / train_step_indexed (a plan-less "
                              "update cannot know which item rows the step touched)")
         ad = self._adam_struct(grad_scale, grad_srcs)
+        # adam_kernel writes the bf16 shadow itself; the fragment image is rebuilt by a launch of its own right behind it
+        # (bsarec_adam_t.wimage_plan: inside the same captured graph)
+        plan = next((p for p in self._plans.values() if p.wimage), None)
+        if plan is not None:
+            ad.wimage_plan = plan.handle
+        elif self._wimage is not None:
+            self._wimage_stale = True
         fn = L.load().bsarec_adam_step if tick else L.load().bsarec_adam_apply
         L.check(fn(C.byref(ad), self._state.data_ptr(), self._stream()), "bsarec_adam_step" if tick else "bsarec_adam_apply")
+
 
     def grad_views(self) -> "OrderedDict[str, torch.Tensor]":
         """The gradient arena per tensor.  After a lazy-Adam step (train_lazy_adam) the item table's rows the step touched

@@ -204,6 +204,7 @@ class Trainer:
         for t in (m._arena, m._adam["m"], m._adam["v"], m._state):
             torch.distributed.broadcast(t, src=torch.distributed.get_global_rank(self.pg, 0), group=self.pg)
         m._state[0] = seed
+        m.weights_changed()
 
     # ---- reference API ---------------------------------------------------------------------------
     def train(self, epoch):

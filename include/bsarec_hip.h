@@ -81,6 +81,14 @@ typedef struct {
     int train_no_logq;    /* sampled head: 1 = no logQ correction */
     int train_lazy_adam;  /* sampled head: 1 = lazy (sparse) Adam for the item table in bsarec_train_step and
                            * bsarec_train_step_indexed (below); 0 (default): dense Adam.  Needs train_negatives > 0 */
+    int weight_image;     /* 1: the fp32 fused block kernels read the Linear weights from a second copy in the order of their MFMA
+                           * operand fragments, the fragment image (one coalesced 16-byte-per-lane load per fragment; same
+                           * values, same registers, same results bit for bit).  Takes effect at the fused shape with storage = 0,
+                           * x3_products = 0, chain_kernels = 0, filter_kind = 0 (bsarec_wimage_floats > 0) and is ignored
+                           * elsewhere.  The image is the caller's memory (bsarec_plan_create, `shadow`); bsarec_train_step and
+                           * bsarec_train_step_indexed keep it current themselves, bsarec_adam_step / _apply through
+                           * bsarec_adam_t.wimage_plan; after any other change of the masters the caller runs
+                           * bsarec_wimage_refresh before the next forward.  0: the kernels read the masters */
 } bsarec_config_t;
 
 /* The 19 tensors of one BSARecBlock, in state_dict order (+ the sibling model's filter weight)
@@ -143,12 +151,24 @@ size_t bsarec_workspace_bytes(const bsarec_config_t *cfg);
  * float* fields) -- the bf16 shadow of the fp32 masters that the MFMA products read; only the six Linear weights of
  * every layer are used.  The caller keeps it current: bsarec_shadow_refresh after it changes the masters itself, or
  * bsarec_adam_t.shadow_bf16 so that the fused Adam writes both.
+ * cfg.weight_image = 1 where it takes effect (bsarec_wimage_floats(cfg) > 0): `shadow->layer[0].query_w` is instead the
+ * fragment image, bsarec_wimage_floats(cfg) floats, 256-byte aligned, shared by every plan of the same parameters; no
+ * other field of `shadow` is read.  Its content is the caller's to initialise (bsarec_wimage_refresh).
  * Replaces: model construction wiring of src/model/bsarec.py:8-14. */
 int bsarec_plan_create(bsarec_plan_t **out, const bsarec_config_t *cfg, const bsarec_tensors_t *params,
                        const bsarec_tensors_t *grads, const bsarec_tensors_t *shadow, void *workspace,
                        size_t workspace_bytes, void *state, const float *twiddle, void *stream);
 /* cfg.storage = 1: bf16 shadow <- fp32 masters for the Linear weights of every layer (one launch per layer). */
 int bsarec_shadow_refresh(bsarec_plan_t *plan, void *stream);
+/* cfg.weight_image = 1: fragment image <- fp32 masters for the Linear weights of every layer (one launch; nothing where the
+ * plan keeps no image). */
+int bsarec_wimage_refresh(bsarec_plan_t *plan, void *stream);
+/* Floats of the fragment image a plan for `cfg` reads (layer after layer); 0: such a plan reads the masters; < 0: bad cfg. */
+long bsarec_wimage_floats(const bsarec_config_t *cfg);
+/* The image's index map: where element [n][k] of Linear weight `which` (0..5 = query, key, value, dense, dense_1, dense_2;
+ * [out][in] row-major) of hidden size d lives inside a layer's image, transposed = 0 for the forward (F) and 1 for the
+ * backward (T) orientation; -1 on a bad argument.  Host arithmetic only. */
+long bsarec_wimage_offset(int which, int transposed, int d, int n, int k);
 /* Element type of a named workspace buffer under this plan: 0 = fp32, 1 = bf16 (cfg.storage = 1: every saved
  * activation of the block stack except the last layer's output; logits, loss and the statistics stay fp32). */
 int bsarec_buffer_is_bf16(const bsarec_plan_t *plan, int buffer, int layer);
@@ -283,6 +303,8 @@ typedef struct {
     int n_grad_srcs;          /* > 0: g = sum of grad_srcs[0 .. n) in index order (`grads` ignored) -- the one-shot       */
     const float *grad_srcs[8];/*   peer-to-peer exchange of bsarec_comm.h: every rank's arena in RANK order, so that every */
                               /*   replica forms the identical sum                                                        */
+    bsarec_plan_t *wimage_plan; /* bsarec_adam_step / _apply only: null, or a plan of `params` that reads the fragment image  */
+                              /*   (cfg.weight_image): bsarec_wimage_refresh(wimage_plan) is launched right behind the update */
 } bsarec_adam_t;
 
 /* Advance Adam's t / bias corrections in `state`, then update. */
