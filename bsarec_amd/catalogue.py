@@ -34,6 +34,11 @@ one GPU) -- the head rows above become, per rank:
   encoder backward, barrier   as above
   owner pull       every owner adds the answer rows of its items and the rank-ordered sum of the candidate partials
   Adam             shard: dense (dE zeroed once per step), or lazy over the owned rows the step touched
+
+Evaluation (``topk`` / ``full_sort_scores``) ranks the owned rows for all Bg sequences and merges the ranks' lists.
+``eval_full_rank`` (the single-GPU flag) picks how a rank gets its list: "dense" (default) materialises the partial logits
+[Bg, Vs]; "fused" calls ``bsarec_topk_full_range`` over the shard with its column base -- O(Bg (s + cap)) working memory, no
+score matrix, and under the sampled-softmax head no O(Bg Vs) buffer for the life of the object.
 """
 from __future__ import annotations
 
@@ -46,6 +51,17 @@ import torch
 from . import _lib as L
 from .dp import PeerExchange, _as_tensor
 from .model import BSARecModel, train_head_of
+
+
+EVAL_FULL_RANK = ("dense", "fused")
+
+
+def eval_full_rank_of(args, full_rank=None) -> str:
+    """The evaluation path of ``topk``: ``full_rank`` when given, else ``args.eval_full_rank``, else "dense"."""
+    mode = getattr(args, "eval_full_rank", "dense") if full_rank is None else full_rank
+    if mode not in EVAL_FULL_RANK:
+        raise ValueError(f"eval_full_rank = {mode!r}, expected one of {EVAL_FULL_RANK}")
+    return mode
 
 
 class ShardedCatalogue:
@@ -63,6 +79,7 @@ class ShardedCatalogue:
             raise ValueError("train_lazy_adam needs the sampled-softmax head (train_negatives > 0)")
         if getattr(args, "storage", None) == "bf16":
             raise ValueError("catalogue sharding is fp32 only")
+        eval_full_rank_of(args)
         if torch.device(device).type != "cuda":        # before the process group, the IPC mappings and any allocation
             head_name = (f"sampled-softmax head, train_negatives = {self.N}" if self.N else "full-catalogue CE head")
             raise ValueError(f"ShardedCatalogue: the catalogue-sharded step ({head_name}) runs on the GPU only, "
@@ -127,10 +144,17 @@ class ShardedCatalogue:
         self._grads8 = L.PTRS8(*([int(p) for p in px.grad_srcs(0)] + [None] * (8 - self.W)))
         dist.barrier(group=group)
 
+    def _gathered_h_buffer(self):
+        """The gathered h_last of all Bg sequences (the full-CE step; evaluation)."""
+        if self.h_all is None:
+            self.h_all = torch.zeros(self.Bg, self.d, dtype=torch.float32, device=self.device)
+
     def _full_head_buffers(self):
-        """Partial logits of all Bg sequences against the owned rows and the gathered h_last (the full-CE step; evaluation)."""
-        self.logits = torch.zeros(self.Bg, self.ld, dtype=torch.float32, device=self.device)
-        self.h_all = torch.zeros(self.Bg, self.d, dtype=torch.float32, device=self.device)
+        """Partial logits of all Bg sequences against the owned rows, and the gathered h_last (the full-CE step; the dense
+        evaluation)."""
+        self._gathered_h_buffer()
+        if self.logits is None:
+            self.logits = torch.zeros(self.Bg, self.ld, dtype=torch.float32, device=self.device)
 
     def _sampled_head_buffers(self, px):
         B, N, d, dev = self.B, self.N, self.d, self.device
@@ -346,19 +370,24 @@ class ShardedCatalogue:
 
     # ---- evaluation ------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def topk(self, input_ids, k: int = 20, seen=None):
+    def topk(self, input_ids, k: int = 20, seen=None, full_rank=None):
         """Full-catalogue top-k of this rank's B sequences over the SHARDED table (the reference's eval step,
         src/trainers.py:118-141: scores of the last position against every item, items the user already interacted
         with set to 0 -- not -inf --, top 20): local scores of all Bg sequences against the owned rows, local top-k,
         all-gather of the W x k candidates, merge.  ``seen``: optional int64 [B, S] of item ids per sequence (padded with
-        -1).  Returns (scores [B, k], item ids [B, k])."""
+        -1).  ``full_rank``: "dense" (the partial logits [Bg, Vs], then ``bsarec_topk_seen``) or "fused"
+        (``bsarec_topk_full_range`` over the owned rows: no score matrix); None: ``args.eval_full_rank``, else "dense".
+        Returns (scores [B, k], item ids [B, k])."""
         import torch.distributed as dist
         lib, enc, g = self.lib, self.encoder, self.group
         B, Lq, d, W, Bg, n = self.B, self.Lq, self.d, self.W, self.Bg, self.n
+        fused = eval_full_rank_of(self.args, full_rank) == "fused"
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
         assert tuple(ids.shape) == (B, Lq)
         st = enc._stream()
-        if self.logits is None:             # sampled-softmax training: the full-catalogue buffers on the first evaluation
+        if fused:                           # the gathered h_last only
+            self._gathered_h_buffer()
+        else:                               # sampled-softmax training: the full-catalogue buffers on the first dense evaluation
             self._full_head_buffers()
         self.px.barrier(st)
         L.check(lib.bsarec_shard_gather_rows(ids.data_ptr(), n, C.byref(self._shards8), W, self.rows_per, self.V, d,
@@ -369,18 +398,21 @@ class ShardedCatalogue:
         enc.train(was_training)
         h_last = plan.view(L.BUF_LAYER_OUT, self.args.num_hidden_layers, (B, Lq, d))[:, Lq - 1, :].float().contiguous()
         dist.all_gather(list(self.h_all.view(W, B, d).unbind(0)), h_last, group=g)
-        L.check(lib.bsarec_shard_logits(self.h_all.data_ptr(), d, Bg, self.E.data_ptr(), self.Vs, d, self.logits.data_ptr(),
-                                        self.ld, st), "bsarec_shard_logits")
-        scores = self.logits[:, :self.Vs]
+        seen_all = None
         if seen is not None:
             sl = seen.to(device=self.device, dtype=torch.int64).contiguous()
             S = sl.shape[1]
             seen_all = torch.empty(W, B, S, dtype=torch.int64, device=self.device)
             dist.all_gather(list(seen_all.unbind(0)), sl, group=g)
-            loc = seen_all.view(Bg, S) - self.lo
-            ok = (seen_all.view(Bg, S) >= 0) & (loc >= 0) & (loc < self.Vs)
-            rows = torch.arange(Bg, device=self.device).view(Bg, 1).expand(Bg, S)
-            scores[rows[ok], loc[ok]] = 0.0
+        if not fused:
+            L.check(lib.bsarec_shard_logits(self.h_all.data_ptr(), d, Bg, self.E.data_ptr(), self.Vs, d, self.logits.data_ptr(),
+                                            self.ld, st), "bsarec_shard_logits")
+            scores = self.logits[:, :self.Vs]
+            if seen_all is not None:
+                loc = seen_all.view(Bg, S) - self.lo
+                ok = (seen_all.view(Bg, S) >= 0) & (loc >= 0) & (loc < self.Vs)
+                rows = torch.arange(Bg, device=self.device).view(Bg, 1).expand(Bg, S)
+                scores[rows[ok], loc[ok]] = 0.0
         if not 1 <= k <= min(L.TOPK_MAX, self.V):
             raise ValueError(f"topk: k = {k} outside 1 .. min(BSAREC_TOPK_MAX = {L.TOPK_MAX}, items = {self.V})")
         # rank r contributes its min(k, Vs_r) best; the gathered blocks are padded to k, and the merge reads only the real
@@ -390,7 +422,9 @@ class ShardedCatalogue:
         kk = n_r[self.rank]
         cand_v = torch.zeros(Bg, k, device=self.device)
         cand_i = torch.zeros(Bg, k, dtype=torch.int64, device=self.device)
-        if kk:
+        if kk and fused:
+            cand_v[:, :kk], cand_i[:, :kk] = self._topk_range(seen_all, kk)
+        elif kk:
             v, i = self._topk_rows(scores, self.logits.stride(0), kk)
             cand_v[:, :kk], cand_i[:, :kk] = v, i + self.lo
         all_v = torch.empty(W, Bg, k, device=self.device)
@@ -415,13 +449,39 @@ class ShardedCatalogue:
                                           self.encoder._stream()), "bsarec_topk_seen")
         return val, idx
 
+    def _topk_range(self, seen_all, k):
+        """k best owned items of all Bg rows of ``h_all`` without the score matrix (``bsarec_topk_full_range`` over the shard,
+        column base ``lo``): (scores [Bg, k], GLOBAL ids [Bg, k]).  ``seen_all`` int64 [W, B, S] of global ids or None: passed as
+        a CSR of S entries per row -- the -1 pads and the other ranks' items lie outside the range and are ignored."""
+        Bg, d, dev = self.Bg, self.d, self.device
+        key = (Bg, k)
+        ws = getattr(self, "_full_rank_ws", {}).get(key)
+        if ws is None:
+            nbytes = self.lib.bsarec_topk_full_workspace_bytes(Bg, self.Vs, d, k, 0)
+            if nbytes < 0:
+                raise ValueError(f"topk: eval_full_rank = 'fused' does not support Bg={Bg} Vs={self.Vs} d={d} k={k}")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self._full_rank_ws = {key: ws}
+        idx = torch.empty(Bg, k, dtype=torch.int64, device=dev)
+        val = torch.empty(Bg, k, dtype=torch.float32, device=dev)
+        csr = (None, None, None)
+        if seen_all is not None:
+            S = seen_all.shape[2]
+            users = torch.arange(Bg, dtype=torch.int64, device=dev)
+            indptr = torch.arange(Bg + 1, dtype=torch.int64, device=dev) * S
+            csr = (users.data_ptr(), indptr.data_ptr(), seen_all.data_ptr())
+        L.check(self.lib.bsarec_topk_full_range(self.h_all.data_ptr(), d, self.E.data_ptr(), Bg, self.Vs, self.lo, d, *csr, k, 0,
+                                                ws.data_ptr(), ws.numel(), idx.data_ptr(), val.data_ptr(),
+                                                self.encoder._stream()), "bsarec_topk_full_range")
+        return val, idx
+
     @torch.no_grad()
-    def full_sort_scores(self, batches, epoch: int = 0, k: int = 20, extra_ks=()):
+    def full_sort_scores(self, batches, epoch: int = 0, k: int = 20, extra_ks=(), full_rank=None):
         """The reference's evaluation bookkeeping (src/trainers.py:118-158 + get_full_sort_score, :70-83) over the SHARDED
         table: ``batches`` yields this rank's (input_ids [B, L], answers [B], seen [B, S] or None) per step (every rank the
         same number of steps); the top-max(k, *extra_ks) of each sequence comes from :meth:`topk`, hits and DCG sums are
         all-reduced, so every rank returns the metrics of the GLOBAL evaluation set: ([HR@5, NDCG@5, HR@10, NDCG@10, HR@20,
-        NDCG@20] + [HR@e, NDCG@e for e in extra_ks], str)."""
+        NDCG@20] + [HR@e, NDCG@e for e in extra_ks], str).  ``full_rank``: as in :meth:`topk`."""
         import torch.distributed as dist
         from .trainer import ndcg_at_k, recall_at_k
         extra = tuple(extra_ks or ())
@@ -429,7 +489,7 @@ class ShardedCatalogue:
         depth = max((k,) + extra)
         sums = torch.zeros(2 * len(ks) + 1, dtype=torch.float64, device=self.device)
         for ids, answers, seen in batches:
-            _, top_i = self.topk(ids, k=depth, seen=seen)
+            _, top_i = self.topk(ids, k=depth, seen=seen, full_rank=full_rank)
             hit = top_i == answers.to(device=self.device, dtype=torch.int64).view(-1, 1)
             n = hit.shape[0]
             for j, kk in enumerate(ks):

@@ -1829,12 +1829,15 @@ extern "C" long bsarec_topk_full_workspace_bytes(int B, int V, int d, int k, int
     return fr_align((long)B * 8) + fr_align((long)B * 4) + fr_align((long)B * f.s * 4) + (long)B * f.cap * 8;
 }
 
-extern "C" int bsarec_topk_full(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* users,
-                                const int64_t* indptr, const int64_t* indices, int k, int cand_cap, void* workspace,
-                                long workspace_bytes, int64_t* out_idx, float* out_val, void* stream) {
+// One code path: bsarec_topk_full is the col_base = 0 case.  item_emb holds rows [col_base, col_base + V) of the catalogue;
+// the CSR entries and out_idx are global ids (full_rank.h).
+extern "C" int bsarec_topk_full_range(const float* h, long ldh, const float* item_emb, int B, int V, long col_base, int d,
+                                      const int64_t* users, const int64_t* indptr, const int64_t* indices, int k, int cand_cap,
+                                      void* workspace, long workspace_bytes, int64_t* out_idx, float* out_val, void* stream) {
     static_assert(BSAREC_TOPK_MAX == TOPK_MAX && ROW_THREADS == 256 && FR_ROWS == 128, "full_rank.h: the header's limits");
     FrShape f;
     if (!fr_shape(B, V, d, k, cand_cap, &f)) return -10;
+    if (col_base < 0 || col_base + V > 0x7fffffffL) return -10;
     if (!h || !item_emb || !workspace || !out_idx || ldh < d || (indptr && (!users || !indices))) return -10;
     if ((uintptr_t)h % 16 != 0 || (uintptr_t)item_emb % 16 != 0 || (uintptr_t)workspace % 16 != 0) return -10;
     if (workspace_bytes < bsarec_topk_full_workspace_bytes(B, V, d, k, cand_cap)) return -10;
@@ -1856,19 +1859,26 @@ extern "C" int bsarec_topk_full(const float* h, long ldh, const float* item_emb,
         if (e != hipSuccess) return (int)e;
         attr = true;
     }
-    hipLaunchKernelGGL(full_rank_sample_kernel, dim3(B), dim3(ROW_THREADS), 0, st, h, ldh, item_emb, V, d, users, indptr, indices,
-                       k, (int)f.s, (int)f.stride, skeys, tau, count);
+    hipLaunchKernelGGL(full_rank_sample_kernel, dim3(B), dim3(ROW_THREADS), 0, st, h, ldh, item_emb, V, col_base, d, users, indptr,
+                       indices, k, (int)f.s, (int)f.stride, skeys, tau, count);
     for (int round = 0; round <= FR_ROUNDS; ++round) {
         if (round > 0)
             hipLaunchKernelGGL(full_rank_rethreshold_kernel, dim3(B), dim3(ROW_THREADS), 0, st, k, cap, tau, count, list);
         hipLaunchKernelGGL(full_rank_filter_kernel, dim3(tiles, groups), dim3(ROW_THREADS), smem, st, h, ldh, item_emb, B, V, d, cap,
                            tau, count, list);
     }
-    hipLaunchKernelGGL(full_rank_select_kernel, dim3(B), dim3(ROW_THREADS), 0, st, V, k, cap, users, indptr, indices, count, list,
-                       out_idx, out_val);
-    hipLaunchKernelGGL(full_rank_fallback_kernel, dim3(B), dim3(ROW_THREADS), 0, st, h, ldh, item_emb, V, d, k, cap, users, indptr,
-                       indices, count, out_idx, out_val);
+    hipLaunchKernelGGL(full_rank_select_kernel, dim3(B), dim3(ROW_THREADS), 0, st, V, col_base, k, cap, users, indptr, indices, count,
+                       list, out_idx, out_val);
+    hipLaunchKernelGGL(full_rank_fallback_kernel, dim3(B), dim3(ROW_THREADS), 0, st, h, ldh, item_emb, V, col_base, d, k, cap, users,
+                       indptr, indices, count, out_idx, out_val);
     return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_topk_full(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* users,
+                                const int64_t* indptr, const int64_t* indices, int k, int cand_cap, void* workspace,
+                                long workspace_bytes, int64_t* out_idx, float* out_val, void* stream) {
+    return bsarec_topk_full_range(h, ldh, item_emb, B, V, 0, d, users, indptr, indices, k, cand_cap, workspace, workspace_bytes,
+                                  out_idx, out_val, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

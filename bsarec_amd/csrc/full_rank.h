@@ -1,6 +1,6 @@
-// Full-catalogue top-k without the B x V score matrix (bsarec_topk_full, include/bsarec_hip.h): every item is scored on the
-// fly and only the items that can still reach a row's top-k are kept.  The order, the seen-item zeros and the result are
-// those of topk_seen_kernel on the materialised matrix.  Launch sequence on one stream (no host synchronisation):
+// Full-catalogue top-k without the B x V score matrix (bsarec_topk_full / bsarec_topk_full_range, include/bsarec_hip.h): every
+// item is scored on the fly and only the items that can still reach a row's top-k are kept.  The order, the seen-item zeros and
+// the result are those of topk_seen_kernel on the materialised matrix.  Launch sequence on one stream (no host synchronisation):
 //   (1) full_rank_sample_kernel: score s strided columns per row (seen items as 0), tau_b = a composite no larger than the
 //       sample's k-th (key << 32 | ~column) composite -- a lower bound on the row's true k-th composite;
 //   (2) full_rank_filter_kernel: (128-row tile x item range) grid, h tile in LDS, items through v_mfma_f32_32x32x2_f32; an
@@ -14,6 +14,9 @@
 //       row (seen bits of a segment in LDS), O(k) state.
 // Every score is the fmaf chain of fr_dot: acc = 0, then acc = fmaf(h[i], e[i], acc) for i = 0 .. d-1 -- which is what the
 // fp32 MFMA computes bit for bit (one rounding per product, k ascending), so all five kernels see identical scores.
+// Column base (bsarec_topk_full_range): E holds rows [base, base + V) of a larger catalogue.  Columns, composites and list
+// entries stay LOCAL (0 .. V), so the tie order inside the range is the global one; the base enters where a GLOBAL id crosses
+// the interface only: a CSR entry `it` applies iff 0 <= it - base < V, and fr_write adds the base to the ids it stores.
 #pragma once
 #include "kernels.h"
 
@@ -104,18 +107,18 @@ __device__ __forceinline__ void fr_sort(unsigned long long* cand, float* val, in
         }
     }
 }
-__device__ __forceinline__ void fr_write(const unsigned long long* cand, const float* val, int V, int k, int64_t* out_idx,
-                                         float* out_val) {
+__device__ __forceinline__ void fr_write(const unsigned long long* cand, const float* val, int V, long base, int k,
+                                         int64_t* out_idx, float* out_val) {
     for (int r = threadIdx.x; r < k; r += ROW_THREADS) {
         const int c = (int)~(unsigned)cand[r];           // (a slot left empty reads -1)
-        out_idx[(long)blockIdx.x * k + r] = c;
+        out_idx[(long)blockIdx.x * k + r] = c >= 0 ? base + c : c;
         if (out_val) out_val[(long)blockIdx.x * k + r] = c >= 0 && c < V ? val[r] : __builtin_nanf("");
     }
 }
 
 // (1) threshold from s columns i * stride, i < s.  skeys: [B][s] keys (the column is implied by the index).
 __global__ void __launch_bounds__(ROW_THREADS)
-full_rank_sample_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ E, int V, int d,
+full_rank_sample_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ E, int V, long base, int d,
                         const int64_t* __restrict__ users, const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
                         int k, int s, int stride, unsigned* skeys, unsigned long long* tau, unsigned* count) {
     __shared__ float hs[256];
@@ -129,7 +132,7 @@ full_rank_sample_kernel(const float* __restrict__ h, long ldh, const float* __re
     if (indptr) {
         const long u = users[b];
         for (long j = indptr[u] + tid; j < indptr[u + 1]; j += ROW_THREADS) {
-            const long it = indices[j];
+            const long g = indices[j], it = g >= base ? g - base : -1;
             if (it >= 0 && it < V && it % stride == 0 && it / stride < s) keys[it / stride] = FR_KEY0;
         }
     }
@@ -239,7 +242,7 @@ __device__ __forceinline__ unsigned fr_hash(long it) { return ((unsigned)it * 26
 
 // (4) rows within capacity.
 __global__ void __launch_bounds__(ROW_THREADS)
-full_rank_select_kernel(int V, int k, int cap, const int64_t* __restrict__ users, const int64_t* __restrict__ indptr,
+full_rank_select_kernel(int V, long base, int k, int cap, const int64_t* __restrict__ users, const int64_t* __restrict__ indptr,
                         const int64_t* __restrict__ indices, const unsigned* __restrict__ count, unsigned long long* list,
                         int64_t* __restrict__ out_idx, float* __restrict__ out_val) {
     static_assert(FR_HASH == 4096, "fr_hash: 12 bits");
@@ -259,7 +262,7 @@ full_rank_select_kernel(int V, int k, int cap, const int64_t* __restrict__ users
             __syncthreads();
             const long c1 = c0 + FR_HASH / 2 < j1 ? c0 + FR_HASH / 2 : j1;
             for (long j = c0 + tid; j < c1; j += ROW_THREADS) {
-                const long it = indices[j];
+                const long g = indices[j], it = g >= base ? g - base : -1;
                 if (it < 0 || it >= V) continue;
                 for (unsigned p = fr_hash(it);; p = (p + 1) & (FR_HASH - 1)) {
                     const int old = atomicCAS(&table[p], -1, (int)it);
@@ -292,13 +295,13 @@ full_rank_select_kernel(int V, int k, int cap, const int64_t* __restrict__ users
     int np = 1;
     while (np < k) np <<= 1;
     fr_sort(cand, cval, np);
-    fr_write(cand, cval, V, k, out_idx, out_val);
+    fr_write(cand, cval, V, base, k, out_idx, out_val);
 }
 
 // (5) rows over capacity after the last round: exact streaming top-k, segment by segment.
 __global__ void __launch_bounds__(ROW_THREADS)
-full_rank_fallback_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ E, int V, int d, int k, int cap,
-                          const int64_t* __restrict__ users, const int64_t* __restrict__ indptr,
+full_rank_fallback_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ E, int V, long base, int d, int k,
+                          int cap, const int64_t* __restrict__ users, const int64_t* __restrict__ indptr,
                           const int64_t* __restrict__ indices, const unsigned* __restrict__ count,
                           int64_t* __restrict__ out_idx, float* __restrict__ out_val) {
     __shared__ float hs[256];
@@ -318,7 +321,7 @@ full_rank_fallback_kernel(const float* __restrict__ h, long ldh, const float* __
         for (int i = tid; i < FR_SEG / 32; i += ROW_THREADS) bits[i] = 0u;
         __syncthreads();
         for (long j = j0 + tid; j < j1; j += ROW_THREADS) {
-            const long it = indices[j];
+            const long g = indices[j], it = g >= base ? g - base : -1;
             if (it >= c0 && it < c0 + m) atomicOr(&bits[(it - c0) >> 5], 1u << ((it - c0) & 31));
         }
         __syncthreads();
@@ -363,5 +366,5 @@ full_rank_fallback_kernel(const float* __restrict__ h, long ldh, const float* __
     while (np < k) np <<= 1;
     for (int i = ncur + tid; i < np; i += ROW_THREADS) cur[i] = 0ull;
     fr_sort(cur, curv, np);
-    fr_write(cur, curv, V, k, out_idx, out_val);
+    fr_write(cur, curv, V, base, k, out_idx, out_val);
 }

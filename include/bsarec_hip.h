@@ -406,6 +406,19 @@ long bsarec_topk_full_workspace_bytes(int B, int V, int d, int k, int cand_cap);
 int bsarec_topk_full(const float *h, long ldh, const float *item_emb, int B, int V, int d, const int64_t *users,
                      const int64_t *indptr, const int64_t *indices, int k, int cand_cap, void *workspace, long workspace_bytes,
                      int64_t *out_idx, float *out_val, void *stream);
+/* bsarec_topk_full over a contiguous item range: item_rows holds rows [col_base, col_base + Vs) of a larger catalogue (one
+ * shard of a catalogue split by rows).  bsarec_topk_full is the col_base = 0 case of the same code.
+ *   Scores: the same fmaf chain of the h row and the item row: the score of an item does not depend on the range it is in.
+ *   Seen items: the CSR indices are GLOBAL item ids; an entry applies (score +0.0) iff col_base <= id < col_base + Vs, every
+ *   other entry (another range's items, negative padding) is ignored.
+ *   Result: out_idx are GLOBAL ids (col_base + the row of item_rows), in bsarec_topk_seen's total order; equal scores go to
+ *   the smaller global id.  So the top-k of a catalogue cut into contiguous ranges is the merge, under that order, of the
+ *   ranges' top-min(k, Vs) lists.
+ *   Execution, workspace (bsarec_topk_full_workspace_bytes(B, Vs, d, k, cand_cap)) and limits: those of bsarec_topk_full with
+ *   V := Vs, and col_base >= 0, col_base + Vs <= 2^31 - 1 (else < 0 before any HIP call). */
+int bsarec_topk_full_range(const float *h, long ldh, const float *item_rows, int B, int Vs, long col_base, int d,
+                           const int64_t *users, const int64_t *indptr, const int64_t *indices, int k, int cand_cap,
+                           void *workspace, long workspace_bytes, int64_t *out_idx, float *out_val, void *stream);
 
 /* Stand-alone FrequencyLayer (src/model/bsarec.py:90-104) for per-op parity tests:
  * y = LN(Drop(low + beta^2 (x - low)) + x); backward given dy. */
