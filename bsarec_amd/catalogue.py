@@ -51,17 +51,7 @@ import torch
 from . import _lib as L
 from .dp import PeerExchange, _as_tensor
 from .model import BSARecModel, train_head_of
-
-
-EVAL_FULL_RANK = ("dense", "fused")
-
-
-def eval_full_rank_of(args, full_rank=None) -> str:
-    """The evaluation path of ``topk``: ``full_rank`` when given, else ``args.eval_full_rank``, else "dense"."""
-    mode = getattr(args, "eval_full_rank", "dense") if full_rank is None else full_rank
-    if mode not in EVAL_FULL_RANK:
-        raise ValueError(f"eval_full_rank = {mode!r}, expected one of {EVAL_FULL_RANK}")
-    return mode
+from .ranking import EVAL_FULL_RANK, REFERENCE_KS, FullRank, cutoff_metrics, eval_full_rank_of, metrics_post_fix, topk_seen
 
 
 class ShardedCatalogue:
@@ -97,6 +87,7 @@ class ShardedCatalogue:
         self.n = self.B * Lq
         self.Bg = self.W * self.B
         self.lib = L.load()
+        self._full_rank = FullRank("topk: eval_full_rank = 'fused' does not support Bg={B} Vs={V} d={d} k={k}")
         # encoder replica over the staging table
         enc_args = copy.copy(args)
         enc_args.item_size = self.n + 1
@@ -425,7 +416,7 @@ class ShardedCatalogue:
         if kk and fused:
             cand_v[:, :kk], cand_i[:, :kk] = self._topk_range(seen_all, kk)
         elif kk:
-            v, i = self._topk_rows(scores, self.logits.stride(0), kk)
+            i, v = topk_seen(scores, kk, values=True)
             cand_v[:, :kk], cand_i[:, :kk] = v, i + self.lo
         all_v = torch.empty(W, Bg, k, device=self.device)
         all_i = torch.empty(W, Bg, k, dtype=torch.int64, device=self.device)
@@ -434,45 +425,19 @@ class ShardedCatalogue:
         real = torch.cat([torch.arange(r * k, r * k + n, device=self.device) for r, n in enumerate(n_r) if n])
         mv = all_v.permute(1, 0, 2).reshape(Bg, W * k)[:, real].contiguous()
         mi = all_i.permute(1, 0, 2).reshape(Bg, W * k)[:, real]
-        top_v, sel = self._topk_rows(mv, mv.shape[1], k)
+        sel, top_v = topk_seen(mv, k, values=True)
         top_i = torch.gather(mi, 1, sel)
         r0 = self.rank * B
         return top_v[r0:r0 + B].clone(), top_i[r0:r0 + B].clone()
 
-    def _topk_rows(self, scores, ld, k):
-        """k best columns of every row, descending (``bsarec_topk_seen`` without a seen-item mask: the HIP top-k of the
-        evaluation path; equal scores go to the smaller column)."""
-        rows, V = scores.shape[0], scores.shape[1]
-        idx = torch.empty(rows, k, dtype=torch.int64, device=self.device)
-        val = torch.empty(rows, k, dtype=torch.float32, device=self.device)
-        L.check(self.lib.bsarec_topk_seen(scores.data_ptr(), ld, rows, V, None, None, None, k, idx.data_ptr(), val.data_ptr(),
-                                          self.encoder._stream()), "bsarec_topk_seen")
-        return val, idx
-
     def _topk_range(self, seen_all, k):
-        """k best owned items of all Bg rows of ``h_all`` without the score matrix (``bsarec_topk_full_range`` over the shard,
-        column base ``lo``): (scores [Bg, k], GLOBAL ids [Bg, k]).  ``seen_all`` int64 [W, B, S] of global ids or None: passed as
-        a CSR of S entries per row -- the -1 pads and the other ranks' items lie outside the range and are ignored."""
-        Bg, d, dev = self.Bg, self.d, self.device
-        key = (Bg, k)
-        ws = getattr(self, "_full_rank_ws", {}).get(key)
-        if ws is None:
-            nbytes = self.lib.bsarec_topk_full_workspace_bytes(Bg, self.Vs, d, k, 0)
-            if nbytes < 0:
-                raise ValueError(f"topk: eval_full_rank = 'fused' does not support Bg={Bg} Vs={self.Vs} d={d} k={k}")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self._full_rank_ws = {key: ws}
-        idx = torch.empty(Bg, k, dtype=torch.int64, device=dev)
-        val = torch.empty(Bg, k, dtype=torch.float32, device=dev)
-        csr = (None, None, None)
+        """k best owned items of all Bg rows of ``h_all`` (``FullRank`` over the shard, column base ``lo``): (scores, GLOBAL ids).
+        ``seen_all`` int64 [W, B, S] or None: a CSR of S entries per row; -1 pads and other ranks' items lie outside the range."""
+        users = csr = None
         if seen_all is not None:
-            S = seen_all.shape[2]
-            users = torch.arange(Bg, dtype=torch.int64, device=dev)
-            indptr = torch.arange(Bg + 1, dtype=torch.int64, device=dev) * S
-            csr = (users.data_ptr(), indptr.data_ptr(), seen_all.data_ptr())
-        L.check(self.lib.bsarec_topk_full_range(self.h_all.data_ptr(), d, self.E.data_ptr(), Bg, self.Vs, self.lo, d, *csr, k, 0,
-                                                ws.data_ptr(), ws.numel(), idx.data_ptr(), val.data_ptr(),
-                                                self.encoder._stream()), "bsarec_topk_full_range")
+            users = torch.arange(self.Bg, dtype=torch.int64, device=self.device)
+            csr = (torch.arange(self.Bg + 1, dtype=torch.int64, device=self.device) * seen_all.shape[2], seen_all)
+        idx, val = self._full_rank(self.h_all, self.E[:self.Vs], k, users, csr, base=self.lo, values=True)
         return val, idx
 
     @torch.no_grad()
@@ -483,25 +448,18 @@ class ShardedCatalogue:
         all-reduced, so every rank returns the metrics of the GLOBAL evaluation set: ([HR@5, NDCG@5, HR@10, NDCG@10, HR@20,
         NDCG@20] + [HR@e, NDCG@e for e in extra_ks], str).  ``full_rank``: as in :meth:`topk`."""
         import torch.distributed as dist
-        from .trainer import ndcg_at_k, recall_at_k
-        extra = tuple(extra_ks or ())
-        ks = (5, 10, 20) + extra
-        depth = max((k,) + extra)
+        ks = REFERENCE_KS + tuple(extra_ks or ())
+        depth = max((k,) + ks[3:])
         sums = torch.zeros(2 * len(ks) + 1, dtype=torch.float64, device=self.device)
         for ids, answers, seen in batches:
             _, top_i = self.topk(ids, k=depth, seen=seen, full_rank=full_rank)
             hit = top_i == answers.to(device=self.device, dtype=torch.int64).view(-1, 1)
             n = hit.shape[0]
-            for j, kk in enumerate(ks):
-                sums[2 * j] += recall_at_k(hit, kk) * n
-                sums[2 * j + 1] += ndcg_at_k(hit, kk) * n
+            sums[:-1] += torch.tensor(cutoff_metrics(ks, hit=hit), dtype=torch.float64, device=self.device) * n
             sums[-1] += n
         dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.group)
         vals = (sums[:-1] / sums[-1].clamp(min=1)).tolist()
-        post_fix = {"Epoch": epoch}
-        for j, kk in enumerate(ks):
-            post_fix[f"HR@{kk}"], post_fix[f"NDCG@{kk}"] = '{:.4f}'.format(vals[2 * j]), '{:.4f}'.format(vals[2 * j + 1])
-        return vals, str(post_fix)
+        return vals, str(metrics_post_fix(epoch, ks, vals))
 
     def close(self):
         torch.cuda.synchronize(self.device)

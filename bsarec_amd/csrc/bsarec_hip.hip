@@ -10,6 +10,7 @@
 #include "fused_chain.h"
 #include "comm.h"
 #include "catalogue_shard.h"
+#include "rank.h"
 #include "sampled_rank.h"
 #include "full_rank.h"
 #include "sampled_softmax.h"

@@ -18,20 +18,17 @@
 // entries stay LOCAL (0 .. V), so the tie order inside the range is the global one; the base enters where a GLOBAL id crosses
 // the interface only: a CSR entry `it` applies iff 0 <= it - base < V, and fr_write adds the base to the ids it stores.
 #pragma once
-#include "kernels.h"
+#include "rank.h"
 
 #define FR_ROWS 128                        // rows per filter tile: 4 row blocks of the 32 x 32 MFMA
 #define FR_ITEMS 128                       // items per filter step: 4 waves x 32
 #define FR_ROUNDS 2                        // re-threshold rounds before the fallback
-#define FR_HASH 4096                       // select: LDS hash slots for 2048 seen items per chunk
+#define FR_HASH RANK_SLOTS                 // select: LDS hash slots (rank_hash) for 2048 seen items per chunk
 #define FR_SEG 2048                        // fallback: items per segment
 #define FR_KEY0 0x80000000u                // topk_key(+0.0f)
 
-__device__ __forceinline__ unsigned long long fr_comp(unsigned key, unsigned col) {
-    return ((unsigned long long)key << 32) | (unsigned)~col;
-}
 __device__ __forceinline__ unsigned long long fr_entry_comp(unsigned long long e) {   // list entry: score bits << 32 | column
-    return fr_comp(topk_key(__uint_as_float((unsigned)(e >> 32))), (unsigned)e);
+    return rank_comp(topk_key(__uint_as_float((unsigned)(e >> 32))), (unsigned)e);
 }
 // One score: h row in LDS, item row from global (16-byte aligned, d % 4 == 0).
 __device__ __forceinline__ float fr_dot(const float* hs, const float* __restrict__ e, int d) {
@@ -47,65 +44,16 @@ __device__ __forceinline__ float fr_dot(const float* hs, const float* __restrict
     return acc;
 }
 
-struct FrRadix { unsigned hist[ROW_THREADS / 64][256]; unsigned wscan[ROW_THREADS / 64]; unsigned sel[3]; };
-
-// Radix select over n DISTINCT 64-bit values get(0 .. n) (8-bit digits from the top, per-wave LDS histograms, early exit when
-// the selected bin is taken whole, as in topk_seen_kernel).  Returns T with #{i : get(i) >= T} == k, for n >= k.  Called by
-// all ROW_THREADS threads; starts and ends with a barrier.
-template <class F>
-__device__ unsigned long long fr_kth(FrRadix& sm, long n, int k, F get) {
-    constexpr int NW = ROW_THREADS / 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned long long prefix = 0ull, mask = 0ull;
-    int rem = k;
-    __syncthreads();
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        for (int i = tid; i < NW * 256; i += ROW_THREADS) (&sm.hist[0][0])[i] = 0u;
-        __syncthreads();
-        if (tid == 0) { sm.sel[0] = 0u; sm.sel[1] = 0u; sm.sel[2] = 0u; }
-        for (long i = tid; i < n; i += ROW_THREADS) {
-            const unsigned long long v = get(i);
-            if ((v & mask) == prefix) atomicAdd(&sm.hist[wave][(unsigned)(v >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        const int bin = 255 - tid;
-        unsigned cnt = 0u;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) cnt += sm.hist[w][bin];
-        unsigned incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const unsigned y = __shfl_up(incl, off, 64); if (lane >= off) incl += y; }
-        if (lane == 63) sm.wscan[wave] = incl;
-        __syncthreads();
-        for (int w = 0; w < wave; ++w) incl += sm.wscan[w];
-        const unsigned above = incl - cnt;
-        if (above < (unsigned)rem && incl >= (unsigned)rem) { sm.sel[0] = bin; sm.sel[1] = above; sm.sel[2] = cnt; }
-        __syncthreads();
-        rem -= (int)sm.sel[1];
-        prefix |= (unsigned long long)sm.sel[0] << shift;
-        mask |= 255ull << shift;
-        if (sm.sel[2] == (unsigned)rem) break;
-    }
-    __syncthreads();
-    return prefix;
+// The k-th largest of n DISTINCT composites get(0 .. n), n >= k: T with #{i : get(i) >= T} == k (rank_select; starts and
+// ends with a barrier).
+template <class N, class F>
+__device__ __forceinline__ unsigned long long fr_kth(RankRadix& sm, N n, int k, F get) {
+    return rank_select<unsigned long long, 1>(sm, n, k, get).prefix;
 }
-
-// Descending bitonic sort of n (power of two) composites with their scores in LDS.  Ends with a barrier.
-__device__ __forceinline__ void fr_sort(unsigned long long* cand, float* val, int n) {
-    __syncthreads();
-    for (int size = 2; size <= n; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = threadIdx.x; i < (n >> 1); i += ROW_THREADS) {
-                const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-                const unsigned long long a = cand[lo], b = cand[hi];
-                if (((lo & size) == 0) == (a < b)) {
-                    cand[lo] = b; cand[hi] = a;
-                    const float t = val[lo]; val[lo] = val[hi]; val[hi] = t;
-                }
-            }
-            __syncthreads();
-        }
-    }
+// A CSR entry g (a GLOBAL id) as a local column of [base, base + V), or -1 when it lies outside.
+__device__ __forceinline__ long fr_local(long g, long base, int V) {
+    const long it = g >= base ? g - base : -1;
+    return it < V ? it : -1;
 }
 __device__ __forceinline__ void fr_write(const unsigned long long* cand, const float* val, int V, long base, int k,
                                          int64_t* out_idx, float* out_val) {
@@ -122,7 +70,7 @@ full_rank_sample_kernel(const float* __restrict__ h, long ldh, const float* __re
                         const int64_t* __restrict__ users, const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
                         int k, int s, int stride, unsigned* skeys, unsigned long long* tau, unsigned* count) {
     __shared__ float hs[256];
-    __shared__ FrRadix sm;
+    __shared__ RankRadix sm;
     const int b = blockIdx.x, tid = threadIdx.x;
     for (int i = tid; i < d; i += ROW_THREADS) hs[i] = h[(long)b * ldh + i];
     __syncthreads();
@@ -132,11 +80,11 @@ full_rank_sample_kernel(const float* __restrict__ h, long ldh, const float* __re
     if (indptr) {
         const long u = users[b];
         for (long j = indptr[u] + tid; j < indptr[u + 1]; j += ROW_THREADS) {
-            const long g = indices[j], it = g >= base ? g - base : -1;
-            if (it >= 0 && it < V && it % stride == 0 && it / stride < s) keys[it / stride] = FR_KEY0;
+            const long it = fr_local(indices[j], base, V);
+            if (it >= 0 && it % stride == 0 && it / stride < s) keys[it / stride] = FR_KEY0;
         }
     }
-    const unsigned long long T = fr_kth(sm, s, k, [&](long i) { return fr_comp(keys[i], (unsigned)(i * stride)); });
+    const unsigned long long T = fr_kth(sm, s, k, [&](long i) { return rank_comp(keys[i], (unsigned)(i * stride)); });
     if (tid == 0) { tau[b] = T; count[b] = 0u; }
 }
 
@@ -187,7 +135,7 @@ full_rank_filter_kernel(const float* __restrict__ h, long ldh, const float* __re
                 acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? a.w : a.z, b1, acc[rb], 0, 0, 0);
             }
         }
-        const unsigned long long zc = fr_comp(FR_KEY0, (unsigned)item);
+        const unsigned long long zc = rank_comp(FR_KEY0, (unsigned)item);
 #pragma unroll
         for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
@@ -198,7 +146,7 @@ full_rank_filter_kernel(const float* __restrict__ h, long ldh, const float* __re
                 bool pass = false;
                 if (iv && key >= lo_s[i]) {
                     const unsigned long long t = tau_s[i];
-                    pass = fr_comp(key, (unsigned)item) >= t || zc >= t;
+                    pass = rank_comp(key, (unsigned)item) >= t || zc >= t;
                 }
                 const unsigned long long bal = __ballot(pass);
                 if (bal) {
@@ -226,31 +174,28 @@ full_rank_filter_kernel(const float* __restrict__ h, long ldh, const float* __re
 // tau = ~0 (the next filter round skips them; their list stays).
 __global__ void __launch_bounds__(ROW_THREADS)
 full_rank_rethreshold_kernel(int k, int cap, unsigned long long* tau, unsigned* count, const unsigned long long* __restrict__ list) {
-    __shared__ FrRadix sm;
+    __shared__ RankRadix sm;
     const int b = blockIdx.x;
     const unsigned n = count[b];
     if (n <= (unsigned)cap) { if (threadIdx.x == 0) tau[b] = ~0ull; return; }
     const unsigned long long* L = list + (long)b * cap;
     const unsigned long long T = fr_kth(sm, cap, k, [&](long i) {
-        const unsigned long long e = L[i], rc = fr_entry_comp(e), zc = fr_comp(FR_KEY0, (unsigned)e);
+        const unsigned long long e = L[i], rc = fr_entry_comp(e), zc = rank_comp(FR_KEY0, (unsigned)e);
         return rc < zc ? rc : zc;
     });
     if (threadIdx.x == 0) { const unsigned long long t = tau[b]; tau[b] = T > t ? T : t; count[b] = 0u; }
 }
-
-__device__ __forceinline__ unsigned fr_hash(long it) { return ((unsigned)it * 2654435761u) >> 20; }   // 12 bits: FR_HASH
 
 // (4) rows within capacity.
 __global__ void __launch_bounds__(ROW_THREADS)
 full_rank_select_kernel(int V, long base, int k, int cap, const int64_t* __restrict__ users, const int64_t* __restrict__ indptr,
                         const int64_t* __restrict__ indices, const unsigned* __restrict__ count, unsigned long long* list,
                         int64_t* __restrict__ out_idx, float* __restrict__ out_val) {
-    static_assert(FR_HASH == 4096, "fr_hash: 12 bits");
     __shared__ int table[FR_HASH];
     __shared__ unsigned long long cand[TOPK_MAX];
     __shared__ float cval[TOPK_MAX];
     __shared__ unsigned ncand;
-    __shared__ FrRadix sm;
+    __shared__ RankRadix sm;
     const int b = blockIdx.x, tid = threadIdx.x;
     const unsigned n = count[b];
     if (n > (unsigned)cap) return;                      // the fallback's row
@@ -262,9 +207,9 @@ full_rank_select_kernel(int V, long base, int k, int cap, const int64_t* __restr
             __syncthreads();
             const long c1 = c0 + FR_HASH / 2 < j1 ? c0 + FR_HASH / 2 : j1;
             for (long j = c0 + tid; j < c1; j += ROW_THREADS) {
-                const long g = indices[j], it = g >= base ? g - base : -1;
-                if (it < 0 || it >= V) continue;
-                for (unsigned p = fr_hash(it);; p = (p + 1) & (FR_HASH - 1)) {
+                const long it = fr_local(indices[j], base, V);
+                if (it < 0) continue;
+                for (unsigned p = rank_hash((unsigned)it);; p = (p + 1) & (FR_HASH - 1)) {
                     const int old = atomicCAS(&table[p], -1, (int)it);
                     if (old == -1 || old == (int)it) break;
                 }
@@ -272,7 +217,7 @@ full_rank_select_kernel(int V, long base, int k, int cap, const int64_t* __restr
             __syncthreads();
             for (unsigned i = tid; i < n; i += ROW_THREADS) {
                 const int col = (int)(unsigned)L[i];
-                for (unsigned p = fr_hash(col);; p = (p + 1) & (FR_HASH - 1)) {
+                for (unsigned p = rank_hash((unsigned)col);; p = (p + 1) & (FR_HASH - 1)) {
                     const int t = table[p];
                     if (t == col) { L[i] = (unsigned)col; break; }   // seen: score +0.0
                     if (t == -1) break;
@@ -294,7 +239,7 @@ full_rank_select_kernel(int V, long base, int k, int cap, const int64_t* __restr
     }
     int np = 1;
     while (np < k) np <<= 1;
-    fr_sort(cand, cval, np);
+    rank_sort<true>(cand, cval, np);
     fr_write(cand, cval, V, base, k, out_idx, out_val);
 }
 
@@ -309,7 +254,7 @@ full_rank_fallback_kernel(const float* __restrict__ h, long ldh, const float* __
     __shared__ float curv[TOPK_MAX], segv[FR_SEG];
     __shared__ unsigned bits[FR_SEG / 32];
     __shared__ unsigned nsel;
-    __shared__ FrRadix sm;
+    __shared__ RankRadix sm;
     const int b = blockIdx.x, tid = threadIdx.x;
     if (count[b] <= (unsigned)cap) return;
     for (int i = tid; i < d; i += ROW_THREADS) hs[i] = h[(long)b * ldh + i];
@@ -321,13 +266,13 @@ full_rank_fallback_kernel(const float* __restrict__ h, long ldh, const float* __
         for (int i = tid; i < FR_SEG / 32; i += ROW_THREADS) bits[i] = 0u;
         __syncthreads();
         for (long j = j0 + tid; j < j1; j += ROW_THREADS) {
-            const long g = indices[j], it = g >= base ? g - base : -1;
+            const long it = fr_local(indices[j], base, V);
             if (it >= c0 && it < c0 + m) atomicOr(&bits[(it - c0) >> 5], 1u << ((it - c0) & 31));
         }
         __syncthreads();
         for (int t = tid; t < m; t += ROW_THREADS) {
             const float sc = (bits[t >> 5] >> (t & 31)) & 1u ? 0.f : fr_dot(hs, E + (long)(c0 + t) * d, d);
-            seg[t] = fr_comp(topk_key(sc), (unsigned)(c0 + t));
+            seg[t] = rank_comp(topk_key(sc), (unsigned)(c0 + t));
             segv[t] = sc;
         }
         __syncthreads();
@@ -365,6 +310,6 @@ full_rank_fallback_kernel(const float* __restrict__ h, long ldh, const float* __
     int np = 1;
     while (np < k) np <<= 1;
     for (int i = ncur + tid; i < np; i += ROW_THREADS) cur[i] = 0ull;
-    fr_sort(cur, curv, np);
+    rank_sort<true>(cur, curv, np);
     fr_write(cur, curv, V, base, k, out_idx, out_val);
 }

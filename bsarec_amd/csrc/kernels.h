@@ -1025,21 +1025,6 @@ bce_bwd_kernel(const float* __restrict__ hlast, long hstride, const float* __res
     }
 }
 
-
-// =============================================================================================
-// Evaluation: scores of the items a user has already interacted with are set to 0 -- not -inf -- before the top-k
-// (src/trainers.py:134: rating_pred[train_matrix[user].toarray() > 0] = 0).  One workgroup per batch row walks the
-// user's CSR row on the device.
-// =============================================================================================
-__global__ void __launch_bounds__(ROW_THREADS)
-mask_seen_kernel(float* __restrict__ scores, long ld, const int64_t* __restrict__ users, const int64_t* __restrict__ indptr,
-                 const int64_t* __restrict__ indices) {
-    const long u = users[blockIdx.x];
-    const long j0 = indptr[u], j1 = indptr[u + 1];
-    float* row = scores + (long)blockIdx.x * ld;
-    for (long j = j0 + threadIdx.x; j < j1; j += ROW_THREADS) row[indices[j]] = 0.f;
-}
-
 // y += x on [n4 * 4] elements: the upstream gradient of an INTERMEDIATE layer output (forward(all_sequence_output=True),
 // src/model/bsarec.py:46-54) joins the gradient that flows down from the layers above.  y: the inter-block gradient
 // buffer (fp32, or bf16 under storage = 1), x: the caller's fp32 tensor.
@@ -1060,123 +1045,5 @@ grad_join_kernel(float* __restrict__ y, const float* __restrict__ x, long n4, in
             a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
             reinterpret_cast<float4*>(y)[i] = a;
         }
-    }
-}
-
-// Order of the top-k (bsarec_topk_seen, include/bsarec_hip.h): a TOTAL order on (score, column) -- score descending with
-// every NaN equal to each other and above +inf, -0 equal to +0; among equal scores the smaller column first.  topk_key maps
-// a score to a 32-bit key whose unsigned order is that score order (canonical NaN / +0 first, then the usual sign flip); a
-// real score's key is >= topk_key(-inf) = 0x007fffff, so key 0 sorts below every score.
-__device__ __forceinline__ unsigned topk_key(float v) {
-    unsigned u = __float_as_uint(v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) u = 0x7fc00000u;          // any NaN -> one quiet NaN (key 0xffc00000 > +inf's)
-    if (u == 0x80000000u) u = 0u;                                   // -0 -> +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-// Seen-item masking of bsarec_topk_seen: the CSR row of the user is written as zeros into the score row (as the reference does
-// -- the caller may still read the masked scores).  Ends with a barrier: the scan that follows reads the zeros.
-__device__ __forceinline__ void topk_mask_seen(float* row, int V, const int64_t* users, const int64_t* indptr, const int64_t* indices) {
-    if (!indptr) return;
-    const long u = users[blockIdx.x];
-    const long j0 = indptr[u], j1 = indptr[u + 1];
-    for (long j = j0 + threadIdx.x; j < j1; j += ROW_THREADS) { const long it = indices[j]; if (it >= 0 && it < V) row[it] = 0.f; }
-    __syncthreads();
-}
-
-// Top-k of every score row with the seen items zeroed first, 1 <= k <= TOPK_MAX: the body of the reference's evaluation loop
-// for one batch (src/trainers.py:134-149: rating_pred[train_matrix[user] > 0] = 0, np.argpartition(..., -20), argsort of the
-// 20) in ONE launch, one workgroup per user.  (1) topk_mask_seen; (2) radix select of the k-th largest key, 8-bit digits from
-// the most significant one: each pass histograms the digit of the keys that match the prefix chosen so far (per-wave LDS
-// histograms), a workgroup scan over the 256 bins (descending digit) picks the bin that holds the k-th key; it stops early
-// once that bin is taken whole.  The result is a (prefix, mask) threshold: `rem` keys with key & mask == prefix are still
-// needed, k - rem keys lie above it.  (3) one ORDERED compaction pass over the row in 256-column chunks: keys above the
-// threshold take slots [0, k - rem) through an LDS counter; keys on the threshold are ranked by column (ballot + workgroup
-// prefix of the wave counts) and the first rem of them fill slots [k - rem, k) -- exact ties at the k-th place (e.g.
-// thousands of seen-item zeros) go to the smaller columns.  (4) bitonic sort (descending) of the k composites
-// key << 32 | ~column in LDS, padded with 0 (below every real key) to a power of two.  Every pass re-reads the row from
-// global memory (L2-resident at these row lengths); LDS: 4 KB of histograms + 8 KB of candidates.
-#define TOPK_MAX 1024
-__global__ void __launch_bounds__(ROW_THREADS)
-topk_seen_kernel(float* __restrict__ scores, long ld, int V, const int64_t* __restrict__ users, const int64_t* __restrict__ indptr,
-                 const int64_t* __restrict__ indices, int k, int64_t* __restrict__ out_idx, float* __restrict__ out_val) {
-    constexpr int NW = ROW_THREADS / 64;
-    __shared__ unsigned hist[NW][256];
-    __shared__ unsigned long long cand[TOPK_MAX];
-    __shared__ unsigned wscan[NW], wcnt[2][NW], sel[3], ngt;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* row = scores + (long)blockIdx.x * ld;
-    topk_mask_seen(row, V, users, indptr, indices);
-    // ---- (2) radix select
-    unsigned prefix = 0u, mask = 0u;
-    int rem = k;                                         // keys still to take among those matching the prefix
-    if (tid == 0) ngt = 0u;
-    for (int i = tid; i < TOPK_MAX; i += ROW_THREADS) cand[i] = 0ull;   // (the sort's padding; the barriers below order it)
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        for (int i = tid; i < NW * 256; i += ROW_THREADS) (&hist[0][0])[i] = 0u;
-        __syncthreads();
-#pragma unroll 4
-        for (int c = tid; c < V; c += ROW_THREADS) {
-            const unsigned key = topk_key(row[c]);
-            if ((key & mask) == prefix) atomicAdd(&hist[wave][(key >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        const int bin = 255 - tid;                       // thread t owns digit 255 - t: the scan runs from the top digit down
-        unsigned cnt = 0u;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) cnt += hist[w][bin];
-        unsigned incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const unsigned y = __shfl_up(incl, off, 64); if (lane >= off) incl += y; }
-        if (lane == 63) wscan[wave] = incl;
-        __syncthreads();
-        for (int w = 0; w < wave; ++w) incl += wscan[w];
-        const unsigned above = incl - cnt;               // matching keys with a larger digit
-        if (above < (unsigned)rem && incl >= (unsigned)rem) { sel[0] = bin; sel[1] = above; sel[2] = cnt; }   // exactly one thread
-        __syncthreads();
-        rem -= (int)sel[1];
-        prefix |= sel[0] << shift;
-        mask |= 255u << shift;
-        if (sel[2] == (unsigned)rem) break;              // the bin is taken whole: no finer digit needed
-    }
-    // ---- (3) ordered compaction
-    const int n_gt = k - rem;
-    int taken = 0;                                       // threshold keys ranked so far (the same in every thread)
-    for (int c0 = 0, par = 0; c0 < V; c0 += ROW_THREADS, par ^= 1) {
-        const int c = c0 + tid;
-        const unsigned key = c < V ? topk_key(row[c]) : 0u;
-        const unsigned long long comp = ((unsigned long long)key << 32) | (unsigned)~c;
-        if (c < V && (key & mask) > prefix) cand[atomicAdd(&ngt, 1u)] = comp;
-        if (taken < rem) {
-            const bool eq = c < V && (key & mask) == prefix;
-            const unsigned long long bal = __ballot(eq);
-            if (lane == 0) wcnt[par][wave] = (unsigned)__popcll(bal);
-            __syncthreads();                             // (wcnt is double-buffered: the next chunk writes the other half)
-            int before = taken;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) { const int n = (int)wcnt[par][w]; if (w < wave) before += n; taken += n; }
-            if (eq) {
-                const int r = before + __popcll(bal & ((1ull << lane) - 1ull));
-                if (r < rem) cand[n_gt + r] = comp;
-            }
-        }
-    }
-    // ---- (4) bitonic sort of the k survivors, descending
-    int n = 1;
-    while (n < k) n <<= 1;
-    __syncthreads();
-    for (int size = 2; size <= n; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < (n >> 1); i += ROW_THREADS) {
-                const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-                const unsigned long long a = cand[lo], b = cand[hi];
-                if (((lo & size) == 0) == (a < b)) { cand[lo] = b; cand[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    for (int r = tid; r < k; r += ROW_THREADS) {
-        const int c = (int)~(unsigned)cand[r];            // (a slot left empty would read -1: never a load out of the row)
-        out_idx[(long)blockIdx.x * k + r] = c;
-        if (out_val) out_val[(long)blockIdx.x * k + r] = c >= 0 && c < V ? row[c] : __builtin_nanf("");
     }
 }

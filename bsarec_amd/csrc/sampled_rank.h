@@ -3,14 +3,14 @@
 // the answer among them.  One 256-thread workgroup per row; the protocol (draw stream, acceptance, tie rule) is the
 // header's, restated in numpy by tests/sampled_eval_ref.py.
 #pragma once
-#include "kernels.h"
+#include "rank.h"
 
 #define NEG_MAX 1024                      // BSAREC_NEG_MAX: the largest N
 #define NEG_MAX_DRAWS (1 << 20)           // BSAREC_NEG_MAX_DRAWS: draws examined before a row fails
-#define NEG_SLOTS (4 * NEG_MAX)           // dedup table: <= N accepted + <= 1024 draws of one round, load <= 1/2
+#define NEG_SLOTS RANK_SLOTS              // dedup table (rank_hash): <= N accepted + <= 1024 draws of one round, load <= 1/2
 #define NEG_SEEN_LDS 2048                 // seen rows up to this length are staged in LDS (longer: searched in global memory)
 
-static_assert((NEG_SLOTS & (NEG_SLOTS - 1)) == 0 && NEG_SLOTS == 4096, "sampled_rank: slot hash takes the top 12 bits");
+static_assert(NEG_SLOTS >= 4 * NEG_MAX, "sampled_rank: the dedup table's load");
 static_assert(NEG_MAX_DRAWS % (ROW_THREADS * 4) == 0 && NEG_MAX_DRAWS % (ROW_THREADS * 2) == 0, "sampled_rank: whole rounds");
 
 // smallest i in [0, V) with cum[i] > r, or V if there is none
@@ -57,7 +57,7 @@ sampled_rank_kernel(const float* __restrict__ h, long ldh, const float* __restri
     __shared__ float sc[NEG_MAX + 1];
     __shared__ unsigned wsum[NW];
     __shared__ int nrank;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const long b = blockIdx.x;
     const int64_t u = users[b], a64 = answers[b];
     const bool ans_ok = a64 >= 1 && a64 < V;
@@ -98,7 +98,7 @@ sampled_rank_kernel(const float* __restrict__ h, long ldh, const float* __restri
             bool e = m < per && it >= 1 && it < V && it != a;
             if (e && ns > 0) e = seen_lds ? !neg_in_sorted(seen_s, ns, it) : !neg_in_sorted(indices + j0, ns, it);
             elig[m] = e;
-            slot[m] = ((unsigned)it * 2654435761u) >> 20;
+            slot[m] = rank_hash((unsigned)it);
             if (e) {
                 for (;;) {                               // at most 2 * NEG_MAX keys in NEG_SLOTS slots: an empty slot exists
                     const unsigned prev = atomicCAS(&key[slot[m]], 0u, (unsigned)it);
@@ -113,14 +113,8 @@ sampled_rank_kernel(const float* __restrict__ h, long ldh, const float* __restri
         unsigned nwin = 0u;
 #pragma unroll
         for (int m = 0; m < 4; ++m) { win[m] = elig[m] && val[slot[m]] == j * per + m + 1u; nwin += win[m] ? 1u : 0u; }
-        unsigned incl = nwin;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const unsigned y = __shfl_up(incl, off, 64); if (lane >= off) incl += y; }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        unsigned before = incl - nwin, total = 0u;
-#pragma unroll
-        for (int v = 0; v < NW; ++v) { const unsigned s = wsum[v]; if (v < wave) before += s; total += s; }
+        unsigned total;
+        const unsigned before = rank_scan(wsum, nwin, &total) - nwin;
         int pos = acc + (int)before;
 #pragma unroll
         for (int m = 0; m < 4; ++m)

@@ -8,53 +8,23 @@ evaluation branch scores, masks seen items and takes the top-20 on the GPU.
 """
 from __future__ import annotations
 
-import math
 import os
 from typing import Optional
 
 import numpy as np
 import torch
 
+from . import _lib as L
 from .data import DeviceBatches
 from .dp import PeerExchange, allreduce_sum_
 from .model import BSARecModel
+from .ranking import (REFERENCE_KS, FullRank, check_pool, cutoff_metrics, extra_cutoffs, metrics_post_fix, ndcg_at_k, recall_at_k,
+                      sampled_metrics, sampled_protocol, sampled_rank, sampling_tables, seen_csr, topk_seen)
 
 
 class _NullLogger:
     def info(self, *a, **k):
         pass
-
-
-def recall_at_k(hit: torch.Tensor, k: int) -> float:
-    """src/metrics.py:3-13 for single-target lists: hit is bool[n, K], K >= k."""
-    return float(hit[:, :k].any(1).double().mean().item())
-
-
-def ndcg_at_k(hit: torch.Tensor, k: int) -> float:
-    """src/metrics.py:15-31: one relevant item -> idcg = 1, dcg = 1/log2(rank + 2)."""
-    w = 1.0 / torch.log2(torch.arange(k, device=hit.device, dtype=torch.float64) + 2.0)
-    return float((hit[:, :k].double() * w).sum(1).mean().item())
-
-
-def extra_cutoffs(args) -> tuple:
-    """Evaluation cutoffs beyond the reference's 5 / 10 / 20 (``--extra_ks``; none by default)."""
-    return tuple(getattr(args, "extra_ks", None) or ())
-
-
-def sampled_protocol(args):
-    """Sampled-candidate evaluation settings (``--eval_negatives / --eval_sampler / --eval_seed``): (negatives per row,
-    sampler, seed); 0 negatives = the reference's full-catalogue ranking (the default)."""
-    n = int(getattr(args, "eval_negatives", 0) or 0)
-    sampler = getattr(args, "eval_sampler", None) or "uniform"
-    seed = getattr(args, "eval_seed", None)
-    return n, sampler, int(getattr(args, "seed", 0) if seed is None else seed)
-
-
-def sampled_metrics(ranks, k: int):
-    """HR@k and NDCG@k of sampled evaluation from the answers' ranks among their candidates (0 = first)."""
-    r = np.asarray(ranks, dtype=np.int64)
-    hit = r < k
-    return float(hit.mean()), float(np.where(hit, 1.0 / np.log2(r.astype(np.float64) + 2.0), 0.0).mean())
 
 
 def graph_sizes(k: int):
@@ -125,7 +95,7 @@ class Trainer:
         self.exchange = os.environ.get("BSAREC_EXCHANGE", exchange)     # "auto" | "rccl" | "p2p" (data parallel only)
         self.use_graph = use_graph                       # data parallel: two graphs around the eager all-reduce
         self._graphs = {}
-        self._seen_cache = {}
+        self._full_rank = FullRank("topk_full: unsupported shape B={B} V={V} d={d} k={k}")
         self._sync_replicas()
         self._setup_exchange()
 
@@ -256,20 +226,9 @@ class Trainer:
         pred = torch.as_tensor(pred_list, device=self.device)
         if extra and pred.shape[1] < max(extra):
             raise ValueError(f"get_full_sort_score: lists of {pred.shape[1]} items, extra cutoffs up to {max(extra)}")
-        hit = pred == ans
-        recall = [recall_at_k(hit, k) for k in (5, 10, 15, 20)]
-        ndcg = [ndcg_at_k(hit, k) for k in (5, 10, 15, 20)]
-        post_fix = {
-            "Epoch": epoch,
-            "HR@5": '{:.4f}'.format(recall[0]), "NDCG@5": '{:.4f}'.format(ndcg[0]),
-            "HR@10": '{:.4f}'.format(recall[1]), "NDCG@10": '{:.4f}'.format(ndcg[1]),
-            "HR@20": '{:.4f}'.format(recall[3]), "NDCG@20": '{:.4f}'.format(ndcg[3]),
-        }
-        scores = [recall[0], ndcg[0], recall[1], ndcg[1], recall[3], ndcg[3]]
-        for k in extra:
-            hr, nd = recall_at_k(hit, k), ndcg_at_k(hit, k)
-            post_fix[f"HR@{k}"], post_fix[f"NDCG@{k}"] = '{:.4f}'.format(hr), '{:.4f}'.format(nd)
-            scores += [hr, nd]
+        ks = REFERENCE_KS + extra
+        scores = cutoff_metrics(ks, hit=pred == ans)
+        post_fix = metrics_post_fix(epoch, ks, scores)
         self.logger.info(post_fix)
         return scores, str(post_fix)
 
@@ -284,13 +243,9 @@ class Trainer:
         r = torch.as_tensor(ranks).cpu().numpy()
         if r.size and r.min() < 0:
             raise ValueError(f"get_sampled_score: {int((r < 0).sum())} rows without {n} sampled negatives")
-        post_fix = {"Epoch": epoch}
-        scores = []
-        for k in (5, 10, 20) + extra:
-            hr, nd = sampled_metrics(r, k)
-            post_fix[f"HR@{k}"], post_fix[f"NDCG@{k}"] = '{:.4f}'.format(hr), '{:.4f}'.format(nd)
-            scores += [hr, nd]
-        post_fix["Protocol"] = f"{sampler}-{n}"
+        ks = REFERENCE_KS + extra
+        scores = cutoff_metrics(ks, ranks=r)
+        post_fix = metrics_post_fix(epoch, ks, scores, protocol=f"{sampler}-{n}")
         self.logger.info(post_fix)
         return scores, str(post_fix)
 
@@ -317,7 +272,6 @@ class Trainer:
         m._run_loss(plan, ans)
         m._run_backward(plan)
         self._exchange_and_adam()
-        from . import _lib as L
         return plan.view(L.BUF_LOSS, 0, (1,))[0]
 
     def _allreduce_param_grads(self):
@@ -637,49 +591,21 @@ class Trainer:
         last position (HIP), then ONE launch that sets the seen items' scores to 0 -- not -inf -- from the device CSR and
         takes the k best ids in descending score order (``bsarec_topk_seen``; no host round trip, no torch.topk).
         1 <= k <= BSAREC_TOPK_MAX (1024) and k <= item_size; equal scores go to the smaller id, NaN ranks above +inf."""
-        from . import _lib as L
         scores = self.model.full_logits(input_ids).clone()           # a copy: the plan's logits buffer stays intact
-        indptr, indices = self._seen_csr()
         users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        pred = torch.empty(scores.shape[0], k, dtype=torch.int64, device=self.device)
-        L.check(L.load().bsarec_topk_seen(scores.data_ptr(), scores.stride(0), scores.shape[0], scores.shape[1], users.data_ptr(),
-                                          indptr.data_ptr(), indices.data_ptr(), k, pred.data_ptr(), None,
-                                          torch.cuda.current_stream(self.device).cuda_stream), "bsarec_topk_seen")
+        pred = topk_seen(scores, k, users, seen_csr(self.args.train_matrix, self.device))
         return (pred, scores) if return_scores else pred
 
     def topk_full(self, user_ids, input_ids, k: int = 20, return_scores: bool = False):
         """topk_after_seen without the B x V score matrix (``--eval_full_rank fused``): ``bsarec_topk_full`` scores every item
         from the last position's hidden state on the fly and returns the same ids (and, with ``return_scores``, the same
         fp32 scores, 0 for seen items) in the same order.  Working memory: a cached workspace of O(B (k + candidates))."""
-        from . import _lib as L
         V = int(self.args.item_size)
         if not 1 <= k <= min(L.TOPK_MAX, V):
             raise ValueError(f"topk_full: k = {k}, expected 1..{min(L.TOPK_MAX, V)}")
-        h = self.model.last_hidden(input_ids)
-        if h.dtype != torch.float32 or h.stride(1) != 1 or h.data_ptr() % 16 or h.stride(0) % 4:
-            h = h.float().contiguous()
-        E = self.model.item_embeddings.weight.detach()
-        if E.dtype != torch.float32 or not E.is_contiguous() or E.data_ptr() % 16:
-            E = E.float().contiguous().clone()
-        B, d = h.shape
-        indptr, indices = self._seen_csr()
         users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        lib = L.load()
-        key = (B, V, d, k)
-        ws = getattr(self, "_full_rank_ws", {}).get(key)
-        if ws is None:
-            nbytes = lib.bsarec_topk_full_workspace_bytes(B, V, d, k, 0)
-            if nbytes < 0:
-                raise ValueError(f"topk_full: unsupported shape B={B} V={V} d={d} k={k}")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._full_rank_ws = {key: ws}
-        pred = torch.empty(B, k, dtype=torch.int64, device=self.device)
-        val = torch.empty(B, k, dtype=torch.float32, device=self.device) if return_scores else None
-        L.check(lib.bsarec_topk_full(h.data_ptr(), h.stride(0), E.data_ptr(), B, V, d, users.data_ptr(), indptr.data_ptr(),
-                                     indices.data_ptr(), k, 0, ws.data_ptr(), ws.numel(), pred.data_ptr(),
-                                     val.data_ptr() if val is not None else None,
-                                     torch.cuda.current_stream(self.device).cuda_stream), "bsarec_topk_full")
-        return (pred, val) if return_scores else pred
+        return self._full_rank(self.model.last_hidden(input_ids), self.model.item_embeddings.weight.detach(), k, users,
+                               seen_csr(self.args.train_matrix, self.device), values=return_scores)
 
     def sampled_ranks(self, user_ids, input_ids, answers, return_candidates: bool = False, tag: int = 1):
         """Sampled-candidate evaluation of one batch: each answer against args.eval_negatives = N items the user has not seen,
@@ -687,95 +613,23 @@ class Trainer:
         the Philox stream of (user, tag, args.eval_seed) -- ``bsarec_sampled_rank``, one launch after the eval forward.
         Returns the int32 ranks [B] (ties count against the model); with ``return_candidates`` also the candidates
         [B, N + 1] (answer first) and their scores.  Raises ValueError when a row has fewer than N eligible items."""
-        from . import _lib as L
         n, sampler, seed = sampled_protocol(self.args)
         if not 1 <= n <= L.NEG_MAX:
             raise ValueError(f"sampled_ranks: eval_negatives = {n}, expected 1..{L.NEG_MAX}")
         V = int(self.args.item_size)
-        tables = self._sampling_tables(sampler, V)
+        mat, pop = self.args.train_matrix, getattr(self.args, "item_popularity", None) if sampler == "popularity" else None
+        key = (id(mat), sampler, id(pop), V)                 # the host tables: cached per (seen matrix, sampler, popularity)
+        if getattr(self, "_neg_key", None) != key:
+            self._neg_tables, self._neg_key = sampling_tables(mat, sampler, pop, V, self.device), key
         users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
         ans = answers.to(device=self.device, dtype=torch.int64).contiguous()
-        self._check_pool(tables, users.cpu().numpy(), ans.cpu().numpy(), n, V)
-        h = self.model.last_hidden(input_ids)
-        if h.dtype != torch.float32 or h.stride(1) != 1:
-            h = h.float().contiguous()
-        E = self.model.item_embeddings.weight.detach()
-        if not E.is_contiguous() or E.data_ptr() % 16:
-            E = E.contiguous().clone()
-        B, d = h.shape
-        indptr, indices = self._seen_csr()
-        rank = torch.empty(B, dtype=torch.int32, device=self.device)
-        cand = torch.empty(B, n + 1, dtype=torch.int64, device=self.device) if return_candidates else None
-        score = torch.empty(B, n + 1, dtype=torch.float32, device=self.device) if return_candidates else None
-        cum = tables["cum"]
-        L.check(L.load().bsarec_sampled_rank(h.data_ptr(), h.stride(0), E.data_ptr(), B, V, d, users.data_ptr(), ans.data_ptr(),
-                                             indptr.data_ptr(), indices.data_ptr(), cum.data_ptr() if cum is not None else None,
-                                             n, seed & 0xFFFFFFFFFFFFFFFF, int(tag), rank.data_ptr(),
-                                             cand.data_ptr() if cand is not None else None,
-                                             score.data_ptr() if score is not None else None,
-                                             torch.cuda.current_stream(self.device).cuda_stream), "bsarec_sampled_rank")
+        check_pool(self._neg_tables, users.cpu().numpy(), ans.cpu().numpy(), n, V)
+        out = sampled_rank(self.model.last_hidden(input_ids), self.model.item_embeddings.weight.detach(), users, ans,
+                           seen_csr(self.args.train_matrix, self.device), n, seed, tag, cum=self._neg_tables["cum"],
+                           candidates=return_candidates)
+        rank = out[0] if return_candidates else out
         bad = torch.nonzero(rank < 0).view(-1)
         if bad.numel():
             raise ValueError(f"sampled_ranks: no {n} negatives within {L.NEG_MAX_DRAWS} draws for users "
                              f"{users[bad[:5]].tolist()}")
-        return (rank, cand, score) if return_candidates else rank
-
-    def _sampling_tables(self, sampler: str, V: int):
-        """Host tables of the eligibility check and the device cumulative popularity, cached per (seen matrix, sampler):
-        keys = u * V + item over the seen CSR (sorted), seen_w[u] = the drawable items in row u, pool = all drawable items."""
-        mat = self.args.train_matrix
-        pop = getattr(self.args, "item_popularity", None) if sampler == "popularity" else None
-        key = (id(mat), sampler, id(pop), V)
-        if getattr(self, "_neg_key", None) != key:
-            if sampler == "uniform":
-                w = np.ones(V, dtype=np.int64)
-            elif sampler == "popularity":
-                if pop is None:
-                    raise ValueError("sampled_ranks: the popularity sampler needs args.item_popularity (data.item_popularity)")
-                pop = np.asarray(pop, dtype=np.int64)
-                if pop.shape != (V,) or pop.min() < 0:
-                    raise ValueError(f"sampled_ranks: item_popularity must be {V} counts >= 0")
-                w = (pop > 0).astype(np.int64)
-            else:
-                raise ValueError(f"sampled_ranks: unknown sampler {sampler!r}")
-            w[0] = 0
-            csr = mat.tocsr()
-            csr.sum_duplicates()
-            ip, ix = csr.indptr.astype(np.int64), csr.indices.astype(np.int64)
-            rows = np.repeat(np.arange(len(ip) - 1, dtype=np.int64), np.diff(ip))
-            inr = (ix >= 0) & (ix < V)
-            seen_w = np.bincount(rows[inr], weights=w[ix[inr]], minlength=len(ip) - 1).astype(np.int64)
-            cum = None
-            if sampler == "popularity":
-                c = np.cumsum(np.where(np.arange(V) == 0, 0, pop))
-                cum = torch.as_tensor(c.astype(np.int64), device=self.device)
-            self._neg_tables = {"keys": rows * V + ix, "seen_w": seen_w, "w": w, "pool": int(w.sum()), "cum": cum}
-            self._neg_key = key
-        return self._neg_tables
-
-    @staticmethod
-    def _check_pool(t, users, answers, n: int, V: int):
-        """Every row must have >= n drawable items that are neither seen nor its answer (the kernel's -1 is only a backstop)."""
-        if ((answers < 1) | (answers >= V)).any():
-            i = int(np.nonzero((answers < 1) | (answers >= V))[0][0])
-            raise ValueError(f"sampled_ranks: answer {int(answers[i])} of user {int(users[i])} outside [1, {V})")
-        q = users * V + answers
-        pos = np.minimum(np.searchsorted(t["keys"], q), max(len(t["keys"]) - 1, 0))
-        a_seen = (t["keys"][pos] == q) if len(t["keys"]) else np.zeros(len(q), dtype=bool)
-        elig = t["pool"] - t["seen_w"][users] - np.where(a_seen, 0, t["w"][answers])
-        short = np.nonzero(elig < n)[0]
-        if short.size:
-            raise ValueError(f"sampled_ranks: {n} negatives requested, but users {users[short[:5]].tolist()} have only "
-                             f"{elig[short[:5]].tolist()} eligible items")
-
-    def _seen_csr(self):
-        """args.train_matrix (scipy CSR, as the reference builds it in src/dataset.py:126-168) on the device --
-        uploaded once per matrix."""
-        mat = self.args.train_matrix
-        key = id(mat)
-        if key not in self._seen_cache:
-            csr = mat.tocsr()
-            csr.sum_duplicates()
-            self._seen_cache = {key: (torch.as_tensor(csr.indptr.astype(np.int64), device=self.device),
-                                      torch.as_tensor(csr.indices.astype(np.int64), device=self.device))}
-        return self._seen_cache[key]
+        return out

@@ -134,38 +134,38 @@ def test_eval_flags_reject(bad):
 
 def _fake_trainer(**kw):
     import scipy.sparse as sp
-    from bsarec_amd.trainer import Trainer
+    from bsarec_amd.ranking import sampling_tables
     seen = [[1, 2, 3], [], [4, 5, 6, 7, 8, 9]]
     indptr = np.concatenate([[0], np.cumsum([len(s) for s in seen])])
     mat = sp.csr_matrix((np.ones(indptr[-1]), np.concatenate(seen).astype(np.int64), indptr), shape=(3, 12))
     args = types.SimpleNamespace(train_matrix=mat, item_size=12, seed=1, **kw)
     logs = []
     fake = types.SimpleNamespace(args=args, device=torch.device("cpu"), logger=types.SimpleNamespace(info=logs.append))
-    fake._sampling_tables = types.MethodType(Trainer._sampling_tables, fake)
+    fake._sampling_tables = lambda sampler, V: sampling_tables(mat, sampler, getattr(args, "item_popularity", None), V, fake.device)
     return fake, logs, seen
 
 
 def test_host_pool_check_names_the_short_users():
-    from bsarec_amd.trainer import Trainer
+    from bsarec_amd.ranking import check_pool
     fake, _, seen = _fake_trainer()
     t = fake._sampling_tables("uniform", 12)
     users, answers = np.array([0, 1, 2]), np.array([3, 10, 11])
     for u, a in zip(users, answers):                      # the host count agrees with the restatement's
         assert t["pool"] - t["seen_w"][u] - (0 if a in seen[u] else t["w"][a]) == R.eligible_count(a, seen[u], 12)
-    Trainer._check_pool(t, users, answers, 4, 12)          # eligible: 8, 10, 4
+    check_pool(t, users, answers, 4, 12)          # eligible: 8, 10, 4
     with pytest.raises(ValueError, match=r"users \[2\]"):
-        Trainer._check_pool(t, users, answers, 5, 12)
+        check_pool(t, users, answers, 5, 12)
     with pytest.raises(ValueError, match="outside"):
-        Trainer._check_pool(t, users, np.array([3, 0, 11]), 1, 12)
+        check_pool(t, users, np.array([3, 0, 11]), 1, 12)
     pop = np.array([0, 5, 0, 1, 1, 1, 1, 1, 1, 1, 0, 2])   # drawable: 1, 3..9, 11
     fake, _, _ = _fake_trainer(item_popularity=pop)
     t = fake._sampling_tables("popularity", 12)
     assert t["cum"].tolist() == np.cumsum(pop).tolist()
     for u, a in zip(users, answers):
         assert t["pool"] - t["seen_w"][u] - (0 if a in seen[u] else t["w"][a]) == R.eligible_count(a, seen[u], 12, pop)
-    Trainer._check_pool(t, users, answers, 2, 12)
+    check_pool(t, users, answers, 2, 12)
     with pytest.raises(ValueError, match=r"users \[2\]"):   # user 2: 1, 3 and 11 left, answer 11 -> 2
-        Trainer._check_pool(t, users, answers, 3, 12)
+        check_pool(t, users, answers, 3, 12)
 
 
 def test_get_sampled_score_positions_and_protocol_key():
