@@ -676,9 +676,10 @@ static int lpr_for(int d) { return d <= 64 ? 16 : (d <= 128 ? 32 : 64); }
          else if ((n) <= 128) { constexpr int BN = 128; __VA_ARGS__; } \
          else { constexpr int BN = 256; __VA_ARGS__; } } while (0)
 
-static size_t freq_smem(int L, int d, int cb, int nsrc) {
-    return (size_t)(rup(2 * L, 4) + (long)nsrc * cb * 2 * d + (long)nsrc * 8192) * 4;
+static size_t freq_smem(int L, int d, int cb, int nsrc, int kc = FREQ_KC) {
+    return (size_t)(rup(2 * L, 4) + (long)nsrc * cb * 2 * d + (long)nsrc * kc * 2048) * 4;
 }
+#define LDS_BYTES_MAX 163840     // LDS one workgroup can have on gfx950 (160 KiB per CU)
 
 template <int LPR>
 static int launch_freq_fwd(const float* X, const float* sb, const float* g, const float* be, float eps, DropP drop,
@@ -691,6 +692,11 @@ static int launch_freq_fwd(const float* X, const float* sb, const float* g, cons
 template <int LPR>
 static int launch_freq_bwd(const float* X, const float* dF, const float* dXin, const float* sb, const float* tw, int B, int L,
                            int d, int cb, float* dX, float* pbeta, hipStream_t s, const float* cw = nullptr, float* pcw = nullptr) {
+    // two spectra plus the four-bin exchange buffer outgrow the LDS once cutoff_bins * hidden > 6,144 - L / 2 (198,656 bytes at
+    // check_cfg's limit, cutoff_bins * hidden = 8192 with L = 256): one bin per pass there, 149,504 bytes at that limit
+    if (freq_smem(L, d, cb, 2) > LDS_BYTES_MAX)
+        return launch_lds<freq_bwd_kernel<LPR, 1>>(dim3(B), dim3(ROW_THREADS), freq_smem(L, d, cb, 2, 1), s, X, dF, dXin, sb, tw, L, d, cb,
+                                                   dX, pbeta, cw, pcw);
     return launch_lds<freq_bwd_kernel<LPR>>(dim3(B), dim3(ROW_THREADS), freq_smem(L, d, cb, 2), s, X, dF, dXin, sb, tw, L, d, cb, dX,
                                             pbeta, cw, pcw);
 }

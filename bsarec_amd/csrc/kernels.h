@@ -153,26 +153,28 @@ ln_bwd_kernel(const float* __restrict__ dY, LnBranch a, LnBranch f, float* __res
 //   forward : DSP = LN(Drop(low + beta^2 (x - low)) + x)                 src/model/bsarec.py:90-104
 //   backward: dX  = dXin + beta^2 dF + lowpass((1 - beta^2) dF),  dbeta = 2 beta sum dF (x - low)
 // =============================================================================================
+// KC bins per pass over the rows: FREQ_KC, or 1 where the backward's two spectra leave no room for the wider exchange buffer
+// (cutoff_bins * hidden near 8192; each bin's sums run in the same order either way)
 #define FREQ_KC 4
-template <int LPR, int NSRC, class Src>
+template <int LPR, int NSRC, int KC = FREQ_KC, class Src>
 __device__ __forceinline__ void dft_spectrum(const Src& src, int L, int d, int cb, const float* __restrict__ tw,
                                              float* __restrict__ spec /* [NSRC][cb][2][d] */,
                                              float* __restrict__ part /* [RPP][NSRC][KC][2][LPR*4] */) {
     constexpr int RPP = ROW_THREADS / LPR, W = LPR * 4;
     const int lr = threadIdx.x / LPR, lc = (threadIdx.x % LPR) << 2;
     const bool colok = lc < d;
-    for (int k0 = 0; k0 < cb; k0 += FREQ_KC) {
-        f32x4 re[NSRC][FREQ_KC], im[NSRC][FREQ_KC];
+    for (int k0 = 0; k0 < cb; k0 += KC) {
+        f32x4 re[NSRC][KC], im[NSRC][KC];
 #pragma unroll
         for (int s = 0; s < NSRC; ++s)
 #pragma unroll
-            for (int j = 0; j < FREQ_KC; ++j) { re[s][j] = f32x4{0, 0, 0, 0}; im[s][j] = f32x4{0, 0, 0, 0}; }
+            for (int j = 0; j < KC; ++j) { re[s][j] = f32x4{0, 0, 0, 0}; im[s][j] = f32x4{0, 0, 0, 0}; }
         for (int t = lr; t < L; t += RPP) {
             f32x4 x[NSRC];
 #pragma unroll
             for (int s = 0; s < NSRC; ++s) x[s] = colok ? src(s, t, lc) : f32x4{0, 0, 0, 0};
 #pragma unroll
-            for (int j = 0; j < FREQ_KC; ++j) {
+            for (int j = 0; j < KC; ++j) {
                 const int k = k0 + j;
                 if (k < cb) {
                     const int a = (int)((unsigned)(k * t) % (unsigned)L);
@@ -185,17 +187,17 @@ __device__ __forceinline__ void dft_spectrum(const Src& src, int L, int d, int c
 #pragma unroll
         for (int s = 0; s < NSRC; ++s)
 #pragma unroll
-            for (int j = 0; j < FREQ_KC; ++j) {
-                st4(part + (((lr * NSRC + s) * FREQ_KC + j) * 2 + 0) * W + lc, re[s][j]);
-                st4(part + (((lr * NSRC + s) * FREQ_KC + j) * 2 + 1) * W + lc, im[s][j]);
+            for (int j = 0; j < KC; ++j) {
+                st4(part + (((lr * NSRC + s) * KC + j) * 2 + 0) * W + lc, re[s][j]);
+                st4(part + (((lr * NSRC + s) * KC + j) * 2 + 1) * W + lc, im[s][j]);
             }
         __syncthreads();
-        for (int i = threadIdx.x; i < NSRC * FREQ_KC * 2 * W; i += ROW_THREADS) {
-            const int c = i % W, ri = (i / W) & 1, j = (i / (2 * W)) % FREQ_KC, s = i / (2 * W * FREQ_KC);
+        for (int i = threadIdx.x; i < NSRC * KC * 2 * W; i += ROW_THREADS) {
+            const int c = i % W, ri = (i / W) & 1, j = (i / (2 * W)) % KC, s = i / (2 * W * KC);
             if (c < d && k0 + j < cb) {
                 float acc = 0.f;
 #pragma unroll
-                for (int g = 0; g < RPP; ++g) acc += part[(((g * NSRC + s) * FREQ_KC + j) * 2 + ri) * W + c];
+                for (int g = 0; g < RPP; ++g) acc += part[(((g * NSRC + s) * KC + j) * 2 + ri) * W + c];
                 spec[((long)(s * cb + k0 + j) * 2 + ri) * d + c] = acc;
             }
         }
@@ -274,7 +276,7 @@ freq_fwd_kernel(const float* __restrict__ X, const float* __restrict__ sqrt_beta
     }
 }
 
-template <int LPR>
+template <int LPR, int KC = FREQ_KC>
 __global__ void __launch_bounds__(ROW_THREADS)
 freq_bwd_kernel(const float* __restrict__ X, const float* __restrict__ dF, const float* __restrict__ dXin,
                 const float* __restrict__ sqrt_beta, const float* __restrict__ twg, int L, int d, int cb,
@@ -300,7 +302,7 @@ freq_bwd_kernel(const float* __restrict__ X, const float* __restrict__ dF, const
         const f32x4 v = ld4((s == 0 ? X : dF) + base + (long)t * d + c);
         return s == 0 ? v : v * omb2;
     };
-    dft_spectrum<LPR, 2>(src, L, d, cb, tw, spec, part);
+    dft_spectrum<LPR, 2, KC>(src, L, d, cb, tw, spec, part);
     if (cw) {
         // sibling model FMLPRec: with D = spectrum of dF, dX = inverse transform of D conj(W) (the same inverse as the
         // forward's) and d(W)_k = (w_k / L) conj(X_k) D_k per sequence (w_k = 1 for DC / Nyquist, else 2)
