@@ -38,7 +38,9 @@ one GPU) -- the head rows above become, per rank:
 Evaluation (``topk`` / ``full_sort_scores``) ranks the owned rows for all Bg sequences and merges the ranks' lists.
 ``eval_full_rank`` (the single-GPU flag) picks how a rank gets its list: "dense" (default) materialises the partial logits
 [Bg, Vs]; "fused" calls ``bsarec_topk_full_range`` over the shard with its column base -- O(Bg (s + cap)) working memory, no
-score matrix, and under the sampled-softmax head no O(Bg Vs) buffer for the life of the object.
+score matrix, and under the sampled-softmax head no O(Bg Vs) buffer for the life of the object.  "rank" (``full_sort_scores``
+only: it produces no lists) exchanges no candidates at all: the answers' scores (``bsarec_answer_score_range``) and the counts of
+the owned items that stand before them (``bsarec_answer_rank_range``) are each summed over the ranks, 4 Bg bytes apiece.
 """
 from __future__ import annotations
 
@@ -51,7 +53,8 @@ import torch
 from . import _lib as L
 from .dp import PeerExchange, _as_tensor
 from .model import BSARecModel, train_head_of
-from .ranking import EVAL_FULL_RANK, REFERENCE_KS, FullRank, cutoff_metrics, eval_full_rank_of, metrics_post_fix, topk_seen
+from .ranking import (EVAL_FULL_RANK, REFERENCE_KS, FullRank, answer_rank, answer_score, cutoff_metrics, eval_full_rank_of,
+                      metrics_post_fix, topk_seen)
 
 
 class ShardedCatalogue:
@@ -370,32 +373,15 @@ class ShardedCatalogue:
         (``bsarec_topk_full_range`` over the owned rows: no score matrix); None: ``args.eval_full_rank``, else "dense".
         Returns (scores [B, k], item ids [B, k])."""
         import torch.distributed as dist
-        lib, enc, g = self.lib, self.encoder, self.group
-        B, Lq, d, W, Bg, n = self.B, self.Lq, self.d, self.W, self.Bg, self.n
-        fused = eval_full_rank_of(self.args, full_rank) == "fused"
-        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        assert tuple(ids.shape) == (B, Lq)
-        st = enc._stream()
-        if fused:                           # the gathered h_last only
-            self._gathered_h_buffer()
-        else:                               # sampled-softmax training: the full-catalogue buffers on the first dense evaluation
-            self._full_head_buffers()
-        self.px.barrier(st)
-        L.check(lib.bsarec_shard_gather_rows(ids.data_ptr(), n, C.byref(self._shards8), W, self.rows_per, self.V, d,
-                                             enc._arena.data_ptr(), self.local_ids.data_ptr(), st), "bsarec_shard_gather_rows")
-        was_training = enc.training
-        enc.eval()
-        plan = enc._run_forward(self.local_ids, train=False, new_step=False)
-        enc.train(was_training)
-        h_last = plan.view(L.BUF_LAYER_OUT, self.args.num_hidden_layers, (B, Lq, d))[:, Lq - 1, :].float().contiguous()
-        dist.all_gather(list(self.h_all.view(W, B, d).unbind(0)), h_last, group=g)
-        seen_all = None
-        if seen is not None:
-            sl = seen.to(device=self.device, dtype=torch.int64).contiguous()
-            S = sl.shape[1]
-            seen_all = torch.empty(W, B, S, dtype=torch.int64, device=self.device)
-            dist.all_gather(list(seen_all.unbind(0)), sl, group=g)
+        mode = eval_full_rank_of(self.args, full_rank)
+        if mode == "rank":                  # before any collective
+            raise ValueError("topk: eval_full_rank = 'rank' produces no lists; use full_sort_scores(full_rank='rank')")
+        fused = mode == "fused"
+        lib, g, st = self.lib, self.group, self.encoder._stream()
+        B, d, W, Bg = self.B, self.d, self.W, self.Bg
+        seen_all = self._gather_h_and_seen(input_ids, seen, dense=not fused)
         if not fused:
+            S = seen_all.shape[2] if seen_all is not None else 0
             L.check(lib.bsarec_shard_logits(self.h_all.data_ptr(), d, Bg, self.E.data_ptr(), self.Vs, d, self.logits.data_ptr(),
                                             self.ld, st), "bsarec_shard_logits")
             scores = self.logits[:, :self.Vs]
@@ -430,13 +416,71 @@ class ShardedCatalogue:
         r0 = self.rank * B
         return top_v[r0:r0 + B].clone(), top_i[r0:r0 + B].clone()
 
+    def _gather_h_and_seen(self, input_ids, seen, dense: bool):
+        """The evaluation forward of this rank's B sequences and the all-gathers every evaluation path starts with: h_last of
+        all Bg sequences into ``h_all``; returns the gathered ``seen`` int64 [W, B, S], or None.  ``dense``: the caller needs
+        the partial-logits buffer too."""
+        import torch.distributed as dist
+        lib, enc, g = self.lib, self.encoder, self.group
+        B, Lq, d, W, n = self.B, self.Lq, self.d, self.W, self.n
+        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
+        assert tuple(ids.shape) == (B, Lq)
+        st = enc._stream()
+        if dense:                           # sampled-softmax training: the full-catalogue buffers on the first dense evaluation
+            self._full_head_buffers()
+        else:                               # the gathered h_last only
+            self._gathered_h_buffer()
+        self.px.barrier(st)
+        L.check(lib.bsarec_shard_gather_rows(ids.data_ptr(), n, C.byref(self._shards8), W, self.rows_per, self.V, d,
+                                             enc._arena.data_ptr(), self.local_ids.data_ptr(), st), "bsarec_shard_gather_rows")
+        was_training = enc.training
+        enc.eval()
+        plan = enc._run_forward(self.local_ids, train=False, new_step=False)
+        enc.train(was_training)
+        h_last = plan.view(L.BUF_LAYER_OUT, self.args.num_hidden_layers, (B, Lq, d))[:, Lq - 1, :].float().contiguous()
+        dist.all_gather(list(self.h_all.view(W, B, d).unbind(0)), h_last, group=g)
+        if seen is None:
+            return None
+        sl = seen.to(device=self.device, dtype=torch.int64).contiguous()
+        seen_all = torch.empty(W, B, sl.shape[1], dtype=torch.int64, device=self.device)
+        dist.all_gather(list(seen_all.unbind(0)), sl, group=g)
+        return seen_all
+
+    def _seen_rows(self, seen_all):
+        """``seen_all`` int64 [W, B, S] as (users, csr) of S entries per row; -1 pads and other ranks' items lie outside the range."""
+        if seen_all is None:
+            return None, None
+        return (torch.arange(self.Bg, dtype=torch.int64, device=self.device),
+                (torch.arange(self.Bg + 1, dtype=torch.int64, device=self.device) * seen_all.shape[2], seen_all))
+
+    @torch.no_grad()
+    def answer_ranks(self, input_ids, answers, seen=None):
+        """The full-catalogue ranks (int32 [B], 0 = first; -1: an answer outside [0, V)) of this rank's B answers over the
+        SHARDED table, in the order of :meth:`topk`, without lists: every rank scores the answers it owns into a zeroed [Bg]
+        buffer (all-reduce SUM: x + 0 = x), counts the owned items that stand before each of the Bg answers, and the counts
+        are all-reduced.  Two exchanges of 4 Bg bytes after the gathers of h_last, the answers and ``seen``."""
+        import torch.distributed as dist
+        g, B, W, Bg = self.group, self.B, self.W, self.Bg
+        seen_all = self._gather_h_and_seen(input_ids, seen, dense=False)
+        dist.all_gather(list(self.ans_all.view(W, B).unbind(0)), answers.to(device=self.device, dtype=torch.int64).contiguous(),
+                        group=g)
+        users, csr = self._seen_rows(seen_all)
+        score = torch.zeros(Bg, dtype=torch.float32, device=self.device)
+        rank = torch.zeros(Bg, dtype=torch.int32, device=self.device)
+        if self.Vs:
+            answer_score(self.h_all, self.E[:self.Vs], self.ans_all, users, csr, base=self.lo, out=score)
+        dist.all_reduce(score, op=dist.ReduceOp.SUM, group=g)
+        if self.Vs:
+            rank = answer_rank(self.h_all, self.E[:self.Vs], self.ans_all, users, csr, base=self.lo, answer_score=score)
+        dist.all_reduce(rank, op=dist.ReduceOp.SUM, group=g)
+        rank[(self.ans_all < 0) | (self.ans_all >= self.V)] = -1      # (every owner said -1, or nobody owns the id)
+        r0 = self.rank * B
+        return rank[r0:r0 + B].clone()
+
     def _topk_range(self, seen_all, k):
         """k best owned items of all Bg rows of ``h_all`` (``FullRank`` over the shard, column base ``lo``): (scores, GLOBAL ids).
         ``seen_all`` int64 [W, B, S] or None: a CSR of S entries per row; -1 pads and other ranks' items lie outside the range."""
-        users = csr = None
-        if seen_all is not None:
-            users = torch.arange(self.Bg, dtype=torch.int64, device=self.device)
-            csr = (torch.arange(self.Bg + 1, dtype=torch.int64, device=self.device) * seen_all.shape[2], seen_all)
+        users, csr = self._seen_rows(seen_all)
         idx, val = self._full_rank(self.h_all, self.E[:self.Vs], k, users, csr, base=self.lo, values=True)
         return val, idx
 
@@ -446,16 +490,24 @@ class ShardedCatalogue:
         table: ``batches`` yields this rank's (input_ids [B, L], answers [B], seen [B, S] or None) per step (every rank the
         same number of steps); the top-max(k, *extra_ks) of each sequence comes from :meth:`topk`, hits and DCG sums are
         all-reduced, so every rank returns the metrics of the GLOBAL evaluation set: ([HR@5, NDCG@5, HR@10, NDCG@10, HR@20,
-        NDCG@20] + [HR@e, NDCG@e for e in extra_ks], str).  ``full_rank``: as in :meth:`topk`."""
+        NDCG@20] + [HR@e, NDCG@e for e in extra_ks], str).  ``full_rank``: as in :meth:`topk`, or "rank": the same values from
+        :meth:`answer_ranks` -- no lists, no candidate gathers, no merge, and cutoffs of any depth."""
         import torch.distributed as dist
         ks = REFERENCE_KS + tuple(extra_ks or ())
         depth = max((k,) + ks[3:])
         sums = torch.zeros(2 * len(ks) + 1, dtype=torch.float64, device=self.device)
+        by_rank = eval_full_rank_of(self.args, full_rank) == "rank"
         for ids, answers, seen in batches:
-            _, top_i = self.topk(ids, k=depth, seen=seen, full_rank=full_rank)
-            hit = top_i == answers.to(device=self.device, dtype=torch.int64).view(-1, 1)
-            n = hit.shape[0]
-            sums[:-1] += torch.tensor(cutoff_metrics(ks, hit=hit), dtype=torch.float64, device=self.device) * n
+            if by_rank:                     # no lists: the answers' ranks (an answer outside the catalogue never hits)
+                r = self.answer_ranks(ids, answers, seen).cpu().numpy().astype(np.int64)
+                n = r.shape[0]
+                vals = cutoff_metrics(ks, ranks=np.where(r < 0, self.V, r))
+            else:
+                _, top_i = self.topk(ids, k=depth, seen=seen, full_rank=full_rank)
+                hit = top_i == answers.to(device=self.device, dtype=torch.int64).view(-1, 1)
+                n = hit.shape[0]
+                vals = cutoff_metrics(ks, hit=hit)
+            sums[:-1] += torch.tensor(vals, dtype=torch.float64, device=self.device) * n
             sums[-1] += n
         dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.group)
         vals = (sums[:-1] / sums[-1].clamp(min=1)).tolist()

@@ -13,6 +13,7 @@
 #include "rank.h"
 #include "sampled_rank.h"
 #include "full_rank.h"
+#include "answer_rank.h"
 #include "sampled_softmax.h"
 #include "lazy_adam.h"
 
@@ -1886,6 +1887,55 @@ extern "C" int bsarec_topk_full(const float* h, long ldh, const float* item_emb,
                                 long workspace_bytes, int64_t* out_idx, float* out_val, void* stream) {
     return bsarec_topk_full_range(h, ldh, item_emb, B, V, 0, d, users, indptr, indices, k, cand_cap, workspace, workspace_bytes,
                                   out_idx, out_val, stream);
+}
+
+// The answer's rank without a list (answer_rank.h): the per-row launch, then the count launch; no workspace.
+static int answer_rank_check(const float* h, long ldh, const float* E, int B, int V, long col_base, int d, const int64_t* users,
+                             const int64_t* indptr, const int64_t* indices, const int64_t* answers, const void* out) {
+    if (B < 1 || V < 1 || d < 4 || d > 256 || d % 4 != 0 || ldh < d) return -10;
+    if (col_base < 0 || col_base + V > 0x7fffffffL) return -10;
+    if (!h || !E || !answers || !out || (indptr && (!users || !indices))) return -10;
+    if ((uintptr_t)h % 16 != 0 || (uintptr_t)E % 16 != 0) return -10;
+    return 0;
+}
+
+extern "C" int bsarec_answer_rank_range(const float* h, long ldh, const float* item_rows, int B, int Vs, long col_base, int d,
+                                        const int64_t* users, const int64_t* indptr, const int64_t* indices, const int64_t* answers,
+                                        const float* answer_score, int32_t* rank_out, float* score_out, void* stream) {
+    RET(answer_rank_check(h, ldh, item_rows, B, Vs, col_base, d, users, indptr, indices, answers, rank_out));
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = (B + FR_ROWS - 1) / FR_ROWS, nblk = (Vs + FR_ITEMS - 1) / FR_ITEMS;
+    int groups = (1024 + tiles - 1) / tiles;                    // the filter's grid: about 1024 workgroups
+    if (groups > nblk) groups = nblk;
+    const size_t smem = (size_t)FR_ROWS * (d + 4) * sizeof(float);
+    static bool attr = false;
+    if (!attr) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(answer_rank_count_kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)FR_ROWS * 260 * sizeof(float)));
+        if (e != hipSuccess) return (int)e;
+        attr = true;
+    }
+    hipLaunchKernelGGL(answer_rank_row_kernel<false>, dim3(B), dim3(ROW_THREADS), 0, st, h, ldh, item_rows, Vs, col_base, d, users,
+                       indptr, indices, answers, answer_score, rank_out, score_out);
+    hipLaunchKernelGGL(answer_rank_count_kernel, dim3(tiles, groups), dim3(ROW_THREADS), smem, st, h, ldh, item_rows, B, Vs, col_base,
+                       d, users, indptr, indices, answers, answer_score, (const float*)score_out, rank_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_answer_rank(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* users,
+                                  const int64_t* indptr, const int64_t* indices, const int64_t* answers, int32_t* rank_out,
+                                  float* score_out, void* stream) {
+    return bsarec_answer_rank_range(h, ldh, item_emb, B, V, 0, d, users, indptr, indices, answers, nullptr, rank_out, score_out,
+                                    stream);
+}
+
+extern "C" int bsarec_answer_score_range(const float* h, long ldh, const float* item_rows, int B, int Vs, long col_base, int d,
+                                         const int64_t* users, const int64_t* indptr, const int64_t* indices,
+                                         const int64_t* answers, float* score_out, void* stream) {
+    RET(answer_rank_check(h, ldh, item_rows, B, Vs, col_base, d, users, indptr, indices, answers, score_out));
+    hipLaunchKernelGGL(answer_rank_row_kernel<true>, dim3(B), dim3(ROW_THREADS), 0, (hipStream_t)stream, h, ldh, item_rows, Vs,
+                       col_base, d, users, indptr, indices, answers, (const float*)nullptr, (int32_t*)nullptr, score_out);
+    return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------

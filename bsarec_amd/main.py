@@ -122,9 +122,11 @@ def parse_args(argv=None):
                    help="how the negatives are drawn: uniform over the catalogue (default) or by training-set popularity")
     p.add_argument("--eval_seed", default=argparse.SUPPRESS, type=seed_value, help="seed of the negative draws (default: --seed)")
     # not a reference flag: how the full ranking is computed -- dense (full_logits + bsarec_topk_seen, the default) or fused
-    # (bsarec_topk_full: no B x V score matrix, the same lists).  Absent unless given, as the --eval_* flags above
-    p.add_argument("--eval_full_rank", default=argparse.SUPPRESS, choices=("dense", "fused"),
-                   help="full-ranking path: dense score matrix + top-k (default) or fused scoring + top-k without the matrix")
+    # (bsarec_topk_full: no B x V score matrix, the same lists) or rank (bsarec_answer_rank: the answers' ranks without lists,
+    # the same six metrics plus MRR).  Absent unless given, as the --eval_* flags above
+    p.add_argument("--eval_full_rank", default=argparse.SUPPRESS, choices=("dense", "fused", "rank"),
+                   help="full-ranking path: dense score matrix + top-k (default), fused scoring + top-k without the matrix, or "
+                        "the answers' exact ranks without lists (adds MRR)")
     # not reference flags: the sampled-softmax training head (the answer against N candidates shared by the batch, logQ-corrected)
     # instead of the full-catalogue cross-entropy.  Absent unless given (argparse.SUPPRESS), as the --eval_* flags are
     p.add_argument("--train_negatives", default=argparse.SUPPRESS, type=train_negatives_count,

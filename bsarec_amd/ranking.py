@@ -5,7 +5,7 @@ import torch
 
 from . import _lib as L
 
-EVAL_FULL_RANK = ("dense", "fused")
+EVAL_FULL_RANK = ("dense", "fused", "rank")
 REFERENCE_KS = (5, 10, 20)                      # the reference's cutoffs: the first six returned values
 _seen_cache: dict = {}                          # seen_csr: the one uploaded matrix
 
@@ -129,6 +129,51 @@ class FullRank:
                                                 *map(_ptr, csr or (None, None)), k, 0, ws.data_ptr(), ws.numel(), idx.data_ptr(),
                                                 _ptr(val), torch.cuda.current_stream(h.device).cuda_stream), "bsarec_topk_full_range")
         return (idx, val) if values else idx
+
+
+def _answer_operands(h, E, answers, users, csr):
+    h, E = rank_operand(h), rank_operand(E.contiguous())
+    ans = answers.to(device=h.device, dtype=torch.int64).contiguous()
+    if ans.shape != (h.shape[0],):
+        raise ValueError(f"answer_rank: {tuple(ans.shape)} answers for {h.shape[0]} rows")
+    return h, E, ans, (_ptr(users), *map(_ptr, csr or (None, None)))
+
+
+def answer_rank(h, E, answers, users=None, csr=None, base: int = 0, answer_score=None, scores: bool = False):
+    """``bsarec_answer_rank_range``: for every row of ``h`` [B, d] the number of items of ``E`` [V, d] -- rows [base, base + V)
+    of the catalogue -- that stand before its answer in ``topk_seen``'s order: over the whole catalogue, the answer's index in
+    the k = V list, at any depth and without a list.  ``answers`` and the ids of ``csr`` are global; ``answer_score`` (fp32 [B])
+    is taken as the answer's score when given (the answer may then belong to another range).  int32 ranks [B] (-1: no valid
+    answer); ``scores``: + the answers' fp32 scores (0 for a seen answer, NaN with rank -1)."""
+    h, E, ans, seen = _answer_operands(h, E, answers, users, csr)
+    (B, d), V = h.shape, E.shape[0]
+    if answer_score is not None:
+        answer_score = answer_score.to(device=h.device, dtype=torch.float32).contiguous()
+    rank = torch.empty(B, dtype=torch.int32, device=h.device)
+    val = torch.empty(B, dtype=torch.float32, device=h.device)      # (always: the count launch reads its target there)
+    L.check(L.load().bsarec_answer_rank_range(h.data_ptr(), h.stride(0), E.data_ptr(), B, V, base, d, *seen, ans.data_ptr(),
+                                              _ptr(answer_score), rank.data_ptr(), val.data_ptr(),
+                                              torch.cuda.current_stream(h.device).cuda_stream), "bsarec_answer_rank_range")
+    return (rank, val) if scores else rank
+
+
+def answer_score(h, E, answers, users=None, csr=None, base: int = 0, out=None):
+    """``bsarec_answer_score_range``: ``out[b]`` (fp32 [B]; default: zeros) = the effective score of ``answers[b]`` for the rows
+    whose answer lies in [base, base + V); the other rows keep their value.  Summed over a catalogue's ranges: the score."""
+    h, E, ans, seen = _answer_operands(h, E, answers, users, csr)
+    (B, d), V = h.shape, E.shape[0]
+    if out is None:
+        out = torch.zeros(B, dtype=torch.float32, device=h.device)
+    L.check(L.load().bsarec_answer_score_range(h.data_ptr(), h.stride(0), E.data_ptr(), B, V, base, d, *seen, ans.data_ptr(),
+                                               out.data_ptr(), torch.cuda.current_stream(h.device).cuda_stream),
+            "bsarec_answer_score_range")
+    return out
+
+
+def mrr(ranks) -> float:
+    """Mean reciprocal rank of the answers' ranks (0 = first)."""
+    r = np.asarray(ranks, dtype=np.float64)
+    return float((1.0 / (r + 1.0)).mean())
 
 
 def sampled_rank(h, E, users, answers, csr, n: int, seed: int, tag: int, cum=None, candidates: bool = False):

@@ -18,8 +18,8 @@ from . import _lib as L
 from .data import DeviceBatches
 from .dp import PeerExchange, allreduce_sum_
 from .model import BSARecModel
-from .ranking import (REFERENCE_KS, FullRank, check_pool, cutoff_metrics, extra_cutoffs, metrics_post_fix, ndcg_at_k, recall_at_k,
-                      sampled_metrics, sampled_protocol, sampled_rank, sampling_tables, seen_csr, topk_seen)
+from .ranking import (REFERENCE_KS, FullRank, answer_rank, check_pool, cutoff_metrics, extra_cutoffs, metrics_post_fix, mrr,
+                      ndcg_at_k, recall_at_k, sampled_metrics, sampled_protocol, sampled_rank, sampling_tables, seen_csr, topk_seen)
 
 
 class _NullLogger:
@@ -246,6 +246,26 @@ class Trainer:
         ks = REFERENCE_KS + extra
         scores = cutoff_metrics(ks, ranks=r)
         post_fix = metrics_post_fix(epoch, ks, scores, protocol=f"{sampler}-{n}")
+        self.logger.info(post_fix)
+        return scores, str(post_fix)
+
+    def get_rank_score(self, epoch, ranks, extra_ks=None):
+        """Metrics of ``eval_full_rank = "rank"`` from the answers' full-catalogue ranks (``answer_ranks``): the reference's six
+        positions (HR / NDCG @ 5, 10, 20: the values of ``get_full_sort_score``, so early stopping reads the same position),
+        then HR@k, NDCG@k of every extra cutoff -- any k <= item_size, there is no list to be deep enough --, then MRR = the
+        mean of 1 / (rank + 1) as one more value; the log line gains the key "MRR" at its end."""
+        extra = extra_cutoffs(self.args) if extra_ks is None else tuple(extra_ks)
+        V = int(self.args.item_size)
+        if extra and not 1 <= min(extra) <= max(extra) <= V:
+            raise ValueError(f"get_rank_score: extra cutoffs {extra} outside 1 .. item_size = {V}")
+        r = torch.as_tensor(ranks).cpu().numpy()
+        if r.size and r.min() < 0:
+            raise ValueError(f"get_rank_score: {int((r < 0).sum())} answers outside [0, {V})")
+        ks = REFERENCE_KS + extra
+        scores = cutoff_metrics(ks, ranks=r)
+        post_fix = metrics_post_fix(epoch, ks, scores)
+        scores.append(mrr(r))
+        post_fix["MRR"] = '{:.4f}'.format(scores[-1])
         self.logger.info(post_fix)
         return scores, str(post_fix)
 
@@ -574,6 +594,13 @@ class Trainer:
                 user_ids, input_ids, answers, _, _ = batch
                 ranks.append(self.sampled_ranks(user_ids, input_ids, answers, tag=getattr(self, "_eval_tag", 1)))
             return self.get_sampled_score(epoch, torch.cat(ranks))
+        if getattr(self.args, "eval_full_rank", "dense") == "rank":      # opt-in: the answers' ranks, no lists
+            ranks = []
+            for batch in dataloader:
+                batch = tuple(t.to(self.device, non_blocking=True) for t in batch)
+                user_ids, input_ids, answers, _, _ = batch
+                ranks.append(self.answer_ranks(user_ids, input_ids, answers))
+            return self.get_rank_score(epoch, torch.cat(ranks))
         preds, answers_all = [], []
         depth = max((20,) + extra_cutoffs(self.args))
         for batch in dataloader:
@@ -606,6 +633,15 @@ class Trainer:
         users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
         return self._full_rank(self.model.last_hidden(input_ids), self.model.item_embeddings.weight.detach(), k, users,
                                seen_csr(self.args.train_matrix, self.device), values=return_scores)
+
+    def answer_ranks(self, user_ids, input_ids, answers, return_scores: bool = False):
+        """The place of every answer in the full-catalogue order of ``topk_after_seen`` / ``topk_full`` (``--eval_full_rank
+        rank``): ``bsarec_answer_rank`` counts the items that stand before the answer while it scores them -- no score matrix,
+        no list, no depth limit, no working memory.  int32 ranks [B], 0 = first (-1: an answer outside [0, item_size)); with
+        ``return_scores`` also the answers' fp32 scores (0 for a seen answer)."""
+        users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
+        return answer_rank(self.model.last_hidden(input_ids), self.model.item_embeddings.weight.detach(), answers, users,
+                           seen_csr(self.args.train_matrix, self.device), scores=return_scores)
 
     def sampled_ranks(self, user_ids, input_ids, answers, return_candidates: bool = False, tag: int = 1):
         """Sampled-candidate evaluation of one batch: each answer against args.eval_negatives = N items the user has not seen,

@@ -420,6 +420,39 @@ int bsarec_topk_full_range(const float *h, long ldh, const float *item_rows, int
                            const int64_t *users, const int64_t *indptr, const int64_t *indices, int k, int cand_cap,
                            void *workspace, long workspace_bytes, int64_t *out_idx, float *out_val, void *stream);
 
+/* The answer's exact place in the full-catalogue order -- the one integer per row that HR@k, NDCG@k and MRR are functions
+ * of -- without a score matrix, a threshold, a candidate list or a sort, and at any depth (no BSAREC_TOPK_MAX).
+ *   Scores: s(b, j) is the fmaf chain of bsarec_topk_full.  The effective score e(b, j) is +0.0 when GLOBAL id j occurs in CSR
+ *   row users[b] (indptr == NULL: nothing is seen), else s(b, j).  CSR entries are global ids as in bsarec_topk_full_range:
+ *   entries outside the range are ignored, rows need not be sorted, may repeat an id (a distinct item counts once) and may
+ *   be of any length.
+ *   Rank: with a = answers[b] and t = e(b, a), rank_out[b] = the number of items j != a of the range that stand before (t, a)
+ *   in bsarec_topk_seen's total order: topk key of e(b, j) above that of t, or equal keys and global j < a (NaN above +inf,
+ *   -0 = +0, column 0 like any other).  An answer that is itself seen has t = +0.0.  Over the whole catalogue rank_out[b] is
+ *   the index of a in the list bsarec_topk_seen would give with k = V, for every input: there is no approximate mode.
+ *   bsarec_answer_rank: the col_base = 0, answer_score = NULL case.  score_out[b] (nullable) = t.  A row whose answer is
+ *   outside [0, V) gets rank -1 and score NaN.
+ *   bsarec_answer_rank_range, answer_score == NULL: the same over [col_base, col_base + Vs).  answer_score given:
+ *   t = answer_score[b] as it is, and a -- any id in [0, 2^31), in this range or another -- serves the tie order and the j != a
+ *   exclusion only (a outside [0, 2^31): -1 and NaN).  So the ranks of the contiguous ranges of a catalogue add up to the rank
+ *   in the whole catalogue.
+ *   bsarec_answer_score_range: score_out[b] = e(b, a) for the rows whose answer lies in the range; the other rows are left
+ *   untouched.  Zero the array and sum it over the ranges: the sum is t (x + 0 = x; -0 and +0 share a key).
+ *   Execution: two launches on `stream` (one for the score call): no host synchronisation, no allocation, no workspace;
+ *   capturable; integer adds only, so bit-deterministic.
+ *   Limits (else < 0 before any HIP call): B >= 1, 1 <= V, Vs < 2^31, col_base >= 0, col_base + Vs <= 2^31 - 1, 4 <= d <= 256,
+ *   d % 4 == 0, ldh >= d, h and the item rows 16-byte aligned and non-null, answers and rank_out non-null (score_out for the
+ *   score call), users and indices non-null when indptr is given. */
+int bsarec_answer_rank(const float *h, long ldh, const float *item_emb, int B, int V, int d, const int64_t *users,
+                       const int64_t *indptr, const int64_t *indices, const int64_t *answers, int32_t *rank_out,
+                       float *score_out, void *stream);
+int bsarec_answer_rank_range(const float *h, long ldh, const float *item_rows, int B, int Vs, long col_base, int d,
+                             const int64_t *users, const int64_t *indptr, const int64_t *indices, const int64_t *answers,
+                             const float *answer_score, int32_t *rank_out, float *score_out, void *stream);
+int bsarec_answer_score_range(const float *h, long ldh, const float *item_rows, int B, int Vs, long col_base, int d,
+                              const int64_t *users, const int64_t *indptr, const int64_t *indices, const int64_t *answers,
+                              float *score_out, void *stream);
+
 /* Stand-alone FrequencyLayer (src/model/bsarec.py:90-104) for per-op parity tests:
  * y = LN(Drop(low + beta^2 (x - low)) + x); backward given dy. */
 int bsarec_freq_layer_fwd(const float *x, const float *sqrt_beta, const float *ln_w, const float *ln_b,
