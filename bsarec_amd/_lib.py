@@ -187,6 +187,11 @@ EXPORTS = {
                                  [C.c_void_p] * 8),
     "bsarec_answer_score_range": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_int] +
                                   [C.c_void_p] * 6),
+    "bsarec_info_nce_workspace_bytes": (C.c_long, [C.c_int] * 3),
+    "bsarec_info_nce_fwd": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_float, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
+    "bsarec_info_nce_bwd": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_float, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

@@ -14,6 +14,7 @@
 #include "sampled_rank.h"
 #include "full_rank.h"
 #include "answer_rank.h"
+#include "info_nce.h"
 #include "sampled_softmax.h"
 #include "lazy_adam.h"
 
@@ -1935,6 +1936,63 @@ extern "C" int bsarec_answer_score_range(const float* h, long ldh, const float* 
     RET(answer_rank_check(h, ldh, item_rows, B, Vs, col_base, d, users, indptr, indices, answers, score_out));
     hipLaunchKernelGGL(answer_rank_row_kernel<true>, dim3(B), dim3(ROW_THREADS), 0, (hipStream_t)stream, h, ldh, item_rows, Vs,
                        col_base, d, users, indptr, indices, answers, (const float*)nullptr, (int32_t*)nullptr, score_out);
+    return (int)hipGetLastError();
+}
+
+// DuoRec's contrastive head (info_nce.h): plan-less, everything on the caller's stream, no allocation.
+static int info_nce_shape_check(int B, int d, int sim) {
+    if (B < 1 || B > 4096 || d < 4 || d > 256 || d % 4 != 0 || (sim != 0 && sim != 1)) return -10;
+    return 0;
+}
+
+extern "C" long bsarec_info_nce_workspace_bytes(int B, int d, int sim) {
+    if (info_nce_shape_check(B, d, sim)) return -10;
+    return nce_workspace_floats(B, d) * (long)sizeof(float);
+}
+
+static int info_nce_params(NceP& P, const float* z_i, long ld_i, const float* z_j, long ld_j, int B, int d, float inv_tau, int sim,
+                           void* workspace, long workspace_bytes) {
+    RET(info_nce_shape_check(B, d, sim));
+    if (ld_i < d || ld_j < d || ld_i % 4 != 0 || ld_j % 4 != 0) return -10;
+    if (!(inv_tau > 0.f) || !std::isfinite(inv_tau)) return -10;
+    if (!z_i || !z_j || !workspace || (uintptr_t)z_i % 16 != 0 || (uintptr_t)z_j % 16 != 0 || (uintptr_t)workspace % 16 != 0) return -10;
+    if (workspace_bytes < bsarec_info_nce_workspace_bytes(B, d, sim)) return -10;
+    const long n = 2L * B;
+    P.zi = z_i; P.zj = z_j; P.ldi = ld_i; P.ldj = ld_j;
+    P.B = B; P.n = (int)n; P.d = d; P.cos = sim; P.S = nce_splits((int)n); P.T = cdiv(n, NCE_TILE);
+    P.inv_tau = inv_tau;
+    float* w = (float*)workspace;
+    P.lse = w; P.spos = w + n; P.norm = w + 2 * n; P.pm = w + 3 * n; P.pl = P.pm + P.S * n; P.slab = w + nce_stat_floats(n, P.S);
+    return 0;
+}
+
+extern "C" int bsarec_info_nce_fwd(const float* z_i, long ld_i, const float* z_j, long ld_j, int B, int d, float inv_tau, int sim,
+                                   float* loss_out, float* rows_out, void* workspace, long workspace_bytes, void* stream) {
+    NceP P;
+    RET(info_nce_params(P, z_i, ld_i, z_j, ld_j, B, d, inv_tau, sim, workspace, workspace_bytes));
+    if (!loss_out) return -10;
+    hipStream_t st = (hipStream_t)stream;
+    if (P.cos) hipLaunchKernelGGL(nce_norm_kernel, dim3(cdiv(P.n, ROW_THREADS / 64)), dim3(ROW_THREADS), 0, st, P);
+    hipLaunchKernelGGL(nce_fwd_kernel, dim3(P.S, P.T), dim3(ROW_THREADS), 0, st, P);
+    hipLaunchKernelGGL(nce_stat_kernel, dim3(1), dim3(1024), 0, st, P, loss_out, rows_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_info_nce_bwd(const float* z_i, long ld_i, const float* z_j, long ld_j, int B, int d, float inv_tau, int sim,
+                                   const float* gout, void* workspace, long workspace_bytes, float* dz_i, float* dz_j,
+                                   void* stream) {
+    NceP P;
+    RET(info_nce_params(P, z_i, ld_i, z_j, ld_j, B, d, inv_tau, sim, workspace, workspace_bytes));
+    if (!gout || !dz_i || !dz_j || (uintptr_t)dz_i % 16 != 0 || (uintptr_t)dz_j % 16 != 0) return -10;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(P.S, P.T);
+    switch (cdiv(d, NCE_TILE)) {
+        case 1: hipLaunchKernelGGL(nce_bwd_kernel<1>, grid, dim3(ROW_THREADS), 0, st, P); break;
+        case 2: hipLaunchKernelGGL(nce_bwd_kernel<2>, grid, dim3(ROW_THREADS), 0, st, P); break;
+        case 3: hipLaunchKernelGGL(nce_bwd_kernel<3>, grid, dim3(ROW_THREADS), 0, st, P); break;
+        default: hipLaunchKernelGGL(nce_bwd_kernel<4>, grid, dim3(ROW_THREADS), 0, st, P); break;
+    }
+    hipLaunchKernelGGL(nce_dz_kernel, dim3(cdiv(P.n, ROW_THREADS / 64)), dim3(ROW_THREADS), 0, st, P, gout, dz_i, dz_j);
     return (int)hipGetLastError();
 }
 

@@ -143,6 +143,10 @@ def parse_args(argv=None):
     p.add_argument("--lmd_sem", default=0.1, type=float)
     p.add_argument("--ssl", default="us_x", type=str)
     p.add_argument("--sim", default="dot", type=str)
+    # not a reference flag: DuoRec's InfoNCE terms through the HIP head (bsarec_info_nce_fwd / _bwd) instead of the restated
+    # torch head.  Absent unless given (argparse.SUPPRESS), as the --eval_* flags are
+    p.add_argument("--duorec_head", default=argparse.SUPPRESS, choices=("torch", "hip"),
+                   help="DuoRec's contrastive head: the reference's torch code restated (default) or the HIP kernels")
     args = p.parse_args(argv)
     n = getattr(args, "eval_negatives", 0)
     if n > 0 and hasattr(args, "eval_full_rank"):

@@ -890,6 +890,63 @@ class FMLPRecModel(BSARecModel):
         return loss
 
 
+def _nce_operand(z):
+    """A [B, d] fp32 operand of bsarec_info_nce_*: as it is where the kernel takes its row stride (the [:, -1, :] view of a
+    forward output), else a contiguous copy."""
+    z = z.to(torch.float32)
+    ok = z.dim() == 2 and z.stride(1) == 1 and z.stride(0) >= z.shape[1] and z.stride(0) % 4 == 0 and z.data_ptr() % 16 == 0
+    return z if ok else z.contiguous()
+
+
+class _InfoNceFn(torch.autograd.Function):
+    """DuoRecModel.info_nce + F.cross_entropy as one autograd node over bsarec_info_nce_fwd / bsarec_info_nce_bwd: no 2B x 2B
+    matrix, no mask, no ``nonzero``.  Both calls go on the current stream (autograd runs a node's backward on its forward's
+    stream).  The workspace carries the forward's row statistics to the backward: it is taken from the model's pool per
+    (B, d, sim) and goes back after the backward, so two live terms of one step (ssl = 'us') never share one."""
+
+    @staticmethod
+    def forward(ctx, model, z_i, z_j):
+        zi, zj = _nce_operand(z_i), _nce_operand(z_j)
+        if zi.shape != zj.shape or zi.dim() != 2 or not zi.is_cuda:
+            raise ValueError("info_nce_loss: z_i and z_j must be [B, d] tensors of one shape on the GPU")
+        lib = L.load()
+        B, d = zi.shape
+        sim = 1 if model.sim == "cos" else 0
+        inv_tau = 1.0 / model.tau
+        nbytes = lib.bsarec_info_nce_workspace_bytes(B, d, sim)
+        if nbytes < 0:
+            raise ValueError(f"info_nce_loss: unsupported shape B = {B}, d = {d} (1 <= B <= 4096, 4 <= d <= 256, d % 4 == 0)")
+        key = (B, d, sim, zi.device)
+        pool = model._nce_pool.setdefault(key, [])
+        ws = pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, device=zi.device)
+        loss = torch.empty(1, dtype=torch.float32, device=zi.device)
+        stream = torch.cuda.current_stream(zi.device).cuda_stream
+        L.check(lib.bsarec_info_nce_fwd(zi.data_ptr(), zi.stride(0), zj.data_ptr(), zj.stride(0), B, d, inv_tau, sim,
+                                        loss.data_ptr(), None, ws.data_ptr(), nbytes, stream), "bsarec_info_nce_fwd")
+        ctx.save_for_backward(zi, zj)
+        ctx.model, ctx.key, ctx.ws, ctx.call = model, key, ws, (B, d, inv_tau, sim, nbytes)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        zi, zj = ctx.saved_tensors
+        B, d, inv_tau, sim, nbytes = ctx.call
+        if ctx.ws is None:
+            raise RuntimeError("info_nce_loss: backward ran twice (the forward's statistics are gone)")
+        g = gout.to(torch.float32).reshape(1).contiguous()
+        dzi, dzj = torch.empty(B, d, dtype=torch.float32, device=zi.device), torch.empty(B, d, dtype=torch.float32, device=zi.device)
+        stream = torch.cuda.current_stream(zi.device).cuda_stream
+        L.check(L.load().bsarec_info_nce_bwd(zi.data_ptr(), zi.stride(0), zj.data_ptr(), zj.stride(0), B, d, inv_tau, sim,
+                                             g.data_ptr(), ctx.ws.data_ptr(), nbytes, dzi.data_ptr(), dzj.data_ptr(), stream),
+                "bsarec_info_nce_bwd")
+        ctx.model._nce_pool[ctx.key].append(ctx.ws)
+        ctx.ws = None
+        return None, dzi, dzj
+
+
+DUOREC_HEADS = ("torch", "hip")
+
+
 class DuoRecModel(SASRecModel):
     """Sibling model: ``MODEL_DICT['duorec']``, src/model/duorec.py.  The encoder is SASRec's
     TransformerEncoder (a BSARec plan with alpha = 0, same 36 state_dict keys); the loss is the full-catalogue CE of the
@@ -897,7 +954,8 @@ class DuoRecModel(SASRecModel):
     the input, the input again under another dropout draw, and a same-target sequence (duorec.py:95-127).  The three
     passes are three live nodes of the differentiable :meth:`forward` (each keeps its own activations and dropout step
     until its backward); the head itself -- two small matmuls and a softmax over 2B x 2B similarities -- is the
-    reference's torch code restated, on the device."""
+    reference's torch code restated, on the device.  ``args.duorec_head = 'hip'`` computes each InfoNCE term (loss and
+    gradient) with bsarec_info_nce_fwd / _bwd instead (:meth:`info_nce_loss`); absent or ``'torch'``: the restated head."""
 
     needs_negatives = False
     needs_same_target = True                     # Trainer / DeviceBatches: feed same_target rows (src/dataset.py:82-96)
@@ -910,6 +968,10 @@ class DuoRecModel(SASRecModel):
         self.sim = getattr(args, "sim", "dot")
         self.lmd = float(getattr(args, "lmd", 0.1))
         self.lmd_sem = float(getattr(args, "lmd_sem", 0.1))
+        self.duorec_head = getattr(args, "duorec_head", "torch")
+        if self.duorec_head not in DUOREC_HEADS:
+            raise ValueError(f"duorec_head must be one of {DUOREC_HEADS}, got {self.duorec_head!r}")
+        self._nce_pool = {}                      # (B, d, sim, device) -> free workspaces of bsarec_info_nce_*
 
     @staticmethod
     def _mask_correlated(batch_size, device):
@@ -934,26 +996,33 @@ class DuoRecModel(SASRecModel):
         labels = torch.zeros(n, dtype=torch.long, device=z.device)
         return torch.cat((pos, neg), dim=1), labels
 
+    def info_nce_loss(self, z_i, z_j):
+        """``F.cross_entropy(*self.info_nce(z_i, z_j, self.tau, B, self.sim))`` as one HIP autograd node."""
+        return _InfoNceFn.apply(self, z_i, z_j)
+
     def calculate_loss(self, input_ids, answers, neg_answers=None, same_target=None, user_ids=None):
         """src/model/duorec.py:95-127."""
         ce = torch.nn.functional.cross_entropy
         B = input_ids.shape[0]
+        if self.duorec_head == "hip":
+            term = self.info_nce_loss
+        else:
+            def term(z_i, z_j):
+                lg, lb = self.info_nce(z_i, z_j, self.tau, B, self.sim)
+                return ce(lg, lb)
         seq_output = self.forward(input_ids)[:, -1, :]
         logits = torch.matmul(seq_output, self.item_embeddings.weight.transpose(0, 1))
         loss = ce(logits, answers.to(logits.device))
         if self.ssl in ("us", "un"):
             aug = self.forward(input_ids)[:, -1, :]
-            lg, lb = self.info_nce(seq_output, aug, self.tau, B, self.sim)
-            loss = loss + self.lmd * ce(lg, lb)
+            loss = loss + self.lmd * term(seq_output, aug)
         if self.ssl in ("us", "su"):
             sem = self.forward(same_target)[:, -1, :]
-            lg, lb = self.info_nce(seq_output, sem, self.tau, B, self.sim)
-            loss = loss + self.lmd_sem * ce(lg, lb)
+            loss = loss + self.lmd_sem * term(seq_output, sem)
         if self.ssl == "us_x":
             aug = self.forward(input_ids)[:, -1, :]
             sem = self.forward(same_target)[:, -1, :]
-            lg, lb = self.info_nce(aug, sem, self.tau, B, self.sim)
-            loss = loss + self.lmd_sem * ce(lg, lb)
+            loss = loss + self.lmd_sem * term(aug, sem)
         return loss
 
     def train_step(self, input_ids, answers, neg_answers=None, same_target=None):

@@ -453,6 +453,35 @@ int bsarec_answer_score_range(const float *h, long ldh, const float *item_rows, 
                               const int64_t *users, const int64_t *indptr, const int64_t *indices, const int64_t *answers,
                               float *score_out, void *stream);
 
+/* DuoRec's contrastive head (src/model/duorec.py:47-78 + F.cross_entropy): InfoNCE between two batches of B rows, loss and
+ * gradient, without the 2B x 2B score matrix.  z = [z_i; z_j], n = 2B rows; pos(r) = (r + B) mod n.
+ *   u_r  = z_r (sim = 0, dot)  or  z_r / max(|z_r|, 1e-8) (sim = 1, cos: each norm clamped on its own)
+ *   s_rc = u_r . u_c * inv_tau
+ *   lse_r = log sum_{c != r} exp(s_rc)       the diagonal excluded, the positive included once; the maximum is subtracted
+ *                                            before every exp, so scores above 88 are fine
+ *   row_r = lse_r - s_{r, pos(r)}            rows_out[r] (nullable, float[2B])
+ *   loss  = mean_r row_r                     loss_out[0]: what F.cross_entropy(*info_nce(z_i, z_j, 1 / inv_tau, B, sim)) returns
+ *   Backward for the upstream scalar g = gout[0] (DEVICE memory, read on the device): with W_rc = exp(s_rc - lse_r) +
+ *   exp(s_rc - lse_c) for c != r and W_rr = 0,
+ *     du_r = g inv_tau / n * (sum_c W_rc u_c - 2 u_pos(r))
+ *     dot: dz_r = du_r.   cos: dz_r = (du_r - u_r (u_r . du_r)) / |z_r| when |z_r| > 1e-8, else du_r / 1e-8 (autograd through
+ *     the clamp).  dz_i, dz_j: contiguous [B, d].  B = 1 gives loss 0 and dz 0 exactly.
+ *   bsarec_info_nce_bwd reads the statistics (lse, the clamped norms) that bsarec_info_nce_fwd left in `workspace` for the SAME
+ *   z_i, z_j, B, d, inv_tau, sim: call the forward first and keep workspace and inputs unchanged in between.
+ *   Workspace: bsarec_info_nce_workspace_bytes(B, d, sim) bytes (host-only query, no HIP call), linear in B: per-row statistics,
+ *   per-split partial (max, sum) pairs, and the backward's S <= 8 key-split slabs of [2B, d] floats with S * 2B <= 16384 + 2B.
+ *   Execution: two launches on `stream` forward (three for cos), two backward; no host synchronisation, no allocation, no
+ *   atomics: capturable, and every sum has ONE order, so loss, rows and gradients are bit-deterministic -- also between a strided
+ *   view and its contiguous copy.  Inputs are read-only and may alias each other; outputs may not alias inputs or the workspace.
+ *   Limits (else < 0 before any HIP call): 1 <= B <= 4096; 4 <= d <= 256, d % 4 == 0; ld_i, ld_j >= d and % 4 == 0 (row
+ *   strides in floats); z_i, z_j, workspace, dz_i, dz_j non-null and 16-byte aligned; loss_out, gout non-null; inv_tau finite
+ *   and > 0; sim in {0, 1}; workspace_bytes at least the queried size. */
+long bsarec_info_nce_workspace_bytes(int B, int d, int sim);
+int bsarec_info_nce_fwd(const float *z_i, long ld_i, const float *z_j, long ld_j, int B, int d, float inv_tau, int sim,
+                        float *loss_out, float *rows_out, void *workspace, long workspace_bytes, void *stream);
+int bsarec_info_nce_bwd(const float *z_i, long ld_i, const float *z_j, long ld_j, int B, int d, float inv_tau, int sim,
+                        const float *gout, void *workspace, long workspace_bytes, float *dz_i, float *dz_j, void *stream);
+
 /* Stand-alone FrequencyLayer (src/model/bsarec.py:90-104) for per-op parity tests:
  * y = LN(Drop(low + beta^2 (x - low)) + x); backward given dy. */
 int bsarec_freq_layer_fwd(const float *x, const float *sqrt_beta, const float *ln_w, const float *ln_b,
