@@ -15,6 +15,7 @@
 #include "full_rank.h"
 #include "answer_rank.h"
 #include "info_nce.h"
+#include "ce_head.h"
 #include "sampled_softmax.h"
 #include "lazy_adam.h"
 
@@ -1993,6 +1994,94 @@ extern "C" int bsarec_info_nce_bwd(const float* z_i, long ld_i, const float* z_j
         default: hipLaunchKernelGGL(nce_bwd_kernel<4>, grid, dim3(ROW_THREADS), 0, st, P); break;
     }
     hipLaunchKernelGGL(nce_dz_kernel, dim3(cdiv(P.n, ROW_THREADS / 64)), dim3(ROW_THREADS), 0, st, P, gout, dz_i, dz_j);
+    return (int)hipGetLastError();
+}
+
+// Full-catalogue cross-entropy on an external hidden state (ce_head.h): plan-less, everything on the caller's stream, no allocation.
+static int ce_head_shape_check(int B, int V, int d) {
+    if (B < 1 || B > 65536 || V < 1 || d < 4 || d > 256 || d % 4 != 0) return -10;
+    return 0;
+}
+
+extern "C" long bsarec_ce_head_workspace_bytes(int B, int V, int d) {
+    if (ce_head_shape_check(B, V, d)) return -10;
+    return ce_workspace_floats(B, V, d) * (long)sizeof(float);
+}
+
+static int ce_head_params(CeP& P, const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* answers,
+                          void* workspace, long workspace_bytes) {
+    RET(ce_head_shape_check(B, V, d));
+    if (ldh < d || ldh % 4 != 0) return -10;
+    if (!h || !item_emb || !answers || !workspace) return -10;
+    if ((uintptr_t)h % 16 != 0 || (uintptr_t)item_emb % 16 != 0 || (uintptr_t)workspace % 16 != 0) return -10;
+    if (workspace_bytes < bsarec_ce_head_workspace_bytes(B, V, d)) return -10;
+    P.h = h; P.ldh = ldh; P.E = item_emb; P.ans = answers;
+    P.B = B; P.V = V; P.d = d; P.S = ce_splits(B, V); P.nblk = ce_nblk(V);
+    float* w = (float*)workspace;
+    P.m = w; P.logl = w + B; P.pm = w + 2L * B; P.pl = P.pm + (long)P.S * B; P.slab = w + ce_stat_floats(B, P.S);
+    return 0;
+}
+
+// the h tile of a kernel may pass the 64 KB a launch gets without asking
+template <class K>
+static hipError_t ce_head_lds(K kernel, int rows) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)((size_t)rows * 260 * sizeof(float)));
+}
+static int ce_head_attributes() {
+    static bool done = false;
+    if (done) return 0;
+    hipError_t e = ce_head_lds(ce_fwd_kernel, CE_ROWS);
+    if (e == hipSuccess) e = ce_head_lds(ce_dh_kernel<4, 1>, 128);
+    if (e == hipSuccess) e = ce_head_lds(ce_dh_kernel<4, 2>, 128);
+    if (e == hipSuccess) e = ce_head_lds(ce_dh_kernel<2, 4>, 64);
+    if (e == hipSuccess) e = ce_head_lds(ce_dh_kernel<1, 8>, 32);
+    if (e == hipSuccess) e = ce_head_lds(ce_de_kernel<1>, CE_ROWS);
+    if (e == hipSuccess) e = ce_head_lds(ce_de_kernel<2>, CE_ROWS);
+    if (e == hipSuccess) e = ce_head_lds(ce_de_kernel<4>, CE_ROWS);
+    if (e == hipSuccess) e = ce_head_lds(ce_de_kernel<8>, CE_ROWS);
+    if (e != hipSuccess) return (int)e;
+    done = true;
+    return 0;
+}
+
+extern "C" int bsarec_ce_head_fwd(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* answers,
+                                  float* loss_out, float* rows_out, void* workspace, long workspace_bytes, void* stream) {
+    CeP P;
+    RET(ce_head_params(P, h, ldh, item_emb, B, V, d, answers, workspace, workspace_bytes));
+    if (!loss_out) return -10;
+    RET(ce_head_attributes());
+    hipStream_t st = (hipStream_t)stream;
+    const size_t smem = (size_t)CE_ROWS * (d + 4) * sizeof(float);
+    hipLaunchKernelGGL(ce_fwd_kernel, dim3(P.S, cdiv(B, CE_ROWS)), dim3(ROW_THREADS), smem, st, P);
+    hipLaunchKernelGGL(ce_stat_kernel, dim3(1), dim3(1024), 0, st, P, loss_out, rows_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_ce_head_bwd(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* answers,
+                                  const float* gout, void* workspace, long workspace_bytes, float* dh, float* d_item_emb,
+                                  void* stream) {
+    CeP P;
+    RET(ce_head_params(P, h, ldh, item_emb, B, V, d, answers, workspace, workspace_bytes));
+    if (!gout || !dh || !d_item_emb || (uintptr_t)dh % 16 != 0 || (uintptr_t)d_item_emb % 16 != 0) return -10;
+    RET(ce_head_attributes());
+    hipStream_t st = (hipStream_t)stream;
+    const int ndc = ce_ndc(d), rows = 32 * ce_dh_rb(ndc);
+    const dim3 grid(P.S, cdiv(B, rows)), wg(ROW_THREADS);
+    const size_t smem_dh = (size_t)rows * (d + 4) * sizeof(float), smem_de = (size_t)CE_ROWS * (d + 4) * sizeof(float);
+    switch (ndc) {
+        case 1: hipLaunchKernelGGL((ce_dh_kernel<4, 1>), grid, wg, smem_dh, st, P); break;
+        case 2: hipLaunchKernelGGL((ce_dh_kernel<4, 2>), grid, wg, smem_dh, st, P); break;
+        case 4: hipLaunchKernelGGL((ce_dh_kernel<2, 4>), grid, wg, smem_dh, st, P); break;
+        default: hipLaunchKernelGGL((ce_dh_kernel<1, 8>), grid, wg, smem_dh, st, P); break;
+    }
+    hipLaunchKernelGGL(ce_dh_sum_kernel, dim3(cdiv((long)B * d / 4, ROW_THREADS)), wg, 0, st, P, gout, dh);
+    switch (ndc) {
+        case 1: hipLaunchKernelGGL(ce_de_kernel<1>, dim3(P.nblk), wg, smem_de, st, P, gout, d_item_emb); break;
+        case 2: hipLaunchKernelGGL(ce_de_kernel<2>, dim3(P.nblk), wg, smem_de, st, P, gout, d_item_emb); break;
+        case 4: hipLaunchKernelGGL(ce_de_kernel<4>, dim3(P.nblk), wg, smem_de, st, P, gout, d_item_emb); break;
+        default: hipLaunchKernelGGL(ce_de_kernel<8>, dim3(P.nblk), wg, smem_de, st, P, gout, d_item_emb); break;
+    }
     return (int)hipGetLastError();
 }
 

@@ -147,6 +147,9 @@ def parse_args(argv=None):
     # torch head.  Absent unless given (argparse.SUPPRESS), as the --eval_* flags are
     p.add_argument("--duorec_head", default=argparse.SUPPRESS, choices=("torch", "hip"),
                    help="DuoRec's contrastive head: the reference's torch code restated (default) or the HIP kernels")
+    # likewise: DuoRec's supervised full-catalogue cross-entropy through bsarec_ce_head_fwd / _bwd (no B x V logits)
+    p.add_argument("--duorec_ce_head", default=argparse.SUPPRESS, choices=("torch", "hip"),
+                   help="DuoRec's supervised cross-entropy: torch.matmul + F.cross_entropy (default) or the HIP kernels")
     args = p.parse_args(argv)
     n = getattr(args, "eval_negatives", 0)
     if n > 0 and hasattr(args, "eval_full_rank"):

@@ -294,6 +294,7 @@ class BSARecModel(nn.Module):
         self.init_weights()
         self._plans: Dict[Tuple[int, str], _Plan] = {}
         self._slots_busy = set()
+        self._ce_pool = {}                       # (B, V, d, device) -> free workspaces of bsarec_ce_head_*
         self._seed = int(getattr(args, "seed", 42))
 
     # ---- module tree with the reference's parameter paths -------------------------------------
@@ -579,6 +580,13 @@ class BSARecModel(nn.Module):
         plan = self._run_forward(input_ids, train=self.training, new_step=self.training, last_only=True)
         self._run_loss(plan, answers)
         return plan.view(L.BUF_LOSS, 0, (1,))[0].clone()
+
+    def catalogue_ce(self, seq_output, answers) -> torch.Tensor:
+        """``F.cross_entropy(seq_output @ self.item_embeddings.weight.T, answers)`` as one HIP autograd node
+        (bsarec_ce_head_fwd / _bwd): a 0-d tensor, differentiable with respect to ``seq_output`` and the item table, with
+        nothing of size B x V allocated.  ``seq_output``: [B, d], or the ``[:, -1, :]`` view of a forward output, which is
+        read through its row stride as it stands."""
+        return _CatalogueCeFn.apply(self, seq_output, self.item_embeddings.weight, answers)
 
     def full_logits(self, input_ids) -> torch.Tensor:
         """Last-position scores over the whole catalogue (Trainer.predict_full of the last position,
@@ -944,7 +952,60 @@ class _InfoNceFn(torch.autograd.Function):
         return None, dzi, dzj
 
 
+class _CatalogueCeFn(torch.autograd.Function):
+    """The full-catalogue cross-entropy of a hidden state as one autograd node over bsarec_ce_head_fwd / bsarec_ce_head_bwd:
+    no logits, no softmax matrix.  Both calls go on the current stream.  The workspace carries the forward's row statistics
+    to the backward: it is taken from the model's pool per (B, V, d) and goes back after the backward."""
+
+    @staticmethod
+    def forward(ctx, model, seq_output, item_emb, answers):
+        h = _nce_operand(seq_output)
+        if h.dim() != 2 or not h.is_cuda:
+            raise ValueError("catalogue_ce: seq_output must be a [B, d] tensor on the GPU")
+        E = item_emb.detach().to(torch.float32)
+        if not E.is_contiguous() or E.data_ptr() % 16 != 0:
+            E = E.contiguous()
+        B, d = h.shape
+        V = E.shape[0]
+        if E.dim() != 2 or E.shape[1] != d or answers.shape != (B,):
+            raise ValueError("catalogue_ce: item table [V, d] and answers [B] must match seq_output [B, d]")
+        a = answers.to(device=h.device, dtype=torch.int64).contiguous()
+        lib = L.load()
+        nbytes = lib.bsarec_ce_head_workspace_bytes(B, V, d)
+        if nbytes < 0:
+            raise ValueError(f"catalogue_ce: unsupported shape B = {B}, V = {V}, d = {d} "
+                             "(1 <= B <= 65536, 1 <= V < 2^31, 4 <= d <= 256, d % 4 == 0)")
+        key = (B, V, d, h.device)
+        pool = model._ce_pool.setdefault(key, [])
+        ws = pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, device=h.device)
+        loss = torch.empty(1, dtype=torch.float32, device=h.device)
+        stream = torch.cuda.current_stream(h.device).cuda_stream
+        L.check(lib.bsarec_ce_head_fwd(h.data_ptr(), h.stride(0), E.data_ptr(), B, V, d, a.data_ptr(), loss.data_ptr(), None,
+                                       ws.data_ptr(), nbytes, stream), "bsarec_ce_head_fwd")
+        ctx.save_for_backward(h, E, a)
+        ctx.model, ctx.key, ctx.ws, ctx.call = model, key, ws, (B, V, d, nbytes)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        h, E, a = ctx.saved_tensors
+        B, V, d, nbytes = ctx.call
+        if ctx.ws is None:
+            raise RuntimeError("catalogue_ce: backward ran twice (the forward's statistics are gone)")
+        g = gout.to(torch.float32).reshape(1).contiguous()
+        dh = torch.empty(B, d, dtype=torch.float32, device=h.device)
+        dE = torch.empty(V, d, dtype=torch.float32, device=h.device)
+        stream = torch.cuda.current_stream(h.device).cuda_stream
+        L.check(L.load().bsarec_ce_head_bwd(h.data_ptr(), h.stride(0), E.data_ptr(), B, V, d, a.data_ptr(), g.data_ptr(),
+                                            ctx.ws.data_ptr(), nbytes, dh.data_ptr(), dE.data_ptr(), stream),
+                "bsarec_ce_head_bwd")
+        ctx.model._ce_pool[ctx.key].append(ctx.ws)
+        ctx.ws = None
+        return None, dh, dE, None
+
+
 DUOREC_HEADS = ("torch", "hip")
+DUOREC_CE_HEADS = ("torch", "hip")
 
 
 class DuoRecModel(SASRecModel):
@@ -955,7 +1016,9 @@ class DuoRecModel(SASRecModel):
     passes are three live nodes of the differentiable :meth:`forward` (each keeps its own activations and dropout step
     until its backward); the head itself -- two small matmuls and a softmax over 2B x 2B similarities -- is the
     reference's torch code restated, on the device.  ``args.duorec_head = 'hip'`` computes each InfoNCE term (loss and
-    gradient) with bsarec_info_nce_fwd / _bwd instead (:meth:`info_nce_loss`); absent or ``'torch'``: the restated head."""
+    gradient) with bsarec_info_nce_fwd / _bwd instead (:meth:`info_nce_loss`); absent or ``'torch'``: the restated head.
+    ``args.duorec_ce_head = 'hip'``, independently, computes the supervised cross-entropy with :meth:`catalogue_ce` (no
+    B x V logits); absent or ``'torch'``: ``torch.matmul`` + ``F.cross_entropy``."""
 
     needs_negatives = False
     needs_same_target = True                     # Trainer / DeviceBatches: feed same_target rows (src/dataset.py:82-96)
@@ -971,6 +1034,9 @@ class DuoRecModel(SASRecModel):
         self.duorec_head = getattr(args, "duorec_head", "torch")
         if self.duorec_head not in DUOREC_HEADS:
             raise ValueError(f"duorec_head must be one of {DUOREC_HEADS}, got {self.duorec_head!r}")
+        self.duorec_ce_head = getattr(args, "duorec_ce_head", "torch")
+        if self.duorec_ce_head not in DUOREC_CE_HEADS:
+            raise ValueError(f"duorec_ce_head must be one of {DUOREC_CE_HEADS}, got {self.duorec_ce_head!r}")
         self._nce_pool = {}                      # (B, d, sim, device) -> free workspaces of bsarec_info_nce_*
 
     @staticmethod
@@ -1011,8 +1077,11 @@ class DuoRecModel(SASRecModel):
                 lg, lb = self.info_nce(z_i, z_j, self.tau, B, self.sim)
                 return ce(lg, lb)
         seq_output = self.forward(input_ids)[:, -1, :]
-        logits = torch.matmul(seq_output, self.item_embeddings.weight.transpose(0, 1))
-        loss = ce(logits, answers.to(logits.device))
+        if self.duorec_ce_head == "hip":
+            loss = self.catalogue_ce(seq_output, answers)
+        else:
+            logits = torch.matmul(seq_output, self.item_embeddings.weight.transpose(0, 1))
+            loss = ce(logits, answers.to(logits.device))
         if self.ssl in ("us", "un"):
             aug = self.forward(input_ids)[:, -1, :]
             loss = loss + self.lmd * term(seq_output, aug)

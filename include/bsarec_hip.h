@@ -482,6 +482,36 @@ int bsarec_info_nce_fwd(const float *z_i, long ld_i, const float *z_j, long ld_j
 int bsarec_info_nce_bwd(const float *z_i, long ld_i, const float *z_j, long ld_j, int B, int d, float inv_tau, int sim,
                         const float *gout, void *workspace, long workspace_bytes, float *dz_i, float *dz_j, void *stream);
 
+/* Full-catalogue cross-entropy on an external hidden state, loss and gradient, without the B x V logits: what
+ * F.cross_entropy(h @ item_emb.T, answers) and its autograd compute, with nothing of size B x V stored.  No plan.
+ *   s(b, j) = the fmaf chain of bsarec_topk_full: acc = 0, then acc = fmaf(h[b * ldh + i], item_emb[j * d + i], acc), i ascending
+ *             (training and evaluation see the same logits); one score routine serves the forward and every backward kernel
+ *   a_b     = answers[b] clamped to [0, V); item 0 (the padding row) is a class like any other
+ *   lse_b   = m_b + log sum_{j < V} exp(s(b, j) - m_b), m_b the row maximum: scores above 88 are fine
+ *   row_b   = lse_b - s(b, a_b)                rows_out[b] (nullable, float[B])
+ *   loss    = mean_b row_b                     loss_out[0].  V = 1 gives loss 0 and zero gradients exactly.
+ *   Backward for the upstream scalar g = gout[0] (DEVICE memory, read on the device): G_bj = g / B * (exp(s(b, j) - lse_b) -
+ *   [j == a_b]),  dh[b] = sum_j G_bj item_emb[j]  (contiguous [B, d]),  d_item_emb[j] = sum_b G_bj h[b]  (contiguous [V, d], every
+ *   row overwritten).  g / B is applied to the finished sums.
+ *   The row statistics are kept as the pair (m_b, log l_b), l_b the sum above: row_b is formed as (m_b - s(b, a_b)) + log l_b and
+ *   the backward's exponent as (s(b, j) - m_b) - log l_b, which do not round at the magnitude of m_b as m_b + log l_b would.
+ *   bsarec_ce_head_bwd reads the row statistics that bsarec_ce_head_fwd left in `workspace` for the SAME h, item_emb, answers,
+ *   B, V, d: call the forward first and keep workspace and inputs unchanged in between.
+ *   Workspace: bsarec_ce_head_workspace_bytes(B, V, d) bytes (host-only query, no HIP call): m[B], log l[B], the (max, sum) pairs of the
+ *   S splits of the catalogue, and the backward's S slabs of [B, d] floats, added in split order; S B <= 16384 + B, so the size
+ *   is at most (16384 + 2B) * (d + 8) * 4 bytes for every V and stops growing with V.
+ *   Execution: two launches on `stream` forward, three backward; no host synchronisation, no allocation, no atomics: capturable,
+ *   and every sum has ONE order, so loss, rows, dh and d_item_emb are bit-deterministic -- also between a strided h (the
+ *   [:, -1, :] view, ldh = L * d) and its contiguous copy.  Inputs are read-only; outputs may not alias inputs or the workspace.
+ *   Limits (else < 0 before any HIP call): 1 <= B <= 65536; 1 <= V < 2^31; 4 <= d <= 256, d % 4 == 0; ldh >= d and % 4 == 0 (row
+ *   stride in floats); h, item_emb, workspace, dh, d_item_emb non-null and 16-byte aligned; answers, loss_out, gout non-null;
+ *   workspace_bytes at least the queried size. */
+long bsarec_ce_head_workspace_bytes(int B, int V, int d);
+int bsarec_ce_head_fwd(const float *h, long ldh, const float *item_emb, int B, int V, int d, const int64_t *answers,
+                       float *loss_out, float *rows_out, void *workspace, long workspace_bytes, void *stream);
+int bsarec_ce_head_bwd(const float *h, long ldh, const float *item_emb, int B, int V, int d, const int64_t *answers,
+                       const float *gout, void *workspace, long workspace_bytes, float *dh, float *d_item_emb, void *stream);
+
 /* Stand-alone FrequencyLayer (src/model/bsarec.py:90-104) for per-op parity tests:
  * y = LN(Drop(low + beta^2 (x - low)) + x); backward given dy. */
 int bsarec_freq_layer_fwd(const float *x, const float *sqrt_beta, const float *ln_w, const float *ln_b,
