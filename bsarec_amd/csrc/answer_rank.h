@@ -14,8 +14,8 @@
 //       dead: an id counts in the chunk of its first occurrence only.  The correction walks the table's live slots.  A row
 //       of n entries costs n table inserts, n rescored items at most, and sum over chunks c >= 1 of c * AR_CHUNK further
 //       index loads and probes -- none for n <= 2048, 2048 for ML-1M's row of 2,314, n^2 / 4096 in general.
-//   (b) answer_rank_count_kernel: the grid and LDS tile of full_rank_filter_kernel (128 rows of h, 32 items per wave through
-//       v_mfma_f32_32x32x2_f32, the same scores bit for bit); the epilogue compares every accumulator element's key with its
+//   (b) answer_rank_count_kernel: the grid, LDS tile and score_tile call of full_rank_filter_kernel (128 rows of h, 32 items
+//       per wave, the same scores bit for bit); the epilogue compares every accumulator element's key with its
 //       row's threshold and adds into ONE INTEGER PER ACCUMULATOR ELEMENT per lane (64 VGPRs).  After the item loop the 32
 //       lanes that hold a row are summed with shuffles, the four waves through LDS, and each row gets one atomicAdd per
 //       workgroup.  (b) reads the target as (a) left it: answer_score[b], else score_out[b], else -- a caller that wants no
@@ -130,16 +130,13 @@ answer_rank_count_kernel(const float* __restrict__ h, long ldh, const float* __r
                          const int64_t* __restrict__ users, const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
                          const int64_t* __restrict__ answers, const float* __restrict__ answer_score,
                          const float* __restrict__ score_in, int32_t* rank_out) {
-    extern __shared__ float sh[];
+    extern __shared__ __attribute__((aligned(16))) float sh[];
     __shared__ uint2 tgt_s[FR_ROWS];
     __shared__ int cnt_s[FR_ROWS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, half = lane >> 5;
     const int r0 = blockIdx.x * FR_ROWS;
     const int dp = d + 4;
-    for (int x = tid; x < FR_ROWS * d; x += ROW_THREADS) {
-        const int i = x / d, c = x - i * d;
-        sh[i * dp + c] = r0 + i < B ? h[(long)(r0 + i) * ldh + c] : 0.f;
-    }
+    score_stage(h, ldh, B, d, r0, FR_ROWS, sh);
     for (int i = tid; i < FR_ROWS; i += ROW_THREADS) cnt_s[i] = 0;
     __syncthreads();
     const bool given = answer_score != nullptr;
@@ -171,24 +168,13 @@ answer_rank_count_kernel(const float* __restrict__ h, long ldh, const float* __r
         for (int r = 0; r < 16; ++r) cnt[rb][r] = 0;
     const int nblk = (V + FR_ITEMS - 1) / FR_ITEMS;
     for (int ib = blockIdx.y; ib < nblk; ib += gridDim.y) {
-        const int item = ib * FR_ITEMS + wave * 32 + l31;
+        const unsigned i0 = (unsigned)ib * FR_ITEMS + wave * 32;         // this wave's 32 items
+        const int item = (int)i0 + l31;
         const bool iv = item < V;
-        const float4* e4 = reinterpret_cast<const float4*>(E + (long)(iv ? item : 0) * d);
+        unsigned eoff;
+        const float* eb = score_items(E, V, d, i0, eoff);
         f32x16 acc[4];
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[rb][r] = 0.f;
-        for (int kc = 0; kc < d; kc += 4) {
-            const float4 e = e4[kc >> 2];
-            const float b0 = half ? e.y : e.x, b1 = half ? e.w : e.z;   // MFMA k-step: lanes 0..31 give k, lanes 32..63 k + 1
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb) {
-                const float4 a = *reinterpret_cast<const float4*>(&sh[(rb * 32 + l31) * dp + kc]);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? a.y : a.x, b0, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? a.w : a.z, b1, acc[rb], 0, 0, 0);
-            }
-        }
+        score_tile<4, false>(sh, eb, eoff, d, acc);
         const int gj = (int)(base + item);
         if (iv) {                                        // ONE divergent region (the last block's tail), a branch-free body
 #pragma unroll

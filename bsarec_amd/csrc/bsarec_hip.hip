@@ -1799,14 +1799,40 @@ extern "C" int bsarec_topk_seen(float* scores, long ld, int B, int V, const int6
     return (int)hipGetLastError();
 }
 
+// Argument conditions the catalogue entry points share: a row of d floats is read as float4s, d <= 256 bounds the LDS tiles;
+// E holds rows [col_base, col_base + V) of a catalogue whose ids fit an int.
+static bool row_dim_ok(int d) { return d >= 4 && d <= 256 && d % 4 == 0; }
+static bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+static bool col_range_ok(long col_base, int V) { return col_base >= 0 && col_base + V <= 0x7fffffffL; }
+
+// A score-tile kernel's h tile is rows x (d + 4) floats: up to 133 KB of the 160 KB LDS (128 rows, d = 256), past the 64 KB a
+// launch gets without asking.  Once per process (`done` is the family's flag) every kernel's limit is raised to its largest tile.
+static size_t tile_smem(int rows, int d) { return (size_t)rows * (d + 4) * sizeof(float); }
+struct TileKernel { const void* fn; int rows; };
+static int tile_lds_once(bool& done, std::initializer_list<TileKernel> kernels) {
+    if (done) return 0;
+    for (const TileKernel& k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_smem(k.rows, 256));
+        if (e != hipSuccess) return (int)e;
+    }
+    done = true;
+    return 0;
+}
+// The grid of the filter and of the count kernel: (row tiles, item groups), about 1024 workgroups.
+static dim3 fr_tile_grid(int B, int V) {
+    const int tiles = (B + FR_ROWS - 1) / FR_ROWS, nblk = (V + FR_ITEMS - 1) / FR_ITEMS;
+    const int groups = (1024 + tiles - 1) / tiles;
+    return dim3(tiles, groups > nblk ? nblk : groups);
+}
+
 extern "C" int bsarec_sampled_rank(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* users,
                                    const int64_t* answers, const int64_t* indptr, const int64_t* indices, const int64_t* pop_cum,
                                    int n_neg, uint64_t seed, uint32_t tag, int32_t* rank_out, int64_t* cand_out, float* score_out,
                                    void* stream) {
     static_assert(BSAREC_NEG_MAX == NEG_MAX && BSAREC_NEG_MAX_DRAWS == NEG_MAX_DRAWS, "sampled_rank_kernel: the header's limits");
     if (!h || !item_emb || !users || !answers || !rank_out || (indptr && !indices)) return -10;
-    if (B < 1 || V < 2 || d < 4 || d > 256 || d % 4 != 0 || ldh < d || n_neg < 1 || n_neg > BSAREC_NEG_MAX) return -10;
-    if ((uintptr_t)item_emb % 16 != 0) return -10;               // float4 row loads
+    if (B < 1 || V < 2 || !row_dim_ok(d) || ldh < d || n_neg < 1 || n_neg > BSAREC_NEG_MAX) return -10;
+    if (!aligned16(item_emb)) return -10;                        // float4 row loads
     hipLaunchKernelGGL(sampled_rank_kernel, dim3(B), dim3(ROW_THREADS), 0, (hipStream_t)stream, h, ldh, item_emb, V, d, users, answers,
                        indptr, indices, pop_cum, n_neg, (uint32_t)seed, (uint32_t)(seed >> 32), tag, rank_out, cand_out, score_out);
     return (int)hipGetLastError();
@@ -1816,7 +1842,7 @@ extern "C" int bsarec_sampled_rank(const float* h, long ldh, const float* item_e
 // k and V only), cap list entries per row (cand_cap, or by default about 4 k V / s: expected survivors ~ k V / s = cap / 4); s ~ 4 sqrt(k V).
 struct FrShape { long s, stride, cap; };
 static bool fr_shape(int B, int V, int d, int k, int cand_cap, FrShape* out) {
-    if (B < 1 || k < 1 || k > BSAREC_TOPK_MAX || V < k || d < 4 || d > 256 || d % 4 != 0) return false;
+    if (B < 1 || k < 1 || k > BSAREC_TOPK_MAX || V < k || !row_dim_ok(d)) return false;
     if (cand_cap < 0 || (cand_cap > 0 && cand_cap < k) || cand_cap > (1 << 30)) return false;
     const long kv = (long)k * V;
     long s = 4 * (long)std::sqrt((double)kv);
@@ -1847,9 +1873,9 @@ extern "C" int bsarec_topk_full_range(const float* h, long ldh, const float* ite
     static_assert(BSAREC_TOPK_MAX == TOPK_MAX && ROW_THREADS == 256 && FR_ROWS == 128, "full_rank.h: the header's limits");
     FrShape f;
     if (!fr_shape(B, V, d, k, cand_cap, &f)) return -10;
-    if (col_base < 0 || col_base + V > 0x7fffffffL) return -10;
+    if (!col_range_ok(col_base, V)) return -10;
     if (!h || !item_emb || !workspace || !out_idx || ldh < d || (indptr && (!users || !indices))) return -10;
-    if ((uintptr_t)h % 16 != 0 || (uintptr_t)item_emb % 16 != 0 || (uintptr_t)workspace % 16 != 0) return -10;
+    if (!aligned16(h) || !aligned16(item_emb) || !aligned16(workspace)) return -10;
     if (workspace_bytes < bsarec_topk_full_workspace_bytes(B, V, d, k, cand_cap)) return -10;
     char* ws = (char*)workspace;
     unsigned long long* tau = (unsigned long long*)ws;           ws += fr_align((long)B * 8);
@@ -1858,24 +1884,15 @@ extern "C" int bsarec_topk_full_range(const float* h, long ldh, const float* ite
     unsigned long long* list = (unsigned long long*)ws;
     const int cap = (int)f.cap;
     hipStream_t st = (hipStream_t)stream;
-    const int tiles = (B + FR_ROWS - 1) / FR_ROWS, nblk = (V + FR_ITEMS - 1) / FR_ITEMS;
-    int groups = (1024 + tiles - 1) / tiles;                    // about 1024 workgroups over the (row tile x item) grid
-    if (groups > nblk) groups = nblk;
-    const size_t smem = (size_t)FR_ROWS * (d + 4) * sizeof(float);
-    static bool attr = false;                                    // up to 133 KB of the 160 KB LDS (d = 256)
-    if (!attr) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(full_rank_filter_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)FR_ROWS * 260 * sizeof(float)));
-        if (e != hipSuccess) return (int)e;
-        attr = true;
-    }
+    static bool raised = false;
+    RET(tile_lds_once(raised, {{(const void*)full_rank_filter_kernel, FR_ROWS}}));
     hipLaunchKernelGGL(full_rank_sample_kernel, dim3(B), dim3(ROW_THREADS), 0, st, h, ldh, item_emb, V, col_base, d, users, indptr,
                        indices, k, (int)f.s, (int)f.stride, skeys, tau, count);
     for (int round = 0; round <= FR_ROUNDS; ++round) {
         if (round > 0)
             hipLaunchKernelGGL(full_rank_rethreshold_kernel, dim3(B), dim3(ROW_THREADS), 0, st, k, cap, tau, count, list);
-        hipLaunchKernelGGL(full_rank_filter_kernel, dim3(tiles, groups), dim3(ROW_THREADS), smem, st, h, ldh, item_emb, B, V, d, cap,
-                           tau, count, list);
+        hipLaunchKernelGGL(full_rank_filter_kernel, fr_tile_grid(B, V), dim3(ROW_THREADS), tile_smem(FR_ROWS, d), st, h, ldh, item_emb, B,
+                           V, d, cap, tau, count, list);
     }
     hipLaunchKernelGGL(full_rank_select_kernel, dim3(B), dim3(ROW_THREADS), 0, st, V, col_base, k, cap, users, indptr, indices, count,
                        list, out_idx, out_val);
@@ -1894,10 +1911,10 @@ extern "C" int bsarec_topk_full(const float* h, long ldh, const float* item_emb,
 // The answer's rank without a list (answer_rank.h): the per-row launch, then the count launch; no workspace.
 static int answer_rank_check(const float* h, long ldh, const float* E, int B, int V, long col_base, int d, const int64_t* users,
                              const int64_t* indptr, const int64_t* indices, const int64_t* answers, const void* out) {
-    if (B < 1 || V < 1 || d < 4 || d > 256 || d % 4 != 0 || ldh < d) return -10;
-    if (col_base < 0 || col_base + V > 0x7fffffffL) return -10;
+    if (B < 1 || V < 1 || !row_dim_ok(d) || ldh < d) return -10;
+    if (!col_range_ok(col_base, V)) return -10;
     if (!h || !E || !answers || !out || (indptr && (!users || !indices))) return -10;
-    if ((uintptr_t)h % 16 != 0 || (uintptr_t)E % 16 != 0) return -10;
+    if (!aligned16(h) || !aligned16(E)) return -10;
     return 0;
 }
 
@@ -1906,21 +1923,12 @@ extern "C" int bsarec_answer_rank_range(const float* h, long ldh, const float* i
                                         const float* answer_score, int32_t* rank_out, float* score_out, void* stream) {
     RET(answer_rank_check(h, ldh, item_rows, B, Vs, col_base, d, users, indptr, indices, answers, rank_out));
     hipStream_t st = (hipStream_t)stream;
-    const int tiles = (B + FR_ROWS - 1) / FR_ROWS, nblk = (Vs + FR_ITEMS - 1) / FR_ITEMS;
-    int groups = (1024 + tiles - 1) / tiles;                    // the filter's grid: about 1024 workgroups
-    if (groups > nblk) groups = nblk;
-    const size_t smem = (size_t)FR_ROWS * (d + 4) * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(answer_rank_count_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)FR_ROWS * 260 * sizeof(float)));
-        if (e != hipSuccess) return (int)e;
-        attr = true;
-    }
+    static bool raised = false;
+    RET(tile_lds_once(raised, {{(const void*)answer_rank_count_kernel, FR_ROWS}}));
     hipLaunchKernelGGL(answer_rank_row_kernel<false>, dim3(B), dim3(ROW_THREADS), 0, st, h, ldh, item_rows, Vs, col_base, d, users,
                        indptr, indices, answers, answer_score, rank_out, score_out);
-    hipLaunchKernelGGL(answer_rank_count_kernel, dim3(tiles, groups), dim3(ROW_THREADS), smem, st, h, ldh, item_rows, B, Vs, col_base,
-                       d, users, indptr, indices, answers, answer_score, (const float*)score_out, rank_out);
+    hipLaunchKernelGGL(answer_rank_count_kernel, fr_tile_grid(B, Vs), dim3(ROW_THREADS), tile_smem(FR_ROWS, d), st, h, ldh, item_rows, B,
+                       Vs, col_base, d, users, indptr, indices, answers, answer_score, (const float*)score_out, rank_out);
     return (int)hipGetLastError();
 }
 
@@ -1942,7 +1950,7 @@ extern "C" int bsarec_answer_score_range(const float* h, long ldh, const float* 
 
 // DuoRec's contrastive head (info_nce.h): plan-less, everything on the caller's stream, no allocation.
 static int info_nce_shape_check(int B, int d, int sim) {
-    if (B < 1 || B > 4096 || d < 4 || d > 256 || d % 4 != 0 || (sim != 0 && sim != 1)) return -10;
+    if (B < 1 || B > 4096 || !row_dim_ok(d) || (sim != 0 && sim != 1)) return -10;
     return 0;
 }
 
@@ -1956,7 +1964,7 @@ static int info_nce_params(NceP& P, const float* z_i, long ld_i, const float* z_
     RET(info_nce_shape_check(B, d, sim));
     if (ld_i < d || ld_j < d || ld_i % 4 != 0 || ld_j % 4 != 0) return -10;
     if (!(inv_tau > 0.f) || !std::isfinite(inv_tau)) return -10;
-    if (!z_i || !z_j || !workspace || (uintptr_t)z_i % 16 != 0 || (uintptr_t)z_j % 16 != 0 || (uintptr_t)workspace % 16 != 0) return -10;
+    if (!z_i || !z_j || !workspace || !aligned16(z_i) || !aligned16(z_j) || !aligned16(workspace)) return -10;
     if (workspace_bytes < bsarec_info_nce_workspace_bytes(B, d, sim)) return -10;
     const long n = 2L * B;
     P.zi = z_i; P.zj = z_j; P.ldi = ld_i; P.ldj = ld_j;
@@ -1984,7 +1992,7 @@ extern "C" int bsarec_info_nce_bwd(const float* z_i, long ld_i, const float* z_j
                                    void* stream) {
     NceP P;
     RET(info_nce_params(P, z_i, ld_i, z_j, ld_j, B, d, inv_tau, sim, workspace, workspace_bytes));
-    if (!gout || !dz_i || !dz_j || (uintptr_t)dz_i % 16 != 0 || (uintptr_t)dz_j % 16 != 0) return -10;
+    if (!gout || !dz_i || !dz_j || !aligned16(dz_i) || !aligned16(dz_j)) return -10;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(P.S, P.T);
     switch (cdiv(d, NCE_TILE)) {
@@ -1999,7 +2007,7 @@ extern "C" int bsarec_info_nce_bwd(const float* z_i, long ld_i, const float* z_j
 
 // Full-catalogue cross-entropy on an external hidden state (ce_head.h): plan-less, everything on the caller's stream, no allocation.
 static int ce_head_shape_check(int B, int V, int d) {
-    if (B < 1 || B > 65536 || V < 1 || d < 4 || d > 256 || d % 4 != 0) return -10;
+    if (B < 1 || B > 65536 || V < 1 || !row_dim_ok(d)) return -10;
     return 0;
 }
 
@@ -2013,7 +2021,7 @@ static int ce_head_params(CeP& P, const float* h, long ldh, const float* item_em
     RET(ce_head_shape_check(B, V, d));
     if (ldh < d || ldh % 4 != 0) return -10;
     if (!h || !item_emb || !answers || !workspace) return -10;
-    if ((uintptr_t)h % 16 != 0 || (uintptr_t)item_emb % 16 != 0 || (uintptr_t)workspace % 16 != 0) return -10;
+    if (!aligned16(h) || !aligned16(item_emb) || !aligned16(workspace)) return -10;
     if (workspace_bytes < bsarec_ce_head_workspace_bytes(B, V, d)) return -10;
     P.h = h; P.ldh = ldh; P.E = item_emb; P.ans = answers;
     P.B = B; P.V = V; P.d = d; P.S = ce_splits(B, V); P.nblk = ce_nblk(V);
@@ -2022,27 +2030,13 @@ static int ce_head_params(CeP& P, const float* h, long ldh, const float* item_em
     return 0;
 }
 
-// the h tile of a kernel may pass the 64 KB a launch gets without asking
-template <class K>
-static hipError_t ce_head_lds(K kernel, int rows) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)((size_t)rows * 260 * sizeof(float)));
-}
 static int ce_head_attributes() {
-    static bool done = false;
-    if (done) return 0;
-    hipError_t e = ce_head_lds(ce_fwd_kernel, CE_ROWS);
-    if (e == hipSuccess) e = ce_head_lds(ce_dh_kernel<4, 1>, 128);
-    if (e == hipSuccess) e = ce_head_lds(ce_dh_kernel<4, 2>, 128);
-    if (e == hipSuccess) e = ce_head_lds(ce_dh_kernel<2, 4>, 64);
-    if (e == hipSuccess) e = ce_head_lds(ce_dh_kernel<1, 8>, 32);
-    if (e == hipSuccess) e = ce_head_lds(ce_de_kernel<1>, CE_ROWS);
-    if (e == hipSuccess) e = ce_head_lds(ce_de_kernel<2>, CE_ROWS);
-    if (e == hipSuccess) e = ce_head_lds(ce_de_kernel<4>, CE_ROWS);
-    if (e == hipSuccess) e = ce_head_lds(ce_de_kernel<8>, CE_ROWS);
-    if (e != hipSuccess) return (int)e;
-    done = true;
-    return 0;
+    static bool raised = false;
+    return tile_lds_once(raised, {{(const void*)ce_fwd_kernel, CE_ROWS},
+                                  {(const void*)ce_dh_kernel<4, 1>, 128}, {(const void*)ce_dh_kernel<4, 2>, 128},
+                                  {(const void*)ce_dh_kernel<2, 4>, 64}, {(const void*)ce_dh_kernel<1, 8>, 32},
+                                  {(const void*)ce_de_kernel<1>, CE_ROWS}, {(const void*)ce_de_kernel<2>, CE_ROWS},
+                                  {(const void*)ce_de_kernel<4>, CE_ROWS}, {(const void*)ce_de_kernel<8>, CE_ROWS}});
 }
 
 extern "C" int bsarec_ce_head_fwd(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* answers,
@@ -2052,8 +2046,7 @@ extern "C" int bsarec_ce_head_fwd(const float* h, long ldh, const float* item_em
     if (!loss_out) return -10;
     RET(ce_head_attributes());
     hipStream_t st = (hipStream_t)stream;
-    const size_t smem = (size_t)CE_ROWS * (d + 4) * sizeof(float);
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3(P.S, cdiv(B, CE_ROWS)), dim3(ROW_THREADS), smem, st, P);
+    hipLaunchKernelGGL(ce_fwd_kernel, dim3(P.S, cdiv(B, CE_ROWS)), dim3(ROW_THREADS), tile_smem(CE_ROWS, d), st, P);
     hipLaunchKernelGGL(ce_stat_kernel, dim3(1), dim3(1024), 0, st, P, loss_out, rows_out);
     return (int)hipGetLastError();
 }
@@ -2063,12 +2056,12 @@ extern "C" int bsarec_ce_head_bwd(const float* h, long ldh, const float* item_em
                                   void* stream) {
     CeP P;
     RET(ce_head_params(P, h, ldh, item_emb, B, V, d, answers, workspace, workspace_bytes));
-    if (!gout || !dh || !d_item_emb || (uintptr_t)dh % 16 != 0 || (uintptr_t)d_item_emb % 16 != 0) return -10;
+    if (!gout || !dh || !d_item_emb || !aligned16(dh) || !aligned16(d_item_emb)) return -10;
     RET(ce_head_attributes());
     hipStream_t st = (hipStream_t)stream;
     const int ndc = ce_ndc(d), rows = 32 * ce_dh_rb(ndc);
     const dim3 grid(P.S, cdiv(B, rows)), wg(ROW_THREADS);
-    const size_t smem_dh = (size_t)rows * (d + 4) * sizeof(float), smem_de = (size_t)CE_ROWS * (d + 4) * sizeof(float);
+    const size_t smem_dh = tile_smem(rows, d), smem_de = tile_smem(CE_ROWS, d);
     switch (ndc) {
         case 1: hipLaunchKernelGGL((ce_dh_kernel<4, 1>), grid, wg, smem_dh, st, P); break;
         case 2: hipLaunchKernelGGL((ce_dh_kernel<4, 2>), grid, wg, smem_dh, st, P); break;

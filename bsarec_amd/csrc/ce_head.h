@@ -1,20 +1,17 @@
 // Full-catalogue cross-entropy on an external hidden state (bsarec_ce_head_fwd / bsarec_ce_head_bwd, include/bsarec_hip.h):
 // loss = mean_b (lse_b - s(b, a_b)), d(h) and dE, without anything of size B x V.  Every kernel forms its scores again, 32 x 32
-// at a time, with v_mfma_f32_32x32x2_f32 -- the fmaf chain of fr_dot bit for bit -- through ONE routine (ce_scores), so the
-// backward's softmax is built from the bits the forward's row statistics were built from.
+// at a time, through score_tile (score_tile.h: the fmaf chain of fr_dot bit for bit), so the backward's softmax is built from
+// the bits the forward's row statistics were built from.
 //
 // Launch shape.  A workgroup is 4 waves; a wave owns 32 items of a 128-item block and RB row blocks of 32 rows whose h rows sit in
-// LDS (row stride d + 4 floats); item rows come from global memory, one float4 per lane and k-step of 4.  The MFMA takes its
-// two operands either way round, which decides what a lane holds of the 32 x 32 result:
-//   ROWS_IN_LANE  (A = items, B = h):  lane (l31, half) holds row l31 and the 16 items rho(r) + 4 half
-//   !ROWS_IN_LANE (A = h, B = items):  lane (l31, half) holds item l31 and the 16 rows rho(r) + 4 half
-// Either way register r of the result is the A operand of k-step r of a second MFMA whose k axis is the axis the lane holds 16
-// of, with no exchange through LDS: k-step r takes k = rho(r) from lanes 0..31 and k = rho(r) + 4 from lanes 32..63.
+// LDS (score_stage).  Whichever way round score_tile takes its operands (ROWS_IN_LANE: a lane holds one row and 16 items; else
+// one item and 16 rows), register r of the result is the A operand of k-step r of a second MFMA whose k axis is the axis the lane
+// holds 16 of, with no exchange through LDS: k-step r takes k = rho(r) from lanes 0..31 and k = rho(r) + 4 from lanes 32..63.
 //   forward:  ce_fwd_kernel   grid (S, ceil(B / 128)), ROWS_IN_LANE: a split owns a contiguous range of item blocks; per lane and
 //                             row block ONE online (max, sum), updated per block of 16 scores; merged over the two halves, then
 //                             over the waves in wave order -> (m, l)[split][row]
-//             ce_stat_kernel  one workgroup: merges the S partials of a row in split order -> m, log l; s(b, a_b) by the fmaf chain;
-//                             rows_out; the mean in a fixed order -> loss_out
+//             ce_stat_kernel  one workgroup: merges the S partials of a row in split order -> m, log l; s(b, a_b) by fr_dot;
+//                             rows_out; the mean in a fixed order (mean_of_1024) -> loss_out
 //   backward: ce_dh_kernel    grid (S, ceil(B / (32 RB))), ROWS_IN_LANE: G = exp((s - m) - log l) - [j == a]; acc[rows x d] += G . E with
 //                             E's rows as the B operand (32 consecutive floats per half-wave); the four waves' tiles are added
 //                             in wave order through LDS and stored to the split's slab.  RB x ceil(d / 32) <= 8 register tiles.
@@ -63,71 +60,17 @@ __device__ __forceinline__ unsigned ce_answer(const CeP& P, int b) {
     return (unsigned)(a < 0 ? 0 : (a >= P.V ? P.V - 1 : a));
 }
 #define CE_NO_ANSWER 0xffffffffu             // of a tile row behind B: no item index reaches it (V + 127 < 2^32)
-// the item blocks [b0, b1) of split s
-__device__ __forceinline__ void ce_split_range(const CeP& P, int s, int& b0, int& b1) {
-    b0 = (int)((long)s * P.nblk / P.S); b1 = (int)((long)(s + 1) * P.nblk / P.S);
-}
-// rows [r0, r0 + rows) of h into sh[rows][d + 4]; zeros behind row B
-__device__ __forceinline__ void ce_stage(const CeP& P, int r0, int rows, float* sh) {
-    const int dq = P.d >> 2, dp = P.d + 4;
-    for (int x = threadIdx.x; x < rows * dq; x += ROW_THREADS) {
-        const int i = x / dq, c = (x - i * dq) << 2;
-        f32x4 v = {0, 0, 0, 0};
-        if (r0 + i < P.B) v = ld4(P.h + (long)(r0 + i) * P.ldh + c);
-        st4(&sh[i * dp + c], v);
-    }
-}
-// A wave's 32 items i0 .. i0 + 31 as a wave-uniform row pointer into E and this lane's offset from it in floats (item i0 + l31);
-// an item behind V reads a row that exists.
-__device__ __forceinline__ const float* ce_items(const CeP& P, unsigned i0, unsigned& off) {
-    off = i0 + (threadIdx.x & 31) < (unsigned)P.V ? (threadIdx.x & 31) * (unsigned)P.d : 0u;
-    return P.E + (long)(i0 < (unsigned)P.V ? i0 : 0u) * P.d;
-}
-// The scores of RB row blocks (LDS rows 32 rb + l31 of sh) against the item of this lane (ebase + eoff, ce_items): the fmaf
-// chain over k = 0 .. d-1, whichever way round the operands go.
-template <int RB, bool ROWS_IN_LANE>
-__device__ __forceinline__ void ce_scores(const float* sh, const float* __restrict__ ebase, unsigned eoff, int d, f32x16 (&acc)[RB]) {
-    const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5, dp = d + 4;
-    const float4* e4 = reinterpret_cast<const float4*>(ebase + eoff);
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[rb][r] = 0.f;
-    for (int kc = 0; kc < d; kc += 4) {
-        const float4 e = e4[kc >> 2];
-        const float e0 = half ? e.y : e.x, e1 = half ? e.w : e.z;       // MFMA k-step: lanes 0..31 give k, lanes 32..63 k + 1
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            const float4 a = *reinterpret_cast<const float4*>(&sh[(rb * 32 + l31) * dp + kc]);
-            const float a0 = half ? a.y : a.x, a1 = half ? a.w : a.z;
-            if (ROWS_IN_LANE) {
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(e0, a0, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(e1, a1, acc[rb], 0, 0, 0);
-            } else {
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, e0, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, e1, acc[rb], 0, 0, 0);
-            }
-        }
-    }
-}
-// (m, l) <- the merge of two (max, sum of exp(. - max)) pairs; an empty pair is (-inf, 0)
-__device__ __forceinline__ void ce_merge(float& m, float& l, float m2, float l2) {
-    const float M = fmaxf(m, m2);
-    if (M == -INFINITY) return;
-    l = l * expf(m - M) + l2 * expf(m2 - M);
-    m = M;
-}
 
 // grid (S, row tiles).  Dynamic LDS: CE_ROWS x (d + 4) floats of h.
 __global__ void __launch_bounds__(ROW_THREADS) ce_fwd_kernel(const CeP P) {
-    extern __shared__ float sh[];
+    extern __shared__ __attribute__((aligned(16))) float sh[];
     __shared__ float wm[ROW_THREADS / 64][CE_ROWS], wl[ROW_THREADS / 64][CE_ROWS];
     constexpr int RB = CE_ROWS / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, half = lane >> 5;
     const int r0 = blockIdx.y * CE_ROWS;
     int b0, b1;
-    ce_split_range(P, blockIdx.x, b0, b1);
-    ce_stage(P, r0, CE_ROWS, sh);
+    split_range(blockIdx.x, P.nblk, P.S, b0, b1);           // this split's item blocks
+    score_stage(P.h, P.ldh, P.B, P.d, r0, CE_ROWS, sh);
     __syncthreads();
     float m[RB], l[RB];
 #pragma unroll
@@ -135,9 +78,9 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_fwd_kernel(const CeP P) {
     for (int ib = b0; ib < b1; ++ib) {
         const unsigned i0 = (unsigned)ib * CE_ITEMS + wave * 32;         // this wave's 32 items
         unsigned eoff;
-        const float* eb = ce_items(P, i0, eoff);
+        const float* eb = score_items(P.E, P.V, P.d, i0, eoff);
         f32x16 acc[RB];
-        ce_scores<RB, true>(sh, eb, eoff, P.d, acc);
+        score_tile<RB, true>(sh, eb, eoff, P.d, acc);
         const bool tail = i0 + 32 > (unsigned)P.V;
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
@@ -160,14 +103,14 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_fwd_kernel(const CeP P) {
     for (int rb = 0; rb < RB; ++rb) {
         const float m2 = __shfl_xor(m[rb], 32, 64), l2 = __shfl_xor(l[rb], 32, 64);
         float ma = half ? m2 : m[rb], la = half ? l2 : l[rb];            // both halves merge (half 0, half 1) in that order
-        ce_merge(ma, la, half ? m[rb] : m2, half ? l[rb] : l2);
+        softmax_merge(ma, la, half ? m[rb] : m2, half ? l[rb] : l2);
         if (half == 0) { wm[wave][rb * 32 + l31] = ma; wl[wave][rb * 32 + l31] = la; }
     }
     __syncthreads();
     if (tid < CE_ROWS && r0 + tid < P.B) {
         float mm = wm[0][tid], ll = wl[0][tid];
 #pragma unroll
-        for (int w = 1; w < ROW_THREADS / 64; ++w) ce_merge(mm, ll, wm[w][tid], wl[w][tid]);
+        for (int w = 1; w < ROW_THREADS / 64; ++w) softmax_merge(mm, ll, wm[w][tid], wl[w][tid]);
         P.pm[(long)blockIdx.x * P.B + r0 + tid] = mm;
         P.pl[(long)blockIdx.x * P.B + r0 + tid] = ll;
     }
@@ -175,12 +118,11 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_fwd_kernel(const CeP P) {
 
 // one workgroup of 1024 lanes: m, log l, rows_out, loss
 __global__ void __launch_bounds__(1024) ce_stat_kernel(const CeP P, float* __restrict__ loss_out, float* __restrict__ rows_out) {
-    __shared__ float red[1024];
     const int tid = threadIdx.x;
     float sum = 0.f;
     for (int b = tid; b < P.B; b += 1024) {
-        float m = -INFINITY, l = 0.f;
-        for (int s = 0; s < P.S; ++s) ce_merge(m, l, P.pm[(long)s * P.B + b], P.pl[(long)s * P.B + b]);
+        const SoftmaxPart part = softmax_merge_splits(P, P.B, b);
+        const float m = part.m, l = part.l;
         const float logl = logf(l);
         const float row = (m - fr_dot(P.h + (long)b * P.ldh, P.E + (long)ce_answer(P, b) * P.d, P.d)) + logl;
         P.m[b] = m;
@@ -188,25 +130,19 @@ __global__ void __launch_bounds__(1024) ce_stat_kernel(const CeP P, float* __res
         if (rows_out) rows_out[b] = row;
         sum += row;
     }
-    red[tid] = sum;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) *loss_out = red[0] / (float)P.B;
+    mean_of_1024(sum, P.B, loss_out);
 }
 
 // grid (S, ceil(B / (32 RB))).  Dynamic LDS: 32 RB x (d + 4) floats: the h tile, then the waves' sum.
 template <int RB, int NDC>
 __global__ void __launch_bounds__(ROW_THREADS) ce_dh_kernel(const CeP P) {
-    extern __shared__ float sh[];
+    extern __shared__ __attribute__((aligned(16))) float sh[];
     constexpr int ROWS = 32 * RB;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, half = lane >> 5;
     const int r0 = blockIdx.y * ROWS, dp = P.d + 4;
     int b0, b1;
-    ce_split_range(P, blockIdx.x, b0, b1);
-    ce_stage(P, r0, ROWS, sh);
+    split_range(blockIdx.x, P.nblk, P.S, b0, b1);           // this split's item blocks
+    score_stage(P.h, P.ldh, P.B, P.d, r0, ROWS, sh);
     float mx[RB], logl[RB];
     unsigned ans[RB];
 #pragma unroll
@@ -227,9 +163,9 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_dh_kernel(const CeP P) {
     for (int ib = b0; ib < b1; ++ib) {
         const unsigned i0 = (unsigned)ib * CE_ITEMS + wave * 32;
         unsigned eoff;
-        const float* eb = ce_items(P, i0, eoff);
+        const float* eb = score_items(P.E, P.V, P.d, i0, eoff);
         f32x16 acc[RB];
-        ce_scores<RB, true>(sh, eb, eoff, P.d, acc);
+        score_tile<RB, true>(sh, eb, eoff, P.d, acc);
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -289,7 +225,7 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_dh_sum_kernel(const CeP P, con
 // one workgroup per item block.  Dynamic LDS: CE_ROWS x (d + 4) floats of h.
 template <int NDC>
 __global__ void __launch_bounds__(ROW_THREADS) ce_de_kernel(const CeP P, const float* __restrict__ gout, float* __restrict__ dE) {
-    extern __shared__ float sh[];
+    extern __shared__ __attribute__((aligned(16))) float sh[];
     __shared__ float m_s[CE_ROWS], logl_s[CE_ROWS];
     __shared__ unsigned ans_s[CE_ROWS];
     constexpr int RB = CE_ROWS / 32;
@@ -297,7 +233,7 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_de_kernel(const CeP P, const f
     const int dp = P.d + 4;
     const unsigned i0 = blockIdx.x * CE_ITEMS + wave * 32, mine = i0 + l31;
     unsigned eoff;
-    const float* eb = ce_items(P, i0, eoff);
+    const float* eb = score_items(P.E, P.V, P.d, i0, eoff);
     f32x16 out[NDC];
 #pragma unroll
     for (int dc = 0; dc < NDC; ++dc)
@@ -305,7 +241,7 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_de_kernel(const CeP P, const f
         for (int r = 0; r < 16; ++r) out[dc][r] = 0.f;
     for (int r0 = 0; r0 < P.B; r0 += CE_ROWS) {
         __syncthreads();
-        ce_stage(P, r0, CE_ROWS, sh);
+        score_stage(P.h, P.ldh, P.B, P.d, r0, CE_ROWS, sh);
         if (tid < CE_ROWS) {
             m_s[tid] = r0 + tid < P.B ? P.m[r0 + tid] : 0.f;
             logl_s[tid] = r0 + tid < P.B ? P.logl[r0 + tid] : 0.f;
@@ -313,7 +249,7 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_de_kernel(const CeP P, const f
         }
         __syncthreads();
         f32x16 acc[RB];
-        ce_scores<RB, false>(sh, eb, eoff, P.d, acc);
+        score_tile<RB, false>(sh, eb, eoff, P.d, acc);
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
 #pragma unroll

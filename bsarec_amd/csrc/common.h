@@ -211,6 +211,45 @@ __device__ __forceinline__ void lds_barrier() {
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
+// Register r of a 32 x 32 MFMA result in lane (l31, half) is row rho(r) + 4 half, column l31.
+__device__ __forceinline__ int rho(int r) { return (r & 3) + 8 * (r >> 2); }
+
+// ---------------------------------------------------------------------------------------------
+// Online-softmax partials of the split heads (ce_head.h, info_nce.h): a row's (max, sum of exp(. - max)) per split, merged
+// in split order, and the mean of the rows in a fixed order.  The order of every sum is part of those heads' contract.
+// ---------------------------------------------------------------------------------------------
+// (m, l) <- the merge of two (max, sum of exp(. - max)) pairs; an empty pair is (-inf, 0)
+__device__ __forceinline__ void softmax_merge(float& m, float& l, float m2, float l2) {
+    const float M = fmaxf(m, m2);
+    if (M == -INFINITY) return;
+    l = l * expf(m - M) + l2 * expf(m2 - M);
+    m = M;
+}
+// the units [u0, u1) of split s, of n units in S splits
+__device__ __forceinline__ void split_range(int s, int n, int S, int& u0, int& u1) {
+    u0 = (int)((long)s * n / S); u1 = (int)((long)(s + 1) * n / S);
+}
+// (m, l) of row r of n: the S partials P.pm / P.pl [split][row] of a head's parameter block, merged in split order
+struct SoftmaxPart { float m, l; };
+template <class HeadP>
+__device__ __forceinline__ SoftmaxPart softmax_merge_splits(const HeadP& P, int n, int r) {
+    float m = -INFINITY, l = 0.f;
+    for (int s = 0; s < P.S; ++s) softmax_merge(m, l, P.pm[(long)s * n + r], P.pl[(long)s * n + r]);
+    return SoftmaxPart{m, l};
+}
+// *out = (the 1024 lanes' sums, added by an LDS tree) / n.  Called by every lane of a 1024-lane workgroup.
+__device__ __forceinline__ void mean_of_1024(float sum, int n, float* out) {
+    __shared__ float red[1024];
+    const int tid = threadIdx.x;
+    red[tid] = sum;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) *out = red[0] / (float)n;
+}
+
 // ---------------------------------------------------------------------------------------------
 // bf16 pieces shared by the bf16 modes (fused bf16 storage, bf16 products of the generic tiled GEMM): two bf16 per dword
 // (element 2j in the low half), v_cvt_pk_bf16_f32 rounding (nearest even), v_mfma_f32_32x32x16_bf16 with fp32 accumulation.

@@ -3,22 +3,23 @@
 // the result are those of topk_seen_kernel on the materialised matrix.  Launch sequence on one stream (no host synchronisation):
 //   (1) full_rank_sample_kernel: score s strided columns per row (seen items as 0), tau_b = a composite no larger than the
 //       sample's k-th (key << 32 | ~column) composite -- a lower bound on the row's true k-th composite;
-//   (2) full_rank_filter_kernel: (128-row tile x item range) grid, h tile in LDS, items through v_mfma_f32_32x32x2_f32; an
-//       item survives when its raw composite or its composite as a seen zero is >= tau_b, and is appended (column, raw
-//       score) to the row's list with one atomic per half-wave; the count grows past the capacity;
+//   (2) full_rank_filter_kernel: (128-row tile x item range) grid, the scores of 128 rows x 32 items per wave by score_tile
+//       (score_tile.h); an item survives when its raw composite or its composite as a seen zero is >= tau_b, and is appended
+//       (column, raw score) to the row's list with one atomic per half-wave; the count grows past the capacity;
 //   (3) FR_ROUNDS x { full_rank_rethreshold_kernel: for an overflowed row, the k-th of min(raw, zero) composites over the
 //       first `cap` stored items is a tighter bound; filter again, overflowed rows only (the others keep tau = ~0) };
 //   (4) full_rank_select_kernel: rows within capacity: seen candidates set to +0 (LDS hash of the CSR row, 2048 entries per
 //       chunk), radix select of the k-th composite, compaction, bitonic sort;
 //   (5) full_rank_fallback_kernel: rows still over capacity: exact streaming top-k over 2048-item segments, rescoring the
 //       row (seen bits of a segment in LDS), O(k) state.
-// Every score is the fmaf chain of fr_dot: acc = 0, then acc = fmaf(h[i], e[i], acc) for i = 0 .. d-1 -- which is what the
-// fp32 MFMA computes bit for bit (one rounding per product, k ascending), so all five kernels see identical scores.
+// Every score is the fmaf chain of fr_dot: acc = 0, then acc = fmaf(h[i], e[i], acc) for i = 0 .. d-1 -- which is what
+// score_tile computes bit for bit, so all five kernels see identical scores.
 // Column base (bsarec_topk_full_range): E holds rows [base, base + V) of a larger catalogue.  Columns, composites and list
 // entries stay LOCAL (0 .. V), so the tie order inside the range is the global one; the base enters where a GLOBAL id crosses
 // the interface only: a CSR entry `it` applies iff 0 <= it - base < V, and fr_write adds the base to the ids it stores.
 #pragma once
 #include "rank.h"
+#include "score_tile.h"
 
 #define FR_ROWS 128                        // rows per filter tile: 4 row blocks of the 32 x 32 MFMA
 #define FR_ITEMS 128                       // items per filter step: 4 waves x 32
@@ -92,11 +93,11 @@ full_rank_sample_kernel(const float* __restrict__ h, long ldh, const float* __re
 __global__ void __launch_bounds__(ROW_THREADS)
 full_rank_filter_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ E, int B, int V, int d, int cap,
                         const unsigned long long* __restrict__ tau, unsigned* count, unsigned long long* list) {
-    extern __shared__ float sh[];
+    extern __shared__ __attribute__((aligned(16))) float sh[];
     __shared__ unsigned long long tau_s[FR_ROWS];
     __shared__ unsigned lo_s[FR_ROWS];
     __shared__ int any;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, half = lane >> 5;
     const int r0 = blockIdx.x * FR_ROWS;
     if (tid == 0) any = 0;
     __syncthreads();
@@ -109,32 +110,17 @@ full_rank_filter_kernel(const float* __restrict__ h, long ldh, const float* __re
     }
     __syncthreads();
     if (!any) return;                                    // a re-threshold round with no overflowed row in this tile
-    const int dp = d + 4;
-    for (int x = tid; x < FR_ROWS * d; x += ROW_THREADS) {
-        const int i = x / d, c = x - i * d;
-        sh[i * dp + c] = r0 + i < B ? h[(long)(r0 + i) * ldh + c] : 0.f;
-    }
+    score_stage(h, ldh, B, d, r0, FR_ROWS, sh);
     __syncthreads();
     const int nblk = (V + FR_ITEMS - 1) / FR_ITEMS;
     for (int ib = blockIdx.y; ib < nblk; ib += gridDim.y) {
-        const int item = ib * FR_ITEMS + wave * 32 + l31;
+        const unsigned i0 = (unsigned)ib * FR_ITEMS + wave * 32;         // this wave's 32 items
+        const int item = (int)i0 + l31;
         const bool iv = item < V;
-        const float4* e4 = reinterpret_cast<const float4*>(E + (long)(iv ? item : 0) * d);
+        unsigned eoff;
+        const float* eb = score_items(E, V, d, i0, eoff);
         f32x16 acc[4];
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[rb][r] = 0.f;
-        for (int kc = 0; kc < d; kc += 4) {
-            const float4 e = e4[kc >> 2];
-            const float b0 = half ? e.y : e.x, b1 = half ? e.w : e.z;   // MFMA k-step: lanes 0..31 give k, lanes 32..63 k + 1
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb) {
-                const float4 a = *reinterpret_cast<const float4*>(&sh[(rb * 32 + l31) * dp + kc]);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? a.y : a.x, b0, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? a.w : a.z, b1, acc[rb], 0, 0, 0);
-            }
-        }
+        score_tile<4, false>(sh, eb, eoff, d, acc);
         const unsigned long long zc = rank_comp(FR_KEY0, (unsigned)item);
 #pragma unroll
         for (int rb = 0; rb < 4; ++rb)

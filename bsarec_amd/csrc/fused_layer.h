@@ -98,8 +98,6 @@ __device__ __forceinline__ float gld(const float* p) { return *(const AS_GLOBAL 
 __device__ __forceinline__ void gst(float* p, float v) { *(AS_GLOBAL float*)p = v; }
 __device__ __forceinline__ int gldi(const int* p) { return *(const AS_GLOBAL int*)p; }
 
-__device__ __forceinline__ int rho(int r) { return (r & 3) + 8 * (r >> 2); }
-
 // ---------------------------------------------------------------------------------------------
 // bf16 storage (cfg.storage = 1, config C2).  BF = true instantiations keep every tensor that crosses a kernel boundary
 // inside the block stack -- the activations saved for the backward, the inter-block gradients, the operands of the

@@ -12,7 +12,7 @@
 //             nce_fwd_kernel  per (split, row tile): an online (max, sum) per lane, merged over the 16 lanes of a row by a
 //                             shuffle butterfly, one (m, l) per (split, row); the lane that holds column pos(r) stores s_pos
 //             nce_stat_kernel one workgroup: merges the S partials of a row in split order -> lse, rows_out; the mean in a
-//                             fixed order (lane-strided sums, then an LDS tree) -> loss_out
+//                             fixed order (lane-strided sums, then mean_of_1024's LDS tree) -> loss_out
 //   backward: nce_bwd_kernel  per (split, row tile): the score tile again, W_rc = exp(s - lse_r) + exp(s - lse_c) through
 //                             LDS, acc[64 x d] += W . u_keys (lanes re-mapped to rows 4 ty + i, columns 4 tx + j of a 64-column
 //                             chunk of d, W read k-major), stored to the split's slab
@@ -104,19 +104,6 @@ __device__ __forceinline__ void nce_scores(const NceP& P, int r0, int c0, float 
     }
 }
 
-// (m, l) <- the merge of two (max, sum of exp(. - max)) pairs; an empty pair is (-inf, 0)
-__device__ __forceinline__ void nce_merge(float& m, float& l, float m2, float l2) {
-    const float M = fmaxf(m, m2);
-    if (M == -INFINITY) return;
-    l = l * expf(m - M) + l2 * expf(m2 - M);
-    m = M;
-}
-
-// the key tiles [t0, t1) of split s
-__device__ __forceinline__ void nce_split_range(const NceP& P, int s, int& t0, int& t1) {
-    t0 = (int)((long)s * P.T / P.S); t1 = (int)((long)(s + 1) * P.T / P.S);
-}
-
 // clamped norms, one wave per row
 __global__ void __launch_bounds__(ROW_THREADS) nce_norm_kernel(const NceP P) {
     const int r = blockIdx.x * (ROW_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -135,7 +122,7 @@ __global__ void __launch_bounds__(ROW_THREADS) nce_fwd_kernel(const NceP P) {
     __shared__ __attribute__((aligned(16))) float Ks[NCE_TILE][NCE_LDP];
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15, r0 = blockIdx.y * NCE_TILE;
     int t0, t1;
-    nce_split_range(P, blockIdx.x, t0, t1);
+    split_range(blockIdx.x, P.T, P.S, t0, t1);              // this split's key tiles
     float m[4], l[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { m[i] = -INFINITY; l[i] = 0.f; }
@@ -169,7 +156,7 @@ __global__ void __launch_bounds__(ROW_THREADS) nce_fwd_kernel(const NceP P) {
 #pragma unroll
         for (int off = 1; off < 16; off <<= 1) {
             const float m2 = __shfl_xor(m[i], off, 64), l2 = __shfl_xor(l[i], off, 64);
-            nce_merge(m[i], l[i], m2, l2);
+            softmax_merge(m[i], l[i], m2, l2);
         }
         const int r = r0 + ty + 16 * i;
         if (tx == 0 && r < P.n) { P.pm[(long)blockIdx.x * P.n + r] = m[i]; P.pl[(long)blockIdx.x * P.n + r] = l[i]; }
@@ -178,25 +165,18 @@ __global__ void __launch_bounds__(ROW_THREADS) nce_fwd_kernel(const NceP P) {
 
 // one workgroup of 1024 lanes: lse, rows_out, loss
 __global__ void __launch_bounds__(1024) nce_stat_kernel(const NceP P, float* __restrict__ loss_out, float* __restrict__ rows_out) {
-    __shared__ float red[1024];
     const int tid = threadIdx.x;
     float sum = 0.f;
     for (int r = tid; r < P.n; r += 1024) {
-        float m = -INFINITY, l = 0.f;
-        for (int s = 0; s < P.S; ++s) nce_merge(m, l, P.pm[(long)s * P.n + r], P.pl[(long)s * P.n + r]);
+        const SoftmaxPart part = softmax_merge_splits(P, P.n, r);
+        const float m = part.m, l = part.l;
         const float lse = m + logf(l);
         const float row = lse - P.spos[r];
         P.lse[r] = lse;
         if (rows_out) rows_out[r] = row;
         sum += row;
     }
-    red[tid] = sum;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) *loss_out = red[0] / (float)P.n;
+    mean_of_1024(sum, P.n, loss_out);
 }
 
 // grid (S, T); NCH = ceil(d / 64) chunks of the output columns
@@ -208,7 +188,7 @@ __global__ void __launch_bounds__(ROW_THREADS) nce_bwd_kernel(const NceP P) {
     __shared__ float lse_q[NCE_TILE], lse_k[NCE_TILE];
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15, r0 = blockIdx.y * NCE_TILE;
     int t0, t1;
-    nce_split_range(P, blockIdx.x, t0, t1);
+    split_range(blockIdx.x, P.T, P.S, t0, t1);              // this split's key tiles
     if (tid < NCE_TILE) lse_q[tid] = r0 + tid < P.n ? P.lse[r0 + tid] : 0.f;
     float acc[NCH][4][4];
 #pragma unroll

@@ -5,6 +5,7 @@
 // wave covers 64/LPR rows and row statistics are intra-wave shuffles.
 #pragma once
 #include "common.h"
+#include "../../include/bsarec_hip.h"          // BSAREC_MAX_LAYERS
 
 #define ROW_THREADS 256
 #include "lazy_adam.h"

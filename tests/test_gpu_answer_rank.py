@@ -208,6 +208,15 @@ def test_corners():
     wide[:, :d] = ht
     wide[:, d:] = 99.0
     assert_same(rank_range(wide[:, :d], Et, seen, answers), want)
+    # ldh % 4 != 0: the tile is staged float by float.  Two row tiles (128 + 2 rows), two full item blocks and a tail whose
+    # second wave is part-filled, a k count (68) that is no multiple of 32
+    h2, E2, S2, seen2, ans2 = int_case(130, 300, 68, seed=31)
+    odd = torch.full((130, 69), 99.0, device="cuda")
+    odd[:, :68] = torch.from_numpy(h2).cuda()
+    assert odd.data_ptr() % 16 == 0 and odd[:, :68].stride(0) == 69
+    want2 = A.ranks(S2, seen2, ans2)
+    assert_same(rank_range(odd[:, :68], torch.from_numpy(E2).cuda(), seen2, ans2), want2, "ldh = d + 1")
+    assert_same(rank_range(odd[:, :68], torch.from_numpy(E2).cuda(), seen2, ans2, scores=False), want2, "ldh = d + 1, no scores")
     # an answer outside [0, V): -1 and NaN, and the other rows as before
     out = answers.copy()
     out[[0, 3, 6]] = [-1, V, 2 ** 40]

@@ -86,7 +86,8 @@ def int_case(B, V, d, seed, lo=-3, hi=3, seen_kind="mixed", k=20):
 def check_exact(h, E, S, seen, k, caps=(0,)):
     if not torch.is_tensor(S):
         S = torch.from_numpy(S).cuda()
-    ht, Et = torch.from_numpy(h).cuda(), torch.from_numpy(E).cuda()
+    ht = h if torch.is_tensor(h) else torch.from_numpy(h).cuda()       # (a device tensor keeps its row stride)
+    Et = torch.from_numpy(E).cuda()
     di, dv = dense(S, seen, k)
     if S.numel() <= 5_000_000:                   # the numpy restatement where it is quick
         ri, rv = R.topk(S.cpu().numpy(), seen if seen is not None else [[]] * S.shape[0], k)
@@ -115,6 +116,23 @@ def test_bit_exact_against_dense_on_integer_data(B, V, d, k):
 def test_forced_overflow_gives_identical_lists(B, V, d, k):
     h, E, S, seen = int_case(B, V, d, seed=11 + V, k=k)
     check_exact(h, E, S, seen, k, caps=(0, k, k + 37 if (k + 37) % 2 else k + 38, 4 * k + 1))
+
+
+def test_row_stride_not_a_multiple_of_four():
+    """h = wide[:, :d] of a (B, d + 1) buffer whose pad column holds 99: the tile is staged float by float.  130 rows: a full
+    row tile and one of two rows; 300 items: two full item blocks and a tail whose second wave is part-filled and whose third
+    and fourth are empty; d = 68: a k count that is no multiple of 32."""
+    B, V, d, k = 130, 300, 68, 20
+    h, E, S, seen = int_case(B, V, d, seed=23, k=k)
+    wide = torch.full((B, d + 1), 99.0, device="cuda")
+    wide[:, :d] = torch.from_numpy(h).cuda()
+    hv = wide[:, :d]
+    assert hv.data_ptr() % 16 == 0 and hv.stride(0) == d + 1
+    check_exact(hv, E, S, seen, k)
+    ci, cv = fused(torch.from_numpy(h).cuda(), torch.from_numpy(E).cuda(), seen, k)
+    fi, fv = fused(hv, torch.from_numpy(E).cuda(), seen, k)
+    np.testing.assert_array_equal(fi, ci)
+    np.testing.assert_array_equal(fv.view(np.uint32), cv.view(np.uint32))
 
 
 def test_negative_rows_seen_zeros_win_and_all_zero_table():
