@@ -197,6 +197,13 @@ EXPORTS = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
     "bsarec_ce_head_bwd": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bsarec_ce_head_range_workspace_bytes": (C.c_long, [C.c_int] * 3),
+    "bsarec_ce_head_range_stats": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
+    "bsarec_ce_head_range_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "bsarec_ce_head_range_bwd": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

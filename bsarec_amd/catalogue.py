@@ -35,6 +35,15 @@ one GPU) -- the head rows above become, per rank:
   owner pull       every owner adds the answer rows of its items and the rank-ordered sum of the candidate partials
   Adam             shard: dense (dE zeroed once per step), or lazy over the owned rows the step touched
 
+Full-catalogue CE without the partial logits (opt-in, ``shard_ce_head = "fused"``) -- the same loss and gradients as
+the head rows of the first table, with no [Bg, Vs] buffer: between the all-gathers and the all-reduce of d h_last,
+
+  statistics       ``bsarec_ce_head_range_stats`` over the owned rows with their column base: per-row (max, sum exp, target score)
+  all-gather       the statistics [W, 3, Bg], as above
+  merge            ``bsarec_ce_head_range_merge``: the whole catalogue's (max, log sum) per row, loss rows, loss (the same bits on
+                   every rank)
+  head backward    ``bsarec_ce_head_range_bwd``: the scores are formed again; dE of the owned rows and the partial d h_last
+
 Evaluation (``topk`` / ``full_sort_scores``) ranks the owned rows for all Bg sequences and merges the ranks' lists.
 ``eval_full_rank`` (the single-GPU flag) picks how a rank gets its list: "dense" (default) materialises the partial logits
 [Bg, Vs]; "fused" calls ``bsarec_topk_full_range`` over the shard with its column base -- O(Bg (s + cap)) working memory, no
@@ -57,6 +66,9 @@ from .ranking import (EVAL_FULL_RANK, REFERENCE_KS, FullRank, answer_rank, answe
                       metrics_post_fix, topk_seen)
 
 
+SHARD_CE_HEADS = ("dense", "fused")
+
+
 class ShardedCatalogue:
     """One rank of the catalogue-sharded step.  ``args`` are the reference's (global ``item_size``); ``batch`` is the
     per-rank batch size (fixed: the staging table and the encoder plan are sized by it)."""
@@ -73,6 +85,12 @@ class ShardedCatalogue:
         if getattr(args, "storage", None) == "bf16":
             raise ValueError("catalogue sharding is fp32 only")
         eval_full_rank_of(args)
+        self.ce_head = getattr(args, "shard_ce_head", "dense")
+        if self.ce_head not in SHARD_CE_HEADS:
+            raise ValueError(f"shard_ce_head = {self.ce_head!r}, expected one of {SHARD_CE_HEADS}")
+        if self.ce_head == "fused" and self.N:
+            raise ValueError("shard_ce_head = 'fused' is the full-catalogue CE head: the sampled-softmax head "
+                             f"(train_negatives = {self.N}) has no full CE")
         if torch.device(device).type != "cuda":        # before the process group, the IPC mappings and any allocation
             head_name = (f"sampled-softmax head, train_negatives = {self.N}" if self.N else "full-catalogue CE head")
             raise ValueError(f"ShardedCatalogue: the catalogue-sharded step ({head_name}) runs on the GPU only, "
@@ -120,10 +138,19 @@ class ShardedCatalogue:
         self.ld = (max(self.Vs, 1) + 3) // 4 * 4
         self.logits = self.h_all = None
         if self.N == 0:
-            self._full_head_buffers()
             self.stats = torch.zeros(3, self.Bg, dtype=torch.float32, device=self.device)
             self.stats_all = torch.zeros(self.W, 3, self.Bg, dtype=torch.float32, device=self.device)
             self.dh = torch.zeros(self.Bg, d, dtype=torch.float32, device=self.device)
+        if self.N == 0 and self.ce_head == "fused":     # no partial logits, no split-K scratch: the workspace of ce_head.h
+            self._gathered_h_buffer()
+            self.ce_ws_bytes = self.lib.bsarec_ce_head_range_workspace_bytes(self.Bg, self.Vs, d)
+            if self.ce_ws_bytes <= 0:
+                raise ValueError(f"shard_ce_head = 'fused' does not support Bg={self.Bg} Vs={self.Vs} d={d}")
+            self.ce_ws = torch.zeros(self.ce_ws_bytes, dtype=torch.uint8, device=self.device)
+            self.ce_g = torch.ones(1, dtype=torch.float32, device=self.device)
+            self.ce_base = min(self.lo, V)          # a rank behind the last row owns the empty range [V, V)
+        elif self.N == 0:
+            self._full_head_buffers()
             self.scratch = torch.zeros(max(1, self.lib.bsarec_shard_head_bwd_scratch_floats(self.Bg, self.Vs, d)),
                                        dtype=torch.float32, device=self.device)
         self.ans_all = torch.zeros(self.Bg, dtype=torch.int64, device=self.device)
@@ -255,17 +282,10 @@ class ShardedCatalogue:
         dist.all_gather(list(self.h_all.view(W, B, d).unbind(0)), h_last, group=g)
         dist.all_gather(list(self.ans_all.view(W, B).unbind(0)), ans, group=g)
         dist.all_gather(list(self.ids_all.unbind(0)), ids.view(-1), group=g)
-        L.check(lib.bsarec_shard_logits(self.h_all.data_ptr(), d, Bg, self.E.data_ptr(), self.Vs, d, self.logits.data_ptr(),
-                                        self.ld, st), "bsarec_shard_logits")
-        L.check(lib.bsarec_shard_ce_stats(self.logits.data_ptr(), self.ld, Bg, self.Vs, self.ans_all.data_ptr(), self.lo, self.V,
-                                          self.stats.data_ptr(), st), "bsarec_shard_ce_stats")
-        dist.all_gather(list(self.stats_all.unbind(0)), self.stats, group=g)
-        L.check(lib.bsarec_shard_ce_grad(self.logits.data_ptr(), self.ld, Bg, self.Vs, self.ans_all.data_ptr(), self.lo, self.V,
-                                         self.stats_all.data_ptr(), W, self.loss_rows.data_ptr(), self.loss.data_ptr(), st),
-                "bsarec_shard_ce_grad")
-        L.check(lib.bsarec_shard_head_bwd(self.logits.data_ptr(), self.ld, Bg, self.Vs, self.h_all.data_ptr(), d,
-                                          self.E.data_ptr(), d, self.dE.data_ptr(), self.dh.data_ptr(), self.scratch.data_ptr(), st),
-                "bsarec_shard_head_bwd")
+        if self.ce_head == "fused":
+            self._fused_ce_head(st)
+        else:
+            self._dense_ce_head(st)
         dist.all_reduce(self.dh, op=dist.ReduceOp.SUM, group=g)
         self.d_out[:, Lq - 1, :] = self.dh[self.rank * B:(self.rank + 1) * B]
         L.check(lib.bsarec_backward_seq(plan.handle, self.d_out.data_ptr(), st), "bsarec_backward_seq")
@@ -280,6 +300,37 @@ class ShardedCatalogue:
             ae = self._adam(self.E.data_ptr(), self.dE.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.Vs * d)
             L.check(lib.bsarec_adam_apply(C.byref(ae), enc._state.data_ptr(), st), "bsarec_adam_apply")
         return self.loss[0]
+
+    def _dense_ce_head(self, st):
+        """The full-CE head over the partial logits [Bg, Vs]: ``loss_rows``, ``loss``, ``dE`` of the owned rows and this rank's
+        part of ``dh``, from ``h_all`` and ``ans_all``."""
+        import torch.distributed as dist
+        lib, d, W, Bg = self.lib, self.d, self.W, self.Bg
+        L.check(lib.bsarec_shard_logits(self.h_all.data_ptr(), d, Bg, self.E.data_ptr(), self.Vs, d, self.logits.data_ptr(),
+                                        self.ld, st), "bsarec_shard_logits")
+        L.check(lib.bsarec_shard_ce_stats(self.logits.data_ptr(), self.ld, Bg, self.Vs, self.ans_all.data_ptr(), self.lo, self.V,
+                                          self.stats.data_ptr(), st), "bsarec_shard_ce_stats")
+        dist.all_gather(list(self.stats_all.unbind(0)), self.stats, group=self.group)
+        L.check(lib.bsarec_shard_ce_grad(self.logits.data_ptr(), self.ld, Bg, self.Vs, self.ans_all.data_ptr(), self.lo, self.V,
+                                         self.stats_all.data_ptr(), W, self.loss_rows.data_ptr(), self.loss.data_ptr(), st),
+                "bsarec_shard_ce_grad")
+        L.check(lib.bsarec_shard_head_bwd(self.logits.data_ptr(), self.ld, Bg, self.Vs, self.h_all.data_ptr(), d,
+                                          self.E.data_ptr(), d, self.dE.data_ptr(), self.dh.data_ptr(), self.scratch.data_ptr(), st),
+                "bsarec_shard_head_bwd")
+
+    def _fused_ce_head(self, st):
+        """The same outputs without the partial logits (``shard_ce_head = "fused"``): the range form of ce_head.h."""
+        import torch.distributed as dist
+        lib, d, W, Bg = self.lib, self.d, self.W, self.Bg
+        h, E, a, ws = self.h_all.data_ptr(), self.E.data_ptr(), self.ans_all.data_ptr(), self.ce_ws.data_ptr()
+        L.check(lib.bsarec_ce_head_range_stats(h, d, E, Bg, self.Vs, self.ce_base, self.V, d, a, self.stats.data_ptr(), ws,
+                                               self.ce_ws_bytes, st), "bsarec_ce_head_range_stats")
+        dist.all_gather(list(self.stats_all.unbind(0)), self.stats, group=self.group)
+        L.check(lib.bsarec_ce_head_range_merge(self.stats_all.data_ptr(), W, Bg, ws, self.ce_ws_bytes, self.loss_rows.data_ptr(),
+                                               self.loss.data_ptr(), st), "bsarec_ce_head_range_merge")
+        L.check(lib.bsarec_ce_head_range_bwd(h, d, E, Bg, self.Vs, self.ce_base, self.V, d, a, self.ce_g.data_ptr(), ws,
+                                             self.ce_ws_bytes, self.dh.data_ptr(), self.dE.data_ptr(), st),
+                "bsarec_ce_head_range_bwd")
 
     def _sampled_step(self, plan, ids, ans, st) -> torch.Tensor:
         """The rest of :meth:`train_step` under the sampled-softmax head (module docstring; include/bsarec_shard.h)."""

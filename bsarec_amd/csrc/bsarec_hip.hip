@@ -2016,15 +2016,24 @@ extern "C" long bsarec_ce_head_workspace_bytes(int B, int V, int d) {
     return ce_workspace_floats(B, V, d) * (long)sizeof(float);
 }
 
-static int ce_head_params(CeP& P, const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* answers,
-                          void* workspace, long workspace_bytes) {
-    RET(ce_head_shape_check(B, V, d));
+// A range without rows (Vs = 0) keeps the workspace of one row.
+extern "C" long bsarec_ce_head_range_workspace_bytes(int Bg, int Vs, int d) {
+    if (Vs < 0) return -10;
+    return bsarec_ce_head_workspace_bytes(Bg, Vs > 1 ? Vs : 1, d);
+}
+
+// item_emb: rows [base, base + V) of a catalogue of N rows (the single-table entry points: base 0, N = V >= 1)
+static int ce_head_params(CeP& P, const float* h, long ldh, const float* item_emb, int B, int V, long base, long N, int d,
+                          const int64_t* answers, void* workspace, long workspace_bytes) {
+    if (V < 0 || base < 0 || base + V > N || N > 2147483647L) return -10;
+    RET(ce_head_shape_check(B, V > 1 ? V : 1, d));
     if (ldh < d || ldh % 4 != 0) return -10;
     if (!h || !item_emb || !answers || !workspace) return -10;
     if (!aligned16(h) || !aligned16(item_emb) || !aligned16(workspace)) return -10;
-    if (workspace_bytes < bsarec_ce_head_workspace_bytes(B, V, d)) return -10;
+    if (workspace_bytes < bsarec_ce_head_range_workspace_bytes(B, V, d)) return -10;
     P.h = h; P.ldh = ldh; P.E = item_emb; P.ans = answers;
     P.B = B; P.V = V; P.d = d; P.S = ce_splits(B, V); P.nblk = ce_nblk(V);
+    P.N = (int)N; P.base = base;
     float* w = (float*)workspace;
     P.m = w; P.logl = w + B; P.pm = w + 2L * B; P.pl = P.pm + (long)P.S * B; P.slab = w + ce_stat_floats(B, P.S);
     return 0;
@@ -2042,33 +2051,30 @@ static int ce_head_attributes() {
 extern "C" int bsarec_ce_head_fwd(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* answers,
                                   float* loss_out, float* rows_out, void* workspace, long workspace_bytes, void* stream) {
     CeP P;
-    RET(ce_head_params(P, h, ldh, item_emb, B, V, d, answers, workspace, workspace_bytes));
+    if (V < 1) return -10;
+    RET(ce_head_params(P, h, ldh, item_emb, B, V, 0, V, d, answers, workspace, workspace_bytes));
     if (!loss_out) return -10;
     RET(ce_head_attributes());
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ce_fwd_kernel, dim3(P.S, cdiv(B, CE_ROWS)), dim3(ROW_THREADS), tile_smem(CE_ROWS, d), st, P);
-    hipLaunchKernelGGL(ce_stat_kernel, dim3(1), dim3(1024), 0, st, P, loss_out, rows_out);
+    hipLaunchKernelGGL(ce_stat_kernel<false>, dim3(1), dim3(1024), 0, st, P, loss_out, rows_out);
     return (int)hipGetLastError();
 }
 
-extern "C" int bsarec_ce_head_bwd(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* answers,
-                                  const float* gout, void* workspace, long workspace_bytes, float* dh, float* d_item_emb,
-                                  void* stream) {
-    CeP P;
-    RET(ce_head_params(P, h, ldh, item_emb, B, V, d, answers, workspace, workspace_bytes));
+// d(h) of P's rows of E (the slabs in split order, times g / B) and dE of those rows, from the m and log l in the workspace
+static int ce_head_bwd_launch(const CeP& P, const float* gout, float* dh, float* d_item_emb, hipStream_t st) {
     if (!gout || !dh || !d_item_emb || !aligned16(dh) || !aligned16(d_item_emb)) return -10;
     RET(ce_head_attributes());
-    hipStream_t st = (hipStream_t)stream;
-    const int ndc = ce_ndc(d), rows = 32 * ce_dh_rb(ndc);
-    const dim3 grid(P.S, cdiv(B, rows)), wg(ROW_THREADS);
-    const size_t smem_dh = tile_smem(rows, d), smem_de = tile_smem(CE_ROWS, d);
+    const int ndc = ce_ndc(P.d), rows = 32 * ce_dh_rb(ndc);
+    const dim3 grid(P.S, cdiv(P.B, rows)), wg(ROW_THREADS);
+    const size_t smem_dh = tile_smem(rows, P.d), smem_de = tile_smem(CE_ROWS, P.d);
     switch (ndc) {
         case 1: hipLaunchKernelGGL((ce_dh_kernel<4, 1>), grid, wg, smem_dh, st, P); break;
         case 2: hipLaunchKernelGGL((ce_dh_kernel<4, 2>), grid, wg, smem_dh, st, P); break;
         case 4: hipLaunchKernelGGL((ce_dh_kernel<2, 4>), grid, wg, smem_dh, st, P); break;
         default: hipLaunchKernelGGL((ce_dh_kernel<1, 8>), grid, wg, smem_dh, st, P); break;
     }
-    hipLaunchKernelGGL(ce_dh_sum_kernel, dim3(cdiv((long)B * d / 4, ROW_THREADS)), wg, 0, st, P, gout, dh);
+    hipLaunchKernelGGL(ce_dh_sum_kernel, dim3(cdiv((long)P.B * P.d / 4, ROW_THREADS)), wg, 0, st, P, gout, dh);
     switch (ndc) {
         case 1: hipLaunchKernelGGL(ce_de_kernel<1>, dim3(P.nblk), wg, smem_de, st, P, gout, d_item_emb); break;
         case 2: hipLaunchKernelGGL(ce_de_kernel<2>, dim3(P.nblk), wg, smem_de, st, P, gout, d_item_emb); break;
@@ -2076,6 +2082,53 @@ extern "C" int bsarec_ce_head_bwd(const float* h, long ldh, const float* item_em
         default: hipLaunchKernelGGL(ce_de_kernel<8>, dim3(P.nblk), wg, smem_de, st, P, gout, d_item_emb); break;
     }
     return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_ce_head_bwd(const float* h, long ldh, const float* item_emb, int B, int V, int d, const int64_t* answers,
+                                  const float* gout, void* workspace, long workspace_bytes, float* dh, float* d_item_emb,
+                                  void* stream) {
+    CeP P;
+    if (V < 1) return -10;
+    RET(ce_head_params(P, h, ldh, item_emb, B, V, 0, V, d, answers, workspace, workspace_bytes));
+    return ce_head_bwd_launch(P, gout, dh, d_item_emb, (hipStream_t)stream);
+}
+
+// Range form of the head: one shard of a catalogue split by rows (ce_head.h).  stats -> (the caller's exchange) -> merge -> bwd.
+extern "C" int bsarec_ce_head_range_stats(const float* h, long ldh, const float* item_rows, int Bg, int Vs, long col_base,
+                                          long item_size, int d, const int64_t* answers, float* stats, void* workspace,
+                                          long workspace_bytes, void* stream) {
+    CeP P;
+    RET(ce_head_params(P, h, ldh, item_rows, Bg, Vs, col_base, item_size, d, answers, workspace, workspace_bytes));
+    if (!stats) return -10;
+    hipStream_t st = (hipStream_t)stream;
+    if (Vs > 0) {
+        RET(ce_head_attributes());
+        hipLaunchKernelGGL(ce_fwd_kernel, dim3(P.S, cdiv(Bg, CE_ROWS)), dim3(ROW_THREADS), tile_smem(CE_ROWS, d), st, P);
+    }
+    hipLaunchKernelGGL(ce_stat_kernel<true>, dim3(1), dim3(1024), 0, st, P, (float*)nullptr, stats);      // Vs = 0: S = 0
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_ce_head_range_merge(const float* stats_all, int world, int Bg, void* workspace, long workspace_bytes,
+                                          float* loss_rows, float* loss, void* stream) {
+    if (world < 1 || world > 8 || Bg < 1 || Bg > 65536) return -10;
+    if (!stats_all || !workspace || !aligned16(workspace) || !loss_rows || !loss) return -10;
+    if (workspace_bytes < 2L * Bg * (long)sizeof(float)) return -10;          // m[Bg] | logl[Bg]: the head of every layout
+    float* w = (float*)workspace;
+    hipLaunchKernelGGL(ce_merge_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, stats_all, world, Bg, w, w + Bg, loss_rows, loss);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_ce_head_range_bwd(const float* h, long ldh, const float* item_rows, int Bg, int Vs, long col_base,
+                                        long item_size, int d, const int64_t* answers, const float* gout, void* workspace,
+                                        long workspace_bytes, float* dh_part, float* dE_rows, void* stream) {
+    CeP P;
+    RET(ce_head_params(P, h, ldh, item_rows, Bg, Vs, col_base, item_size, d, answers, workspace, workspace_bytes));
+    if (Vs == 0) {
+        if (!gout || !dh_part || !aligned16(dh_part)) return -10;
+        return (int)hipMemsetAsync(dh_part, 0, (size_t)Bg * d * sizeof(float), (hipStream_t)stream);
+    }
+    return ce_head_bwd_launch(P, gout, dh_part, dE_rows, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

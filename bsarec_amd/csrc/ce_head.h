@@ -23,6 +23,13 @@
 // The row statistics stay in two parts, the maximum m and log l: lse = m + log l rounds at the magnitude of m (half an ulp of 100
 // is 3.8e-6, relative, in every exp(s - lse) of the row), (s - m) - log l does not; row = (m - s_a) + log l likewise.
 // Workspace (floats): m[B] | logl[B] | pm[S][B] | pl[S][B] | pad to 4 | slab[S][B][d].
+//
+// Range form (bsarec_ce_head_range_stats / _merge / _bwd): E holds rows [base, base + V) of a catalogue of N rows, one shard of a
+// table split by rows.  Items, tiles and every comparison j == a stay LOCAL; the base enters in ce_answer alone, which clamps the
+// answer to [0, N) globally and gives its local index, or CE_NO_ANSWER when another range owns it.  The single-table entry
+// points are base 0, N = V of the same kernels.  Between the forward and the backward the ranges exchange a row's (max, sum,
+// target score): ce_stat_kernel<true> writes them, ce_merge_kernel merges every range's in range order and leaves the whole
+// catalogue's m and log l in the workspace slots the backward kernels read.
 #pragma once
 #include "full_rank.h"
 
@@ -33,7 +40,8 @@ struct CeP {
     const float* h; long ldh;
     const float* E;
     const int64_t* ans;
-    int B, V, d, S, nblk;
+    int B, V, d, S, nblk;                    // V: the rows of E
+    int N; long base;                        // E's rows are items [base, base + V) of N
     float *m, *logl, *pm, *pl, *slab;        // the workspace
 };
 
@@ -55,11 +63,14 @@ static inline long ce_workspace_floats(int B, int V, int d) {
 static inline int ce_dh_rb(int ndc) { return ndc <= 2 ? 4 : (ndc <= 4 ? 2 : 1); }
 static inline int ce_ndc(int d) { const int n = (d + 31) / 32; return n <= 2 ? n : (n <= 4 ? 4 : 8); }
 
+#define CE_NO_ANSWER 0xffffffffu             // of a tile row behind B, of an answer in another range: no item index reaches it
+                                             // (V + 127 < 2^32)
+// the local index of row b's answer (clamped to [0, N) globally), or CE_NO_ANSWER when it lies outside [base, base + V)
 __device__ __forceinline__ unsigned ce_answer(const CeP& P, int b) {
     const long a = P.ans[b];
-    return (unsigned)(a < 0 ? 0 : (a >= P.V ? P.V - 1 : a));
+    const long c = (a < 0 ? 0 : (a >= P.N ? P.N - 1 : a)) - P.base;
+    return c >= 0 && c < P.V ? (unsigned)c : CE_NO_ANSWER;
 }
-#define CE_NO_ANSWER 0xffffffffu             // of a tile row behind B: no item index reaches it (V + 127 < 2^32)
 
 // grid (S, row tiles).  Dynamic LDS: CE_ROWS x (d + 4) floats of h.
 __global__ void __launch_bounds__(ROW_THREADS) ce_fwd_kernel(const CeP P) {
@@ -116,13 +127,22 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_fwd_kernel(const CeP P) {
     }
 }
 
-// one workgroup of 1024 lanes: m, log l, rows_out, loss
+// one workgroup of 1024 lanes.  !RANGE: m, log l, rows_out, loss.  RANGE: rows_out is stats[3][B] -- the range's maximum, its
+// sum and the answer's score where the range owns the answer, else 0 (S = 0, a range without rows: -inf, 0, 0); no loss.
+template <bool RANGE>
 __global__ void __launch_bounds__(1024) ce_stat_kernel(const CeP P, float* __restrict__ loss_out, float* __restrict__ rows_out) {
     const int tid = threadIdx.x;
     float sum = 0.f;
     for (int b = tid; b < P.B; b += 1024) {
         const SoftmaxPart part = softmax_merge_splits(P, P.B, b);
         const float m = part.m, l = part.l;
+        if (RANGE) {
+            const unsigned a = ce_answer(P, b);
+            rows_out[b] = m;
+            rows_out[P.B + b] = l;
+            rows_out[2 * P.B + b] = a == CE_NO_ANSWER ? 0.f : fr_dot(P.h + (long)b * P.ldh, P.E + (long)a * P.d, P.d);
+            continue;
+        }
         const float logl = logf(l);
         const float row = (m - fr_dot(P.h + (long)b * P.ldh, P.E + (long)ce_answer(P, b) * P.d, P.d)) + logl;
         P.m[b] = m;
@@ -130,7 +150,33 @@ __global__ void __launch_bounds__(1024) ce_stat_kernel(const CeP P, float* __res
         if (rows_out) rows_out[b] = row;
         sum += row;
     }
-    mean_of_1024(sum, P.B, loss_out);
+    if (!RANGE) mean_of_1024(sum, P.B, loss_out);
+}
+
+// one workgroup of 1024 lanes: stats_all[world][3][B], every range's ce_stat_kernel<true> output in range order -> the whole
+// catalogue's m and log l (the slots of ce_dh_kernel / ce_de_kernel), loss_rows, loss.  A range without rows, (-inf, 0), is
+// neutral in softmax_merge: M is the other maximum, and l * expf(0) + 0 * expf(-inf) = l exactly.  One range: what
+// ce_stat_kernel<false> writes, bit for bit.  The target is the sum over the ranges: one owner, the others wrote 0.
+__global__ void __launch_bounds__(1024) ce_merge_kernel(const float* __restrict__ stats_all, int world, int B, float* __restrict__ m_out,
+                                                        float* __restrict__ logl_out, float* __restrict__ loss_rows,
+                                                        float* __restrict__ loss_out) {
+    const int tid = threadIdx.x;
+    float sum = 0.f;
+    for (int b = tid; b < B; b += 1024) {
+        float m = -INFINITY, l = 0.f, target = 0.f;
+        for (int w = 0; w < world; ++w) {
+            const float* s = stats_all + (long)w * 3 * B;
+            softmax_merge(m, l, s[b], s[B + b]);
+            target += s[2 * B + b];
+        }
+        const float logl = logf(l);
+        const float row = (m - target) + logl;
+        m_out[b] = m;
+        logl_out[b] = logl;
+        loss_rows[b] = row;
+        sum += row;
+    }
+    mean_of_1024(sum, B, loss_out);
 }
 
 // grid (S, ceil(B / (32 RB))).  Dynamic LDS: 32 RB x (d + 4) floats: the h tile, then the waves' sum.

@@ -511,6 +511,40 @@ int bsarec_ce_head_fwd(const float *h, long ldh, const float *item_emb, int B, i
                        float *loss_out, float *rows_out, void *workspace, long workspace_bytes, void *stream);
 int bsarec_ce_head_bwd(const float *h, long ldh, const float *item_emb, int B, int V, int d, const int64_t *answers,
                        const float *gout, void *workspace, long workspace_bytes, float *dh, float *d_item_emb, void *stream);
+/* The same head over a catalogue split by rows into contiguous ranges, one per rank (the catalogue-sharded step,
+ * bsarec_shard.h): exact full-catalogue CE, d(h) and dE with no [Bg, Vs] buffer.  item_rows holds rows [col_base, col_base + Vs)
+ * of a catalogue of item_size rows; h, answers and every output cover ALL Bg rows of the global batch.  bsarec_ce_head_fwd /
+ * _bwd are the col_base = 0, Vs = item_size case of the same kernels.
+ *   Scores: the same fmaf chain of the h row and the item row; a score does not depend on the range the item is in.
+ *   Answers: clamped to [0, item_size) GLOBALLY; a range owns a_b iff col_base <= a_b < col_base + Vs.
+ *   bsarec_ce_head_range_stats: stats[3][Bg] in the layout of bsarec_shard_ce_stats -- row 0 the row maximum over the owned
+ *     items, row 1 sum exp(s - max) over them, row 2 s(b, a_b) if owned, else 0.  Vs = 0 reports (-inf, 0, 0) and launches
+ *     nothing over items.  Two launches.
+ *   The caller gathers every range's stats into stats_all[world][3][Bg], in range order (an all-gather).
+ *   bsarec_ce_head_range_merge: one launch of one workgroup; per row the `world` (max, sum) pairs merged in range order (a
+ *     (-inf, 0) pair is neutral), target = the sum of row 2 over the ranges (one owner, the others wrote 0); m_b and log l_b of
+ *     the WHOLE catalogue go into this range's `workspace` where the backward reads them; loss_rows[b] = (m_b - target) +
+ *     log l_b, loss[0] = their mean.  Every range that merges the same stats_all gets the same bits.  With world = 1 over the
+ *     whole table, loss and loss_rows are those of bsarec_ce_head_fwd bit for bit.
+ *   bsarec_ce_head_range_bwd: G_bj = g / Bg * (exp((s(b, j) - m_b) - log l_b) - [col_base + j == a_b]) for the owned j;
+ *     dh_part[Bg, d] = sum over the owned j of G_bj item_rows[j] -- the ranges' parts add up to d(h) (an all-reduce);
+ *     dE_rows[Vs, d] = sum_b G_bj h[b], every row overwritten, one writer per row, one order.  Vs = 0 zeroes dh_part and
+ *     touches nothing else.  Three launches.  With world = 1 over the whole table: the bits of bsarec_ce_head_bwd.
+ *   Call stats, merge and bwd in that order with the SAME workspace, h, item_rows and answers; the workspace is
+ *   bsarec_ce_head_range_workspace_bytes(Bg, Vs, d) = bsarec_ce_head_workspace_bytes(Bg, max(Vs, 1), d) bytes (host only).
+ *   Execution: as bsarec_ce_head_fwd / _bwd -- the caller's stream, no host synchronisation, no allocation, no atomics,
+ *   capturable, bit-deterministic, h through its row stride.
+ *   Limits (else < 0 before any HIP call): those of bsarec_ce_head_fwd / _bwd with B := Bg, V := Vs (Vs = 0 allowed);
+ *   0 <= col_base, col_base + Vs <= item_size < 2^31; 1 <= world <= 8; stats, stats_all, loss_rows, loss non-null;
+ *   merge: workspace 16-byte aligned and at least 8 Bg bytes. */
+long bsarec_ce_head_range_workspace_bytes(int Bg, int Vs, int d);
+int bsarec_ce_head_range_stats(const float *h, long ldh, const float *item_rows, int Bg, int Vs, long col_base, long item_size,
+                               int d, const int64_t *answers, float *stats, void *workspace, long workspace_bytes, void *stream);
+int bsarec_ce_head_range_merge(const float *stats_all, int world, int Bg, void *workspace, long workspace_bytes,
+                               float *loss_rows, float *loss, void *stream);
+int bsarec_ce_head_range_bwd(const float *h, long ldh, const float *item_rows, int Bg, int Vs, long col_base, long item_size,
+                             int d, const int64_t *answers, const float *gout, void *workspace, long workspace_bytes,
+                             float *dh_part, float *dE_rows, void *stream);
 
 /* Stand-alone FrequencyLayer (src/model/bsarec.py:90-104) for per-op parity tests:
  * y = LN(Drop(low + beta^2 (x - low)) + x); backward given dy. */

@@ -37,6 +37,11 @@
  *   Adam                          dense (bsarec_adam_apply over the shard; dE zeroed once per step), or lazy:
  *                                 bsarec_shard_lazy_mark + bsarec_shard_lazy_adam over the owned rows the step touched
  *
+ * Full-catalogue CE without the partial logits (opt-in, ShardedCatalogue with shard_ce_head = "fused"): bsarec_shard_logits,
+ * bsarec_shard_ce_stats, bsarec_shard_ce_grad and bsarec_shard_head_bwd are replaced by bsarec_ce_head_range_stats, the same
+ * all-gather of the statistics, bsarec_ce_head_range_merge and bsarec_ce_head_range_bwd (bsarec_hip.h): the same loss, dE and
+ * partial d h_last with no [Bg, Vs] buffer.
+ *
  * Same conventions as bsarec_hip.h: plain pointers and sizes, caller-owned memory, caller's stream, no synchronisation,
  * return 0 / <0 invalid argument / >0 hipError_t.  fp32.  hidden % 4 == 0, world <= 8.
  */
