@@ -136,6 +136,12 @@ class Comm(C.Structure):
                 ("error", C.c_void_p), ("timeout_ms", C.c_int)]
 
 
+class GruConfig(C.Structure):
+    """bsarec_gru_config_t"""
+    _fields_ = [("batch", C.c_int), ("seq_len", C.c_int), ("input_size", C.c_int), ("hidden_size", C.c_int),
+                ("num_layers", C.c_int), ("out_size", C.c_int)]
+
+
 HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)          # bsarec_hook_t
 
 
@@ -204,6 +210,12 @@ EXPORTS = {
                                              C.c_void_p]),
     "bsarec_ce_head_range_bwd": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bsarec_gru_weight_floats": (C.c_long, [C.POINTER(GruConfig)]),
+    "bsarec_gru_workspace_bytes": (C.c_long, [C.POINTER(GruConfig), C.c_int]),
+    "bsarec_gru_fwd": (C.c_int, [C.POINTER(GruConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long,
+                                 C.c_void_p]),
+    "bsarec_gru_bwd": (C.c_int, [C.POINTER(GruConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

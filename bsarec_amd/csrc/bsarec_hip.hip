@@ -18,6 +18,7 @@
 #include "ce_head.h"
 #include "sampled_softmax.h"
 #include "lazy_adam.h"
+#include "gru.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -2129,6 +2130,240 @@ extern "C" int bsarec_ce_head_range_bwd(const float* h, long ldh, const float* i
         return (int)hipMemsetAsync(dh_part, 0, (size_t)Bg * d * sizeof(float), (hipStream_t)stream);
     }
     return ce_head_bwd_launch(P, gout, dh_part, dE_rows, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// GRU stack (gru.h): plan-less, everything on the caller's stream, no allocation
+// ---------------------------------------------------------------------------------------------
+static int gru_check(const bsarec_gru_config_t* c) {
+    if (!c) return -10;
+    if (c->batch < 1 || c->batch > 65536 || c->seq_len < 1 || c->seq_len > 256) return -10;
+    if (!row_dim_ok(c->input_size)) return -10;
+    if (c->hidden_size != 32 && c->hidden_size != 64 && c->hidden_size != 96 && c->hidden_size != 128) return -10;
+    if (c->num_layers < 1 || c->num_layers > 4) return -10;
+    if (c->out_size != 0 && !row_dim_ok(c->out_size)) return -10;
+    return 0;
+}
+
+// split-K of a weight-gradient product over K rows: slices of >= 256 rows, 64 at the most; a function of K alone
+static void gru_split(long K, int* nsplit, int* kchunk) {
+    long ns = (K + 255) / 256;
+    ns = ns < 1 ? 1 : (ns > 64 ? 64 : ns);
+    const long kc = rup((K + ns - 1) / ns, GEMM_BK);
+    *kchunk = (int)kc;
+    *nsplit = kc > 0 ? (int)((K + kc - 1) / kc) : 1;
+    if (*nsplit < 1) *nsplit = 1;
+}
+
+// Workspace, in floats (every region a multiple of 4): A / da [T][3H] | Y_k [T][H], k < NY | S_k [T][4H] | db_n [T][H] |
+// dY ping [T][H] | dY pong [T][H] | x time-major [T][I] | dout time-major [T][O] | slabs [ns][max(3H max(I, H), O H)] |
+// bias partials [ns][O]; T = L B, NY = N in training, else min(N, 2); everything behind Y_k in training only
+struct GruWs {
+    long a, y, s, dbn, dya, dyb, xt, dot, slab, bpart, total;
+    int ny, ns;        // ns: the most slabs any of the backward's split-K products writes
+};
+static GruWs gru_ws(const bsarec_gru_config_t& c, bool train) {
+    const long T = (long)c.batch * c.seq_len, H = c.hidden_size, I = c.input_size, O = c.out_size, N = c.num_layers;
+    GruWs w;
+    memset(&w, 0, sizeof(w));
+    for (long K : {T, T - c.batch, (long)c.batch}) {        // the K of every split-K product of the backward
+        int ns, kc;
+        gru_split(K, &ns, &kc);
+        w.ns = std::max(w.ns, ns);
+    }
+    w.ny = train ? (int)N : (int)(N < 2 ? N : 2);
+    long off = 0;
+    w.a = off; off += T * 3 * H;
+    w.y = off; off += w.ny * T * H;
+    if (train) {
+        w.s = off; off += N * T * 4 * H;
+        w.dbn = off; off += T * H;
+        w.dya = off; off += T * H;
+        w.dyb = off; off += T * H;
+        w.xt = off; off += T * I;
+        w.dot = off; off += T * O;
+        const long big = std::max(3 * H * std::max(I, H), O * H);
+        w.slab = off; off += w.ns * big;
+        w.bpart = off; off += (long)w.ns * O;
+    }
+    w.total = off;
+    return w;
+}
+
+// offsets (floats) into the flat weight array: w_ih_l0 | w_hh_l0 | w_ih_l1 | ... | w_out | b_out
+struct GruW { long ih[4], hh[4], out, bout, total; };
+static GruW gru_weights(const bsarec_gru_config_t& c) {
+    GruW w;
+    long off = 0;
+    for (int k = 0; k < c.num_layers; ++k) {
+        w.ih[k] = off; off += 3L * c.hidden_size * (k == 0 ? c.input_size : c.hidden_size);
+        w.hh[k] = off; off += 3L * c.hidden_size * c.hidden_size;
+    }
+    w.out = off; off += (long)c.out_size * c.hidden_size;
+    w.bout = off; off += c.out_size;
+    w.total = off;
+    return w;
+}
+
+extern "C" long bsarec_gru_weight_floats(const bsarec_gru_config_t* cfg) {
+    if (gru_check(cfg)) return -10;
+    return gru_weights(*cfg).total;
+}
+
+extern "C" long bsarec_gru_workspace_bytes(const bsarec_gru_config_t* cfg, int train) {
+    if (gru_check(cfg)) return -10;
+    return gru_ws(*cfg, train != 0).total * (long)sizeof(float);
+}
+
+static EpiGru gru_epi(float* C, long ldc, const float* bias = nullptr, int P = 0, int Q = 0) {
+    EpiGru e;
+    e.C = C; e.ldc = ldc; e.c_split = 0; e.bias = bias; e.P = P; e.Q = Q;
+    return e;
+}
+// C[M, N] = A[M, K] . W[N, K]^T (+ bias)
+static int gru_nt(const float* A, const float* W, int M, int N, int K, const EpiGru& e, hipStream_t s) {
+    GemmP g = gemm_defaults(M, N, K);
+    g.lda = K; g.ldb = K; g.A[0] = A; g.B[0] = W;
+    return launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_NONE, true);
+}
+// C[M, N] = A[M, K] . W[K, N]
+static int gru_nn(const float* A, const float* W, int M, int N, int K, const EpiGru& e, hipStream_t s) {
+    GemmP g = gemm_defaults(M, N, K);
+    g.lda = K; g.ldb = N; g.A[0] = A; g.B[0] = W;
+    return launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_NONE, true);
+}
+// out[M, N] = A[K, M]^T . Bm[K, N] in split-K slabs at slab + coff, M x Nfull each (the caller sums them); bpart: the column
+// sums of A per split, [ns][M]
+static int gru_tn(const float* A, long lda, const float* Bm, int M, int N, long K, float* slab, long slab_floats, long coff,
+                  float* bpart, hipStream_t s) {
+    int ns, kc;
+    gru_split(K, &ns, &kc);
+    GemmP g = gemm_defaults(M, N, (int)K);
+    g.lda = lda; g.ldb = N; g.A[0] = A; g.B[0] = Bm; g.nsplit = ns; g.kchunk = kc;
+    EpiGru e = gru_epi(slab + coff, N);
+    e.c_split = slab_floats;
+    if (bpart) return launch_gemm<64, 64, 2, 2, true, true, XF_NONE, XF_NONE, true>(g, no_xform(), e, bpart, 1, s, BSAREC_K_NONE, true);
+    return launch_gemm<64, 64, 2, 2, true, true, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_NONE, true);
+}
+static void gru_sum(const float* slab, long K, long floats, float* out, hipStream_t s) {
+    int ns, kc;
+    gru_split(K, &ns, &kc);
+    hipLaunchKernelGGL(gru_slab_sum_kernel, dim3(cdiv(floats / 4, 256)), dim3(256), 0, s, slab, ns, floats / 4, out);
+}
+static void gru_swap(const float* src, float* dst, long P, long Q, int W, hipStream_t s) {
+    hipLaunchKernelGGL(gru_swap_rows_kernel, dim3(cdiv(P * Q * (W / 4), 256)), dim3(256), 0, s, src, dst, P, Q, W / 4);
+}
+#define GRU_DISPATCH(H, KERNEL, ...) \
+    switch ((H) / 32) { \
+        case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break; \
+        case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break; \
+        case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break; \
+        default: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break; \
+    }
+
+static int gru_args(const bsarec_gru_config_t* cfg, const float* x, const float* weights, const void* workspace, long workspace_bytes,
+                    bool train) {
+    RET(gru_check(cfg));
+    if (!x || !weights || !workspace) return -10;
+    if (!aligned16(x) || !aligned16(weights) || !aligned16(workspace)) return -10;
+    if (workspace_bytes < gru_ws(*cfg, train).total * (long)sizeof(float)) return -10;
+    return 0;
+}
+
+extern "C" int bsarec_gru_fwd(const bsarec_gru_config_t* cfg, const float* x, const float* weights, int train, int last_only,
+                              float* out, void* workspace, long workspace_bytes, void* stream) {
+    RET(gru_args(cfg, x, weights, workspace, workspace_bytes, train != 0));
+    if (!out || !aligned16(out)) return -10;
+    const bsarec_gru_config_t& c = *cfg;
+    const int B = c.batch, L = c.seq_len, I = c.input_size, H = c.hidden_size, N = c.num_layers, O = c.out_size;
+    const long T = (long)B * L;
+    const GruWs ws = gru_ws(c, train != 0);
+    const GruW wo = gru_weights(c);
+    float* w = (float*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(cdiv(B, GRU_ROWS)), wg(2 * H);
+    const float* y = nullptr;
+    for (int k = 0; k < N; ++k) {
+        // a = in . W_ih^T, time-major: x's rows (b, t) go through the row map, a layer output is time-major already
+        if (k == 0) RET(gru_nt(x, weights + wo.ih[0], (int)T, 3 * H, I, gru_epi(w + ws.a, 3 * H, nullptr, B, L), s));
+        else RET(gru_nt(y, weights + wo.ih[k], (int)T, 3 * H, H, gru_epi(w + ws.a, 3 * H), s));
+        GruFwdP P;
+        P.A = w + ws.a; P.Whh = weights + wo.hh[k]; P.B = B; P.L = L;
+        P.Y = w + ws.y + (long)(train ? k : (k & 1)) * T * H;
+        P.S = train ? w + ws.s + (long)k * T * 4 * H : nullptr;
+        GRU_DISPATCH(H, gru_seq_fwd_kernel, grid, wg, 0, s, P);
+        y = P.Y;
+    }
+    const float* ylast = y + (long)(L - 1) * B * H;
+    if (O > 0) {
+        if (last_only) RET(gru_nt(ylast, weights + wo.out, B, O, H, gru_epi(out, O, weights + wo.bout), s));
+        else RET(gru_nt(y, weights + wo.out, (int)T, O, H, gru_epi(out, O, weights + wo.bout, L, B), s));
+    } else {
+        if (last_only) gru_swap(ylast, out, 1, B, H, s);
+        else gru_swap(y, out, L, B, H, s);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_gru_bwd(const bsarec_gru_config_t* cfg, const float* x, const float* weights, int last_only, const float* dout,
+                              void* workspace, long workspace_bytes, float* dx, float* dweights, void* stream) {
+    RET(gru_args(cfg, x, weights, workspace, workspace_bytes, true));
+    if (!dout || !dx || !dweights || !aligned16(dout) || !aligned16(dx) || !aligned16(dweights)) return -10;
+    const bsarec_gru_config_t& c = *cfg;
+    const int B = c.batch, L = c.seq_len, I = c.input_size, H = c.hidden_size, N = c.num_layers, O = c.out_size;
+    const long T = (long)B * L;
+    const GruWs ws = gru_ws(c, true);
+    const GruW wo = gru_weights(c);
+    float* w = (float*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(cdiv(B, GRU_ROWS)), wg(2 * H);
+    float* slab = w + ws.slab;
+    const float* ytop = w + ws.y + (long)(N - 1) * T * H;
+    // the top layer's dY (time-major, or the B rows of t = L - 1) and the projection's gradients
+    const float* dy = w + ws.dya;
+    float* dy_next = w + ws.dyb;
+    if (O > 0) {
+        const float* d = dout;                    // rows in the order of y's rows
+        const float* yrows = ytop + (last_only ? (long)(L - 1) * B * H : 0);
+        const long K = last_only ? B : T;
+        if (!last_only) { gru_swap(dout, w + ws.dot, B, L, O, s); d = w + ws.dot; }
+        RET(gru_nn(d, weights + wo.out, (int)K, H, O, gru_epi(w + ws.dya, H), s));
+        RET(gru_tn(d, O, yrows, O, H, K, slab, (long)O * H, 0, w + ws.bpart, s));
+        gru_sum(slab, K, (long)O * H, dweights + wo.out, s);
+        gru_sum(w + ws.bpart, K, O, dweights + wo.bout, s);
+    } else if (last_only) {
+        dy = dout;
+    } else {
+        gru_swap(dout, w + ws.dya, B, L, H, s);
+    }
+    gru_swap(x, w + ws.xt, B, L, I, s);
+    for (int k = N - 1; k >= 0; --k) {
+        const int Ik = k == 0 ? I : H;
+        const float* yk = w + ws.y + (long)k * T * H;
+        const float* in = k == 0 ? w + ws.xt : w + ws.y + (long)(k - 1) * T * H;
+        GruBwdP P;
+        P.S = w + ws.s + (long)k * T * 4 * H; P.Y = yk; P.Whh = weights + wo.hh[k]; P.dY = dy;
+        P.da = w + ws.a; P.dbn = w + ws.dbn; P.B = B; P.L = L; P.dy_last = (last_only && k == N - 1) ? 1 : 0;
+        GRU_DISPATCH(H, gru_seq_bwd_kernel, grid, wg, 0, s, P);
+        // d(in) = da . W_ih: the layer below's dY, or dx through the row map
+        if (k > 0) {
+            RET(gru_nn(P.da, weights + wo.ih[k], (int)T, H, 3 * H, gru_epi(dy_next, H), s));
+            const float* t = dy_next;
+            dy_next = (dy == dout) ? w + ws.dya : const_cast<float*>(dy);
+            dy = t;
+        } else {
+            RET(gru_nn(P.da, weights + wo.ih[0], (int)T, I, 3 * H, gru_epi(dx, I, nullptr, L, B), s));
+        }
+        // dW_ih = da^T . in over all T rows
+        RET(gru_tn(P.da, 3 * H, in, 3 * H, Ik, T, slab, 3L * H * Ik, 0, nullptr, s));
+        gru_sum(slab, T, 3L * H * Ik, dweights + wo.ih[k], s);
+        // dW_hh = (da_r, da_z | db_n)[t >= 1]^T . y[t - 1]: rows 0 .. 2H from da, rows 2H .. 3H from db_n, over (L - 1) B rows
+        const long K = T - B;
+        RET(gru_tn(P.da + 3L * B * H, 3 * H, yk, 2 * H, H, K, slab, 3L * H * H, 0, nullptr, s));
+        RET(gru_tn(P.dbn + (long)B * H, H, yk, H, H, K, slab, 3L * H * H, 2L * H * H, nullptr, s));
+        gru_sum(slab, K, 3L * H * H, dweights + wo.hh[k], s);
+    }
+    return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------

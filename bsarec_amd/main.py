@@ -150,6 +150,9 @@ def parse_args(argv=None):
     # likewise: DuoRec's supervised full-catalogue cross-entropy through bsarec_ce_head_fwd / _bwd (no B x V logits)
     p.add_argument("--duorec_ce_head", default=argparse.SUPPRESS, choices=("torch", "hip"),
                    help="DuoRec's supervised cross-entropy: torch.matmul + F.cross_entropy (default) or the HIP kernels")
+    # not a reference flag: width of GRU4Rec's recurrent state (--model_type GRU4Rec).  Absent unless given, as the flags above
+    p.add_argument("--gru_hidden_size", default=argparse.SUPPRESS, type=int, choices=(32, 64, 96, 128),
+                   help="GRU4Rec: hidden size of the GRU layers (default 64)")
     args = p.parse_args(argv)
     n = getattr(args, "eval_negatives", 0)
     if n > 0 and hasattr(args, "eval_full_rank"):

@@ -1099,4 +1099,7 @@ class DuoRecModel(SASRecModel):
 
 
 # src/model/__init__.py:10-19: the hot-path entry and its siblings on the same kernels
-MODEL_DICT = {"bsarec": BSARecModel, "sasrec": SASRecModel, "fmlprec": FMLPRecModel, "duorec": DuoRecModel}
+from .gru4rec import GRU4RecModel  # noqa: E402  (its own kernels and module: bsarec_amd/gru4rec.py)
+
+MODEL_DICT = {"bsarec": BSARecModel, "sasrec": SASRecModel, "fmlprec": FMLPRecModel, "duorec": DuoRecModel,
+              "gru4rec": GRU4RecModel}

@@ -5,6 +5,10 @@ get_full_sort_score``); the per-batch body of ``iteration(train=True)`` is ONE C
 (``bsarec_train_step``: forward + loss + backward + fused Adam), optionally replayed from a captured
 hipGraph, the epoch loss is accumulated on the device (no per-step ``loss.item()`` sync), and the
 evaluation branch scores, masks seen items and takes the top-20 on the GPU.
+
+A model without the flat parameter arena (GRU4Rec, bsarec_amd/gru4rec.py) trains on one GPU through the ``torch_optim``
+branch of ``iteration``; it has ``last_hidden`` and the item table but no ``full_logits``, so the default ("dense")
+evaluation takes ``topk_full`` for it, which returns the same lists by construction.
 """
 from __future__ import annotations
 
@@ -77,16 +81,23 @@ class Trainer:
     def __init__(self, model: BSARecModel, train_dataloader, eval_dataloader, test_dataloader, args, logger=None,
                  use_graph: bool = True, process_group=None, exchange: str = "auto"):
         self.args = args
+        arena = hasattr(model, "_arena")       # the flat-arena models of model.py; GRU4Rec (gru4rec.py) has none
+        if not arena:
+            self._check_arenaless(args, process_group)
         check_train_head(model, args, train_dataloader, process_group)
         self.logger = logger or _NullLogger()
         if not torch.cuda.is_available() or getattr(args, "no_cuda", False):
             raise RuntimeError("bsarec_amd.Trainer needs an MI355X: there is no CPU training path "
                                "(the CPU restatement under oracle/ is test infrastructure)")
         self.device = torch.device("cuda", torch.cuda.current_device())
-        self.model = model.to(self.device) if model._arena.device != self.device else model
+        if arena:
+            self.model = model.to(self.device) if model._arena.device != self.device else model
+        else:
+            self.model = model.to(self.device)
         self.train_dataloader, self.eval_dataloader, self.test_dataloader = train_dataloader, eval_dataloader, test_dataloader
-        self.model.configure_adam(lr=args.lr, betas=(args.adam_beta1, args.adam_beta2),
-                                  weight_decay=args.weight_decay)           # src/trainers.py:27-28
+        if arena:
+            self.model.configure_adam(lr=args.lr, betas=(args.adam_beta1, args.adam_beta2),
+                                      weight_decay=args.weight_decay)           # src/trainers.py:27-28
         self.logger.info(f"Total Parameters: {sum(p.nelement() for p in self.model.parameters())}")
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
@@ -96,8 +107,23 @@ class Trainer:
         self.use_graph = use_graph                       # data parallel: two graphs around the eager all-reduce
         self._graphs = {}
         self._full_rank = FullRank("topk_full: unsupported shape B={B} V={V} d={d} k={k}")
+        if not arena:       # steps through calculate_loss / backward / torch.optim.Adam (iteration): nothing to sync or exchange
+            self._px, self.exchange = None, "none"
+            return
         self._sync_replicas()
         self._setup_exchange()
+
+    @staticmethod
+    def _check_arenaless(args, process_group):
+        """A model without the flat parameter arena (GRU4Rec): single GPU, its own loss head, fp32."""
+        if process_group is not None:
+            raise ValueError("GRU4Rec: single GPU only")
+        if getattr(args, "train_negatives", 0):
+            raise ValueError("GRU4Rec: train_negatives does not apply (the model has its own BPR head)")
+        if getattr(args, "train_lazy_adam", False):
+            raise ValueError("GRU4Rec: train_lazy_adam does not apply (the model steps through torch.optim.Adam)")
+        if getattr(args, "storage", None) == "bf16":
+            raise ValueError("GRU4Rec: storage = 'bf16' does not apply (the GRU kernels are fp32)")
 
     # ---- data-parallel gradient exchange (bsarec_amd/dp.py) ------------------------------------------
     def _setup_exchange(self):
@@ -603,10 +629,13 @@ class Trainer:
             return self.get_rank_score(epoch, torch.cat(ranks))
         preds, answers_all = [], []
         depth = max((20,) + extra_cutoffs(self.args))
+        # a model without ``full_logits`` (GRU4Rec) takes topk_full on the default ("dense") path too: it returns the same
+        # lists by construction, from ``last_hidden`` and the item table alone
+        fused = getattr(self.args, "eval_full_rank", "dense") == "fused" or not hasattr(self.model, "full_logits")
         for batch in dataloader:
             batch = tuple(t.to(self.device, non_blocking=True) for t in batch)
             user_ids, input_ids, answers, _, _ = batch
-            if getattr(self.args, "eval_full_rank", "dense") == "fused":
+            if fused:
                 preds.append(self.topk_full(user_ids, input_ids, k=depth))
             else:
                 preds.append(self.topk_after_seen(user_ids, input_ids, k=depth))

@@ -546,6 +546,49 @@ int bsarec_ce_head_range_bwd(const float *h, long ldh, const float *item_rows, i
                              int d, const int64_t *answers, const float *gout, void *workspace, long workspace_bytes,
                              float *dh_part, float *dE_rows, void *stream);
 
+/* GRU stack of the GRU4Rec sibling model (csrc/gru.h): num_layers bias-free GRU layers in torch's gate order (r, z, n), h_0 = 0,
+ * no dropout between layers, and an optional Linear on top -- what nn.GRU(input_size, hidden_size, num_layers, bias=False,
+ * batch_first=True) followed by nn.Linear(hidden_size, out_size) and their autograd compute, in fp32.  No plan.
+ *   One layer, with a_t = W_ih x_t and b_t = W_hh h_{t-1} (three gate blocks of hidden_size rows each):
+ *     r = sigmoid(a_r + b_r), z = sigmoid(a_z + b_z), n = tanh(a_n + r * b_n), h_t = n + z * (h_{t-1} - n);
+ *   layer k > 0 reads layer k - 1's h; y = the top layer's h; out = y . w_out^T + b_out, or y itself when out_size is 0.
+ *   Every position is computed: the caller masks nothing.
+ *   weights: ONE flat array of bsarec_gru_weight_floats(cfg) floats, row-major tensors in this order:
+ *     w_ih_l0 [3H, I] | w_hh_l0 [3H, H] | w_ih_l1 [3H, H] | w_hh_l1 [3H, H] | ... | w_out [O, H] | b_out [O]
+ *   (I = input_size, H = hidden_size, O = out_size; the last two are empty when O is 0).  dweights has the same layout.
+ *   x is [B, L, I]; out is [B, L, O'] with O' = O, or H when O is 0; with last_only != 0 out is [B, O'], position L - 1 alone,
+ *   the bits of that row of the full output.  train = 0 gives the bits of train = 1 and keeps nothing for a backward.
+ *   bsarec_gru_bwd: dout has out's shape; with last_only != 0 it is [B, O'], the gradient at position L - 1, zero elsewhere.
+ *   dx [B, L, I] and every float of dweights are overwritten.  It reads what bsarec_gru_fwd(train = 1) left in the SAME
+ *   workspace for the same cfg, x and weights: call the forward first and keep all three unchanged in between.
+ *   Launches, all on `stream`: forward, per layer one product a = in . W_ih^T of all L B rows (the library's tiled fp32 MFMA
+ *   product) and one sequence kernel -- ceil(B / 16) workgroups, each owning 16 sequences for all L steps with W_hh resident in
+ *   registers, no communication between workgroups --, then the projection (on B rows with last_only).  Backward, per layer
+ *   from the top: one sequence kernel (t descending; writes da [L B, 3H] and db_n [L B, H]), then d(in) = da . W_ih,
+ *   dW_ih = da^T . in and dW_hh = db^T . h_prev as split-K products into slabs added in split order; before them the
+ *   projection's d(y), dw_out, db_out.  No atomics, no allocation, no host synchronisation: capturable, and every sum has ONE
+ *   order that depends on the shape alone, so all outputs are bit-deterministic; a sequence's forward bits do not depend on B
+ *   or on its place in the batch.
+ *   Workspace: bsarec_gru_workspace_bytes(cfg, train) bytes (host-only query, no HIP call).  Activations are kept time-major,
+ *   [L][B][.].  In floats, with T = L B: a / da [T, 3H] | y_k [T, H] for k < N (train = 0: min(N, 2)) | and with train != 0:
+ *   (r, z, n, b_n)_k [T, 4H] for k < N | db_n [T, H] | two d(y) [T, H] | x time-major [T, I] | dout time-major [T, O] |
+ *   S slabs of max(3H max(I, H), O H) | S x O bias partials; S <= 64: a product over K rows is split into at most min(64, ceil(K / 256))
+ *   slices of a multiple of 32 rows.
+ *   Limits (else < 0 before any HIP call): 1 <= batch <= 65536; 1 <= seq_len <= 256; 4 <= input_size <= 256, % 4 == 0;
+ *   hidden_size in {32, 64, 96, 128}; 1 <= num_layers <= 4; out_size 0, or 4 <= out_size <= 256, % 4 == 0; every pointer
+ *   non-null and 16-byte aligned; workspace_bytes at least the queried size (bsarec_gru_bwd: that of train = 1).  Inputs are
+ *   read-only; outputs may not alias inputs, each other or the workspace. */
+typedef struct {
+    int batch, seq_len, input_size, hidden_size, num_layers;
+    int out_size;                      /* 0: no projection */
+} bsarec_gru_config_t;
+long bsarec_gru_weight_floats(const bsarec_gru_config_t *cfg);
+long bsarec_gru_workspace_bytes(const bsarec_gru_config_t *cfg, int train);
+int bsarec_gru_fwd(const bsarec_gru_config_t *cfg, const float *x, const float *weights, int train, int last_only, float *out,
+                   void *workspace, long workspace_bytes, void *stream);
+int bsarec_gru_bwd(const bsarec_gru_config_t *cfg, const float *x, const float *weights, int last_only, const float *dout,
+                   void *workspace, long workspace_bytes, float *dx, float *dweights, void *stream);
+
 /* Stand-alone FrequencyLayer (src/model/bsarec.py:90-104) for per-op parity tests:
  * y = LN(Drop(low + beta^2 (x - low)) + x); backward given dy. */
 int bsarec_freq_layer_fwd(const float *x, const float *sqrt_beta, const float *ln_w, const float *ln_b,
