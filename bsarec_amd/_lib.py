@@ -142,6 +142,11 @@ class GruConfig(C.Structure):
                 ("num_layers", C.c_int), ("out_size", C.c_int)]
 
 
+class Gru4RecConfig(C.Structure):
+    """bsarec_gru4rec_config_t"""
+    _fields_ = [("gru", GruConfig), ("item_size", C.c_int), ("dropout", C.c_float)]
+
+
 HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)          # bsarec_hook_t
 
 
@@ -216,6 +221,11 @@ EXPORTS = {
                                  C.c_void_p]),
     "bsarec_gru_bwd": (C.c_int, [C.POINTER(GruConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
+    "bsarec_gru4rec_workspace_bytes": (C.c_long, [C.POINTER(Gru4RecConfig)]),
+    "bsarec_gru4rec_loss_grad": (C.c_int, [C.POINTER(Gru4RecConfig)] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4 +
+                                 [C.c_long, C.c_void_p]),
+    "bsarec_gru4rec_train_step": (C.c_int, [C.POINTER(Gru4RecConfig)] + [C.c_void_p] * 3 + [C.POINTER(Adam)] * 2 +
+                                  [C.c_void_p] * 3 + [C.c_long, C.c_void_p]),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

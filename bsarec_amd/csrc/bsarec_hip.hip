@@ -19,6 +19,7 @@
 #include "sampled_softmax.h"
 #include "lazy_adam.h"
 #include "gru.h"
+#include "gru4rec_step.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -2364,6 +2365,145 @@ extern "C" int bsarec_gru_bwd(const bsarec_gru_config_t* cfg, const float* x, co
         gru_sum(slab, K, 3L * H * H, dweights + wo.hh[k], s);
     }
     return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// GRU4Rec training step (gru4rec_step.h): lookup + dropout, the GRU stack, the BPR head, every gradient, Adam -- plan-less, one
+// linear chain of launches on the caller's stream, no allocation, no host synchronisation
+// ---------------------------------------------------------------------------------------------
+static int gru4rec_check(const bsarec_gru4rec_config_t* c) {
+    if (!c) return -10;
+    RET(gru_check(&c->gru));
+    if (c->gru.input_size != c->gru.out_size) return -10;
+    if (c->item_size < 2) return -10;
+    if (!(c->dropout >= 0.f && c->dropout < 1.f)) return -10;          // NaN fails both comparisons
+    return 0;
+}
+
+// Workspace, in floats (every region a multiple of 4): the GRU workspace of train = 1 | x [T][d] | s [B][d] | ds [B][d] |
+// dx [T][d] | c [B up to 4] | loss rows [B up to 4] | the fixed-point accumulator [V][d] of 64-bit words
+struct Gru4RecWs { long gru, x, s, ds, dx, c, rows, acc, total; long gru_bytes; };
+static Gru4RecWs gru4rec_ws(const bsarec_gru4rec_config_t& c) {
+    const long B = c.gru.batch, T = B * c.gru.seq_len, d = c.gru.input_size;
+    Gru4RecWs w;
+    long off = 0;
+    w.gru = off; off += gru_ws(c.gru, true).total;
+    w.gru_bytes = off * (long)sizeof(float);
+    w.x = off; off += T * d;
+    w.s = off; off += B * d;
+    w.ds = off; off += B * d;
+    w.dx = off; off += T * d;
+    w.c = off; off += rup(B, 4);
+    w.rows = off; off += rup(B, 4);
+    w.acc = off; off += 2L * c.item_size * d;
+    w.total = off;
+    return w;
+}
+
+extern "C" long bsarec_gru4rec_workspace_bytes(const bsarec_gru4rec_config_t* cfg) {
+    if (gru4rec_check(cfg)) return -10;
+    return gru4rec_ws(*cfg).total * (long)sizeof(float);
+}
+
+static bool aligned_to(const void* p, uintptr_t a) { return p && (uintptr_t)p % a == 0; }
+
+static int gru4rec_args(const bsarec_gru4rec_config_t* cfg, const float* item_emb, const float* weights, const int64_t* ids,
+                        const int64_t* answers, const int64_t* neg_answers, const void* state, const float* loss_out,
+                        const float* d_item_emb, const float* dweights, const void* workspace, long workspace_bytes) {
+    RET(gru4rec_check(cfg));
+    for (const void* p : {(const void*)item_emb, (const void*)weights, (const void*)d_item_emb, (const void*)dweights, workspace})
+        if (!aligned_to(p, 16)) return -10;
+    for (const void* p : {(const void*)ids, (const void*)answers, (const void*)neg_answers, state})
+        if (!aligned_to(p, 8)) return -10;
+    if (!aligned_to(loss_out, 4)) return -10;
+    if (workspace_bytes < gru4rec_ws(*cfg).total * (long)sizeof(float)) return -10;
+    return 0;
+}
+
+// tick_adam: null, or the Adam whose t the step's closing block advances (bsarec_gru4rec_train_step)
+static int gru4rec_run(const bsarec_gru4rec_config_t& c, const float* E, const float* weights, const int64_t* ids,
+                       const int64_t* answers, const int64_t* neg_answers, void* state, int train, float* loss_out, float* dE,
+                       float* dweights, void* workspace, const bsarec_adam_t* tick_adam, hipStream_t s) {
+    const int B = c.gru.batch, d = c.gru.input_size, V = c.item_size;
+    const long T = (long)B * c.gru.seq_len;
+    const Gru4RecWs ws = gru4rec_ws(c);
+    float* w = (float*)workspace;
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(w + ws.acc);
+    if (train) hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(1), 0, s, (uint64_t*)state, (long long*)nullptr, 0);
+    DropP drop;
+    drop.thresh = train ? drop_thresh(c.dropout) : 0;
+    drop.scale = (train && c.dropout > 0.f) ? (float)(1.0 / (1.0 - (double)c.dropout)) : 1.0f;
+    drop.rng = (const uint64_t*)state; drop.site = 0;
+
+    Gru4RecEmbedP pe;
+    pe.E = E; pe.ids = ids; pe.x = w + ws.x; pe.T = T; pe.d = d; pe.V = V; pe.drop = drop;
+    pe.acc = acc; pe.acc_n2 = (long)V * d / 2;
+    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_embed_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)),
+                                       dim3(ROW_THREADS), 0, s, pe));
+    RET(bsarec_gru_fwd(&c.gru, w + ws.x, weights, 1, 1, w + ws.s, w + ws.gru, ws.gru_bytes, s));
+
+    Gru4RecBprP pb;
+    pb.s = w + ws.s; pb.E = E; pb.ans = answers; pb.neg = neg_answers; pb.B = B; pb.d = d; pb.V = V;
+    pb.ds = w + ws.ds; pb.c = w + ws.c; pb.loss_rows = w + ws.rows;
+    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_bpr_kernel<LPR>, dim3(cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS), 0, s, pb));
+    RET(bsarec_gru_bwd(&c.gru, w + ws.x, weights, 1, w + ws.ds, w + ws.gru, ws.gru_bytes, w + ws.dx, dweights, s));
+
+    Gru4RecGradP pg;
+    pg.dx = w + ws.dx; pg.ids = ids; pg.s = w + ws.s; pg.c = w + ws.c; pg.ans = answers; pg.neg = neg_answers;
+    pg.T = T; pg.B = B; pg.d = d; pg.V = V; pg.drop = drop; pg.dA = acc;
+    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_item_grad_kernel<LPR>, dim3(cdiv(T + 2L * B, SCATTER_FLOATS / (4 * LPR))),
+                                       dim3(ROW_THREADS), 0, s, pg));
+
+    LookupAcc la;
+    memset(&la, 0, sizeof(la));
+    la.acc = acc; la.dst = dE; la.n4 = (long)V * d / 4; la.dense_zero = 1;
+    la.nblocks = std::min(cdiv(la.n4, ROW_THREADS), 1024);
+    const TickP tk = tick_adam ? make_tick(state, 1, tick_adam->lr, tick_adam->beta1, tick_adam->beta2, w + ws.rows, B, loss_out,
+                                           nullptr, 0, 0)
+                               : make_tick(state, 0, 0.f, 0.f, 0.f, w + ws.rows, B, loss_out, nullptr, 0, 0);
+    hipLaunchKernelGGL(gru4rec_flush_kernel, dim3(la.nblocks + 1), dim3(ROW_THREADS), 0, s, la, tk);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_gru4rec_loss_grad(const bsarec_gru4rec_config_t* cfg, const float* item_emb, const float* weights,
+                                        const int64_t* ids, const int64_t* answers, const int64_t* neg_answers, void* state,
+                                        int train, float* loss_out, float* d_item_emb, float* dweights, void* workspace,
+                                        long workspace_bytes, void* stream) {
+    RET(gru4rec_args(cfg, item_emb, weights, ids, answers, neg_answers, state, loss_out, d_item_emb, dweights, workspace,
+                     workspace_bytes));
+    return gru4rec_run(*cfg, item_emb, weights, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights, workspace,
+                       nullptr, (hipStream_t)stream);
+}
+
+// fp32 arrays only, one gradient source, 16-byte aligned
+static int gru4rec_adam_check(const bsarec_adam_t* a, long n) {
+    RET(adam_check(a));
+    if (a->n != n) return -10;
+    if (a->shadow_bf16 || a->grads2 || a->grads2_n || a->n_grad_srcs || a->wimage_plan) return -10;
+    for (const void* p : {(const void*)a->params, (const void*)a->grads, (const void*)a->exp_avg, (const void*)a->exp_avg_sq})
+        if (!aligned_to(p, 16)) return -10;
+    return 0;
+}
+
+extern "C" int bsarec_gru4rec_train_step(const bsarec_gru4rec_config_t* cfg, const int64_t* ids, const int64_t* answers,
+                                         const int64_t* neg_answers, const bsarec_adam_t* adam_items,
+                                         const bsarec_adam_t* adam_weights, void* state, float* loss_out, void* workspace,
+                                         long workspace_bytes, void* stream) {
+    RET(gru4rec_check(cfg));
+    RET(gru4rec_adam_check(adam_items, (long)cfg->item_size * cfg->gru.input_size));
+    RET(gru4rec_adam_check(adam_weights, gru_weights(cfg->gru).total));
+    // one t and one pair of bias corrections in `state` serve both arrays
+    if (adam_items->lr != adam_weights->lr || adam_items->beta1 != adam_weights->beta1 || adam_items->beta2 != adam_weights->beta2)
+        return -10;
+    float* dE = const_cast<float*>(adam_items->grads);
+    float* dW = const_cast<float*>(adam_weights->grads);
+    RET(gru4rec_args(cfg, adam_items->params, adam_weights->params, ids, answers, neg_answers, state, loss_out, dE, dW, workspace,
+                     workspace_bytes));
+    hipStream_t s = (hipStream_t)stream;
+    RET(gru4rec_run(*cfg, adam_items->params, adam_weights->params, ids, answers, neg_answers, state, 1, loss_out, dE, dW, workspace,
+                    adam_items, s));
+    RET(adam_launch(*adam_items, state, s));
+    return adam_launch(*adam_weights, state, s);
 }
 
 // ---------------------------------------------------------------------------------------------

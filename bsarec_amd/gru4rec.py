@@ -4,7 +4,9 @@ with BPR at the last position.
 The contract of this model is the math of its docstrings, checked against ``torch.nn.Embedding`` / ``nn.GRU(bias=False)`` /
 ``nn.Linear`` on the CPU (tests/gru_ref.py, tests/test_gru_cpu.py); no reference golden exists for it yet.  Everything between
 the dropped-out embeddings and the output runs in libbsarec_hip.so in both directions (bsarec_gru_fwd / bsarec_gru_bwd,
-csrc/gru.h); the embedding lookup, the dropout mask and the B-row BPR head are torch ops.  There is no CPU path.
+csrc/gru.h); on the default path the embedding lookup, the dropout mask and the B-row BPR head are torch ops.  With
+``gru_step = "fused"`` the whole training step -- those parts, the item-table gradient and Adam included -- is one C call
+(bsarec_gru4rec_train_step, csrc/gru4rec_step.h).  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -213,7 +215,16 @@ class GRU4RecModel(nn.Module):
     masked), no dropout between layers; out = y . dense.weight^T + dense.bias, [B, L, d].
     Loss: BPR at the last position, mean_b -log(sigmoid(s . E[answers] - s . E[neg_answers]) + 1e-10) with s = out[:, L - 1].
     Init: Embedding and Linear weights N(0, initializer_range), the Linear bias 0, GRU weights U(-1 / sqrt(H), 1 / sqrt(H)).
-    Steps through calculate_loss / backward / torch.optim.Adam (``torch_optim``), single GPU."""
+
+    ``args.gru_step`` selects how the model steps, single GPU either way:
+      "torch" (the default, also when absent): calculate_loss / backward / torch.optim.Adam (``torch_optim``); the dropout mask
+        is drawn from a torch generator seeded by ``set_seed``.
+      "fused": ``train_step`` is ONE C call (bsarec_gru4rec_train_step: lookup, dropout, GRU, BPR head, every gradient, Adam on
+        the item table and on the GRU flat array), replayed from a hipGraph per batch shape unless ``args.gru_step_graph`` is
+        False; the instance sets ``torch_optim = False`` so that Trainer.iteration calls it.  Its dropout mask is the library's
+        Philox stream (site 0, the step counter of the device state that ``set_seed`` seeds and resets).  The two streams have
+        the same distribution and DIFFERENT draws: the two modes do not train bit for bit alike at p > 0.
+    calculate_loss, forward, predict and last_hidden are the same in both modes (torch-generator dropout in training mode)."""
 
     needs_negatives = True
     needs_same_target = False
@@ -222,6 +233,13 @@ class GRU4RecModel(nn.Module):
     def __init__(self, args):
         super().__init__()
         self.args = args
+        mode = getattr(args, "gru_step", "torch")
+        if mode not in ("torch", "fused"):
+            raise ValueError(f"gru_step must be 'torch' or 'fused', got {mode!r}")
+        self.gru_step = mode
+        if mode == "fused":
+            self.torch_optim = False                      # Trainer.iteration: the pairwise branch, model.train_step
+        self._fused = None                                # the fused step's buffers (_step_buffers)
         d, H = int(args.hidden_size), int(getattr(args, "gru_hidden_size", 64))
         self.item_embeddings = nn.Embedding(int(args.item_size), d)
         self.gru_layers = GruStack(d, H, int(args.num_hidden_layers), d)
@@ -238,17 +256,25 @@ class GRU4RecModel(nn.Module):
         out = super()._apply(fn, recurse)
         self.gru_layers.reflatten()
         self._gen = None
+        self._fused = None                                # with the Adam moments and the step state, as the workspace pool goes
         return out
 
+    def _stream_seed(self):
+        return (self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF
+
     def set_seed(self, seed: int, rank: int = 0):
-        """Seed of the dropout draws (rank-decorrelated)."""
+        """Seed of the dropout draws (rank-decorrelated): of the torch generator and of the fused step's device state, whose
+        step counter goes back to 0."""
         self._seed, self._rank = int(seed), int(rank)
         self._gen = None
+        if self._fused is not None:
+            self._fused["state"][0] = self._stream_seed()
+            self._fused["state"][1] = 0
 
     def _generator(self, device):
         if self._gen is None or self._gen.device != device:
             self._gen = torch.Generator(device=device)
-            self._gen.manual_seed((self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF)
+            self._gen.manual_seed(self._stream_seed())
         return self._gen
 
     def _require_gpu(self, input_ids=None):
@@ -289,5 +315,119 @@ class GRU4RecModel(nn.Module):
         diff = (s * pos).sum(-1) - (s * neg).sum(-1)
         return -torch.log(torch.sigmoid(diff) + 1e-10).mean()
 
+    # ---- the fused step (gru_step = "fused"; bsarec_gru4rec_loss_grad / bsarec_gru4rec_train_step) -------------------------
+    def _step_buffers(self):
+        """What the fused step owns beside the parameters: the device step state (seed, step counter, Adam t), both gradient
+        arrays, the Adam moments of the item table and of the GRU flat array, and per batch shape a workspace, static id
+        buffers and a captured graph.  Built on first use; dropped by ``.to()`` / ``reflatten()`` (a new parameter storage)."""
+        self._require_gpu()
+        self.gru_layers.reflatten()
+        E, flat = self.item_embeddings.weight.data, self.gru_layers._flat
+        if flat.device != E.device or not E.is_contiguous() or E.dtype != torch.float32:
+            raise RuntimeError("gru4rec: the item table and the GRU weights must be contiguous fp32 on one device")
+        key = (E.data_ptr(), flat.data_ptr(), E.device)
+        f = self._fused
+        if f is None or f["key"] != key:
+            state = torch.zeros(8, dtype=torch.int64, device=E.device)
+            state[0] = self._stream_seed()
+            f = dict(key=key, state=state, E=E, flat=flat, dE=torch.empty_like(E), dW=torch.empty_like(flat),
+                     mE=torch.zeros_like(E), vE=torch.zeros_like(E), mW=torch.zeros_like(flat), vW=torch.zeros_like(flat),
+                     adam=None, slots={})
+            self._fused = f
+        return f
+
+    @property
+    def step_state(self) -> torch.Tensor:
+        """The fused step's device state, int64[8]: [0] the Philox seed, [1] the step counter of the dropout stream, [2] Adam's t."""
+        return self._step_buffers()["state"]
+
+    def _slot(self, f, B: int, Lq: int):
+        s = f["slots"].get((B, Lq))
+        if s is None:
+            g = self.gru_layers
+            cfg = L.Gru4RecConfig(L.GruConfig(B, Lq, g.input_size, g.hidden_size, g.num_layers, g.out_size),
+                                  self.item_embeddings.num_embeddings, self.p_drop)
+            nbytes = L.load().bsarec_gru4rec_workspace_bytes(cfg)
+            if nbytes < 0:
+                raise ValueError(f"gru4rec: unsupported step shape B = {B}, L = {Lq}, dropout = {self.p_drop} "
+                                 "(1 <= B <= 65536, 1 <= L <= 256, 0 <= p < 1)")
+            dev = f["E"].device
+            s = dict(cfg=cfg, nbytes=nbytes, ws=torch.empty(nbytes, dtype=torch.uint8, device=dev),
+                     ids=torch.zeros((B, Lq), dtype=torch.int64, device=dev), ans=torch.zeros(B, dtype=torch.int64, device=dev),
+                     neg=torch.zeros(B, dtype=torch.int64, device=dev), loss=torch.zeros((), dtype=torch.float32, device=dev),
+                     graph=None)
+            f["slots"][(B, Lq)] = s
+        return s
+
+    def _fill(self, s, input_ids, answers, neg_answers):
+        if neg_answers is None:
+            raise ValueError("GRU4Rec's loss needs neg_answers")
+        if input_ids.dim() != 2:
+            raise ValueError(f"gru4rec: input_ids must be [B, L], got {tuple(input_ids.shape)}")
+        s["ids"].copy_(input_ids)
+        s["ans"].copy_(answers.reshape(-1))
+        s["neg"].copy_(neg_answers.reshape(-1))
+
+    def _loss_grad(self, f, s, train: bool):
+        stream = torch.cuda.current_stream(f["E"].device).cuda_stream
+        L.check(L.load().bsarec_gru4rec_loss_grad(s["cfg"], f["E"].data_ptr(), f["flat"].data_ptr(), s["ids"].data_ptr(),
+                                                  s["ans"].data_ptr(), s["neg"].data_ptr(), f["state"].data_ptr(), int(train),
+                                                  s["loss"].data_ptr(), f["dE"].data_ptr(), f["dW"].data_ptr(), s["ws"].data_ptr(),
+                                                  s["nbytes"], stream), "bsarec_gru4rec_loss_grad")
+
+    def loss_and_grads(self, input_ids, answers, neg_answers, train: bool = True):
+        """The BPR loss (0-d tensor) and {state_dict key: gradient} of one batch through bsarec_gru4rec_loss_grad, no update.
+        ``train``: draw the next dropout mask of the device stream (the step counter advances); else no dropout."""
+        self._require_gpu(input_ids)
+        f = self._step_buffers()
+        s = self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1]))
+        self._fill(s, input_ids, answers, neg_answers)
+        self._loss_grad(f, s, train)
+        grads = OrderedDict([("item_embeddings.weight", f["dE"].clone())])
+        names = {"out_weight": "dense.weight", "out_bias": "dense.bias"}
+        for name, (o, n, shp) in self.gru_layers._slices.items():
+            grads[names.get(name, "gru_layers." + name)] = f["dW"][o:o + n].view(shp).clone()
+        return s["loss"].clone(), grads
+
+    def _adam_structs(self, f):
+        if f["adam"] is None:
+            a = self.args
+            hyper = (float(getattr(a, "lr", 1e-3)), float(getattr(a, "adam_beta1", 0.9)), float(getattr(a, "adam_beta2", 0.999)),
+                     1e-8, float(getattr(a, "weight_decay", 0.0)), 1.0, None, 0)
+            f["adam"] = (L.Adam(f["E"].data_ptr(), f["dE"].data_ptr(), f["mE"].data_ptr(), f["vE"].data_ptr(), f["E"].numel(), *hyper),
+                         L.Adam(f["flat"].data_ptr(), f["dW"].data_ptr(), f["mW"].data_ptr(), f["vW"].data_ptr(), f["flat"].numel(),
+                                *hyper))
+        return f["adam"]
+
+    def _train_step(self, f, s):
+        items, weights = self._adam_structs(f)
+        stream = torch.cuda.current_stream(f["E"].device).cuda_stream
+        L.check(L.load().bsarec_gru4rec_train_step(s["cfg"], s["ids"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), items,
+                                                   weights, f["state"].data_ptr(), s["loss"].data_ptr(), s["ws"].data_ptr(),
+                                                   s["nbytes"], stream), "bsarec_gru4rec_train_step")
+
     def train_step(self, input_ids, answers, neg_answers=None, same_target=None):
-        raise RuntimeError("GRU4Rec steps through calculate_loss / backward / torch.optim.Adam (Trainer does)")
+        """gru_step = "fused": one optimisation step in one C call -- the step counter, lookup + Philox dropout, the GRU stack,
+        the BPR head, every gradient, Adam (``args.lr``, ``adam_beta1``, ``adam_beta2``, ``weight_decay``) on the item table and
+        on the GRU flat array, in place.  Returns the mean loss as a 0-d device tensor (no host sync; the next step overwrites
+        it).  The call is captured once per batch shape over static id buffers and replayed -- the mask and Adam's t advance on
+        the device, and the capture is one linear chain on one stream, so it has no parallel branches to replay;
+        ``args.gru_step_graph = False`` calls eagerly instead."""
+        if self.gru_step != "fused":
+            raise RuntimeError("GRU4Rec steps through calculate_loss / backward / torch.optim.Adam (Trainer does)")
+        self._require_gpu(input_ids)
+        f = self._step_buffers()
+        s = self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1]))
+        self._fill(s, input_ids, answers, neg_answers)
+        if not getattr(self.args, "gru_step_graph", True):
+            self._train_step(f, s)
+            return s["loss"]
+        if s["graph"] is None:
+            self._adam_structs(f)
+            self._loss_grad(f, s, False)                  # every kernel of the chain has run once before the capture; no
+            graph = torch.cuda.CUDAGraph()                # counter moves and nothing is updated (train = 0)
+            with torch.cuda.graph(graph):
+                self._train_step(f, s)
+            s["graph"] = graph
+        s["graph"].replay()
+        return s["loss"]

@@ -153,6 +153,9 @@ def parse_args(argv=None):
     # not a reference flag: width of GRU4Rec's recurrent state (--model_type GRU4Rec).  Absent unless given, as the flags above
     p.add_argument("--gru_hidden_size", default=argparse.SUPPRESS, type=int, choices=(32, 64, 96, 128),
                    help="GRU4Rec: hidden size of the GRU layers (default 64)")
+    p.add_argument("--gru_step", default=argparse.SUPPRESS, choices=("torch", "fused"),
+                   help="GRU4Rec: step through autograd and torch.optim.Adam (default) or through the one-call HIP step "
+                        "(lookup, Philox dropout, BPR head, item-table gradient and Adam in the library)")
     args = p.parse_args(argv)
     n = getattr(args, "eval_negatives", 0)
     if n > 0 and hasattr(args, "eval_full_rank"):

@@ -589,6 +589,50 @@ int bsarec_gru_fwd(const bsarec_gru_config_t *cfg, const float *x, const float *
 int bsarec_gru_bwd(const bsarec_gru_config_t *cfg, const float *x, const float *weights, int last_only, const float *dout,
                    void *workspace, long workspace_bytes, float *dx, float *dweights, void *stream);
 
+/* One GRU4Rec training step (csrc/gru4rec_step.h): with E = item_emb [V, d], x = Dropout_p(E[ids]) [B, L, d], s = the GRU stack's
+ * output at position L - 1 (bsarec_gru_fwd, last_only) and
+ *   diff_b = s_b . E[answers_b] - s_b . E[neg_answers_b],  loss = mean_b -log(sigmoid(diff_b) + 1e-10),
+ * bsarec_gru4rec_loss_grad writes the loss (one float) and the gradient of every parameter: d_item_emb [V, d] -- the lookup rows
+ * dE[ids[b, t]] += dx[b, t] * mask plus the head's 2 B rows; EVERY float is written, zero where no row was touched -- and dweights
+ * in the layout of bsarec_gru_fwd's weights.  Id 0 is an ordinary row (nn.Embedding without padding_idx).  The sigmoid gives 0 or 1
+ * exactly for large |diff| and never NaN.
+ *   Dropout is the library's Philox stream, site 0, element index (b L + t) d + c, keyed by the device-resident step state
+ * (`state`: u64[8], [0] = seed, [1] = forward-step counter, [2] = Adam t, [3..6] owned by the library).  A call with train != 0
+ * advances the step counter FIRST and draws with the new value, as bsarec_train_step does; train = 0 draws nothing (the result of
+ * dropout = 0) and touches no counter.  The mask is regenerated in the backward, not stored.
+ *   bsarec_gru4rec_train_step is the above with train = 1 followed by Adam on both arrays, Adam's t advanced ONCE:
+ * adam_items->params / grads are E / dE with n = V d, adam_weights->params / grads the GRU flat array and its gradient with
+ * n = bsarec_gru_weight_floats(&cfg->gru); grads are written, then read.  lr, beta1 and beta2 of the two must agree (one t and one
+ * pair of bias corrections serve both); shadow_bf16, grads2, grads2_n, n_grad_srcs and wimage_plan must be null / 0.
+ *   Launches, all on `stream`, one after the other: the step counter (train != 0), lookup + dropout, bsarec_gru_fwd, the BPR
+ * rows, bsarec_gru_bwd, the item-table gradient, its flush with the mean loss (and Adam's t) in a closing block, then one Adam
+ * launch per array.  No allocation, no host synchronisation: capturable, and a replay of a captured bsarec_gru4rec_train_step is
+ * the NEXT step -- a fresh mask, the next t.  Every output is bit-deterministic: the item-table gradient is summed in 64-bit fixed
+ * point (2^-40 units, exact while |sum| < 2^22, the range of the BSARec lookup path), the mean loss in one fixed order.  The result
+ * does not depend on what the workspace holds on entry.
+ *   Workspace: bsarec_gru4rec_workspace_bytes(cfg) bytes (host-only query, no HIP call).  In floats, with T = L B: the GRU
+ * workspace of train = 1 | x [T, d] | s [B, d] | ds [B, d] | dx [T, d] | c [B, rounded up to 4] | loss rows [B, rounded up to 4] |
+ * the accumulator, V d 64-bit words.
+ *   Limits (else < 0 before any HIP call): cfg->gru inside the limits of bsarec_gru_workspace_bytes with input_size == out_size;
+ * item_size >= 2; 0 <= dropout < 1 (NaN refused); every pointer non-null; the float arrays (Adam's four included) and the
+ * workspace 16-byte aligned, ids / answers / neg_answers / state 8-byte, loss_out 4-byte; workspace_bytes at least the queried
+ * size; adam_*->n as above.  ids, answers and neg_answers inside [0, V) are the caller's contract.  Outputs may not alias
+ * inputs, each other or the workspace. */
+typedef struct {
+    bsarec_gru_config_t gru;           /* input_size == out_size == d, the embedding width */
+    int item_size;                     /* V >= 2 */
+    float dropout;                     /* p in [0, 1) */
+} bsarec_gru4rec_config_t;
+long bsarec_gru4rec_workspace_bytes(const bsarec_gru4rec_config_t *cfg);
+int bsarec_gru4rec_loss_grad(const bsarec_gru4rec_config_t *cfg, const float *item_emb, const float *weights,
+                             const int64_t *ids, const int64_t *answers, const int64_t *neg_answers,
+                             void *state, int train, float *loss_out, float *d_item_emb, float *dweights,
+                             void *workspace, long workspace_bytes, void *stream);
+int bsarec_gru4rec_train_step(const bsarec_gru4rec_config_t *cfg, const int64_t *ids, const int64_t *answers,
+                              const int64_t *neg_answers, const bsarec_adam_t *adam_items,
+                              const bsarec_adam_t *adam_weights, void *state, float *loss_out,
+                              void *workspace, long workspace_bytes, void *stream);
+
 /* Stand-alone FrequencyLayer (src/model/bsarec.py:90-104) for per-op parity tests:
  * y = LN(Drop(low + beta^2 (x - low)) + x); backward given dy. */
 int bsarec_freq_layer_fwd(const float *x, const float *sqrt_beta, const float *ln_w, const float *ln_b,
