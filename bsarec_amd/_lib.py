@@ -147,6 +147,15 @@ class Gru4RecConfig(C.Structure):
     _fields_ = [("gru", GruConfig), ("item_size", C.c_int), ("dropout", C.c_float)]
 
 
+class Gru4RecHead(C.Structure):
+    """bsarec_gru4rec_head_t"""
+    _fields_ = [("loss", C.c_int), ("candidates", C.c_int), ("bpreg", C.c_float)]
+
+
+GRU4REC_CAND_MAX = 8192                          # BSAREC_GRU4REC_CAND_MAX: the most candidate columns of a GRU4Rec head
+GRU4REC_LOSSES = {"ce": 1, "top1": 2, "bpr_max": 3}                 # bsarec_gru4rec_head_t.loss
+GRU4REC_CANDIDATES = {"in_batch": 1, "in_batch+sampled": 2}         # bsarec_gru4rec_head_t.candidates
+
 HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)          # bsarec_hook_t
 
 
@@ -226,6 +235,14 @@ EXPORTS = {
                                  [C.c_long, C.c_void_p]),
     "bsarec_gru4rec_train_step": (C.c_int, [C.POINTER(Gru4RecConfig)] + [C.c_void_p] * 3 + [C.POINTER(Adam)] * 2 +
                                   [C.c_void_p] * 3 + [C.c_long, C.c_void_p]),
+    "bsarec_gru4rec_cand_head_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.POINTER(Gru4RecHead)]),
+    "bsarec_gru4rec_cand_head": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.POINTER(Gru4RecHead)] + [C.c_void_p] * 4 +
+                                 [C.c_long, C.c_void_p]),
+    "bsarec_gru4rec_cand_workspace_bytes": (C.c_long, [C.POINTER(Gru4RecConfig), C.POINTER(Gru4RecHead)]),
+    "bsarec_gru4rec_cand_loss_grad": (C.c_int, [C.POINTER(Gru4RecConfig)] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4 +
+                                      [C.c_long, C.c_void_p, C.POINTER(Gru4RecHead)]),
+    "bsarec_gru4rec_cand_train_step": (C.c_int, [C.POINTER(Gru4RecConfig)] + [C.c_void_p] * 3 + [C.POINTER(Adam)] * 2 +
+                                       [C.c_void_p] * 3 + [C.c_long, C.c_void_p, C.POINTER(Gru4RecHead)]),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

@@ -20,6 +20,7 @@
 #include "lazy_adam.h"
 #include "gru.h"
 #include "gru4rec_step.h"
+#include "gru4rec_cand.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -2420,10 +2421,73 @@ static int gru4rec_args(const bsarec_gru4rec_config_t* cfg, const float* item_em
     return 0;
 }
 
-// tick_adam: null, or the Adam whose t the step's closing block advances (bsarec_gru4rec_train_step)
+// The heads over candidates shared by the batch (gru4rec_cand.h; bsarec_gru4rec_cand_*): in a step, scores, rows, backward (and
+// slab sum) stand where the BPR rows do, and the item-table gradient runs over T + C rows
+static int g4c_head_check(const bsarec_gru4rec_head_t* h, long B) {
+    if (!h) return -10;
+    if (h->loss < G4C_CE || h->loss > G4C_BPR_MAX || h->candidates < 1 || h->candidates > 2) return -10;
+    if (!(h->bpreg >= 0.f)) return -10;                                 // NaN fails the comparison
+    if (B < 1 || B * h->candidates > G4C_MAX) return -10;
+    return 0;
+}
+
+// The head's own regions, in floats from `off` (every one a multiple of 4): R / G [B][C] | slabs of dEc [nslab][C][d] | slabs of
+// ds [nslab][B][d] (both empty when nslab is 1).  A slab of dEc sums chunkB rows, one of ds chunkC candidates.  The products are
+// bound by the latency of their 16-deep k-slices (about 3 us each, measured), not by their flops, so the summed dimension is cut
+// short: nslab = min(16, ceil(C / 64)), i.e. at least 64 candidates per slab of ds, lowered while the slabs would pass 2^26 floats.
+struct G4cWs { long R, slabE, slabS, end; int C, nslab, chunkB, chunkC; };
+static G4cWs g4c_ws(long B, int candidates, long d, long off) {
+    G4cWs w;
+    w.C = (int)(B * candidates);
+    w.nslab = std::min(16, cdiv(w.C, SSM_TILE));
+    while (w.nslab > 1 && w.nslab * (B + w.C) * d > (1L << 26)) --w.nslab;
+    w.chunkB = (int)rup(cdiv(B, w.nslab), SSM_KS);
+    w.chunkC = (int)rup(cdiv(w.C, w.nslab), SSM_TILE);
+    w.R = off; off += rup(B * w.C, 4);
+    w.slabE = off; off += w.nslab > 1 ? w.nslab * (long)w.C * d : 0;
+    w.slabS = off; off += w.nslab > 1 ? w.nslab * B * d : 0;
+    w.end = off;
+    return w;
+}
+
+// scores, rows, backward (+ slab sum): loss_rows [B], ds [B][d] and dEc [C][d] are written
+static void g4c_launch(const G4cWs& g, float* w, const float* sv, const float* E, const int64_t* answers, const int64_t* neg_answers,
+                       int B, int d, int V, const bsarec_gru4rec_head_t& head, float* loss_rows, float* ds, float* dEc,
+                       hipStream_t s) {
+    Gru4RecCandP P;
+    memset(&P, 0, sizeof(P));
+    P.s = sv; P.E = E; P.ans = answers; P.neg = neg_answers; P.B = B; P.C = g.C; P.d = d; P.V = V; P.loss = head.loss;
+    P.bpreg = head.bpreg; P.R = w + g.R; P.loss_rows = loss_rows;
+    P.nslab = g.nslab; P.chunkB = g.chunkB; P.chunkC = g.chunkC;
+    const bool direct = g.nslab == 1;
+    P.outE = direct ? dEc : w + g.slabE; P.strideE = (long)g.C * d;
+    P.outS = direct ? ds : w + g.slabS; P.strideS = (long)B * d;
+    const int dt = cdiv(d, SSM_TILE), ct = cdiv(g.C, SSM_TILE), rt = cdiv(B, SSM_TILE);
+    P.tilesA = ct * dt * g.nslab;
+    hipLaunchKernelGGL(g4c_scores_kernel, dim3(ct, rt), dim3(ROW_THREADS), 0, s, P);
+    hipLaunchKernelGGL(g4c_rows_kernel, dim3(B), dim3(ROW_THREADS), 0, s, P);
+    hipLaunchKernelGGL(g4c_bwd_kernel, dim3(P.tilesA + rt * dt * g.nslab), dim3(ROW_THREADS), 0, s, P);
+    if (!direct) {
+        const long nE4 = (long)g.C * d / 4, nS4 = (long)B * d / 4;
+        hipLaunchKernelGGL(g4c_slab_sum_kernel, dim3(cdiv(nE4 + nS4, ROW_THREADS)), dim3(ROW_THREADS), 0, s, w + g.slabE,
+                           w + g.slabS, g.nslab, nE4, nS4, dEc, ds);
+    }
+}
+
+// a candidate step's workspace: the step's (gru4rec_ws; its c region is not used), then the head's regions, then dEc [C][d]
+static G4cWs g4c_step_ws(const bsarec_gru4rec_config_t& c, const bsarec_gru4rec_head_t& h, long* dEc, long* total) {
+    const G4cWs g = g4c_ws(c.gru.batch, h.candidates, c.gru.input_size, gru4rec_ws(c).total);
+    *dEc = g.end;
+    *total = g.end + (long)g.C * c.gru.input_size;
+    return g;
+}
+
+// tick_adam: null, or the Adam whose t the step's closing block advances (bsarec_gru4rec_train_step); head: null (the BPR rows
+// against one negative per row), or the head over shared candidates
 static int gru4rec_run(const bsarec_gru4rec_config_t& c, const float* E, const float* weights, const int64_t* ids,
                        const int64_t* answers, const int64_t* neg_answers, void* state, int train, float* loss_out, float* dE,
-                       float* dweights, void* workspace, const bsarec_adam_t* tick_adam, hipStream_t s) {
+                       float* dweights, void* workspace, const bsarec_adam_t* tick_adam, const bsarec_gru4rec_head_t* head,
+                       hipStream_t s) {
     const int B = c.gru.batch, d = c.gru.input_size, V = c.item_size;
     const long T = (long)B * c.gru.seq_len;
     const Gru4RecWs ws = gru4rec_ws(c);
@@ -2442,17 +2506,33 @@ static int gru4rec_run(const bsarec_gru4rec_config_t& c, const float* E, const f
                                        dim3(ROW_THREADS), 0, s, pe));
     RET(bsarec_gru_fwd(&c.gru, w + ws.x, weights, 1, 1, w + ws.s, w + ws.gru, ws.gru_bytes, s));
 
-    Gru4RecBprP pb;
-    pb.s = w + ws.s; pb.E = E; pb.ans = answers; pb.neg = neg_answers; pb.B = B; pb.d = d; pb.V = V;
-    pb.ds = w + ws.ds; pb.c = w + ws.c; pb.loss_rows = w + ws.rows;
-    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_bpr_kernel<LPR>, dim3(cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS), 0, s, pb));
+    long dEc = 0, total = 0;
+    G4cWs g = {};
+    if (head) {
+        g = g4c_step_ws(c, *head, &dEc, &total);
+        g4c_launch(g, w, w + ws.s, E, answers, neg_answers, B, d, V, *head, w + ws.rows, w + ws.ds, w + dEc, s);
+    } else {
+        Gru4RecBprP pb;
+        pb.s = w + ws.s; pb.E = E; pb.ans = answers; pb.neg = neg_answers; pb.B = B; pb.d = d; pb.V = V;
+        pb.ds = w + ws.ds; pb.c = w + ws.c; pb.loss_rows = w + ws.rows;
+        DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_bpr_kernel<LPR>, dim3(cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS), 0, s, pb));
+    }
     RET(bsarec_gru_bwd(&c.gru, w + ws.x, weights, 1, w + ws.ds, w + ws.gru, ws.gru_bytes, w + ws.dx, dweights, s));
 
-    Gru4RecGradP pg;
-    pg.dx = w + ws.dx; pg.ids = ids; pg.s = w + ws.s; pg.c = w + ws.c; pg.ans = answers; pg.neg = neg_answers;
-    pg.T = T; pg.B = B; pg.d = d; pg.V = V; pg.drop = drop; pg.dA = acc;
-    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_item_grad_kernel<LPR>, dim3(cdiv(T + 2L * B, SCATTER_FLOATS / (4 * LPR))),
-                                       dim3(ROW_THREADS), 0, s, pg));
+    if (head) {
+        Gru4RecCandGradP pg;
+        memset(&pg, 0, sizeof(pg));
+        pg.dx = w + ws.dx; pg.ids = ids; pg.dEc = w + dEc; pg.T = T; pg.d = d; pg.drop = drop; pg.dA = acc;
+        pg.head.ans = answers; pg.head.neg = neg_answers; pg.head.B = B; pg.head.C = g.C; pg.head.V = V;
+        DISPATCH_LPR(d, hipLaunchKernelGGL(g4c_item_grad_kernel<LPR>, dim3(cdiv(T + g.C, SCATTER_FLOATS / (4 * LPR))),
+                                           dim3(ROW_THREADS), 0, s, pg));
+    } else {
+        Gru4RecGradP pg;
+        pg.dx = w + ws.dx; pg.ids = ids; pg.s = w + ws.s; pg.c = w + ws.c; pg.ans = answers; pg.neg = neg_answers;
+        pg.T = T; pg.B = B; pg.d = d; pg.V = V; pg.drop = drop; pg.dA = acc;
+        DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_item_grad_kernel<LPR>, dim3(cdiv(T + 2L * B, SCATTER_FLOATS / (4 * LPR))),
+                                           dim3(ROW_THREADS), 0, s, pg));
+    }
 
     LookupAcc la;
     memset(&la, 0, sizeof(la));
@@ -2465,14 +2545,43 @@ static int gru4rec_run(const bsarec_gru4rec_config_t& c, const float* E, const f
     return (int)hipGetLastError();
 }
 
+extern "C" long bsarec_gru4rec_cand_workspace_bytes(const bsarec_gru4rec_config_t* cfg, const bsarec_gru4rec_head_t* head) {
+    if (gru4rec_check(cfg) || g4c_head_check(head, cfg->gru.batch)) return -10;
+    long dEc, total;
+    g4c_step_ws(*cfg, *head, &dEc, &total);
+    return total * (long)sizeof(float);
+}
+
+// head: null, or checked here with the larger workspace it needs
+static int gru4rec_loss_grad(const bsarec_gru4rec_config_t* cfg, const float* item_emb, const float* weights, const int64_t* ids,
+                             const int64_t* answers, const int64_t* neg_answers, void* state, int train, float* loss_out,
+                             float* d_item_emb, float* dweights, void* workspace, long workspace_bytes,
+                             const bsarec_adam_t* tick_adam, const bsarec_gru4rec_head_t* head, hipStream_t s) {
+    RET(gru4rec_args(cfg, item_emb, weights, ids, answers, neg_answers, state, loss_out, d_item_emb, dweights, workspace,
+                     workspace_bytes));
+    if (head) {
+        RET(g4c_head_check(head, cfg->gru.batch));
+        if (workspace_bytes < bsarec_gru4rec_cand_workspace_bytes(cfg, head)) return -10;
+    }
+    return gru4rec_run(*cfg, item_emb, weights, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights, workspace,
+                       tick_adam, head, s);
+}
+
 extern "C" int bsarec_gru4rec_loss_grad(const bsarec_gru4rec_config_t* cfg, const float* item_emb, const float* weights,
                                         const int64_t* ids, const int64_t* answers, const int64_t* neg_answers, void* state,
                                         int train, float* loss_out, float* d_item_emb, float* dweights, void* workspace,
                                         long workspace_bytes, void* stream) {
-    RET(gru4rec_args(cfg, item_emb, weights, ids, answers, neg_answers, state, loss_out, d_item_emb, dweights, workspace,
-                     workspace_bytes));
-    return gru4rec_run(*cfg, item_emb, weights, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights, workspace,
-                       nullptr, (hipStream_t)stream);
+    return gru4rec_loss_grad(cfg, item_emb, weights, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights,
+                             workspace, workspace_bytes, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int bsarec_gru4rec_cand_loss_grad(const bsarec_gru4rec_config_t* cfg, const float* item_emb, const float* weights,
+                                             const int64_t* ids, const int64_t* answers, const int64_t* neg_answers, void* state,
+                                             int train, float* loss_out, float* d_item_emb, float* dweights, void* workspace,
+                                             long workspace_bytes, void* stream, const bsarec_gru4rec_head_t* head) {
+    if (!head) return -10;
+    return gru4rec_loss_grad(cfg, item_emb, weights, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights,
+                             workspace, workspace_bytes, nullptr, head, (hipStream_t)stream);
 }
 
 // fp32 arrays only, one gradient source, 16-byte aligned
@@ -2485,10 +2594,10 @@ static int gru4rec_adam_check(const bsarec_adam_t* a, long n) {
     return 0;
 }
 
-extern "C" int bsarec_gru4rec_train_step(const bsarec_gru4rec_config_t* cfg, const int64_t* ids, const int64_t* answers,
-                                         const int64_t* neg_answers, const bsarec_adam_t* adam_items,
-                                         const bsarec_adam_t* adam_weights, void* state, float* loss_out, void* workspace,
-                                         long workspace_bytes, void* stream) {
+static int gru4rec_train_step(const bsarec_gru4rec_config_t* cfg, const int64_t* ids, const int64_t* answers,
+                              const int64_t* neg_answers, const bsarec_adam_t* adam_items, const bsarec_adam_t* adam_weights,
+                              void* state, float* loss_out, void* workspace, long workspace_bytes,
+                              const bsarec_gru4rec_head_t* head, void* stream) {
     RET(gru4rec_check(cfg));
     RET(gru4rec_adam_check(adam_items, (long)cfg->item_size * cfg->gru.input_size));
     RET(gru4rec_adam_check(adam_weights, gru_weights(cfg->gru).total));
@@ -2497,13 +2606,56 @@ extern "C" int bsarec_gru4rec_train_step(const bsarec_gru4rec_config_t* cfg, con
         return -10;
     float* dE = const_cast<float*>(adam_items->grads);
     float* dW = const_cast<float*>(adam_weights->grads);
-    RET(gru4rec_args(cfg, adam_items->params, adam_weights->params, ids, answers, neg_answers, state, loss_out, dE, dW, workspace,
-                     workspace_bytes));
     hipStream_t s = (hipStream_t)stream;
-    RET(gru4rec_run(*cfg, adam_items->params, adam_weights->params, ids, answers, neg_answers, state, 1, loss_out, dE, dW, workspace,
-                    adam_items, s));
+    RET(gru4rec_loss_grad(cfg, adam_items->params, adam_weights->params, ids, answers, neg_answers, state, 1, loss_out, dE, dW,
+                          workspace, workspace_bytes, adam_items, head, s));
     RET(adam_launch(*adam_items, state, s));
     return adam_launch(*adam_weights, state, s);
+}
+
+extern "C" int bsarec_gru4rec_train_step(const bsarec_gru4rec_config_t* cfg, const int64_t* ids, const int64_t* answers,
+                                         const int64_t* neg_answers, const bsarec_adam_t* adam_items,
+                                         const bsarec_adam_t* adam_weights, void* state, float* loss_out, void* workspace,
+                                         long workspace_bytes, void* stream) {
+    return gru4rec_train_step(cfg, ids, answers, neg_answers, adam_items, adam_weights, state, loss_out, workspace, workspace_bytes,
+                              nullptr, stream);
+}
+
+extern "C" int bsarec_gru4rec_cand_train_step(const bsarec_gru4rec_config_t* cfg, const int64_t* ids, const int64_t* answers,
+                                              const int64_t* neg_answers, const bsarec_adam_t* adam_items,
+                                              const bsarec_adam_t* adam_weights, void* state, float* loss_out, void* workspace,
+                                              long workspace_bytes, void* stream, const bsarec_gru4rec_head_t* head) {
+    if (!head) return -10;
+    return gru4rec_train_step(cfg, ids, answers, neg_answers, adam_items, adam_weights, state, loss_out, workspace, workspace_bytes,
+                              head, stream);
+}
+
+static int g4c_alone_check(int B, int d, int V, const bsarec_gru4rec_head_t* head) {
+    if (B < 1 || B > 65536 || d < 4 || d > 256 || d % 4 || V < 2) return -10;
+    return g4c_head_check(head, B);
+}
+
+// the head alone: its regions, then the loss rows [B up to 4]
+extern "C" long bsarec_gru4rec_cand_head_workspace_bytes(int batch, int width, const bsarec_gru4rec_head_t* head) {
+    if (g4c_alone_check(batch, width, 2, head)) return -10;
+    return (g4c_ws(batch, head->candidates, width, 0).end + rup(batch, 4)) * (long)sizeof(float);
+}
+
+extern "C" int bsarec_gru4rec_cand_head(const float* s, const float* item_emb, const int64_t* answers, const int64_t* neg_answers,
+                                        int batch, int width, int item_size, const bsarec_gru4rec_head_t* head, float* loss_out,
+                                        float* ds, float* dEc, void* workspace, long workspace_bytes, void* stream) {
+    RET(g4c_alone_check(batch, width, item_size, head));
+    for (const void* p : {(const void*)s, (const void*)item_emb, (const void*)ds, (const void*)dEc, (const void*)workspace})
+        if (!aligned_to(p, 16)) return -10;
+    if (!aligned_to(answers, 8) || !aligned_to(neg_answers, 8) || !aligned_to(loss_out, 4)) return -10;
+    if (workspace_bytes < bsarec_gru4rec_cand_head_workspace_bytes(batch, width, head)) return -10;
+    const G4cWs g = g4c_ws(batch, head->candidates, width, 0);
+    float* w = (float*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    g4c_launch(g, w, s, item_emb, answers, neg_answers, batch, width, item_size, *head, w + g.end, ds, dEc, st);
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(ROW_THREADS), 0, st,
+                       make_tick(nullptr, 0, 0.f, 0.f, 0.f, w + g.end, batch, loss_out, nullptr, 0, 0));
+    return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------

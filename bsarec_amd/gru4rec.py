@@ -6,7 +6,9 @@ The contract of this model is the math of its docstrings, checked against ``torc
 the dropped-out embeddings and the output runs in libbsarec_hip.so in both directions (bsarec_gru_fwd / bsarec_gru_bwd,
 csrc/gru.h); on the default path the embedding lookup, the dropout mask and the B-row BPR head are torch ops.  With
 ``gru_step = "fused"`` the whole training step -- those parts, the item-table gradient and Adam included -- is one C call
-(bsarec_gru4rec_train_step, csrc/gru4rec_step.h).  There is no CPU path.
+(bsarec_gru4rec_train_step, csrc/gru4rec_step.h).  ``gru_loss`` / ``gru_negatives`` replace the pairwise BPR loss by
+cross-entropy, TOP1 or BPR-max over mini-batch negatives (csrc/gru4rec_cand.h inside the fused step, ``cand_head_loss`` in torch
+ops on the default path).  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -196,6 +198,38 @@ class GruStack(nn.Module):
         return out
 
 
+GRU_LOSSES = ("bpr",) + tuple(L.GRU4REC_LOSSES)
+GRU_NEGATIVES = ("pair",) + tuple(L.GRU4REC_CANDIDATES)
+
+
+def cand_head_loss(s, E, answers, neg_answers, loss: str, negatives: str, bpreg: float = 1.0):
+    """The heads over candidates shared by the batch (bsarec_gru4rec_cand_head, include/bsarec_hip.h) in torch ops, differentiable
+    in ``s`` [B, d] and ``E`` [V, d]: the loss of ``gru_step = "torch"`` and the cross-check of the HIP head.  The candidates are
+    the batch's answers ("in_batch") and behind them the negatives ("in_batch+sampled"); row b's positive is column b, its
+    negatives are the columns whose item is not answers[b]; a row without negatives has loss 0."""
+    cand = answers if negatives == "in_batch" else torch.cat([answers, neg_answers])
+    return cand_scores_loss(s @ E[cand].T, cand, answers, loss, bpreg)
+
+
+def cand_scores_loss(r, cand, answers, loss: str, bpreg: float = 1.0):
+    """``cand_head_loss`` from the scores r [B, C] of the candidates ``cand`` [C] (the first B are ``answers``)."""
+    B = r.shape[0]
+    pos = r[:, :B].diagonal().unsqueeze(1)
+    neg = cand.unsqueeze(0) != answers.unsqueeze(1)            # M_b
+    m = neg.sum(1)
+    some = m > 0
+    if loss == "ce":
+        keep = neg | torch.eye(B, r.shape[1], dtype=torch.bool, device=r.device)
+        rows = torch.logsumexp(r.masked_fill(~keep, -math.inf), 1) - pos.squeeze(1)
+    elif loss == "top1":
+        rows = ((torch.sigmoid(r - pos) + torch.sigmoid(r * r)) * neg).sum(1) / m.clamp(min=1)
+    else:
+        x = torch.where(some.unsqueeze(1), r.masked_fill(~neg, -math.inf), torch.zeros_like(r))
+        p = torch.softmax(x, 1)
+        rows = -torch.log((p * torch.sigmoid(pos - r)).sum(1) + 1e-10) + bpreg * (p * r * r).sum(1)
+    return torch.where(some, rows, torch.zeros_like(rows)).mean()
+
+
 class _Dense(nn.Module):
     """Holder of ``dense.weight`` / ``dense.bias``: views of the stack's flat tensor (the projection runs in bsarec_gru_fwd)."""
 
@@ -224,7 +258,15 @@ class GRU4RecModel(nn.Module):
         False; the instance sets ``torch_optim = False`` so that Trainer.iteration calls it.  Its dropout mask is the library's
         Philox stream (site 0, the step counter of the device state that ``set_seed`` seeds and resets).  The two streams have
         the same distribution and DIFFERENT draws: the two modes do not train bit for bit alike at p > 0.
-    calculate_loss, forward, predict and last_hidden are the same in both modes (torch-generator dropout in training mode)."""
+    calculate_loss, forward, predict and last_hidden are the same in both modes (torch-generator dropout in training mode).
+
+    ``args.gru_loss`` / ``args.gru_negatives`` / ``args.gru_bpreg`` select the loss at the last position.  "bpr" with "pair" (the
+    defaults, also when absent) is the pairwise loss above.  "ce", "top1" and "bpr_max" go with "in_batch" (the other rows'
+    answers are a row's negatives) or "in_batch+sampled" (those and every row's neg_answers): the heads of
+    bsarec_gru4rec_cand_head (include/bsarec_hip.h; ``cand_head_loss`` is their math in torch ops), ``gru_bpreg`` (default 1.0)
+    the weight of BPR-max's score regulariser.  With ``gru_step = "fused"`` the step calls bsarec_gru4rec_cand_train_step (the
+    head as HIP kernels inside the one C call), with "torch" calculate_loss forms the loss with torch ops.  Any other pair of
+    loss and negatives raises ValueError."""
 
     needs_negatives = True
     needs_same_target = False
@@ -237,6 +279,20 @@ class GRU4RecModel(nn.Module):
         if mode not in ("torch", "fused"):
             raise ValueError(f"gru_step must be 'torch' or 'fused', got {mode!r}")
         self.gru_step = mode
+        loss, negatives = getattr(args, "gru_loss", "bpr"), getattr(args, "gru_negatives", "pair")
+        if loss not in GRU_LOSSES:
+            raise ValueError(f"gru_loss must be one of {GRU_LOSSES}, got {loss!r}")
+        if negatives not in GRU_NEGATIVES:
+            raise ValueError(f"gru_negatives must be one of {GRU_NEGATIVES}, got {negatives!r}")
+        if (loss == "bpr") != (negatives == "pair"):
+            raise ValueError(f"gru_loss = {loss!r} does not go with gru_negatives = {negatives!r}: 'bpr' takes 'pair', and "
+                             f"{GRU_LOSSES[1:]} take {GRU_NEGATIVES[1:]}")
+        bpreg = float(getattr(args, "gru_bpreg", 1.0))
+        if not bpreg >= 0.0:
+            raise ValueError(f"gru_bpreg must be >= 0, got {bpreg}")
+        self.gru_loss, self.gru_negatives, self.gru_bpreg = loss, negatives, bpreg
+        # the head over shared candidates (bsarec_gru4rec_head_t), or None: the pairwise BPR head
+        self._head = None if loss == "bpr" else L.Gru4RecHead(L.GRU4REC_LOSSES[loss], L.GRU4REC_CANDIDATES[negatives], bpreg)
         if mode == "fused":
             self.torch_optim = False                      # Trainer.iteration: the pairwise branch, model.train_step
         self._fused = None                                # the fused step's buffers (_step_buffers)
@@ -310,6 +366,9 @@ class GRU4RecModel(nn.Module):
         self._require_gpu(input_ids)
         s = self.gru_layers(self._embed(input_ids, self.training), last_only=True)
         dev = s.device
+        if self._head is not None:
+            return cand_head_loss(s, self.item_embeddings.weight, answers.to(dev).reshape(-1), neg_answers.to(dev).reshape(-1),
+                                  self.gru_loss, self.gru_negatives, self.gru_bpreg)
         pos = self.item_embeddings(answers.to(dev))
         neg = self.item_embeddings(neg_answers.to(dev))
         diff = (s * pos).sum(-1) - (s * neg).sum(-1)
@@ -347,10 +406,15 @@ class GRU4RecModel(nn.Module):
             g = self.gru_layers
             cfg = L.Gru4RecConfig(L.GruConfig(B, Lq, g.input_size, g.hidden_size, g.num_layers, g.out_size),
                                   self.item_embeddings.num_embeddings, self.p_drop)
-            nbytes = L.load().bsarec_gru4rec_workspace_bytes(cfg)
+            if self._head is None:
+                nbytes = L.load().bsarec_gru4rec_workspace_bytes(cfg)
+            else:
+                nbytes = L.load().bsarec_gru4rec_cand_workspace_bytes(cfg, self._head)
             if nbytes < 0:
                 raise ValueError(f"gru4rec: unsupported step shape B = {B}, L = {Lq}, dropout = {self.p_drop} "
-                                 "(1 <= B <= 65536, 1 <= L <= 256, 0 <= p < 1)")
+                                 "(1 <= B <= 65536, 1 <= L <= 256, 0 <= p < 1" +
+                                 ("" if self._head is None else
+                                  f", at most {L.GRU4REC_CAND_MAX} candidates: {self._head.candidates} B") + ")")
             dev = f["E"].device
             s = dict(cfg=cfg, nbytes=nbytes, ws=torch.empty(nbytes, dtype=torch.uint8, device=dev),
                      ids=torch.zeros((B, Lq), dtype=torch.int64, device=dev), ans=torch.zeros(B, dtype=torch.int64, device=dev),
@@ -370,10 +434,13 @@ class GRU4RecModel(nn.Module):
 
     def _loss_grad(self, f, s, train: bool):
         stream = torch.cuda.current_stream(f["E"].device).cuda_stream
-        L.check(L.load().bsarec_gru4rec_loss_grad(s["cfg"], f["E"].data_ptr(), f["flat"].data_ptr(), s["ids"].data_ptr(),
-                                                  s["ans"].data_ptr(), s["neg"].data_ptr(), f["state"].data_ptr(), int(train),
-                                                  s["loss"].data_ptr(), f["dE"].data_ptr(), f["dW"].data_ptr(), s["ws"].data_ptr(),
-                                                  s["nbytes"], stream), "bsarec_gru4rec_loss_grad")
+        call = (s["cfg"], f["E"].data_ptr(), f["flat"].data_ptr(), s["ids"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(),
+                f["state"].data_ptr(), int(train), s["loss"].data_ptr(), f["dE"].data_ptr(), f["dW"].data_ptr(), s["ws"].data_ptr(),
+                s["nbytes"], stream)
+        if self._head is None:
+            L.check(L.load().bsarec_gru4rec_loss_grad(*call), "bsarec_gru4rec_loss_grad")
+        else:
+            L.check(L.load().bsarec_gru4rec_cand_loss_grad(*call, self._head), "bsarec_gru4rec_cand_loss_grad")
 
     def loss_and_grads(self, input_ids, answers, neg_answers, train: bool = True):
         """The BPR loss (0-d tensor) and {state_dict key: gradient} of one batch through bsarec_gru4rec_loss_grad, no update.
@@ -402,9 +469,12 @@ class GRU4RecModel(nn.Module):
     def _train_step(self, f, s):
         items, weights = self._adam_structs(f)
         stream = torch.cuda.current_stream(f["E"].device).cuda_stream
-        L.check(L.load().bsarec_gru4rec_train_step(s["cfg"], s["ids"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), items,
-                                                   weights, f["state"].data_ptr(), s["loss"].data_ptr(), s["ws"].data_ptr(),
-                                                   s["nbytes"], stream), "bsarec_gru4rec_train_step")
+        call = (s["cfg"], s["ids"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), items, weights, f["state"].data_ptr(),
+                s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream)
+        if self._head is None:
+            L.check(L.load().bsarec_gru4rec_train_step(*call), "bsarec_gru4rec_train_step")
+        else:
+            L.check(L.load().bsarec_gru4rec_cand_train_step(*call, self._head), "bsarec_gru4rec_cand_train_step")
 
     def train_step(self, input_ids, answers, neg_answers=None, same_target=None):
         """gru_step = "fused": one optimisation step in one C call -- the step counter, lookup + Philox dropout, the GRU stack,

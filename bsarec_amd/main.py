@@ -156,6 +156,14 @@ def parse_args(argv=None):
     p.add_argument("--gru_step", default=argparse.SUPPRESS, choices=("torch", "fused"),
                    help="GRU4Rec: step through autograd and torch.optim.Adam (default) or through the one-call HIP step "
                         "(lookup, Philox dropout, BPR head, item-table gradient and Adam in the library)")
+    p.add_argument("--gru_loss", default=argparse.SUPPRESS, choices=("bpr", "ce", "top1", "bpr_max"),
+                   help="GRU4Rec: pairwise BPR against one negative per row (default), or cross-entropy, TOP1 or BPR-max over "
+                        "candidates shared by the batch (--gru_negatives)")
+    p.add_argument("--gru_negatives", default=argparse.SUPPRESS, choices=("pair", "in_batch", "in_batch+sampled"),
+                   help="GRU4Rec: a row's negatives -- its own sampled negative (default, with --gru_loss bpr), the other rows' "
+                        "answers, or those and every row's sampled negative")
+    p.add_argument("--gru_bpreg", default=argparse.SUPPRESS, type=float,
+                   help="GRU4Rec: weight of BPR-max's score regulariser (default 1.0)")
     args = p.parse_args(argv)
     n = getattr(args, "eval_negatives", 0)
     if n > 0 and hasattr(args, "eval_full_rank"):

@@ -633,6 +633,56 @@ int bsarec_gru4rec_train_step(const bsarec_gru4rec_config_t *cfg, const int64_t 
                               const bsarec_adam_t *adam_weights, void *state, float *loss_out,
                               void *workspace, long workspace_bytes, void *stream);
 
+/* GRU4Rec heads over candidates shared by the batch (csrc/gru4rec_cand.h), beside the pairwise head above.  The candidates are
+ * c_0 .. c_C-1: candidates = 1: C = B, c_j = answers[j]; candidates = 2: C = 2 B, c_j = answers[j] for j < B and
+ * c_{B+k} = neg_answers[k].  With r_bj = s_b . E[c_j], row b's positive is column b and its negatives are
+ * M_b = { j : c_j != answers[b] }, m_b = |M_b| (every column holding the row's own target is left out; duplicates that are not the
+ * target each count).  loss = mean_b loss_b over all B rows; a row with m_b = 0 has loss 0 and gradient 0 exactly:
+ *   loss = 1 (cross-entropy)  loss_b = logsumexp_{j in {b} + M_b} r_bj - r_bb
+ *   loss = 2 (TOP1)           loss_b = (1 / m_b) sum_{M_b} [sigmoid(r_bj - r_bb) + sigmoid(r_bj^2)]
+ *   loss = 3 (BPR-max)        p = softmax of r_bj over M_b;  loss_b = -log(sum_j p_bj sigmoid(r_bb - r_bj) + 1e-10)
+ *                                                                     + bpreg sum_j p_bj r_bj^2
+ * Every softmax subtracts its maximum; the sigmoid is the pairwise head's (0 or 1 exactly for large arguments, never NaN).
+ *   bsarec_gru4rec_cand_head is the head alone: s [B, width], item_emb [item_size, width] -> the loss (one float), ds [B, width] =
+ * G . E_c and dEc [C, width] = G^T . s with G = d(loss) / d(r); dEc[j] is the gradient of item_emb's row c_j through column j (the
+ * caller adds rows of equal items).  bsarec_gru4rec_cand_loss_grad / _cand_train_step are bsarec_gru4rec_loss_grad /
+ * _train_step with this head in place of the pairwise rows: the same arguments, then the head; the item-table gradient takes
+ * T + C rows (the lookup rows, then dEc[j] into row c_j) through the same fixed-point accumulator, flush, closing block and Adam
+ * launches.
+ *   Launches, all on `stream`, one after the other: the scores R [B, C] in 64 x 64 tiles; one workgroup per row (the row's
+ * statistics, loss_b, G_b written over R_b); one grid that forms dEc and ds, each split over its summed dimension into
+ * nslab slabs (nslab = min(16, ceil(C / 64)), lowered while nslab (B + C) width would pass 2^26 floats: a function of the shape
+ * alone); with nslab > 1 one launch that adds the slabs in slab order; the head alone closes with the mean loss.  No floating-point atomics, no allocation, no host synchronisation: capturable, bit-deterministic, and independent of
+ * what the workspace holds on entry.
+ *   Workspace (host-only queries, no HIP call), in floats: R [B, C] (rounded up to 4) | nslab slabs [C, width] | nslab slabs
+ * [B, width] (both absent when nslab is 1); bsarec_gru4rec_cand_head_workspace_bytes: those, then loss rows [B, rounded up to 4];
+ * bsarec_gru4rec_cand_workspace_bytes: the workspace of bsarec_gru4rec_workspace_bytes, then those, then dEc [C, width].
+ *   Limits (else < 0 before any HIP call): those of bsarec_gru4rec_loss_grad / _train_step (the head alone: 1 <= batch <= 65536,
+ * 4 <= width <= 256, % 4 == 0, item_size >= 2); head non-null, loss in 1..3, candidates in 1..2, bpreg >= 0 (NaN refused);
+ * C <= BSAREC_GRU4REC_CAND_MAX; every pointer non-null (neg_answers too when candidates is 1), float arrays and the workspace
+ * 16-byte aligned, answers / neg_answers 8-byte, loss_out 4-byte; workspace_bytes at least the queried size.  answers and
+ * neg_answers inside [0, item_size) are the caller's contract (a value outside is never dereferenced: it is no column of any row,
+ * and a row whose answer is outside has loss 0).  Outputs may not alias inputs, each other or the workspace. */
+#define BSAREC_GRU4REC_CAND_MAX 8192
+typedef struct {
+    int loss;                          /* 1 cross-entropy, 2 TOP1, 3 BPR-max */
+    int candidates;                    /* 1 the batch's answers, 2 the answers and the negatives */
+    float bpreg;                       /* BPR-max: the weight of the score regulariser, >= 0; ignored by the others */
+} bsarec_gru4rec_head_t;
+long bsarec_gru4rec_cand_head_workspace_bytes(int batch, int width, const bsarec_gru4rec_head_t *head);
+int bsarec_gru4rec_cand_head(const float *s, const float *item_emb, const int64_t *answers, const int64_t *neg_answers,
+                             int batch, int width, int item_size, const bsarec_gru4rec_head_t *head, float *loss_out,
+                             float *ds, float *dEc, void *workspace, long workspace_bytes, void *stream);
+long bsarec_gru4rec_cand_workspace_bytes(const bsarec_gru4rec_config_t *cfg, const bsarec_gru4rec_head_t *head);
+int bsarec_gru4rec_cand_loss_grad(const bsarec_gru4rec_config_t *cfg, const float *item_emb, const float *weights,
+                                  const int64_t *ids, const int64_t *answers, const int64_t *neg_answers,
+                                  void *state, int train, float *loss_out, float *d_item_emb, float *dweights,
+                                  void *workspace, long workspace_bytes, void *stream, const bsarec_gru4rec_head_t *head);
+int bsarec_gru4rec_cand_train_step(const bsarec_gru4rec_config_t *cfg, const int64_t *ids, const int64_t *answers,
+                                   const int64_t *neg_answers, const bsarec_adam_t *adam_items,
+                                   const bsarec_adam_t *adam_weights, void *state, float *loss_out,
+                                   void *workspace, long workspace_bytes, void *stream, const bsarec_gru4rec_head_t *head);
+
 /* Stand-alone FrequencyLayer (src/model/bsarec.py:90-104) for per-op parity tests:
  * y = LN(Drop(low + beta^2 (x - low)) + x); backward given dy. */
 int bsarec_freq_layer_fwd(const float *x, const float *sqrt_beta, const float *ln_w, const float *ln_b,
