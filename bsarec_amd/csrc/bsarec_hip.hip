@@ -1514,7 +1514,7 @@ static int embed_bwd(bsarec_plan& p, const float* dY, hipStream_t s) {
     DISPATCH_LPR(d, {
         constexpr int CHUNK = SCATTER_FLOATS / (LPR * 4);
         const int sb = cdiv(T, CHUNK);
-        RET(launch_lds<embed_bwd_kernel<LPR>>(dim3(sb + L * p.pos_slices), dim3(ROW_THREADS), SCATTER_FLOATS * 8 + 2 * CHUNK * 4, s,
+        RET(launch_lds<embed_bwd_kernel<LPR>>(dim3(sb + L * p.pos_slices), dim3(ROW_THREADS), fix_scatter_lds_bytes(LPR), s,
                                               p.dz, p.ids32, B, L, d, p.lookup_acc, p.part_pos, sb));
     });
     return 0;
@@ -1805,7 +1805,7 @@ extern "C" int bsarec_topk_seen(float* scores, long ld, int B, int V, const int6
 // Argument conditions the catalogue entry points share: a row of d floats is read as float4s, d <= 256 bounds the LDS tiles;
 // E holds rows [col_base, col_base + V) of a catalogue whose ids fit an int.
 static bool row_dim_ok(int d) { return d >= 4 && d <= 256 && d % 4 == 0; }
-static bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+static bool aligned_to(const void* p, uintptr_t a) { return p && (uintptr_t)p % a == 0; }
 static bool col_range_ok(long col_base, int V) { return col_base >= 0 && col_base + V <= 0x7fffffffL; }
 
 // A score-tile kernel's h tile is rows x (d + 4) floats: up to 133 KB of the 160 KB LDS (128 rows, d = 256), past the 64 KB a
@@ -1835,7 +1835,7 @@ extern "C" int bsarec_sampled_rank(const float* h, long ldh, const float* item_e
     static_assert(BSAREC_NEG_MAX == NEG_MAX && BSAREC_NEG_MAX_DRAWS == NEG_MAX_DRAWS, "sampled_rank_kernel: the header's limits");
     if (!h || !item_emb || !users || !answers || !rank_out || (indptr && !indices)) return -10;
     if (B < 1 || V < 2 || !row_dim_ok(d) || ldh < d || n_neg < 1 || n_neg > BSAREC_NEG_MAX) return -10;
-    if (!aligned16(item_emb)) return -10;                        // float4 row loads
+    if (!aligned_to(item_emb, 16)) return -10;                        // float4 row loads
     hipLaunchKernelGGL(sampled_rank_kernel, dim3(B), dim3(ROW_THREADS), 0, (hipStream_t)stream, h, ldh, item_emb, V, d, users, answers,
                        indptr, indices, pop_cum, n_neg, (uint32_t)seed, (uint32_t)(seed >> 32), tag, rank_out, cand_out, score_out);
     return (int)hipGetLastError();
@@ -1878,7 +1878,7 @@ extern "C" int bsarec_topk_full_range(const float* h, long ldh, const float* ite
     if (!fr_shape(B, V, d, k, cand_cap, &f)) return -10;
     if (!col_range_ok(col_base, V)) return -10;
     if (!h || !item_emb || !workspace || !out_idx || ldh < d || (indptr && (!users || !indices))) return -10;
-    if (!aligned16(h) || !aligned16(item_emb) || !aligned16(workspace)) return -10;
+    if (!aligned_to(h, 16) || !aligned_to(item_emb, 16) || !aligned_to(workspace, 16)) return -10;
     if (workspace_bytes < bsarec_topk_full_workspace_bytes(B, V, d, k, cand_cap)) return -10;
     char* ws = (char*)workspace;
     unsigned long long* tau = (unsigned long long*)ws;           ws += fr_align((long)B * 8);
@@ -1917,7 +1917,7 @@ static int answer_rank_check(const float* h, long ldh, const float* E, int B, in
     if (B < 1 || V < 1 || !row_dim_ok(d) || ldh < d) return -10;
     if (!col_range_ok(col_base, V)) return -10;
     if (!h || !E || !answers || !out || (indptr && (!users || !indices))) return -10;
-    if (!aligned16(h) || !aligned16(E)) return -10;
+    if (!aligned_to(h, 16) || !aligned_to(E, 16)) return -10;
     return 0;
 }
 
@@ -1967,7 +1967,7 @@ static int info_nce_params(NceP& P, const float* z_i, long ld_i, const float* z_
     RET(info_nce_shape_check(B, d, sim));
     if (ld_i < d || ld_j < d || ld_i % 4 != 0 || ld_j % 4 != 0) return -10;
     if (!(inv_tau > 0.f) || !std::isfinite(inv_tau)) return -10;
-    if (!z_i || !z_j || !workspace || !aligned16(z_i) || !aligned16(z_j) || !aligned16(workspace)) return -10;
+    if (!z_i || !z_j || !workspace || !aligned_to(z_i, 16) || !aligned_to(z_j, 16) || !aligned_to(workspace, 16)) return -10;
     if (workspace_bytes < bsarec_info_nce_workspace_bytes(B, d, sim)) return -10;
     const long n = 2L * B;
     P.zi = z_i; P.zj = z_j; P.ldi = ld_i; P.ldj = ld_j;
@@ -1995,7 +1995,7 @@ extern "C" int bsarec_info_nce_bwd(const float* z_i, long ld_i, const float* z_j
                                    void* stream) {
     NceP P;
     RET(info_nce_params(P, z_i, ld_i, z_j, ld_j, B, d, inv_tau, sim, workspace, workspace_bytes));
-    if (!gout || !dz_i || !dz_j || !aligned16(dz_i) || !aligned16(dz_j)) return -10;
+    if (!gout || !dz_i || !dz_j || !aligned_to(dz_i, 16) || !aligned_to(dz_j, 16)) return -10;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(P.S, P.T);
     switch (cdiv(d, NCE_TILE)) {
@@ -2032,7 +2032,7 @@ static int ce_head_params(CeP& P, const float* h, long ldh, const float* item_em
     RET(ce_head_shape_check(B, V > 1 ? V : 1, d));
     if (ldh < d || ldh % 4 != 0) return -10;
     if (!h || !item_emb || !answers || !workspace) return -10;
-    if (!aligned16(h) || !aligned16(item_emb) || !aligned16(workspace)) return -10;
+    if (!aligned_to(h, 16) || !aligned_to(item_emb, 16) || !aligned_to(workspace, 16)) return -10;
     if (workspace_bytes < bsarec_ce_head_range_workspace_bytes(B, V, d)) return -10;
     P.h = h; P.ldh = ldh; P.E = item_emb; P.ans = answers;
     P.B = B; P.V = V; P.d = d; P.S = ce_splits(B, V); P.nblk = ce_nblk(V);
@@ -2066,7 +2066,7 @@ extern "C" int bsarec_ce_head_fwd(const float* h, long ldh, const float* item_em
 
 // d(h) of P's rows of E (the slabs in split order, times g / B) and dE of those rows, from the m and log l in the workspace
 static int ce_head_bwd_launch(const CeP& P, const float* gout, float* dh, float* d_item_emb, hipStream_t st) {
-    if (!gout || !dh || !d_item_emb || !aligned16(dh) || !aligned16(d_item_emb)) return -10;
+    if (!gout || !dh || !d_item_emb || !aligned_to(dh, 16) || !aligned_to(d_item_emb, 16)) return -10;
     RET(ce_head_attributes());
     const int ndc = ce_ndc(P.d), rows = 32 * ce_dh_rb(ndc);
     const dim3 grid(P.S, cdiv(P.B, rows)), wg(ROW_THREADS);
@@ -2115,7 +2115,7 @@ extern "C" int bsarec_ce_head_range_stats(const float* h, long ldh, const float*
 extern "C" int bsarec_ce_head_range_merge(const float* stats_all, int world, int Bg, void* workspace, long workspace_bytes,
                                           float* loss_rows, float* loss, void* stream) {
     if (world < 1 || world > 8 || Bg < 1 || Bg > 65536) return -10;
-    if (!stats_all || !workspace || !aligned16(workspace) || !loss_rows || !loss) return -10;
+    if (!stats_all || !workspace || !aligned_to(workspace, 16) || !loss_rows || !loss) return -10;
     if (workspace_bytes < 2L * Bg * (long)sizeof(float)) return -10;          // m[Bg] | logl[Bg]: the head of every layout
     float* w = (float*)workspace;
     hipLaunchKernelGGL(ce_merge_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, stats_all, world, Bg, w, w + Bg, loss_rows, loss);
@@ -2128,7 +2128,7 @@ extern "C" int bsarec_ce_head_range_bwd(const float* h, long ldh, const float* i
     CeP P;
     RET(ce_head_params(P, h, ldh, item_rows, Bg, Vs, col_base, item_size, d, answers, workspace, workspace_bytes));
     if (Vs == 0) {
-        if (!gout || !dh_part || !aligned16(dh_part)) return -10;
+        if (!gout || !dh_part || !aligned_to(dh_part, 16)) return -10;
         return (int)hipMemsetAsync(dh_part, 0, (size_t)Bg * d * sizeof(float), (hipStream_t)stream);
     }
     return ce_head_bwd_launch(P, gout, dh_part, dE_rows, (hipStream_t)stream);
@@ -2267,7 +2267,7 @@ static int gru_args(const bsarec_gru_config_t* cfg, const float* x, const float*
                     bool train) {
     RET(gru_check(cfg));
     if (!x || !weights || !workspace) return -10;
-    if (!aligned16(x) || !aligned16(weights) || !aligned16(workspace)) return -10;
+    if (!aligned_to(x, 16) || !aligned_to(weights, 16) || !aligned_to(workspace, 16)) return -10;
     if (workspace_bytes < gru_ws(*cfg, train).total * (long)sizeof(float)) return -10;
     return 0;
 }
@@ -2275,7 +2275,7 @@ static int gru_args(const bsarec_gru_config_t* cfg, const float* x, const float*
 extern "C" int bsarec_gru_fwd(const bsarec_gru_config_t* cfg, const float* x, const float* weights, int train, int last_only,
                               float* out, void* workspace, long workspace_bytes, void* stream) {
     RET(gru_args(cfg, x, weights, workspace, workspace_bytes, train != 0));
-    if (!out || !aligned16(out)) return -10;
+    if (!out || !aligned_to(out, 16)) return -10;
     const bsarec_gru_config_t& c = *cfg;
     const int B = c.batch, L = c.seq_len, I = c.input_size, H = c.hidden_size, N = c.num_layers, O = c.out_size;
     const long T = (long)B * L;
@@ -2310,7 +2310,7 @@ extern "C" int bsarec_gru_fwd(const bsarec_gru_config_t* cfg, const float* x, co
 extern "C" int bsarec_gru_bwd(const bsarec_gru_config_t* cfg, const float* x, const float* weights, int last_only, const float* dout,
                               void* workspace, long workspace_bytes, float* dx, float* dweights, void* stream) {
     RET(gru_args(cfg, x, weights, workspace, workspace_bytes, true));
-    if (!dout || !dx || !dweights || !aligned16(dout) || !aligned16(dx) || !aligned16(dweights)) return -10;
+    if (!dout || !dx || !dweights || !aligned_to(dout, 16) || !aligned_to(dx, 16) || !aligned_to(dweights, 16)) return -10;
     const bsarec_gru_config_t& c = *cfg;
     const int B = c.batch, L = c.seq_len, I = c.input_size, H = c.hidden_size, N = c.num_layers, O = c.out_size;
     const long T = (long)B * L;
@@ -2405,8 +2405,6 @@ extern "C" long bsarec_gru4rec_workspace_bytes(const bsarec_gru4rec_config_t* cf
     if (gru4rec_check(cfg)) return -10;
     return gru4rec_ws(*cfg).total * (long)sizeof(float);
 }
-
-static bool aligned_to(const void* p, uintptr_t a) { return p && (uintptr_t)p % a == 0; }
 
 static int gru4rec_args(const bsarec_gru4rec_config_t* cfg, const float* item_emb, const float* weights, const int64_t* ids,
                         const int64_t* answers, const int64_t* neg_answers, const void* state, const float* loss_out,
@@ -2519,20 +2517,16 @@ static int gru4rec_run(const bsarec_gru4rec_config_t& c, const float* E, const f
     }
     RET(bsarec_gru_bwd(&c.gru, w + ws.x, weights, 1, w + ws.ds, w + ws.gru, ws.gru_bytes, w + ws.dx, dweights, s));
 
-    if (head) {
-        Gru4RecCandGradP pg;
-        memset(&pg, 0, sizeof(pg));
-        pg.dx = w + ws.dx; pg.ids = ids; pg.dEc = w + dEc; pg.T = T; pg.d = d; pg.drop = drop; pg.dA = acc;
-        pg.head.ans = answers; pg.head.neg = neg_answers; pg.head.B = B; pg.head.C = g.C; pg.head.V = V;
-        DISPATCH_LPR(d, hipLaunchKernelGGL(g4c_item_grad_kernel<LPR>, dim3(cdiv(T + g.C, SCATTER_FLOATS / (4 * LPR))),
-                                           dim3(ROW_THREADS), 0, s, pg));
-    } else {
-        Gru4RecGradP pg;
-        pg.dx = w + ws.dx; pg.ids = ids; pg.s = w + ws.s; pg.c = w + ws.c; pg.ans = answers; pg.neg = neg_answers;
-        pg.T = T; pg.B = B; pg.d = d; pg.V = V; pg.drop = drop; pg.dA = acc;
-        DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_item_grad_kernel<LPR>, dim3(cdiv(T + 2L * B, SCATTER_FLOATS / (4 * LPR))),
-                                           dim3(ROW_THREADS), 0, s, pg));
-    }
+    Gru4RecGradP pg;                                   // the token rows, then the head's: 2 B pairwise rows or C candidate rows
+    pg.dx = w + ws.dx; pg.ids = ids; pg.ans = answers; pg.neg = neg_answers;
+    pg.T = T; pg.B = B; pg.C = g.C; pg.d = d; pg.V = V; pg.drop = drop; pg.dA = acc;
+    pg.head_rows = head ? w + dEc : w + ws.s; pg.c = w + ws.c;
+    const long n_head = head ? g.C : 2L * B;
+    DISPATCH_LPR(d, {
+        const dim3 grid(cdiv(T + n_head, SCATTER_FLOATS / (4 * LPR)));
+        if (head) hipLaunchKernelGGL(g4c_item_grad_kernel<LPR>, grid, dim3(ROW_THREADS), 0, s, pg);
+        else hipLaunchKernelGGL(gru4rec_item_grad_kernel<LPR>, grid, dim3(ROW_THREADS), 0, s, pg);
+    });
 
     LookupAcc la;
     memset(&la, 0, sizeof(la));

@@ -369,7 +369,8 @@ __device__ __forceinline__ void dw_wg_body(const DwProblem& Q, int m0, int n0, i
 // tk.state != null: one extra (last) workgroup closes the optimisation step here -- mean loss, Adam's t and bias
 // corrections, next dropout step, batch cursor (kernels.h, tick_body) -- so that the step's final kernel can reduce AND
 // update with a read-only state.  Every reader of the dropout step / cursor of this step has run before this launch.
-// sc.nblocks > 0: the lookup-path scatter of the item-table gradient (embed_scatter_block, 64-token chunks) rides here
+// sc.nblocks > 0: the lookup-path scatter of the item-table gradient (embed_scatter_block: fix_scatter_block over
+// the token rows of dz, 64-token chunks at d = 64, this kernel's reduction scratch lent as its LDS) rides here
 // too, as the workgroups after the weight-gradient ones: light, latency-bound blocks that fill the slots the big
 // workgroups leave free instead of a launch of their own (11.6 us + a launch boundary at C1).
 struct ScatterP { const float* de; const int* ids32; int T; unsigned long long* dA; int nblocks; };
@@ -379,7 +380,7 @@ struct ScatterP { const float* de; const int* ids32; int T; unsigned long long* 
 __global__ void __launch_bounds__(256)
 dw_direct_kernel(const DwP G, const TickP tk, const ScatterP sc) {
     __shared__ __attribute__((aligned(16))) float red[4][66][64];      // accumulators (64) + bias sums (2) of the 4 waves
-    static_assert(sizeof(red) >= (2 * SCATTER_FLOATS + 2 * (SCATTER_FLOATS / 64)) * 4, "scatter scratch fits the reduction scratch");
+    static_assert(sizeof(red) >= fix_scatter_lds_bytes(16), "scatter scratch fits the reduction scratch");
     DW_STAMP_SCOPE;
     {
         const int nmain = 8 * ((G.nslab + 7) >> 3) * (G.nunits - G.nsmall) + G.nsmall * G.small_slabs;

@@ -8,11 +8,11 @@
 //   g4c_bwd_kernel        two roles in one grid: dEc [C][d] = G^T . s and ds [B][d] = G . E_c, each split over its summed dimension
 //                         into nslab slabs (a function of the shape alone)
 //   g4c_slab_sum_kernel   nslab > 1: the slabs added in slab order
-//   g4c_item_grad_kernel  gru4rec_item_grad_kernel over T + C rows: row r < T adds dx[r, :] * m to row ids[r], row T + j adds
-//                         dEc[j, :] to row c_j
-// No floating-point atomics: every float sum has one order; the item-table rows are summed in 64-bit fixed point as in
-// gru4rec_step.h.  An id outside [0, V) is never dereferenced: such a candidate is no column of any row (G = 0), and a row whose
-// answer is outside has loss 0 and gradient 0.  The restatement in numpy is tests/gru4rec_cand_ref.py.
+//   g4c_item_grad_kernel  fix_scatter_block (kernels.h) over T + C rows: row r < T adds dx[r, :] * m to row ids[r] (the token rows
+//                         of gru4rec_item_grad_kernel, gru4rec_token_row), row T + j adds dEc[j, :] to row c_j
+// No floating-point atomics: every float sum has one order; the item-table rows are summed in 64-bit fixed point as
+// gru4rec_step.h describes.  An id outside [0, V) is never dereferenced: such a candidate is no column of any row (G = 0), and a
+// row whose answer is outside has loss 0 and gradient 0.  The restatement in numpy is tests/gru4rec_cand_ref.py.
 #pragma once
 #include "gru4rec_step.h"
 #include "sampled_softmax.h"
@@ -35,10 +35,10 @@ struct Gru4RecCandP {
     int nslab, chunkB, chunkC, tilesA;
 };
 
-// candidate j's item, -1 outside [0, V)
-__device__ __forceinline__ int g4c_cand(const Gru4RecCandP& P, int j) {
-    const long id = j < P.B ? P.ans[j] : P.neg[j - P.B];
-    return id >= 0 && id < P.V ? (int)id : -1;
+// candidate j's item, -1 outside [0, V); P: Gru4RecCandP, or the Gru4RecGradP of g4c_item_grad_kernel
+template <class Params>
+__device__ __forceinline__ int g4c_cand(const Params& P, int j) {
+    return gru4rec_row_id(j < P.B ? P.ans[j] : P.neg[j - P.B], P.V);
 }
 
 // grid (ceil(C / 64), ceil(B / 64)): rows = batch rows, columns = candidates
@@ -247,88 +247,14 @@ __global__ void __launch_bounds__(ROW_THREADS) g4c_slab_sum_kernel(const float* 
     st4((e ? dEc : ds) + at, v);
 }
 
-struct Gru4RecCandGradP {
-    const float* dx; const int64_t* ids;                 // [T, d], [T]
-    const float* dEc;                                    // [C, d]
-    Gru4RecCandP head;                                   // the candidates: ans, neg, B, C, V
-    long T; int d;
-    DropP drop;
-    unsigned long long* dA;                              // [V][d] fixed point, zero on entry
-};
-
-// gru4rec_item_grad_kernel with the head's rows read from dEc: grid ceil((T + C) / CHUNK), CHUNK = SCATTER_FLOATS / (4 LPR)
+// gru4rec_item_grad_kernel with the head's rows read from dEc (Gru4RecGradP.head_rows): grid ceil((T + C) / CHUNK), CHUNK =
+// SCATTER_FLOATS / (4 LPR)
 template <int LPR>
-__global__ void __launch_bounds__(ROW_THREADS) g4c_item_grad_kernel(const Gru4RecCandGradP P) {
-    constexpr int RPP = ROW_THREADS / LPR, W = LPR * 4, CHUNK = SCATTER_FLOATS / W, NP = CHUNK / RPP;
-    __shared__ __attribute__((aligned(16))) unsigned long long acc[SCATTER_FLOATS];       // [CHUNK][W]
-    __shared__ __attribute__((aligned(16))) int sid[CHUNK];
-    __shared__ int lead[CHUNK];
-    const int lr = threadIdx.x / LPR, lc = (threadIdx.x % LPR) << 2, d = P.d, V = P.head.V;
-    const bool colok = lc < d;
-    const long T = P.T, R = T + P.head.C;
-    const long r0 = (long)blockIdx.x * CHUNK;
-    const int n = (int)(R - r0 < CHUNK ? R - r0 : CHUNK);
+__global__ void __launch_bounds__(ROW_THREADS) g4c_item_grad_kernel(const Gru4RecGradP P) {
+    __shared__ __attribute__((aligned(16))) float lds[fix_scatter_lds_bytes(LPR) / 4];
+    const long T = P.T;
     const DropSeed sd = drop_seed(P.drop);
-    for (int i = threadIdx.x; i < CHUNK; i += ROW_THREADS) {
-        long id = -1;                                    // no row: never equal to an id, never added
-        if (i < n) {
-            const long r = r0 + i;
-            id = r < T ? P.ids[r] : (long)g4c_cand(P.head, (int)(r - T));
-            if (id < 0 || id >= V) id = -1;
-        }
-        sid[i] = (int)id;
-    }
-    for (int i = threadIdx.x; i < SCATTER_FLOATS; i += ROW_THREADS) acc[i] = 0ull;
-    __syncthreads();
-    f32x4 g[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const int j = lr + p * RPP;
-        g[p] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (colok && j < n && sid[j] >= 0) {
-            const long r = r0 + j;
-            if (r < T) {
-                const long e = r * d + lc;
-                g[p] = ld4(P.dx + e) * drop_mult4(P.drop, sd, (uint64_t)e >> 2);
-            } else {
-                g[p] = ld4(P.dEc + (r - T) * d + lc);
-            }
-        }
-    }
-    for (int j = threadIdx.x; j < CHUNK; j += ROW_THREADS) {          // first occurrence of sid[j] in the chunk: its leader
-        const int id = sid[j];
-        int l = j;
-        for (int i = CHUNK - 4; i >= 0; i -= 4) {
-            const int4 q = *reinterpret_cast<const int4*>(sid + i);
-            if (q.w == id && i + 3 < l) l = i + 3;
-            if (q.z == id && i + 2 < l) l = i + 2;
-            if (q.y == id && i + 1 < l) l = i + 1;
-            if (q.x == id && i < l) l = i;
-        }
-        lead[j] = l;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const int j = lr + p * RPP;
-        if (colok && j < n && sid[j] >= 0) {
-            unsigned long long* a = acc + lead[j] * W + lc;
-            atomicAdd(a + 0, lookup_fix(g[p].x)); atomicAdd(a + 1, lookup_fix(g[p].y));
-            atomicAdd(a + 2, lookup_fix(g[p].z)); atomicAdd(a + 3, lookup_fix(g[p].w));
-        }
-    }
-    __syncthreads();
-    // one leader row per wave instruction, lane = column: a global 64-bit add covers contiguous bytes of one row
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    constexpr int PW = CHUNK / (ROW_THREADS / 64);       // rows owned by one wave (<= 16)
-    const int j0 = wv * PW, myj = j0 + lane;
-    const bool is_leader = lane < PW && myj < n && sid[myj] >= 0 && lead[myj] == myj;
-    unsigned long long todo = __ballot(is_leader);
-    while (todo) {
-        const int j = j0 + __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const long row = (long)sid[j] * d;
-        for (int c0 = 0; c0 < d; c0 += 64)
-            if (c0 + lane < d) atomicAdd(P.dA + row + c0 + lane, acc[j * W + c0 + lane]);
-    }
+    fix_scatter_block<LPR>(T + P.C, P.d, P.dA, blockIdx.x, lds,
+        [&](long r) { return r < T ? gru4rec_row_id(P.ids[r], P.V) : g4c_cand(P, (int)(r - T)); },
+        [&](long r, int lc) { return r < T ? gru4rec_token_row(P, sd, r, lc) : ld4(P.head_rows + (r - T) * P.d + lc); });
 }

@@ -13,12 +13,12 @@
 //   gru4rec_flush_kernel      accumulator -> EVERY float of d_item_emb (zero where no row was touched, LookupAcc.dense_zero) and, in
 //                             one closing block, the mean loss in a fixed order and -- in a training step -- Adam's t (tick_body).
 //
-// The gradient rows are summed as the BSARec lookup path sums them (kernels.h: lookup_fix, embed_scatter_block, lookup_flush):
-// 64-bit fixed point in 2^-40 units, an addend clamped to |x| <= 2^22, so |sum| < 2^22 after the clamp is exact -- the same range as
-// the BSARec lookup path.  Duplicates of a chunk are folded in LDS and one global integer row add goes out per distinct id and
-// chunk; integer adds commute, so dE has the same bits on every run whatever order tokens and chunks arrive in.  x and -x round to
-// opposite integers: a row with a_b == n_b contributes exactly zero.  embed_scatter_block itself skips id 0 (BSARec's padding_idx)
-// and reads 32-bit ids of one source; the block below is its body without the skip, over three row sources.
+// The gradient rows are summed by the code that sums the BSARec lookup path (kernels.h: lookup_fix, fix_scatter_block,
+// lookup_flush): 64-bit fixed point in 2^-40 units, an addend clamped to |x| <= 2^22, so |sum| < 2^22 after the clamp is exact.
+// Duplicates of a chunk are folded in LDS and one global integer row add goes out per distinct id and chunk; integer adds commute,
+// so dE has the same bits on every run whatever order tokens and chunks arrive in.  x and -x round to opposite integers: a row with
+// a_b == n_b contributes exactly zero.  gru4rec_item_grad_kernel only tells fix_scatter_block the id and the addend of row r, over
+// its three row sources; BSARec's caller maps id 0 (its padding_idx) to "no row", this one maps ids outside [0, V) to it.
 //
 // ids, answers and negatives inside [0, V) are the caller's contract; a value outside is never dereferenced (its x row is zero, its
 // gradient row is dropped).
@@ -94,93 +94,42 @@ __global__ void __launch_bounds__(ROW_THREADS) gru4rec_bpr_kernel(const Gru4RecB
     }
 }
 
+// The item-table gradient of a step under either head.  Rows [0, T) are the token rows; behind them stand the head's rows:
+//   gru4rec_item_grad_kernel           2 B rows: T + b adds c[b] head_rows[b, :] to ans[b], T + B + b adds its negative to neg[b];
+//                                      head_rows = s [B, d]
+//   g4c_item_grad_kernel (gru4rec_cand.h)  C rows: T + j adds head_rows[j, :] to candidate j; head_rows = dEc [C, d], c is not read
 struct Gru4RecGradP {
     const float* dx; const int64_t* ids;                 // [T, d], [T]
-    const float* s; const float* c;                      // [B, d], [B]
+    const float* head_rows; const float* c;
     const int64_t* ans; const int64_t* neg;              // [B]
-    long T; int B, d, V;
+    long T; int B, C, d, V;
     DropP drop;
     unsigned long long* dA;                              // [V][d] fixed point, zero on entry
 };
 
+// the scatter's id of an item: an id outside [0, V) is no row
+__device__ __forceinline__ int gru4rec_row_id(long id, int V) { return id >= 0 && id < V ? (int)id : -1; }
+// token row r < T of either kernel: dx[r, lc .. lc + 3] times the regenerated dropout multiplier, into ids[r]
+__device__ __forceinline__ f32x4 gru4rec_token_row(const Gru4RecGradP& P, const DropSeed& sd, long r, int lc) {
+    const long e = r * P.d + lc;
+    return ld4(P.dx + e) * drop_mult4(P.drop, sd, (uint64_t)e >> 2);
+}
+
 // grid ceil((T + 2 B) / CHUNK), CHUNK = SCATTER_FLOATS / (4 LPR) rows per block
 template <int LPR>
 __global__ void __launch_bounds__(ROW_THREADS) gru4rec_item_grad_kernel(const Gru4RecGradP P) {
-    constexpr int RPP = ROW_THREADS / LPR, W = LPR * 4, CHUNK = SCATTER_FLOATS / W, NP = CHUNK / RPP;
-    __shared__ __attribute__((aligned(16))) unsigned long long acc[SCATTER_FLOATS];       // [CHUNK][W]
-    __shared__ __attribute__((aligned(16))) int sid[CHUNK];
-    __shared__ int lead[CHUNK];
-    const int lr = threadIdx.x / LPR, lc = (threadIdx.x % LPR) << 2, d = P.d;
-    const bool colok = lc < d;
-    const long T = P.T, R = T + 2L * P.B;
-    const long r0 = (long)blockIdx.x * CHUNK;
-    const int n = (int)(R - r0 < CHUNK ? R - r0 : CHUNK);
+    __shared__ __attribute__((aligned(16))) float lds[fix_scatter_lds_bytes(LPR) / 4];
+    const long T = P.T, B = P.B;
     const DropSeed sd = drop_seed(P.drop);
-    for (int i = threadIdx.x; i < CHUNK; i += ROW_THREADS) {
-        long id = -1;                                    // no row: never equal to an id, never added
-        if (i < n) {
-            const long r = r0 + i;
-            id = r < T ? P.ids[r] : (r < T + P.B ? P.ans[r - T] : P.neg[r - T - P.B]);
-            if (id < 0 || id >= P.V) id = -1;
-        }
-        sid[i] = (int)id;
-    }
-    for (int i = threadIdx.x; i < SCATTER_FLOATS; i += ROW_THREADS) acc[i] = 0ull;
-    __syncthreads();
-    f32x4 g[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const int j = lr + p * RPP;
-        g[p] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (colok && j < n && sid[j] >= 0) {
-            const long r = r0 + j;
-            if (r < T) {
-                const long e = r * d + lc;
-                g[p] = ld4(P.dx + e) * drop_mult4(P.drop, sd, (uint64_t)e >> 2);
-            } else {
-                const bool isneg = r >= T + P.B;
-                const long b = r - T - (isneg ? P.B : 0);
-                const f32x4 v = P.c[b] * ld4(P.s + b * d + lc);
-                g[p] = isneg ? -v : v;
-            }
-        }
-    }
-    for (int j = threadIdx.x; j < CHUNK; j += ROW_THREADS) {          // first occurrence of sid[j] in the chunk: its leader
-        const int id = sid[j];
-        int l = j;
-        for (int i = CHUNK - 4; i >= 0; i -= 4) {
-            const int4 q = *reinterpret_cast<const int4*>(sid + i);
-            if (q.w == id && i + 3 < l) l = i + 3;
-            if (q.z == id && i + 2 < l) l = i + 2;
-            if (q.y == id && i + 1 < l) l = i + 1;
-            if (q.x == id && i < l) l = i;
-        }
-        lead[j] = l;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const int j = lr + p * RPP;
-        if (colok && j < n && sid[j] >= 0) {
-            unsigned long long* a = acc + lead[j] * W + lc;
-            atomicAdd(a + 0, lookup_fix(g[p].x)); atomicAdd(a + 1, lookup_fix(g[p].y));
-            atomicAdd(a + 2, lookup_fix(g[p].z)); atomicAdd(a + 3, lookup_fix(g[p].w));
-        }
-    }
-    __syncthreads();
-    // one leader row per wave instruction, lane = column: a global 64-bit add covers contiguous bytes of one row
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    constexpr int PW = CHUNK / (ROW_THREADS / 64);       // rows owned by one wave (<= 16)
-    const int j0 = wv * PW, myj = j0 + lane;
-    const bool is_leader = lane < PW && myj < n && sid[myj] >= 0 && lead[myj] == myj;
-    unsigned long long todo = __ballot(is_leader);
-    while (todo) {
-        const int j = j0 + __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const long row = (long)sid[j] * d;
-        for (int c0 = 0; c0 < d; c0 += 64)
-            if (c0 + lane < d) atomicAdd(P.dA + row + c0 + lane, acc[j * W + c0 + lane]);
-    }
+    fix_scatter_block<LPR>(T + 2 * B, P.d, P.dA, blockIdx.x, lds,
+        [&](long r) { return gru4rec_row_id(r < T ? P.ids[r] : (r < T + B ? P.ans[r - T] : P.neg[r - T - B]), P.V); },
+        [&](long r, int lc) {
+            if (r < T) return gru4rec_token_row(P, sd, r, lc);
+            const bool isneg = r >= T + B;
+            const long b = r - T - (isneg ? B : 0);
+            const f32x4 v = P.c[b] * ld4(P.head_rows + b * P.d + lc);
+            return isneg ? -v : v;
+        });
 }
 
 // blocks [0, la.nblocks): accumulator -> la.dst, every float written; the block behind them closes the step

@@ -500,7 +500,9 @@ dlast_kernel(const float* __restrict__ slabs, int nsplit, long slab_stride, int 
 // 64-bit fixed point (2^-40 units) with integer atomics -- LDS inside a chunk, then one global row add per chunk leader
 // into the plan's accumulator -- so the sum does not depend on the order in which tokens and chunks arrive: a step gives
 // the same gradient bit for bit on every run.  The final reduction kernel of the backward adds the accumulator once onto
-// the dense logits-path dE and zeroes it (LookupAcc).
+// the dense logits-path dE and zeroes it (LookupAcc).  The scatter has ONE body, fix_scatter_block: BSARec's token rows
+// (embed_scatter_block, in embed_bwd_kernel and at d = 64 inside dw_direct_kernel) and the T + 2 B / T + C rows of the GRU4Rec
+// steps (gru4rec_step.h, gru4rec_cand.h) only tell it which id and which addend belong to a row.
 // =============================================================================================
 #define LOOKUP_FIX_ONE 0x1p40f         // fixed-point unit: |sum| < 2^23 representable, resolution 2^-40
 __device__ __forceinline__ unsigned long long lookup_fix(float x) {
@@ -538,73 +540,85 @@ __device__ __forceinline__ void lookup_flush(const LookupAcc& la, long first, lo
 #define SCATTER_FLOATS 4096           // LDS row accumulators per block: chunk = 4096 / (4*LPR) tokens (64 at d = 64:
                                       // 200 blocks at C1; 128-token chunks measured 18.2 us, 64- and 32-token chunks 11.6 us)
 #endif
-// One scatter block: CHUNK tokens starting at chunk * CHUNK into the fixed-point accumulator dA ([V][d]).
-// esm: SCATTER_FLOATS 64-bit words + 2 * CHUNK ints of LDS.
-template <int LPR>
-__device__ __forceinline__ void embed_scatter_block(const float* __restrict__ de, const int* __restrict__ ids32, int T, int d,
-                                                    unsigned long long* __restrict__ dA, int chunk, float* __restrict__ esm) {
+// LDS of one scatter block: SCATTER_FLOATS 64-bit row accumulators, then the ids and the leaders of its CHUNK rows
+constexpr int fix_scatter_lds_bytes(int lpr) { return SCATTER_FLOATS * 8 + 2 * (SCATTER_FLOATS / (4 * lpr)) * 4; }
+// One scatter block, the only body of the fixed-point row scatter: rows [chunk * CHUNK, min(R, (chunk + 1) * CHUNK)) of R
+// gradient rows into the accumulator dA ([V][d]).  The callers differ only in which id and which addend belong to row r:
+//   id_of(r)      -> int item id of row r, < 0: the row adds nothing and is never dereferenced
+//   row_of(r, lc) -> f32x4, the addend of row r at columns lc .. lc + 3 (called only where id_of(r) >= 0 and lc < d)
+// lds: fix_scatter_lds_bytes(LPR) bytes, 16-byte aligned.
+template <int LPR, class IdOf, class RowOf>
+__device__ __forceinline__ void fix_scatter_block(long R, int d, unsigned long long* __restrict__ dA, long chunk,
+                                                  float* __restrict__ lds, IdOf id_of, RowOf row_of) {
     constexpr int RPP = ROW_THREADS / LPR, W = LPR * 4, CHUNK = SCATTER_FLOATS / W;
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(esm);     // [CHUNK][W]
-    int* sid = reinterpret_cast<int*>(esm + 2 * SCATTER_FLOATS);  // [CHUNK]
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(lds);     // [CHUNK][W]
+    int* sid = reinterpret_cast<int*>(lds + 2 * SCATTER_FLOATS);  // [CHUNK]
     int* lead = sid + CHUNK;                                      // [CHUNK]
     const int lr = threadIdx.x / LPR, lc = (threadIdx.x % LPR) << 2;
     const bool colok = lc < d;
-    {
-        // Popular items (Zipf) would serialise hundreds of global float atomics on one row.  Each block
-        // owns CHUNK tokens: every token finds the first occurrence of its id in the chunk (its leader),
-        // all rows are folded into the leader's LDS row with LDS atomics, and each leader then issues ONE
-        // global atomic row add (>= 64 B contiguous per row).
-        const int t0 = chunk * CHUNK;
-        const int n = min(CHUNK, T - t0);
-        for (int i = threadIdx.x; i < CHUNK; i += ROW_THREADS) sid[i] = i < n ? ids32[t0 + i] : 0;
-        for (int i = threadIdx.x; i < SCATTER_FLOATS; i += ROW_THREADS) acc[i] = 0ull;
-        __syncthreads();
-        constexpr int NP = CHUNK / RPP;                   // rows per thread group, loads issued together
-        f32x4 g[NP];
+    // Popular items (Zipf) would serialise hundreds of global float atomics on one row.  Each block
+    // owns CHUNK rows: every row finds the first occurrence of its id in the chunk (its leader),
+    // all rows are folded into the leader's LDS row with LDS atomics, and each leader then issues ONE
+    // global atomic row add (>= 64 B contiguous per row).
+    const long r0 = chunk * CHUNK;
+    const int n = (int)(R - r0 < CHUNK ? R - r0 : CHUNK);
+    for (int i = threadIdx.x; i < CHUNK; i += ROW_THREADS) sid[i] = i < n ? id_of(r0 + i) : -1;   // no row: never added
+    for (int i = threadIdx.x; i < SCATTER_FLOATS; i += ROW_THREADS) acc[i] = 0ull;
+    __syncthreads();
+    constexpr int NP = CHUNK / RPP;                   // rows per thread group, loads issued together
+    f32x4 g[NP];
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const int j = lr + p * RPP;
-            g[p] = f32x4{0, 0, 0, 0};
-            if (colok && j < n && sid[j] != 0) g[p] = ld4(de + (long)(t0 + j) * d + lc);
+    for (int p = 0; p < NP; ++p) {
+        const int j = lr + p * RPP;
+        g[p] = f32x4{0, 0, 0, 0};
+        if (colok && j < n && sid[j] >= 0) g[p] = row_of(r0 + j, lc);
+    }
+    for (int j = threadIdx.x; j < CHUNK; j += ROW_THREADS) {      // first occurrence of sid[j]: 4 ids per LDS read,
+        const int id = sid[j];                                    // no early exit (independent, pipelined reads)
+        int l = j;
+        for (int i = CHUNK - 4; i >= 0; i -= 4) {
+            const int4 q = *reinterpret_cast<const int4*>(sid + i);
+            if (q.w == id && i + 3 < l) l = i + 3;
+            if (q.z == id && i + 2 < l) l = i + 2;
+            if (q.y == id && i + 1 < l) l = i + 1;
+            if (q.x == id && i < l) l = i;
         }
-        for (int j = threadIdx.x; j < CHUNK; j += ROW_THREADS) {      // first occurrence of sid[j]: 4 ids per LDS read,
-            const int id = sid[j];                                    // no early exit (independent, pipelined reads)
-            int l = j;
-            for (int i = CHUNK - 4; i >= 0; i -= 4) {
-                const int4 q = *reinterpret_cast<const int4*>(sid + i);
-                if (q.w == id && i + 3 < l) l = i + 3;
-                if (q.z == id && i + 2 < l) l = i + 2;
-                if (q.y == id && i + 1 < l) l = i + 1;
-                if (q.x == id && i < l) l = i;
-            }
-            lead[j] = l;
-        }
-        __syncthreads();
+        lead[j] = l;
+    }
+    __syncthreads();
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const int j = lr + p * RPP;
-            if (colok && j < n && sid[j] != 0) {          // padding_idx = 0: no lookup gradient for id 0
-                unsigned long long* a = acc + lead[j] * W + lc;
-                atomicAdd(a + 0, lookup_fix(g[p].x)); atomicAdd(a + 1, lookup_fix(g[p].y));
-                atomicAdd(a + 2, lookup_fix(g[p].z)); atomicAdd(a + 3, lookup_fix(g[p].w));
-            }
-        }
-        __syncthreads();
-        // one leader row per wave-instruction: lane = column, so every global 64-bit atomic add covers 512 contiguous
-        // bytes (contiguous rows: 4-byte pieces at a 16-byte stride ran ~17x slower as float atomics)
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        constexpr int PW = CHUNK / (ROW_THREADS / 64);      // tokens owned by one wave (<= 64)
-        const int j0 = wv * PW, myj = j0 + lane;
-        const bool is_leader = lane < PW && myj < n && sid[myj] != 0 && lead[myj] == myj;
-        unsigned long long todo = __ballot(is_leader);      // wave-uniform work list: no per-token LDS round trips
-        while (todo) {
-            const int j = j0 + __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const long row = (long)sid[j] * d;
-            for (int c0 = 0; c0 < d; c0 += 64)
-                if (c0 + lane < d) atomicAdd(dA + row + c0 + lane, acc[j * W + c0 + lane]);
+    for (int p = 0; p < NP; ++p) {
+        const int j = lr + p * RPP;
+        if (colok && j < n && sid[j] >= 0) {
+            unsigned long long* a = acc + lead[j] * W + lc;
+            atomicAdd(a + 0, lookup_fix(g[p].x)); atomicAdd(a + 1, lookup_fix(g[p].y));
+            atomicAdd(a + 2, lookup_fix(g[p].z)); atomicAdd(a + 3, lookup_fix(g[p].w));
         }
     }
+    __syncthreads();
+    // one leader row per wave-instruction: lane = column, so every global 64-bit atomic add covers 512 contiguous
+    // bytes (contiguous rows: 4-byte pieces at a 16-byte stride ran ~17x slower as float atomics)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    constexpr int PW = CHUNK / (ROW_THREADS / 64);      // rows owned by one wave (<= 16)
+    const int j0 = wv * PW, myj = j0 + lane;
+    const bool is_leader = lane < PW && myj < n && sid[myj] >= 0 && lead[myj] == myj;
+    unsigned long long todo = __ballot(is_leader);      // wave-uniform work list: no per-row LDS round trips
+    while (todo) {
+        const int j = j0 + __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const long row = (long)sid[j] * d;
+        for (int c0 = 0; c0 < d; c0 += 64)
+            if (c0 + lane < d) atomicAdd(dA + row + c0 + lane, acc[j * W + c0 + lane]);
+    }
+}
+// BSARec's rows: the T token rows of de into ids32; padding_idx = 0: no lookup gradient for id 0.  Ids are not checked against
+// V; a negative id, invalid input, is the core's "no row" and is dropped
+template <int LPR>
+__device__ __forceinline__ void embed_scatter_block(const float* __restrict__ de, const int* __restrict__ ids32, int T, int d,
+                                                    unsigned long long* __restrict__ dA, int chunk, float* __restrict__ lds) {
+    fix_scatter_block<LPR>(T, d, dA, chunk, lds,
+        [&](long r) { const int id = ids32[r]; return id != 0 ? id : -1; },
+        [&](long r, int lc) { return ld4(de + r * d + lc); });
 }
 
 template <int LPR>
