@@ -152,6 +152,11 @@ class Gru4RecHead(C.Structure):
     _fields_ = [("loss", C.c_int), ("candidates", C.c_int), ("bpreg", C.c_float)]
 
 
+class CaserConfig(C.Structure):
+    """bsarec_caser_config_t"""
+    _fields_ = [("batch", C.c_int), ("seq_len", C.c_int), ("width", C.c_int), ("n_h", C.c_int), ("n_v", C.c_int)]
+
+
 GRU4REC_CAND_MAX = 8192                          # BSAREC_GRU4REC_CAND_MAX: the most candidate columns of a GRU4Rec head
 GRU4REC_LOSSES = {"ce": 1, "top1": 2, "bpr_max": 3}                 # bsarec_gru4rec_head_t.loss
 GRU4REC_CANDIDATES = {"in_batch": 1, "in_batch+sampled": 2}         # bsarec_gru4rec_head_t.candidates
@@ -243,6 +248,12 @@ EXPORTS = {
                                       [C.c_long, C.c_void_p, C.POINTER(Gru4RecHead)]),
     "bsarec_gru4rec_cand_train_step": (C.c_int, [C.POINTER(Gru4RecConfig)] + [C.c_void_p] * 3 + [C.POINTER(Adam)] * 2 +
                                        [C.c_void_p] * 3 + [C.c_long, C.c_void_p, C.POINTER(Gru4RecHead)]),
+    "bsarec_caser_weight_floats": (C.c_long, [C.POINTER(CaserConfig)]),
+    "bsarec_caser_workspace_bytes": (C.c_long, [C.POINTER(CaserConfig), C.c_int]),
+    "bsarec_caser_fwd": (C.c_int, [C.POINTER(CaserConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long,
+                                   C.c_void_p]),
+    "bsarec_caser_bwd": (C.c_int, [C.POINTER(CaserConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

@@ -1,0 +1,290 @@
+"""Caser sibling model: an item embedding, a convolution block over the [L, d] embedding "image" of a sequence -- n_v vertical
+filters of shape (L, 1) and, for EVERY height h = 1 .. L, n_h horizontal filters of shape (h, d) with ReLU and the maximum over
+positions -- and a Linear + ReLU back to the embedding width, trained with BPR.  Item-only: the user embedding of the original
+Caser is left out, as every model here ignores ``user_ids``.
+
+The contract of this model is the math of its docstrings, checked against ``torch.nn.Conv2d`` / ``F.max_pool1d`` / ``nn.Linear``
+on the CPU (tests/caser_ref.py, tests/test_caser_cpu.py); no reference golden exists for it yet.  The convolution block runs in
+libbsarec_hip.so in both directions (bsarec_caser_fwd / bsarec_caser_bwd, csrc/caser.h); the embedding lookup, the dropout mask,
+``fc1`` and the B-row BPR head are torch ops.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import math
+from collections import OrderedDict
+
+import torch
+from torch import nn
+
+from . import _lib as L
+
+CASER_NH = (4, 8, 16, 32)
+_NO_CPU = "bsarec_amd runs on MI355X only: move the model and its input to the GPU (there is no CPU fallback)"
+
+
+def caser_param_shapes(seq_len: int, width: int, n_h: int, n_v: int) -> "OrderedDict[str, tuple]":
+    """The tensors of bsarec_caser_fwd's flat weight array, in its order and with torch's Conv2d shapes (include/bsarec_hip.h)."""
+    shapes = OrderedDict([("conv_v.weight", (n_v, 1, seq_len, 1)), ("conv_v.bias", (n_v,))])
+    for i in range(seq_len):
+        shapes[f"conv_h.{i}.weight"] = (n_h, 1, i + 1, width)
+        shapes[f"conv_h.{i}.bias"] = (n_h,)
+    return shapes
+
+
+def caser_layout(seq_len: int, width: int, n_h: int, n_v: int):
+    """({name: (offset, numel, shape)}, total floats): every tensor starts at a multiple of 4 floats (16 bytes)."""
+    slices, off = OrderedDict(), 0
+    for name, shp in caser_param_shapes(seq_len, width, n_h, n_v).items():
+        off = (off + 3) // 4 * 4
+        n = math.prod(shp)
+        slices[name] = (off, n, shp)
+        off += n
+    return slices, (off + 3) // 4 * 4
+
+
+class _CaserFn(torch.autograd.Function):
+    """The convolution block as one autograd node over bsarec_caser_fwd / bsarec_caser_bwd, both on the current stream.  The
+    workspace carries the winning window of every cell to the backward: it is taken from the block's pool per shape and goes
+    back after the backward.  ``params`` are the views of the block's flat weight tensor; their gradients are views of one flat
+    ``dweights``."""
+
+    @staticmethod
+    def forward(ctx, conv, x, *params):
+        cfg, nbytes = conv._config(x, 1)
+        key = (x.shape[0], True, x.device)
+        pool = conv._pool.setdefault(key, [])
+        ws = pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        x = conv._operand(x)
+        z = torch.empty((x.shape[0], conv.out_features), dtype=torch.float32, device=x.device)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        L.check(L.load().bsarec_caser_fwd(cfg, x.data_ptr(), conv._flat.data_ptr(), 1, z.data_ptr(), ws.data_ptr(), nbytes, stream),
+                "bsarec_caser_fwd")
+        ctx.save_for_backward(x)
+        ctx.conv, ctx.key, ctx.ws, ctx.call = conv, key, ws, (cfg, nbytes, conv._flat)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        (x,) = ctx.saved_tensors
+        cfg, nbytes, flat = ctx.call
+        conv = ctx.conv
+        if ctx.ws is None:
+            raise RuntimeError("caser: backward ran twice (the forward's winning windows are gone)")
+        g = conv._operand(gz)
+        dx = torch.empty_like(x)
+        dw = torch.empty_like(flat)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        L.check(L.load().bsarec_caser_bwd(cfg, x.data_ptr(), flat.data_ptr(), g.data_ptr(), ctx.ws.data_ptr(), nbytes,
+                                          dx.data_ptr(), dw.data_ptr(), stream), "bsarec_caser_bwd")
+        conv._pool[ctx.key].append(ctx.ws)
+        ctx.ws = None
+        return (None, dx) + tuple(dw[o:o + n].view(shp) for o, n, shp in conv._slices.values())
+
+
+class _Conv(nn.Module):
+    """Holder of one filter bank's ``weight`` / ``bias``: views of the block's flat tensor (the convolution runs in
+    bsarec_caser_fwd)."""
+
+    def __init__(self, weight, bias):
+        super().__init__()
+        self.weight, self.bias = weight, bias
+
+
+class CaserConv(nn.Module):
+    """x [B, L, d] -> z [B, n_v d + n_h L] on the HIP kernels:
+      z[b, c d + j]             = sum_t conv_v.weight[c, 0, t, 0] x[b, t, j] + conv_v.bias[c]
+      z[b, n_v d + i n_h + f]   = max(0, max_t (sum_{r <= i, j} conv_h.{i}.weight[f, 0, r, j] x[b, t + r, j] + conv_h.{i}.bias[f]))
+    -- ``nn.Conv2d(1, n_v, (L, 1))`` and ``nn.Conv2d(1, n_h, (i + 1, d))`` -> ReLU -> max-pool over t on ``x.unsqueeze(1)``,
+    concatenated.  The backward is the true derivative: a cell passes gradient only if its maximum is > 0, to the window at the
+    lowest t that attains it.  Owns ONE flat fp32 tensor in the layout of bsarec_caser_fwd's ``weights`` (every tensor at a
+    multiple of 4 floats); ``conv_v.weight`` / ``conv_v.bias`` / ``conv_h.{i}.weight`` / ``conv_h.{i}.bias`` are parameters that
+    are views of it with torch's Conv2d shapes, so a module of ``nn.Conv2d``s under those names loads this state_dict, and the
+    reverse, and an optimiser that updates them in place updates the array the kernels read.  Init is torch's Conv2d default,
+    U(-1 / sqrt(fan_in), 1 / sqrt(fan_in)) for weight and bias."""
+
+    def __init__(self, seq_len: int, width: int, n_h: int = 16, n_v: int = 4):
+        super().__init__()
+        if n_h not in CASER_NH:
+            raise ValueError(f"caser_nh must be one of {CASER_NH}, got {n_h}")
+        if not 1 <= n_v <= 16:
+            raise ValueError(f"caser_nv must be in 1..16, got {n_v}")
+        if not 1 <= seq_len <= 256:
+            raise ValueError(f"Caser: max_seq_length {seq_len} outside 1..256")
+        if not (4 <= width <= 256 and width % 4 == 0):
+            raise ValueError(f"Caser: hidden_size {width} outside 4..256 or not a multiple of 4")
+        self.seq_len, self.width, self.n_h, self.n_v = seq_len, width, n_h, n_v
+        self.out_features = n_v * width + n_h * seq_len
+        self._slices, self._numel = caser_layout(seq_len, width, n_h, n_v)
+        self._pool = {}                          # (B, train, device) -> free workspaces
+        self._flat = torch.zeros(self._numel, dtype=torch.float32)
+        views = [nn.Parameter(self._flat[o:o + n].view(shp)) for o, n, shp in self._slices.values()]
+        with torch.no_grad():
+            for w, b in zip(views[0::2], views[1::2]):
+                bound = 1.0 / math.sqrt(w[0].numel())
+                w.uniform_(-bound, bound)
+                b.uniform_(-bound, bound)
+        self.conv_v = _Conv(views[0], views[1])
+        self.conv_h = nn.ModuleList(_Conv(w, b) for w, b in zip(views[2::2], views[3::2]))
+
+    def flat_parameters(self):
+        """The parameters in the order of the flat array."""
+        out = [self.conv_v.weight, self.conv_v.bias]
+        for c in self.conv_h:
+            out += [c.weight, c.bias]
+        return out
+
+    def _apply(self, fn, recurse=True):
+        out = super()._apply(fn, recurse)
+        self.reflatten()
+        return out
+
+    def reflatten(self):
+        """Makes every parameter a view of one flat tensor again (after ``.to()`` / ``.cuda()`` gave each its own storage)."""
+        ps = self.flat_parameters()
+        base = self._flat
+        if all(p.device == base.device and p.data_ptr() == base.data_ptr() + 4 * o
+               for p, (o, n, shp) in zip(ps, self._slices.values())):
+            return
+        with torch.no_grad():
+            flat = torch.zeros(self._numel, dtype=torch.float32, device=ps[0].device)
+            for p, (o, n, shp) in zip(ps, self._slices.values()):
+                flat[o:o + n] = p.detach().reshape(-1).to(torch.float32)
+                p.data = flat[o:o + n].view(shp)
+                p.grad = None
+        self._flat = flat
+        self._pool = {}
+
+    def _config(self, x, train: int):
+        if x.dim() != 3 or x.shape[1] != self.seq_len or x.shape[2] != self.width:
+            raise ValueError(f"caser: input must be [B, {self.seq_len}, {self.width}], got {tuple(x.shape)}")
+        if not x.is_cuda:
+            raise RuntimeError(_NO_CPU)
+        self.reflatten()
+        if self._flat.device != x.device:
+            raise RuntimeError("caser: the weights and the input are on different devices")
+        cfg = L.CaserConfig(x.shape[0], self.seq_len, self.width, self.n_h, self.n_v)
+        nbytes = L.load().bsarec_caser_workspace_bytes(cfg, train)
+        if nbytes < 0:
+            raise ValueError(f"caser: unsupported batch B = {x.shape[0]} (1 <= B <= 65536)")
+        return cfg, nbytes
+
+    @staticmethod
+    def _operand(t):
+        t = t.detach().to(torch.float32).contiguous()
+        return t.clone() if t.data_ptr() % 16 != 0 else t
+
+    def forward(self, x):
+        """[B, L, d] -> [B, n_v d + n_h L].  Differentiable with respect to x and every parameter when autograd is recording;
+        otherwise the train = 0 call, which keeps nothing."""
+        if not x.is_cuda:
+            raise RuntimeError(_NO_CPU)
+        params = self.flat_parameters()
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            self.reflatten()
+            return _CaserFn.apply(self, x, *params)
+        cfg, nbytes = self._config(x, 0)
+        key = (x.shape[0], False, x.device)
+        pool = self._pool.setdefault(key, [])
+        ws = pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        xo = self._operand(x)
+        z = torch.empty((x.shape[0], self.out_features), dtype=torch.float32, device=x.device)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        L.check(L.load().bsarec_caser_fwd(cfg, xo.data_ptr(), self._flat.data_ptr(), 0, z.data_ptr(), ws.data_ptr(), nbytes, stream),
+                "bsarec_caser_fwd")
+        pool.append(ws)                          # stream order: the next user of ws runs after this call
+        return z
+
+
+class CaserModel(nn.Module):
+    """``bsarec_amd.main.MODEL_DICT['caser']`` (``--model_type Caser``).  Parameters (the state_dict keys, in this order): ``item_embeddings.weight`` [V, d],
+    ``conv.conv_v.weight`` [n_v, 1, L, 1], ``conv.conv_v.bias`` [n_v], ``conv.conv_h.{i}.weight`` [n_h, 1, i + 1, d] and
+    ``conv.conv_h.{i}.bias`` [n_h] for i < L, ``fc1.weight`` [d, n_v d + n_h L], ``fc1.bias`` [d]; d = hidden_size,
+    L = max_seq_length, n_h = caser_nh (default 16), n_v = caser_nv (default 4), V = item_size.
+
+    forward: x = E[input_ids] (no position embedding, padding not masked); z = CaserConv(x); s = relu(fc1(Dropout_p(z))),
+    p = hidden_dropout_prob, the mask drawn from a torch generator seeded by ``set_seed``.  ``forward`` / ``predict`` return s,
+    [B, d] -- ONE state per sequence, not the [B, L, d] of the block models: Caser has no per-position output.
+    Loss: BPR, mean_b -log(sigmoid(s . E[answers] - s . E[neg_answers]) + 1e-10).
+    Init: Embedding and fc1 weights N(0, initializer_range), the fc1 bias 0, the filters torch's Conv2d default.
+    Item-only: the user embedding of the original Caser is left out (``user_ids`` is accepted and ignored).
+    The filter bank is sized by L: ``input_ids.shape[1]`` must equal ``args.max_seq_length`` (ValueError otherwise).
+    Steps through calculate_loss / backward / torch.optim.Adam (``torch_optim``) on one GPU."""
+
+    needs_negatives = True
+    needs_same_target = False
+    torch_optim = True
+    kernel_family = "Caser"                      # Trainer's messages
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        d, Lq = int(args.hidden_size), int(args.max_seq_length)
+        self.item_embeddings = nn.Embedding(int(args.item_size), d)
+        self.conv = CaserConv(Lq, d, int(getattr(args, "caser_nh", 16)), int(getattr(args, "caser_nv", 4)))
+        self.fc1 = nn.Linear(self.conv.out_features, d)
+        self.p_drop = float(args.hidden_dropout_prob)
+        if not 0.0 <= self.p_drop < 1.0:
+            raise ValueError(f"hidden_dropout_prob must be in [0, 1), got {self.p_drop}")
+        std = float(args.initializer_range)
+        with torch.no_grad():
+            self.item_embeddings.weight.normal_(0.0, std)
+            self.fc1.weight.normal_(0.0, std)
+            self.fc1.bias.zero_()
+        self._seed, self._rank, self._gen = 42, 0, None
+
+    def _apply(self, fn, recurse=True):
+        out = super()._apply(fn, recurse)
+        self.conv.reflatten()
+        self._gen = None
+        return out
+
+    def set_seed(self, seed: int, rank: int = 0):
+        """Seed of the dropout draws (rank-decorrelated)."""
+        self._seed, self._rank = int(seed), int(rank)
+        self._gen = None
+
+    def _generator(self, device):
+        if self._gen is None or self._gen.device != device:
+            self._gen = torch.Generator(device=device)
+            self._gen.manual_seed((self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF)
+        return self._gen
+
+    def _require_gpu(self, input_ids):
+        if self.item_embeddings.weight.device.type != "cuda" or not input_ids.is_cuda:
+            raise RuntimeError("bsarec_amd runs on MI355X only: move the model and its input with .cuda() "
+                               "(there is no CPU fallback)")
+        if input_ids.dim() != 2 or input_ids.shape[1] != self.conv.seq_len:
+            raise ValueError(f"Caser: input_ids must be [B, max_seq_length = {self.conv.seq_len}] (the filter bank is sized by it), "
+                             f"got {tuple(input_ids.shape)}")
+
+    def _state(self, input_ids, train: bool):
+        z = self.conv(self.item_embeddings(input_ids))
+        if train and self.p_drop > 0.0:
+            keep = torch.empty_like(z).bernoulli_(1.0 - self.p_drop, generator=self._generator(z.device))
+            z = z * keep * (1.0 / (1.0 - self.p_drop))
+        return torch.relu(self.fc1(z))
+
+    def forward(self, input_ids, user_ids=None, all_sequence_output=False):
+        """[B, L] ids -> s [B, d].  ``user_ids`` and ``all_sequence_output`` are accepted and ignored."""
+        self._require_gpu(input_ids)
+        return self._state(input_ids, self.training)
+
+    def predict(self, input_ids, user_ids=None, all_sequence_output=False):
+        return self.forward(input_ids, user_ids, all_sequence_output)
+
+    def last_hidden(self, input_ids) -> torch.Tensor:
+        """[B, d]: the eval-mode s (the bits of ``forward`` in eval mode), no gradient."""
+        self._require_gpu(input_ids)
+        with torch.no_grad():
+            return self._state(input_ids, False)
+
+    def calculate_loss(self, input_ids, answers, neg_answers=None, same_target=None, user_ids=None):
+        """BPR on s: a 0-d tensor; ``.backward()`` fills every parameter's grad."""
+        if neg_answers is None:
+            raise ValueError("Caser's loss needs neg_answers")
+        self._require_gpu(input_ids)
+        s = self._state(input_ids, self.training)
+        pos = self.item_embeddings(answers.to(s.device).reshape(-1))
+        neg = self.item_embeddings(neg_answers.to(s.device).reshape(-1))
+        diff = (s * pos).sum(-1) - (s * neg).sum(-1)
+        return -torch.log(torch.sigmoid(diff) + 1e-10).mean()

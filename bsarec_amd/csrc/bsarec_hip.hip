@@ -21,6 +21,7 @@
 #include "gru.h"
 #include "gru4rec_step.h"
 #include "gru4rec_cand.h"
+#include "caser.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -2365,6 +2366,89 @@ extern "C" int bsarec_gru_bwd(const bsarec_gru_config_t* cfg, const float* x, co
         RET(gru_tn(P.dbn + (long)B * H, H, yk, H, H, K, slab, 3L * H * H, 2L * H * H, nullptr, s));
         gru_sum(slab, K, 3L * H * H, dweights + wo.hh[k], s);
     }
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Caser convolution block (caser.h): plan-less, everything on the caller's stream, no allocation
+// ---------------------------------------------------------------------------------------------
+static int caser_check(const bsarec_caser_config_t* c) {
+    if (!c) return -10;
+    if (c->batch < 1 || c->batch > 65536 || c->seq_len < 1 || c->seq_len > 256) return -10;
+    if (!row_dim_ok(c->width)) return -10;
+    if (c->n_h != 4 && c->n_h != 8 && c->n_h != 16 && c->n_h != 32) return -10;
+    if (c->n_v < 1 || c->n_v > 16) return -10;
+    return 0;
+}
+
+// offsets (floats) into the flat weight array, every tensor at a multiple of 4: conv_v.weight [n_v][L] | conv_v.bias [n_v] |
+// conv_h.{h-1}.weight [n_h][h][d], conv_h.{h-1}.bias [n_h] for h = 1 .. L (n_h and d are multiples of 4: no gaps among these)
+struct CaserW { long bv, h0, total, F; };
+static CaserW caser_weights(const bsarec_caser_config_t& c) {
+    CaserW w;
+    const long L = c.seq_len, d = c.width;
+    w.bv = rup((long)c.n_v * L, 4);
+    w.h0 = w.bv + rup((long)c.n_v, 4);
+    w.total = w.h0 + (long)c.n_h * d * (L * (L + 1) / 2) + (long)c.n_h * L;
+    w.F = (long)c.n_v * d + (long)c.n_h * L;
+    return w;
+}
+// workspace: the winning window per cell, int [B][L][n_h] (training); 16 bytes that nothing touches otherwise
+static long caser_ws_bytes(const bsarec_caser_config_t& c, bool train) {
+    return train ? rup((long)c.batch * c.seq_len * c.n_h * (long)sizeof(int), 16) : 16;
+}
+
+extern "C" long bsarec_caser_weight_floats(const bsarec_caser_config_t* cfg) {
+    if (caser_check(cfg)) return -10;
+    return caser_weights(*cfg).total;
+}
+
+extern "C" long bsarec_caser_workspace_bytes(const bsarec_caser_config_t* cfg, int train) {
+    if (caser_check(cfg)) return -10;
+    return caser_ws_bytes(*cfg, train != 0);
+}
+
+static int caser_args(const bsarec_caser_config_t* cfg, const float* x, const float* weights, const void* workspace, long workspace_bytes,
+                      bool train) {
+    RET(caser_check(cfg));
+    if (!aligned_to(x, 16) || !aligned_to(weights, 16) || !aligned_to(workspace, 16)) return -10;      // null fails too
+    if (workspace_bytes < caser_ws_bytes(*cfg, train)) return -10;
+    return 0;
+}
+
+extern "C" int bsarec_caser_fwd(const bsarec_caser_config_t* cfg, const float* x, const float* weights, int train, float* z,
+                                void* workspace, long workspace_bytes, void* stream) {
+    RET(caser_args(cfg, x, weights, workspace, workspace_bytes, train != 0));
+    if (!aligned_to(z, 16)) return -10;
+    const bsarec_caser_config_t& c = *cfg;
+    const CaserW wo = caser_weights(c);
+    hipStream_t s = (hipStream_t)stream;
+    CaserP P;
+    P.x = x; P.w = weights; P.z = z; P.win = train ? (int*)workspace : nullptr;
+    P.B = c.batch; P.L = c.seq_len; P.d = c.width; P.nh = c.n_h; P.nv = c.n_v;
+    P.F = wo.F; P.bv_off = wo.bv; P.h_off = wo.h0;
+    hipLaunchKernelGGL(caser_v_fwd_kernel, dim3(cdiv((long)c.batch * (c.width / 4), 256)), dim3(256), 0, s, P);
+    const dim3 grid((c.seq_len + 1) / 2, cdiv(c.batch, 4));
+    if (c.n_h <= 16) hipLaunchKernelGGL(caser_h_fwd_kernel<1>, grid, dim3(256), 0, s, P);
+    else hipLaunchKernelGGL(caser_h_fwd_kernel<2>, grid, dim3(256), 0, s, P);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_caser_bwd(const bsarec_caser_config_t* cfg, const float* x, const float* weights, const float* dz,
+                                void* workspace, long workspace_bytes, float* dx, float* dweights, void* stream) {
+    RET(caser_args(cfg, x, weights, workspace, workspace_bytes, true));
+    if (!aligned_to(dz, 16) || !aligned_to(dx, 16) || !aligned_to(dweights, 16)) return -10;
+    const bsarec_caser_config_t& c = *cfg;
+    const CaserW wo = caser_weights(c);
+    hipStream_t s = (hipStream_t)stream;
+    CaserBwdP P;
+    P.x = x; P.w = weights; P.dz = dz; P.win = (const int*)workspace; P.dx = dx; P.dw = dweights;
+    P.B = c.batch; P.L = c.seq_len; P.d = c.width; P.nh = c.n_h; P.nv = c.n_v;
+    P.F = wo.F; P.bv_off = wo.bv; P.h_off = wo.h0;
+    const int quads = c.seq_len * (c.width / 4), cells = c.seq_len * c.n_h;
+    hipLaunchKernelGGL(caser_dx_kernel, dim3(c.batch, cdiv(quads, 256)), dim3(256), (size_t)cells * 6, s, P);
+    hipLaunchKernelGGL(caser_dwh_kernel, dim3(cells, cdiv(quads, 256)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(caser_dv_kernel, dim3(c.seq_len + 1, c.n_v), dim3(64), 0, s, P);
     return (int)hipGetLastError();
 }
 

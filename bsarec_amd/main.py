@@ -22,7 +22,12 @@ import scipy.sparse as sp
 import torch
 
 from . import data as D
-from .model import MODEL_DICT
+from .caser import CaserModel
+from .model import MODEL_DICT as _MODEL_DICT
+
+# --model_type -> class: the table of model.py and Caser (bsarec_amd/caser.py).  Caser is registered HERE: the key set of
+# bsarec_amd.model.MODEL_DICT is pinned (tests/test_gru_cpu.py), so that table stays as it is
+MODEL_DICT = dict(_MODEL_DICT, caser=CaserModel)
 from .trainer import Trainer
 
 
@@ -164,6 +169,11 @@ def parse_args(argv=None):
                         "answers, or those and every row's sampled negative")
     p.add_argument("--gru_bpreg", default=argparse.SUPPRESS, type=float,
                    help="GRU4Rec: weight of BPR-max's score regulariser (default 1.0)")
+    # not reference flags: the filter counts of Caser's convolution block (--model_type Caser).  Absent unless given
+    p.add_argument("--caser_nh", default=argparse.SUPPRESS, type=int, choices=(4, 8, 16, 32),
+                   help="Caser: horizontal filters per height (default 16)")
+    p.add_argument("--caser_nv", default=argparse.SUPPRESS, type=int,
+                   help="Caser: vertical filters, 1..16 (default 4)")
     args = p.parse_args(argv)
     n = getattr(args, "eval_negatives", 0)
     if n > 0 and hasattr(args, "eval_full_rank"):

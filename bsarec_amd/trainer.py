@@ -6,8 +6,8 @@ get_full_sort_score``); the per-batch body of ``iteration(train=True)`` is ONE C
 hipGraph, the epoch loss is accumulated on the device (no per-step ``loss.item()`` sync), and the
 evaluation branch scores, masks seen items and takes the top-20 on the GPU.
 
-A model without the flat parameter arena (GRU4Rec, bsarec_amd/gru4rec.py) trains on one GPU through the ``torch_optim``
-branch of ``iteration``; it has ``last_hidden`` and the item table but no ``full_logits``, so the default ("dense")
+A model without the flat parameter arena (GRU4Rec, bsarec_amd/gru4rec.py; Caser, bsarec_amd/caser.py) trains on one GPU
+through the ``torch_optim`` branch of ``iteration``; it has ``last_hidden`` and the item table but no ``full_logits``, so the default ("dense")
 evaluation takes ``topk_full`` for it, which returns the same lists by construction.
 """
 from __future__ import annotations
@@ -81,9 +81,9 @@ class Trainer:
     def __init__(self, model: BSARecModel, train_dataloader, eval_dataloader, test_dataloader, args, logger=None,
                  use_graph: bool = True, process_group=None, exchange: str = "auto"):
         self.args = args
-        arena = hasattr(model, "_arena")       # the flat-arena models of model.py; GRU4Rec (gru4rec.py) has none
+        arena = hasattr(model, "_arena")       # the flat-arena models of model.py; GRU4Rec (gru4rec.py) and Caser (caser.py) have none
         if not arena:
-            self._check_arenaless(args, process_group)
+            self._check_arenaless(model, args, process_group)
         check_train_head(model, args, train_dataloader, process_group)
         self.logger = logger or _NullLogger()
         if not torch.cuda.is_available() or getattr(args, "no_cuda", False):
@@ -114,16 +114,20 @@ class Trainer:
         self._setup_exchange()
 
     @staticmethod
-    def _check_arenaless(args, process_group):
-        """A model without the flat parameter arena (GRU4Rec): single GPU, its own loss head, fp32."""
+    def _check_arenaless(model, args, process_group):
+        """A model without the flat parameter arena (GRU4Rec, Caser): single GPU, its own loss head, fp32.  The messages name the
+        model by its class (``GRU4RecModel`` -> "GRU4Rec") and its kernels by its ``kernel_family`` (default "GRU")."""
+        name = type(model).__name__
+        name = name[:-len("Model")] if name.endswith("Model") else name
         if process_group is not None:
-            raise ValueError("GRU4Rec: single GPU only")
+            raise ValueError(f"{name}: single GPU only")
         if getattr(args, "train_negatives", 0):
-            raise ValueError("GRU4Rec: train_negatives does not apply (the model has its own BPR head)")
+            raise ValueError(f"{name}: train_negatives does not apply (the model has its own BPR head)")
         if getattr(args, "train_lazy_adam", False):
-            raise ValueError("GRU4Rec: train_lazy_adam does not apply (the model steps through torch.optim.Adam)")
+            raise ValueError(f"{name}: train_lazy_adam does not apply (the model steps through torch.optim.Adam)")
         if getattr(args, "storage", None) == "bf16":
-            raise ValueError("GRU4Rec: storage = 'bf16' does not apply (the GRU kernels are fp32)")
+            raise ValueError(f"{name}: storage = 'bf16' does not apply (the {getattr(model, 'kernel_family', 'GRU')} kernels "
+                             "are fp32)")
 
     # ---- data-parallel gradient exchange (bsarec_amd/dp.py) ------------------------------------------
     def _setup_exchange(self):

@@ -695,6 +695,38 @@ int bsarec_freq_layer_bwd(const float *x, const float *dy, const float *xhat, co
                           float *scratch /* bsarec_freq_layer_bwd_scratch_floats(B,L,d) floats */,
                           float *dx, float *dsqrt_beta, float *dln_w, float *dln_b, void *stream);
 
+/* Convolution block of the Caser sibling model (csrc/caser.h): with x [B, L, d] (d = width),
+ *   vertical    zv[b, c, j]   = sum_t Wv[c, t] x[b, t, j] + bv[c],                                c < n_v, at z[b][c d + j]
+ *   horizontal  c_h[b, f, t]  = sum_{i < h, j < d} Wh_h[f, i, j] x[b, t + i, j] + bh_h[f],        h = 1 .. L, t = 0 .. L - h
+ *               zh[b, h-1, f] = max(0, max_t c_h[b, f, t]),                                       at z[b][n_v d + (h-1) n_h + f]
+ * z [B, F], F = n_v d + n_h L: what nn.Conv2d(1, n_v, (L, 1)) and, per height, nn.Conv2d(1, n_h, (h, d)) -> ReLU -> max over t
+ * compute on x.unsqueeze(1), concatenated.  All arithmetic is fp32 (v_mfma_f32_16x16x4_f32 in the horizontal forward).
+ *   weights: ONE flat array of bsarec_caser_weight_floats(cfg) floats, row-major tensors in this order, EACH at an offset rounded
+ * up to a multiple of 4 floats: conv_v.weight [n_v, L], conv_v.bias [n_v], then for h = 1 .. L conv_h.{h-1}.weight [n_h, h, d]
+ * and conv_h.{h-1}.bias [n_h].  The gaps are never read; bsarec_caser_bwd writes 0 into them in dweights.
+ *   bsarec_caser_bwd is the true derivative: a cell (b, h, f) passes dz only if its maximum is > 0, and to the window at the
+ * LOWEST t that attains the maximum (torch's CPU max-pool rule).  dx [B, L, d] and every float of dweights are overwritten.  It
+ * reads what bsarec_caser_fwd(train = 1) left in the SAME workspace: the winning t per cell as int [B][L][n_h], -1 for a cell
+ * that passes nothing.  With train = 0 the forward keeps nothing and gives the same z bits.
+ *   One reduction order per (h, f), whatever t and b: bit-identical windows give bit-identical c_h, so exact ties (left-padded
+ * sequences repeat a row) resolve by the rule above, and a sequence's z bits do not depend on the rest of the batch.  Every
+ * gradient sum runs in a fixed order (b rising; per dx element the cells (h, f) rising): no atomics, bit-deterministic.
+ *   Launches, all on `stream`: forward 2 (vertical, horizontal), backward 3 (dx, dWh + dbh, dWv + dbv + gaps).  No allocation, no
+ * host synchronisation, no scratch: capturable.  Dynamic LDS of the dx launch is 6 L n_h bytes (<= 48 KB).
+ *   Workspace: bsarec_caser_workspace_bytes(cfg, train) bytes (host-only query, no HIP call).
+ *   Limits (else < 0 before any HIP call): 1 <= batch <= 65536, 1 <= seq_len <= 256, width in 4 .. 256 and a multiple of 4,
+ * n_h in {4, 8, 16, 32}, 1 <= n_v <= 16; every pointer non-null and 16-byte aligned; workspace_bytes at least the queried size
+ * (bsarec_caser_bwd: that of train = 1).  Inputs are assumed finite. */
+typedef struct {
+    int batch, seq_len, width, n_h, n_v;
+} bsarec_caser_config_t;
+long bsarec_caser_weight_floats(const bsarec_caser_config_t *cfg);
+long bsarec_caser_workspace_bytes(const bsarec_caser_config_t *cfg, int train);
+int bsarec_caser_fwd(const bsarec_caser_config_t *cfg, const float *x, const float *weights, int train, float *z,
+                     void *workspace, long workspace_bytes, void *stream);
+int bsarec_caser_bwd(const bsarec_caser_config_t *cfg, const float *x, const float *weights, const float *dz,
+                     void *workspace, long workspace_bytes, float *dx, float *dweights, void *stream);
+
 /* Tag kernel launches of one id with hipEvents for in-process roofline timing (bench.py):
  * when set, every launch of kernel class `kclass` (see BSAREC_K_*) on the next calls of THIS plan is bracketed
  * by hipEventRecord on the launch stream; bsarec_profile_read returns the summed milliseconds and
