@@ -13,7 +13,7 @@ TRAIN_NEG_MAX = 8192                             # BSAREC_TRAIN_NEG_MAX: the mos
 TRAIN_NEG_SITE = 0x4E454753                      # BSAREC_TRAIN_NEG_SITE: Philox counter word 2 of its draws
 
 (BUF_LAYER_OUT, BUF_LOGITS, BUF_LOSS, BUF_DSP, BUF_HMIX, BUF_PROBS, BUF_DLAYER_IN, BUF_LOSS_ROWS, BUF_CTX,
- BUF_DLOGITS, BUF_TRAIN_CAND, BUF_TRAIN_CORR, BUF_TRAIN_LOGITS, BUF_TRAIN_DLOGITS) = range(14)
+ BUF_DLOGITS, BUF_TRAIN_CAND, BUF_TRAIN_CORR, BUF_TRAIN_LOGITS, BUF_TRAIN_DLOGITS, BUF_DROP_BITS) = range(15)
 K_NONE, K_FFN1, K_FFN2, K_QKV, K_LOGITS, K_DU, K_DW1, K_FUSED_FWD, K_FUSED_BWD = range(9)
 
 LAYER_FIELDS = ["sqrt_beta", "filter_ln_w", "filter_ln_b", "query_w", "query_b", "key_w", "key_b", "value_w", "value_b",
@@ -59,12 +59,15 @@ TRAIN_SAMPLERS = {"uniform": 0, "popularity": 1}
 
 OPTION_FIELDS = ("storage", "no_fused", "no_prune_top", "dw_tiled", "splits", "top_slabs", "separate_embed", "separate_top", "chain_kernels", "x3_products",
                  "weight_image")
+# options a plan takes through a setter after its creation, not through bsarec_config_t (bsarec_plan_set_drop_bits)
+PLAN_SETTERS = ("drop_bits",)
 HIDDEN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "tanh": 3, "sigmoid": 4}      # src/model/_modules.py:38-45
 
 # Plan options the HOST gives to plans it creates from now on.  The C ABI has no process-wide state: these are Python
 # defaults (test / bench shims and the environment knobs of INTEGRATION.md), copied into bsarec_config_t per plan.
-_defaults = {k: 0 for k in OPTION_FIELDS}
+_defaults = {k: 0 for k in OPTION_FIELDS + PLAN_SETTERS}
 _defaults["weight_image"] = 1        # on wherever the library can use it (fp32 plans at the fused shape), ignored elsewhere
+_defaults["drop_bits"] = 1           # fused plans: the backward reads the forward's dropout keep bits (csrc/drop_bits.h)
 
 
 def _env_defaults():
@@ -91,6 +94,8 @@ def _env_defaults():
         d["storage"] = 1
     if e.get("BSAREC_WEIGHT_IMAGE") == "0":
         d["weight_image"] = 0
+    if e.get("BSAREC_DROP_BITS") == "0":
+        d["drop_bits"] = 0
     return d
 
 
@@ -175,6 +180,10 @@ EXPORTS = {
     "bsarec_wimage_offset": (C.c_long, [C.c_int] * 5),
     "bsarec_plan_set_dense_grad_hook": (C.c_int, [C.c_void_p, HOOK, C.c_void_p, C.c_void_p]),
     "bsarec_plan_set_train_sampler": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bsarec_plan_set_drop_bits": (C.c_int, [C.c_void_p, C.c_int]),
+    "bsarec_drop_bits_bytes": (C.c_long, [C.POINTER(Config)]),
+    "bsarec_drop_bits_hidden_bit": (C.c_long, [C.c_int, C.c_long, C.c_long, C.c_int]),
+    "bsarec_drop_bits_attn_bit": (C.c_long, [C.c_long, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int]),
     "bsarec_buffer_is_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "bsarec_plan_is_fused": (C.c_int, [C.c_void_p]),
     "bsarec_config_is_fused": (C.c_int, [C.c_void_p]),

@@ -122,6 +122,11 @@ struct bsarec_plan {
     // fragment image of the Linear weights (cfg.weight_image; wimage.h): [layers][wimage_layer_floats(d)], the caller's
     // memory (bsarec_plan_create); null = the block kernels read the masters
     float* wimg = nullptr;
+    // keep bits of the dropout masks (drop_bits.h): one buffer per layer, written by the forward block kernels of a training
+    // step and read by the matching backward; carved wherever drop_bits_wanted(cfg), used while drop_bits is set
+    // (bsarec_plan_set_drop_bits; on by default)
+    unsigned char* dbitsL[BSAREC_MAX_LAYERS] = {};
+    bool drop_bits = true;
 };
 struct PlanScope {                           // marks the plan a C call works on for this thread (nesting-safe)
     bsarec_plan* prev;
@@ -254,6 +259,12 @@ static bool wimage_wanted(const bsarec_config_t& c) {
     return c.weight_image && fused_shape_ok(c) && c.storage == 0 && !c.x3_products && !c.chain_kernels && c.filter_kind == 0;
 }
 
+// keep bits: where the LDS-phase BSARec block kernels run both directions in fp32 or bf16 storage (the x3, chain and FMLPRec
+// variants evaluate Philox in both) and the embedding front-end rides in the bottom block (derive: embed_in_block)
+static bool drop_bits_wanted(const bsarec_config_t& c) {
+    return fused_shape_ok(c) && c.filter_kind == 0 && (c.storage == 1 || (!c.x3_products && !c.chain_kernels && !c.separate_embed));
+}
+
 static bool fused_shape_ok(const bsarec_config_t& c) {
     const int dh = c.hidden / c.heads;
     if (c.no_fused || c.hidden_act != 0 || c.hidden != 64 || c.seq_len > 64 || !(dh == 16 || dh == 32 || dh == 64)) return false;
@@ -369,6 +380,8 @@ static void carve(bsarec_plan& p, char* base, size_t* total) {
         p.lazy.d4 = (int)(d / 4);
         p.lazy.mark = cv.take<int>(c.item_size); p.lazy.rows = cv.take<int>(p.lazy.cap); p.lazy.count = cv.take<int>(1);
     }
+    if (drop_bits_wanted(c))
+        for (int l = 0; l < N; ++l) p.dbitsL[l] = cv.take<unsigned char>((size_t)drop_bits_layer_bytes(B, L, c.heads));
     // (no guard pad: the direct weight-gradient kernels prefetch past a slice without predicates, but through buffer
     // descriptors sized to their operand -- dw_direct.h)
     *total = cv.off;
@@ -547,7 +560,7 @@ extern "C" long bsarec_buffer_offset(const bsarec_plan_t* p, int buffer, int lay
     if (!p) return -1;
     const int N = p->cfg.layers;
     const void* ptr = nullptr;
-    if (buffer >= BSAREC_BUF_TRAIN_CAND && p->cfg.train_negatives == 0) return -1;
+    if (buffer >= BSAREC_BUF_TRAIN_CAND && buffer <= BSAREC_BUF_TRAIN_DLOGITS && p->cfg.train_negatives == 0) return -1;
     switch (buffer) {
         case BSAREC_BUF_LAYER_OUT: if (layer < 0 || layer > N) return -1; ptr = p->X[layer]; break;
         case BSAREC_BUF_LOGITS: ptr = p->logits; break;
@@ -563,6 +576,7 @@ extern "C" long bsarec_buffer_offset(const bsarec_plan_t* p, int buffer, int lay
         case BSAREC_BUF_TRAIN_CORR: ptr = p->ssm_corr; break;
         case BSAREC_BUF_TRAIN_LOGITS: ptr = p->ssm_logits; break;
         case BSAREC_BUF_TRAIN_DLOGITS: ptr = p->ssm_dlogits; break;
+        case BSAREC_BUF_DROP_BITS: if (layer < 0 || layer >= N || !p->dbitsL[layer]) return -1; ptr = p->dbitsL[layer]; break;
         default: return -1;
     }
     return (long)((const char*)ptr - p->ws);
@@ -573,6 +587,24 @@ extern "C" int bsarec_plan_set_dense_grad_hook(bsarec_plan_t* p, bsarec_hook_t h
     if (p->cfg.train_negatives > 0 && (hook || lookup_grad)) return -22;     // the sampled head has no dense part to exchange early
     p->dense_hook = hook; p->dense_hook_user = user; p->lookup_grad = lookup_grad;
     return 0;
+}
+
+extern "C" int bsarec_plan_set_drop_bits(bsarec_plan_t* p, int on) {
+    if (!p || on < 0 || on > 1) return -10;
+    p->drop_bits = on != 0;
+    return 0;
+}
+extern "C" long bsarec_drop_bits_bytes(const bsarec_config_t* cfg) {
+    if (!cfg || check_cfg(*cfg) != 0) return -1;
+    return drop_bits_wanted(*cfg) ? drop_bits_layer_bytes(cfg->batch, cfg->seq_len, cfg->heads) : 0;
+}
+extern "C" long bsarec_drop_bits_hidden_bit(int slot, long tokens, long token, int column) {
+    if (slot < 0 || slot >= DB_SLOTS || tokens < 1 || token < 0 || token >= tokens || column < 0 || column >= 64) return -1;
+    return drop_bits_hidden_bit(slot, tokens, token, column);
+}
+extern "C" long bsarec_drop_bits_attn_bit(long tokens, int heads, long b, int head, int query, int key) {
+    if (tokens < 1 || heads < 1 || b < 0 || head < 0 || head >= heads || query < 0 || query >= 64 || key < 0 || key >= 64) return -1;
+    return drop_bits_attn_bit(tokens, heads, b, head, query, key);
 }
 
 extern "C" int bsarec_plan_set_train_sampler(bsarec_plan_t* p, const int64_t* pop_cum) {
@@ -758,6 +790,7 @@ static void fill_block(const bsarec_plan& p, int l, bool tr, const bsarec_layer_
     F.drop_f = make_drop(p, c.p_hidden, 1 + 4 * l, tr); F.drop_p = make_drop(p, c.p_attn, 2 + 4 * l, tr);
     F.drop_o = make_drop(p, c.p_hidden, 3 + 4 * l, tr); F.drop_ff = make_drop(p, c.p_hidden, 4 + 4 * l, tr);
     F.stamps = p.stamps ? p.stamps + 32 * (2 * l + (FWD ? 0 : 1)) : nullptr;
+    F.dbits = p.drop_bits ? p.dbitsL[l] : nullptr;             // (null where the plan carved none)
     if constexpr (FWD) {       // the forward alone: the output, the biases and LayerNorm betas, the activations it saves
         F.Xout = p.X[l + 1];
         F.f_b = w.filter_ln_b; F.bq = w.query_b; F.bk = w.key_b; F.bv = w.value_b; F.bo = w.dense_b; F.a_b = w.attn_ln_b;
@@ -850,6 +883,18 @@ static int launch_fused_bwd(bsarec_plan& p, int l, bool tr, const float* dY, flo
         return launch_lds<fused_layer_bwd_kernel<32, false, NoTail, false, true>>(grid, block, smem, s, F, NoTail());
     }
     int rc = 0;
+    if (F.dbits) {      // the forward left keep bits (drop_bits.h): the instantiations without Philox; fp32 (image or masters) / bf16
+        if (p.wimg)
+            DISPATCH_DH(p.dh, rc = head ? launch_lds<fused_layer_bwd_kernel<DH, false, TopBwdP, false, false, true, true>>(grid, block, smem, s, F, *head)
+                                        : launch_lds<fused_layer_bwd_kernel<DH, false, NoTail, false, false, true, true>>(grid, block, smem, s, F, NoTail()));
+        else if (p.bf)
+            DISPATCH_DH(p.dh, rc = head ? launch_lds<fused_layer_bwd_kernel<DH, true, TopBwdP, false, false, false, true>>(grid, block, smem, s, F, *head)
+                                        : launch_lds<fused_layer_bwd_kernel<DH, true, NoTail, false, false, false, true>>(grid, block, smem, s, F, NoTail()));
+        else
+            DISPATCH_DH(p.dh, rc = head ? launch_lds<fused_layer_bwd_kernel<DH, false, TopBwdP, false, false, false, true>>(grid, block, smem, s, F, *head)
+                                        : launch_lds<fused_layer_bwd_kernel<DH, false, NoTail, false, false, false, true>>(grid, block, smem, s, F, NoTail()));
+        return rc;
+    }
     if (p.wimg) {
         DISPATCH_DH(p.dh, rc = head ? launch_lds<fused_layer_bwd_kernel<DH, false, TopBwdP, false, false, true>>(grid, block, smem, s, F, *head)
                                     : launch_lds<fused_layer_bwd_kernel<DH, false, NoTail, false, false, true>>(grid, block, smem, s, F, NoTail()));
@@ -884,6 +929,11 @@ static int launch_top_bwd(bsarec_plan& p, int l, bool tr, float* dXout, hipStrea
     TopBwdP F;
     fill_top_bwd(p, l, tr, dXout, F);
     int rc = 0;
+    if (F.dbits) {
+        if (p.bf) DISPATCH_DH(p.dh, rc = launch_lds<top_bwd_kernel<DH, true, true>>(dim3(p.cfg.batch), dim3(256), top_bwd_smem_bytes(), s, F));
+        else DISPATCH_DH(p.dh, rc = launch_lds<top_bwd_kernel<DH, false, true>>(dim3(p.cfg.batch), dim3(256), top_bwd_smem_bytes(), s, F));
+        return rc;
+    }
     DISPATCH_BLOCK(p, rc = launch_lds<top_bwd_kernel<DH, BF>>(dim3(p.cfg.batch), dim3(256), top_bwd_smem_bytes(), s, F));
     return rc;
 }

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "wimage.h"
+#include "drop_bits.h"
 #include <type_traits>
 
 #define FS 68          // LDS row stride (floats) of a 64-wide tile: 16-B aligned rows, conflict-free b128 reads
@@ -41,6 +42,7 @@ struct FusedFwdP {
     float *e_X0, *e_xhat, *e_rstd; int* e_ids32;
     int xout_f32;           // bf16 storage: Xout is the LAST layer's output, which stays an fp32 tensor (logits / API)
     const float* filter_cw; // FM instantiation only: FMLPRec's complex_weight [L/2 + 1][64][2] (re, im)
+    unsigned char* dbits;   // this layer's keep-bits buffer (drop_bits.h) for the backward; null: the plan keeps none
 };
 
 
@@ -366,7 +368,9 @@ __device__ __forceinline__ void ln_rows_64(const LnPre& P, const float* __restri
                                            float alpha, float oma, long tok0, int L, float* __restrict__ outL,
                                            float* __restrict__ outG, float* __restrict__ xhatG, float* __restrict__ rstdG,
                                            bool out_f32 = false /* BF: outG is an fp32 tensor (the last layer's output) */,
-                                           bool round_outL = false /* BF: the LDS copy holds what a reader of outG would see */) {
+                                           bool round_outL = false /* BF: the LDS copy holds what a reader of outG would see */,
+                                           unsigned char* bits = nullptr /* keep bits of P.dm -> slot `slot` (drop_bits.h) */,
+                                           int slot = 0) {
     const int lr = threadIdx.x >> 4, lc = (threadIdx.x & 15) << 2;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -388,6 +392,7 @@ __device__ __forceinline__ void ln_rows_64(const LnPre& P, const float* __restri
             ast4<BF>(xhatG, e, xh);
             if (BF && out_f32) gst4(outG + e, y); else ast4<BF>(outG, e, y);
             if (lc == 0) gst(rstdG + tok0 + r, rs);
+            if (bits) drop_bits_st8(bits + drop_bits_hidden_byte(slot, (long)gridDim.x * L, tok0, 0), drop_bits_row_off(r, lc), drop_keep4(P.dm[i]));
         }
         if (BF && round_outL) {
             const unsigned a = pk_bf16(y.x, y.y), c = pk_bf16(y.z, y.w);
@@ -419,12 +424,13 @@ struct TopBwdRegs {                                 // what top_bwd_prefetch req
     float xh_ff, g_ff, rs_ff, xa, xf, g_a, g_f, rs_a, rs_f, bt, low_l, x_l, q_l;
     f32x4 tq[16];                                   // waves 1..3 (fused head only): the x / k / v tile, one per wave
     float p_pre;                                    // waves < heads (fused head only): the probability row of the last query
+    unsigned kb, kw;                                // keep bits (drop_bits.h): the wave's row-L-1 byte; its head's attention word
 };
 struct TopBwdHelpRegs { f32x4 w2c[16], w1c[16], u4; };      // waves 4..7: dense_2 / dense_1 columns, gelu' input of their units
-template <bool BF, unsigned KOFF> __device__ __forceinline__ void top_bwd_prefetch(TopBwdRegs& R);
-template <bool BF, unsigned KOFF> __device__ __forceinline__ void top_bwd_prefetch_tile(TopBwdRegs& R);
+template <bool BF, unsigned KOFF, bool DB> __device__ __forceinline__ void top_bwd_prefetch(TopBwdRegs& R);
+template <bool BF, unsigned KOFF, bool DB> __device__ __forceinline__ void top_bwd_prefetch_tile(TopBwdRegs& R);
 template <bool BF, unsigned KOFF> __device__ __forceinline__ void top_bwd_help_prefetch(TopBwdHelpRegs& H);
-template <int DH, bool BF, unsigned KOFF, bool HELPED>
+template <int DH, bool BF, unsigned KOFF, bool HELPED, bool DB>
 __device__ __forceinline__ void top_bwd_body(const TopBwdRegs& R, const DropSeed& dseed, float* sX, float* sK, float* sV, const float* sTab,
                                              float* sVec, float* sDX);
 template <bool BF, unsigned KOFF> __device__ __forceinline__ void top_bwd_help_a(const TopBwdHelpRegs& H, float* sVec);
@@ -456,6 +462,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
     static_assert(!FM || (!BF && !X3 && !IsTail<TAILP>::value), "the FMLPRec block runs in fp32, without a top-block tail");
     constexpr int MAXCB = FM ? 36 : FUSED_MAX_CB;
     constexpr bool TAIL = IsTail<TAILP>::value;
+    constexpr bool DBITS = !X3 && !FM;              // the BSARec block in fp32 / bf16 storage leaves keep bits (drop_bits.h)
     constexpr unsigned KOFF = (unsigned)((sizeof(FusedFwdP) + 7) & ~(size_t)7);     // kernarg offset of T_unused
     const auto R0_L = KARG(FusedFwdP, L);
     const auto R0_Lp = KARG(FusedFwdP, Lp);
@@ -485,6 +492,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
     const int L = R0_L, Lp = R0_Lp, heads = R0_heads, cb = R0_cb;
     const int b = blockIdx.x;
     const long tok0 = (long)b * L;
+    const long Ttok = (long)gridDim.x * L;      // tokens of the batch (drop_bits.h)
     const int col = wn * 32 + l31;              // this lane's output feature inside a 64-wide block
     constexpr int KHM = MM ? 8 : 4;             // k values per lane half and k-block (see WFrag)
     const int KH = KHM * half;
@@ -521,6 +529,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
         const float* const e_g = KARG(FusedFwdP, e_g); const float* const e_b = KARG(FusedFwdP, e_b);
         int* const e_ids32 = KARG(FusedFwdP, e_ids32); const DropP e_drop = KARG(FusedFwdP, e_drop);
         float* const e_xhat = KARG(FusedFwdP, e_xhat); float* const e_X0 = KARG(FusedFwdP, e_X0); float* const e_rstd = KARG(FusedFwdP, e_rstd);
+        unsigned char* const e_bits = DBITS ? KARG(FusedFwdP, dbits) : nullptr;
         long src = 0;
         if (gp.table) {
             src = *(const AS_GLOBAL long long*)gp.cursor + b;
@@ -554,10 +563,12 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
             f32x4 y = {0, 0, 0, 0};
             if (ok) {
                 const f32x4 xh = dl * rs;
-                y = (eg * xh + eb) * drop_mult4(e_drop, dseed, (uint64_t)e >> 2);
+                const f32x4 em = drop_mult4(e_drop, dseed, (uint64_t)e >> 2);
+                y = (eg * xh + eb) * em;
                 ast4<BF>(e_xhat, e, xh);
                 ast4<BF>(e_X0, e, y);
                 if (c4 == 0) gst(e_rstd + tok0 + r, rs);
+                if (drop_bits_live(e_drop, e_bits)) drop_bits_st8(e_bits + drop_bits_hidden_byte(DB_EMBED, Ttok, tok0, 0), drop_bits_row_off(r, c4), drop_keep4(em));
             }
             st4(sX + r * FS + c4, y);
         }
@@ -592,6 +603,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
     const auto R2_wo = KARG(FusedFwdP, wo);
     const auto R2_wv = KARG(FusedFwdP, wv);
     const auto R2_xhat_f = KARG(FusedFwdP, xhat_f);
+    unsigned char* const R2_dbits = DBITS ? KARG(FusedFwdP, dbits) : nullptr;
     // ---- phases 1 || 2: FrequencyLayer (group 0)  ||  Q, K, V projections (group 1)
     {
         float* part = sH;                            // [16][4][2][64] = 8192 floats over sH + sE
@@ -681,10 +693,13 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
                 const bool ok = t < L;
                 const long e = (tok0 + t) * 64 + lc;
                 f32x4 v = {0, 0, 0, 0};
+                unsigned keep_f = 0;
                 if (ok) {
                     const f32x4 xv = ld4(sX + t * FS + lc);
                     const f32x4 low = lowpass_tab(sSpec, t, lc, L, cb, sTab);
-                    v = (low + b2 * (xv - low)) * drop_mult4(R2_drop_f, dseed, (uint64_t)e >> 2) + xv;
+                    const f32x4 fm = drop_mult4(R2_drop_f, dseed, (uint64_t)e >> 2);
+                    keep_f = drop_keep4(fm);
+                    v = (low + b2 * (xv - low)) * fm + xv;
                 }
                 const float mean = group_sum<16>(v.x + v.y + v.z + v.w) * (1.0f / 64.0f);
                 f32x4 dl = {0, 0, 0, 0};
@@ -699,6 +714,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
                     if (R2_dsp) gst4(R2_dsp + e, y);
                     if constexpr (FM) gst4(R2_hmix + e, y);          // alpha = 1: the block's mixed activation IS this output
                     if (lc == 0) gst(R2_rstd_f + (tok0 + t), rs);
+                    if (drop_bits_live(R2_drop_f, R2_dbits)) drop_bits_st8(R2_dbits + drop_bits_hidden_byte(DB_F, Ttok, tok0, 0), drop_bits_row_off(t, lc), keep_f);
                 }
                 st4((FM ? sH : sD) + t * FS + lc, y);
             }
@@ -728,6 +744,7 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
     const auto R3_ctx = KARG(FusedFwdP, ctx);
     const auto R3_drop_p = KARG(FusedFwdP, drop_p);
     const auto R3_probs = KARG(FusedFwdP, probs);
+    unsigned char* const R3_dbits = DBITS ? KARG(FusedFwdP, dbits) : nullptr;
     // ---- phase 3: attention, transposed: lane = query, registers = keys    src/model/_modules.py:118-135
     {
         const int nt = (L + 31) >> 5;                        // token tiles actually populated (1 or 2)
@@ -777,7 +794,8 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
             if (act) {
                 if (nt == 2) sum += sRed[(pair * 2 + (kt ^ 1)) * 64 + lane];
                 const float inv = 1.0f / sum;
-                // probabilities -> global (16 B per lane), then dropout in place
+                // probabilities -> global (16 B per lane), then dropout in place; the lane's 16 keep bits -> its word
+                unsigned keep_p = 0;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int key0 = 32 * kt + 8 * g + 4 * half;
@@ -787,10 +805,13 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
                         const long e = (((long)b * heads + head) * L + query) * Lp + key0;
                         ast4<BF>(R3_probs, e, p);
                         m = drop_mult4(R3_drop_p, dseed, (uint64_t)e >> 2);
+                        keep_p |= drop_keep4(m) << (4 * g);
                     }
                     p = p * m;
                     st[4 * g] = p.x; st[4 * g + 1] = p.y; st[4 * g + 2] = p.z; st[4 * g + 3] = p.w;
                 }
+                if (drop_bits_live(R3_drop_p, R3_dbits) && query < L)
+                    drop_bits_st16(R3_dbits + drop_bits_attn_base(Ttok) + 2 * drop_bits_attn_word(heads, b, head, 0, 0, 0), drop_bits_word_off(kt, half, query), keep_p);
                 // partial ctx^T over this wave's key tile  (P^T accumulators are the B operand as they stand)
                 float* dstT = kt == 0 ? sC : sE;
 #pragma unroll
@@ -883,7 +904,8 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
     }
     if constexpr (!FM) {
     lds_barrier();
-    ln_rows_64<true, BF>(lnA, sQ, sK, sX, R4_eps, sD, R4_alpha, R4_oma, tok0, L, sH, R4_hmix, R4_xhat_a, R4_rstd_a);
+    ln_rows_64<true, BF>(lnA, sQ, sK, sX, R4_eps, sD, R4_alpha, R4_oma, tok0, L, sH, R4_hmix, R4_xhat_a, R4_rstd_a, false, false,
+                         DBITS && R4_drop_o.thresh != 0 ? KARG(FusedFwdP, dbits) : nullptr, DB_O);
     lds_barrier();
     }
 
@@ -961,7 +983,8 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
     const auto R7_rstd_ff = KARG(FusedFwdP, rstd_ff);
     const auto R7_xhat_ff = KARG(FusedFwdP, xhat_ff);
     ln_rows_64<false, BF>(lnF, sX, sE, sH, R7_eps, nullptr, 0.f, 1.f, tok0, L,
-                          TAIL ? sD : nullptr, R7_Xout, R7_xhat_ff, R7_rstd_ff, KARG(FusedFwdP, xout_f32) != 0, TAIL);
+                          TAIL ? sD : nullptr, R7_Xout, R7_xhat_ff, R7_rstd_ff, KARG(FusedFwdP, xout_f32) != 0, TAIL,
+                          DBITS && R7_drop_ff.thresh != 0 ? KARG(FusedFwdP, dbits) : nullptr, DB_FF);
     STAMP(8);
     if constexpr (TAIL) {
         // x tile of the top block = sD; K, V tiles and the DFT partials alias the dead feed-forward tile; row vectors alias
@@ -1007,6 +1030,7 @@ struct FusedBwdP {
     const float* filter_cw; float* pcw;     // FM instantiation only: FMLPRec's complex_weight [cb][64][2]; per-sequence d(complex_weight) [B][cb][64][2]
     const float* e_dx_extra;      // bottom block, optional: an upstream gradient of the EMBEDDING output itself (fp32 [B, L, 64]),
                                   // added to dX before the embedding LayerNorm backward (forward(all_sequence_output=True)[0])
+    const unsigned char* dbits;   // DB instantiations: the keep bits this layer's forward left (drop_bits.h)
 };
 
 
@@ -1038,20 +1062,22 @@ __device__ __forceinline__ void seq_partials_64(const f32x4 (&v)[N], float* cons
 #pragma unroll
     for (int i = 0; i < N; ++i) st4(red[i] + lr * 64 + lc, v[i]);
     lds_barrier();
-    const int i = threadIdx.x >> 6, c = threadIdx.x & 63;
-    if (i < N) {
-        const float* r = red[0];
-        float* d = dst[0];
+    // wave k sums vector k.  The wave number is uniform: one copy of the loop per vector behind a scalar branch, every
+    // red[k] / dst[k] a compile-time pick (a per-lane pick among the array's elements is lowered to an indexed stack array:
+    // scratch stores and a dependent scratch load on the kernel's critical path)
+    const int i = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), c = threadIdx.x & 63;
 #pragma unroll
-        for (int k = 1; k < N; ++k) if (i == k) { r = red[k]; d = dst[k]; }
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        for (int g = 0; g < ng; g += 4) {
-            s0 += r[g * 64 + c]; s1 += r[(g + 1) * 64 + c]; s2 += r[(g + 2) * 64 + c]; s3 += r[(g + 3) * 64 + c];
+    for (int k = 0; k < N; ++k)
+        if (i == k) {
+            const float* r = red[k];
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+            for (int g = 0; g < ng; g += 4) {
+                s0 += r[g * 64 + c]; s1 += r[(g + 1) * 64 + c]; s2 += r[(g + 2) * 64 + c]; s3 += r[(g + 3) * 64 + c];
+            }
+            float sum = (s0 + s1) + (s2 + s3);
+            if (k == 0) { if (mul0) sum *= gld(mul0 + c); sum *= scale0; }
+            gst(dst[k] + c, sum);
         }
-        float sum = (s0 + s1) + (s2 + s3);
-        if (i == 0) { if (mul0) sum *= gld(mul0 + c); sum *= scale0; }
-        gst(d + c, sum);
-    }
 }
 
 // Backward: 8 waves = 2 groups of 4, two waves per SIMD.  dU splits its four 64-wide blocks across the groups;
@@ -1061,7 +1087,8 @@ __device__ __forceinline__ void seq_partials_64(const f32x4 (&v)[N], float* cons
 // HEADP = TopBwdP: the block above is the one-row top block of the loss path; its backward runs first, inside this
 // kernel, on waves 0..3 (its dX tile stays in LDS), while waves 4..7 stage this block's gelu' tile.
 // IMG: wq .. w2 point at the weights' T images (wimage.h); the head (TopBwdP) keeps reading the masters.
-template <int DH, bool BF, class HEADP, bool X3 = false, bool FM = false, bool IMG = false>
+// DB: the dropout multipliers come from the keep bits the forward left (drop_bits.h), not from a second Philox evaluation.
+template <int DH, bool BF, class HEADP, bool X3 = false, bool FM = false, bool IMG = false, bool DB = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
 #define PTYPE FusedBwdP
@@ -1071,6 +1098,8 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
     // FM: backward of the sibling model FMLPRec's block (see the forward): stages A1..A3 (feed-forward), then its own tail
     static_assert(!FM || (!BF && !X3 && !IsTail<HEADP>::value), "the FMLPRec block runs in fp32, without a top-block head");
     constexpr bool HEAD = IsTail<HEADP>::value;
+    static_assert(!DB || (!X3 && !FM), "keep bits are left by the BSARec block's forward in fp32 / bf16 storage");
+    constexpr bool DBITS = DB;
     constexpr unsigned KOFF = (unsigned)((sizeof(FusedBwdP) + 7) & ~(size_t)7);     // kernarg offset of H_unused
     const auto R0_L = KARG(FusedBwdP, L);
     const auto R0_Lp = KARG(FusedBwdP, Lp);
@@ -1097,6 +1126,7 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
     const int L = R0_L, Lp = R0_Lp, heads = R0_heads, cb = R0_cb;
     const int b = blockIdx.x;
     const long tok0 = (long)b * L;
+    const long Ttok = (long)gridDim.x * L;          // tokens of the batch (drop_bits.h)
     const int col = wn * 32 + l31;
     constexpr int KHM = MM ? 8 : 4;
     const int KH = KHM * half;
@@ -1111,12 +1141,12 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
     TopBwdRegs HR;
     TopBwdHelpRegs HH;
     if constexpr (HEAD) {
-        if (wave == 0) top_bwd_prefetch<BF, KOFF>(HR);
+        if (wave == 0) top_bwd_prefetch<BF, KOFF, DB>(HR);
         else if (wave < 4) {
             // wave 3 (the one without a dropout multiplier to evaluate in the head's first step) builds the twiddle table, ahead
             // of its tile request: a load behind 16 KB of tile rows would not return for thousands of cycles
             if (wave == 3) build_twiddle_table(KARG(FusedBwdP, tw), L, cb, sTab, 192, 64);
-            top_bwd_prefetch_tile<BF, KOFF>(HR);
+            top_bwd_prefetch_tile<BF, KOFF, DB>(HR);
         } else top_bwd_help_prefetch<BF, KOFF>(HH);
     }
     const DropSeed dseed = drop_seed(KARG(FusedBwdP, drop_f));
@@ -1134,6 +1164,7 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
     const auto R1_tw = KARG(FusedBwdP, tw);
     const auto R1_w2 = KARG(FusedBwdP, w2);
     const auto R1_xhat_ff = KARG(FusedBwdP, xhat_ff);
+    const unsigned char* const R1_dbits = DBITS ? KARG(FusedBwdP, dbits) : nullptr;
     if constexpr (!FM && !HEAD) build_twiddle_table(R1_tw, L, cb, sTab);      // (FM: all L/2 + 1 bins do not fit here; built in its tail)
     if constexpr (HEAD) {
         // (no barrier here: the head first reads the twiddle table after its third barrier, and every wave has written its
@@ -1141,7 +1172,7 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
         if (wave < 4) {
             // top block's tiles alias T6..T8, its row vectors T0, its dX tile T1 (= this block's dY); T2..T5 stay free for
             // the gelu' tile the other waves are staging
-            top_bwd_body<DH, BF, KOFF, true>(HR, dseed, sG, sdF, sPm, sTab, sAcc, sT);
+            top_bwd_body<DH, BF, KOFF, true, DB>(HR, dseed, sG, sdF, sPm, sTab, sAcc, sT);
         } else {
             top_bwd_help_a<BF, KOFF>(HH, sAcc);
             // this block's gelu' tile trickles into registers during the head's narrow steps (top_bwd_help_b) and is stored
@@ -1164,11 +1195,13 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
     const f32x4 g = gld4(R1_ff_g + lc);
     f32x4 dy[2], xh[2];
     float rs[2];
+    unsigned kb_ff[2];                              // the keep bits of drop_ff, requested with the rows they belong to
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int r = 32 * i + lr;
         const long e = (tok0 + r) * 64 + lc;
         dy[i] = f32x4{0, 0, 0, 0}; xh[i] = dy[i]; rs[i] = 0.f;
+        kb_ff[i] = drop_bits_request<DBITS>(R1_drop_ff, R1_dbits + drop_bits_hidden_byte(DB_FF, Ttok, tok0, 0), drop_bits_row_off(min(r, L - 1), lc));
         if (R1_dh_slabs) {                              // only the last position feeds the loss (bsarec.py:32)
             if (r < L) {
                 if (r == L - 1)
@@ -1214,7 +1247,7 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
             const f32x4 dz = rs[i] * (gg - m1 - xh[i] * m2);
             sg += dy[i] * xh[i]; sb += dy[i];
             f32x4 dt = {0, 0, 0, 0};
-            if (ok) { dt = dz * drop_mult4(R1_drop_ff, dseed, (uint64_t)e >> 2); ast4<BF>(R1_dT, e, dt); }
+            if (ok) { dt = dz * drop_mult4_saved<DBITS>(R1_drop_ff, dseed, (uint64_t)e >> 2, kb_ff[i]); ast4<BF>(R1_dT, e, dt); }
             st4(sAcc + r * FS + lc, dz);
             st4(sT + r * FS + lc, dt);
         }
@@ -1300,10 +1333,13 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
     STAMP(2);
     const auto R3_w1 = KARG(FusedBwdP, w1);
     const auto R3_wo = KARG(FusedBwdP, wo);
+    const unsigned char* const R3_dbits = DBITS ? KARG(FusedBwdP, dbits) : nullptr;
+    const DropP R3_drop_o = KARG(FusedBwdP, drop_o), R3_drop_f = KARG(FusedBwdP, drop_f);
     // ---- stage A3: dH = dU . W1, K split: group g owns inner units [128g, 128g+128) -> partial tiles sG / sdF
     WFrag<MM, 32> wO;
     f32x4 pq[2], pk[2], pv[2], xa[2], xf[2];                 // stage B1's operands, prefetched below
     float ra[2], rf[2];
+    unsigned kb_o[2] = {0u, 0u}, kb_f[2] = {0u, 0u};         // ... and the keep bits of its two dropout sites
     {
         f32x16 acc;
 #pragma unroll
@@ -1323,6 +1359,8 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
             }
             xf[i] = ald4<BF>(KARG(FusedBwdP, xhat_f), ec);
             rf[i] = gld(KARG(FusedBwdP, rstd_f) + tok0 + min(r, L - 1));
+            kb_o[i] = drop_bits_request<DBITS>(R3_drop_o, R3_dbits + drop_bits_hidden_byte(DB_O, Ttok, tok0, 0), drop_bits_row_off(min(r, L - 1), lc));
+            kb_f[i] = drop_bits_request<DBITS>(R3_drop_f, R3_dbits + drop_bits_hidden_byte(DB_F, Ttok, tok0, 0), drop_bits_row_off(min(r, L - 1), lc));
         }
         mma_w<MM, 64>(sa, wA, acc);                          // chunk 0 of this group sits in wA
         mma_w<MM, 64>(sa + 64, wB, acc);
@@ -1533,8 +1571,8 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
             sga += dya * xa[i]; sba += dya; sgf += dyf * xf[i]; sbf += dyf;
             f32x4 dO = {0, 0, 0, 0}, dF = dO;
             if (ok) {
-                dO = dza * drop_mult4(R4_drop_o, dseed, (uint64_t)e >> 2);
-                dF = dzf * drop_mult4(R4_drop_f, dseed, (uint64_t)e >> 2);
+                dO = dza * drop_mult4_saved<DBITS>(R4_drop_o, dseed, (uint64_t)e >> 2, kb_o[i]);
+                dF = dzf * drop_mult4_saved<DBITS>(R4_drop_f, dseed, (uint64_t)e >> 2, kb_f[i]);
                 ast4<BF>(R4_dO, e, dO);
             }
             st4(sAcc + r * FS + lc, dza + dzf);
@@ -1575,6 +1613,7 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
     const auto R6_drop_p = KARG(FusedBwdP, drop_p);
     const auto R6_dv = KARG(FusedBwdP, dv);
     const auto R6_probs = KARG(FusedBwdP, probs);
+    const unsigned char* const R6_dbits = DBITS ? KARG(FusedBwdP, dbits) : nullptr;
     // ---- stage C: attention backward, one head at a time; lane = query, registers = keys
     {
         const int nt = (L + 31) >> 5;
@@ -1587,18 +1626,31 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
             const int qt = (wave >> 1) & 1, kt = wave & 1;
             const int query = 32 * qt + l31;
             const bool c1 = wave < 4;
-            f32x4 pp[4], mm[4];
+            f32x4 pp[4];
             f32x16 da;
             float delta = 0.f;
             if (c1) {
+                // DBITS: the multipliers are the lane's 16 keep bits in ONE register (drop_bits.h; the same lane wrote the word
+                // in the forward's phase 3), requested with the probabilities and expanded where they are used; else four
+                // Philox quads held across the product
+                constexpr bool SAVED = DBITS;
+                f32x4 mm[SAVED ? 1 : 4];
+                unsigned kw = 0;
+                if constexpr (SAVED) {
+                    if (R6_drop_p.thresh != 0 && query < L)      // (no word was written for a padded query)
+                        kw = drop_bits_ld16(R6_dbits + drop_bits_attn_base(Ttok) + 2 * drop_bits_attn_word(heads, b, head, 0, 0, 0),
+                                            drop_bits_word_off(kt, half, query));
+                }
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int key0 = 32 * kt + 8 * g + 4 * half;
-                    pp[g] = f32x4{0, 0, 0, 0}; mm[g] = pp[g];
+                    pp[g] = f32x4{0, 0, 0, 0};
+                    if constexpr (!SAVED) mm[g] = pp[g];
                     if (query < L && key0 < Lp) {
                         const long e = (((long)b * heads + head) * L + query) * Lp + key0;
                         pp[g] = ald4<BF>(R6_probs, e);
-                        mm[g] = drop_mult4(R6_drop_p, dseed, (uint64_t)e >> 2);
+                        if constexpr (!SAVED) mm[g] = drop_mult4(R6_drop_p, dseed, (uint64_t)e >> 2);
+                        else if (R6_drop_p.thresh == 0) kw |= 0xFu << (4 * g);     // no dropout: every element of the group is kept
                     }
                 }
 #pragma unroll
@@ -1609,10 +1661,13 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
                 for (int g = 0; g < 4; ++g)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float dA = da[4 * g + j] * mm[g][j];
+                        float m;
+                        if constexpr (SAVED) m = (kw >> (4 * g + j)) & 1u ? R6_drop_p.scale : 0.f;   // (bits past Lp were never set)
+                        else m = mm[g][j];
+                        const float dA = da[4 * g + j] * m;
                         delta += dA * pp[g][j];
                         da[4 * g + j] = dA;
-                        sPm[(32 * kt + 8 * g + 4 * half + j) * FS + query] = pp[g][j] * mm[g][j];
+                        sPm[(32 * kt + 8 * g + 4 * half + j) * FS + query] = pp[g][j] * m;
                     }
                 delta = xor32_sum(delta);
                 sRed[(qt * 2 + kt) * 64 + lane] = delta;
@@ -1759,20 +1814,29 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
         float* const e_dz = KARG(FusedBwdP, e_dz);
         const float* const e_dx_extra = KARG(FusedBwdP, e_dx_extra);
         f32x4 g0 = {0, 0, 0, 0}, e_xh[2], e_ex[2], e_dm[2];
-        float e_rs[2];
+        float e_rs[2], e_scale = 1.f;
+        unsigned kb_e[2] = {0u, 0u};                    // DBITS: keep bits of the embedding dropout, requested here, expanded at their use
+        bool e_nodrop = true;
 #pragma unroll
         for (int i = 0; i < 2; ++i) { e_xh[i] = f32x4{0, 0, 0, 0}; e_ex[i] = e_xh[i]; e_dm[i] = e_xh[i]; e_rs[i] = 0.f; }
         if (e_dz || e_dx_extra) {
             const float* const e_xhat = KARG(FusedBwdP, e_xhat);
             const float* const e_rstd = KARG(FusedBwdP, e_rstd);
             const DropP e_drop = KARG(FusedBwdP, e_drop);
+            const unsigned char* const e_bits = DBITS ? KARG(FusedBwdP, dbits) : nullptr;
+            e_nodrop = e_drop.thresh == 0; e_scale = e_drop.scale;
             if (e_dz) g0 = gld4(KARG(FusedBwdP, e_g) + lc);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int t = 32 * i + lr;
                 const long e = (tok0 + min(t, L - 1)) * 64 + lc;
                 if (e_dx_extra) e_ex[i] = gld4(e_dx_extra + e);
-                if (e_dz) { e_xh[i] = ald4<BF>(e_xhat, e); e_rs[i] = gld(e_rstd + tok0 + min(t, L - 1)); e_dm[i] = drop_mult4(e_drop, dseed, (uint64_t)e >> 2); }
+                if (e_dz) {
+                    e_xh[i] = ald4<BF>(e_xhat, e); e_rs[i] = gld(e_rstd + tok0 + min(t, L - 1));
+                    if constexpr (DBITS)
+                        kb_e[i] = drop_bits_request<DBITS>(e_drop, e_bits + drop_bits_hidden_byte(DB_EMBED, Ttok, tok0, 0), drop_bits_row_off(min(t, L - 1), lc));
+                    else e_dm[i] = drop_mult4(e_drop, dseed, (uint64_t)e >> 2);
+                }
             }
         }
 #pragma unroll
@@ -1841,7 +1905,11 @@ fused_layer_bwd_kernel(const FusedBwdP P_unused, const HEADP H_unused) {
                 dx = ld4(sG + t * FS + lc) + b2 * df + lowg;
                 if (e_dx_extra) dx += e_ex[i];
                 sb += df * (xv - lowx);
-                if (e_dz) { xh = e_xh[i]; rs = e_rs[i]; dx = dx * e_dm[i]; }
+                if (e_dz) {
+                    xh = e_xh[i]; rs = e_rs[i];
+                    if constexpr (DBITS) dx = dx * drop_expand4(e_nodrop ? 0xFu : kb_e[i], e_scale);
+                    else dx = dx * e_dm[i];
+                }
                 else ast4<BF>(R8_dX, e, dx);
             }
             if (e_dz) {                                     // embedding LayerNorm backward on the finished row

@@ -27,6 +27,7 @@ struct TopFwdP {
     // block kernel reads its weights): the bf16 shadow (BF instantiation), or the F images of wimage.h (fused tail with
     // IMG); the one-row vector products keep the fp32 masters
     const float *wk_sh, *wv_sh;
+    unsigned char* dbits;          // this layer's keep-bits buffer (drop_bits.h): row L-1 of its sites; null: the plan keeps none
 };
 
 // keep-mask x scale of ONE element (common.h: DropSeed, drop_mult4)
@@ -37,6 +38,42 @@ __device__ __forceinline__ float drop_mult1(const DropP& d, const DropSeed& sd, 
     const int j = (int)(e & 3);
     const uint32_t r = j == 0 ? w.x : j == 1 ? w.y : j == 2 ? w.z : w.w;
     return r >= d.thresh ? d.scale : 0.f;
+}
+
+// Keep bits of the one-row block (drop_bits.h): row L-1 of a hidden-size site held one column per lane of a wave, and the
+// attention row of the last query held one key per lane.  The wave's ballot is the row; lanes 0..15 store its 16 bytes,
+// lanes 0..3 the attention row's four words (kt, half) = (lane >> 1, lane & 1): nibbles 8 kt + 2 g + half of the ballot.
+// Called by whole waves (wave-uniform branches only).
+__device__ __forceinline__ void top_keep_row(const DropP& d, unsigned char* bits, int slot, long T, long tok, float mult) {
+    if (!drop_bits_live(d, bits)) return;
+    const unsigned long long k = __ballot(mult != 0.f);
+    const int lane = threadIdx.x & 63;
+    if (lane < 16) drop_bits_st8(bits + drop_bits_hidden_byte(slot, T, tok, 0), (unsigned)lane, (unsigned)(k >> (4 * lane)) & 0xFu);
+}
+__device__ __forceinline__ void top_keep_attn(const DropP& d, unsigned char* bits, long T, int heads, long b, int head, int query, int Lp,
+                                              float mult) {
+    if (!drop_bits_live(d, bits)) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long k = __ballot(mult != 0.f && lane < Lp);
+    if (lane < 4) {
+        unsigned w = 0;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) w |= ((unsigned)(k >> (4 * (8 * (lane >> 1) + 2 * g + (lane & 1)))) & 0xFu) << (4 * g);
+        drop_bits_st16(bits + drop_bits_attn_base(T) + 2 * drop_bits_attn_word(heads, b, head, 0, 0, 0),
+                       drop_bits_word_off(lane >> 1, lane & 1, query), w);
+    }
+}
+// ... and the backward's side: the byte of column c's quad in row `tok`, the word of key `key` of the last query
+__device__ __forceinline__ unsigned top_row_request(const unsigned char* bits, int slot, long T, long tok, int c) {
+    return drop_bits_ld8(bits + drop_bits_hidden_byte(slot, T, tok, 0), (unsigned)(c >> 2));
+}
+__device__ __forceinline__ unsigned top_attn_request(const unsigned char* bits, long T, int heads, long b, int head, int query, int key) {
+    return drop_bits_ld16(bits + drop_bits_attn_base(T) + 2 * drop_bits_attn_word(heads, b, head, 0, 0, 0),
+                          drop_bits_word_off(key >> 5, (key >> 2) & 1, query));
+}
+__device__ __forceinline__ float top_row_mult(const DropP& d, unsigned keep, int c) { return (keep >> (c & 3)) & 1u ? d.scale : 0.f; }
+__device__ __forceinline__ float top_attn_mult(const DropP& d, unsigned word, int key) {
+    return (word >> (4 * ((key >> 3) & 3) + (key & 3))) & 1u ? d.scale : 0.f;
 }
 
 // y[n] = sum_k W[n][k] x[k]  (nn.Linear forward, W row-major [*][ldw]); KS adjacent lanes share one output.
@@ -170,6 +207,8 @@ __device__ __forceinline__ void top_fwd_rest(const TopFwdRegs<BF>& R, const Drop
     float* const k_low = TP(low); const DropP d_f = TP(drop_f); const float k_eps = TP(eps);
     float* const k_xhat_f = TP(xhat_f); float* const k_rstd_f = TP(rstd_f);
     const float* const pW1 = TP(w1); const float* const pW2 = TP(w2);
+    unsigned char* const dbits = TP(dbits);
+    const long Ttok = (long)gridDim.x * L;
 
     // ---- K, V projections of all rows (MFMA; HELPED: by waves 4..7, top_fwd_help), spectrum of x (VALU)
     if constexpr (!HELPED) {
@@ -197,7 +236,11 @@ __device__ __forceinline__ void top_fwd_rest(const TopFwdRegs<BF>& R, const Drop
         //   low[L-1][c] = sum_t P[t] x[t][c],  P[t] = (1/L) sum_k w_k cos(2 pi k (t - (L-1)) / L)   (w_0 = w_{L/2} = 1, else 2)
         // (the spectrum + synthesis of dft_spectrum_tab / lowpass_tab, contracted over the bins first).  Wave w takes rows
         // [16 w, 16 w + 16): lanes 0..15 evaluate P, each lane = one column sums its 16 rows with P read lane by lane.
-        if (wave == 1) sMul[lane] = drop_mult1(d_f, dseed, (uint64_t)(el + lane));      // wave 0 needs this one first
+        if (wave == 1) {                                                                 // wave 0 needs this one first
+            const float m = drop_mult1(d_f, dseed, (uint64_t)(el + lane));
+            sMul[lane] = m;
+            top_keep_row(d_f, dbits, DB_F, Ttok, tok0 + tl, m);
+        }
         const int t = 16 * wave + (lane & 15);
         float pl = 0.f;
         if (t < L)
@@ -245,7 +288,9 @@ __device__ __forceinline__ void top_fwd_rest(const TopFwdRegs<BF>& R, const Drop
         gst(k_low + el + c, low);
         const float bt = R.c_beta;
         const float f = low + bt * bt * (xv - low);
-        const float v = f * (HELPED ? sMul[c] : drop_mult1(d_f, dseed, (uint64_t)(el + c))) + xv;
+        const float m_f = HELPED ? sMul[c] : drop_mult1(d_f, dseed, (uint64_t)(el + c));
+        if constexpr (!HELPED) top_keep_row(d_f, dbits, DB_F, Ttok, tok0 + tl, m_f);
+        const float v = f * m_f + xv;
         float xh, rs;
         ln_row(v, k_eps, xh, rs);
         ast<BF>(k_xhat_f, el + c, xh);
@@ -257,11 +302,15 @@ __device__ __forceinline__ void top_fwd_rest(const TopFwdRegs<BF>& R, const Drop
         // dense output's and the attention rows of heads 0, 2; wave 3 the feed-forward output's and heads 1, 3
         if (wave >= 2) {
             const DropP dd = wave == 2 ? TP(drop_o) : TP(drop_ff);
-            sMul[(wave - 1) * 64 + lane] = drop_mult1(dd, dseed, (uint64_t)(el + lane));
+            const float m = drop_mult1(dd, dseed, (uint64_t)(el + lane));
+            sMul[(wave - 1) * 64 + lane] = m;
+            top_keep_row(dd, dbits, wave == 2 ? DB_O : DB_FF, Ttok, tok0 + tl, m);
             const DropP dp = TP(drop_p);
             for (int h = wave - 2; h < heads; h += 2) {
                 const long pe = (((long)b * heads + h) * L + tl) * Lp;
-                sMp[h * 64 + lane] = drop_mult1(dp, dseed, (uint64_t)(pe + lane));
+                const float mp = drop_mult1(dp, dseed, (uint64_t)(pe + lane));
+                sMp[h * 64 + lane] = mp;
+                top_keep_attn(dp, dbits, Ttok, heads, b, h, tl, Lp, mp);
             }
         }
     }
@@ -295,7 +344,9 @@ __device__ __forceinline__ void top_fwd_rest(const TopFwdRegs<BF>& R, const Drop
         const float p = e / group_sum<64>(e);
         const long pe = (((long)b * heads + head) * L + tl) * Lp;
         if (key < Lp) ast<BF>(k_probs, pe + key, p);
-        sPd[head * 64 + key] = key < L ? p * (HELPED ? sMp[head * 64 + key] : drop_mult1(d_p, dseed, (uint64_t)(pe + key))) : 0.f;
+        const float m_p = HELPED ? sMp[head * 64 + key] : drop_mult1(d_p, dseed, (uint64_t)(pe + key));
+        if constexpr (!HELPED) top_keep_attn(d_p, dbits, Ttok, heads, b, head, tl, Lp, m_p);
+        sPd[head * 64 + key] = key < L ? p * m_p : 0.f;
     }
     const DropP d_o = TP(drop_o); float* const k_xhat_a = TP(xhat_a); float* const k_rstd_a = TP(rstd_a);
     const float k_alpha = TP(alpha), k_oma = TP(oma); float* const k_hmix = TP(hmix); float* const k_u = TP(u);
@@ -324,7 +375,9 @@ __device__ __forceinline__ void top_fwd_rest(const TopFwdRegs<BF>& R, const Drop
     if constexpr (!HELPED) { if (wave != 0) gemv_rows_load<256, 4>(pW2, 256, on, osl, w2r); }
     if (wave == 0) {
         const int c = lane;
-        const float v = sG[c] * (HELPED ? sMul[64 + c] : drop_mult1(d_o, dseed, (uint64_t)(el + c))) + sX[tl * FS + c];
+        const float m_o = HELPED ? sMul[64 + c] : drop_mult1(d_o, dseed, (uint64_t)(el + c));
+        if constexpr (!HELPED) top_keep_row(d_o, dbits, DB_O, Ttok, tok0 + tl, m_o);
+        const float v = sG[c] * m_o + sX[tl * FS + c];
         float xh, rs;
         ln_row(v, k_eps, xh, rs);
         ast<BF>(k_xhat_a, el + c, xh);
@@ -355,7 +408,9 @@ __device__ __forceinline__ void top_fwd_rest(const TopFwdRegs<BF>& R, const Drop
     TSTAMP(8);
     if (wave == 0) {
         const int c = lane;
-        const float v = sQ[c] * (HELPED ? sMul[128 + c] : drop_mult1(d_ff, dseed, (uint64_t)(el + c))) + sHm[c];
+        const float m_ff = HELPED ? sMul[128 + c] : drop_mult1(d_ff, dseed, (uint64_t)(el + c));
+        if constexpr (!HELPED) top_keep_row(d_ff, dbits, DB_FF, Ttok, tok0 + tl, m_ff);
+        const float v = sQ[c] * m_ff + sHm[c];
         float xh, rs;
         ln_row(v, k_eps, xh, rs);
         ast<BF>(k_xhat_ff, el + c, xh);
@@ -538,6 +593,7 @@ struct TopBwdP {
     float alpha, oma;
     DropP drop_f, drop_p, drop_o, drop_ff;
     long long* stamps;
+    const unsigned char* dbits;    // DB instantiations: the keep bits the forward left (drop_bits.h)
 };
 
 // LayerNorm backward of one row, one column per lane: returns dz; g = dy * gamma
@@ -561,7 +617,7 @@ static_assert(TOP_BWD_BARRIERS == 11, "barriers of top_bwd_body (fused_layer.h h
 // What the chain that opens the top block's backward needs from memory (wave 0, one column per lane): requested at the
 // very top of the kernel so that the ~4 k cycles these loads take (the slabs were written by the previous kernel, on other
 // XCDs) pass under the twiddle-table build instead of in front of the first LayerNorm backward.
-template <bool BF, unsigned KOFF>
+template <bool BF, unsigned KOFF, bool DB>
 __device__ __forceinline__ void top_bwd_prefetch(TopBwdRegs& R) {          // wave 0 only
     const int c = threadIdx.x & 63;
     const int L = TB(L), b = blockIdx.x, tl = L - 1;
@@ -589,16 +645,32 @@ __device__ __forceinline__ void top_bwd_prefetch(TopBwdRegs& R) {          // wa
     R.q_l = ald<BF>(k_q, el + c);
     const int heads = TB(heads), Lp = TB(Lp);
     R.p_pre = c < L ? ald<BF>(TB(probs), (((long)b * heads + 0) * L + tl) * Lp + c) : 0.f;
+    // the keep bits this wave's multipliers come from (drop_bits.h): drop_ff of row L-1, the attention row of head 0
+    R.kb = 0; R.kw = 0;
+    if constexpr (DB) {
+        const unsigned char* const bits = TB(dbits);
+        const long Ttok = (long)gridDim.x * L;
+        if (TB(drop_ff).thresh != 0) R.kb = top_row_request(bits, DB_FF, Ttok, tok0 + tl, c);
+        if (TB(drop_p).thresh != 0) R.kw = top_attn_request(bits, Ttok, heads, b, 0, tl, c);
+    }
 }
 // waves 1..3 of the fused head: wave 1 the x tile, wave 2 k, wave 3 v (16 loads a lane; rows past L re-read row L-1 and are
 // zeroed at the store), and the probability row of head `wave` where there is one
-template <bool BF, unsigned KOFF>
+template <bool BF, unsigned KOFF, bool DB>
 __device__ __forceinline__ void top_bwd_prefetch_tile(TopBwdRegs& R) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int L = TB(L), Lp = TB(Lp), heads = TB(heads), b = blockIdx.x, tl = L - 1;
     const long tok0 = (long)b * L;
     const float* const src = wave == 1 ? TB(X) : wave == 2 ? TB(k) : TB(v);
     R.p_pre = (wave < heads && lane < L) ? ald<BF>(TB(probs), (((long)b * heads + wave) * L + tl) * Lp + lane) : 0.f;
+    // keep bits ahead of the tile (loads return in issue order): wave 1 drop_o, wave 2 drop_f of row L-1; head `wave`'s attention row
+    R.kb = 0; R.kw = 0;
+    if constexpr (DB) {
+        const unsigned char* const bits = TB(dbits);
+        const long Ttok = (long)gridDim.x * L;
+        if (wave < 3 && (wave == 1 ? TB(drop_o) : TB(drop_f)).thresh != 0) R.kb = top_row_request(bits, wave == 1 ? DB_O : DB_F, Ttok, tok0 + tl, lane);
+        if (wave < heads && TB(drop_p).thresh != 0) R.kw = top_attn_request(bits, Ttok, heads, b, wave, tl, lane);
+    }
 #pragma unroll
     for (int p = 0; p < 16; ++p) {
         const int idx = lane + p * 64, r = idx >> 4, c4 = (idx & 15) << 2;
@@ -704,7 +776,7 @@ __device__ __forceinline__ void top_bwd_help_b(const float* sX, float* sVec, con
     lds_barrier();
 }
 
-template <int DH, bool BF, unsigned KOFF, bool HELPED>
+template <int DH, bool BF, unsigned KOFF, bool HELPED, bool DB>
 __device__ __forceinline__ void top_bwd_body(const TopBwdRegs& R, const DropSeed& dseed, float* sX, float* sK, float* sV, const float* sTab,
                                              float* sVec, float* sDX) {
     float* sDT = sVec;            // 64   dT2 (grad of the dense_2 output)
@@ -747,6 +819,16 @@ __device__ __forceinline__ void top_bwd_body(const TopBwdRegs& R, const DropSeed
     const float* const pX = TB(X); const float* const pK = TB(k); const float* const pV = TB(v);
     const float* const pW1 = TB(w1); const float* const pW2 = TB(w2); const float* const pU = TB(u);
     const float* const pWo = TB(wo); const float* const pWq = TB(wq); const float* const pWk = TB(wk); const float* const pWv = TB(wv);
+    const unsigned char* const dbits = DB ? TB(dbits) : nullptr;
+    const long Ttok = (long)gridDim.x * L;
+    // a multiplier of row L-1: DB: from its keep bits (requested with the kernel's first loads where there are such, R.kb), else Philox
+    auto row_mult = [&](const DropP& d, int slot) {
+        if constexpr (!DB) return drop_mult1(d, dseed, (uint64_t)(el + c));
+        else {
+            if (d.thresh == 0) return d.scale;
+            return top_row_mult(d, (HELPED || wave == 0) ? R.kb : top_row_request(dbits, slot, Ttok, tok0 + tl, c), c);
+        }
+    };
     auto weight_loads = [&]() {                  // (HELPED: waves 4..7 hold these columns)
         if constexpr (!HELPED) {
             u_mine = ald<BF>(pU, (tok0 + tl) * 256 + tid);
@@ -767,8 +849,8 @@ __device__ __forceinline__ void top_bwd_body(const TopBwdRegs& R, const DropSeed
         if constexpr (!HELPED) { weight_loads(); tile_loads(); }
         // the other two dropout multipliers of row L-1 (Philox, independent of the data): waves 1 and 2 have nothing else to do
         // in this stage, wave 0 picks them up in the LayerNorm step (sDH / sDQ are free until then)
-        if (wave == 1) { const DropP d_o = TB(drop_o); sDH[c] = drop_mult1(d_o, dseed, (uint64_t)(el + c)); }
-        if (wave == 2) { const DropP d_f = TB(drop_f); sDQ[c] = drop_mult1(d_f, dseed, (uint64_t)(el + c)); }
+        if (wave == 1) { const DropP d_o = TB(drop_o); sDH[c] = row_mult(d_o, DB_O); }
+        if (wave == 2) { const DropP d_f = TB(drop_f); sDQ[c] = row_mult(d_f, DB_F); }
     }
     if (wave == 0) {
         // upstream gradient of the last row = sum of the logits backward's split-K slabs (requested by top_bwd_prefetch)
@@ -776,7 +858,7 @@ __device__ __forceinline__ void top_bwd_body(const TopBwdRegs& R, const DropSeed
         const DropP d_ff = TB(drop_ff);
         float* const k_pg_ff = TB(pg_ff); float* const k_pb_ff = TB(pb_ff); float* const k_dT = TB(dT);
         xa = R.xa; xf = R.xf; g_a = R.g_a; g_f = R.g_f; rs_a = R.rs_a; rs_f = R.rs_f; bt = R.bt; low_l = R.low_l; x_l = R.x_l;
-        const float m_ff = drop_mult1(d_ff, dseed, (uint64_t)(el + c));        // under what is left of the loads' latency
+        const float m_ff = row_mult(d_ff, DB_FF);                              // under what is left of the loads' latency
         asm volatile("" :: "v"(m_ff));
         __builtin_amdgcn_sched_barrier(0);
         float part[4] = {0.f, 0.f, 0.f, 0.f};
@@ -900,7 +982,9 @@ __device__ __forceinline__ void top_bwd_body(const TopBwdRegs& R, const DropSeed
             }
             const long pe = (((long)b * heads + head) * L + tl) * Lp + key;
             p = HELPED ? R.p_pre : ald<BF>(k_probs, pe);
-            mp = drop_mult1(d_p, dseed, (uint64_t)pe);
+            if constexpr (!DB) mp = drop_mult1(d_p, dseed, (uint64_t)pe);
+            else if (d_p.thresh == 0) mp = d_p.scale;
+            else mp = top_attn_mult(d_p, (HELPED || wave == 0) ? R.kw : top_attn_request(dbits, Ttok, heads, b, head, tl, key), key);
         }
         const float dp = dpd * mp;
         const float delta = group_sum<64>(p * dp);
@@ -961,7 +1045,7 @@ __device__ __forceinline__ void top_bwd_body(const TopBwdRegs& R, const DropSeed
     BSTAMP(15);
 }
 
-template <int DH, bool BF>
+template <int DH, bool BF, bool DB = false>
 __global__ void __launch_bounds__(256)
 top_bwd_kernel(const TopBwdP P_unused) {
     constexpr unsigned KOFF = 0;
@@ -974,11 +1058,11 @@ top_bwd_kernel(const TopBwdP P_unused) {
     float* sVec = sTab + FUSED_MAX_CB * 128;
     BSTAMP(0);
     TopBwdRegs R;
-    if (threadIdx.x < 64) top_bwd_prefetch<BF, KOFF>(R);
+    if (threadIdx.x < 64) top_bwd_prefetch<BF, KOFF, DB>(R);
     const DropSeed dseed = drop_seed(TB(drop_f));
     build_twiddle_table(TB(tw), TB(L), TB(cb), sTab);
     lds_barrier();
-    top_bwd_body<DH, BF, KOFF, false>(R, dseed, sX, sK, sV, sTab, sVec, nullptr);
+    top_bwd_body<DH, BF, KOFF, false, DB>(R, dseed, sX, sK, sV, sTab, sVec, nullptr);
 }
 
 

@@ -79,6 +79,7 @@ class _Plan:
         for k in L.OPTION_FIELDS:
             setattr(self.cfg, k, int(opts.get(k, 0)))
         self.options = {k: int(getattr(self.cfg, k)) for k in L.OPTION_FIELDS}
+        self.options.update({k: int(opts.get(k, 0)) for k in L.PLAN_SETTERS})
         for k in L.TRAIN_FIELDS:                        # the model's training head (0: full-catalogue CE)
             setattr(self.cfg, k, model.train_head[k])
         self.cfg.train_lazy_adam = int(model.lazy_adam)
@@ -113,6 +114,7 @@ class _Plan:
                                        self.ws.data_ptr(), nbytes, self.state.data_ptr(),
                                        model._twiddle.data_ptr(), stream), "bsarec_plan_create")
         self.lib = lib
+        L.check(lib.bsarec_plan_set_drop_bits(self.handle, self.options["drop_bits"]), "bsarec_plan_set_drop_bits")
         if self.cfg.train_negatives > 0 and self.cfg.train_sampler == 1 and model._train_cum is not None:
             model._install_train_sampler(self)
 

@@ -126,7 +126,9 @@ enum {
     BSAREC_BUF_TRAIN_CAND = 10,    /* int32 [N]     the step's candidates n_0 .. n_N-1 */
     BSAREC_BUF_TRAIN_CORR = 11,    /* [N]           their corrections c(n_j) */
     BSAREC_BUF_TRAIN_LOGITS = 12,  /* [B, N+1]      x_b0 (answer), x_b1 .. x_bN (candidates; -inf on an accidental hit) */
-    BSAREC_BUF_TRAIN_DLOGITS = 13  /* [B, N+1]      d loss / d x = (softmax - onehot_0) / B (exactly 0 on a hit) */
+    BSAREC_BUF_TRAIN_DLOGITS = 13, /* [B, N+1]      d loss / d x = (softmax - onehot_0) / B (exactly 0 on a hit) */
+    BSAREC_BUF_DROP_BITS = 14      /* bytes: keep bits of layer l's dropout masks after a training forward (bsarec_drop_bits_bytes;
+                                    * -1 where the plan keeps none) */
 };
 
 typedef struct bsarec_plan bsarec_plan_t;   /* host-side launch plan (no device memory of its own) */
@@ -235,6 +237,23 @@ int bsarec_plan_set_dense_grad_hook(bsarec_plan_t *plan, bsarec_hook_t hook, voi
 /* The popularity table of train_sampler = 1: int64[V] on the device, kept valid by the caller while the plan trains (null
  * clears it).  < 0 on a plan without train_negatives > 0 and train_sampler = 1. */
 int bsarec_plan_set_train_sampler(bsarec_plan_t *plan, const int64_t *pop_cum);
+
+/* Keep bits of the dropout masks (plan option drop_bits).  At the fused shape, in fp32 and bf16 storage (not with
+ * x3_products, chain_kernels or filter_kind = 1), the forward block kernels of a training step leave one bit per element of
+ * every dropout mask in BSAREC_BUF_DROP_BITS of their layer -- 1 = kept -- and the matching backward reads the bits instead of
+ * evaluating the Philox stream a second time; results are the same bit for bit.  On by default; bsarec_plan_set_drop_bits(plan, 0)
+ * makes the backward evaluate Philox again (and the forward store nothing).  Change it between steps, not between a forward
+ * and its backward.  Eval forwards and sites with p = 0 touch no bits.
+ * bsarec_drop_bits_bytes: bytes of one layer's buffer for `cfg` (0: such a plan keeps none; < 0: bad cfg).
+ * The index map, host arithmetic only (bit i of the buffer = bit i & 7 of byte i >> 3; -1 on a bad argument):
+ *   bsarec_drop_bits_hidden_bit: element (token, column) of hidden-size site `slot` (0 embedding -- layer 0 only --, 1 the
+ *     FrequencyLayer's, 2 the attention output's, 3 the feed-forward's dropout) among `tokens` = B L tokens;
+ *   bsarec_drop_bits_attn_bit: element (b, head, query, key) of the attention-probability dropout.
+ * After bsarec_forward_last with a pruned top block the top layer holds row / query L - 1 only. */
+int bsarec_plan_set_drop_bits(bsarec_plan_t *plan, int on);
+long bsarec_drop_bits_bytes(const bsarec_config_t *cfg);
+long bsarec_drop_bits_hidden_bit(int slot, long tokens, long token, int column);
+long bsarec_drop_bits_attn_bit(long tokens, int heads, long b, int head, int query, int key);
 
 /* Byte offset of a named buffer inside the workspace, or -1. */
 long bsarec_buffer_offset(const bsarec_plan_t *plan, int buffer, int layer);
