@@ -162,6 +162,11 @@ class CaserConfig(C.Structure):
     _fields_ = [("batch", C.c_int), ("seq_len", C.c_int), ("width", C.c_int), ("n_h", C.c_int), ("n_v", C.c_int)]
 
 
+class CaserStepConfig(C.Structure):
+    """bsarec_caser_step_config_t"""
+    _fields_ = [("conv", CaserConfig), ("item_size", C.c_int), ("dropout", C.c_float)]
+
+
 GRU4REC_CAND_MAX = 8192                          # BSAREC_GRU4REC_CAND_MAX: the most candidate columns of a GRU4Rec head
 GRU4REC_LOSSES = {"ce": 1, "top1": 2, "bpr_max": 3}                 # bsarec_gru4rec_head_t.loss
 GRU4REC_CANDIDATES = {"in_batch": 1, "in_batch+sampled": 2}         # bsarec_gru4rec_head_t.candidates
@@ -263,6 +268,17 @@ EXPORTS = {
                                    C.c_void_p]),
     "bsarec_caser_bwd": (C.c_int, [C.POINTER(CaserConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "bsarec_caser_fc_floats": (C.c_long, [C.POINTER(CaserConfig)]),
+    "bsarec_caser_fc_workspace_bytes": (C.c_long, [C.c_int] * 3),
+    "bsarec_caser_fc_fwd": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_long,
+                                      C.c_void_p]),
+    "bsarec_caser_fc_bwd": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int, C.c_float] + [C.c_void_p] * 3 +
+                            [C.c_long, C.c_void_p]),
+    "bsarec_caser_step_workspace_bytes": (C.c_long, [C.POINTER(CaserStepConfig)]),
+    "bsarec_caser_loss_grad": (C.c_int, [C.POINTER(CaserStepConfig)] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 5 +
+                               [C.c_long, C.c_void_p]),
+    "bsarec_caser_train_step": (C.c_int, [C.POINTER(CaserStepConfig)] + [C.c_void_p] * 3 + [C.POINTER(Adam)] * 3 +
+                                [C.c_void_p] * 3 + [C.c_long, C.c_void_p]),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

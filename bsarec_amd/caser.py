@@ -6,7 +6,8 @@ Caser is left out, as every model here ignores ``user_ids``.
 The contract of this model is the math of its docstrings, checked against ``torch.nn.Conv2d`` / ``F.max_pool1d`` / ``nn.Linear``
 on the CPU (tests/caser_ref.py, tests/test_caser_cpu.py); no reference golden exists for it yet.  The convolution block runs in
 libbsarec_hip.so in both directions (bsarec_caser_fwd / bsarec_caser_bwd, csrc/caser.h); the embedding lookup, the dropout mask,
-``fc1`` and the B-row BPR head are torch ops.  There is no CPU path.
+``fc1`` and the B-row BPR head are torch ops -- unless ``args.caser_step = "fused"``, where the whole training step is one C call
+(bsarec_caser_train_step, csrc/caser_step.h).  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -208,7 +209,18 @@ class CaserModel(nn.Module):
     Init: Embedding and fc1 weights N(0, initializer_range), the fc1 bias 0, the filters torch's Conv2d default.
     Item-only: the user embedding of the original Caser is left out (``user_ids`` is accepted and ignored).
     The filter bank is sized by L: ``input_ids.shape[1]`` must equal ``args.max_seq_length`` (ValueError otherwise).
-    Steps through calculate_loss / backward / torch.optim.Adam (``torch_optim``) on one GPU."""
+
+    ``args.caser_step`` selects how the model steps, single GPU either way:
+      "torch" (the default, also when absent): calculate_loss / backward / torch.optim.Adam (``torch_optim``); the dropout mask
+        is drawn from a torch generator seeded by ``set_seed``.
+      "fused": ``train_step`` is ONE C call (bsarec_caser_train_step: lookup, convolution block, fc1 with its dropout, BPR head,
+        every gradient, Adam on the item table, the convolution's flat array and the fc1 flat array), replayed from a hipGraph
+        per batch shape unless ``args.caser_step_graph`` is False; the instance sets ``torch_optim = False`` so that
+        Trainer.iteration calls it, and ``fc1.weight`` / ``fc1.bias`` are views of one flat tensor (weight, then bias).  Its
+        dropout mask is the library's Philox stream (site 0, the step counter of the device state that ``set_seed`` seeds and
+        resets).  The two streams have the same distribution and DIFFERENT draws: the modes do not train bit for bit alike at
+        p > 0.
+    calculate_loss, forward, predict and last_hidden are the same in both modes (torch-generator dropout in training mode)."""
 
     needs_negatives = True
     needs_same_target = False
@@ -218,6 +230,14 @@ class CaserModel(nn.Module):
     def __init__(self, args):
         super().__init__()
         self.args = args
+        mode = getattr(args, "caser_step", "torch")
+        if mode not in ("torch", "fused"):
+            raise ValueError(f"caser_step must be 'torch' or 'fused', got {mode!r}")
+        self.caser_step = mode
+        if mode == "fused":
+            self.torch_optim = False                      # Trainer.iteration: the pairwise branch, model.train_step
+        self._fused = None                                # the fused step's buffers (_step_buffers)
+        self._fc_flat = None                              # fused: fc1.weight [d, F] then fc1.bias [d]
         d, Lq = int(args.hidden_size), int(args.max_seq_length)
         self.item_embeddings = nn.Embedding(int(args.item_size), d)
         self.conv = CaserConv(Lq, d, int(getattr(args, "caser_nh", 16)), int(getattr(args, "caser_nv", 4)))
@@ -231,29 +251,60 @@ class CaserModel(nn.Module):
             self.fc1.weight.normal_(0.0, std)
             self.fc1.bias.zero_()
         self._seed, self._rank, self._gen = 42, 0, None
+        self.reflatten()
 
     def _apply(self, fn, recurse=True):
         out = super()._apply(fn, recurse)
-        self.conv.reflatten()
+        self.reflatten()
         self._gen = None
+        self._fused = None                                # with the Adam moments and the step state, as the workspace pool goes
         return out
 
+    def reflatten(self):
+        """Makes the convolution's parameters views of its flat tensor again and, with ``caser_step = "fused"``, ``fc1.weight``
+        and ``fc1.bias`` views of one flat tensor, weight then bias (after ``.to()`` / ``.cuda()`` / ``load_state_dict(assign=True)``
+        gave each its own storage).  The fused step's buffers go with a storage that changed."""
+        self.conv.reflatten()
+        if self.caser_step != "fused":
+            return
+        w, b = self.fc1.weight, self.fc1.bias
+        flat, nw = self._fc_flat, w.numel()
+        if (flat is not None and flat.device == w.device == b.device and w.data_ptr() == flat.data_ptr()
+                and b.data_ptr() == flat.data_ptr() + 4 * nw and w.is_contiguous()):
+            return
+        with torch.no_grad():
+            flat = torch.empty(nw + b.numel(), dtype=torch.float32, device=w.device)
+            flat[:nw] = w.detach().reshape(-1).to(torch.float32)
+            flat[nw:] = b.detach().reshape(-1).to(torch.float32)
+            w.data = flat[:nw].view(w.shape)
+            b.data = flat[nw:].view(b.shape)
+            w.grad = b.grad = None
+        self._fc_flat = flat
+        self._fused = None
+
+    def _stream_seed(self):
+        return (self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF
+
     def set_seed(self, seed: int, rank: int = 0):
-        """Seed of the dropout draws (rank-decorrelated)."""
+        """Seed of the dropout draws (rank-decorrelated): of the torch generator and of the fused step's device state, whose
+        step counter goes back to 0."""
         self._seed, self._rank = int(seed), int(rank)
         self._gen = None
+        if self._fused is not None:
+            self._fused["state"][0] = self._stream_seed()
+            self._fused["state"][1] = 0
 
     def _generator(self, device):
         if self._gen is None or self._gen.device != device:
             self._gen = torch.Generator(device=device)
-            self._gen.manual_seed((self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF)
+            self._gen.manual_seed(self._stream_seed())
         return self._gen
 
-    def _require_gpu(self, input_ids):
-        if self.item_embeddings.weight.device.type != "cuda" or not input_ids.is_cuda:
+    def _require_gpu(self, input_ids=None):
+        if self.item_embeddings.weight.device.type != "cuda" or (input_ids is not None and not input_ids.is_cuda):
             raise RuntimeError("bsarec_amd runs on MI355X only: move the model and its input with .cuda() "
                                "(there is no CPU fallback)")
-        if input_ids.dim() != 2 or input_ids.shape[1] != self.conv.seq_len:
+        if input_ids is not None and (input_ids.dim() != 2 or input_ids.shape[1] != self.conv.seq_len):
             raise ValueError(f"Caser: input_ids must be [B, max_seq_length = {self.conv.seq_len}] (the filter bank is sized by it), "
                              f"got {tuple(input_ids.shape)}")
 
@@ -288,3 +339,124 @@ class CaserModel(nn.Module):
         neg = self.item_embeddings(neg_answers.to(s.device).reshape(-1))
         diff = (s * pos).sum(-1) - (s * neg).sum(-1)
         return -torch.log(torch.sigmoid(diff) + 1e-10).mean()
+
+    # ---- the fused step (caser_step = "fused"; bsarec_caser_loss_grad / bsarec_caser_train_step) ---------------------------
+    def _step_buffers(self):
+        """What the fused step owns beside the parameters: the device step state (seed, step counter, Adam t), the three gradient
+        arrays, the Adam moments of the item table, of the convolution's flat array and of the fc1 flat array, and per batch
+        shape a workspace, static id buffers and a captured graph.  Built on first use; dropped by ``.to()`` / ``reflatten()``
+        (a new parameter storage)."""
+        if self.caser_step != "fused":
+            raise RuntimeError("Caser: the fused step's buffers exist only with caser_step = 'fused'")
+        self._require_gpu()
+        self.reflatten()
+        E, flat, fc = self.item_embeddings.weight.data, self.conv._flat, self._fc_flat
+        if flat.device != E.device or fc.device != E.device or not E.is_contiguous() or E.dtype != torch.float32:
+            raise RuntimeError("caser: the item table, the filters and fc1 must be contiguous fp32 on one device")
+        key = (E.data_ptr(), flat.data_ptr(), fc.data_ptr(), E.device)
+        f = self._fused
+        if f is None or f["key"] != key:
+            state = torch.zeros(8, dtype=torch.int64, device=E.device)
+            state[0] = self._stream_seed()
+            f = dict(key=key, state=state, E=E, flat=flat, fc=fc, adam=None, slots={})
+            for name, t in (("E", E), ("W", flat), ("F", fc)):
+                f["d" + name], f["m" + name], f["v" + name] = torch.empty_like(t), torch.zeros_like(t), torch.zeros_like(t)
+            self._fused = f
+        return f
+
+    @property
+    def step_state(self) -> torch.Tensor:
+        """The fused step's device state, int64[8]: [0] the Philox seed, [1] the step counter of the dropout stream, [2] Adam's t."""
+        return self._step_buffers()["state"]
+
+    def _slot(self, f, B: int):
+        s = f["slots"].get(B)
+        if s is None:
+            c = self.conv
+            cfg = L.CaserStepConfig(L.CaserConfig(B, c.seq_len, c.width, c.n_h, c.n_v), self.item_embeddings.num_embeddings,
+                                    self.p_drop)
+            nbytes = L.load().bsarec_caser_step_workspace_bytes(cfg)
+            if nbytes < 0:
+                raise ValueError(f"caser: unsupported step shape B = {B}, dropout = {self.p_drop} (1 <= B <= 65536, 0 <= p < 1)")
+            dev = f["E"].device
+            s = dict(cfg=cfg, nbytes=nbytes, ws=torch.empty(nbytes, dtype=torch.uint8, device=dev),
+                     ids=torch.zeros((B, c.seq_len), dtype=torch.int64, device=dev),
+                     ans=torch.zeros(B, dtype=torch.int64, device=dev), neg=torch.zeros(B, dtype=torch.int64, device=dev),
+                     loss=torch.zeros((), dtype=torch.float32, device=dev), graph=None)
+            f["slots"][B] = s
+        return s
+
+    @staticmethod
+    def _fill(s, input_ids, answers, neg_answers):
+        if neg_answers is None:
+            raise ValueError("Caser's loss needs neg_answers")
+        s["ids"].copy_(input_ids)
+        s["ans"].copy_(answers.reshape(-1))
+        s["neg"].copy_(neg_answers.reshape(-1))
+
+    def _loss_grad(self, f, s, train: bool):
+        stream = torch.cuda.current_stream(f["E"].device).cuda_stream
+        L.check(L.load().bsarec_caser_loss_grad(
+            s["cfg"], f["E"].data_ptr(), f["flat"].data_ptr(), f["fc"].data_ptr(), s["ids"].data_ptr(), s["ans"].data_ptr(),
+            s["neg"].data_ptr(), f["state"].data_ptr(), int(train), s["loss"].data_ptr(), f["dE"].data_ptr(), f["dW"].data_ptr(),
+            f["dF"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream), "bsarec_caser_loss_grad")
+
+    def loss_and_grads(self, input_ids, answers, neg_answers, train: bool = True):
+        """The BPR loss (0-d tensor) and {state_dict key: gradient} of one batch through bsarec_caser_loss_grad, no update.
+        ``train``: draw the next dropout mask of the device stream (the step counter advances); else no dropout."""
+        if self.caser_step != "fused":
+            raise RuntimeError("Caser: loss_and_grads is the fused step's (caser_step = 'fused')")
+        self._require_gpu(input_ids)
+        f = self._step_buffers()
+        s = self._slot(f, int(input_ids.shape[0]))
+        self._fill(s, input_ids, answers, neg_answers)
+        self._loss_grad(f, s, train)
+        grads = OrderedDict([("item_embeddings.weight", f["dE"].clone())])
+        for name, (o, n, shp) in self.conv._slices.items():
+            grads["conv." + name] = f["dW"][o:o + n].view(shp).clone()
+        nw = self.fc1.weight.numel()
+        grads["fc1.weight"] = f["dF"][:nw].view(self.fc1.weight.shape).clone()
+        grads["fc1.bias"] = f["dF"][nw:].clone()
+        return s["loss"].clone(), grads
+
+    def _adam_structs(self, f):
+        if f["adam"] is None:
+            a = self.args
+            hyper = (float(getattr(a, "lr", 1e-3)), float(getattr(a, "adam_beta1", 0.9)), float(getattr(a, "adam_beta2", 0.999)),
+                     1e-8, float(getattr(a, "weight_decay", 0.0)), 1.0, None, 0)
+            f["adam"] = tuple(L.Adam(f[p].data_ptr(), f["d" + k].data_ptr(), f["m" + k].data_ptr(), f["v" + k].data_ptr(),
+                                     f[p].numel(), *hyper) for p, k in (("E", "E"), ("flat", "W"), ("fc", "F")))
+        return f["adam"]
+
+    def _train_step(self, f, s):
+        items, weights, fc = self._adam_structs(f)
+        stream = torch.cuda.current_stream(f["E"].device).cuda_stream
+        L.check(L.load().bsarec_caser_train_step(
+            s["cfg"], s["ids"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), items, weights, fc, f["state"].data_ptr(),
+            s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream), "bsarec_caser_train_step")
+
+    def train_step(self, input_ids, answers, neg_answers=None, same_target=None):
+        """caser_step = "fused": one optimisation step in one C call -- the step counter, the lookup, the convolution block, fc1
+        with its Philox dropout, the BPR head, every gradient, Adam (``args.lr``, ``adam_beta1``, ``adam_beta2``,
+        ``weight_decay``) on the three arrays, in place.  Returns the mean loss as a 0-d device tensor (no host sync; the next
+        step overwrites it).  The call is captured once per batch shape over static id buffers and replayed -- the mask and
+        Adam's t advance on the device, and the capture is one linear chain on one stream, so it has no parallel branches to
+        replay; ``args.caser_step_graph = False`` calls eagerly instead."""
+        if self.caser_step != "fused":
+            raise RuntimeError("Caser steps through calculate_loss / backward / torch.optim.Adam unless caser_step = 'fused'")
+        self._require_gpu(input_ids)
+        f = self._step_buffers()
+        s = self._slot(f, int(input_ids.shape[0]))
+        self._fill(s, input_ids, answers, neg_answers)
+        if not getattr(self.args, "caser_step_graph", True):
+            self._train_step(f, s)
+            return s["loss"]
+        if s["graph"] is None:
+            self._adam_structs(f)
+            self._loss_grad(f, s, False)                  # every kernel of the chain has run once before the capture; no
+            graph = torch.cuda.CUDAGraph()                # counter moves and nothing is updated (train = 0)
+            with torch.cuda.graph(graph):
+                self._train_step(f, s)
+            s["graph"] = graph
+        s["graph"].replay()
+        return s["loss"]

@@ -22,6 +22,7 @@
 #include "gru4rec_step.h"
 #include "gru4rec_cand.h"
 #include "caser.h"
+#include "caser_step.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -2784,6 +2785,218 @@ extern "C" int bsarec_gru4rec_cand_head(const float* s, const float* item_emb, c
     hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(ROW_THREADS), 0, st,
                        make_tick(nullptr, 0, 0.f, 0.f, 0.f, w + g.end, batch, loss_out, nullptr, 0, 0));
     return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Caser training step (caser_step.h): fc1 in both directions alone, and the whole step -- lookup, bsarec_caser_fwd, fc1, the BPR
+// head, every gradient, Adam -- plan-less, one linear chain of launches on the caller's stream, no allocation, no host
+// synchronisation
+// ---------------------------------------------------------------------------------------------
+static bool caser_fc_shape_ok(int B, int F, int d) {
+    return B >= 1 && B <= 65536 && F >= 4 && F <= 12288 && F % 4 == 0 && row_dim_ok(d);
+}
+static bool dropout_ok(float p) { return p >= 0.f && p < 1.f; }           // NaN fails both comparisons
+
+extern "C" long bsarec_caser_fc_floats(const bsarec_caser_config_t* cfg) {
+    if (caser_check(cfg)) return -10;
+    return (caser_weights(*cfg).F + 1) * cfg->width;
+}
+
+// zd [B][F]: the dropped-out z of a masked forward, read by the backward
+extern "C" long bsarec_caser_fc_workspace_bytes(int batch, int features, int width) {
+    if (!caser_fc_shape_ok(batch, features, width)) return -10;
+    return (long)batch * features * (long)sizeof(float);
+}
+
+static DropP caser_fc_drop(float p, const void* state, bool train) {
+    DropP d;
+    d.thresh = train ? drop_thresh(p) : 0;
+    d.scale = (train && p > 0.f) ? (float)(1.0 / (1.0 - (double)p)) : 1.0f;
+    d.rng = (const uint64_t*)state; d.site = 0;
+    return d;
+}
+
+// z, fc, the drop and the shape are set; the masked forward leaves zd in `zd`, and the backward reads it there (z otherwise)
+static CaserFcP caser_fc_params(int B, int F, int d, const float* z, const float* fc, const DropP& drop, float* zd) {
+    CaserFcP P;
+    memset(&P, 0, sizeof(P));
+    P.z = z; P.w = fc; P.B = B; P.F = F; P.d = d; P.drop = drop;
+    P.zd_out = drop.thresh ? zd : nullptr;
+    P.zd = drop.thresh ? zd : z;
+    return P;
+}
+
+static void caser_fc_fwd_launch(const CaserFcP& P, hipStream_t s) {
+    const dim3 grid(cdiv(P.B, 16));
+    const int nt = P.d <= 64 ? 4 : (P.d <= 128 ? 8 : 16), nw = nt <= 8 ? 8 : 4;
+    const size_t lds = (size_t)(nw - 1) * 16 * (16 * nt + CASER_FC_LDS_PAD) * sizeof(float);      // 30,464 / 59,136 / 49,920 bytes
+    if (nt == 4) hipLaunchKernelGGL((caser_fc_fwd_kernel<4, 8>), grid, dim3(512), lds, s, P);
+    else if (nt == 8) hipLaunchKernelGGL((caser_fc_fwd_kernel<8, 8>), grid, dim3(512), lds, s, P);
+    else hipLaunchKernelGGL((caser_fc_fwd_kernel<16, 4>), grid, dim3(256), lds, s, P);
+}
+
+static void caser_fc_bwd_launch(const CaserFcP& P, hipStream_t s) {
+    hipLaunchKernelGGL(caser_fc_dz_kernel, dim3(cdiv(P.F, 256), cdiv(P.B, 16)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(caser_fc_dw_kernel, dim3(cdiv(P.F, 64), cdiv(P.d, 64)), dim3(256), 0, s, P);
+}
+
+extern "C" int bsarec_caser_fc_fwd(int batch, int features, int width, const float* z, const float* fc, const void* state,
+                                   int train, float dropout, float* s, void* workspace, long workspace_bytes, void* stream) {
+    if (!caser_fc_shape_ok(batch, features, width) || !dropout_ok(dropout)) return -10;
+    for (const void* p : {(const void*)z, (const void*)fc, (const void*)s, (const void*)workspace})
+        if (!aligned_to(p, 16)) return -10;
+    if (!aligned_to(state, 8)) return -10;
+    if (workspace_bytes < bsarec_caser_fc_workspace_bytes(batch, features, width)) return -10;
+    CaserFcP P = caser_fc_params(batch, features, width, z, fc, caser_fc_drop(dropout, state, train != 0), (float*)workspace);
+    P.s_out = s;
+    caser_fc_fwd_launch(P, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_caser_fc_bwd(int batch, int features, int width, const float* z, const float* fc, const float* s,
+                                   const float* ds, const void* state, int train, float dropout, float* dz, float* dfc,
+                                   void* workspace, long workspace_bytes, void* stream) {
+    if (!caser_fc_shape_ok(batch, features, width) || !dropout_ok(dropout)) return -10;
+    for (const void* p : {(const void*)z, (const void*)fc, (const void*)s, (const void*)ds, (const void*)dz, (const void*)dfc,
+                          (const void*)workspace})
+        if (!aligned_to(p, 16)) return -10;
+    if (!aligned_to(state, 8)) return -10;
+    if (workspace_bytes < bsarec_caser_fc_workspace_bytes(batch, features, width)) return -10;
+    CaserFcP P = caser_fc_params(batch, features, width, z, fc, caser_fc_drop(dropout, state, train != 0), (float*)workspace);
+    P.s = s; P.ds = ds; P.dz = dz; P.dw = dfc;
+    caser_fc_bwd_launch(P, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+static int caser_step_check(const bsarec_caser_step_config_t* c) {
+    if (!c) return -10;
+    RET(caser_check(&c->conv));
+    if (c->item_size < 2 || !dropout_ok(c->dropout)) return -10;
+    return 0;
+}
+
+// Workspace, in floats (every region a multiple of 4): the convolution workspace of train = 1 | x [T][d] | z [B][F] | zd [B][F] |
+// s [B][d] | ds [B][d] | dz [B][F] | dx [T][d] | c [B up to 4] | loss rows [B up to 4] | the fixed-point accumulator [V][d] of
+// 64-bit words
+struct CaserStepWs { long conv, x, z, zd, s, ds, dz, dx, c, rows, acc, total; long conv_bytes; };
+static CaserStepWs caser_step_ws(const bsarec_caser_step_config_t& c) {
+    const long B = c.conv.batch, T = B * c.conv.seq_len, d = c.conv.width, F = caser_weights(c.conv).F;
+    CaserStepWs w;
+    long off = 0;
+    w.conv = off; w.conv_bytes = caser_ws_bytes(c.conv, true); off += w.conv_bytes / (long)sizeof(float);
+    w.x = off; off += T * d;
+    w.z = off; off += B * F;
+    w.zd = off; off += B * F;
+    w.s = off; off += B * d;
+    w.ds = off; off += B * d;
+    w.dz = off; off += B * F;
+    w.dx = off; off += T * d;
+    w.c = off; off += rup(B, 4);
+    w.rows = off; off += rup(B, 4);
+    w.acc = off; off += 2L * c.item_size * d;
+    w.total = off;
+    return w;
+}
+
+extern "C" long bsarec_caser_step_workspace_bytes(const bsarec_caser_step_config_t* cfg) {
+    if (caser_step_check(cfg)) return -10;
+    return caser_step_ws(*cfg).total * (long)sizeof(float);
+}
+
+// tick_adam: null, or the Adam whose t the step's closing block advances (bsarec_caser_train_step)
+static int caser_run(const bsarec_caser_step_config_t& c, const float* E, const float* weights, const float* fc, const int64_t* ids,
+                     const int64_t* answers, const int64_t* neg_answers, void* state, int train, float* loss_out, float* dE,
+                     float* dweights, float* dfc, void* workspace, const bsarec_adam_t* tick_adam, hipStream_t s) {
+    const int B = c.conv.batch, d = c.conv.width, V = c.item_size;
+    const long T = (long)B * c.conv.seq_len;
+    const int F = (int)caser_weights(c.conv).F;
+    const CaserStepWs ws = caser_step_ws(c);
+    float* w = (float*)workspace;
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(w + ws.acc);
+    if (train) hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(1), 0, s, (uint64_t*)state, (long long*)nullptr, 0);
+    DropP none;                                         // the token rows carry no mask
+    none.thresh = 0; none.scale = 1.0f; none.rng = (const uint64_t*)state; none.site = 0;
+
+    Gru4RecEmbedP pe;
+    pe.E = E; pe.ids = ids; pe.x = w + ws.x; pe.T = T; pe.d = d; pe.V = V; pe.drop = none;
+    pe.acc = acc; pe.acc_n2 = (long)V * d / 2;
+    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_embed_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)),
+                                       dim3(ROW_THREADS), 0, s, pe));
+    RET(bsarec_caser_fwd(&c.conv, w + ws.x, weights, 1, w + ws.z, w + ws.conv, ws.conv_bytes, s));
+
+    CaserFcP pf = caser_fc_params(B, F, d, w + ws.z, fc, caser_fc_drop(c.dropout, state, train != 0), w + ws.zd);
+    pf.s_out = w + ws.s; pf.s = w + ws.s; pf.ds = w + ws.ds; pf.dz = w + ws.dz; pf.dw = dfc;
+    caser_fc_fwd_launch(pf, s);
+
+    Gru4RecBprP pb;
+    pb.s = w + ws.s; pb.E = E; pb.ans = answers; pb.neg = neg_answers; pb.B = B; pb.d = d; pb.V = V;
+    pb.ds = w + ws.ds; pb.c = w + ws.c; pb.loss_rows = w + ws.rows;
+    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_bpr_kernel<LPR>, dim3(cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS), 0, s, pb));
+
+    caser_fc_bwd_launch(pf, s);
+    RET(bsarec_caser_bwd(&c.conv, w + ws.x, weights, w + ws.dz, w + ws.conv, ws.conv_bytes, w + ws.dx, dweights, s));
+
+    Gru4RecGradP pg;                                   // T token rows, then the head's 2 B
+    pg.dx = w + ws.dx; pg.ids = ids; pg.ans = answers; pg.neg = neg_answers;
+    pg.T = T; pg.B = B; pg.C = 0; pg.d = d; pg.V = V; pg.drop = none; pg.dA = acc;
+    pg.head_rows = w + ws.s; pg.c = w + ws.c;
+    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_item_grad_kernel<LPR>, dim3(cdiv(T + 2L * B, SCATTER_FLOATS / (4 * LPR))),
+                                       dim3(ROW_THREADS), 0, s, pg));
+
+    LookupAcc la;
+    memset(&la, 0, sizeof(la));
+    la.acc = acc; la.dst = dE; la.n4 = (long)V * d / 4; la.dense_zero = 1;
+    la.nblocks = std::min(cdiv(la.n4, ROW_THREADS), 1024);
+    const TickP tk = tick_adam ? make_tick(state, 1, tick_adam->lr, tick_adam->beta1, tick_adam->beta2, w + ws.rows, B, loss_out,
+                                           nullptr, 0, 0)
+                               : make_tick(state, 0, 0.f, 0.f, 0.f, w + ws.rows, B, loss_out, nullptr, 0, 0);
+    hipLaunchKernelGGL(gru4rec_flush_kernel, dim3(la.nblocks + 1), dim3(ROW_THREADS), 0, s, la, tk);
+    return (int)hipGetLastError();
+}
+
+static int caser_loss_grad(const bsarec_caser_step_config_t* cfg, const float* item_emb, const float* weights, const float* fc,
+                           const int64_t* ids, const int64_t* answers, const int64_t* neg_answers, void* state, int train,
+                           float* loss_out, float* d_item_emb, float* dweights, float* dfc, void* workspace, long workspace_bytes,
+                           const bsarec_adam_t* tick_adam, hipStream_t s) {
+    RET(caser_step_check(cfg));
+    for (const void* p : {(const void*)item_emb, (const void*)weights, (const void*)fc, (const void*)d_item_emb,
+                          (const void*)dweights, (const void*)dfc, (const void*)workspace})
+        if (!aligned_to(p, 16)) return -10;
+    for (const void* p : {(const void*)ids, (const void*)answers, (const void*)neg_answers, (const void*)state})
+        if (!aligned_to(p, 8)) return -10;
+    if (!aligned_to(loss_out, 4)) return -10;
+    if (workspace_bytes < caser_step_ws(*cfg).total * (long)sizeof(float)) return -10;
+    return caser_run(*cfg, item_emb, weights, fc, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights, dfc,
+                     workspace, tick_adam, s);
+}
+
+extern "C" int bsarec_caser_loss_grad(const bsarec_caser_step_config_t* cfg, const float* item_emb, const float* weights,
+                                      const float* fc, const int64_t* ids, const int64_t* answers, const int64_t* neg_answers,
+                                      void* state, int train, float* loss_out, float* d_item_emb, float* dweights, float* dfc,
+                                      void* workspace, long workspace_bytes, void* stream) {
+    return caser_loss_grad(cfg, item_emb, weights, fc, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights, dfc,
+                           workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int bsarec_caser_train_step(const bsarec_caser_step_config_t* cfg, const int64_t* ids, const int64_t* answers,
+                                       const int64_t* neg_answers, const bsarec_adam_t* adam_items,
+                                       const bsarec_adam_t* adam_weights, const bsarec_adam_t* adam_fc, void* state,
+                                       float* loss_out, void* workspace, long workspace_bytes, void* stream) {
+    RET(caser_step_check(cfg));
+    const CaserW wo = caser_weights(cfg->conv);
+    RET(gru4rec_adam_check(adam_items, (long)cfg->item_size * cfg->conv.width));
+    RET(gru4rec_adam_check(adam_weights, wo.total));
+    RET(gru4rec_adam_check(adam_fc, (wo.F + 1) * cfg->conv.width));
+    // one t and one pair of bias corrections in `state` serve the three arrays
+    for (const bsarec_adam_t* a : {adam_weights, adam_fc})
+        if (a->lr != adam_items->lr || a->beta1 != adam_items->beta1 || a->beta2 != adam_items->beta2) return -10;
+    hipStream_t s = (hipStream_t)stream;
+    RET(caser_loss_grad(cfg, adam_items->params, adam_weights->params, adam_fc->params, ids, answers, neg_answers, state, 1,
+                        loss_out, const_cast<float*>(adam_items->grads), const_cast<float*>(adam_weights->grads),
+                        const_cast<float*>(adam_fc->grads), workspace, workspace_bytes, adam_items, s));
+    RET(adam_launch(*adam_items, state, s));
+    RET(adam_launch(*adam_weights, state, s));
+    return adam_launch(*adam_fc, state, s);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -174,6 +174,9 @@ def parse_args(argv=None):
                    help="Caser: horizontal filters per height (default 16)")
     p.add_argument("--caser_nv", default=argparse.SUPPRESS, type=int,
                    help="Caser: vertical filters, 1..16 (default 4)")
+    p.add_argument("--caser_step", default=argparse.SUPPRESS, choices=("torch", "fused"),
+                   help="Caser: step through autograd and torch.optim.Adam (default) or through the one-call HIP step "
+                        "(lookup, convolutions, fc1 with Philox dropout, BPR head, item-table gradient and Adam in the library)")
     args = p.parse_args(argv)
     n = getattr(args, "eval_negatives", 0)
     if n > 0 and hasattr(args, "eval_full_rank"):

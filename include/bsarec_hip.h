@@ -746,6 +746,74 @@ int bsarec_caser_fwd(const bsarec_caser_config_t *cfg, const float *x, const flo
 int bsarec_caser_bwd(const bsarec_caser_config_t *cfg, const float *x, const float *weights, const float *dz,
                      void *workspace, long workspace_bytes, float *dx, float *dweights, void *stream);
 
+/* fc1 of the Caser model alone (csrc/caser_step.h), for per-op parity: with z [batch, features] (features = F), fc = W1
+ * [width, F] followed by b1 [width] (bsarec_caser_fc_floats(cfg) = width F + width floats for a convolution config),
+ *   forward   zd = z (.) m,  s = max(0, zd W1^T + b1) [batch, width];  m = keep / (1 - dropout) of the library's Philox stream,
+ *             site 0, element index b F + k, keyed by state[0] = seed and state[1] = the step counter, which this call READS
+ *             (it advances nothing).  train = 0 or dropout = 0: m = 1, no draw.
+ *   backward  du = ds where s > 0, else 0 (an s of exactly 0 passes nothing);  dfc = [dW1 = du^T zd | db1 = sum_b du];
+ *             dz = (du W1) (.) m [batch, F].  Every float of dz and dfc is overwritten.
+ * A masked forward (train != 0 and dropout > 0) leaves zd in the workspace and bsarec_caser_fc_bwd with the same arguments reads
+ * it from the SAME workspace; the mask of dz is regenerated.  Without a mask the workspace is not touched (zd is z).
+ *   All products run on v_mfma_f32_16x16x4_f32 in fp32.  Every sum has one order that is a function of the shape alone (the
+ * forward splits F over eight waves, four at width > 128, the weight gradient the batch over four; the waves' parts are added in
+ * wave order): no atomics, equal bits
+ * on every run, and a row of s does not depend on the other rows of the batch.  Launches on `stream`: forward 1, backward 2
+ * (dz; dW1 + db1).  No allocation, no host synchronisation, no scratch: capturable.
+ *   Workspace: bsarec_caser_fc_workspace_bytes(batch, features, width) = 4 batch F bytes (host-only query).
+ *   Limits (else < 0 before any HIP call): 1 <= batch <= 65536; features in 4 .. 12288 and a multiple of 4; width in 4 .. 256
+ * and a multiple of 4; 0 <= dropout < 1 (NaN refused); every pointer non-null, float arrays and the workspace 16-byte aligned,
+ * state 8-byte; workspace_bytes at least the queried size.  Outputs may not alias inputs, each other or the workspace.
+ *
+ * One Caser training step: with E = item_emb [V, d], x = E[ids] [B, L, d] (no mask on x), z = bsarec_caser_fwd(x),
+ * s = the forward above with dropout = cfg->dropout, and
+ *   diff_b = s_b . E[answers_b] - s_b . E[neg_answers_b],  loss = mean_b -log(sigmoid(diff_b) + 1e-10),
+ * bsarec_caser_loss_grad writes the loss (one float) and the gradient of every parameter: d_item_emb [V, d] -- the lookup rows
+ * dE[ids[b, t]] += dx[b, t] plus the head's 2 B rows; EVERY float is written, zero where no row was touched -- dweights in the
+ * layout of bsarec_caser_fwd's weights and dfc in the layout of fc.  Id 0 is an ordinary row.  The head, the fixed-point row
+ * scatter (2^-40 units, exact while |sum| < 2^22), the flush and the closing block are those of bsarec_gru4rec_loss_grad.
+ *   `state` is u64[8] as there: [0] = seed, [1] = forward-step counter, [2] = Adam t.  A call with train != 0 advances the step
+ * counter FIRST and draws with the new value; train = 0 draws nothing (the result of dropout = 0) and touches no counter.
+ *   bsarec_caser_train_step is the above with train = 1 followed by Adam on the three arrays, Adam's t advanced ONCE:
+ * adam_items->params / grads are E / dE with n = V d, adam_weights the convolution's flat array with
+ * n = bsarec_caser_weight_floats(&cfg->conv), adam_fc the fc array with n = bsarec_caser_fc_floats(&cfg->conv); grads are written,
+ * then read.  lr, beta1 and beta2 of the three must agree (one t and one pair of bias corrections serve all); shadow_bf16,
+ * grads2, grads2_n, n_grad_srcs and wimage_plan must be null / 0.
+ *   Launches, all on `stream`, one after the other: the step counter (train != 0), the lookup (which also clears the
+ * accumulator), bsarec_caser_fwd(train = 1), the fc forward, the BPR rows, the fc backward, bsarec_caser_bwd, the item-table
+ * gradient over L B + 2 B rows, its flush with the mean loss (and Adam's t) in a closing block, then one Adam launch per array.
+ * No allocation, no host synchronisation: capturable, and a replay of a captured bsarec_caser_train_step is the NEXT step -- a
+ * fresh mask, the next t.  Every output is bit-deterministic, and the result does not depend on what the workspace holds on entry.
+ *   Workspace: bsarec_caser_step_workspace_bytes(cfg) bytes (host-only query).  In floats, with T = L B and F as above: the
+ * convolution workspace of train = 1 | x [T, d] | z [B, F] | zd [B, F] | s [B, d] | ds [B, d] | dz [B, F] | dx [T, d] |
+ * c [B, rounded up to 4] | loss rows [B, rounded up to 4] | the accumulator, V d 64-bit words.
+ *   Limits (else < 0 before any HIP call): cfg->conv inside the limits of bsarec_caser_workspace_bytes; item_size >= 2;
+ * 0 <= dropout < 1 (NaN refused); every pointer non-null; the float arrays (Adam's four included) and the workspace 16-byte
+ * aligned, ids / answers / neg_answers / state 8-byte, loss_out 4-byte; workspace_bytes at least the queried size; adam_*->n as
+ * above.  ids, answers and neg_answers inside [0, V) are the caller's contract (a value outside is never dereferenced).  Outputs
+ * may not alias inputs, each other or the workspace. */
+typedef struct {
+    bsarec_caser_config_t conv;
+    int item_size;                     /* V >= 2 */
+    float dropout;                     /* p in [0, 1), on z */
+} bsarec_caser_step_config_t;
+long bsarec_caser_fc_floats(const bsarec_caser_config_t *cfg);
+long bsarec_caser_fc_workspace_bytes(int batch, int features, int width);
+int bsarec_caser_fc_fwd(int batch, int features, int width, const float *z, const float *fc, const void *state, int train,
+                        float dropout, float *s, void *workspace, long workspace_bytes, void *stream);
+int bsarec_caser_fc_bwd(int batch, int features, int width, const float *z, const float *fc, const float *s, const float *ds,
+                        const void *state, int train, float dropout, float *dz, float *dfc,
+                        void *workspace, long workspace_bytes, void *stream);
+long bsarec_caser_step_workspace_bytes(const bsarec_caser_step_config_t *cfg);
+int bsarec_caser_loss_grad(const bsarec_caser_step_config_t *cfg, const float *item_emb, const float *weights, const float *fc,
+                           const int64_t *ids, const int64_t *answers, const int64_t *neg_answers,
+                           void *state, int train, float *loss_out, float *d_item_emb, float *dweights, float *dfc,
+                           void *workspace, long workspace_bytes, void *stream);
+int bsarec_caser_train_step(const bsarec_caser_step_config_t *cfg, const int64_t *ids, const int64_t *answers,
+                            const int64_t *neg_answers, const bsarec_adam_t *adam_items, const bsarec_adam_t *adam_weights,
+                            const bsarec_adam_t *adam_fc, void *state, float *loss_out,
+                            void *workspace, long workspace_bytes, void *stream);
+
 /* Tag kernel launches of one id with hipEvents for in-process roofline timing (bench.py):
  * when set, every launch of kernel class `kclass` (see BSAREC_K_*) on the next calls of THIS plan is bracketed
  * by hipEventRecord on the launch stream; bsarec_profile_read returns the summed milliseconds and
