@@ -8,5 +8,6 @@ Host API mirrors the reference (Sun-Sir/BSARec): ``BSARecModel(args)`` with ``fo
 from .model import BSARecModel, SASRecModel, FMLPRecModel, DuoRecModel, MODEL_DICT, param_shapes  # noqa: F401
 from .gru4rec import GRU4RecModel  # noqa: F401
 from .caser import CaserModel  # noqa: F401
+from .bert4rec import BERT4RecModel  # noqa: F401
 
-__all__ = ["BSARecModel", "SASRecModel", "FMLPRecModel", "DuoRecModel", "GRU4RecModel", "CaserModel", "MODEL_DICT", "param_shapes"]
+__all__ = ["BSARecModel", "SASRecModel", "FMLPRecModel", "DuoRecModel", "GRU4RecModel", "CaserModel", "BERT4RecModel", "MODEL_DICT", "param_shapes"]

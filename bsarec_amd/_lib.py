@@ -11,6 +11,7 @@ NEG_MAX = 1024                                   # BSAREC_NEG_MAX: the most nega
 NEG_MAX_DRAWS = 1 << 20                          # BSAREC_NEG_MAX_DRAWS: draws examined before a row fails
 TRAIN_NEG_MAX = 8192                             # BSAREC_TRAIN_NEG_MAX: the most candidates of the sampled-softmax head
 TRAIN_NEG_SITE = 0x4E454753                      # BSAREC_TRAIN_NEG_SITE: Philox counter word 2 of its draws
+CLOZE_SITE = 0x434C4F5A                          # BSAREC_CLOZE_SITE: Philox counter word 2 of BERT4Rec's masking draws
 
 (BUF_LAYER_OUT, BUF_LOGITS, BUF_LOSS, BUF_DSP, BUF_HMIX, BUF_PROBS, BUF_DLAYER_IN, BUF_LOSS_ROWS, BUF_CTX,
  BUF_DLOGITS, BUF_TRAIN_CAND, BUF_TRAIN_CORR, BUF_TRAIN_LOGITS, BUF_TRAIN_DLOGITS, BUF_DROP_BITS) = range(15)
@@ -186,6 +187,7 @@ EXPORTS = {
     "bsarec_plan_set_dense_grad_hook": (C.c_int, [C.c_void_p, HOOK, C.c_void_p, C.c_void_p]),
     "bsarec_plan_set_train_sampler": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bsarec_plan_set_drop_bits": (C.c_int, [C.c_void_p, C.c_int]),
+    "bsarec_plan_set_bidirectional": (C.c_int, [C.c_void_p, C.c_int]),
     "bsarec_drop_bits_bytes": (C.c_long, [C.POINTER(Config)]),
     "bsarec_drop_bits_hidden_bit": (C.c_long, [C.c_int, C.c_long, C.c_long, C.c_int]),
     "bsarec_drop_bits_attn_bit": (C.c_long, [C.c_long, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int]),
@@ -243,6 +245,12 @@ EXPORTS = {
                                              C.c_void_p]),
     "bsarec_ce_head_range_bwd": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bsarec_cloze_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int64] + [C.c_void_p] * 6),
+    "bsarec_cloze_head_workspace_bytes": (C.c_long, [C.c_int] * 3),
+    "bsarec_cloze_head_fwd": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int] +
+                              [C.c_void_p] * 6 + [C.c_long, C.c_void_p]),
+    "bsarec_cloze_head_bwd": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int] +
+                              [C.c_void_p] * 5 + [C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_gru_weight_floats": (C.c_long, [C.POINTER(GruConfig)]),
     "bsarec_gru_workspace_bytes": (C.c_long, [C.POINTER(GruConfig), C.c_int]),
     "bsarec_gru_fwd": (C.c_int, [C.POINTER(GruConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long,

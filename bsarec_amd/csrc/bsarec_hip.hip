@@ -16,6 +16,7 @@
 #include "answer_rank.h"
 #include "info_nce.h"
 #include "ce_head.h"
+#include "cloze.h"
 #include "sampled_softmax.h"
 #include "lazy_adam.h"
 #include "gru.h"
@@ -128,6 +129,7 @@ struct bsarec_plan {
     // (bsarec_plan_set_drop_bits; on by default)
     unsigned char* dbitsL[BSAREC_MAX_LAYERS] = {};
     bool drop_bits = true;
+    bool bidir = false;                        // attention without the causal term (bsarec_plan_set_bidirectional)
 };
 struct PlanScope {                           // marks the plan a C call works on for this thread (nesting-safe)
     bsarec_plan* prev;
@@ -595,6 +597,11 @@ extern "C" int bsarec_plan_set_drop_bits(bsarec_plan_t* p, int on) {
     p->drop_bits = on != 0;
     return 0;
 }
+extern "C" int bsarec_plan_set_bidirectional(bsarec_plan_t* p, int on) {
+    if (!p || on < 0 || on > 1) return -10;
+    p->bidir = on != 0;
+    return 0;
+}
 extern "C" long bsarec_drop_bits_bytes(const bsarec_config_t* cfg) {
     if (!cfg || check_cfg(*cfg) != 0) return -1;
     return drop_bits_wanted(*cfg) ? drop_bits_layer_bytes(cfg->batch, cfg->seq_len, cfg->heads) : 0;
@@ -830,6 +837,7 @@ static int launch_fused_fwd(bsarec_plan& p, int l, bool tr, hipStream_t s, const
         F.e_X0 = p.X[0]; F.e_xhat = p.xhat0; F.e_rstd = p.rstd0; F.e_ids32 = p.ids32;
     }
     F.trash = p.trash;
+    F.q_or = p.bidir ? 255 : 0;            // L <= 64: query | 255 is behind every key
     TopFwdP TF;
     if (top_tail) {
         fill_top_fwd(p, l + 1, tr, TF);
@@ -1004,7 +1012,7 @@ static int generic_layer_fwd(bsarec_plan& p, int l, bool tr, hipStream_t s) {
         g.Nb = L; g.lda = d; g.ldb = d; g.nh = h;
         g.A[0] = b.q; g.B[0] = b.k;
         g.a_sb = (long)L * d; g.a_sh = dh; g.b_sb = (long)L * d; g.b_sh = dh;
-        EpiSoftmax e; e.ids = p.ids32; e.L = L; e.Lp = Lp; e.sqrt_dh = sqrtf((float)dh); e.P = b.probs;
+        EpiSoftmax e; e.ids = p.ids32; e.L = L; e.Lp = Lp; e.sqrt_dh = sqrtf((float)dh); e.P = b.probs; e.bidir = p.bidir;
         DISPATCH_BN(Lp, RET((launch_gemm<64, BN, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, B * h, s))));
     }
     // K4b context = Drop(probs) . V
@@ -2089,6 +2097,7 @@ static int ce_head_params(CeP& P, const float* h, long ldh, const float* item_em
     P.h = h; P.ldh = ldh; P.E = item_emb; P.ans = answers;
     P.B = B; P.V = V; P.d = d; P.S = ce_splits(B, V); P.nblk = ce_nblk(V);
     P.N = (int)N; P.base = base;
+    P.rows = nullptr; P.count = nullptr;          // the identity, all B rows live
     float* w = (float*)workspace;
     P.m = w; P.logl = w + B; P.pm = w + 2L * B; P.pl = P.pm + (long)P.S * B; P.slab = w + ce_stat_floats(B, P.S);
     return 0;
@@ -2146,6 +2155,61 @@ extern "C" int bsarec_ce_head_bwd(const float* h, long ldh, const float* item_em
     if (V < 1) return -10;
     RET(ce_head_params(P, h, ldh, item_emb, B, V, 0, V, d, answers, workspace, workspace_bytes));
     return ce_head_bwd_launch(P, gout, dh, d_item_emb, (hipStream_t)stream);
+}
+
+// The cloze head (BERT4Rec): the same kernels over a row list of capacity R with a live count on the device (ce_head.h).
+extern "C" long bsarec_cloze_head_workspace_bytes(int R, int V, int d) { return bsarec_ce_head_workspace_bytes(R, V, d); }
+
+static int cloze_head_params(CeP& P, const float* h, long ldh, long T, const float* item_emb, int R, int V, int d,
+                             const int32_t* rows, const int64_t* targets, const int32_t* count, void* workspace,
+                             long workspace_bytes) {
+    if (V < 1 || T < 1 || !row_dim_ok(d) || T > 2147483647L / d) return -10;
+    if (!rows || !count || !aligned_to(rows, 4) || !aligned_to(count, 4) || !aligned_to(targets, 8)) return -10;
+    RET(ce_head_params(P, h, ldh, item_emb, R, V, 0, V, d, targets, workspace, workspace_bytes));
+    P.rows = rows; P.count = count;
+    return 0;
+}
+
+extern "C" int bsarec_cloze_head_fwd(const float* h, long ldh, long T, const float* item_emb, int R, int V, int d,
+                                     const int32_t* rows, const int64_t* targets, const int32_t* count, float* loss_out,
+                                     float* rows_out, void* workspace, long workspace_bytes, void* stream) {
+    CeP P;
+    RET(cloze_head_params(P, h, ldh, T, item_emb, R, V, d, rows, targets, count, workspace, workspace_bytes));
+    if (!loss_out) return -10;
+    RET(ce_head_attributes());
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ce_fwd_kernel, dim3(P.S, cdiv(R, CE_ROWS)), dim3(ROW_THREADS), tile_smem(CE_ROWS, d), st, P);
+    hipLaunchKernelGGL(ce_stat_kernel<false>, dim3(1), dim3(1024), 0, st, P, loss_out, rows_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_cloze_head_bwd(const float* h, long ldh, long T, const float* item_emb, int R, int V, int d,
+                                     const int32_t* rows, const int64_t* targets, const int32_t* count, const float* gout,
+                                     void* workspace, long workspace_bytes, float* dh, float* d_item_emb, void* stream) {
+    CeP P;
+    RET(cloze_head_params(P, h, ldh, T, item_emb, R, V, d, rows, targets, count, workspace, workspace_bytes));
+    if (!gout || !dh || !d_item_emb || !aligned_to(dh, 16) || !aligned_to(d_item_emb, 16)) return -10;
+    RET((int)hipMemsetAsync(dh, 0, (size_t)T * d * sizeof(float), (hipStream_t)stream));      // the rows outside the list
+    return ce_head_bwd_launch(P, gout, dh, d_item_emb, (hipStream_t)stream);
+}
+
+// BERT4Rec's masking step (cloze.h)
+extern "C" int bsarec_cloze_mask(const int64_t* ids, int B, int L, float ratio, int slots, int64_t mask_token, const void* state,
+                                 int64_t* masked_ids, int32_t* rows, int64_t* targets, int32_t* count, void* stream) {
+    if (B < 1 || B > 65536 || L < 1 || L > 256 || slots < 1 || slots > L || (long)B * slots > 65536) return -10;
+    if (!(ratio >= 0.0f && ratio <= 1.0f)) return -10;                          // (NaN fails both comparisons)
+    if (!ids || !state || !masked_ids || !rows || !targets || !count) return -10;
+    if (!aligned_to(ids, 8) || !aligned_to(state, 8) || !aligned_to(masked_ids, 8) || !aligned_to(targets, 8) ||
+        !aligned_to(rows, 4) || !aligned_to(count, 4)) return -10;
+    ClozeP P;
+    P.ids = ids; P.B = B; P.L = L; P.slots = slots; P.mask_token = mask_token; P.state = (const uint64_t*)state;
+    const double th = (double)ratio * 4294967296.0;                              // oracle.dropout_threshold
+    P.thresh = th >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)th;
+    P.masked_ids = masked_ids; P.rows = rows; P.targets = targets; P.count = count;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(cloze_draw_kernel, dim3(cdiv(B, CLOZE_THREADS / 64)), dim3(CLOZE_THREADS), 0, st, P);
+    hipLaunchKernelGGL(cloze_compact_kernel, dim3(1), dim3(1024), 0, st, P);
+    return (int)hipGetLastError();
 }
 
 // Range form of the head: one shard of a catalogue split by rows (ce_head.h).  stats -> (the caller's exchange) -> merge -> bwd.

@@ -43,7 +43,20 @@ struct CeP {
     int B, V, d, S, nblk;                    // V: the rows of E
     int N; long base;                        // E's rows are items [base, base + V) of N
     float *m, *logl, *pm, *pl, *slab;        // the workspace
+    const int32_t* rows;                     // row r is row rows[r] of h and of dh; null: the identity
+    const int32_t* count;                    // device scalar: the first min(count[0], B) rows are live; null: all B
 };
+// Row list and live count (the cloze head, cloze.h's output): B stays the CAPACITY -- it sizes the splits, the workspace and the
+// grids on the host -- and n = ce_live(P) <= B rows exist.  A row tile at or behind n exits at once, the dE kernel's row loop
+// ends at n, every mean is over max(n, 1), and an entry of the list at or behind n is never read as an index.  The plain and
+// range entry points pass (null, null): n = B and row r = r, the bits they always gave.
+__device__ __forceinline__ int ce_live(const CeP& P) {
+    if (!P.count) return P.B;
+    const int n = *P.count;
+    return n < 0 ? 0 : (n < P.B ? n : P.B);
+}
+__device__ __forceinline__ long ce_row(const CeP& P, int r) { return P.rows ? (long)P.rows[r] : (long)r; }
+__device__ __forceinline__ float ce_mean_div(int n) { return (float)(n > 0 ? n : 1); }
 
 static inline int ce_nblk(int V) { return (int)(((long)V + CE_ITEMS - 1) / CE_ITEMS); }
 static inline int ce_splits(int B, int V) {
@@ -78,10 +91,11 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_fwd_kernel(const CeP P) {
     __shared__ float wm[ROW_THREADS / 64][CE_ROWS], wl[ROW_THREADS / 64][CE_ROWS];
     constexpr int RB = CE_ROWS / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, half = lane >> 5;
-    const int r0 = blockIdx.y * CE_ROWS;
+    const int r0 = blockIdx.y * CE_ROWS, n = ce_live(P);
+    if (r0 >= n) return;
     int b0, b1;
     split_range(blockIdx.x, P.nblk, P.S, b0, b1);           // this split's item blocks
-    score_stage(P.h, P.ldh, P.B, P.d, r0, CE_ROWS, sh);
+    score_stage(P.h, P.ldh, n, P.d, r0, CE_ROWS, sh, P.rows);
     __syncthreads();
     float m[RB], l[RB];
 #pragma unroll
@@ -118,7 +132,7 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_fwd_kernel(const CeP P) {
         if (half == 0) { wm[wave][rb * 32 + l31] = ma; wl[wave][rb * 32 + l31] = la; }
     }
     __syncthreads();
-    if (tid < CE_ROWS && r0 + tid < P.B) {
+    if (tid < CE_ROWS && r0 + tid < n) {
         float mm = wm[0][tid], ll = wl[0][tid];
 #pragma unroll
         for (int w = 1; w < ROW_THREADS / 64; ++w) softmax_merge(mm, ll, wm[w][tid], wl[w][tid]);
@@ -131,26 +145,28 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_fwd_kernel(const CeP P) {
 // sum and the answer's score where the range owns the answer, else 0 (S = 0, a range without rows: -inf, 0, 0); no loss.
 template <bool RANGE>
 __global__ void __launch_bounds__(1024) ce_stat_kernel(const CeP P, float* __restrict__ loss_out, float* __restrict__ rows_out) {
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, n = ce_live(P);
     float sum = 0.f;
-    for (int b = tid; b < P.B; b += 1024) {
+    if (!RANGE && rows_out)
+        for (int b = n + tid; b < P.B; b += 1024) rows_out[b] = 0.f;
+    for (int b = tid; b < n; b += 1024) {
         const SoftmaxPart part = softmax_merge_splits(P, P.B, b);
         const float m = part.m, l = part.l;
         if (RANGE) {
             const unsigned a = ce_answer(P, b);
             rows_out[b] = m;
             rows_out[P.B + b] = l;
-            rows_out[2 * P.B + b] = a == CE_NO_ANSWER ? 0.f : fr_dot(P.h + (long)b * P.ldh, P.E + (long)a * P.d, P.d);
+            rows_out[2 * P.B + b] = a == CE_NO_ANSWER ? 0.f : fr_dot(P.h + ce_row(P, b) * P.ldh, P.E + (long)a * P.d, P.d);
             continue;
         }
         const float logl = logf(l);
-        const float row = (m - fr_dot(P.h + (long)b * P.ldh, P.E + (long)ce_answer(P, b) * P.d, P.d)) + logl;
+        const float row = (m - fr_dot(P.h + ce_row(P, b) * P.ldh, P.E + (long)ce_answer(P, b) * P.d, P.d)) + logl;
         P.m[b] = m;
         P.logl[b] = logl;
         if (rows_out) rows_out[b] = row;
         sum += row;
     }
-    if (!RANGE) mean_of_1024(sum, P.B, loss_out);
+    if (!RANGE) mean_of_1024(sum, n > 0 ? n : 1, loss_out);
 }
 
 // one workgroup of 1024 lanes: stats_all[world][3][B], every range's ce_stat_kernel<true> output in range order -> the whole
@@ -185,18 +201,19 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_dh_kernel(const CeP P) {
     extern __shared__ __attribute__((aligned(16))) float sh[];
     constexpr int ROWS = 32 * RB;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, half = lane >> 5;
-    const int r0 = blockIdx.y * ROWS, dp = P.d + 4;
+    const int r0 = blockIdx.y * ROWS, dp = P.d + 4, n = ce_live(P);
+    if (r0 >= n) return;
     int b0, b1;
     split_range(blockIdx.x, P.nblk, P.S, b0, b1);           // this split's item blocks
-    score_stage(P.h, P.ldh, P.B, P.d, r0, ROWS, sh);
+    score_stage(P.h, P.ldh, n, P.d, r0, ROWS, sh, P.rows);
     float mx[RB], logl[RB];
     unsigned ans[RB];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
         const int b = r0 + rb * 32 + l31;
-        mx[rb] = b < P.B ? P.m[b] : 0.f;
-        logl[rb] = b < P.B ? P.logl[b] : 0.f;
-        ans[rb] = b < P.B ? ce_answer(P, b) : CE_NO_ANSWER;
+        mx[rb] = b < n ? P.m[b] : 0.f;
+        logl[rb] = b < n ? P.logl[b] : 0.f;
+        ans[rb] = b < n ? ce_answer(P, b) : CE_NO_ANSWER;
     }
     __syncthreads();
     f32x16 out[RB][NDC];
@@ -255,17 +272,19 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_dh_kernel(const CeP P) {
     const int dq = P.d >> 2;
     for (int x = tid; x < ROWS * dq; x += ROW_THREADS) {
         const int i = x / dq, c = (x - i * dq) << 2;
-        if (r0 + i < P.B) st4(slab + (long)(r0 + i) * P.d + c, ld4(&sh[i * dp + c]));
+        if (r0 + i < n) st4(slab + (long)(r0 + i) * P.d + c, ld4(&sh[i * dp + c]));
     }
 }
 
-// one lane per float4 of dh
+// one lane per float4 of the live rows' gradient; row r goes to row ce_row(r) of dh (a row list: the caller zeroed dh)
 __global__ void __launch_bounds__(ROW_THREADS) ce_dh_sum_kernel(const CeP P, const float* __restrict__ gout, float* __restrict__ dh) {
-    const long n4 = (long)P.B * P.d / 4, x = (long)blockIdx.x * ROW_THREADS + threadIdx.x;
+    const int n = ce_live(P);
+    const long n4 = (long)n * P.d / 4, x = (long)blockIdx.x * ROW_THREADS + threadIdx.x;
     if (x >= n4) return;
     f32x4 v = ld4(P.slab + 4 * x);
     for (int s = 1; s < P.S; ++s) v += ld4(P.slab + (long)s * P.B * P.d + 4 * x);
-    st4(dh + 4 * x, v * (*gout / (float)P.B));
+    const unsigned e = (unsigned)(4 * x), r = e / (unsigned)P.d;                 // n d <= 2^24
+    st4(dh + ce_row(P, (int)r) * P.d + (e - r * (unsigned)P.d), v * (*gout / ce_mean_div(n)));
 }
 
 // one workgroup per item block.  Dynamic LDS: CE_ROWS x (d + 4) floats of h.
@@ -276,7 +295,7 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_de_kernel(const CeP P, const f
     __shared__ unsigned ans_s[CE_ROWS];
     constexpr int RB = CE_ROWS / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, half = lane >> 5;
-    const int dp = P.d + 4;
+    const int dp = P.d + 4, n = ce_live(P);
     const unsigned i0 = blockIdx.x * CE_ITEMS + wave * 32, mine = i0 + l31;
     unsigned eoff;
     const float* eb = score_items(P.E, P.V, P.d, i0, eoff);
@@ -285,13 +304,13 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_de_kernel(const CeP P, const f
     for (int dc = 0; dc < NDC; ++dc)
 #pragma unroll
         for (int r = 0; r < 16; ++r) out[dc][r] = 0.f;
-    for (int r0 = 0; r0 < P.B; r0 += CE_ROWS) {
+    for (int r0 = 0; r0 < n; r0 += CE_ROWS) {
         __syncthreads();
-        score_stage(P.h, P.ldh, P.B, P.d, r0, CE_ROWS, sh);
+        score_stage(P.h, P.ldh, n, P.d, r0, CE_ROWS, sh, P.rows);
         if (tid < CE_ROWS) {
-            m_s[tid] = r0 + tid < P.B ? P.m[r0 + tid] : 0.f;
-            logl_s[tid] = r0 + tid < P.B ? P.logl[r0 + tid] : 0.f;
-            ans_s[tid] = r0 + tid < P.B ? ce_answer(P, r0 + tid) : CE_NO_ANSWER;
+            m_s[tid] = r0 + tid < n ? P.m[r0 + tid] : 0.f;
+            logl_s[tid] = r0 + tid < n ? P.logl[r0 + tid] : 0.f;
+            ans_s[tid] = r0 + tid < n ? ce_answer(P, r0 + tid) : CE_NO_ANSWER;
         }
         __syncthreads();
         f32x16 acc[RB];
@@ -310,7 +329,7 @@ __global__ void __launch_bounds__(ROW_THREADS) ce_de_kernel(const CeP P, const f
                 }
             }
     }
-    const float coef = *gout / (float)P.B;
+    const float coef = *gout / ce_mean_div(n);
 #pragma unroll
     for (int dc = 0; dc < NDC; ++dc)
 #pragma unroll

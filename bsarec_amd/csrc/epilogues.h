@@ -85,10 +85,11 @@ struct EpiLN {
 // ---------------------------------------------------------------------------------------------
 // attention probabilities: P = softmax_k(acc / sqrt(dh) + mask)      (needs BN >= L keys)
 // mask(q,k) = 0 if (k <= q and ids[b,k] > 0) else -10000, added in fp32 before the row max, as
-// the reference does (src/model/_abstract_model.py:53-69, src/model/_modules.py:118-128)
+// the reference does (src/model/_abstract_model.py:53-69, src/model/_modules.py:118-128); bidir != 0 (plan option
+// bidirectional) drops the k <= q term: the padding mask alone
 // ---------------------------------------------------------------------------------------------
 struct EpiSoftmax {
-    const int* ids; int L, Lp; float sqrt_dh; float* P;
+    const int* ids; int L, Lp; float sqrt_dh; float* P; int bidir;
 
     template <int BM, int BN, int NT = GEMM_THREADS>
     __device__ __forceinline__ void run(const float* Cs, const TileCtx& c) const {
@@ -105,7 +106,7 @@ struct EpiSoftmax {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int k = lc + j;
-                s[j] = a[j] / sqrt_dh + ((kvalid[j] && k <= q) ? 0.0f : -10000.0f);
+                s[j] = a[j] / sqrt_dh + ((kvalid[j] && (k <= q || bidir)) ? 0.0f : -10000.0f);
                 if (k >= L) s[j] = -INFINITY;
                 mx = fmaxf(mx, s[j]);
             }

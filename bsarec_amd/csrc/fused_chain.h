@@ -407,6 +407,7 @@ fused_chain_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
         float* const probsG = KARG(FusedFwdP, probs);
         float* const ctxG = KARG(FusedFwdP, ctx);
         const float inv_sqrt = 1.0f / sqrtf((float)DH);
+        const int tlast = t | KARG(FusedFwdP, q_or);             // the last key query t sees: t, or (bidirectional) every key
         f32x4 ctx[2];
 #pragma unroll
         for (int hh = 0; hh < NHW; ++hh) {
@@ -435,7 +436,7 @@ fused_chain_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {                        // (selects, not branches)
                     const int key = key0 + r;
-                    const float add = (key <= t && idk[r] > 0) ? 0.0f : -10000.0f;
+                    const float add = (key <= tlast && idk[r] > 0) ? 0.0f : -10000.0f;
                     float sv = __fadd_rn(__fmul_rn(s[kt][r], inv_sqrt), add);      // scaled, THEN masked, two roundings as the reference's two ops
                     sv = key < L ? sv : -INFINITY;
                     s[kt][r] = sv;

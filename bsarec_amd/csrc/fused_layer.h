@@ -32,6 +32,8 @@ struct FusedFwdP {
                             // consumers need (dU = (dT2 . W2) * gelu'; dW2 = dT2^T . gelu), neither has to evaluate erf again
     int L, Lp, cb, heads;
     float alpha, oma, eps;
+    int q_or;               // phase 3 admits key <= (query | q_or): 0 causal, 255 every key (plan option bidirectional); sits in
+                            // the padding in front of drop_f, so no other field moves
     DropP drop_f, drop_p, drop_o, drop_ff;
     float* trash;           // >= 1 KiB scratch: target of the stores of padded rows (keeps the store stream branch-free)
     long long* stamps;      // diagnostic: per-phase s_memtime of workgroup 0 (null in production)
@@ -763,12 +765,13 @@ fused_layer_fwd_kernel(const FusedFwdP P_unused, const TAILP T_unused) {
             float mx = -INFINITY;
             if (act) {
                 mma_ll<MM, DH>(sK + (32 * kt + l31) * FS + head * DH + KH, sQ + query * FS + head * DH + KH, st);
-                // scale, mask (-10000, additive, fp32)
+                // scale, mask (-10000, additive, fp32); the last key a query sees: itself, or (bidirectional) every key
+                const int qlast = query | KARG(FusedFwdP, q_or);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = 32 * kt + rho(r) + 4 * half;
                     float s = -INFINITY;
-                    if (key < L) s = st[r] / sqrt_dh + ((key <= query && sIds[key] > 0) ? 0.0f : -10000.0f);
+                    if (key < L) s = st[r] / sqrt_dh + ((key <= qlast && sIds[key] > 0) ? 0.0f : -10000.0f);
                     st[r] = s;
                     mx = fmaxf(mx, s);
                 }

@@ -13,23 +13,32 @@
 #include "kernels.h"
 
 // rows [r0, r0 + rows) of h (any row stride ldh >= d) into sh[rows][d + 4]; zeros behind row B.  Whole float4s when the rows
-// are 16-byte aligned (h is, so ldh % 4 == 0 decides for the workgroup), single floats otherwise.
-__device__ __forceinline__ void score_stage(const float* __restrict__ h, long ldh, int B, int d, int r0, int rows, float* sh) {
+// are 16-byte aligned (h is, so ldh % 4 == 0 decides for the workgroup), single floats otherwise.  With a row list, row r is
+// row list[r] of h (ce_head.h: the cloze head's scattered tokens); entries at or behind B are never read.  The list is a
+// workgroup-uniform choice made once, outside the copy loops: without one the loops are the ones they always were.
+template <bool LIST>
+__device__ __forceinline__ void score_stage_rows(const float* __restrict__ h, long ldh, int B, int d, int r0, int rows, float* sh,
+                                                 const int32_t* __restrict__ list) {
     const int dp = d + 4;
     if ((ldh & 3) == 0) {
         const int dq = d >> 2;
         for (int x = threadIdx.x; x < rows * dq; x += ROW_THREADS) {
             const int i = x / dq, c = (x - i * dq) << 2;
             f32x4 v = {0, 0, 0, 0};
-            if (r0 + i < B) v = ld4(h + (long)(r0 + i) * ldh + c);
+            if (r0 + i < B) v = ld4(h + (long)(LIST ? list[r0 + i] : r0 + i) * ldh + c);
             st4(&sh[i * dp + c], v);
         }
     } else {
         for (int x = threadIdx.x; x < rows * d; x += ROW_THREADS) {
             const int i = x / d, c = x - i * d;
-            sh[i * dp + c] = r0 + i < B ? h[(long)(r0 + i) * ldh + c] : 0.f;
+            sh[i * dp + c] = r0 + i < B ? h[(long)(LIST ? list[r0 + i] : r0 + i) * ldh + c] : 0.f;
         }
     }
+}
+__device__ __forceinline__ void score_stage(const float* __restrict__ h, long ldh, int B, int d, int r0, int rows, float* sh,
+                                            const int32_t* __restrict__ list = nullptr) {
+    if (list) score_stage_rows<true>(h, ldh, B, d, r0, rows, sh, list);
+    else score_stage_rows<false>(h, ldh, B, d, r0, rows, sh, nullptr);
 }
 // A wave's 32 items i0 .. i0 + 31 (i0 wave-uniform) as a wave-uniform row pointer into E and this lane's offset from it in
 // floats (item i0 + l31); an item behind V reads a row that exists.

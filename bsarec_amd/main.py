@@ -28,7 +28,32 @@ from .model import MODEL_DICT as _MODEL_DICT
 # --model_type -> class: the table of model.py and Caser (bsarec_amd/caser.py).  Caser is registered HERE: the key set of
 # bsarec_amd.model.MODEL_DICT is pinned (tests/test_gru_cpu.py), so that table stays as it is
 MODEL_DICT = dict(_MODEL_DICT, caser=CaserModel)
+# ... and MODEL_DICT's key set is pinned too (tests/test_caser_cpu.py): later siblings register in a table of their own, which
+# model_class consults after MODEL_DICT
+from .bert4rec import BERT4RecModel
+SIBLING_MODELS = {"bert4rec": BERT4RecModel}
 from .trainer import Trainer
+
+
+def model_class(model_type: str):
+    """--model_type -> class (case-insensitive): MODEL_DICT, then SIBLING_MODELS."""
+    key = model_type.lower()
+    if key in MODEL_DICT:
+        return MODEL_DICT[key]
+    if key in SIBLING_MODELS:
+        return SIBLING_MODELS[key]
+    raise KeyError(model_type)
+
+
+def mask_ratio_value(text: str) -> float:
+    """--mask_ratio: a share in (0, 1]."""
+    try:
+        r = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}") from None
+    if not 0.0 < r <= 1.0:
+        raise argparse.ArgumentTypeError(f"{r} outside (0, 1]")
+    return r
 
 
 def cutoff_list(text: str) -> tuple:
@@ -177,6 +202,11 @@ def parse_args(argv=None):
     p.add_argument("--caser_step", default=argparse.SUPPRESS, choices=("torch", "fused"),
                    help="Caser: step through autograd and torch.optim.Adam (default) or through the one-call HIP step "
                         "(lookup, convolutions, fc1 with Philox dropout, BPR head, item-table gradient and Adam in the library)")
+    # not reference flags: BERT4Rec's cloze task (--model_type BERT4Rec).  Absent unless given
+    p.add_argument("--mask_ratio", default=argparse.SUPPRESS, type=mask_ratio_value,
+                   help="BERT4Rec: share of the real positions replaced by the mask token in a training step (default 0.2)")
+    p.add_argument("--bert_mask_slots", default=argparse.SUPPRESS, type=int,
+                   help="BERT4Rec: loss positions kept per sequence (default min(L, 2 ceil(mask_ratio L)))")
     args = p.parse_args(argv)
     n = getattr(args, "eval_negatives", 0)
     if n > 0 and hasattr(args, "eval_full_rank"):
@@ -234,7 +264,7 @@ def run(args, user_seq, logger=None, checkpoint_path=None):
     if (getattr(args, "eval_negatives", 0) > 0 and getattr(args, "eval_sampler", "uniform") == "popularity") or \
             (getattr(args, "train_negatives", 0) > 0 and getattr(args, "train_sampler", "uniform") == "popularity"):
         args.item_popularity = D.item_popularity(user_seq, args.item_size)    # training part only: one table for both splits
-    model = MODEL_DICT[args.model_type.lower()](args=args)
+    model = model_class(args.model_type)(args=args)
     if getattr(model, "needs_negatives", False):
         train_dl.enable_negatives(user_seq, args.item_size)
     if getattr(model, "needs_same_target", False):

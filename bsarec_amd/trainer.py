@@ -85,6 +85,8 @@ class Trainer:
         if not arena:
             self._check_arenaless(model, args, process_group)
         check_train_head(model, args, train_dataloader, process_group)
+        if getattr(model, "check_trainer", None) is not None:       # a sibling model's own refusals (BERT4Rec: single GPU only)
+            model.check_trainer(args, process_group)
         self.logger = logger or _NullLogger()
         if not torch.cuda.is_available() or getattr(args, "no_cuda", False):
             raise RuntimeError("bsarec_amd.Trainer needs an MI355X: there is no CPU training path "
@@ -246,7 +248,13 @@ class Trainer:
 
     def predict_full(self, seq_out):
         """src/trainers.py:62-68 (kept for API parity; evaluation uses model.full_logits)."""
-        return torch.matmul(seq_out, self.model.item_embeddings.weight.transpose(0, 1))
+        return torch.matmul(seq_out, self._item_table().transpose(0, 1))
+
+    def _item_table(self):
+        """The table a ranking scores against: ``model.catalogue_weight()`` where the model has it (BERT4Rec: the table without
+        its mask-token row), else the item embedding."""
+        cw = getattr(self.model, "catalogue_weight", None)
+        return cw() if cw is not None else self.model.item_embeddings.weight
 
     def get_full_sort_score(self, epoch, answers, pred_list, extra_ks=None):
         """src/trainers.py:70-83: answers int[n], pred_list int[n, K] (device tensors or numpy), K >= 20.  ``extra_ks``
@@ -635,7 +643,7 @@ class Trainer:
         depth = max((20,) + extra_cutoffs(self.args))
         # a model without ``full_logits`` (GRU4Rec) takes topk_full on the default ("dense") path too: it returns the same
         # lists by construction, from ``last_hidden`` and the item table alone
-        fused = getattr(self.args, "eval_full_rank", "dense") == "fused" or not hasattr(self.model, "full_logits")
+        fused = getattr(self.args, "eval_full_rank", "dense") == "fused" or getattr(self.model, "full_logits", None) is None
         for batch in dataloader:
             batch = tuple(t.to(self.device, non_blocking=True) for t in batch)
             user_ids, input_ids, answers, _, _ = batch
@@ -664,7 +672,7 @@ class Trainer:
         if not 1 <= k <= min(L.TOPK_MAX, V):
             raise ValueError(f"topk_full: k = {k}, expected 1..{min(L.TOPK_MAX, V)}")
         users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        return self._full_rank(self.model.last_hidden(input_ids), self.model.item_embeddings.weight.detach(), k, users,
+        return self._full_rank(self.model.last_hidden(input_ids), self._item_table().detach(), k, users,
                                seen_csr(self.args.train_matrix, self.device), values=return_scores)
 
     def answer_ranks(self, user_ids, input_ids, answers, return_scores: bool = False):
@@ -673,7 +681,7 @@ class Trainer:
         no list, no depth limit, no working memory.  int32 ranks [B], 0 = first (-1: an answer outside [0, item_size)); with
         ``return_scores`` also the answers' fp32 scores (0 for a seen answer)."""
         users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        return answer_rank(self.model.last_hidden(input_ids), self.model.item_embeddings.weight.detach(), answers, users,
+        return answer_rank(self.model.last_hidden(input_ids), self._item_table().detach(), answers, users,
                            seen_csr(self.args.train_matrix, self.device), scores=return_scores)
 
     def sampled_ranks(self, user_ids, input_ids, answers, return_candidates: bool = False, tag: int = 1):
@@ -693,7 +701,7 @@ class Trainer:
         users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
         ans = answers.to(device=self.device, dtype=torch.int64).contiguous()
         check_pool(self._neg_tables, users.cpu().numpy(), ans.cpu().numpy(), n, V)
-        out = sampled_rank(self.model.last_hidden(input_ids), self.model.item_embeddings.weight.detach(), users, ans,
+        out = sampled_rank(self.model.last_hidden(input_ids), self._item_table().detach(), users, ans,
                            seen_csr(self.args.train_matrix, self.device), n, seed, tag, cum=self._neg_tables["cum"],
                            candidates=return_candidates)
         rank = out[0] if return_candidates else out

@@ -255,6 +255,16 @@ long bsarec_drop_bits_bytes(const bsarec_config_t *cfg);
 long bsarec_drop_bits_hidden_bit(int slot, long tokens, long token, int column);
 long bsarec_drop_bits_attn_bit(long tokens, int heads, long b, int head, int query, int key);
 
+/* Attention without the causal term (plan option bidirectional; the encoder of the BERT4Rec sibling model).
+ *   on = 0 (default): mask(q, k) = (k <= q && ids[b, k] > 0) ? 0 : -10000 -- the reference's causal + padding mask;
+ *   on = 1:           mask(q, k) = ids[b, k] > 0 ? 0 : -10000 -- the padding mask alone.
+ * Either is added in fp32 before the row maximum.  A run-time argument of the three forward kernels that form the mask (the
+ * LDS-phase block kernel, the register-chain block kernel, the generic path's softmax epilogue): no kernel is instantiated for
+ * it, and a causal plan computes the bits it always did.  The backward kernels read the saved probabilities and form no mask;
+ * the one-row top block of bsarec_forward_last looks at the last row, where both masks agree.  Change it between steps, not
+ * between a forward and its backward. */
+int bsarec_plan_set_bidirectional(bsarec_plan_t *plan, int on);
+
 /* Byte offset of a named buffer inside the workspace, or -1. */
 long bsarec_buffer_offset(const bsarec_plan_t *plan, int buffer, int layer);
 
@@ -564,6 +574,53 @@ int bsarec_ce_head_range_merge(const float *stats_all, int world, int Bg, void *
 int bsarec_ce_head_range_bwd(const float *h, long ldh, const float *item_rows, int Bg, int Vs, long col_base, long item_size,
                              int d, const int64_t *answers, const float *gout, void *workspace, long workspace_bytes,
                              float *dh_part, float *dE_rows, void *stream);
+
+/* BERT4Rec's masking step (csrc/cloze.h): which tokens of a batch are replaced by the mask token, and the compacted list of
+ * the positions that carry a loss term, for bsarec_cloze_head_fwd / _bwd.  No plan.
+ *   Draw: token e = b * L + t takes word e & 3 of Philox4x32-10 call (lo32(e >> 2), hi32(e >> 2), BSAREC_CLOZE_SITE,
+ *   lo32(state[1])) keyed by state[0] -- the dropout stream at a site no dropout mask uses; threshold floor(ratio * 2^32),
+ *   at most 2^32 - 1.
+ *   drawn(b, t) = ids[b, t] > 0 && word < threshold; a row that draws nothing while ids[b, L - 1] > 0 draws position L - 1,
+ *   so every sequence that ends in an item gives at least one row.
+ *   masked_ids[b, t] = drawn ? mask_token : ids[b, t]                                   int64 [B, L]
+ *   The loss positions of row b are its LAST min(count_b, slots) drawn positions; earlier drawn ones stay masked in the input
+ *   and carry no loss.  rows[R], R = B * slots: the token indices b * L + t of all loss positions, ascending, no gaps;
+ *   targets[r] = ids at that token; count[0] = n, the number of live rows; rows = -1 and targets = 0 at r >= n.
+ *   Every output element is written; the outputs depend on (ids, ratio, slots, state[0], state[1]) only.  `state` (u64[8], as
+ *   a plan's) is read, not advanced.
+ *   Execution: two launches on `stream`; no atomics, no allocation, no host synchronisation: capturable, and a replay reads the
+ *   state's current step.  rows doubles as the staging area of the compaction.
+ *   Limits (else < 0 before any HIP call): 1 <= B <= 65536; 1 <= L <= 256; 1 <= slots <= L; B * slots <= 65536;
+ *   0 <= ratio <= 1 (NaN refused); every pointer non-null, ids / masked_ids / targets / state 8-byte aligned, rows / count
+ *   4-byte aligned. */
+#define BSAREC_CLOZE_SITE 0x434C4F5Au
+int bsarec_cloze_mask(const int64_t *ids, int B, int L, float ratio, int slots, int64_t mask_token, const void *state,
+                      int64_t *masked_ids, int32_t *rows, int64_t *targets, int32_t *count, void *stream);
+
+/* The cloze loss: bsarec_ce_head_fwd / _bwd on the rows of h that a row list names, of which the first n are live -- the SAME
+ * kernels with a row list and a live count (csrc/ce_head.h), nothing of size rows x V.  No plan.
+ *   h: [T, d] with row stride ldh (the encoder's [B, L, d] output: T = B * L).  rows[R], targets[R], count[1] as
+ *   bsarec_cloze_mask writes them; n = min(count[0], R) (< 0 counts as 0), read on the device.
+ *   For r < n: row_r = lse_r - s(r, a_r) over the items j < V, the scores those of h[rows[r]] through the fmaf chain of
+ *   bsarec_ce_head_fwd, a_r = targets[r] clamped to [0, V).  loss_out[0] = (sum_{r < n} row_r) / max(n, 1).  rows_out
+ *   (nullable, float[R]): row_r, and 0 at r >= n.
+ *   Backward for the device scalar g = gout[0]: G_rj = g / max(n, 1) * (softmax_rj - [j == a_r]);  dh is contiguous [T, d] and
+ *   every float of it is written: row rows[r] holds sum_j G_rj item_emb[j], every other row 0;  d_item_emb [V, d], every row
+ *   overwritten with sum_{r < n} G_rj h[rows[r]].  n = 0: loss 0 and all-zero gradients.
+ *   rows[r < n] are distinct and inside [0, T) -- the caller's contract, which bsarec_cloze_mask keeps; entries at r >= n are
+ *   never read as indices.  item_emb may be the first V rows of a larger table (BERT4Rec's has V + 1: the mask token is no class).
+ *   The splits, the grids and the workspace (bsarec_cloze_head_workspace_bytes = bsarec_ce_head_workspace_bytes(R, V, d)) are
+ *   sized by the capacity R on the host; row tiles at or behind n exit at once, so the time follows n.
+ *   Execution: as bsarec_ce_head_fwd / _bwd (the backward adds one memset node for dh); capturable, bit-deterministic.
+ *   Limits (else < 0 before any HIP call): those of bsarec_ce_head_fwd / _bwd with B := R; 1 <= T < 2^31 / d; rows, targets,
+ *   count non-null, rows / count 4-byte and targets 8-byte aligned. */
+long bsarec_cloze_head_workspace_bytes(int R, int V, int d);
+int bsarec_cloze_head_fwd(const float *h, long ldh, long T, const float *item_emb, int R, int V, int d, const int32_t *rows,
+                          const int64_t *targets, const int32_t *count, float *loss_out, float *rows_out, void *workspace,
+                          long workspace_bytes, void *stream);
+int bsarec_cloze_head_bwd(const float *h, long ldh, long T, const float *item_emb, int R, int V, int d, const int32_t *rows,
+                          const int64_t *targets, const int32_t *count, const float *gout, void *workspace,
+                          long workspace_bytes, float *dh, float *d_item_emb, void *stream);
 
 /* GRU stack of the GRU4Rec sibling model (csrc/gru.h): num_layers bias-free GRU layers in torch's gate order (r, z, n), h_0 = 0,
  * no dropout between layers, and an optional Linear on top -- what nn.GRU(input_size, hidden_size, num_layers, bias=False,
