@@ -24,6 +24,7 @@
 #include "gru4rec_cand.h"
 #include "caser.h"
 #include "caser_step.h"
+#include "fea_attn.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -2564,6 +2565,81 @@ extern "C" int bsarec_caser_bwd(const bsarec_caser_config_t* cfg, const float* x
     hipLaunchKernelGGL(caser_dx_kernel, dim3(c.batch, cdiv(quads, 256)), dim3(256), (size_t)cells * 6, s, P);
     hipLaunchKernelGGL(caser_dwh_kernel, dim3(cells, cdiv(quads, 256)), dim3(256), 0, s, P);
     hipLaunchKernelGGL(caser_dv_kernel, dim3(c.seq_len + 1, c.n_v), dim3(64), 0, s, P);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// FEARec autocorrelation attention (fea_attn.h): plan-less, one linear chain on the caller's stream, no allocation
+// ---------------------------------------------------------------------------------------------
+static int fea_check(const bsarec_fea_attn_config_t* c) {
+    if (!c) return -10;
+    if (c->batch < 1 || c->batch > 65536 || c->seq_len < 2 || c->seq_len > 256) return -10;
+    if (!row_dim_ok(c->width)) return -10;
+    if (c->lo < 0 || c->lo >= c->hi || c->hi > c->seq_len / 2 + 1) return -10;
+    if (c->topk < 1 || c->topk > 32 || c->topk > c->seq_len) return -10;
+    return 0;
+}
+
+// workspace, in 4-byte words, every part at a multiple of 4: m [B][L] | idx (train: [k], else [B][k]) | p [B][k] | h [L] | cv [B][L]
+struct FeaWs { long m, idx, p, h, cv, total; };
+static FeaWs fea_ws(const bsarec_fea_attn_config_t& c) {
+    FeaWs w;
+    const long B = c.batch, L = c.seq_len, k = c.topk;
+    w.m = 0;
+    w.idx = rup(B * L, 4);
+    w.p = w.idx + rup(c.train ? k : B * k, 4);
+    w.h = w.p + rup(B * k, 4);
+    w.cv = w.h + rup(L, 4);
+    w.total = w.cv + rup(B * L, 4);
+    return w;
+}
+
+extern "C" long bsarec_fea_attn_workspace_bytes(const bsarec_fea_attn_config_t* cfg) {
+    if (fea_check(cfg)) return -10;
+    return fea_ws(*cfg).total * 4;
+}
+
+static FeaP fea_params(const bsarec_fea_attn_config_t& c, void* workspace) {
+    const FeaWs w = fea_ws(c);
+    float* f = (float*)workspace;
+    FeaP P = {};
+    P.m = f + w.m; P.idx = (int*)(f + w.idx); P.p = f + w.p; P.h = f + w.h; P.cv = f + w.cv;
+    P.B = c.batch; P.L = c.seq_len; P.D = c.width; P.lo = c.lo; P.hi = c.hi; P.topk = c.topk; P.train = c.train != 0;
+    return P;
+}
+
+extern "C" int bsarec_fea_attn_fwd(const bsarec_fea_attn_config_t* cfg, const float* q, const float* k, const float* v, float* out,
+                                   void* workspace, long workspace_bytes, void* stream) {
+    RET(fea_check(cfg));
+    if (!aligned_to(q, 16) || !aligned_to(k, 16) || !aligned_to(v, 16) || !aligned_to(out, 16) || !aligned_to(workspace, 16))
+        return -10;                                                                                        // null fails too
+    if (workspace_bytes < fea_ws(*cfg).total * 4) return -10;
+    const bsarec_fea_attn_config_t& c = *cfg;
+    hipStream_t s = (hipStream_t)stream;
+    FeaP P = fea_params(c, workspace);
+    P.q = q; P.k = k; P.v = v; P.out = out;
+    hipLaunchKernelGGL(fea_band_kernel, dim3(1), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(fea_corr_kernel, dim3(c.batch), dim3(256), 0, s, P);
+    if (P.train) hipLaunchKernelGGL(fea_select_kernel, dim3(1), dim3(1024), 0, s, P);
+    hipLaunchKernelGGL(fea_shift_kernel<true>, dim3(c.batch, cdiv((long)c.seq_len * (c.width / 4), 256)), dim3(256), 0, s, P);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_fea_attn_bwd(const bsarec_fea_attn_config_t* cfg, const float* q, const float* k, const float* v,
+                                   const float* dout, void* workspace, long workspace_bytes, float* dq, float* dk, float* dv,
+                                   void* stream) {
+    RET(fea_check(cfg));
+    if (!aligned_to(q, 16) || !aligned_to(k, 16) || !aligned_to(v, 16) || !aligned_to(dout, 16) || !aligned_to(workspace, 16) ||
+        !aligned_to(dq, 16) || !aligned_to(dk, 16) || !aligned_to(dv, 16))
+        return -10;
+    if (workspace_bytes < fea_ws(*cfg).total * 4) return -10;
+    const bsarec_fea_attn_config_t& c = *cfg;
+    hipStream_t s = (hipStream_t)stream;
+    FeaP P = fea_params(c, workspace);
+    P.q = q; P.k = k; P.v = v; P.dout = dout; P.dq = dq; P.dk = dk; P.dv = dv;
+    hipLaunchKernelGGL(fea_dp_kernel, dim3(c.batch), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(fea_shift_kernel<false>, dim3(c.batch, cdiv((long)c.seq_len * (c.width / 4), 256)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(fea_dqk_kernel, dim3(c.batch, 2), dim3(256), 0, s, P);
     return (int)hipGetLastError();
 }
 

@@ -32,17 +32,51 @@ MODEL_DICT = dict(_MODEL_DICT, caser=CaserModel)
 # model_class consults after MODEL_DICT
 from .bert4rec import BERT4RecModel
 SIBLING_MODELS = {"bert4rec": BERT4RecModel}
+# ... as is SIBLING_MODELS' (tests/test_cloze_cpu.py).  MODEL_REGISTRY is the open table: tests check membership in it, never its
+# key set, so the next sibling adds a key here
+from .fearec import FEARecModel
+MODEL_REGISTRY = {"fearec": FEARecModel}
 from .trainer import Trainer
 
 
 def model_class(model_type: str):
-    """--model_type -> class (case-insensitive): MODEL_DICT, then SIBLING_MODELS."""
+    """--model_type -> class (case-insensitive): MODEL_DICT, then SIBLING_MODELS, then MODEL_REGISTRY."""
     key = model_type.lower()
-    if key in MODEL_DICT:
-        return MODEL_DICT[key]
-    if key in SIBLING_MODELS:
-        return SIBLING_MODELS[key]
+    for table in (MODEL_DICT, SIBLING_MODELS, MODEL_REGISTRY):
+        if key in table:
+            return table[key]
     raise KeyError(model_type)
+
+
+def ratio_value(lo_open: bool):
+    """--global_ratio (0, 1] / --spatial_ratio [0, 1]."""
+    def parse(text: str) -> float:
+        try:
+            r = float(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not a number: {text!r}") from None
+        if not ((0.0 < r if lo_open else 0.0 <= r) and r <= 1.0):                # (NaN fails)
+            raise argparse.ArgumentTypeError(f"{r} outside {'(0' if lo_open else '[0'}, 1]")
+        return r
+    return parse
+
+
+def positive_value(text: str) -> float:
+    """--fea_topk_factor: a finite number > 0."""
+    try:
+        r = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}") from None
+    if not 0.0 < r < float("inf"):
+        raise argparse.ArgumentTypeError(f"{r} is not a finite number > 0")
+    return r
+
+
+def bool_value(text: str) -> bool:
+    """--fredom: True / False."""
+    if text not in ("True", "False"):
+        raise argparse.ArgumentTypeError(f"expected True or False, got {text!r}")
+    return text == "True"
 
 
 def mask_ratio_value(text: str) -> float:
@@ -207,6 +241,17 @@ def parse_args(argv=None):
                    help="BERT4Rec: share of the real positions replaced by the mask token in a training step (default 0.2)")
     p.add_argument("--bert_mask_slots", default=argparse.SUPPRESS, type=int,
                    help="BERT4Rec: loss positions kept per sequence (default min(L, 2 ceil(mask_ratio L)))")
+    # not reference-checked flags: FEARec's layer and loss (--model_type FEARec).  Absent unless given
+    p.add_argument("--global_ratio", default=argparse.SUPPRESS, type=ratio_value(True),
+                   help="FEARec: share of the rfft bins in a layer's band, in (0, 1] (default 0.6)")
+    p.add_argument("--spatial_ratio", default=argparse.SUPPRESS, type=ratio_value(False),
+                   help="FEARec: weight of the causal softmax attention beside the autocorrelation attention, in [0, 1] (default 0.1)")
+    p.add_argument("--fredom", default=argparse.SUPPRESS, type=bool_value,
+                   help="FEARec: True / False, the frequency-domain regulariser of the us_x loss (default True)")
+    p.add_argument("--fredom_type", default=argparse.SUPPRESS, choices=("un", "su", "us_x"),
+                   help="FEARec: which views the frequency-domain regulariser compares (default us_x)")
+    p.add_argument("--fea_topk_factor", default=argparse.SUPPRESS, type=positive_value,
+                   help="FEARec: the layer keeps int(factor ln L) delays, clamped to 1 .. min(L, 32) (default 1.0)")
     args = p.parse_args(argv)
     n = getattr(args, "eval_negatives", 0)
     if n > 0 and hasattr(args, "eval_full_rank"):

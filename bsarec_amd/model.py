@@ -1010,6 +1010,80 @@ DUOREC_HEADS = ("torch", "hip")
 DUOREC_CE_HEADS = ("torch", "hip")
 
 
+def duorec_mask_correlated(batch_size, device):
+    n = 2 * batch_size
+    mask = torch.ones((n, n), dtype=torch.bool, device=device)
+    mask.fill_diagonal_(False)
+    idx = torch.arange(batch_size, device=device)
+    mask[idx, batch_size + idx] = False
+    mask[batch_size + idx, idx] = False
+    return mask
+
+
+def duorec_info_nce(z_i, z_j, temp, batch_size, sim="dot"):
+    """duorec.py:47-78: positives = the two views of a sequence, negatives = the other 2(B - 1) rows of the batch."""
+    n = 2 * batch_size
+    z = torch.cat((z_i, z_j), dim=0)
+    if sim == "cos":
+        s = torch.nn.functional.cosine_similarity(z.unsqueeze(1), z.unsqueeze(0), dim=2) / temp
+    else:
+        s = torch.mm(z, z.T) / temp
+    pos = torch.cat((torch.diag(s, batch_size), torch.diag(s, -batch_size)), dim=0).reshape(n, 1)
+    neg = s[duorec_mask_correlated(batch_size, z.device)].reshape(n, -1)
+    labels = torch.zeros(n, dtype=torch.long, device=z.device)
+    return torch.cat((pos, neg), dim=1), labels
+
+
+def duorec_head_options(model, args):
+    """The options of the DuoRec loss on ``model`` (DuoRecModel, FEARecModel): tau, ssl, sim, lmd, lmd_sem, the two head
+    switches and the workspace pool of the HIP InfoNCE head."""
+    model.tau = float(getattr(args, "tau", 1.0))
+    model.ssl = getattr(args, "ssl", "us_x")
+    model.sim = getattr(args, "sim", "dot")
+    model.lmd = float(getattr(args, "lmd", 0.1))
+    model.lmd_sem = float(getattr(args, "lmd_sem", 0.1))
+    model.duorec_head = getattr(args, "duorec_head", "torch")
+    if model.duorec_head not in DUOREC_HEADS:
+        raise ValueError(f"duorec_head must be one of {DUOREC_HEADS}, got {model.duorec_head!r}")
+    model.duorec_ce_head = getattr(args, "duorec_ce_head", "torch")
+    if model.duorec_ce_head not in DUOREC_CE_HEADS:
+        raise ValueError(f"duorec_ce_head must be one of {DUOREC_CE_HEADS}, got {model.duorec_ce_head!r}")
+    model._nce_pool = {}                         # (B, d, sim, device) -> free workspaces of bsarec_info_nce_*
+
+
+def duorec_loss(model, encode, input_ids, answers, same_target):
+    """src/model/duorec.py:95-127 on ``encode(ids) -> [B, L, d]`` (one call per view, in the reference's order): the loss and
+    the views' whole outputs {"seq", "aug", "sem"} (those the ``ssl`` variant ran).  ``model`` carries the options of
+    duorec_head_options, ``item_embeddings`` and ``catalogue_ce``."""
+    ce = torch.nn.functional.cross_entropy
+    B = input_ids.shape[0]
+    if model.duorec_head == "hip":
+        def term(z_i, z_j):
+            return _InfoNceFn.apply(model, z_i, z_j)
+    else:
+        def term(z_i, z_j):
+            lg, lb = duorec_info_nce(z_i, z_j, model.tau, B, model.sim)
+            return ce(lg, lb)
+    views = {"seq": encode(input_ids)}
+    seq_output = views["seq"][:, -1, :]
+    if model.duorec_ce_head == "hip":
+        loss = model.catalogue_ce(seq_output, answers)
+    else:
+        logits = torch.matmul(seq_output, model.item_embeddings.weight.transpose(0, 1))
+        loss = ce(logits, answers.to(logits.device))
+    if model.ssl in ("us", "un"):
+        views["aug"] = encode(input_ids)
+        loss = loss + model.lmd * term(seq_output, views["aug"][:, -1, :])
+    if model.ssl in ("us", "su"):
+        views["sem"] = encode(same_target)
+        loss = loss + model.lmd_sem * term(seq_output, views["sem"][:, -1, :])
+    if model.ssl == "us_x":
+        views["aug"] = encode(input_ids)
+        views["sem"] = encode(same_target)
+        loss = loss + model.lmd_sem * term(views["aug"][:, -1, :], views["sem"][:, -1, :])
+    return loss, views
+
+
 class DuoRecModel(SASRecModel):
     """Sibling model: ``MODEL_DICT['duorec']``, src/model/duorec.py.  The encoder is SASRec's
     TransformerEncoder (a BSARec plan with alpha = 0, same 36 state_dict keys); the loss is the full-catalogue CE of the
@@ -1028,73 +1102,21 @@ class DuoRecModel(SASRecModel):
 
     def __init__(self, args):
         super().__init__(args)
-        self.tau = float(getattr(args, "tau", 1.0))
-        self.ssl = getattr(args, "ssl", "us_x")
-        self.sim = getattr(args, "sim", "dot")
-        self.lmd = float(getattr(args, "lmd", 0.1))
-        self.lmd_sem = float(getattr(args, "lmd_sem", 0.1))
-        self.duorec_head = getattr(args, "duorec_head", "torch")
-        if self.duorec_head not in DUOREC_HEADS:
-            raise ValueError(f"duorec_head must be one of {DUOREC_HEADS}, got {self.duorec_head!r}")
-        self.duorec_ce_head = getattr(args, "duorec_ce_head", "torch")
-        if self.duorec_ce_head not in DUOREC_CE_HEADS:
-            raise ValueError(f"duorec_ce_head must be one of {DUOREC_CE_HEADS}, got {self.duorec_ce_head!r}")
-        self._nce_pool = {}                      # (B, d, sim, device) -> free workspaces of bsarec_info_nce_*
+        duorec_head_options(self, args)
 
-    @staticmethod
-    def _mask_correlated(batch_size, device):
-        n = 2 * batch_size
-        mask = torch.ones((n, n), dtype=torch.bool, device=device)
-        mask.fill_diagonal_(False)
-        idx = torch.arange(batch_size, device=device)
-        mask[idx, batch_size + idx] = False
-        mask[batch_size + idx, idx] = False
-        return mask
+    _mask_correlated = staticmethod(duorec_mask_correlated)
 
     def info_nce(self, z_i, z_j, temp, batch_size, sim="dot"):
         """duorec.py:47-78: positives = the two views of a sequence, negatives = the other 2(B - 1) rows of the batch."""
-        n = 2 * batch_size
-        z = torch.cat((z_i, z_j), dim=0)
-        if sim == "cos":
-            s = torch.nn.functional.cosine_similarity(z.unsqueeze(1), z.unsqueeze(0), dim=2) / temp
-        else:
-            s = torch.mm(z, z.T) / temp
-        pos = torch.cat((torch.diag(s, batch_size), torch.diag(s, -batch_size)), dim=0).reshape(n, 1)
-        neg = s[self._mask_correlated(batch_size, z.device)].reshape(n, -1)
-        labels = torch.zeros(n, dtype=torch.long, device=z.device)
-        return torch.cat((pos, neg), dim=1), labels
+        return duorec_info_nce(z_i, z_j, temp, batch_size, sim)
 
     def info_nce_loss(self, z_i, z_j):
         """``F.cross_entropy(*self.info_nce(z_i, z_j, self.tau, B, self.sim))`` as one HIP autograd node."""
         return _InfoNceFn.apply(self, z_i, z_j)
 
     def calculate_loss(self, input_ids, answers, neg_answers=None, same_target=None, user_ids=None):
-        """src/model/duorec.py:95-127."""
-        ce = torch.nn.functional.cross_entropy
-        B = input_ids.shape[0]
-        if self.duorec_head == "hip":
-            term = self.info_nce_loss
-        else:
-            def term(z_i, z_j):
-                lg, lb = self.info_nce(z_i, z_j, self.tau, B, self.sim)
-                return ce(lg, lb)
-        seq_output = self.forward(input_ids)[:, -1, :]
-        if self.duorec_ce_head == "hip":
-            loss = self.catalogue_ce(seq_output, answers)
-        else:
-            logits = torch.matmul(seq_output, self.item_embeddings.weight.transpose(0, 1))
-            loss = ce(logits, answers.to(logits.device))
-        if self.ssl in ("us", "un"):
-            aug = self.forward(input_ids)[:, -1, :]
-            loss = loss + self.lmd * term(seq_output, aug)
-        if self.ssl in ("us", "su"):
-            sem = self.forward(same_target)[:, -1, :]
-            loss = loss + self.lmd_sem * term(seq_output, sem)
-        if self.ssl == "us_x":
-            aug = self.forward(input_ids)[:, -1, :]
-            sem = self.forward(same_target)[:, -1, :]
-            loss = loss + self.lmd_sem * term(aug, sem)
-        return loss
+        """src/model/duorec.py:95-127 (duorec_loss)."""
+        return duorec_loss(self, self.forward, input_ids, answers, same_target)[0]
 
     def train_step(self, input_ids, answers, neg_answers=None, same_target=None):
         raise RuntimeError("DuoRec steps through calculate_loss / backward / torch.optim.Adam (Trainer does)")

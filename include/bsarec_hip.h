@@ -871,6 +871,38 @@ int bsarec_caser_train_step(const bsarec_caser_step_config_t *cfg, const int64_t
                             const bsarec_adam_t *adam_fc, void *state, float *loss_out,
                             void *workspace, long workspace_bytes, void *stream);
 
+/* Band-limited autocorrelation attention of the FEARec sibling model (csrc/fea_attn.h): with q, k, v [B, L, D] (D = width),
+ * F = L / 2 + 1 and a band lo <= f < hi of rfft bins,
+ *   Qf[b, c, f] = sum_t q[b, t, c] e^{-2 pi i f t / L} (Kf alike),  S[b, f] = sum_c Qf[b, c, f] conj(Kf[b, c, f]),
+ *   m[b, tau]   = 1 / (D L) sum_{f in band} w_f Re(S[b, f] e^{+2 pi i f tau / L}),  tau = 0 .. L - 1;  w_f = 1 at f = 0 and at
+ *                 f = L / 2 of an even L, else 2 -- irfft(n = L) of the band-masked cross-spectrum, averaged over channels,
+ *   idx         = the topk delays with the largest g[tau] = mean_b m[b, tau], ONE set for the batch (train != 0), or with the
+ *                 largest m[b, .] per sequence (train = 0); equal values go to the lower tau,
+ *   p[b, i]     = softmax_i(m[b, idx_i]),  out[b, t, c] = sum_i p[b, i] v[b, (t + idx_i) mod L, c].
+ * bsarec_fea_attn_bwd is the true derivative with idx held fixed (nothing flows through g): every float of dq, dk and dv is
+ * overwritten.  It reads what bsarec_fea_attn_fwd left in the SAME workspace with the same cfg.  The kernels evaluate m in its
+ * equivalent time-domain form (the Gram matrix's diagonal sums against the band's impulse response, csrc/fea_attn.h), so no
+ * spectrum is stored or recomputed.  All arithmetic is fp32 (v_mfma_f32_16x16x4_f32 in the products), the impulse response is
+ * summed in fp64.
+ *   Every sum has one order that is a function of the shape alone: no atomics, equal bits on every run, and with train = 0
+ * nothing of a sequence depends on the rest of the batch.  Launches, all on `stream`, one after the other: forward 3 (4 with
+ * train != 0), backward 3.  No allocation, no host synchronisation: capturable.
+ *   Workspace: bsarec_fea_attn_workspace_bytes(cfg) bytes (host-only query, no HIP call).  In 4-byte words, each part at an
+ * offset rounded up to a multiple of 4: m [B, L] float at 0 | idx int32, [topk] (train != 0) or [B, topk], at
+ * round_up(B L, 4) | p [B, topk] | the impulse response [L] | cv [B, L] (backward only).
+ *   Limits (else < 0 before any HIP call, nothing written): 1 <= batch <= 65536, 2 <= seq_len <= 256, width in 4 .. 256 and a
+ * multiple of 4, 0 <= lo < hi <= seq_len / 2 + 1, 1 <= topk <= min(seq_len, 32); every pointer non-null and 16-byte aligned;
+ * workspace_bytes at least the queried size.  Outputs may not alias inputs, each other or the workspace.  Inputs are assumed
+ * finite. */
+typedef struct {
+    int batch, seq_len, width, lo, hi, topk, train;
+} bsarec_fea_attn_config_t;
+long bsarec_fea_attn_workspace_bytes(const bsarec_fea_attn_config_t *cfg);
+int bsarec_fea_attn_fwd(const bsarec_fea_attn_config_t *cfg, const float *q, const float *k, const float *v, float *out,
+                        void *workspace, long workspace_bytes, void *stream);
+int bsarec_fea_attn_bwd(const bsarec_fea_attn_config_t *cfg, const float *q, const float *k, const float *v, const float *dout,
+                        void *workspace, long workspace_bytes, float *dq, float *dk, float *dv, void *stream);
+
 /* Tag kernel launches of one id with hipEvents for in-process roofline timing (bench.py):
  * when set, every launch of kernel class `kclass` (see BSAREC_K_*) on the next calls of THIS plan is bracketed
  * by hipEventRecord on the launch stream; bsarec_profile_read returns the summed milliseconds and
