@@ -168,6 +168,11 @@ class CaserStepConfig(C.Structure):
     _fields_ = [("conv", CaserConfig), ("item_size", C.c_int), ("dropout", C.c_float)]
 
 
+class CaserUserStepConfig(C.Structure):
+    """bsarec_caser_user_step_config_t"""
+    _fields_ = [("step", CaserStepConfig), ("num_users", C.c_int)]
+
+
 class FeaAttnConfig(C.Structure):
     """bsarec_fea_attn_config_t"""
     _fields_ = [("batch", C.c_int), ("seq_len", C.c_int), ("width", C.c_int), ("lo", C.c_int), ("hi", C.c_int),
@@ -293,6 +298,12 @@ EXPORTS = {
                                [C.c_long, C.c_void_p]),
     "bsarec_caser_train_step": (C.c_int, [C.POINTER(CaserStepConfig)] + [C.c_void_p] * 3 + [C.POINTER(Adam)] * 3 +
                                 [C.c_void_p] * 3 + [C.c_long, C.c_void_p]),
+    "bsarec_caser_fc2_floats": (C.c_long, [C.POINTER(CaserConfig)]),
+    "bsarec_caser_user_step_workspace_bytes": (C.c_long, [C.POINTER(CaserUserStepConfig)]),
+    "bsarec_caser_user_loss_grad": (C.c_int, [C.POINTER(CaserUserStepConfig)] + [C.c_void_p] * 10 + [C.c_int] +
+                                    [C.c_void_p] * 7 + [C.c_long, C.c_void_p]),
+    "bsarec_caser_user_train_step": (C.c_int, [C.POINTER(CaserUserStepConfig)] + [C.c_void_p] * 4 + [C.POINTER(Adam)] * 5 +
+                                     [C.c_void_p] * 3 + [C.c_long, C.c_void_p]),
     "bsarec_fea_attn_workspace_bytes": (C.c_long, [C.POINTER(FeaAttnConfig)]),
     "bsarec_fea_attn_fwd": (C.c_int, [C.POINTER(FeaAttnConfig)] + [C.c_void_p] * 5 + [C.c_long, C.c_void_p]),
     "bsarec_fea_attn_bwd": (C.c_int, [C.POINTER(FeaAttnConfig)] + [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 4),

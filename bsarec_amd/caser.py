@@ -1,13 +1,15 @@
 """Caser sibling model: an item embedding, a convolution block over the [L, d] embedding "image" of a sequence -- n_v vertical
 filters of shape (L, 1) and, for EVERY height h = 1 .. L, n_h horizontal filters of shape (h, d) with ReLU and the maximum over
-positions -- and a Linear + ReLU back to the embedding width, trained with BPR.  Item-only: the user embedding of the original
-Caser is left out, as every model here ignores ``user_ids``.
+positions -- and a Linear + ReLU back to the embedding width, trained with BPR.  Item-only by default; ``args.caser_user`` adds the
+user embedding of the original Caser and its second Linear + ReLU on [z1 | P[user]] (this is the one model here that reads
+``user_ids``).
 
 The contract of this model is the math of its docstrings, checked against ``torch.nn.Conv2d`` / ``F.max_pool1d`` / ``nn.Linear``
 on the CPU (tests/caser_ref.py, tests/test_caser_cpu.py); no reference golden exists for it yet.  The convolution block runs in
 libbsarec_hip.so in both directions (bsarec_caser_fwd / bsarec_caser_bwd, csrc/caser.h); the embedding lookup, the dropout mask,
 ``fc1`` and the B-row BPR head are torch ops -- unless ``args.caser_step = "fused"``, where the whole training step is one C call
-(bsarec_caser_train_step, csrc/caser_step.h).  There is no CPU path.
+(bsarec_caser_train_step, csrc/caser_step.h; with ``caser_user`` bsarec_caser_user_train_step, csrc/caser_user.h).  There is no
+CPU path.
 """
 from __future__ import annotations
 
@@ -207,7 +209,7 @@ class CaserModel(nn.Module):
     [B, d] -- ONE state per sequence, not the [B, L, d] of the block models: Caser has no per-position output.
     Loss: BPR, mean_b -log(sigmoid(s . E[answers] - s . E[neg_answers]) + 1e-10).
     Init: Embedding and fc1 weights N(0, initializer_range), the fc1 bias 0, the filters torch's Conv2d default.
-    Item-only: the user embedding of the original Caser is left out (``user_ids`` is accepted and ignored).
+    Item-only unless ``args.caser_user`` is set (below); without it ``user_ids`` is accepted and ignored.
     The filter bank is sized by L: ``input_ids.shape[1]`` must equal ``args.max_seq_length`` (ValueError otherwise).
 
     ``args.caser_step`` selects how the model steps, single GPU either way:
@@ -220,10 +222,21 @@ class CaserModel(nn.Module):
         dropout mask is the library's Philox stream (site 0, the step counter of the device state that ``set_seed`` seeds and
         resets).  The two streams have the same distribution and DIFFERENT draws: the modes do not train bit for bit alike at
         p > 0.
-    calculate_loss, forward, predict and last_hidden are the same in both modes (torch-generator dropout in training mode)."""
+    calculate_loss, forward, predict and last_hidden are the same in both modes (torch-generator dropout in training mode).
+
+    ``args.caser_user`` (default False, also when absent) is the personalised Caser, valid in both modes: two more modules, so the
+    state_dict keys are ``item_embeddings.weight``, ``user_embeddings.weight`` [U, d] (U = ``args.num_users``), ``conv.*``,
+    ``fc1.*``, ``fc2.weight`` [d, 2 d], ``fc2.bias`` [d] (init N(0, initializer_range) and 0).  With z1 = relu(fc1(Dropout_p(z))),
+    the state is s = relu(fc2([z1 | P[user_ids]])): what forward / predict / last_hidden return and the BPR head reads.  A user id
+    is the 0-based index of the user's line (what data.train_table / eval_table emit); id 0 is an ordinary row; an id outside
+    [0, U) is never looked up -- its half is zero and it gets no gradient.  ``user_ids`` is then REQUIRED, [B] or [B, 1]
+    (ValueError otherwise), and the instance sets ``needs_user_ids = True`` so that the Trainer passes it.  In fused mode the
+    step is bsarec_caser_user_train_step, ``fc2.weight`` / ``fc2.bias`` are views of one flat tensor like fc1's, and Adam runs on
+    five arrays.  Without the flag the model is what it was: same parameters, same bits, same state_dict."""
 
     needs_negatives = True
     needs_same_target = False
+    needs_user_ids = False                       # True on an instance with caser_user: Trainer passes user_ids
     torch_optim = True
     kernel_family = "Caser"                      # Trainer's messages
 
@@ -238,10 +251,20 @@ class CaserModel(nn.Module):
             self.torch_optim = False                      # Trainer.iteration: the pairwise branch, model.train_step
         self._fused = None                                # the fused step's buffers (_step_buffers)
         self._fc_flat = None                              # fused: fc1.weight [d, F] then fc1.bias [d]
+        self._fc2_flat = None                             # fused with caser_user: fc2.weight [d, 2 d] then fc2.bias [d]
+        self.caser_user = bool(getattr(args, "caser_user", False))
         d, Lq = int(args.hidden_size), int(args.max_seq_length)
         self.item_embeddings = nn.Embedding(int(args.item_size), d)
+        if self.caser_user:
+            U = getattr(args, "num_users", None)
+            if U is None or int(U) < 1:
+                raise ValueError(f"Caser: caser_user needs args.num_users >= 1, got {U!r}")
+            self.needs_user_ids = True
+            self.user_embeddings = nn.Embedding(int(U), d)
         self.conv = CaserConv(Lq, d, int(getattr(args, "caser_nh", 16)), int(getattr(args, "caser_nv", 4)))
         self.fc1 = nn.Linear(self.conv.out_features, d)
+        if self.caser_user:
+            self.fc2 = nn.Linear(2 * d, d)
         self.p_drop = float(args.hidden_dropout_prob)
         if not 0.0 <= self.p_drop < 1.0:
             raise ValueError(f"hidden_dropout_prob must be in [0, 1), got {self.p_drop}")
@@ -250,6 +273,10 @@ class CaserModel(nn.Module):
             self.item_embeddings.weight.normal_(0.0, std)
             self.fc1.weight.normal_(0.0, std)
             self.fc1.bias.zero_()
+            if self.caser_user:
+                self.user_embeddings.weight.normal_(0.0, std)
+                self.fc2.weight.normal_(0.0, std)
+                self.fc2.bias.zero_()
         self._seed, self._rank, self._gen = 42, 0, None
         self.reflatten()
 
@@ -267,11 +294,18 @@ class CaserModel(nn.Module):
         self.conv.reflatten()
         if self.caser_step != "fused":
             return
-        w, b = self.fc1.weight, self.fc1.bias
-        flat, nw = self._fc_flat, w.numel()
+        self._fc_flat = self._flat_linear(self.fc1, self._fc_flat)
+        if self.caser_user:                               # fc2 alike: weight [d, 2 d], then bias [d]
+            self._fc2_flat = self._flat_linear(self.fc2, self._fc2_flat)
+
+    def _flat_linear(self, lin, flat):
+        """``lin.weight`` / ``lin.bias`` as views of one flat tensor, weight then bias: ``flat`` if they still are, else a new one
+        with their values (and the fused step's buffers go)."""
+        w, b = lin.weight, lin.bias
+        nw = w.numel()
         if (flat is not None and flat.device == w.device == b.device and w.data_ptr() == flat.data_ptr()
                 and b.data_ptr() == flat.data_ptr() + 4 * nw and w.is_contiguous()):
-            return
+            return flat
         with torch.no_grad():
             flat = torch.empty(nw + b.numel(), dtype=torch.float32, device=w.device)
             flat[:nw] = w.detach().reshape(-1).to(torch.float32)
@@ -279,8 +313,8 @@ class CaserModel(nn.Module):
             w.data = flat[:nw].view(w.shape)
             b.data = flat[nw:].view(b.shape)
             w.grad = b.grad = None
-        self._fc_flat = flat
         self._fused = None
+        return flat
 
     def _stream_seed(self):
         return (self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF
@@ -308,33 +342,55 @@ class CaserModel(nn.Module):
             raise ValueError(f"Caser: input_ids must be [B, max_seq_length = {self.conv.seq_len}] (the filter bank is sized by it), "
                              f"got {tuple(input_ids.shape)}")
 
-    def _state(self, input_ids, train: bool):
+    def _users(self, user_ids, input_ids):
+        """caser_user: ``user_ids`` as int64 [B] on the device of ``input_ids`` [B, L]; [B] or [B, 1] only (ValueError: missing,
+        another shape).  None without the flag: the ids are ignored.  Stands before the device check of every public call."""
+        if not self.caser_user:
+            return None
+        if user_ids is None:
+            raise ValueError("Caser: caser_user needs user_ids")
+        B = input_ids.shape[0] if input_ids.dim() else -1
+        if tuple(user_ids.shape) not in ((B,), (B, 1)):
+            raise ValueError(f"Caser: user_ids must be [B] or [B, 1] with B = {B}, got {tuple(user_ids.shape)}")
+        return user_ids.to(device=input_ids.device, dtype=torch.int64).reshape(-1)
+
+    def _state(self, input_ids, train: bool, users=None):
         z = self.conv(self.item_embeddings(input_ids))
         if train and self.p_drop > 0.0:
             keep = torch.empty_like(z).bernoulli_(1.0 - self.p_drop, generator=self._generator(z.device))
             z = z * keep * (1.0 / (1.0 - self.p_drop))
-        return torch.relu(self.fc1(z))
+        z1 = torch.relu(self.fc1(z))
+        if not self.caser_user:
+            return z1
+        U = self.user_embeddings.num_embeddings
+        inside = (users >= 0) & (users < U)               # an id outside [0, U): never looked up, a zero half, no gradient
+        pu = self.user_embeddings(users.clamp(0, U - 1)) * inside.unsqueeze(-1).to(z1.dtype)
+        return torch.relu(self.fc2(torch.cat([z1, pu], dim=-1)))
 
     def forward(self, input_ids, user_ids=None, all_sequence_output=False):
-        """[B, L] ids -> s [B, d].  ``user_ids`` and ``all_sequence_output`` are accepted and ignored."""
+        """[B, L] ids -> s [B, d].  ``all_sequence_output`` is accepted and ignored, and so is ``user_ids`` unless
+        ``caser_user`` is set."""
+        users = self._users(user_ids, input_ids)
         self._require_gpu(input_ids)
-        return self._state(input_ids, self.training)
+        return self._state(input_ids, self.training, users)
 
     def predict(self, input_ids, user_ids=None, all_sequence_output=False):
         return self.forward(input_ids, user_ids, all_sequence_output)
 
-    def last_hidden(self, input_ids) -> torch.Tensor:
+    def last_hidden(self, input_ids, user_ids=None) -> torch.Tensor:
         """[B, d]: the eval-mode s (the bits of ``forward`` in eval mode), no gradient."""
+        users = self._users(user_ids, input_ids)
         self._require_gpu(input_ids)
         with torch.no_grad():
-            return self._state(input_ids, False)
+            return self._state(input_ids, False, users)
 
     def calculate_loss(self, input_ids, answers, neg_answers=None, same_target=None, user_ids=None):
         """BPR on s: a 0-d tensor; ``.backward()`` fills every parameter's grad."""
         if neg_answers is None:
             raise ValueError("Caser's loss needs neg_answers")
+        users = self._users(user_ids, input_ids)
         self._require_gpu(input_ids)
-        s = self._state(input_ids, self.training)
+        s = self._state(input_ids, self.training, users)
         pos = self.item_embeddings(answers.to(s.device).reshape(-1))
         neg = self.item_embeddings(neg_answers.to(s.device).reshape(-1))
         diff = (s * pos).sum(-1) - (s * neg).sum(-1)
@@ -345,7 +401,8 @@ class CaserModel(nn.Module):
         """What the fused step owns beside the parameters: the device step state (seed, step counter, Adam t), the three gradient
         arrays, the Adam moments of the item table, of the convolution's flat array and of the fc1 flat array, and per batch
         shape a workspace, static id buffers and a captured graph.  Built on first use; dropped by ``.to()`` / ``reflatten()``
-        (a new parameter storage)."""
+        (a new parameter storage).  With ``caser_user`` two more arrays, the user table and the fc2 flat array, each with its
+        gradient and moments (dP / mP / vP, dG / mG / vG), and a static ``users`` buffer per batch shape."""
         if self.caser_step != "fused":
             raise RuntimeError("Caser: the fused step's buffers exist only with caser_step = 'fused'")
         self._require_gpu()
@@ -354,12 +411,21 @@ class CaserModel(nn.Module):
         if flat.device != E.device or fc.device != E.device or not E.is_contiguous() or E.dtype != torch.float32:
             raise RuntimeError("caser: the item table, the filters and fc1 must be contiguous fp32 on one device")
         key = (E.data_ptr(), flat.data_ptr(), fc.data_ptr(), E.device)
+        arrays = [("E", E), ("W", flat), ("F", fc)]
+        if self.caser_user:                               # the user table and the fc2 flat array: dP / mP / vP, dG / mG / vG
+            P, fc2 = self.user_embeddings.weight.data, self._fc2_flat
+            if P.device != E.device or fc2.device != E.device or not P.is_contiguous() or P.dtype != torch.float32:
+                raise RuntimeError("caser: the user table and fc2 must be contiguous fp32 on the item table's device")
+            key += (P.data_ptr(), fc2.data_ptr())
+            arrays += [("P", P), ("G", fc2)]
         f = self._fused
         if f is None or f["key"] != key:
             state = torch.zeros(8, dtype=torch.int64, device=E.device)
             state[0] = self._stream_seed()
             f = dict(key=key, state=state, E=E, flat=flat, fc=fc, adam=None, slots={})
-            for name, t in (("E", E), ("W", flat), ("F", fc)):
+            if self.caser_user:
+                f["P"], f["fc2"] = P, fc2
+            for name, t in arrays:
                 f["d" + name], f["m" + name], f["v" + name] = torch.empty_like(t), torch.zeros_like(t), torch.zeros_like(t)
             self._fused = f
         return f
@@ -375,7 +441,11 @@ class CaserModel(nn.Module):
             c = self.conv
             cfg = L.CaserStepConfig(L.CaserConfig(B, c.seq_len, c.width, c.n_h, c.n_v), self.item_embeddings.num_embeddings,
                                     self.p_drop)
-            nbytes = L.load().bsarec_caser_step_workspace_bytes(cfg)
+            if self.caser_user:
+                cfg = L.CaserUserStepConfig(cfg, self.user_embeddings.num_embeddings)
+                nbytes = L.load().bsarec_caser_user_step_workspace_bytes(cfg)
+            else:
+                nbytes = L.load().bsarec_caser_step_workspace_bytes(cfg)
             if nbytes < 0:
                 raise ValueError(f"caser: unsupported step shape B = {B}, dropout = {self.p_drop} (1 <= B <= 65536, 0 <= p < 1)")
             dev = f["E"].device
@@ -383,40 +453,58 @@ class CaserModel(nn.Module):
                      ids=torch.zeros((B, c.seq_len), dtype=torch.int64, device=dev),
                      ans=torch.zeros(B, dtype=torch.int64, device=dev), neg=torch.zeros(B, dtype=torch.int64, device=dev),
                      loss=torch.zeros((), dtype=torch.float32, device=dev), graph=None)
+            if self.caser_user:
+                s["users"] = torch.zeros(B, dtype=torch.int64, device=dev)
             f["slots"][B] = s
         return s
 
-    @staticmethod
-    def _fill(s, input_ids, answers, neg_answers):
+    def _fill(self, s, input_ids, answers, neg_answers, users=None):
         if neg_answers is None:
             raise ValueError("Caser's loss needs neg_answers")
         s["ids"].copy_(input_ids)
         s["ans"].copy_(answers.reshape(-1))
         s["neg"].copy_(neg_answers.reshape(-1))
+        if users is not None:
+            s["users"].copy_(users)
 
     def _loss_grad(self, f, s, train: bool):
         stream = torch.cuda.current_stream(f["E"].device).cuda_stream
+        if self.caser_user:
+            L.check(L.load().bsarec_caser_user_loss_grad(
+                s["cfg"], f["E"].data_ptr(), f["P"].data_ptr(), f["flat"].data_ptr(), f["fc"].data_ptr(), f["fc2"].data_ptr(),
+                s["ids"].data_ptr(), s["users"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), f["state"].data_ptr(),
+                int(train), s["loss"].data_ptr(), f["dE"].data_ptr(), f["dP"].data_ptr(), f["dW"].data_ptr(), f["dF"].data_ptr(),
+                f["dG"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream), "bsarec_caser_user_loss_grad")
+            return
         L.check(L.load().bsarec_caser_loss_grad(
             s["cfg"], f["E"].data_ptr(), f["flat"].data_ptr(), f["fc"].data_ptr(), s["ids"].data_ptr(), s["ans"].data_ptr(),
             s["neg"].data_ptr(), f["state"].data_ptr(), int(train), s["loss"].data_ptr(), f["dE"].data_ptr(), f["dW"].data_ptr(),
             f["dF"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream), "bsarec_caser_loss_grad")
 
-    def loss_and_grads(self, input_ids, answers, neg_answers, train: bool = True):
-        """The BPR loss (0-d tensor) and {state_dict key: gradient} of one batch through bsarec_caser_loss_grad, no update.
+    def loss_and_grads(self, input_ids, answers, neg_answers, train: bool = True, user_ids=None):
+        """The BPR loss (0-d tensor) and {state_dict key: gradient} of one batch through bsarec_caser_loss_grad
+        (bsarec_caser_user_loss_grad with ``caser_user``, which needs ``user_ids``), no update.
         ``train``: draw the next dropout mask of the device stream (the step counter advances); else no dropout."""
         if self.caser_step != "fused":
             raise RuntimeError("Caser: loss_and_grads is the fused step's (caser_step = 'fused')")
+        users = self._users(user_ids, input_ids)
         self._require_gpu(input_ids)
         f = self._step_buffers()
         s = self._slot(f, int(input_ids.shape[0]))
-        self._fill(s, input_ids, answers, neg_answers)
+        self._fill(s, input_ids, answers, neg_answers, users)
         self._loss_grad(f, s, train)
         grads = OrderedDict([("item_embeddings.weight", f["dE"].clone())])
+        if self.caser_user:
+            grads["user_embeddings.weight"] = f["dP"].clone()
         for name, (o, n, shp) in self.conv._slices.items():
             grads["conv." + name] = f["dW"][o:o + n].view(shp).clone()
         nw = self.fc1.weight.numel()
         grads["fc1.weight"] = f["dF"][:nw].view(self.fc1.weight.shape).clone()
         grads["fc1.bias"] = f["dF"][nw:].clone()
+        if self.caser_user:
+            nw = self.fc2.weight.numel()
+            grads["fc2.weight"] = f["dG"][:nw].view(self.fc2.weight.shape).clone()
+            grads["fc2.bias"] = f["dG"][nw:].clone()
         return s["loss"].clone(), grads
 
     def _adam_structs(self, f):
@@ -425,29 +513,39 @@ class CaserModel(nn.Module):
             hyper = (float(getattr(a, "lr", 1e-3)), float(getattr(a, "adam_beta1", 0.9)), float(getattr(a, "adam_beta2", 0.999)),
                      1e-8, float(getattr(a, "weight_decay", 0.0)), 1.0, None, 0)
             f["adam"] = tuple(L.Adam(f[p].data_ptr(), f["d" + k].data_ptr(), f["m" + k].data_ptr(), f["v" + k].data_ptr(),
-                                     f[p].numel(), *hyper) for p, k in (("E", "E"), ("flat", "W"), ("fc", "F")))
+                                     f[p].numel(), *hyper) for p, k in (("E", "E"), ("flat", "W"), ("fc", "F")) +
+                              ((("P", "P"), ("fc2", "G")) if self.caser_user else ()))
         return f["adam"]
 
     def _train_step(self, f, s):
-        items, weights, fc = self._adam_structs(f)
         stream = torch.cuda.current_stream(f["E"].device).cuda_stream
+        if self.caser_user:
+            items, weights, fc, users, fc2 = self._adam_structs(f)
+            L.check(L.load().bsarec_caser_user_train_step(
+                s["cfg"], s["ids"].data_ptr(), s["users"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), items, users,
+                weights, fc, fc2, f["state"].data_ptr(), s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream),
+                "bsarec_caser_user_train_step")
+            return
+        items, weights, fc = self._adam_structs(f)
         L.check(L.load().bsarec_caser_train_step(
             s["cfg"], s["ids"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), items, weights, fc, f["state"].data_ptr(),
             s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream), "bsarec_caser_train_step")
 
-    def train_step(self, input_ids, answers, neg_answers=None, same_target=None):
+    def train_step(self, input_ids, answers, neg_answers=None, same_target=None, user_ids=None):
         """caser_step = "fused": one optimisation step in one C call -- the step counter, the lookup, the convolution block, fc1
         with its Philox dropout, the BPR head, every gradient, Adam (``args.lr``, ``adam_beta1``, ``adam_beta2``,
         ``weight_decay``) on the three arrays, in place.  Returns the mean loss as a 0-d device tensor (no host sync; the next
         step overwrites it).  The call is captured once per batch shape over static id buffers and replayed -- the mask and
         Adam's t advance on the device, and the capture is one linear chain on one stream, so it has no parallel branches to
-        replay; ``args.caser_step_graph = False`` calls eagerly instead."""
+        replay; ``args.caser_step_graph = False`` calls eagerly instead.  With ``caser_user`` the call is
+        bsarec_caser_user_train_step (five arrays) and ``user_ids`` goes into a static buffer beside the ids."""
         if self.caser_step != "fused":
             raise RuntimeError("Caser steps through calculate_loss / backward / torch.optim.Adam unless caser_step = 'fused'")
+        users = self._users(user_ids, input_ids)
         self._require_gpu(input_ids)
         f = self._step_buffers()
         s = self._slot(f, int(input_ids.shape[0]))
-        self._fill(s, input_ids, answers, neg_answers)
+        self._fill(s, input_ids, answers, neg_answers, users)
         if not getattr(self.args, "caser_step_graph", True):
             self._train_step(f, s)
             return s["loss"]

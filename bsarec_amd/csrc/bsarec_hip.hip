@@ -24,6 +24,7 @@
 #include "gru4rec_cand.h"
 #include "caser.h"
 #include "caser_step.h"
+#include "caser_user.h"
 #include "fea_attn.h"
 
 #include <hip/hip_runtime.h>
@@ -3137,6 +3138,182 @@ extern "C" int bsarec_caser_train_step(const bsarec_caser_step_config_t* cfg, co
     RET(adam_launch(*adam_items, state, s));
     RET(adam_launch(*adam_weights, state, s));
     return adam_launch(*adam_fc, state, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Personalised Caser step (caser_user.h): the step above with a user table and fc2 = Linear(2 d, d) behind fc1.  fc2 runs on
+// fc1's launches; the chain is linear on the caller's stream, no allocation, no host synchronisation
+// ---------------------------------------------------------------------------------------------
+static int caser_user_check(const bsarec_caser_user_step_config_t* c) {
+    if (!c) return -10;
+    RET(caser_step_check(&c->step));
+    if (c->num_users < 1) return -10;
+    return 0;
+}
+
+extern "C" long bsarec_caser_fc2_floats(const bsarec_caser_config_t* cfg) {
+    if (caser_check(cfg)) return -10;
+    return (2L * cfg->width + 1) * cfg->width;
+}
+
+// Workspace, in floats: the regions of caser_step_ws (its s holds z1, its ds holds dz1) | x2 [B][2 d] | s [B][d] | ds [B][d] |
+// dx2 [B][2 d] | the fixed-point accumulator [U][d] of 64-bit words
+struct CaserUserWs { CaserStepWs st; long x2, s, ds, dx2, uacc, total; };
+static CaserUserWs caser_user_ws(const bsarec_caser_user_step_config_t& c) {
+    const long B = c.step.conv.batch, d = c.step.conv.width;
+    CaserUserWs w;
+    w.st = caser_step_ws(c.step);
+    long off = w.st.total;
+    w.x2 = off; off += 2 * B * d;
+    w.s = off; off += B * d;
+    w.ds = off; off += B * d;
+    w.dx2 = off; off += 2 * B * d;
+    w.uacc = off; off += 2L * c.num_users * d;
+    w.total = off;
+    return w;
+}
+
+extern "C" long bsarec_caser_user_step_workspace_bytes(const bsarec_caser_user_step_config_t* cfg) {
+    if (caser_user_check(cfg)) return -10;
+    return caser_user_ws(*cfg).total * (long)sizeof(float);
+}
+
+// tick_adam: null, or the Adam whose t the step's closing block advances (bsarec_caser_user_train_step)
+static int caser_user_run(const bsarec_caser_user_step_config_t& cu, const float* E, const float* Pu, const float* weights,
+                          const float* fc, const float* fc2, const int64_t* ids, const int64_t* users, const int64_t* answers,
+                          const int64_t* neg_answers, void* state, int train, float* loss_out, float* dE, float* dP,
+                          float* dweights, float* dfc, float* dfc2, void* workspace, const bsarec_adam_t* tick_adam,
+                          hipStream_t s) {
+    const bsarec_caser_step_config_t& c = cu.step;
+    const int B = c.conv.batch, d = c.conv.width, V = c.item_size, U = cu.num_users;
+    const long T = (long)B * c.conv.seq_len;
+    const int F = (int)caser_weights(c.conv).F;
+    const CaserUserWs wu = caser_user_ws(cu);
+    const CaserStepWs& ws = wu.st;
+    float* w = (float*)workspace;
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(w + ws.acc);
+    unsigned long long* uacc = reinterpret_cast<unsigned long long*>(w + wu.uacc);
+    if (train) hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(1), 0, s, (uint64_t*)state, (long long*)nullptr, 0);
+    DropP none;                                         // the token rows and fc2 carry no mask
+    none.thresh = 0; none.scale = 1.0f; none.rng = (const uint64_t*)state; none.site = 0;
+
+    Gru4RecEmbedP pe;
+    pe.E = E; pe.ids = ids; pe.x = w + ws.x; pe.T = T; pe.d = d; pe.V = V; pe.drop = none;
+    pe.acc = acc; pe.acc_n2 = (long)V * d / 2;
+    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_embed_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)),
+                                       dim3(ROW_THREADS), 0, s, pe));
+    RET(bsarec_caser_fwd(&c.conv, w + ws.x, weights, 1, w + ws.z, w + ws.conv, ws.conv_bytes, s));
+
+    CaserFcP pf = caser_fc_params(B, F, d, w + ws.z, fc, caser_fc_drop(c.dropout, state, train != 0), w + ws.zd);
+    pf.s_out = w + ws.s; pf.s = w + ws.s; pf.ds = w + ws.ds; pf.dz = w + ws.dz; pf.dw = dfc;      // s = z1, ds = dz1
+    caser_fc_fwd_launch(pf, s);
+
+    CaserUserP pu;
+    memset(&pu, 0, sizeof(pu));
+    pu.z1 = w + ws.s; pu.P = Pu; pu.users = users; pu.x2 = w + wu.x2; pu.dx2 = w + wu.dx2; pu.dz1 = w + ws.ds;
+    pu.B = B; pu.d = d; pu.U = U; pu.acc = uacc; pu.acc_n2 = (long)U * d / 2;
+    DISPATCH_LPR(d, hipLaunchKernelGGL(caser_user_concat_kernel<LPR>, dim3(std::min(cdiv(B, ROW_THREADS / LPR), 4096)),
+                                       dim3(ROW_THREADS), 0, s, pu));
+
+    CaserFcP p2 = caser_fc_params(B, 2 * d, d, w + wu.x2, fc2, none, nullptr);
+    p2.s_out = w + wu.s; p2.s = w + wu.s; p2.ds = w + wu.ds; p2.dz = w + wu.dx2; p2.dw = dfc2;
+    caser_fc_fwd_launch(p2, s);
+
+    Gru4RecBprP pb;
+    pb.s = w + wu.s; pb.E = E; pb.ans = answers; pb.neg = neg_answers; pb.B = B; pb.d = d; pb.V = V;
+    pb.ds = w + wu.ds; pb.c = w + ws.c; pb.loss_rows = w + ws.rows;
+    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_bpr_kernel<LPR>, dim3(cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS), 0, s, pb));
+
+    caser_fc_bwd_launch(p2, s);
+    DISPATCH_LPR(d, {
+        pu.scatter_blocks = cdiv(B, SCATTER_FLOATS / (4 * LPR));
+        hipLaunchKernelGGL(caser_user_grad_kernel<LPR>, dim3(pu.scatter_blocks + cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS),
+                           0, s, pu);
+    });
+    caser_fc_bwd_launch(pf, s);
+    RET(bsarec_caser_bwd(&c.conv, w + ws.x, weights, w + ws.dz, w + ws.conv, ws.conv_bytes, w + ws.dx, dweights, s));
+
+    Gru4RecGradP pg;                                   // T token rows, then the head's 2 B
+    pg.dx = w + ws.dx; pg.ids = ids; pg.ans = answers; pg.neg = neg_answers;
+    pg.T = T; pg.B = B; pg.C = 0; pg.d = d; pg.V = V; pg.drop = none; pg.dA = acc;
+    pg.head_rows = w + wu.s; pg.c = w + ws.c;
+    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_item_grad_kernel<LPR>, dim3(cdiv(T + 2L * B, SCATTER_FLOATS / (4 * LPR))),
+                                       dim3(ROW_THREADS), 0, s, pg));
+
+    LookupAcc lu;
+    memset(&lu, 0, sizeof(lu));
+    lu.acc = uacc; lu.dst = dP; lu.n4 = (long)U * d / 4; lu.dense_zero = 1;
+    lu.nblocks = std::min(cdiv(lu.n4, ROW_THREADS), 1024);
+    hipLaunchKernelGGL(caser_user_flush_kernel, dim3(lu.nblocks), dim3(ROW_THREADS), 0, s, lu);
+
+    LookupAcc la;
+    memset(&la, 0, sizeof(la));
+    la.acc = acc; la.dst = dE; la.n4 = (long)V * d / 4; la.dense_zero = 1;
+    la.nblocks = std::min(cdiv(la.n4, ROW_THREADS), 1024);
+    const TickP tk = tick_adam ? make_tick(state, 1, tick_adam->lr, tick_adam->beta1, tick_adam->beta2, w + ws.rows, B, loss_out,
+                                           nullptr, 0, 0)
+                               : make_tick(state, 0, 0.f, 0.f, 0.f, w + ws.rows, B, loss_out, nullptr, 0, 0);
+    hipLaunchKernelGGL(gru4rec_flush_kernel, dim3(la.nblocks + 1), dim3(ROW_THREADS), 0, s, la, tk);
+    return (int)hipGetLastError();
+}
+
+static int caser_user_loss_grad(const bsarec_caser_user_step_config_t* cfg, const float* item_emb, const float* user_emb,
+                                const float* weights, const float* fc, const float* fc2, const int64_t* ids,
+                                const int64_t* users, const int64_t* answers, const int64_t* neg_answers, void* state, int train,
+                                float* loss_out, float* d_item_emb, float* d_user_emb, float* dweights, float* dfc, float* dfc2,
+                                void* workspace, long workspace_bytes, const bsarec_adam_t* tick_adam, hipStream_t s) {
+    RET(caser_user_check(cfg));
+    for (const void* p : {(const void*)item_emb, (const void*)user_emb, (const void*)weights, (const void*)fc, (const void*)fc2,
+                          (const void*)d_item_emb, (const void*)d_user_emb, (const void*)dweights, (const void*)dfc,
+                          (const void*)dfc2, (const void*)workspace})
+        if (!aligned_to(p, 16)) return -10;
+    for (const void* p : {(const void*)ids, (const void*)users, (const void*)answers, (const void*)neg_answers, (const void*)state})
+        if (!aligned_to(p, 8)) return -10;
+    if (!aligned_to(loss_out, 4)) return -10;
+    if (workspace_bytes < caser_user_ws(*cfg).total * (long)sizeof(float)) return -10;
+    return caser_user_run(*cfg, item_emb, user_emb, weights, fc, fc2, ids, users, answers, neg_answers, state, train, loss_out,
+                          d_item_emb, d_user_emb, dweights, dfc, dfc2, workspace, tick_adam, s);
+}
+
+extern "C" int bsarec_caser_user_loss_grad(const bsarec_caser_user_step_config_t* cfg, const float* item_emb,
+                                           const float* user_emb, const float* weights, const float* fc, const float* fc2,
+                                           const int64_t* ids, const int64_t* users, const int64_t* answers,
+                                           const int64_t* neg_answers, void* state, int train, float* loss_out,
+                                           float* d_item_emb, float* d_user_emb, float* dweights, float* dfc, float* dfc2,
+                                           void* workspace, long workspace_bytes, void* stream) {
+    return caser_user_loss_grad(cfg, item_emb, user_emb, weights, fc, fc2, ids, users, answers, neg_answers, state, train,
+                                loss_out, d_item_emb, d_user_emb, dweights, dfc, dfc2, workspace, workspace_bytes, nullptr,
+                                (hipStream_t)stream);
+}
+
+extern "C" int bsarec_caser_user_train_step(const bsarec_caser_user_step_config_t* cfg, const int64_t* ids,
+                                            const int64_t* users, const int64_t* answers, const int64_t* neg_answers,
+                                            const bsarec_adam_t* adam_items, const bsarec_adam_t* adam_users,
+                                            const bsarec_adam_t* adam_weights, const bsarec_adam_t* adam_fc,
+                                            const bsarec_adam_t* adam_fc2, void* state, float* loss_out, void* workspace,
+                                            long workspace_bytes, void* stream) {
+    RET(caser_user_check(cfg));
+    const bsarec_caser_config_t& cv = cfg->step.conv;
+    const CaserW wo = caser_weights(cv);
+    RET(gru4rec_adam_check(adam_items, (long)cfg->step.item_size * cv.width));
+    RET(gru4rec_adam_check(adam_users, (long)cfg->num_users * cv.width));
+    RET(gru4rec_adam_check(adam_weights, wo.total));
+    RET(gru4rec_adam_check(adam_fc, (wo.F + 1) * cv.width));
+    RET(gru4rec_adam_check(adam_fc2, (2L * cv.width + 1) * cv.width));
+    // one t and one pair of bias corrections in `state` serve the five arrays
+    for (const bsarec_adam_t* a : {adam_users, adam_weights, adam_fc, adam_fc2})
+        if (a->lr != adam_items->lr || a->beta1 != adam_items->beta1 || a->beta2 != adam_items->beta2) return -10;
+    hipStream_t s = (hipStream_t)stream;
+    RET(caser_user_loss_grad(cfg, adam_items->params, adam_users->params, adam_weights->params, adam_fc->params,
+                             adam_fc2->params, ids, users, answers, neg_answers, state, 1, loss_out,
+                             const_cast<float*>(adam_items->grads), const_cast<float*>(adam_users->grads),
+                             const_cast<float*>(adam_weights->grads), const_cast<float*>(adam_fc->grads),
+                             const_cast<float*>(adam_fc2->grads), workspace, workspace_bytes, adam_items, s));
+    RET(adam_launch(*adam_items, state, s));
+    RET(adam_launch(*adam_users, state, s));
+    RET(adam_launch(*adam_weights, state, s));
+    RET(adam_launch(*adam_fc, state, s));
+    return adam_launch(*adam_fc2, state, s);
 }
 
 // ---------------------------------------------------------------------------------------------

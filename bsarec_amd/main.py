@@ -236,6 +236,9 @@ def parse_args(argv=None):
     p.add_argument("--caser_step", default=argparse.SUPPRESS, choices=("torch", "fused"),
                    help="Caser: step through autograd and torch.optim.Adam (default) or through the one-call HIP step "
                         "(lookup, convolutions, fc1 with Philox dropout, BPR head, item-table gradient and Adam in the library)")
+    p.add_argument("--caser_user", default=argparse.SUPPRESS, action="store_true",
+                   help="Caser: the personalised model -- a user embedding and a second Linear + ReLU on [z1 | P[user]] "
+                        "(valid with either --caser_step)")
     # not reference flags: BERT4Rec's cloze task (--model_type BERT4Rec).  Absent unless given
     p.add_argument("--mask_ratio", default=argparse.SUPPRESS, type=mask_ratio_value,
                    help="BERT4Rec: share of the real positions replaced by the mask token in a training step (default 0.2)")

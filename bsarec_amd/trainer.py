@@ -603,7 +603,7 @@ class Trainer:
                         loss = self.model.grad_step(input_ids, answers, neg_answers)
                         self._exchange_and_adam()
                     else:
-                        loss = self.model.train_step(input_ids, answers, neg_answers)
+                        loss = self._with_users(self.model.train_step, user_ids, input_ids, answers, neg_answers)
                 elif self.use_graph and not self.dp:
                     B = input_ids.shape[0]
                     first = B not in self._graphs
@@ -654,6 +654,13 @@ class Trainer:
             answers_all.append(answers)
         return self.get_full_sort_score(epoch, torch.cat(answers_all), torch.cat(preds))
 
+    def _with_users(self, fn, user_ids, *a):
+        """``fn(*a)``, with ``user_ids=`` behind it only for a model that reads them (``needs_user_ids``: the personalised
+        Caser); every other model is called exactly as it was."""
+        if getattr(self.model, "needs_user_ids", False):
+            return fn(*a, user_ids=user_ids)
+        return fn(*a)
+
     def topk_after_seen(self, user_ids, input_ids, k: int = 20, return_scores: bool = False):
         """The body of the reference's eval loop for one batch (src/trainers.py:126-149): full-catalogue scores of the
         last position (HIP), then ONE launch that sets the seen items' scores to 0 -- not -inf -- from the device CSR and
@@ -672,8 +679,8 @@ class Trainer:
         if not 1 <= k <= min(L.TOPK_MAX, V):
             raise ValueError(f"topk_full: k = {k}, expected 1..{min(L.TOPK_MAX, V)}")
         users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        return self._full_rank(self.model.last_hidden(input_ids), self._item_table().detach(), k, users,
-                               seen_csr(self.args.train_matrix, self.device), values=return_scores)
+        return self._full_rank(self._with_users(self.model.last_hidden, user_ids, input_ids), self._item_table().detach(), k,
+                               users, seen_csr(self.args.train_matrix, self.device), values=return_scores)
 
     def answer_ranks(self, user_ids, input_ids, answers, return_scores: bool = False):
         """The place of every answer in the full-catalogue order of ``topk_after_seen`` / ``topk_full`` (``--eval_full_rank
@@ -681,8 +688,8 @@ class Trainer:
         no list, no depth limit, no working memory.  int32 ranks [B], 0 = first (-1: an answer outside [0, item_size)); with
         ``return_scores`` also the answers' fp32 scores (0 for a seen answer)."""
         users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        return answer_rank(self.model.last_hidden(input_ids), self._item_table().detach(), answers, users,
-                           seen_csr(self.args.train_matrix, self.device), scores=return_scores)
+        return answer_rank(self._with_users(self.model.last_hidden, user_ids, input_ids), self._item_table().detach(), answers,
+                           users, seen_csr(self.args.train_matrix, self.device), scores=return_scores)
 
     def sampled_ranks(self, user_ids, input_ids, answers, return_candidates: bool = False, tag: int = 1):
         """Sampled-candidate evaluation of one batch: each answer against args.eval_negatives = N items the user has not seen,
@@ -701,8 +708,8 @@ class Trainer:
         users = user_ids.to(device=self.device, dtype=torch.int64).contiguous()
         ans = answers.to(device=self.device, dtype=torch.int64).contiguous()
         check_pool(self._neg_tables, users.cpu().numpy(), ans.cpu().numpy(), n, V)
-        out = sampled_rank(self.model.last_hidden(input_ids), self._item_table().detach(), users, ans,
-                           seen_csr(self.args.train_matrix, self.device), n, seed, tag, cum=self._neg_tables["cum"],
+        out = sampled_rank(self._with_users(self.model.last_hidden, user_ids, input_ids), self._item_table().detach(), users,
+                           ans, seen_csr(self.args.train_matrix, self.device), n, seed, tag, cum=self._neg_tables["cum"],
                            candidates=return_candidates)
         rank = out[0] if return_candidates else out
         bad = torch.nonzero(rank < 0).view(-1)

@@ -871,6 +871,50 @@ int bsarec_caser_train_step(const bsarec_caser_step_config_t *cfg, const int64_t
                             const bsarec_adam_t *adam_fc, void *state, float *loss_out,
                             void *workspace, long workspace_bytes, void *stream);
 
+/* The personalised Caser step (csrc/caser_user.h): the step above with a user table P = user_emb [U, d] and a second
+ * Linear + ReLU, fc2 = W2 [d, 2 d] followed by b2 [d] (bsarec_caser_fc2_floats(cfg) = 2 d d + d floats).  With z1 the s of the
+ * step above (relu(fc1(Dropout(z))), [B, d]) and users int64 [B]:
+ *   x2 = [ z1 | P[users] ] [B, 2 d];   s = max(0, x2 W2^T + b2) [B, d];   the BPR head of the step above on this s.
+ * bsarec_caser_user_loss_grad writes the loss and the gradient of every parameter: d_item_emb, dweights and dfc as above,
+ * d_user_emb [U, d] -- row u is the sum of dx2[b, d:2d] over the rows b with users[b] = u, duplicates included; EVERY float is
+ * written, exactly zero where no row names the user -- and dfc2 in the layout of fc2.  A user id is the 0-based index of the
+ * user; id 0 is an ordinary row; an id outside [0, U) is never dereferenced: its half of x2 is zero and it adds nothing.
+ *   fc2 runs on the launches of bsarec_caser_fc_fwd / _bwd with features = 2 d and no mask (the sums and their orders are those
+ * documented there).  The user rows are summed by the fixed-point row scatter of the item table (2^-40 units, exact while
+ * |sum| < 2^22) into an accumulator of their own, which the concatenation launch clears.  `state` and `train` as above.
+ *   bsarec_caser_user_train_step is the above with train = 1 followed by Adam on the five arrays, Adam's t advanced ONCE:
+ * adam_items (n = V d), adam_users (n = U d), adam_weights, adam_fc as above, adam_fc2 (n = bsarec_caser_fc2_floats).  lr, beta1
+ * and beta2 of the five must agree; shadow_bf16, grads2, grads2_n, n_grad_srcs and wimage_plan must be null / 0.
+ *   Launches, all on `stream`, one after the other: the step counter (train != 0), the item lookup, bsarec_caser_fwd (2), the
+ * fc1 forward, the concatenation, the fc2 forward, the BPR rows on s, the fc2 backward (2), the user gradient with the split of
+ * dx2, the fc1 backward (2), bsarec_caser_bwd (3), the item-table gradient, the user flush, the item flush with the mean loss
+ * (and Adam's t) in its closing block, then one Adam launch per array.  No allocation, no host synchronisation: capturable, a
+ * replay is the NEXT step.  Every output is bit-deterministic (no floating-point atomics, every sum in an order that is a
+ * function of the shape alone) and does not depend on what the workspace holds on entry.
+ *   Workspace: bsarec_caser_user_step_workspace_bytes(cfg) bytes (host-only query).  In floats: the regions of
+ * bsarec_caser_step_workspace_bytes(&cfg->step) in their order -- its s region holds z1, its ds region d(z1) -- then
+ * x2 [B, 2 d] | s [B, d] | ds [B, d] | dx2 [B, 2 d] | the user accumulator, U d 64-bit words.
+ *   Limits (else < 0 before any HIP call): those of bsarec_caser_loss_grad / _train_step for cfg->step and every argument they
+ * share; num_users >= 1; user_emb, fc2, d_user_emb and dfc2 (Adam's four included) non-null and 16-byte aligned, users 8-byte;
+ * workspace_bytes at least the queried size. */
+typedef struct {
+    bsarec_caser_step_config_t step;
+    int num_users;                     /* U >= 1 */
+} bsarec_caser_user_step_config_t;
+long bsarec_caser_fc2_floats(const bsarec_caser_config_t *cfg);
+long bsarec_caser_user_step_workspace_bytes(const bsarec_caser_user_step_config_t *cfg);
+int bsarec_caser_user_loss_grad(const bsarec_caser_user_step_config_t *cfg, const float *item_emb, const float *user_emb,
+                                const float *weights, const float *fc, const float *fc2, const int64_t *ids,
+                                const int64_t *users, const int64_t *answers, const int64_t *neg_answers,
+                                void *state, int train, float *loss_out, float *d_item_emb, float *d_user_emb,
+                                float *dweights, float *dfc, float *dfc2,
+                                void *workspace, long workspace_bytes, void *stream);
+int bsarec_caser_user_train_step(const bsarec_caser_user_step_config_t *cfg, const int64_t *ids, const int64_t *users,
+                                 const int64_t *answers, const int64_t *neg_answers, const bsarec_adam_t *adam_items,
+                                 const bsarec_adam_t *adam_users, const bsarec_adam_t *adam_weights,
+                                 const bsarec_adam_t *adam_fc, const bsarec_adam_t *adam_fc2, void *state, float *loss_out,
+                                 void *workspace, long workspace_bytes, void *stream);
+
 /* Band-limited autocorrelation attention of the FEARec sibling model (csrc/fea_attn.h): with q, k, v [B, L, D] (D = width),
  * F = L / 2 + 1 and a band lo <= f < hi of rfft bins,
  *   Qf[b, c, f] = sum_t q[b, t, c] e^{-2 pi i f t / L} (Kf alike),  S[b, f] = sum_c Qf[b, c, f] conj(Kf[b, c, f]),

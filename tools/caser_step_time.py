@@ -9,7 +9,12 @@
 Three models of the same shape, everything allocated (and the graph captured) first; 20 warm-up and 200 timed steps, the three
 paths alternating step by step, an event pair around each step.  Per shape one JSON line: median / min / max milliseconds of
 each path and the ratios of the medians.  The host stays ahead of the device only as far as one step: an event pair is read
-back after every step, so a path that is bound by launching from the host shows that cost."""
+back after every step, so a path that is bound by launching from the host shows that cost.
+
+    python tools/caser_step_time.py --user        # the personalised Caser (caser_user), U = 6040 users
+
+  the three paths with the flag ON (the torch path is the torch-mode step of the personalised model) and, beside them,
+  graph_off: the flag-off fused step of the same run, so that the cost of the user half's eight launches is visible."""
 import argparse
 import json
 import os
@@ -37,11 +42,14 @@ def main():
     ap.add_argument("--nv", type=int, default=4)
     ap.add_argument("--dropout", type=float, default=0.5)
     ap.add_argument("--batches", type=int, nargs="+", default=[256, 1024])
+    ap.add_argument("--user", action="store_true", help="time the personalised Caser (caser_user) and the flag-off step beside it")
+    ap.add_argument("--users", type=int, default=6040)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("caser_step_time: no GPU (there is nothing to measure on a CPU)")
     from bsarec_amd import CaserModel
     L, d, V = a.seq_len, a.hidden, a.items
+    flag = dict(caser_user=True, num_users=a.users) if a.user else {}
     for B in a.batches:
         def model(**kw):
             torch.manual_seed(B)
@@ -51,21 +59,27 @@ def main():
             m.train()
             m.set_seed(42)
             return m
-        mt, me, mg = model(), model(caser_step="fused", caser_step_graph=False), model(caser_step="fused")
+        mt, me, mg = model(**flag), model(caser_step="fused", caser_step_graph=False, **flag), model(caser_step="fused", **flag)
         g = torch.Generator(device="cuda").manual_seed(B)
         ids = torch.randint(1, V, (B, L), device="cuda", generator=g)
         pos = torch.randint(1, V, (B,), device="cuda", generator=g)
         neg = torch.randint(1, V, (B,), device="cuda", generator=g)
+        users = torch.randint(0, a.users, (B,), device="cuda", generator=g) if a.user else None
+        kw = dict(user_ids=users) if a.user else {}
         opt = torch.optim.Adam(mt.parameters(), lr=1e-3)
 
         def torch_step():
-            loss = mt.calculate_loss(ids, pos, neg)
+            loss = mt.calculate_loss(ids, pos, neg, **kw)
             opt.zero_grad()
             loss.backward()
             opt.step()
             return loss.detach()
 
-        paths = {"torch": torch_step, "eager": lambda: me.train_step(ids, pos, neg), "graph": lambda: mg.train_step(ids, pos, neg)}
+        paths = {"torch": torch_step, "eager": lambda: me.train_step(ids, pos, neg, **kw),
+                 "graph": lambda: mg.train_step(ids, pos, neg, **kw)}
+        if a.user:
+            m0 = model(caser_step="fused")
+            paths["graph_off"] = lambda: m0.train_step(ids, pos, neg)
 
         def timed(fn):
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -88,9 +102,13 @@ def main():
         med = {k: float(np.median(v)) for k, v in ms.items()}
         line = {"B": B, "L": L, "d": d, "n_h": a.nh, "n_v": a.nv, "V": V, "dropout": a.dropout, "steps": a.steps,
                 "optimiser_tensors": len(list(mt.parameters()))}
+        if a.user:
+            line["U"] = a.users
         line.update({f"{k}_ms": stats(v) for k, v in ms.items()})
         line["eager_over_torch"] = round(med["eager"] / med["torch"], 3)
         line["graph_over_torch"] = round(med["graph"] / med["torch"], 3)
+        if a.user:
+            line["graph_minus_graph_off_ms"] = round(med["graph"] - med["graph_off"], 4)
         print(json.dumps(line), flush=True)
 
 
