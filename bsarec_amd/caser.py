@@ -19,6 +19,7 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
+from . import _fused_step as FS
 from . import _lib as L
 
 CASER_NH = (4, 8, 16, 32)
@@ -396,13 +397,14 @@ class CaserModel(nn.Module):
         diff = (s * pos).sum(-1) - (s * neg).sum(-1)
         return -torch.log(torch.sigmoid(diff) + 1e-10).mean()
 
-    # ---- the fused step (caser_step = "fused"; bsarec_caser_loss_grad / bsarec_caser_train_step) ---------------------------
+    # ---- the fused step (caser_step = "fused"; bsarec_caser_loss_grad / bsarec_caser_train_step; host side: _fused_step.py) ----
     def _step_buffers(self):
         """What the fused step owns beside the parameters: the device step state (seed, step counter, Adam t), the three gradient
-        arrays, the Adam moments of the item table, of the convolution's flat array and of the fc1 flat array, and per batch
-        shape a workspace, static id buffers and a captured graph.  Built on first use; dropped by ``.to()`` / ``reflatten()``
-        (a new parameter storage).  With ``caser_user`` two more arrays, the user table and the fc2 flat array, each with its
-        gradient and moments (dP / mP / vP, dG / mG / vG), and a static ``users`` buffer per batch shape."""
+        arrays, the Adam moments of the item table ("E"), of the convolution's flat array ("W") and of the fc1 flat array ("F"),
+        and per batch shape a workspace, static id buffers and a captured graph.  Built on first use; dropped by ``.to()`` /
+        ``reflatten()`` (a new parameter storage).  With ``caser_user`` two more arrays, the user table ("P") and the fc2 flat
+        array ("G"), each with its gradient and moments (dP / mP / vP, dG / mG / vG), and a static ``users`` buffer per batch
+        shape."""
         if self.caser_step != "fused":
             raise RuntimeError("Caser: the fused step's buffers exist only with caser_step = 'fused'")
         self._require_gpu()
@@ -410,25 +412,14 @@ class CaserModel(nn.Module):
         E, flat, fc = self.item_embeddings.weight.data, self.conv._flat, self._fc_flat
         if flat.device != E.device or fc.device != E.device or not E.is_contiguous() or E.dtype != torch.float32:
             raise RuntimeError("caser: the item table, the filters and fc1 must be contiguous fp32 on one device")
-        key = (E.data_ptr(), flat.data_ptr(), fc.data_ptr(), E.device)
         arrays = [("E", E), ("W", flat), ("F", fc)]
-        if self.caser_user:                               # the user table and the fc2 flat array: dP / mP / vP, dG / mG / vG
+        if self.caser_user:
             P, fc2 = self.user_embeddings.weight.data, self._fc2_flat
             if P.device != E.device or fc2.device != E.device or not P.is_contiguous() or P.dtype != torch.float32:
                 raise RuntimeError("caser: the user table and fc2 must be contiguous fp32 on the item table's device")
-            key += (P.data_ptr(), fc2.data_ptr())
             arrays += [("P", P), ("G", fc2)]
-        f = self._fused
-        if f is None or f["key"] != key:
-            state = torch.zeros(8, dtype=torch.int64, device=E.device)
-            state[0] = self._stream_seed()
-            f = dict(key=key, state=state, E=E, flat=flat, fc=fc, adam=None, slots={})
-            if self.caser_user:
-                f["P"], f["fc2"] = P, fc2
-            for name, t in arrays:
-                f["d" + name], f["m" + name], f["v" + name] = torch.empty_like(t), torch.zeros_like(t), torch.zeros_like(t)
-            self._fused = f
-        return f
+        self._fused = FS.buffers(self._fused, arrays, self._stream_seed())
+        return self._fused
 
     @property
     def step_state(self) -> torch.Tensor:
@@ -448,14 +439,7 @@ class CaserModel(nn.Module):
                 nbytes = L.load().bsarec_caser_step_workspace_bytes(cfg)
             if nbytes < 0:
                 raise ValueError(f"caser: unsupported step shape B = {B}, dropout = {self.p_drop} (1 <= B <= 65536, 0 <= p < 1)")
-            dev = f["E"].device
-            s = dict(cfg=cfg, nbytes=nbytes, ws=torch.empty(nbytes, dtype=torch.uint8, device=dev),
-                     ids=torch.zeros((B, c.seq_len), dtype=torch.int64, device=dev),
-                     ans=torch.zeros(B, dtype=torch.int64, device=dev), neg=torch.zeros(B, dtype=torch.int64, device=dev),
-                     loss=torch.zeros((), dtype=torch.float32, device=dev), graph=None)
-            if self.caser_user:
-                s["users"] = torch.zeros(B, dtype=torch.int64, device=dev)
-            f["slots"][B] = s
+            s = FS.slot(f, B, cfg, nbytes, (B, c.seq_len), ("users",) if self.caser_user else ())
         return s
 
     def _fill(self, s, input_ids, answers, neg_answers, users=None):
@@ -466,20 +450,20 @@ class CaserModel(nn.Module):
         s["neg"].copy_(neg_answers.reshape(-1))
         if users is not None:
             s["users"].copy_(users)
+        return s
 
     def _loss_grad(self, f, s, train: bool):
-        stream = torch.cuda.current_stream(f["E"].device).cuda_stream
+        ptr = lambda t: t.data_ptr()
+        tail = (ptr(f["state"]), int(train), ptr(s["loss"]))
         if self.caser_user:
             L.check(L.load().bsarec_caser_user_loss_grad(
-                s["cfg"], f["E"].data_ptr(), f["P"].data_ptr(), f["flat"].data_ptr(), f["fc"].data_ptr(), f["fc2"].data_ptr(),
-                s["ids"].data_ptr(), s["users"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), f["state"].data_ptr(),
-                int(train), s["loss"].data_ptr(), f["dE"].data_ptr(), f["dP"].data_ptr(), f["dW"].data_ptr(), f["dF"].data_ptr(),
-                f["dG"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream), "bsarec_caser_user_loss_grad")
+                s["cfg"], ptr(f["E"]), ptr(f["P"]), ptr(f["W"]), ptr(f["F"]), ptr(f["G"]), ptr(s["ids"]), ptr(s["users"]),
+                ptr(s["ans"]), ptr(s["neg"]), *tail, ptr(f["dE"]), ptr(f["dP"]), ptr(f["dW"]), ptr(f["dF"]), ptr(f["dG"]),
+                ptr(s["ws"]), s["nbytes"], FS.stream(f)), "bsarec_caser_user_loss_grad")
             return
         L.check(L.load().bsarec_caser_loss_grad(
-            s["cfg"], f["E"].data_ptr(), f["flat"].data_ptr(), f["fc"].data_ptr(), s["ids"].data_ptr(), s["ans"].data_ptr(),
-            s["neg"].data_ptr(), f["state"].data_ptr(), int(train), s["loss"].data_ptr(), f["dE"].data_ptr(), f["dW"].data_ptr(),
-            f["dF"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream), "bsarec_caser_loss_grad")
+            s["cfg"], ptr(f["E"]), ptr(f["W"]), ptr(f["F"]), ptr(s["ids"]), ptr(s["ans"]), ptr(s["neg"]), *tail, ptr(f["dE"]),
+            ptr(f["dW"]), ptr(f["dF"]), ptr(s["ws"]), s["nbytes"], FS.stream(f)), "bsarec_caser_loss_grad")
 
     def loss_and_grads(self, input_ids, answers, neg_answers, train: bool = True, user_ids=None):
         """The BPR loss (0-d tensor) and {state_dict key: gradient} of one batch through bsarec_caser_loss_grad
@@ -490,46 +474,31 @@ class CaserModel(nn.Module):
         users = self._users(user_ids, input_ids)
         self._require_gpu(input_ids)
         f = self._step_buffers()
-        s = self._slot(f, int(input_ids.shape[0]))
-        self._fill(s, input_ids, answers, neg_answers, users)
+        s = self._fill(self._slot(f, int(input_ids.shape[0])), input_ids, answers, neg_answers, users)
         self._loss_grad(f, s, train)
         grads = OrderedDict([("item_embeddings.weight", f["dE"].clone())])
         if self.caser_user:
             grads["user_embeddings.weight"] = f["dP"].clone()
         for name, (o, n, shp) in self.conv._slices.items():
             grads["conv." + name] = f["dW"][o:o + n].view(shp).clone()
-        nw = self.fc1.weight.numel()
-        grads["fc1.weight"] = f["dF"][:nw].view(self.fc1.weight.shape).clone()
-        grads["fc1.bias"] = f["dF"][nw:].clone()
-        if self.caser_user:
-            nw = self.fc2.weight.numel()
-            grads["fc2.weight"] = f["dG"][:nw].view(self.fc2.weight.shape).clone()
-            grads["fc2.bias"] = f["dG"][nw:].clone()
+        for name, lin, g in (("fc1", self.fc1, "dF"),) + ((("fc2", self.fc2, "dG"),) if self.caser_user else ()):
+            nw = lin.weight.numel()
+            grads[name + ".weight"] = f[g][:nw].view(lin.weight.shape).clone()
+            grads[name + ".bias"] = f[g][nw:].clone()
         return s["loss"].clone(), grads
 
-    def _adam_structs(self, f):
-        if f["adam"] is None:
-            a = self.args
-            hyper = (float(getattr(a, "lr", 1e-3)), float(getattr(a, "adam_beta1", 0.9)), float(getattr(a, "adam_beta2", 0.999)),
-                     1e-8, float(getattr(a, "weight_decay", 0.0)), 1.0, None, 0)
-            f["adam"] = tuple(L.Adam(f[p].data_ptr(), f["d" + k].data_ptr(), f["m" + k].data_ptr(), f["v" + k].data_ptr(),
-                                     f[p].numel(), *hyper) for p, k in (("E", "E"), ("flat", "W"), ("fc", "F")) +
-                              ((("P", "P"), ("fc2", "G")) if self.caser_user else ()))
-        return f["adam"]
-
     def _train_step(self, f, s):
-        stream = torch.cuda.current_stream(f["E"].device).cuda_stream
+        ptr = lambda t: t.data_ptr()
+        adams = FS.adam_structs(f, self.args)             # in the arrays' order: items, weights, fc (, users, fc2)
+        tail = (ptr(f["state"]), ptr(s["loss"]), ptr(s["ws"]), s["nbytes"], FS.stream(f))
         if self.caser_user:
-            items, weights, fc, users, fc2 = self._adam_structs(f)
+            items, weights, fc, users, fc2 = adams
             L.check(L.load().bsarec_caser_user_train_step(
-                s["cfg"], s["ids"].data_ptr(), s["users"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), items, users,
-                weights, fc, fc2, f["state"].data_ptr(), s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream),
+                s["cfg"], ptr(s["ids"]), ptr(s["users"]), ptr(s["ans"]), ptr(s["neg"]), items, users, weights, fc, fc2, *tail),
                 "bsarec_caser_user_train_step")
             return
-        items, weights, fc = self._adam_structs(f)
-        L.check(L.load().bsarec_caser_train_step(
-            s["cfg"], s["ids"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), items, weights, fc, f["state"].data_ptr(),
-            s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream), "bsarec_caser_train_step")
+        L.check(L.load().bsarec_caser_train_step(s["cfg"], ptr(s["ids"]), ptr(s["ans"]), ptr(s["neg"]), *adams, *tail),
+                "bsarec_caser_train_step")
 
     def train_step(self, input_ids, answers, neg_answers=None, same_target=None, user_ids=None):
         """caser_step = "fused": one optimisation step in one C call -- the step counter, the lookup, the convolution block, fc1
@@ -544,17 +513,5 @@ class CaserModel(nn.Module):
         users = self._users(user_ids, input_ids)
         self._require_gpu(input_ids)
         f = self._step_buffers()
-        s = self._slot(f, int(input_ids.shape[0]))
-        self._fill(s, input_ids, answers, neg_answers, users)
-        if not getattr(self.args, "caser_step_graph", True):
-            self._train_step(f, s)
-            return s["loss"]
-        if s["graph"] is None:
-            self._adam_structs(f)
-            self._loss_grad(f, s, False)                  # every kernel of the chain has run once before the capture; no
-            graph = torch.cuda.CUDAGraph()                # counter moves and nothing is updated (train = 0)
-            with torch.cuda.graph(graph):
-                self._train_step(f, s)
-            s["graph"] = graph
-        s["graph"].replay()
-        return s["loss"]
+        s = self._fill(self._slot(f, int(input_ids.shape[0])), input_ids, answers, neg_answers, users)
+        return FS.train_step(f, s, self.args, getattr(self.args, "caser_step_graph", True), self._loss_grad, self._train_step)

@@ -20,7 +20,7 @@
 #include "sampled_softmax.h"
 #include "lazy_adam.h"
 #include "gru.h"
-#include "gru4rec_step.h"
+#include "pair_step.h"
 #include "gru4rec_cand.h"
 #include "caser.h"
 #include "caser_step.h"
@@ -2645,8 +2645,122 @@ extern "C" int bsarec_fea_attn_bwd(const bsarec_fea_attn_config_t* cfg, const fl
 }
 
 // ---------------------------------------------------------------------------------------------
-// GRU4Rec training step (gru4rec_step.h): lookup + dropout, the GRU stack, the BPR head, every gradient, Adam -- plan-less, one
-// linear chain of launches on the caller's stream, no allocation, no host synchronisation
+// The shell of a pairwise step (pair_step.h), once for the GRU4Rec, Caser and personalised Caser steps: a driver fills one
+// PairStep and calls pair_begin_embed, pair_bpr (or its own head), pair_item_grad and pair_flush_tick around its encoder's
+// launches.  Behind them the argument checks that the entry points of the three steps share.
+// ---------------------------------------------------------------------------------------------
+// dropout site 0 of a step (GRU4Rec: the token rows; Caser: z in front of fc1); train = false: no mask, whatever p
+static DropP site0_drop(float p, const void* state, bool train) {
+    DropP d;
+    d.thresh = train ? drop_thresh(p) : 0;
+    d.scale = (train && p > 0.f) ? (float)(1.0 / (1.0 - (double)p)) : 1.0f;
+    d.rng = (const uint64_t*)state; d.site = 0;
+    return d;
+}
+
+struct PairStep {
+    int B, d, V; long T;                                 // rows, width, items, tokens
+    const float* E; const int64_t* ids; const int64_t* answers; const int64_t* neg_answers;
+    void* state; int train;
+    DropP drop;                                          // of the token rows
+    float* x; float* dx; float* c; float* rows;          // workspace: [T][d], [T][d], [B], the loss rows [B]
+    unsigned long long* acc;                             // workspace: the fixed-point accumulator [V][d]
+    float* dE; float* loss_out;
+    const bsarec_adam_t* tick_adam;                      // null, or the Adam whose t the closing block advances (a *_train_step)
+    hipStream_t s;
+};
+
+// a training step moves the step counter first; then x = E[ids] (times the mask), and the same launch clears the accumulator
+static void pair_begin_embed(const PairStep& p) {
+    if (p.train) hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(1), 0, p.s, (uint64_t*)p.state, (long long*)nullptr, 0);
+    PairEmbedP pe;
+    pe.E = p.E; pe.ids = p.ids; pe.x = p.x; pe.T = p.T; pe.d = p.d; pe.V = p.V; pe.drop = p.drop;
+    pe.acc = p.acc; pe.acc_n2 = (long)p.V * p.d / 2;
+    DISPATCH_LPR(p.d, hipLaunchKernelGGL(pair_embed_kernel<LPR>, dim3(std::min(cdiv(p.T, ROW_THREADS / LPR), 4096)),
+                                         dim3(ROW_THREADS), 0, p.s, pe));
+}
+
+// the BPR rows on the encoder's state sv [B][d]: ds [B][d], c and the loss rows are written
+static void pair_bpr(const PairStep& p, const float* sv, float* ds) {
+    PairBprP pb;
+    pb.s = sv; pb.E = p.E; pb.ans = p.answers; pb.neg = p.neg_answers; pb.B = p.B; pb.d = p.d; pb.V = p.V;
+    pb.ds = ds; pb.c = p.c; pb.loss_rows = p.rows;
+    DISPATCH_LPR(p.d, hipLaunchKernelGGL(pair_bpr_kernel<LPR>, dim3(cdiv(p.B, ROW_THREADS / LPR)), dim3(ROW_THREADS), 0, p.s, pb));
+}
+
+// dE's rows into the accumulator: the T token rows, then the head's -- 2 B pairwise rows with head_rows = the sv of pair_bpr
+// (C = 0), or C candidate rows with head_rows = the dEc [C][d] of g4c_launch
+static void pair_item_grad(const PairStep& p, const float* head_rows, int C = 0) {
+    PairGradP pg;
+    pg.dx = p.dx; pg.ids = p.ids; pg.ans = p.answers; pg.neg = p.neg_answers;
+    pg.T = p.T; pg.B = p.B; pg.C = C; pg.d = p.d; pg.V = p.V; pg.drop = p.drop; pg.dA = p.acc;
+    pg.head_rows = head_rows; pg.c = p.c;
+    const long n_head = C ? C : 2L * p.B;
+    DISPATCH_LPR(p.d, {
+        const dim3 grid(cdiv(p.T + n_head, SCATTER_FLOATS / (4 * LPR)));
+        if (C) hipLaunchKernelGGL(g4c_item_grad_kernel<LPR>, grid, dim3(ROW_THREADS), 0, p.s, pg);
+        else hipLaunchKernelGGL(pair_item_grad_kernel<LPR>, grid, dim3(ROW_THREADS), 0, p.s, pg);
+    });
+}
+
+// the flush of a table's accumulator [n] into every float of dst
+static LookupAcc pair_flush_acc(unsigned long long* acc, float* dst, long n) {
+    LookupAcc la;
+    memset(&la, 0, sizeof(la));
+    la.acc = acc; la.dst = dst; la.n4 = n / 4; la.dense_zero = 1;
+    la.nblocks = std::min(cdiv(la.n4, ROW_THREADS), 1024);
+    return la;
+}
+
+// accumulator -> dE, and the one closing block of the step: the mean loss and, with tick_adam, Adam's t
+static int pair_flush_tick(const PairStep& p) {
+    const LookupAcc la = pair_flush_acc(p.acc, p.dE, (long)p.V * p.d);
+    const bsarec_adam_t* a = p.tick_adam;
+    const TickP tk = a ? make_tick(p.state, 1, a->lr, a->beta1, a->beta2, p.rows, p.B, p.loss_out, nullptr, 0, 0)
+                       : make_tick(p.state, 0, 0.f, 0.f, 0.f, p.rows, p.B, p.loss_out, nullptr, 0, 0);
+    hipLaunchKernelGGL(pair_flush_kernel, dim3(la.nblocks + 1), dim3(ROW_THREADS), 0, p.s, la, tk);
+    return (int)hipGetLastError();
+}
+
+// the pointers of an entry point: p16 aligned to 16 bytes, p8 to 8, loss_out to 4, none null
+static int pair_ptrs_check(std::initializer_list<const void*> p16, std::initializer_list<const void*> p8, const float* loss_out) {
+    for (const void* p : p16)
+        if (!aligned_to(p, 16)) return -10;
+    for (const void* p : p8)
+        if (!aligned_to(p, 8)) return -10;
+    return aligned_to(loss_out, 4) ? 0 : -10;
+}
+
+// an Adam of a step: fp32 arrays only, one gradient source, 16-byte aligned, n floats
+struct StepAdam { const bsarec_adam_t* a; long n; };
+static int pair_adam_check(const bsarec_adam_t* a, long n) {
+    RET(adam_check(a));
+    if (a->n != n) return -10;
+    if (a->shadow_bf16 || a->grads2 || a->grads2_n || a->n_grad_srcs || a->wimage_plan) return -10;
+    for (const void* p : {(const void*)a->params, (const void*)a->grads, (const void*)a->exp_avg, (const void*)a->exp_avg_sq})
+        if (!aligned_to(p, 16)) return -10;
+    return 0;
+}
+// every Adam of a *_train_step: one t and one pair of bias corrections in `state` serve them all, so lr and the betas are
+// the first's
+template <int N>
+static int pair_adams_check(const StepAdam (&adams)[N]) {
+    for (const StepAdam& x : adams) RET(pair_adam_check(x.a, x.n));
+    const bsarec_adam_t* a0 = adams[0].a;
+    for (const StepAdam& x : adams)
+        if (x.a->lr != a0->lr || x.a->beta1 != a0->beta1 || x.a->beta2 != a0->beta2) return -10;
+    return 0;
+}
+template <int N>
+static int pair_adams_launch(const StepAdam (&adams)[N], void* state, hipStream_t s) {
+    for (const StepAdam& x : adams) RET(adam_launch(*x.a, state, s));
+    return 0;
+}
+static float* adam_grads(const bsarec_adam_t* a) { return const_cast<float*>(a->grads); }
+
+// ---------------------------------------------------------------------------------------------
+// GRU4Rec training step: lookup + dropout, the GRU stack, the BPR head, every gradient, Adam -- plan-less, one linear chain of
+// launches on the caller's stream, no allocation, no host synchronisation
 // ---------------------------------------------------------------------------------------------
 static int gru4rec_check(const bsarec_gru4rec_config_t* c) {
     if (!c) return -10;
@@ -2680,19 +2794,6 @@ static Gru4RecWs gru4rec_ws(const bsarec_gru4rec_config_t& c) {
 extern "C" long bsarec_gru4rec_workspace_bytes(const bsarec_gru4rec_config_t* cfg) {
     if (gru4rec_check(cfg)) return -10;
     return gru4rec_ws(*cfg).total * (long)sizeof(float);
-}
-
-static int gru4rec_args(const bsarec_gru4rec_config_t* cfg, const float* item_emb, const float* weights, const int64_t* ids,
-                        const int64_t* answers, const int64_t* neg_answers, const void* state, const float* loss_out,
-                        const float* d_item_emb, const float* dweights, const void* workspace, long workspace_bytes) {
-    RET(gru4rec_check(cfg));
-    for (const void* p : {(const void*)item_emb, (const void*)weights, (const void*)d_item_emb, (const void*)dweights, workspace})
-        if (!aligned_to(p, 16)) return -10;
-    for (const void* p : {(const void*)ids, (const void*)answers, (const void*)neg_answers, state})
-        if (!aligned_to(p, 8)) return -10;
-    if (!aligned_to(loss_out, 4)) return -10;
-    if (workspace_bytes < gru4rec_ws(*cfg).total * (long)sizeof(float)) return -10;
-    return 0;
 }
 
 // The heads over candidates shared by the batch (gru4rec_cand.h; bsarec_gru4rec_cand_*): in a step, scores, rows, backward (and
@@ -2762,57 +2863,25 @@ static int gru4rec_run(const bsarec_gru4rec_config_t& c, const float* E, const f
                        const int64_t* answers, const int64_t* neg_answers, void* state, int train, float* loss_out, float* dE,
                        float* dweights, void* workspace, const bsarec_adam_t* tick_adam, const bsarec_gru4rec_head_t* head,
                        hipStream_t s) {
-    const int B = c.gru.batch, d = c.gru.input_size, V = c.item_size;
-    const long T = (long)B * c.gru.seq_len;
+    const int B = c.gru.batch, d = c.gru.input_size;
     const Gru4RecWs ws = gru4rec_ws(c);
     float* w = (float*)workspace;
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(w + ws.acc);
-    if (train) hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(1), 0, s, (uint64_t*)state, (long long*)nullptr, 0);
-    DropP drop;
-    drop.thresh = train ? drop_thresh(c.dropout) : 0;
-    drop.scale = (train && c.dropout > 0.f) ? (float)(1.0 / (1.0 - (double)c.dropout)) : 1.0f;
-    drop.rng = (const uint64_t*)state; drop.site = 0;
-
-    Gru4RecEmbedP pe;
-    pe.E = E; pe.ids = ids; pe.x = w + ws.x; pe.T = T; pe.d = d; pe.V = V; pe.drop = drop;
-    pe.acc = acc; pe.acc_n2 = (long)V * d / 2;
-    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_embed_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)),
-                                       dim3(ROW_THREADS), 0, s, pe));
-    RET(bsarec_gru_fwd(&c.gru, w + ws.x, weights, 1, 1, w + ws.s, w + ws.gru, ws.gru_bytes, s));
-
+    const PairStep p = {B, d, c.item_size, (long)B * c.gru.seq_len, E, ids, answers, neg_answers, state, train,
+                        site0_drop(c.dropout, state, train != 0), w + ws.x, w + ws.dx, w + ws.c, w + ws.rows,
+                        reinterpret_cast<unsigned long long*>(w + ws.acc), dE, loss_out, tick_adam, s};
+    pair_begin_embed(p);
+    RET(bsarec_gru_fwd(&c.gru, p.x, weights, 1, 1, w + ws.s, w + ws.gru, ws.gru_bytes, s));
     long dEc = 0, total = 0;
     G4cWs g = {};
     if (head) {
         g = g4c_step_ws(c, *head, &dEc, &total);
-        g4c_launch(g, w, w + ws.s, E, answers, neg_answers, B, d, V, *head, w + ws.rows, w + ws.ds, w + dEc, s);
+        g4c_launch(g, w, w + ws.s, E, answers, neg_answers, B, d, p.V, *head, p.rows, w + ws.ds, w + dEc, s);
     } else {
-        Gru4RecBprP pb;
-        pb.s = w + ws.s; pb.E = E; pb.ans = answers; pb.neg = neg_answers; pb.B = B; pb.d = d; pb.V = V;
-        pb.ds = w + ws.ds; pb.c = w + ws.c; pb.loss_rows = w + ws.rows;
-        DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_bpr_kernel<LPR>, dim3(cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS), 0, s, pb));
+        pair_bpr(p, w + ws.s, w + ws.ds);
     }
-    RET(bsarec_gru_bwd(&c.gru, w + ws.x, weights, 1, w + ws.ds, w + ws.gru, ws.gru_bytes, w + ws.dx, dweights, s));
-
-    Gru4RecGradP pg;                                   // the token rows, then the head's: 2 B pairwise rows or C candidate rows
-    pg.dx = w + ws.dx; pg.ids = ids; pg.ans = answers; pg.neg = neg_answers;
-    pg.T = T; pg.B = B; pg.C = g.C; pg.d = d; pg.V = V; pg.drop = drop; pg.dA = acc;
-    pg.head_rows = head ? w + dEc : w + ws.s; pg.c = w + ws.c;
-    const long n_head = head ? g.C : 2L * B;
-    DISPATCH_LPR(d, {
-        const dim3 grid(cdiv(T + n_head, SCATTER_FLOATS / (4 * LPR)));
-        if (head) hipLaunchKernelGGL(g4c_item_grad_kernel<LPR>, grid, dim3(ROW_THREADS), 0, s, pg);
-        else hipLaunchKernelGGL(gru4rec_item_grad_kernel<LPR>, grid, dim3(ROW_THREADS), 0, s, pg);
-    });
-
-    LookupAcc la;
-    memset(&la, 0, sizeof(la));
-    la.acc = acc; la.dst = dE; la.n4 = (long)V * d / 4; la.dense_zero = 1;
-    la.nblocks = std::min(cdiv(la.n4, ROW_THREADS), 1024);
-    const TickP tk = tick_adam ? make_tick(state, 1, tick_adam->lr, tick_adam->beta1, tick_adam->beta2, w + ws.rows, B, loss_out,
-                                           nullptr, 0, 0)
-                               : make_tick(state, 0, 0.f, 0.f, 0.f, w + ws.rows, B, loss_out, nullptr, 0, 0);
-    hipLaunchKernelGGL(gru4rec_flush_kernel, dim3(la.nblocks + 1), dim3(ROW_THREADS), 0, s, la, tk);
-    return (int)hipGetLastError();
+    RET(bsarec_gru_bwd(&c.gru, p.x, weights, 1, w + ws.ds, w + ws.gru, ws.gru_bytes, p.dx, dweights, s));
+    pair_item_grad(p, head ? w + dEc : w + ws.s, g.C);
+    return pair_flush_tick(p);
 }
 
 extern "C" long bsarec_gru4rec_cand_workspace_bytes(const bsarec_gru4rec_config_t* cfg, const bsarec_gru4rec_head_t* head) {
@@ -2827,8 +2896,9 @@ static int gru4rec_loss_grad(const bsarec_gru4rec_config_t* cfg, const float* it
                              const int64_t* answers, const int64_t* neg_answers, void* state, int train, float* loss_out,
                              float* d_item_emb, float* dweights, void* workspace, long workspace_bytes,
                              const bsarec_adam_t* tick_adam, const bsarec_gru4rec_head_t* head, hipStream_t s) {
-    RET(gru4rec_args(cfg, item_emb, weights, ids, answers, neg_answers, state, loss_out, d_item_emb, dweights, workspace,
-                     workspace_bytes));
+    RET(gru4rec_check(cfg));
+    RET(pair_ptrs_check({item_emb, weights, d_item_emb, dweights, workspace}, {ids, answers, neg_answers, state}, loss_out));
+    if (workspace_bytes < gru4rec_ws(*cfg).total * (long)sizeof(float)) return -10;
     if (head) {
         RET(g4c_head_check(head, cfg->gru.batch));
         if (workspace_bytes < bsarec_gru4rec_cand_workspace_bytes(cfg, head)) return -10;
@@ -2854,33 +2924,18 @@ extern "C" int bsarec_gru4rec_cand_loss_grad(const bsarec_gru4rec_config_t* cfg,
                              workspace, workspace_bytes, nullptr, head, (hipStream_t)stream);
 }
 
-// fp32 arrays only, one gradient source, 16-byte aligned
-static int gru4rec_adam_check(const bsarec_adam_t* a, long n) {
-    RET(adam_check(a));
-    if (a->n != n) return -10;
-    if (a->shadow_bf16 || a->grads2 || a->grads2_n || a->n_grad_srcs || a->wimage_plan) return -10;
-    for (const void* p : {(const void*)a->params, (const void*)a->grads, (const void*)a->exp_avg, (const void*)a->exp_avg_sq})
-        if (!aligned_to(p, 16)) return -10;
-    return 0;
-}
-
 static int gru4rec_train_step(const bsarec_gru4rec_config_t* cfg, const int64_t* ids, const int64_t* answers,
                               const int64_t* neg_answers, const bsarec_adam_t* adam_items, const bsarec_adam_t* adam_weights,
                               void* state, float* loss_out, void* workspace, long workspace_bytes,
                               const bsarec_gru4rec_head_t* head, void* stream) {
     RET(gru4rec_check(cfg));
-    RET(gru4rec_adam_check(adam_items, (long)cfg->item_size * cfg->gru.input_size));
-    RET(gru4rec_adam_check(adam_weights, gru_weights(cfg->gru).total));
-    // one t and one pair of bias corrections in `state` serve both arrays
-    if (adam_items->lr != adam_weights->lr || adam_items->beta1 != adam_weights->beta1 || adam_items->beta2 != adam_weights->beta2)
-        return -10;
-    float* dE = const_cast<float*>(adam_items->grads);
-    float* dW = const_cast<float*>(adam_weights->grads);
+    const StepAdam adams[] = {{adam_items, (long)cfg->item_size * cfg->gru.input_size},
+                              {adam_weights, gru_weights(cfg->gru).total}};
+    RET(pair_adams_check(adams));
     hipStream_t s = (hipStream_t)stream;
-    RET(gru4rec_loss_grad(cfg, adam_items->params, adam_weights->params, ids, answers, neg_answers, state, 1, loss_out, dE, dW,
-                          workspace, workspace_bytes, adam_items, head, s));
-    RET(adam_launch(*adam_items, state, s));
-    return adam_launch(*adam_weights, state, s);
+    RET(gru4rec_loss_grad(cfg, adam_items->params, adam_weights->params, ids, answers, neg_answers, state, 1, loss_out,
+                          adam_grads(adam_items), adam_grads(adam_weights), workspace, workspace_bytes, adam_items, head, s));
+    return pair_adams_launch(adams, state, s);
 }
 
 extern "C" int bsarec_gru4rec_train_step(const bsarec_gru4rec_config_t* cfg, const int64_t* ids, const int64_t* answers,
@@ -2949,14 +3004,6 @@ extern "C" long bsarec_caser_fc_workspace_bytes(int batch, int features, int wid
     return (long)batch * features * (long)sizeof(float);
 }
 
-static DropP caser_fc_drop(float p, const void* state, bool train) {
-    DropP d;
-    d.thresh = train ? drop_thresh(p) : 0;
-    d.scale = (train && p > 0.f) ? (float)(1.0 / (1.0 - (double)p)) : 1.0f;
-    d.rng = (const uint64_t*)state; d.site = 0;
-    return d;
-}
-
 // z, fc, the drop and the shape are set; the masked forward leaves zd in `zd`, and the backward reads it there (z otherwise)
 static CaserFcP caser_fc_params(int B, int F, int d, const float* z, const float* fc, const DropP& drop, float* zd) {
     CaserFcP P;
@@ -2988,7 +3035,7 @@ extern "C" int bsarec_caser_fc_fwd(int batch, int features, int width, const flo
         if (!aligned_to(p, 16)) return -10;
     if (!aligned_to(state, 8)) return -10;
     if (workspace_bytes < bsarec_caser_fc_workspace_bytes(batch, features, width)) return -10;
-    CaserFcP P = caser_fc_params(batch, features, width, z, fc, caser_fc_drop(dropout, state, train != 0), (float*)workspace);
+    CaserFcP P = caser_fc_params(batch, features, width, z, fc, site0_drop(dropout, state, train != 0), (float*)workspace);
     P.s_out = s;
     caser_fc_fwd_launch(P, (hipStream_t)stream);
     return (int)hipGetLastError();
@@ -3003,7 +3050,7 @@ extern "C" int bsarec_caser_fc_bwd(int batch, int features, int width, const flo
         if (!aligned_to(p, 16)) return -10;
     if (!aligned_to(state, 8)) return -10;
     if (workspace_bytes < bsarec_caser_fc_workspace_bytes(batch, features, width)) return -10;
-    CaserFcP P = caser_fc_params(batch, features, width, z, fc, caser_fc_drop(dropout, state, train != 0), (float*)workspace);
+    CaserFcP P = caser_fc_params(batch, features, width, z, fc, site0_drop(dropout, state, train != 0), (float*)workspace);
     P.s = s; P.ds = ds; P.dz = dz; P.dw = dfc;
     caser_fc_bwd_launch(P, (hipStream_t)stream);
     return (int)hipGetLastError();
@@ -3044,105 +3091,10 @@ extern "C" long bsarec_caser_step_workspace_bytes(const bsarec_caser_step_config
     return caser_step_ws(*cfg).total * (long)sizeof(float);
 }
 
-// tick_adam: null, or the Adam whose t the step's closing block advances (bsarec_caser_train_step)
-static int caser_run(const bsarec_caser_step_config_t& c, const float* E, const float* weights, const float* fc, const int64_t* ids,
-                     const int64_t* answers, const int64_t* neg_answers, void* state, int train, float* loss_out, float* dE,
-                     float* dweights, float* dfc, void* workspace, const bsarec_adam_t* tick_adam, hipStream_t s) {
-    const int B = c.conv.batch, d = c.conv.width, V = c.item_size;
-    const long T = (long)B * c.conv.seq_len;
-    const int F = (int)caser_weights(c.conv).F;
-    const CaserStepWs ws = caser_step_ws(c);
-    float* w = (float*)workspace;
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(w + ws.acc);
-    if (train) hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(1), 0, s, (uint64_t*)state, (long long*)nullptr, 0);
-    DropP none;                                         // the token rows carry no mask
-    none.thresh = 0; none.scale = 1.0f; none.rng = (const uint64_t*)state; none.site = 0;
-
-    Gru4RecEmbedP pe;
-    pe.E = E; pe.ids = ids; pe.x = w + ws.x; pe.T = T; pe.d = d; pe.V = V; pe.drop = none;
-    pe.acc = acc; pe.acc_n2 = (long)V * d / 2;
-    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_embed_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)),
-                                       dim3(ROW_THREADS), 0, s, pe));
-    RET(bsarec_caser_fwd(&c.conv, w + ws.x, weights, 1, w + ws.z, w + ws.conv, ws.conv_bytes, s));
-
-    CaserFcP pf = caser_fc_params(B, F, d, w + ws.z, fc, caser_fc_drop(c.dropout, state, train != 0), w + ws.zd);
-    pf.s_out = w + ws.s; pf.s = w + ws.s; pf.ds = w + ws.ds; pf.dz = w + ws.dz; pf.dw = dfc;
-    caser_fc_fwd_launch(pf, s);
-
-    Gru4RecBprP pb;
-    pb.s = w + ws.s; pb.E = E; pb.ans = answers; pb.neg = neg_answers; pb.B = B; pb.d = d; pb.V = V;
-    pb.ds = w + ws.ds; pb.c = w + ws.c; pb.loss_rows = w + ws.rows;
-    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_bpr_kernel<LPR>, dim3(cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS), 0, s, pb));
-
-    caser_fc_bwd_launch(pf, s);
-    RET(bsarec_caser_bwd(&c.conv, w + ws.x, weights, w + ws.dz, w + ws.conv, ws.conv_bytes, w + ws.dx, dweights, s));
-
-    Gru4RecGradP pg;                                   // T token rows, then the head's 2 B
-    pg.dx = w + ws.dx; pg.ids = ids; pg.ans = answers; pg.neg = neg_answers;
-    pg.T = T; pg.B = B; pg.C = 0; pg.d = d; pg.V = V; pg.drop = none; pg.dA = acc;
-    pg.head_rows = w + ws.s; pg.c = w + ws.c;
-    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_item_grad_kernel<LPR>, dim3(cdiv(T + 2L * B, SCATTER_FLOATS / (4 * LPR))),
-                                       dim3(ROW_THREADS), 0, s, pg));
-
-    LookupAcc la;
-    memset(&la, 0, sizeof(la));
-    la.acc = acc; la.dst = dE; la.n4 = (long)V * d / 4; la.dense_zero = 1;
-    la.nblocks = std::min(cdiv(la.n4, ROW_THREADS), 1024);
-    const TickP tk = tick_adam ? make_tick(state, 1, tick_adam->lr, tick_adam->beta1, tick_adam->beta2, w + ws.rows, B, loss_out,
-                                           nullptr, 0, 0)
-                               : make_tick(state, 0, 0.f, 0.f, 0.f, w + ws.rows, B, loss_out, nullptr, 0, 0);
-    hipLaunchKernelGGL(gru4rec_flush_kernel, dim3(la.nblocks + 1), dim3(ROW_THREADS), 0, s, la, tk);
-    return (int)hipGetLastError();
-}
-
-static int caser_loss_grad(const bsarec_caser_step_config_t* cfg, const float* item_emb, const float* weights, const float* fc,
-                           const int64_t* ids, const int64_t* answers, const int64_t* neg_answers, void* state, int train,
-                           float* loss_out, float* d_item_emb, float* dweights, float* dfc, void* workspace, long workspace_bytes,
-                           const bsarec_adam_t* tick_adam, hipStream_t s) {
-    RET(caser_step_check(cfg));
-    for (const void* p : {(const void*)item_emb, (const void*)weights, (const void*)fc, (const void*)d_item_emb,
-                          (const void*)dweights, (const void*)dfc, (const void*)workspace})
-        if (!aligned_to(p, 16)) return -10;
-    for (const void* p : {(const void*)ids, (const void*)answers, (const void*)neg_answers, (const void*)state})
-        if (!aligned_to(p, 8)) return -10;
-    if (!aligned_to(loss_out, 4)) return -10;
-    if (workspace_bytes < caser_step_ws(*cfg).total * (long)sizeof(float)) return -10;
-    return caser_run(*cfg, item_emb, weights, fc, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights, dfc,
-                     workspace, tick_adam, s);
-}
-
-extern "C" int bsarec_caser_loss_grad(const bsarec_caser_step_config_t* cfg, const float* item_emb, const float* weights,
-                                      const float* fc, const int64_t* ids, const int64_t* answers, const int64_t* neg_answers,
-                                      void* state, int train, float* loss_out, float* d_item_emb, float* dweights, float* dfc,
-                                      void* workspace, long workspace_bytes, void* stream) {
-    return caser_loss_grad(cfg, item_emb, weights, fc, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights, dfc,
-                           workspace, workspace_bytes, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int bsarec_caser_train_step(const bsarec_caser_step_config_t* cfg, const int64_t* ids, const int64_t* answers,
-                                       const int64_t* neg_answers, const bsarec_adam_t* adam_items,
-                                       const bsarec_adam_t* adam_weights, const bsarec_adam_t* adam_fc, void* state,
-                                       float* loss_out, void* workspace, long workspace_bytes, void* stream) {
-    RET(caser_step_check(cfg));
-    const CaserW wo = caser_weights(cfg->conv);
-    RET(gru4rec_adam_check(adam_items, (long)cfg->item_size * cfg->conv.width));
-    RET(gru4rec_adam_check(adam_weights, wo.total));
-    RET(gru4rec_adam_check(adam_fc, (wo.F + 1) * cfg->conv.width));
-    // one t and one pair of bias corrections in `state` serve the three arrays
-    for (const bsarec_adam_t* a : {adam_weights, adam_fc})
-        if (a->lr != adam_items->lr || a->beta1 != adam_items->beta1 || a->beta2 != adam_items->beta2) return -10;
-    hipStream_t s = (hipStream_t)stream;
-    RET(caser_loss_grad(cfg, adam_items->params, adam_weights->params, adam_fc->params, ids, answers, neg_answers, state, 1,
-                        loss_out, const_cast<float*>(adam_items->grads), const_cast<float*>(adam_weights->grads),
-                        const_cast<float*>(adam_fc->grads), workspace, workspace_bytes, adam_items, s));
-    RET(adam_launch(*adam_items, state, s));
-    RET(adam_launch(*adam_weights, state, s));
-    return adam_launch(*adam_fc, state, s);
-}
-
 // ---------------------------------------------------------------------------------------------
 // Personalised Caser step (caser_user.h): the step above with a user table and fc2 = Linear(2 d, d) behind fc1.  fc2 runs on
-// fc1's launches; the chain is linear on the caller's stream, no allocation, no host synchronisation
+// fc1's launches; the chain is linear on the caller's stream, no allocation, no host synchronisation.  Both steps run through
+// one driver, caser_run, with the user part absent or present
 // ---------------------------------------------------------------------------------------------
 static int caser_user_check(const bsarec_caser_user_step_config_t* c) {
     if (!c) return -10;
@@ -3178,101 +3130,100 @@ extern "C" long bsarec_caser_user_step_workspace_bytes(const bsarec_caser_user_s
     return caser_user_ws(*cfg).total * (long)sizeof(float);
 }
 
-// tick_adam: null, or the Adam whose t the step's closing block advances (bsarec_caser_user_train_step)
-static int caser_user_run(const bsarec_caser_user_step_config_t& cu, const float* E, const float* Pu, const float* weights,
-                          const float* fc, const float* fc2, const int64_t* ids, const int64_t* users, const int64_t* answers,
-                          const int64_t* neg_answers, void* state, int train, float* loss_out, float* dE, float* dP,
-                          float* dweights, float* dfc, float* dfc2, void* workspace, const bsarec_adam_t* tick_adam,
-                          hipStream_t s) {
-    const bsarec_caser_step_config_t& c = cu.step;
-    const int B = c.conv.batch, d = c.conv.width, V = c.item_size, U = cu.num_users;
-    const long T = (long)B * c.conv.seq_len;
-    const int F = (int)caser_weights(c.conv).F;
-    const CaserUserWs wu = caser_user_ws(cu);
-    const CaserStepWs& ws = wu.st;
+// what the personalised step has beyond the item-only one: its arrays, and in ws its regions of the workspace
+struct CaserUserPart { int U; const int64_t* users; const float* P; const float* fc2; float* dP; float* dfc2; CaserUserWs ws; };
+
+// tick_adam: null, or the Adam whose t the step's closing block advances (a *_train_step); u: null, or the user part
+static int caser_run(const bsarec_caser_step_config_t& c, const CaserUserPart* u, const float* E, const float* weights,
+                     const float* fc, const int64_t* ids, const int64_t* answers, const int64_t* neg_answers, void* state, int train,
+                     float* loss_out, float* dE, float* dweights, float* dfc, void* workspace, const bsarec_adam_t* tick_adam,
+                     hipStream_t s) {
+    const int B = c.conv.batch, d = c.conv.width, F = (int)caser_weights(c.conv).F;
+    const CaserStepWs ws = caser_step_ws(c);
     float* w = (float*)workspace;
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(w + ws.acc);
-    unsigned long long* uacc = reinterpret_cast<unsigned long long*>(w + wu.uacc);
-    if (train) hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(1), 0, s, (uint64_t*)state, (long long*)nullptr, 0);
-    DropP none;                                         // the token rows and fc2 carry no mask
-    none.thresh = 0; none.scale = 1.0f; none.rng = (const uint64_t*)state; none.site = 0;
+    const DropP none = site0_drop(0.f, state, false);  // the token rows and fc2 carry no mask
+    const PairStep p = {B, d, c.item_size, (long)B * c.conv.seq_len, E, ids, answers, neg_answers, state, train, none,
+                        w + ws.x, w + ws.dx, w + ws.c, w + ws.rows, reinterpret_cast<unsigned long long*>(w + ws.acc), dE, loss_out,
+                        tick_adam, s};
+    pair_begin_embed(p);
+    RET(bsarec_caser_fwd(&c.conv, p.x, weights, 1, w + ws.z, w + ws.conv, ws.conv_bytes, s));
 
-    Gru4RecEmbedP pe;
-    pe.E = E; pe.ids = ids; pe.x = w + ws.x; pe.T = T; pe.d = d; pe.V = V; pe.drop = none;
-    pe.acc = acc; pe.acc_n2 = (long)V * d / 2;
-    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_embed_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)),
-                                       dim3(ROW_THREADS), 0, s, pe));
-    RET(bsarec_caser_fwd(&c.conv, w + ws.x, weights, 1, w + ws.z, w + ws.conv, ws.conv_bytes, s));
-
-    CaserFcP pf = caser_fc_params(B, F, d, w + ws.z, fc, caser_fc_drop(c.dropout, state, train != 0), w + ws.zd);
-    pf.s_out = w + ws.s; pf.s = w + ws.s; pf.ds = w + ws.ds; pf.dz = w + ws.dz; pf.dw = dfc;      // s = z1, ds = dz1
+    CaserFcP pf = caser_fc_params(B, F, d, w + ws.z, fc, site0_drop(c.dropout, state, train != 0), w + ws.zd);
+    pf.s_out = w + ws.s; pf.s = w + ws.s; pf.ds = w + ws.ds; pf.dz = w + ws.dz; pf.dw = dfc;      // with u: s = z1, ds = dz1
     caser_fc_fwd_launch(pf, s);
 
+    float* sv = w + (u ? u->ws.s : ws.s);               // the state the head reads, and its gradient
+    float* dsv = w + (u ? u->ws.ds : ws.ds);
     CaserUserP pu;
-    memset(&pu, 0, sizeof(pu));
-    pu.z1 = w + ws.s; pu.P = Pu; pu.users = users; pu.x2 = w + wu.x2; pu.dx2 = w + wu.dx2; pu.dz1 = w + ws.ds;
-    pu.B = B; pu.d = d; pu.U = U; pu.acc = uacc; pu.acc_n2 = (long)U * d / 2;
-    DISPATCH_LPR(d, hipLaunchKernelGGL(caser_user_concat_kernel<LPR>, dim3(std::min(cdiv(B, ROW_THREADS / LPR), 4096)),
-                                       dim3(ROW_THREADS), 0, s, pu));
+    CaserFcP p2;
+    if (u) {                                            // x2 = [z1 | P[users]], the state = relu(fc2(x2))
+        memset(&pu, 0, sizeof(pu));
+        pu.z1 = w + ws.s; pu.P = u->P; pu.users = u->users; pu.x2 = w + u->ws.x2; pu.dx2 = w + u->ws.dx2; pu.dz1 = w + ws.ds;
+        pu.B = B; pu.d = d; pu.U = u->U; pu.acc_n2 = (long)u->U * d / 2;
+        pu.acc = reinterpret_cast<unsigned long long*>(w + u->ws.uacc);
+        DISPATCH_LPR(d, hipLaunchKernelGGL(caser_user_concat_kernel<LPR>, dim3(std::min(cdiv(B, ROW_THREADS / LPR), 4096)),
+                                           dim3(ROW_THREADS), 0, s, pu));
+        p2 = caser_fc_params(B, 2 * d, d, pu.x2, u->fc2, none, nullptr);
+        p2.s_out = sv; p2.s = sv; p2.ds = dsv; p2.dz = w + u->ws.dx2; p2.dw = u->dfc2;
+        caser_fc_fwd_launch(p2, s);
+    }
+    pair_bpr(p, sv, dsv);
 
-    CaserFcP p2 = caser_fc_params(B, 2 * d, d, w + wu.x2, fc2, none, nullptr);
-    p2.s_out = w + wu.s; p2.s = w + wu.s; p2.ds = w + wu.ds; p2.dz = w + wu.dx2; p2.dw = dfc2;
-    caser_fc_fwd_launch(p2, s);
-
-    Gru4RecBprP pb;
-    pb.s = w + wu.s; pb.E = E; pb.ans = answers; pb.neg = neg_answers; pb.B = B; pb.d = d; pb.V = V;
-    pb.ds = w + wu.ds; pb.c = w + ws.c; pb.loss_rows = w + ws.rows;
-    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_bpr_kernel<LPR>, dim3(cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS), 0, s, pb));
-
-    caser_fc_bwd_launch(p2, s);
-    DISPATCH_LPR(d, {
-        pu.scatter_blocks = cdiv(B, SCATTER_FLOATS / (4 * LPR));
-        hipLaunchKernelGGL(caser_user_grad_kernel<LPR>, dim3(pu.scatter_blocks + cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS),
-                           0, s, pu);
-    });
+    if (u) {                                            // fc2 backwards; dx2 -> the user rows and dz1
+        caser_fc_bwd_launch(p2, s);
+        DISPATCH_LPR(d, {
+            pu.scatter_blocks = cdiv(B, SCATTER_FLOATS / (4 * LPR));
+            hipLaunchKernelGGL(caser_user_grad_kernel<LPR>, dim3(pu.scatter_blocks + cdiv(B, ROW_THREADS / LPR)), dim3(ROW_THREADS),
+                               0, s, pu);
+        });
+    }
     caser_fc_bwd_launch(pf, s);
-    RET(bsarec_caser_bwd(&c.conv, w + ws.x, weights, w + ws.dz, w + ws.conv, ws.conv_bytes, w + ws.dx, dweights, s));
+    RET(bsarec_caser_bwd(&c.conv, p.x, weights, w + ws.dz, w + ws.conv, ws.conv_bytes, p.dx, dweights, s));
+    pair_item_grad(p, sv);
 
-    Gru4RecGradP pg;                                   // T token rows, then the head's 2 B
-    pg.dx = w + ws.dx; pg.ids = ids; pg.ans = answers; pg.neg = neg_answers;
-    pg.T = T; pg.B = B; pg.C = 0; pg.d = d; pg.V = V; pg.drop = none; pg.dA = acc;
-    pg.head_rows = w + wu.s; pg.c = w + ws.c;
-    DISPATCH_LPR(d, hipLaunchKernelGGL(gru4rec_item_grad_kernel<LPR>, dim3(cdiv(T + 2L * B, SCATTER_FLOATS / (4 * LPR))),
-                                       dim3(ROW_THREADS), 0, s, pg));
-
-    LookupAcc lu;
-    memset(&lu, 0, sizeof(lu));
-    lu.acc = uacc; lu.dst = dP; lu.n4 = (long)U * d / 4; lu.dense_zero = 1;
-    lu.nblocks = std::min(cdiv(lu.n4, ROW_THREADS), 1024);
-    hipLaunchKernelGGL(caser_user_flush_kernel, dim3(lu.nblocks), dim3(ROW_THREADS), 0, s, lu);
-
-    LookupAcc la;
-    memset(&la, 0, sizeof(la));
-    la.acc = acc; la.dst = dE; la.n4 = (long)V * d / 4; la.dense_zero = 1;
-    la.nblocks = std::min(cdiv(la.n4, ROW_THREADS), 1024);
-    const TickP tk = tick_adam ? make_tick(state, 1, tick_adam->lr, tick_adam->beta1, tick_adam->beta2, w + ws.rows, B, loss_out,
-                                           nullptr, 0, 0)
-                               : make_tick(state, 0, 0.f, 0.f, 0.f, w + ws.rows, B, loss_out, nullptr, 0, 0);
-    hipLaunchKernelGGL(gru4rec_flush_kernel, dim3(la.nblocks + 1), dim3(ROW_THREADS), 0, s, la, tk);
-    return (int)hipGetLastError();
+    if (u) {                                            // a grid of exactly nblocks: no closing block, the tick is not read
+        const LookupAcc lu = pair_flush_acc(pu.acc, u->dP, (long)u->U * d);
+        hipLaunchKernelGGL(pair_flush_kernel, dim3(lu.nblocks), dim3(ROW_THREADS), 0, s, lu,
+                           make_tick(nullptr, 0, 0.f, 0.f, 0.f, nullptr, 0, nullptr, nullptr, 0, 0));
+    }
+    return pair_flush_tick(p);
 }
 
-static int caser_user_loss_grad(const bsarec_caser_user_step_config_t* cfg, const float* item_emb, const float* user_emb,
-                                const float* weights, const float* fc, const float* fc2, const int64_t* ids,
-                                const int64_t* users, const int64_t* answers, const int64_t* neg_answers, void* state, int train,
-                                float* loss_out, float* d_item_emb, float* d_user_emb, float* dweights, float* dfc, float* dfc2,
-                                void* workspace, long workspace_bytes, const bsarec_adam_t* tick_adam, hipStream_t s) {
-    RET(caser_user_check(cfg));
-    for (const void* p : {(const void*)item_emb, (const void*)user_emb, (const void*)weights, (const void*)fc, (const void*)fc2,
-                          (const void*)d_item_emb, (const void*)d_user_emb, (const void*)dweights, (const void*)dfc,
-                          (const void*)dfc2, (const void*)workspace})
-        if (!aligned_to(p, 16)) return -10;
-    for (const void* p : {(const void*)ids, (const void*)users, (const void*)answers, (const void*)neg_answers, (const void*)state})
-        if (!aligned_to(p, 8)) return -10;
-    if (!aligned_to(loss_out, 4)) return -10;
-    if (workspace_bytes < caser_user_ws(*cfg).total * (long)sizeof(float)) return -10;
-    return caser_user_run(*cfg, item_emb, user_emb, weights, fc, fc2, ids, users, answers, neg_answers, state, train, loss_out,
-                          d_item_emb, d_user_emb, dweights, dfc, dfc2, workspace, tick_adam, s);
+static int caser_loss_grad(const bsarec_caser_step_config_t* cfg, const CaserUserPart* u, const float* item_emb,
+                           const float* weights, const float* fc, const int64_t* ids, const int64_t* answers,
+                           const int64_t* neg_answers, void* state, int train, float* loss_out, float* d_item_emb, float* dweights,
+                           float* dfc, void* workspace, long workspace_bytes, const bsarec_adam_t* tick_adam, hipStream_t s) {
+    RET(caser_step_check(cfg));
+    RET(pair_ptrs_check({item_emb, weights, fc, d_item_emb, dweights, dfc, workspace}, {ids, answers, neg_answers, state},
+                        loss_out));
+    if (u) RET(pair_ptrs_check({u->P, u->fc2, u->dP, u->dfc2}, {u->users}, loss_out));
+    if (workspace_bytes < (u ? u->ws.total : caser_step_ws(*cfg).total) * (long)sizeof(float)) return -10;
+    return caser_run(*cfg, u, item_emb, weights, fc, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights, dfc,
+                     workspace, tick_adam, s);
+}
+
+extern "C" int bsarec_caser_loss_grad(const bsarec_caser_step_config_t* cfg, const float* item_emb, const float* weights,
+                                      const float* fc, const int64_t* ids, const int64_t* answers, const int64_t* neg_answers,
+                                      void* state, int train, float* loss_out, float* d_item_emb, float* dweights, float* dfc,
+                                      void* workspace, long workspace_bytes, void* stream) {
+    return caser_loss_grad(cfg, nullptr, item_emb, weights, fc, ids, answers, neg_answers, state, train, loss_out, d_item_emb,
+                           dweights, dfc, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int bsarec_caser_train_step(const bsarec_caser_step_config_t* cfg, const int64_t* ids, const int64_t* answers,
+                                       const int64_t* neg_answers, const bsarec_adam_t* adam_items,
+                                       const bsarec_adam_t* adam_weights, const bsarec_adam_t* adam_fc, void* state,
+                                       float* loss_out, void* workspace, long workspace_bytes, void* stream) {
+    RET(caser_step_check(cfg));
+    const CaserW wo = caser_weights(cfg->conv);
+    const StepAdam adams[] = {{adam_items, (long)cfg->item_size * cfg->conv.width}, {adam_weights, wo.total},
+                              {adam_fc, (wo.F + 1) * cfg->conv.width}};
+    RET(pair_adams_check(adams));
+    hipStream_t s = (hipStream_t)stream;
+    RET(caser_loss_grad(cfg, nullptr, adam_items->params, adam_weights->params, adam_fc->params, ids, answers, neg_answers, state,
+                        1, loss_out, adam_grads(adam_items), adam_grads(adam_weights), adam_grads(adam_fc), workspace,
+                        workspace_bytes, adam_items, s));
+    return pair_adams_launch(adams, state, s);
 }
 
 extern "C" int bsarec_caser_user_loss_grad(const bsarec_caser_user_step_config_t* cfg, const float* item_emb,
@@ -3281,9 +3232,10 @@ extern "C" int bsarec_caser_user_loss_grad(const bsarec_caser_user_step_config_t
                                            const int64_t* neg_answers, void* state, int train, float* loss_out,
                                            float* d_item_emb, float* d_user_emb, float* dweights, float* dfc, float* dfc2,
                                            void* workspace, long workspace_bytes, void* stream) {
-    return caser_user_loss_grad(cfg, item_emb, user_emb, weights, fc, fc2, ids, users, answers, neg_answers, state, train,
-                                loss_out, d_item_emb, d_user_emb, dweights, dfc, dfc2, workspace, workspace_bytes, nullptr,
-                                (hipStream_t)stream);
+    RET(caser_user_check(cfg));
+    const CaserUserPart u = {cfg->num_users, users, user_emb, fc2, d_user_emb, dfc2, caser_user_ws(*cfg)};
+    return caser_loss_grad(&cfg->step, &u, item_emb, weights, fc, ids, answers, neg_answers, state, train, loss_out, d_item_emb,
+                           dweights, dfc, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int bsarec_caser_user_train_step(const bsarec_caser_user_step_config_t* cfg, const int64_t* ids,
@@ -3295,25 +3247,17 @@ extern "C" int bsarec_caser_user_train_step(const bsarec_caser_user_step_config_
     RET(caser_user_check(cfg));
     const bsarec_caser_config_t& cv = cfg->step.conv;
     const CaserW wo = caser_weights(cv);
-    RET(gru4rec_adam_check(adam_items, (long)cfg->step.item_size * cv.width));
-    RET(gru4rec_adam_check(adam_users, (long)cfg->num_users * cv.width));
-    RET(gru4rec_adam_check(adam_weights, wo.total));
-    RET(gru4rec_adam_check(adam_fc, (wo.F + 1) * cv.width));
-    RET(gru4rec_adam_check(adam_fc2, (2L * cv.width + 1) * cv.width));
-    // one t and one pair of bias corrections in `state` serve the five arrays
-    for (const bsarec_adam_t* a : {adam_users, adam_weights, adam_fc, adam_fc2})
-        if (a->lr != adam_items->lr || a->beta1 != adam_items->beta1 || a->beta2 != adam_items->beta2) return -10;
+    const StepAdam adams[] = {{adam_items, (long)cfg->step.item_size * cv.width}, {adam_users, (long)cfg->num_users * cv.width},
+                              {adam_weights, wo.total}, {adam_fc, (wo.F + 1) * cv.width},
+                              {adam_fc2, (2L * cv.width + 1) * cv.width}};
+    RET(pair_adams_check(adams));
     hipStream_t s = (hipStream_t)stream;
-    RET(caser_user_loss_grad(cfg, adam_items->params, adam_users->params, adam_weights->params, adam_fc->params,
-                             adam_fc2->params, ids, users, answers, neg_answers, state, 1, loss_out,
-                             const_cast<float*>(adam_items->grads), const_cast<float*>(adam_users->grads),
-                             const_cast<float*>(adam_weights->grads), const_cast<float*>(adam_fc->grads),
-                             const_cast<float*>(adam_fc2->grads), workspace, workspace_bytes, adam_items, s));
-    RET(adam_launch(*adam_items, state, s));
-    RET(adam_launch(*adam_users, state, s));
-    RET(adam_launch(*adam_weights, state, s));
-    RET(adam_launch(*adam_fc, state, s));
-    return adam_launch(*adam_fc2, state, s);
+    const CaserUserPart u = {cfg->num_users, users, adam_users->params, adam_fc2->params, adam_grads(adam_users),
+                             adam_grads(adam_fc2), caser_user_ws(*cfg)};
+    RET(caser_loss_grad(&cfg->step, &u, adam_items->params, adam_weights->params, adam_fc->params, ids, answers, neg_answers, state,
+                        1, loss_out, adam_grads(adam_items), adam_grads(adam_weights), adam_grads(adam_fc), workspace,
+                        workspace_bytes, adam_items, s));
+    return pair_adams_launch(adams, state, s);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -5,18 +5,19 @@
 // what stands around them.  All fp32; rows are float4 lanes as in kernels.h (ROW_THREADS lanes, LPR lanes per row, d <= 256,
 // d % 4 == 0, so a float4 never straddles the halves of x2).
 //   caser_user_concat_kernel  x2[b, 0:d] = z1[b], x2[b, d:2d] = P[users[b]] (zeros for an id outside [0, U)).  Its lanes also
-//                             clear the fixed-point accumulator of the user-table gradient, as gru4rec_embed_kernel clears the
-//                             item table's: a step does not depend on what the workspace holds on entry.
+//                             clear the fixed-point accumulator of the user-table gradient, as pair_embed_kernel clears the
+//                             item table's (acc_clear): a step does not depend on what the workspace holds on entry.
 //   caser_user_grad_kernel    with dx2 [B, 2 d] of fc2's dz launch: blocks [0, scatter_blocks) run fix_scatter_block over the B
 //                             rows -- row b adds dx2[b, d:2d] to row users[b] of the [U][d] accumulator, duplicates folded in
 //                             LDS -- and the blocks behind them copy dx2[b, 0:d] into the contiguous dz1 [B, d] that fc1's
 //                             backward reads as its ds.
-//   caser_user_flush_kernel   accumulator -> EVERY float of d_user_emb (lookup_flush with dense_zero: zero where no row of the
-//                             batch names the user).  No closing block: the item flush behind it closes the step.
+// The accumulator goes into EVERY float of d_user_emb through pair_flush_kernel on a grid of la.nblocks (lookup_flush with
+// dense_zero: zero where no row of the batch names the user), so without the closing block: the item flush behind it closes the
+// step.
 // The scatter is the one of kernels.h: 64-bit fixed point in 2^-40 units, exact while |sum| < 2^22, integer adds, so d_user_emb
-// has the same bits on every run.  A user id outside [0, U) is never dereferenced and adds nothing (gru4rec_row_id).
+// has the same bits on every run.  A user id outside [0, U) is never dereferenced and adds nothing (pair_row_id).
 #pragma once
-#include "gru4rec_step.h"
+#include "pair_step.h"
 
 struct CaserUserP {
     const float* z1;            // [B][d]
@@ -46,9 +47,7 @@ __global__ void __launch_bounds__(ROW_THREADS) caser_user_concat_kernel(const Ca
             st4(P.x2 + e + P.d, v);
         }
     }
-    ulonglong2* a = reinterpret_cast<ulonglong2*>(P.acc);
-    for (long i = (long)blockIdx.x * ROW_THREADS + threadIdx.x; i < P.acc_n2; i += (long)gridDim.x * ROW_THREADS)
-        a[i] = make_ulonglong2(0ull, 0ull);
+    acc_clear(P.acc, P.acc_n2);
 }
 
 // grid scatter_blocks + ceil(B / RPP), scatter_blocks = ceil(B / CHUNK), CHUNK = SCATTER_FLOATS / (4 LPR) rows per block
@@ -58,7 +57,7 @@ __global__ void __launch_bounds__(ROW_THREADS) caser_user_grad_kernel(const Case
     const int d = P.d;
     if ((int)blockIdx.x < P.scatter_blocks) {             // block-uniform
         fix_scatter_block<LPR>(P.B, d, P.acc, blockIdx.x, lds,
-            [&](long r) { return gru4rec_row_id(P.users[r], P.U); },
+            [&](long r) { return pair_row_id(P.users[r], P.U); },
             [&](long r, int lc) { return ld4(P.dx2 + r * 2 * d + d + lc); });
         return;
     }
@@ -66,9 +65,4 @@ __global__ void __launch_bounds__(ROW_THREADS) caser_user_grad_kernel(const Case
     const int lr = threadIdx.x / LPR, lc = (threadIdx.x % LPR) << 2;
     const long b = (long)(blockIdx.x - P.scatter_blocks) * RPP + lr;
     if (b < P.B && lc < d) st4(P.dz1 + b * d + lc, ld4(P.dx2 + b * 2 * d + lc));
-}
-
-// grid la.nblocks
-__global__ void __launch_bounds__(ROW_THREADS) caser_user_flush_kernel(const LookupAcc la) {
-    lookup_flush(la, (long)blockIdx.x * ROW_THREADS + threadIdx.x, (long)la.nblocks * ROW_THREADS);
 }

@@ -9,12 +9,12 @@
 //                         into nslab slabs (a function of the shape alone)
 //   g4c_slab_sum_kernel   nslab > 1: the slabs added in slab order
 //   g4c_item_grad_kernel  fix_scatter_block (kernels.h) over T + C rows: row r < T adds dx[r, :] * m to row ids[r] (the token rows
-//                         of gru4rec_item_grad_kernel, gru4rec_token_row), row T + j adds dEc[j, :] to row c_j
+//                         of pair_item_grad_kernel, pair_token_row), row T + j adds dEc[j, :] to row c_j
 // No floating-point atomics: every float sum has one order; the item-table rows are summed in 64-bit fixed point as
-// gru4rec_step.h describes.  An id outside [0, V) is never dereferenced: such a candidate is no column of any row (G = 0), and a
+// pair_step.h describes.  An id outside [0, V) is never dereferenced: such a candidate is no column of any row (G = 0), and a
 // row whose answer is outside has loss 0 and gradient 0.  The restatement in numpy is tests/gru4rec_cand_ref.py.
 #pragma once
-#include "gru4rec_step.h"
+#include "pair_step.h"
 #include "sampled_softmax.h"
 
 #define G4C_MAX 8192                      // BSAREC_GRU4REC_CAND_MAX: the most candidate columns
@@ -35,10 +35,10 @@ struct Gru4RecCandP {
     int nslab, chunkB, chunkC, tilesA;
 };
 
-// candidate j's item, -1 outside [0, V); P: Gru4RecCandP, or the Gru4RecGradP of g4c_item_grad_kernel
+// candidate j's item, -1 outside [0, V); P: Gru4RecCandP, or the PairGradP of g4c_item_grad_kernel
 template <class Params>
 __device__ __forceinline__ int g4c_cand(const Params& P, int j) {
-    return gru4rec_row_id(j < P.B ? P.ans[j] : P.neg[j - P.B], P.V);
+    return pair_row_id(j < P.B ? P.ans[j] : P.neg[j - P.B], P.V);
 }
 
 // grid (ceil(C / 64), ceil(B / 64)): rows = batch rows, columns = candidates
@@ -84,7 +84,7 @@ __device__ __forceinline__ float g4c_block_max(float v, float* red) {
 }
 
 // One workgroup per row b.  M = the columns j whose item is inside [0, V) and is not answers[b], m = |M|, x_j = r_bj, x_b the
-// positive's score, sig' = sig (1 - sig), both from gru4rec_sigmoid; inv = 1 / B:
+// positive's score, sig' = sig (1 - sig), both from pair_sigmoid; inv = 1 / B:
 //   ce       loss = logsumexp_{{b} + M} x - x_b;  G_j = (softmax_j - [j == b]) inv
 //   top1     loss = (1 / m) sum_M [sig(x_j - x_b) + sig(x_j^2)];  G_j = (sig'(x_j - x_b) + 2 x_j sig'(x_j^2)) inv / m,
 //            G_b = -sum_M sig'(x_j - x_b) inv / m.  x_j^2 = inf gives sig = 1 and sig' = 0 exactly.
@@ -134,8 +134,8 @@ __global__ void __launch_bounds__(ROW_THREADS) g4c_rows_kernel(const Gru4RecCand
             float g = 0.f;
             if (in_m[j]) {
                 float sg, om, sq, oq;
-                gru4rec_sigmoid(x[j] - xb, sg, om);
-                gru4rec_sigmoid(x[j] * x[j], sq, oq);
+                pair_sigmoid(x[j] - xb, sg, om);
+                pair_sigmoid(x[j] * x[j], sq, oq);
                 ls += sg + sq;
                 us += sg * om;
                 g = (sg * om + 2.0f * x[j] * (sq * oq)) * w;
@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(ROW_THREADS) g4c_rows_kernel(const Gru4RecCand
         if (!in_m[j]) continue;
         const float e = expf(x[j] - mx);
         float sg, om;
-        gru4rec_sigmoid(xb - x[j], sg, om);
+        pair_sigmoid(xb - x[j], sg, om);
         z += e;
         a += e * sg;
         sp += e * (sg * om);
@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(ROW_THREADS) g4c_rows_kernel(const Gru4RecCand
         if (in_m[j]) {
             const float p = expf(x[j] - mx) * rz;
             float sg, om;
-            gru4rec_sigmoid(xb - x[j], sg, om);
+            pair_sigmoid(xb - x[j], sg, om);
             if (p > 0.f) g = p * ((sg * om - (sg - a)) * ra + lam * (x[j] * x[j] - q + 2.0f * x[j])) * inv;
         }
         if (j != b) row[j] = g;
@@ -247,14 +247,14 @@ __global__ void __launch_bounds__(ROW_THREADS) g4c_slab_sum_kernel(const float* 
     st4((e ? dEc : ds) + at, v);
 }
 
-// gru4rec_item_grad_kernel with the head's rows read from dEc (Gru4RecGradP.head_rows): grid ceil((T + C) / CHUNK), CHUNK =
+// pair_item_grad_kernel with the head's rows read from dEc (PairGradP.head_rows): grid ceil((T + C) / CHUNK), CHUNK =
 // SCATTER_FLOATS / (4 LPR)
 template <int LPR>
-__global__ void __launch_bounds__(ROW_THREADS) g4c_item_grad_kernel(const Gru4RecGradP P) {
+__global__ void __launch_bounds__(ROW_THREADS) g4c_item_grad_kernel(const PairGradP P) {
     __shared__ __attribute__((aligned(16))) float lds[fix_scatter_lds_bytes(LPR) / 4];
     const long T = P.T;
     const DropSeed sd = drop_seed(P.drop);
     fix_scatter_block<LPR>(T + P.C, P.d, P.dA, blockIdx.x, lds,
-        [&](long r) { return r < T ? gru4rec_row_id(P.ids[r], P.V) : g4c_cand(P, (int)(r - T)); },
-        [&](long r, int lc) { return r < T ? gru4rec_token_row(P, sd, r, lc) : ld4(P.head_rows + (r - T) * P.d + lc); });
+        [&](long r) { return r < T ? pair_row_id(P.ids[r], P.V) : g4c_cand(P, (int)(r - T)); },
+        [&](long r, int lc) { return r < T ? pair_token_row(P, sd, r, lc) : ld4(P.head_rows + (r - T) * P.d + lc); });
 }

@@ -502,7 +502,7 @@ dlast_kernel(const float* __restrict__ slabs, int nsplit, long slab_stride, int 
 // the same gradient bit for bit on every run.  The final reduction kernel of the backward adds the accumulator once onto
 // the dense logits-path dE and zeroes it (LookupAcc).  The scatter has ONE body, fix_scatter_block: BSARec's token rows
 // (embed_scatter_block, in embed_bwd_kernel and at d = 64 inside dw_direct_kernel) and the T + 2 B / T + C rows of the GRU4Rec
-// steps (gru4rec_step.h, gru4rec_cand.h) only tell it which id and which addend belong to a row.
+// steps (pair_step.h, gru4rec_cand.h) only tell it which id and which addend belong to a row.
 // =============================================================================================
 #define LOOKUP_FIX_ONE 0x1p40f         // fixed-point unit: |sum| < 2^23 representable, resolution 2^-40
 __device__ __forceinline__ unsigned long long lookup_fix(float x) {
@@ -535,6 +535,12 @@ __device__ __forceinline__ void lookup_flush(const LookupAcc& la, long first, lo
         if (lookup_take(la.acc, i, add)) st4(la.dst + 4 * i, la.dense_zero ? add : ld4(la.dst + 4 * i) + add);
         else if (la.dense_zero) st4(la.dst + 4 * i, f32x4{0, 0, 0, 0});
     }
+}
+// the accumulator as n2 pairs of 64-bit words, zeroed by the whole grid: the tail of the launch that opens a step's use of it
+__device__ __forceinline__ void acc_clear(unsigned long long* acc, long n2) {
+    ulonglong2* a = reinterpret_cast<ulonglong2*>(acc);
+    for (long i = (long)blockIdx.x * ROW_THREADS + threadIdx.x; i < n2; i += (long)gridDim.x * ROW_THREADS)
+        a[i] = make_ulonglong2(0ull, 0ull);
 }
 #ifndef SCATTER_FLOATS
 #define SCATTER_FLOATS 4096           // LDS row accumulators per block: chunk = 4096 / (4*LPR) tokens (64 at d = 64:

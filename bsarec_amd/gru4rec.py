@@ -6,7 +6,7 @@ The contract of this model is the math of its docstrings, checked against ``torc
 the dropped-out embeddings and the output runs in libbsarec_hip.so in both directions (bsarec_gru_fwd / bsarec_gru_bwd,
 csrc/gru.h); on the default path the embedding lookup, the dropout mask and the B-row BPR head are torch ops.  With
 ``gru_step = "fused"`` the whole training step -- those parts, the item-table gradient and Adam included -- is one C call
-(bsarec_gru4rec_train_step, csrc/gru4rec_step.h).  ``gru_loss`` / ``gru_negatives`` replace the pairwise BPR loss by
+(bsarec_gru4rec_train_step, csrc/pair_step.h).  ``gru_loss`` / ``gru_negatives`` replace the pairwise BPR loss by
 cross-entropy, TOP1 or BPR-max over mini-batch negatives (csrc/gru4rec_cand.h inside the fused step, ``cand_head_loss`` in torch
 ops on the default path).  There is no CPU path.
 """
@@ -18,6 +18,7 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
+from . import _fused_step as FS
 from . import _lib as L
 
 GRU_HIDDEN = (32, 64, 96, 128)
@@ -374,26 +375,18 @@ class GRU4RecModel(nn.Module):
         diff = (s * pos).sum(-1) - (s * neg).sum(-1)
         return -torch.log(torch.sigmoid(diff) + 1e-10).mean()
 
-    # ---- the fused step (gru_step = "fused"; bsarec_gru4rec_loss_grad / bsarec_gru4rec_train_step) -------------------------
+    # ---- the fused step (gru_step = "fused"; bsarec_gru4rec_loss_grad / bsarec_gru4rec_train_step; host side: _fused_step.py) ----
     def _step_buffers(self):
         """What the fused step owns beside the parameters: the device step state (seed, step counter, Adam t), both gradient
-        arrays, the Adam moments of the item table and of the GRU flat array, and per batch shape a workspace, static id
-        buffers and a captured graph.  Built on first use; dropped by ``.to()`` / ``reflatten()`` (a new parameter storage)."""
+        arrays, the Adam moments of the item table ("E") and of the GRU flat array ("W"), and per batch shape a workspace, static
+        id buffers and a captured graph.  Built on first use; dropped by ``.to()`` / ``reflatten()`` (a new parameter storage)."""
         self._require_gpu()
         self.gru_layers.reflatten()
         E, flat = self.item_embeddings.weight.data, self.gru_layers._flat
         if flat.device != E.device or not E.is_contiguous() or E.dtype != torch.float32:
             raise RuntimeError("gru4rec: the item table and the GRU weights must be contiguous fp32 on one device")
-        key = (E.data_ptr(), flat.data_ptr(), E.device)
-        f = self._fused
-        if f is None or f["key"] != key:
-            state = torch.zeros(8, dtype=torch.int64, device=E.device)
-            state[0] = self._stream_seed()
-            f = dict(key=key, state=state, E=E, flat=flat, dE=torch.empty_like(E), dW=torch.empty_like(flat),
-                     mE=torch.zeros_like(E), vE=torch.zeros_like(E), mW=torch.zeros_like(flat), vW=torch.zeros_like(flat),
-                     adam=None, slots={})
-            self._fused = f
-        return f
+        self._fused = FS.buffers(self._fused, [("E", E), ("W", flat)], self._stream_seed())
+        return self._fused
 
     @property
     def step_state(self) -> torch.Tensor:
@@ -415,12 +408,7 @@ class GRU4RecModel(nn.Module):
                                  "(1 <= B <= 65536, 1 <= L <= 256, 0 <= p < 1" +
                                  ("" if self._head is None else
                                   f", at most {L.GRU4REC_CAND_MAX} candidates: {self._head.candidates} B") + ")")
-            dev = f["E"].device
-            s = dict(cfg=cfg, nbytes=nbytes, ws=torch.empty(nbytes, dtype=torch.uint8, device=dev),
-                     ids=torch.zeros((B, Lq), dtype=torch.int64, device=dev), ans=torch.zeros(B, dtype=torch.int64, device=dev),
-                     neg=torch.zeros(B, dtype=torch.int64, device=dev), loss=torch.zeros((), dtype=torch.float32, device=dev),
-                     graph=None)
-            f["slots"][(B, Lq)] = s
+            s = FS.slot(f, (B, Lq), cfg, nbytes, (B, Lq))
         return s
 
     def _fill(self, s, input_ids, answers, neg_answers):
@@ -431,12 +419,12 @@ class GRU4RecModel(nn.Module):
         s["ids"].copy_(input_ids)
         s["ans"].copy_(answers.reshape(-1))
         s["neg"].copy_(neg_answers.reshape(-1))
+        return s
 
     def _loss_grad(self, f, s, train: bool):
-        stream = torch.cuda.current_stream(f["E"].device).cuda_stream
-        call = (s["cfg"], f["E"].data_ptr(), f["flat"].data_ptr(), s["ids"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(),
+        call = (s["cfg"], f["E"].data_ptr(), f["W"].data_ptr(), s["ids"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(),
                 f["state"].data_ptr(), int(train), s["loss"].data_ptr(), f["dE"].data_ptr(), f["dW"].data_ptr(), s["ws"].data_ptr(),
-                s["nbytes"], stream)
+                s["nbytes"], FS.stream(f))
         if self._head is None:
             L.check(L.load().bsarec_gru4rec_loss_grad(*call), "bsarec_gru4rec_loss_grad")
         else:
@@ -447,8 +435,7 @@ class GRU4RecModel(nn.Module):
         ``train``: draw the next dropout mask of the device stream (the step counter advances); else no dropout."""
         self._require_gpu(input_ids)
         f = self._step_buffers()
-        s = self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1]))
-        self._fill(s, input_ids, answers, neg_answers)
+        s = self._fill(self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1])), input_ids, answers, neg_answers)
         self._loss_grad(f, s, train)
         grads = OrderedDict([("item_embeddings.weight", f["dE"].clone())])
         names = {"out_weight": "dense.weight", "out_bias": "dense.bias"}
@@ -456,21 +443,10 @@ class GRU4RecModel(nn.Module):
             grads[names.get(name, "gru_layers." + name)] = f["dW"][o:o + n].view(shp).clone()
         return s["loss"].clone(), grads
 
-    def _adam_structs(self, f):
-        if f["adam"] is None:
-            a = self.args
-            hyper = (float(getattr(a, "lr", 1e-3)), float(getattr(a, "adam_beta1", 0.9)), float(getattr(a, "adam_beta2", 0.999)),
-                     1e-8, float(getattr(a, "weight_decay", 0.0)), 1.0, None, 0)
-            f["adam"] = (L.Adam(f["E"].data_ptr(), f["dE"].data_ptr(), f["mE"].data_ptr(), f["vE"].data_ptr(), f["E"].numel(), *hyper),
-                         L.Adam(f["flat"].data_ptr(), f["dW"].data_ptr(), f["mW"].data_ptr(), f["vW"].data_ptr(), f["flat"].numel(),
-                                *hyper))
-        return f["adam"]
-
     def _train_step(self, f, s):
-        items, weights = self._adam_structs(f)
-        stream = torch.cuda.current_stream(f["E"].device).cuda_stream
+        items, weights = FS.adam_structs(f, self.args)
         call = (s["cfg"], s["ids"].data_ptr(), s["ans"].data_ptr(), s["neg"].data_ptr(), items, weights, f["state"].data_ptr(),
-                s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], stream)
+                s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], FS.stream(f))
         if self._head is None:
             L.check(L.load().bsarec_gru4rec_train_step(*call), "bsarec_gru4rec_train_step")
         else:
@@ -487,17 +463,5 @@ class GRU4RecModel(nn.Module):
             raise RuntimeError("GRU4Rec steps through calculate_loss / backward / torch.optim.Adam (Trainer does)")
         self._require_gpu(input_ids)
         f = self._step_buffers()
-        s = self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1]))
-        self._fill(s, input_ids, answers, neg_answers)
-        if not getattr(self.args, "gru_step_graph", True):
-            self._train_step(f, s)
-            return s["loss"]
-        if s["graph"] is None:
-            self._adam_structs(f)
-            self._loss_grad(f, s, False)                  # every kernel of the chain has run once before the capture; no
-            graph = torch.cuda.CUDAGraph()                # counter moves and nothing is updated (train = 0)
-            with torch.cuda.graph(graph):
-                self._train_step(f, s)
-            s["graph"] = graph
-        s["graph"].replay()
-        return s["loss"]
+        s = self._fill(self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1])), input_ids, answers, neg_answers)
+        return FS.train_step(f, s, self.args, getattr(self.args, "gru_step_graph", True), self._loss_grad, self._train_step)

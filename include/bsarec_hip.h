@@ -665,7 +665,7 @@ int bsarec_gru_fwd(const bsarec_gru_config_t *cfg, const float *x, const float *
 int bsarec_gru_bwd(const bsarec_gru_config_t *cfg, const float *x, const float *weights, int last_only, const float *dout,
                    void *workspace, long workspace_bytes, float *dx, float *dweights, void *stream);
 
-/* One GRU4Rec training step (csrc/gru4rec_step.h): with E = item_emb [V, d], x = Dropout_p(E[ids]) [B, L, d], s = the GRU stack's
+/* One GRU4Rec training step (csrc/pair_step.h): with E = item_emb [V, d], x = Dropout_p(E[ids]) [B, L, d], s = the GRU stack's
  * output at position L - 1 (bsarec_gru_fwd, last_only) and
  *   diff_b = s_b . E[answers_b] - s_b . E[neg_answers_b],  loss = mean_b -log(sigmoid(diff_b) + 1e-10),
  * bsarec_gru4rec_loss_grad writes the loss (one float) and the gradient of every parameter: d_item_emb [V, d] -- the lookup rows
