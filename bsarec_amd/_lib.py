@@ -179,7 +179,12 @@ class FeaAttnConfig(C.Structure):
                 ("topk", C.c_int), ("train", C.c_int)]
 
 
-GRU4REC_CAND_MAX = 8192                          # BSAREC_GRU4REC_CAND_MAX: the most candidate columns of a GRU4Rec head
+class LruConfig(C.Structure):
+    """bsarec_lru_config_t"""
+    _fields_ = [("batch", C.c_int), ("seq_len", C.c_int), ("width", C.c_int)]
+
+
+GRU4REC_CAND_MAX = 8192                         # BSAREC_GRU4REC_CAND_MAX: the most candidate columns of a GRU4Rec head
 GRU4REC_LOSSES = {"ce": 1, "top1": 2, "bpr_max": 3}                 # bsarec_gru4rec_head_t.loss
 GRU4REC_CANDIDATES = {"in_batch": 1, "in_batch+sampled": 2}         # bsarec_gru4rec_head_t.candidates
 
@@ -307,6 +312,10 @@ EXPORTS = {
     "bsarec_fea_attn_workspace_bytes": (C.c_long, [C.POINTER(FeaAttnConfig)]),
     "bsarec_fea_attn_fwd": (C.c_int, [C.POINTER(FeaAttnConfig)] + [C.c_void_p] * 5 + [C.c_long, C.c_void_p]),
     "bsarec_fea_attn_bwd": (C.c_int, [C.POINTER(FeaAttnConfig)] + [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 4),
+    "bsarec_lru_weight_floats": (C.c_long, [C.POINTER(LruConfig)]),
+    "bsarec_lru_workspace_bytes": (C.c_long, [C.POINTER(LruConfig), C.c_int]),
+    "bsarec_lru_fwd": (C.c_int, [C.POINTER(LruConfig)] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
+    "bsarec_lru_bwd": (C.c_int, [C.POINTER(LruConfig)] + [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 3),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

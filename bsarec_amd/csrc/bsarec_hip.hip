@@ -26,6 +26,7 @@
 #include "caser_step.h"
 #include "caser_user.h"
 #include "fea_attn.h"
+#include "lru.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -2641,6 +2642,119 @@ extern "C" int bsarec_fea_attn_bwd(const bsarec_fea_attn_config_t* cfg, const fl
     hipLaunchKernelGGL(fea_dp_kernel, dim3(c.batch), dim3(256), 0, s, P);
     hipLaunchKernelGGL(fea_shift_kernel<false>, dim3(c.batch, cdiv((long)c.seq_len * (c.width / 4), 256)), dim3(256), 0, s, P);
     hipLaunchKernelGGL(fea_dqk_kernel, dim3(c.batch, 2), dim3(256), 0, s, P);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Linear recurrent unit layer (lru.h): plan-less, one linear chain on the caller's stream, no allocation
+// ---------------------------------------------------------------------------------------------
+static int lru_check(const bsarec_lru_config_t* c) {
+    if (!c) return -10;
+    if (c->batch < 1 || c->batch > 65536 || c->seq_len < 1 || c->seq_len > 256) return -10;
+    if (!row_dim_ok(c->width)) return -10;
+    return 0;
+}
+
+// offsets (floats) into the flat weight array: nu_log | theta_log | gamma_log | in_proj.weight [2d][d] | in_proj.bias [2d] |
+// out_proj.weight [d][2d] | out_proj.bias [d]
+struct LruW { long win, bin, wout, bout, total; };
+static LruW lru_weights(const bsarec_lru_config_t& c) {
+    const long d = c.width;
+    LruW w;
+    w.win = 3 * d; w.bin = w.win + 2 * d * d; w.wout = w.bin + 2 * d; w.bout = w.wout + 2 * d * d; w.total = w.bout + d;
+    return w;
+}
+
+// Workspace, in floats (every region a multiple of 4): V [T][2d] | H [T][2d] | lambda, gamma [3d] | G [T][2d] |
+// slabs [ns][2 d d] | bias partials [ns][2d] | scan partials [workgroups][3d]; T = B L; everything behind lambda in training only
+struct LruWs { long v, h, lam, g, slab, bpart, part, total; int ns, nwg; };
+static LruWs lru_ws(const bsarec_lru_config_t& c, bool train) {
+    const long T = (long)c.batch * c.seq_len, d = c.width;
+    LruWs w;
+    memset(&w, 0, sizeof(w));
+    int kc;
+    gru_split(T, &w.ns, &kc);
+    w.nwg = cdiv(c.batch, lru_geom(c.width).seqs);
+    long off = 0;
+    w.v = off; off += T * 2 * d;
+    w.h = off; off += T * 2 * d;
+    w.lam = off; off += 3 * d;
+    if (train) {
+        w.g = off; off += T * 2 * d;
+        w.slab = off; off += w.ns * 2 * d * d;
+        w.bpart = off; off += w.ns * 2 * d;
+        w.part = off; off += w.nwg * 3 * d;
+    }
+    w.total = off;
+    return w;
+}
+
+extern "C" long bsarec_lru_weight_floats(const bsarec_lru_config_t* cfg) {
+    if (lru_check(cfg)) return -10;
+    return lru_weights(*cfg).total;
+}
+
+extern "C" long bsarec_lru_workspace_bytes(const bsarec_lru_config_t* cfg, int train) {
+    if (lru_check(cfg)) return -10;
+    return lru_ws(*cfg, train != 0).total * (long)sizeof(float);
+}
+
+static int lru_args(const bsarec_lru_config_t* cfg, const float* x, const float* weights, const void* workspace, long workspace_bytes,
+                    bool train) {
+    RET(lru_check(cfg));
+    if (!x || !weights || !workspace) return -10;
+    if (!aligned_to(x, 16) || !aligned_to(weights, 16) || !aligned_to(workspace, 16)) return -10;
+    if (workspace_bytes < lru_ws(*cfg, train).total * (long)sizeof(float)) return -10;
+    return 0;
+}
+
+extern "C" int bsarec_lru_fwd(const bsarec_lru_config_t* cfg, const float* x, const int64_t* ids, const float* weights, int train,
+                              float* y, void* workspace, long workspace_bytes, void* stream) {
+    RET(lru_args(cfg, x, weights, workspace, workspace_bytes, train != 0));
+    if (!y || !aligned_to(y, 16)) return -10;
+    const bsarec_lru_config_t& c = *cfg;
+    const int B = c.batch, L = c.seq_len, d = c.width;
+    const long T = (long)B * L;
+    const LruWs ws = lru_ws(c, train != 0);
+    const LruW wo = lru_weights(c);
+    float* w = (float*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(lru_lambda_kernel, dim3(cdiv(d, 256)), dim3(256), 0, s, weights, w + ws.lam, d);
+    RET(gru_nt(x, weights + wo.win, (int)T, 2 * d, d, gru_epi(w + ws.v, 2 * d, weights + wo.bin), s));
+    LruFwdP P;
+    P.V = w + ws.v; P.H = w + ws.h; P.ids = ids; P.lam = w + ws.lam; P.B = B; P.L = L; P.d = d; P.save_v = train != 0;
+    hipLaunchKernelGGL(lru_scan_fwd_kernel, dim3(ws.nwg), dim3(LRU_THREADS), 0, s, P);
+    RET(gru_nt(w + ws.h, weights + wo.wout, (int)T, d, 2 * d, gru_epi(y, d, weights + wo.bout), s));
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_lru_bwd(const bsarec_lru_config_t* cfg, const float* x, const int64_t* ids, const float* weights, const float* dy,
+                              void* workspace, long workspace_bytes, float* dx, float* dweights, void* stream) {
+    RET(lru_args(cfg, x, weights, workspace, workspace_bytes, true));
+    if (!dy || !dx || !dweights || !aligned_to(dy, 16) || !aligned_to(dx, 16) || !aligned_to(dweights, 16)) return -10;
+    const bsarec_lru_config_t& c = *cfg;
+    const int B = c.batch, L = c.seq_len, d = c.width;
+    const long T = (long)B * L;
+    const LruWs ws = lru_ws(c, true);
+    const LruW wo = lru_weights(c);
+    float* w = (float*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    float* slab = w + ws.slab;
+    hipLaunchKernelGGL(lru_lambda_kernel, dim3(cdiv(d, 256)), dim3(256), 0, s, weights, w + ws.lam, d);
+    // g = dy . W_out;  dW_out = dy^T . [Re h | Im h], db_out = its column sums
+    RET(gru_nn(dy, weights + wo.wout, (int)T, 2 * d, d, gru_epi(w + ws.g, 2 * d), s));
+    RET(gru_tn(dy, d, w + ws.h, d, 2 * d, T, slab, 2L * d * d, 0, w + ws.bpart, s));
+    gru_sum(slab, T, 2L * d * d, dweights + wo.wout, s);
+    gru_sum(w + ws.bpart, T, d, dweights + wo.bout, s);
+    LruBwdP P;
+    P.G = w + ws.g; P.V = w + ws.v; P.H = w + ws.h; P.ids = ids; P.lam = w + ws.lam; P.part = w + ws.part; P.B = B; P.L = L; P.d = d;
+    hipLaunchKernelGGL(lru_scan_bwd_kernel, dim3(ws.nwg), dim3(LRU_THREADS), 0, s, P);
+    hipLaunchKernelGGL(lru_param_grad_kernel, dim3(d / 4), dim3(256), 0, s, w + ws.part, ws.nwg, weights, w + ws.lam, d, dweights);
+    // dx = du . W_in;  dW_in = du^T . x, db_in = its column sums
+    RET(gru_nn(w + ws.g, weights + wo.win, (int)T, d, 2 * d, gru_epi(dx, d), s));
+    RET(gru_tn(w + ws.g, 2 * d, x, 2 * d, d, T, slab, 2L * d * d, 0, w + ws.bpart, s));
+    gru_sum(slab, T, 2L * d * d, dweights + wo.win, s);
+    gru_sum(w + ws.bpart, T, 2 * d, dweights + wo.bin, s);
     return (int)hipGetLastError();
 }
 

@@ -35,7 +35,8 @@ SIBLING_MODELS = {"bert4rec": BERT4RecModel}
 # ... as is SIBLING_MODELS' (tests/test_cloze_cpu.py).  MODEL_REGISTRY is the open table: tests check membership in it, never its
 # key set, so the next sibling adds a key here
 from .fearec import FEARecModel
-MODEL_REGISTRY = {"fearec": FEARecModel}
+from .lrurec import LRURecModel
+MODEL_REGISTRY = {"fearec": FEARecModel, "lrurec": LRURecModel}
 from .trainer import Trainer
 
 
@@ -69,6 +70,17 @@ def positive_value(text: str) -> float:
         raise argparse.ArgumentTypeError(f"not a number: {text!r}") from None
     if not 0.0 < r < float("inf"):
         raise argparse.ArgumentTypeError(f"{r} is not a finite number > 0")
+    return r
+
+
+def radius_value(text: str) -> float:
+    """--lru_r_min / --lru_r_max: a ring radius in [0, 1)."""
+    try:
+        r = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}") from None
+    if not 0.0 <= r < 1.0:                                                       # (NaN fails)
+        raise argparse.ArgumentTypeError(f"{r} outside [0, 1)")
     return r
 
 
@@ -255,7 +267,14 @@ def parse_args(argv=None):
                    help="FEARec: which views the frequency-domain regulariser compares (default us_x)")
     p.add_argument("--fea_topk_factor", default=argparse.SUPPRESS, type=positive_value,
                    help="FEARec: the layer keeps int(factor ln L) delays, clamped to 1 .. min(L, 32) (default 1.0)")
+    # not reference-checked flags: the ring of LRURec's initial eigenvalues (--model_type LRURec).  Absent unless given
+    p.add_argument("--lru_r_min", default=argparse.SUPPRESS, type=radius_value,
+                   help="LRURec: smallest initial |lambda|, 0 <= r_min < r_max (default 0.8)")
+    p.add_argument("--lru_r_max", default=argparse.SUPPRESS, type=radius_value,
+                   help="LRURec: largest initial |lambda|, r_min < r_max < 1 (default 0.99)")
     args = p.parse_args(argv)
+    if not getattr(args, "lru_r_min", 0.8) < getattr(args, "lru_r_max", 0.99):
+        p.error("--lru_r_min / --lru_r_max: expected 0 <= r_min < r_max < 1")
     n = getattr(args, "eval_negatives", 0)
     if n > 0 and hasattr(args, "eval_full_rank"):
         p.error("--eval_full_rank: applies to the full ranking, not to --eval_negatives > 0")

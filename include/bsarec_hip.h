@@ -947,6 +947,37 @@ int bsarec_fea_attn_fwd(const bsarec_fea_attn_config_t *cfg, const float *q, con
 int bsarec_fea_attn_bwd(const bsarec_fea_attn_config_t *cfg, const float *q, const float *k, const float *v, const float *dout,
                         void *workspace, long workspace_bytes, float *dq, float *dk, float *dv, void *stream);
 
+/* Linear recurrent unit layer of the LRURec sibling model (csrc/lru.h): with x [B, L, d] (d = width), ids [B, L] (int64, 0 is
+ * padding; a null pointer means no padding) and m_t = (ids[b, t] != 0),
+ *   lambda = exp(-exp(nu_log)) (cos(exp(theta_log)) + i sin(exp(theta_log))),
+ *   u_t = in_proj.weight x_t + in_proj.bias (first d entries the real part, last d the imaginary part),
+ *   v_t = m_t exp(gamma_log) u_t,  h_t = lambda h_{t-1} + v_t (h_{-1} = 0),
+ *   y_t = out_proj.weight [Re h_t | Im h_t] + out_proj.bias, y [B, L, d].
+ * `weights` is ONE flat fp32 array, every tensor at a multiple of 4 floats: nu_log [d] | theta_log [d] | gamma_log [d] |
+ * in_proj.weight [2d, d] | in_proj.bias [2d] | out_proj.weight [d, 2d] | out_proj.bias [d]; bsarec_lru_weight_floats is their
+ * sum, 4 d d + 6 d.  bsarec_lru_bwd is the true derivative: every float of dx [B, L, d] and of dweights (the layout of weights)
+ * is overwritten.  It reads what bsarec_lru_fwd(train = 1) left in the SAME workspace with the same cfg, ids and weights: v and
+ * [Re h | Im h], [B, L, 2d] each.  train = 0 keeps nothing and gives the same y, bit for bit.
+ *   The products run in the GEMM core (v_mfma_f32, split-K slabs added in slice order, bias gradients as column sums), the
+ * recurrence as a chunked scan over time (csrc/lru.h).  A masked step is selected to 0, so nothing at an item's position depends
+ * on what x holds under the padding; a row of padding alone gives y = out_proj.bias bit for bit and dx = 0.  With seq_len = 1,
+ * dnu_log and dtheta_log are exact zeros.  Every sum has one order that is a function of the shape alone: no atomics, equal bits
+ * on every run, and a sequence's y and dx do not depend on the batch or on its place in it.  Launches, all on `stream`, one after
+ * the other: forward 4, backward 11.  No allocation, no host synchronisation, static LDS only: capturable.
+ *   Workspace: bsarec_lru_workspace_bytes(cfg, train) bytes (host-only query, no HIP call); train != 0 asks for no less.
+ *   Limits (else < 0 before any HIP call, nothing written): 1 <= batch <= 65536, 1 <= seq_len <= 256, width in 4 .. 256 and a
+ * multiple of 4; every float pointer non-null and 16-byte aligned; workspace_bytes at least the queried size.  Outputs may not
+ * alias inputs, each other or the workspace.  Inputs are assumed finite. */
+typedef struct {
+    int batch, seq_len, width;
+} bsarec_lru_config_t;
+long bsarec_lru_weight_floats(const bsarec_lru_config_t *cfg);
+long bsarec_lru_workspace_bytes(const bsarec_lru_config_t *cfg, int train);
+int bsarec_lru_fwd(const bsarec_lru_config_t *cfg, const float *x, const int64_t *ids, const float *weights, int train, float *y,
+                   void *workspace, long workspace_bytes, void *stream);
+int bsarec_lru_bwd(const bsarec_lru_config_t *cfg, const float *x, const int64_t *ids, const float *weights, const float *dy,
+                   void *workspace, long workspace_bytes, float *dx, float *dweights, void *stream);
+
 /* Tag kernel launches of one id with hipEvents for in-process roofline timing (bench.py):
  * when set, every launch of kernel class `kclass` (see BSAREC_K_*) on the next calls of THIS plan is bracketed
  * by hipEventRecord on the launch stream; bsarec_profile_read returns the summed milliseconds and
