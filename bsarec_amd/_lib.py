@@ -184,7 +184,12 @@ class LruConfig(C.Structure):
     _fields_ = [("batch", C.c_int), ("seq_len", C.c_int), ("width", C.c_int)]
 
 
-GRU4REC_CAND_MAX = 8192                         # BSAREC_GRU4REC_CAND_MAX: the most candidate columns of a GRU4Rec head
+class LruRecConfig(C.Structure):
+    """bsarec_lrurec_config_t"""
+    _fields_ = [("lru", LruConfig), ("layers", C.c_int), ("item_size", C.c_int), ("dropout", C.c_float), ("ln_eps", C.c_float)]
+
+
+GRU4REC_CAND_MAX = 8192                        # BSAREC_GRU4REC_CAND_MAX: the most candidate columns of a GRU4Rec head
 GRU4REC_LOSSES = {"ce": 1, "top1": 2, "bpr_max": 3}                 # bsarec_gru4rec_head_t.loss
 GRU4REC_CANDIDATES = {"in_batch": 1, "in_batch+sampled": 2}         # bsarec_gru4rec_head_t.candidates
 
@@ -316,6 +321,12 @@ EXPORTS = {
     "bsarec_lru_workspace_bytes": (C.c_long, [C.POINTER(LruConfig), C.c_int]),
     "bsarec_lru_fwd": (C.c_int, [C.POINTER(LruConfig)] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
     "bsarec_lru_bwd": (C.c_int, [C.POINTER(LruConfig)] + [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 3),
+    "bsarec_lrurec_weight_floats": (C.c_long, [C.POINTER(LruRecConfig)]),
+    "bsarec_lrurec_workspace_bytes": (C.c_long, [C.POINTER(LruRecConfig)]),
+    "bsarec_lrurec_loss_grad": (C.c_int, [C.POINTER(LruRecConfig)] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 +
+                                [C.c_long, C.c_void_p]),
+    "bsarec_lrurec_train_step": (C.c_int, [C.POINTER(LruRecConfig)] + [C.c_void_p] * 2 + [C.POINTER(Adam)] * 2 +
+                                 [C.c_void_p] * 3 + [C.c_long, C.c_void_p]),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

@@ -27,6 +27,7 @@
 #include "caser_user.h"
 #include "fea_attn.h"
 #include "lru.h"
+#include "lrurec_step.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -3067,6 +3068,290 @@ extern "C" int bsarec_gru4rec_cand_train_step(const bsarec_gru4rec_config_t* cfg
     if (!head) return -10;
     return gru4rec_train_step(cfg, ids, answers, neg_answers, adam_items, adam_weights, state, loss_out, workspace, workspace_bytes,
                               head, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// LRURec training step (lrurec_step.h): lookup + LayerNorm + dropout, N blocks of recurrent layer and feed-forward net, the CE head
+// at position L - 1, every gradient, Adam -- plan-less, one linear chain of launches on the caller's stream, no allocation, no
+// host synchronisation.  Launches: 11 + 28 N for a loss and its gradients (one more when train != 0: the step counter), and two
+// Adam launches behind them in a training step.
+// ---------------------------------------------------------------------------------------------
+static int lrurec_check(const bsarec_lrurec_config_t* c) {
+    if (!c) return -10;
+    RET(lru_check(&c->lru));
+    if (c->layers < 1 || c->layers > BSAREC_MAX_LAYERS) return -10;
+    if (c->item_size < 2) return -10;
+    if (!(c->dropout >= 0.f && c->dropout < 1.f)) return -10;          // NaN fails both comparisons
+    if (!(c->ln_eps > 0.f)) return -10;                                 // NaN fails it
+    return 0;
+}
+
+// offsets (floats) into the flat weight array: LayerNorm.weight | LayerNorm.bias, then per block (`first` + k `stride`) the array
+// of bsarec_lru_fwd | lru.LayerNorm w, b | dense_1 w [4d][d], b [4d] | dense_2 w [d][4d], b [d] | feed_forward.LayerNorm w, b
+struct LrrW { long first, stride, lru_ln, w1, b1, w2, b2, ff_ln, total; };
+static LrrW lrurec_weights(const bsarec_lrurec_config_t& c) {
+    const long d = c.lru.width;
+    LrrW w;
+    w.first = 2 * d;
+    w.lru_ln = lru_weights(c.lru).total;
+    w.w1 = w.lru_ln + 2 * d; w.b1 = w.w1 + 4 * d * d;
+    w.w2 = w.b1 + 4 * d; w.b2 = w.w2 + 4 * d * d;
+    w.ff_ln = w.b2 + d; w.stride = w.ff_ln + 2 * d;
+    w.total = w.first + c.layers * w.stride;
+    return w;
+}
+
+// Workspace, in floats (every region a multiple of 4), T = B L, T4 = T rounded up to 4:
+//   one [4] | xhat0 [T][d] | rstd0 [T4] | x_0 .. x_N [N + 1][T][d] | z [T][d] |
+//   per block (`blk` + k `blk_stride`): the workspace of bsarec_lru_fwd(train = 1) | a [T][d] | xhat_a [T][d] | rstd_a [T4] |
+//     u [T][4d] | xhat_f [T][d] | rstd_f [T4] |
+//   dy [T][d] | dz [T][d] | dt [T][d] | du [T][4d] | da [T][d] | dxl [T][d] | dh [B][d] | the CE head's workspace |
+//   slabs of dW1 [ns][4d][d] | of dW2 [ns][d][4d] | of db1 [ns][4d] | of db2 [ns][d] | LayerNorm partials [2 N + 1][2][nb][d] |
+//   the fixed-point accumulator [V][d] of 64-bit words
+// ns: the split-K slices of a product over T rows (gru_split); nb blocks of rows_pb rows: the grid of ln_bwd_kernel
+struct LrrWs {
+    long one, xhat0, rstd0, x, z, blk, blk_stride, dy, dz, dt, du, da, dxl, dh, ce, slab1, slab2, bp1, bp2, lnpart, acc, total;
+    long b_a, b_xhat_a, b_rstd_a, b_u, b_xhat_f, b_rstd_f;        // inside a block's region, behind the LRU workspace at 0
+    long lru_bytes, ce_bytes;
+    int ns, kc, nb, rows_pb;
+};
+static LrrWs lrurec_ws(const bsarec_lrurec_config_t& c) {
+    const long B = c.lru.batch, T = B * c.lru.seq_len, d = c.lru.width, N = c.layers, T4 = rup(T, 4);
+    LrrWs w;
+    memset(&w, 0, sizeof(w));
+    gru_split(T, &w.ns, &w.kc);
+    w.nb = std::min(cdiv(T, 64), 256);
+    w.rows_pb = (int)rup(cdiv(T, w.nb), 16);
+    w.nb = cdiv(T, w.rows_pb);
+    const long lru = lru_ws(c.lru, true).total, ce = ce_workspace_floats((int)B, c.item_size, (int)d);
+    w.lru_bytes = lru * (long)sizeof(float); w.ce_bytes = ce * (long)sizeof(float);
+    long off = 0;
+    w.one = off; off += 4;
+    w.xhat0 = off; off += T * d;
+    w.rstd0 = off; off += T4;
+    w.x = off; off += (N + 1) * T * d;
+    w.z = off; off += T * d;
+    long b = lru;
+    w.b_a = b; b += T * d;
+    w.b_xhat_a = b; b += T * d;
+    w.b_rstd_a = b; b += T4;
+    w.b_u = b; b += T * 4 * d;
+    w.b_xhat_f = b; b += T * d;
+    w.b_rstd_f = b; b += T4;
+    w.blk = off; w.blk_stride = b; off += N * b;
+    w.dy = off; off += T * d;
+    w.dz = off; off += T * d;
+    w.dt = off; off += T * d;
+    w.du = off; off += T * 4 * d;
+    w.da = off; off += T * d;
+    w.dxl = off; off += T * d;
+    w.dh = off; off += B * d;
+    w.ce = off; off += rup(ce, 4);
+    w.slab1 = off; off += w.ns * 4 * d * d;
+    w.slab2 = off; off += w.ns * 4 * d * d;
+    w.bp1 = off; off += w.ns * 4 * d;
+    w.bp2 = off; off += w.ns * d;
+    w.lnpart = off; off += (2 * N + 1) * 2 * w.nb * d;
+    w.acc = off; off += 2L * c.item_size * d;
+    w.total = off;
+    return w;
+}
+
+extern "C" long bsarec_lrurec_weight_floats(const bsarec_lrurec_config_t* cfg) {
+    if (lrurec_check(cfg)) return -10;
+    return lrurec_weights(*cfg).total;
+}
+
+extern "C" long bsarec_lrurec_workspace_bytes(const bsarec_lrurec_config_t* cfg) {
+    if (lrurec_check(cfg)) return -10;
+    return lrurec_ws(*cfg).total * (long)sizeof(float);
+}
+
+// dropout site `site` of a step; train = false: no mask, whatever p
+static DropP lrurec_drop(const bsarec_lrurec_config_t& c, const void* state, bool train, int site) {
+    DropP d = site0_drop(c.dropout, state, train);
+    d.site = (uint32_t)site;
+    return d;
+}
+
+// ln_bwd_kernel over the step's T rows, MODE 0 (y = LN(Drop(z) + res): dz and dt = dz times the mask) or MODE 2 (y = Drop(LN(e)):
+// dz = de); the d(gamma), d(beta) partials go to LayerNorm j's slot of the workspace
+template <int MODE>
+static void lrurec_ln_bwd(const LrrWs& ws, float* w, int j, const float* dy, const float* xhat, const float* rstd, const float* gamma,
+                          const DropP& drop, float* dz, float* dt, long T, int d, hipStream_t s) {
+    LnBranch a;
+    memset(&a, 0, sizeof(a));
+    a.xhat = xhat; a.rstd = rstd; a.gamma = gamma; a.in_scale = 1.f; a.drop = drop; a.dT = dt;
+    a.pgamma = w + ws.lnpart + (long)j * 2 * ws.nb * d; a.pbeta = a.pgamma + (long)ws.nb * d;
+    DISPATCH_LPR(d, hipLaunchKernelGGL((ln_bwd_kernel<LPR, MODE>), dim3(ws.nb), dim3(ROW_THREADS), 0, s, dy, a, a, dz, (int)T, d,
+                                       ws.rows_pb));
+}
+
+// tick_adam: null, or the Adam whose t the step's closing block advances (bsarec_lrurec_train_step)
+static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const float* weights, const int64_t* ids,
+                      const int64_t* answers, void* state, int train, float* loss_out, float* dE, float* dweights, void* workspace,
+                      const bsarec_adam_t* tick_adam, hipStream_t s) {
+    const int B = c.lru.batch, L = c.lru.seq_len, d = c.lru.width, N = c.layers, V = c.item_size;
+    const long T = (long)B * L, Td = T * d;
+    const bool tr = train != 0;
+    const LrrWs ws = lrurec_ws(c);
+    const LrrW wo = lrurec_weights(c);
+    float* w = (float*)workspace;
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(w + ws.acc);
+    const XformP nox = no_xform();
+    const dim3 wg(ROW_THREADS);
+    const dim3 flat_grid(std::min(cdiv(Td / 4, ROW_THREADS), 4096));
+    auto X = [&](int k) { return w + ws.x + (long)k * Td; };
+    auto blk = [&](int k) { return w + ws.blk + (long)k * ws.blk_stride; };
+    auto Wb = [&](int k) { return weights + wo.first + (long)k * wo.stride; };
+
+    // ---- forward
+    if (tr) hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(1), 0, s, (uint64_t*)state, (long long*)nullptr, 0);
+    {
+        LrrEmbedP P;
+        P.E = E; P.ids = ids; P.gamma = weights; P.beta = weights + d; P.eps = c.ln_eps; P.drop = lrurec_drop(c, state, tr, 0);
+        P.T = T; P.d = d; P.V = V; P.x = X(0); P.xhat = w + ws.xhat0; P.rstd = w + ws.rstd0;
+        P.acc = acc; P.acc_n2 = (long)V * d / 2; P.one = w + ws.one;
+        DISPATCH_LPR(d, hipLaunchKernelGGL(lrr_embed_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)), wg, 0, s, P));
+    }
+    for (int k = 0; k < N; ++k) {
+        float* bw = blk(k);
+        const float* wk = Wb(k);
+        RET(bsarec_lru_fwd(&c.lru, X(k), ids, wk, 1, w + ws.z, bw, ws.lru_bytes, s));
+        {   // a = LN(Drop(z) + x)
+            LrrAddLnP P;
+            P.z = w + ws.z; P.x = X(k); P.gamma = wk + wo.lru_ln; P.beta = wk + wo.lru_ln + d; P.eps = c.ln_eps;
+            P.drop = lrurec_drop(c, state, tr, 1 + 2 * k); P.T = T; P.d = d;
+            P.a = bw + ws.b_a; P.xhat = bw + ws.b_xhat_a; P.rstd = bw + ws.b_rstd_a;
+            DISPATCH_LPR(d, hipLaunchKernelGGL(lrr_add_ln_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)), wg, 0, s, P));
+        }
+        {   // u = dense_1(a)
+            GemmP g = gemm_defaults((int)T, 4 * d, d);
+            g.lda = d; g.ldb = d; g.A[0] = bw + ws.b_a; g.B[0] = wk + wo.w1;
+            auto e = epi_linear<true, false, false>(bw + ws.b_u, 4 * d);
+            e.bias[0] = wk + wo.b1;
+            RET((launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_NONE, true)));
+        }
+        {   // x_{k+1} = LN(Drop(dense_2(gelu(u))) + a)
+            GemmP g = gemm_defaults((int)T, d, 4 * d);
+            g.lda = 4 * d; g.ldb = 4 * d; g.A[0] = bw + ws.b_u; g.B[0] = wk + wo.w2;
+            EpiLN<false> e;
+            e.bias = wk + wo.b2; e.R = bw + ws.b_a; e.drop = lrurec_drop(c, state, tr, 2 + 2 * k);
+            e.gamma = wk + wo.ff_ln; e.beta = wk + wo.ff_ln + d; e.eps = c.ln_eps;
+            e.Y = X(k + 1); e.xhat = bw + ws.b_xhat_f; e.rstd = bw + ws.b_rstd_f;
+            e.dsp = nullptr; e.alpha = 0.f; e.oma = 1.f;
+            XformP xa = nox; xa.act = 0;
+            DISPATCH_BN(d, RET((launch_gemm<64, BN, 2, 2, false, false, XF_GELU, XF_NONE, false>(g, xa, e, nullptr, 1, s, BSAREC_K_NONE,
+                                                                                                  true))));
+        }
+    }
+    // ---- the CE head on position L - 1 of x_N: the loss, dh [B][d] and the dense part of dE (every row written)
+    const float* hlast = X(N) + (long)(L - 1) * d;
+    RET(bsarec_ce_head_fwd(hlast, (long)L * d, E, B, V, d, answers, loss_out, nullptr, w + ws.ce, ws.ce_bytes, s));
+    RET(bsarec_ce_head_bwd(hlast, (long)L * d, E, B, V, d, answers, w + ws.one, w + ws.ce, ws.ce_bytes, w + ws.dh, dE, s));
+    hipLaunchKernelGGL(lrr_top_fill_kernel, flat_grid, wg, 0, s, w + ws.dh, w + ws.dy, Td / 4, L, d / 4);
+    // ---- the blocks, top down; dy is the gradient of x_{k+1}
+    for (int k = N - 1; k >= 0; --k) {
+        float* bw = blk(k);
+        const float* wk = Wb(k);
+        float* dwk = dweights + wo.first + (long)k * wo.stride;
+        lrurec_ln_bwd<0>(ws, w, 2 + 2 * k, w + ws.dy, bw + ws.b_xhat_f, bw + ws.b_rstd_f, wk + wo.ff_ln,
+                         lrurec_drop(c, state, tr, 2 + 2 * k), w + ws.dz, w + ws.dt, T, d, s);
+        {   // du = (dt . W2) * gelu'(u)
+            GemmP g = gemm_defaults((int)T, 4 * d, d);
+            g.lda = d; g.ldb = 4 * d; g.A[0] = w + ws.dt; g.B[0] = wk + wo.w2;
+            auto e = epi_linear<false, false, true>(w + ws.du, 4 * d);
+            e.U = bw + ws.b_u; e.ldu = 4 * d; e.act = 0;
+            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_NONE, true)));
+        }
+        {   // da = du . W1 + dz
+            GemmP g = gemm_defaults((int)T, d, 4 * d);
+            g.lda = 4 * d; g.ldb = d; g.A[0] = w + ws.du; g.B[0] = wk + wo.w1;
+            auto e = epi_linear<false, true, false>(w + ws.da, d);
+            e.R = w + ws.dz; e.ldr = d;
+            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_NONE, true)));
+        }
+        {   // dW1 = du^T . a, dW2 = dt^T . gelu(u), db1 and db2 the column sums of du and dt: split-K slabs in one grouped launch
+            GroupedTN G;
+            memset(&G, 0, sizeof(G));
+            struct Spec { const float* A; long lda; const float* B; long ldb; int M, N; float* slab; float* bpart; int gelu; };
+            const Spec sp[2] = {{w + ws.du, 4L * d, bw + ws.b_a, d, 4 * d, d, w + ws.slab1, w + ws.bp1, 0},
+                                {w + ws.dt, d, bw + ws.b_u, 4L * d, d, 4 * d, w + ws.slab2, w + ws.bp2, 1}};
+            int tiles = 0;
+            for (int i = 0; i < 2; ++i) {
+                GemmP g = gemm_defaults(sp[i].M, sp[i].N, (int)T);
+                g.lda = sp[i].lda; g.ldb = sp[i].ldb; g.A[0] = sp[i].A; g.B[0] = sp[i].B; g.nsplit = ws.ns; g.kchunk = ws.kc;
+                G.P[i] = g;
+                G.E[i] = epi_linear<false, false, false>(sp[i].slab, sp[i].N);
+                G.E[i].c_split = (long)sp[i].M * sp[i].N;
+                G.bgrad[i] = sp[i].bpart;
+                G.tile0[i] = tiles;
+                G.tiles_n[i] = cdiv(sp[i].N, 64);
+                G.b_gelu[i] = sp[i].gelu;
+                tiles += cdiv(sp[i].M, 64) * G.tiles_n[i];
+            }
+            G.tile0[2] = tiles; G.nprob = 2; G.act = 0;
+            RET((launch_lds<gemm_grouped_tn_kernel<false, 64>>(dim3(tiles, ws.ns), dim3(GEMM_THREADS),
+                                                               GemmSmem<64, 64, true, true, false>::BYTES, s, G)));
+            gru_sum(w + ws.slab1, T, 4L * d * d, dwk + wo.w1, s);
+            gru_sum(w + ws.bp1, T, 4L * d, dwk + wo.b1, s);
+            gru_sum(w + ws.slab2, T, 4L * d * d, dwk + wo.w2, s);
+            gru_sum(w + ws.bp2, T, d, dwk + wo.b2, s);
+        }
+        lrurec_ln_bwd<0>(ws, w, 1 + 2 * k, w + ws.da, bw + ws.b_xhat_a, bw + ws.b_rstd_a, wk + wo.lru_ln,
+                         lrurec_drop(c, state, tr, 1 + 2 * k), w + ws.dz, w + ws.dt, T, d, s);
+        RET(bsarec_lru_bwd(&c.lru, X(k), ids, wk, w + ws.dt, bw, ws.lru_bytes, w + ws.dxl, dwk, s));
+        hipLaunchKernelGGL(lrr_add_kernel, flat_grid, wg, 0, s, w + ws.dxl, w + ws.dz, w + ws.dy, Td / 4);
+    }
+    // ---- the embedding: de = LNbwd(dy times the mask), every LayerNorm's parameter gradient, the lookup rows onto dE
+    lrurec_ln_bwd<2>(ws, w, 0, w + ws.dy, w + ws.xhat0, w + ws.rstd0, weights, lrurec_drop(c, state, tr, 0), w + ws.dz, nullptr, T, d, s);
+    {
+        LrrLnSumP P;
+        P.part = w + ws.lnpart; P.nb = ws.nb; P.d = d; P.dw = dweights;
+        P.first = wo.first; P.stride = wo.stride; P.at_lru = wo.lru_ln; P.at_ff = wo.ff_ln;
+        hipLaunchKernelGGL(lrr_ln_sum_kernel, dim3(2 * N + 1), wg, 0, s, P);
+    }
+    {
+        LrrItemGradP P;
+        P.de = w + ws.dz; P.ids = ids; P.T = T; P.d = d; P.V = V; P.dA = acc;
+        DISPATCH_LPR(d, hipLaunchKernelGGL(lrr_item_grad_kernel<LPR>, dim3(cdiv(T, SCATTER_FLOATS / (4 * LPR))), wg, 0, s, P));
+    }
+    // the accumulator is ADDED onto the head's dense dE; the closing block of a training step advances Adam's t
+    LookupAcc la = pair_flush_acc(acc, dE, (long)V * d);
+    la.dense_zero = 0;
+    const bsarec_adam_t* a = tick_adam;
+    const TickP tk = a ? make_tick(state, 1, a->lr, a->beta1, a->beta2, nullptr, 0, nullptr, nullptr, 0, 0)
+                       : make_tick(state, 0, 0.f, 0.f, 0.f, nullptr, 0, nullptr, nullptr, 0, 0);
+    hipLaunchKernelGGL(pair_flush_kernel, dim3(la.nblocks + (a ? 1 : 0)), wg, 0, s, la, tk);
+    return (int)hipGetLastError();
+}
+
+static int lrurec_loss_grad(const bsarec_lrurec_config_t* cfg, const float* item_emb, const float* weights, const int64_t* ids,
+                            const int64_t* answers, void* state, int train, float* loss_out, float* d_item_emb, float* dweights,
+                            void* workspace, long workspace_bytes, const bsarec_adam_t* tick_adam, hipStream_t s) {
+    RET(lrurec_check(cfg));
+    RET(pair_ptrs_check({item_emb, weights, d_item_emb, dweights, workspace}, {ids, answers, state}, loss_out));
+    if (workspace_bytes < lrurec_ws(*cfg).total * (long)sizeof(float)) return -10;
+    return lrurec_run(*cfg, item_emb, weights, ids, answers, state, train, loss_out, d_item_emb, dweights, workspace, tick_adam, s);
+}
+
+extern "C" int bsarec_lrurec_loss_grad(const bsarec_lrurec_config_t* cfg, const float* item_emb, const float* weights,
+                                       const int64_t* ids, const int64_t* answers, void* state, int train, float* loss_out,
+                                       float* d_item_emb, float* dweights, void* workspace, long workspace_bytes, void* stream) {
+    return lrurec_loss_grad(cfg, item_emb, weights, ids, answers, state, train, loss_out, d_item_emb, dweights, workspace,
+                            workspace_bytes, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int bsarec_lrurec_train_step(const bsarec_lrurec_config_t* cfg, const int64_t* ids, const int64_t* answers,
+                                        const bsarec_adam_t* adam_items, const bsarec_adam_t* adam_weights, void* state,
+                                        float* loss_out, void* workspace, long workspace_bytes, void* stream) {
+    RET(lrurec_check(cfg));
+    const StepAdam adams[] = {{adam_items, (long)cfg->item_size * cfg->lru.width}, {adam_weights, lrurec_weights(*cfg).total}};
+    RET(pair_adams_check(adams));
+    hipStream_t s = (hipStream_t)stream;
+    RET(lrurec_loss_grad(cfg, adam_items->params, adam_weights->params, ids, answers, state, 1, loss_out, adam_grads(adam_items),
+                         adam_grads(adam_weights), workspace, workspace_bytes, adam_items, s));
+    return pair_adams_launch(adams, state, s);
 }
 
 static int g4c_alone_check(int B, int d, int V, const bsarec_gru4rec_head_t* head) {

@@ -9,8 +9,9 @@ exists for it.  Where it departs from the paper's code, on purpose: the loss is 
 already expands every prefix), there is no item bias, and the out-projection is a real matrix on the stacked real and imaginary
 parts of the state (``Re(C h)`` with the sign of the imaginary half absorbed into the parameter).  The recurrent layer runs in
 libbsarec_hip.so in both directions (bsarec_lru_fwd / bsarec_lru_bwd, csrc/lru.h) and the loss in the catalogue CE head
-(bsarec_ce_head_fwd / _bwd); the embedding lookup, the LayerNorms, the feed-forward net and the dropout are torch ops.  There
-is no CPU path.
+(bsarec_ce_head_fwd / _bwd); on the default path the embedding lookup, the LayerNorms, the feed-forward net and the dropout are
+torch ops.  With ``lru_step = "fused"`` the whole training step -- those parts, the item-table gradient and Adam included -- is one
+C call (bsarec_lrurec_train_step, csrc/lrurec_step.h).  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
+from . import _fused_step as FS
 from . import _lib as L
 from .fearec import _LayerNorm, _act
 from .model import _CatalogueCeFn
@@ -32,6 +34,22 @@ def lru_param_shapes(width: int) -> "OrderedDict[str, tuple]":
     d = int(width)
     return OrderedDict([("nu_log", (d,)), ("theta_log", (d,)), ("gamma_log", (d,)), ("in_proj.weight", (2 * d, d)),
                         ("in_proj.bias", (2 * d,)), ("out_proj.weight", (d, 2 * d)), ("out_proj.bias", (d,))])
+
+
+def lrurec_param_shapes(width: int, layers: int) -> "OrderedDict[str, tuple]":
+    """The tensors of bsarec_lrurec_loss_grad's flat weight array under their state_dict keys, in its order (include/bsarec_hip.h):
+    every parameter of LRURecModel but the item table."""
+    d = int(width)
+    shapes = OrderedDict([("LayerNorm.weight", (d,)), ("LayerNorm.bias", (d,))])
+    for k in range(int(layers)):
+        blk = f"item_encoder.blocks.{k}."
+        for name, shp in lru_param_shapes(d).items():
+            shapes[blk + "lru." + name] = shp
+        shapes[blk + "lru.LayerNorm.weight"] = shapes[blk + "lru.LayerNorm.bias"] = (d,)
+        shapes[blk + "feed_forward.dense_1.weight"], shapes[blk + "feed_forward.dense_1.bias"] = (4 * d, d), (4 * d,)
+        shapes[blk + "feed_forward.dense_2.weight"], shapes[blk + "feed_forward.dense_2.bias"] = (d, 4 * d), (d,)
+        shapes[blk + "feed_forward.LayerNorm.weight"] = shapes[blk + "feed_forward.LayerNorm.bias"] = (d,)
+    return shapes
 
 
 class _LruFn(torch.autograd.Function):
@@ -139,7 +157,9 @@ class LruLayer(nn.Module):
         return list(self._views.values())
 
     def reflatten(self):
-        """Makes every parameter a view of one flat tensor again (after ``.to()`` / ``.cuda()`` gave each its own storage)."""
+        """Makes every parameter a view of one flat tensor again (after ``.to()`` / ``.cuda()`` gave each its own storage).
+        ``_flat`` may itself be a slice of a larger array (LRURecModel with ``lru_step = "fused"``): the test compares addresses,
+        and ``data_ptr()`` of a slice is the address of its first element."""
         ps = self.flat_parameters()
         base = self._flat
         if all(p.device == base.device and p.data_ptr() == base.data_ptr() + 4 * o
@@ -239,16 +259,40 @@ class LRURecModel(nn.Module):
     state is 0 until a sequence's first item.
     Loss: ``cross_entropy(x[:, L - 1] @ E.T, answers)`` as one HIP node (no [B, V] logits).
     Init: Embedding and Linear weights N(0, initializer_range), biases 0, LayerNorm 1 / 0, the recurrent parameters as
-    ``LruLayer`` has them with ``lru_r_min`` (default 0.8) and ``lru_r_max`` (default 0.99)."""
+    ``LruLayer`` has them with ``lru_r_min`` (default 0.8) and ``lru_r_max`` (default 0.99).
+
+    ``args.lru_step`` selects how the model steps, single GPU either way:
+      "torch" (the default, also when absent): calculate_loss / backward / torch.optim.Adam (``torch_optim``); the dropout masks
+        are drawn from a torch generator seeded by ``set_seed``.
+      "fused": ``train_step`` is ONE C call (bsarec_lrurec_train_step: lookup, every LayerNorm, the recurrent layers, the
+        feed-forward nets, the CE head, every gradient, Adam on the item table and on the flat weight array), replayed from a
+        hipGraph per batch shape unless ``args.lru_step_graph`` is False.  The model then owns ONE flat fp32 tensor in the layout
+        of bsarec_lrurec_loss_grad's ``weights`` (``lrurec_param_shapes``); every parameter but the item table is a view of it and
+        each ``LruLayer._flat`` a slice of it, so state_dict keys and shapes are those of the default mode and checkpoints pass
+        between the two.  The instance sets ``torch_optim = False`` and ``own_train_step = True``, which is what Trainer.iteration
+        routes by.  Its dropout masks are the library's Philox stream (site 0 on the embeddings, 1 + 2 k and 2 + 2 k in block k;
+        the step counter of the device state that ``set_seed`` seeds and resets).  The two streams have the same distribution and
+        DIFFERENT draws: the two modes do not train bit for bit alike at p > 0.
+    forward, predict, last_hidden, calculate_loss and evaluation are the same in both modes (torch-generator dropout in training
+    mode)."""
 
     needs_negatives = False
     needs_same_target = False
     torch_optim = True
+    own_train_step = False                       # lru_step = "fused": Trainer.iteration calls train_step(input_ids, answers)
     full_logits = None                           # no dense-logits path: the rankings take last_hidden + catalogue_weight
     kernel_family = "LRU"
 
     def __init__(self, args):
         super().__init__()
+        mode = getattr(args, "lru_step", "torch")
+        if mode not in ("torch", "fused"):
+            raise ValueError(f"lru_step must be 'torch' or 'fused', got {mode!r}")
+        self.lru_step = mode
+        if mode == "fused":
+            self.torch_optim, self.own_train_step = False, True
+        self._fused = None                       # the fused step's buffers (_step_buffers)
+        self._wflat = None                       # lru_step = "fused": the flat weight array (reflatten)
         if getattr(args, "storage", None) == "bf16" or (getattr(args, "plan_options", None) or {}).get("storage", 0):
             raise ValueError("LRURec: storage = 'bf16' does not apply (the LRU kernels are fp32)")
         if getattr(args, "train_negatives", 0):
@@ -276,25 +320,66 @@ class LRURecModel(nn.Module):
                     m.bias.zero_()
         self._ce_pool = {}                       # (B, V, d, device) -> free workspaces of bsarec_ce_head_*
         self._seed, self._rank, self._gen = 42, 0, None
+        self._wslices = OrderedDict()            # state_dict key -> (offset, floats, shape) in the flat weight array
+        off = 0
+        for name, shp in lrurec_param_shapes(d, N).items():
+            self._wslices[name] = (off, math.prod(shp), shp)
+            off += math.prod(shp)
+        self.reflatten()
 
     def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
+        out = super()._apply(fn, recurse)         # every LruLayer has flattened itself again by now
         self._gen, self._ce_pool = None, {}
+        self._fused = None                        # with the Adam moments and the step state, as the workspace pools go
+        self.reflatten()
         return out
+
+    def flat_parameters(self):
+        """Every parameter but the item table, in the order of the flat weight array."""
+        named = dict(self.named_parameters())
+        return [named[k] for k in self._wslices]
+
+    def reflatten(self):
+        """lru_step = "fused": makes every parameter but the item table a view of ONE flat tensor in the layout of
+        bsarec_lrurec_loss_grad's ``weights`` and every ``LruLayer._flat`` a slice of it (at construction, and after ``.to()`` /
+        ``.cuda()`` gave the parameters storages of their own and the layers flattened themselves).  The values do not change.
+        A no-op in the default mode."""
+        if self.lru_step != "fused":
+            return
+        ps, base = self.flat_parameters(), self._wflat
+        if base is not None and all(p.device == base.device and p.data_ptr() == base.data_ptr() + 4 * o
+                                    for p, (o, n, shp) in zip(ps, self._wslices.values())):
+            return
+        with torch.no_grad():
+            flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps])
+            for p, (o, n, shp) in zip(ps, self._wslices.values()):
+                p.data = flat[o:o + n].view(shp)
+                p.grad = None
+        self._wflat, self._fused = flat, None
+        for k, blk in enumerate(self.item_encoder.blocks):
+            o = self._wslices[f"item_encoder.blocks.{k}.lru.nu_log"][0]
+            blk.lru._flat, blk.lru._pool = flat[o:o + sum(n for _, n, _ in blk.lru._slices.values())], {}
 
     def check_trainer(self, args, process_group):
         """Called by Trainer before the first step."""
         if process_group is not None:
             raise ValueError("LRURec: single GPU only")
 
+    def _stream_seed(self):
+        return (self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF
+
     def set_seed(self, seed: int, rank: int = 0):
-        """Seed of the dropout draws (rank-decorrelated)."""
+        """Seed of the dropout draws (rank-decorrelated): of the torch generator and of the fused step's device state, whose
+        step counter goes back to 0."""
         self._seed, self._rank, self._gen = int(seed), int(rank), None
+        if self._fused is not None:
+            self._fused["state"][0] = self._stream_seed()
+            self._fused["state"][1] = 0
 
     def _generator(self, device):
         if self._gen is None or self._gen.device != device:
             self._gen = torch.Generator(device=device)
-            self._gen.manual_seed((self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF)
+            self._gen.manual_seed(self._stream_seed())
         return self._gen
 
     def _drop(self, x, train):
@@ -350,8 +435,81 @@ class LRURecModel(nn.Module):
         self._require_gpu(input_ids)
         return self.catalogue_ce(self.forward(input_ids)[:, -1, :], answers)
 
+    # ---- the fused step (lru_step = "fused"; bsarec_lrurec_loss_grad / bsarec_lrurec_train_step; host side: _fused_step.py) ----
+    def _step_buffers(self):
+        """What the fused step owns beside the parameters: the device step state (seed, step counter, Adam t), both gradient
+        arrays, the Adam moments of the item table ("E") and of the flat weight array ("W"), and per batch shape a workspace,
+        static id buffers and a captured graph.  Built on first use; dropped by ``.to()`` / ``reflatten()`` (a new parameter
+        storage)."""
+        if self.lru_step != "fused":
+            raise RuntimeError("LRURec steps through calculate_loss / backward / torch.optim.Adam (Trainer does); "
+                               "the one-call step needs lru_step = 'fused'")
+        self._require_gpu()
+        self.reflatten()
+        E, flat = self.item_embeddings.weight.data, self._wflat
+        if flat.device != E.device or not E.is_contiguous() or E.dtype != torch.float32:
+            raise RuntimeError("lrurec: the item table and the flat weight array must be contiguous fp32 on one device")
+        self._fused = FS.buffers(self._fused, [("E", E), ("W", flat)], self._stream_seed())
+        return self._fused
+
+    @property
+    def step_state(self) -> torch.Tensor:
+        """The fused step's device state, int64[8]: [0] the Philox seed, [1] the step counter of the dropout stream, [2] Adam's t."""
+        return self._step_buffers()["state"]
+
+    def _slot(self, f, B: int, Lq: int):
+        s = f["slots"].get((B, Lq))
+        if s is None:
+            cfg = L.LruRecConfig(L.LruConfig(B, Lq, self.LayerNorm.weight.shape[0]), len(self.item_encoder.blocks),
+                                 self.item_embeddings.num_embeddings, self.p_hidden, self.LayerNorm.eps)
+            nbytes = L.load().bsarec_lrurec_workspace_bytes(cfg)
+            if nbytes < 0:
+                raise ValueError(f"lrurec: unsupported step shape B = {B}, L = {Lq}, N = {cfg.layers}, dropout = {self.p_hidden} "
+                                 f"(1 <= B <= 65536, 1 <= L <= 256, 1 <= N <= {L.MAX_LAYERS}, 0 <= p < 1)")
+            s = FS.slot(f, (B, Lq), cfg, nbytes, (B, Lq))           # the slot's ``neg`` buffer stays unused
+        return s
+
+    def _fill(self, s, input_ids, answers):
+        self._require_gpu(input_ids)
+        s["ids"].copy_(input_ids)
+        s["ans"].copy_(answers.reshape(-1))
+        return s
+
+    def _loss_grad(self, f, s, train: bool):
+        L.check(L.load().bsarec_lrurec_loss_grad(s["cfg"], f["E"].data_ptr(), f["W"].data_ptr(), s["ids"].data_ptr(),
+                                                 s["ans"].data_ptr(), f["state"].data_ptr(), int(train), s["loss"].data_ptr(),
+                                                 f["dE"].data_ptr(), f["dW"].data_ptr(), s["ws"].data_ptr(), s["nbytes"],
+                                                 FS.stream(f)), "bsarec_lrurec_loss_grad")
+
+    def loss_and_grads(self, input_ids, answers, train: bool = False):
+        """The loss (0-d tensor) and {state_dict key: gradient} of one batch through bsarec_lrurec_loss_grad, no update.
+        ``train``: draw the next dropout masks of the device stream (the step counter advances); else no dropout."""
+        f = self._step_buffers()
+        s = self._fill(self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1])), input_ids, answers)
+        self._loss_grad(f, s, train)
+        grads = OrderedDict([("item_embeddings.weight", f["dE"].clone())])
+        for name, (o, n, shp) in self._wslices.items():
+            grads[name] = f["dW"][o:o + n].view(shp).clone()
+        return s["loss"].clone(), grads
+
+    def _train_step(self, f, s):
+        items, weights = FS.adam_structs(f, self.args)
+        L.check(L.load().bsarec_lrurec_train_step(s["cfg"], s["ids"].data_ptr(), s["ans"].data_ptr(), items, weights,
+                                                  f["state"].data_ptr(), s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"],
+                                                  FS.stream(f)), "bsarec_lrurec_train_step")
+
     def train_step(self, input_ids, answers, neg_answers=None, same_target=None):
-        raise RuntimeError("LRURec steps through calculate_loss / backward / torch.optim.Adam (Trainer does)")
+        """lru_step = "fused": one optimisation step in one C call -- the step counter, lookup + LayerNorm + Philox dropout, the
+        blocks, the CE head, every gradient, Adam (``args.lr``, ``adam_beta1``, ``adam_beta2``, ``weight_decay``) on the item
+        table and on the flat weight array, in place.  Returns the mean loss as a 0-d device tensor (no host sync; the next step
+        overwrites it).  The call is captured once per batch shape over static id buffers and replayed -- the masks and Adam's t
+        advance on the device, and the capture is one linear chain on one stream, so it has no parallel branches to replay;
+        ``args.lru_step_graph = False`` calls eagerly instead.  ``neg_answers`` and ``same_target`` are ignored."""
+        if self.lru_step != "fused":
+            raise RuntimeError("LRURec steps through calculate_loss / backward / torch.optim.Adam (Trainer does)")
+        f = self._step_buffers()
+        s = self._fill(self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1])), input_ids, answers)
+        return FS.train_step(f, s, self.args, getattr(self.args, "lru_step_graph", True), self._loss_grad, self._train_step)
 
     def grad_step(self, input_ids, answers, neg_answers=None):
         raise RuntimeError("LRURec steps through calculate_loss / backward / torch.optim.Adam (Trainer does)")

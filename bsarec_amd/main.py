@@ -272,6 +272,10 @@ def parse_args(argv=None):
                    help="LRURec: smallest initial |lambda|, 0 <= r_min < r_max (default 0.8)")
     p.add_argument("--lru_r_max", default=argparse.SUPPRESS, type=radius_value,
                    help="LRURec: largest initial |lambda|, r_min < r_max < 1 (default 0.99)")
+    p.add_argument("--lru_step", default=argparse.SUPPRESS, choices=("torch", "fused"),
+                   help="LRURec: step through autograd and torch.optim.Adam (default) or through the one-call HIP step "
+                        "(lookup, LayerNorms, recurrent layers, feed-forward nets with Philox dropout, CE head, item-table "
+                        "gradient and Adam in the library)")
     args = p.parse_args(argv)
     if not getattr(args, "lru_r_min", 0.8) < getattr(args, "lru_r_max", 0.99):
         p.error("--lru_r_min / --lru_r_max: expected 0 <= r_min < r_max < 1")

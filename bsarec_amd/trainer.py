@@ -563,6 +563,8 @@ class Trainer:
     def iteration(self, epoch, dataloader, train=True):
         pairwise = getattr(self.model, "needs_negatives", False)       # sibling models with a pos / neg loss head (SASRec)
         pairwise = pairwise or getattr(self.model, "torch_optim", False)
+        own_step = getattr(self.model, "own_train_step", False)        # the model's one-call step on (input_ids, answers): LRURec fused
+        pairwise = pairwise or own_step                                # ... which, like those, takes the batch loop below
         if train and isinstance(dataloader, DeviceBatches) and not pairwise:
             self.model.train()
             loss_sum, nb = self._epoch_indexed(dataloader)
@@ -598,6 +600,8 @@ class Trainer:
                         self._allreduce_param_grads()
                     self._torch_opt.step()
                     loss = loss.detach()
+                elif own_step:                      # the model steps itself (and replays its own graph: none is captured here)
+                    loss = self.model.train_step(input_ids, answers)
                 elif pairwise:
                     if self.dp:                     # sibling models with a pos / neg head: local gradients, one exchange, Adam
                         loss = self.model.grad_step(input_ids, answers, neg_answers)

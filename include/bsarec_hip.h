@@ -978,6 +978,67 @@ int bsarec_lru_fwd(const bsarec_lru_config_t *cfg, const float *x, const int64_t
 int bsarec_lru_bwd(const bsarec_lru_config_t *cfg, const float *x, const int64_t *ids, const float *weights, const float *dy,
                    void *workspace, long workspace_bytes, float *dx, float *dweights, void *stream);
 
+/* One LRURec training step (csrc/lrurec_step.h): with E = item_emb [V, d], T = B L rows and N = layers blocks,
+ *   x_0 = Drop_0(LN(E[ids])),
+ *   per block k < N:  z = LRU_k(x_k, ids) (bsarec_lru_fwd),  a = LN(Drop_{1+2k}(z) + x_k),
+ *                     x_{k+1} = LN(Drop_{2+2k}(dense_2(gelu(dense_1(a)))) + a)       (4 d inner, the erf gelu),
+ *   loss = mean_b cross_entropy(x_N[b, L - 1] . E^T, answers_b)                      (bsarec_ce_head_fwd with ldh = L d),
+ * LayerNorm TF style with ln_eps inside the root.  Id 0 is an ordinary table row (nn.Embedding without padding_idx); it is masked
+ * only inside the recurrent layer.  bsarec_lrurec_loss_grad writes the loss (one float) and the gradient of every parameter:
+ * d_item_emb [V, d] -- the CE head's dense dE, which overwrites every row, plus the T lookup rows dE[ids[b, t]] += de[b, t] -- and
+ * dweights in the layout of weights.
+ *   `weights` is ONE flat fp32 array in the model's state_dict order, every tensor at a multiple of 4 floats:
+ *   LayerNorm.weight [d] | LayerNorm.bias [d], then per block the 4 d d + 6 d array of bsarec_lru_fwd | lru.LayerNorm.weight,
+ *   .bias [d] | dense_1.weight [4d, d] | dense_1.bias [4d] | dense_2.weight [d, 4d] | dense_2.bias [d] |
+ *   feed_forward.LayerNorm.weight, .bias [d];  bsarec_lrurec_weight_floats is their sum, 2 d + N (12 d d + 15 d).
+ *   Dropout is the library's Philox stream: site 0 on the embeddings, 1 + 2 k behind block k's recurrent layer, 2 + 2 k behind
+ * its dense_2; element index row d + c (oracle dropout_keep(B L d, p, seed, step, site)), keyed by the device-resident step state
+ * (`state`: u64[8], [0] = seed, [1] = forward-step counter, [2] = Adam t, [3..6] owned by the library).  A call with train != 0
+ * advances the step counter FIRST and draws with the new value; train = 0 draws nothing (the result of dropout = 0) and touches
+ * no counter.  Masks are regenerated in the backward, not stored.
+ *   Backward: the gradient entering the top block is the head's dh at position L - 1 and zero elsewhere; per block the
+ * feed-forward LayerNorm, du with the gelu' epilogue, da with the residual gradient added in the epilogue, dW1, dW2 and both bias
+ * gradients as split-K TN products whose slabs are added in slice order (dW2 takes gelu(u) on load), the LayerNorm behind the
+ * recurrent layer, bsarec_lru_bwd -- its dweights go straight into the block's slice of the flat gradient -- and dx = its dx + the
+ * residual gradient.  Every LayerNorm's d(weight), d(bias) partials are added in one fixed order.  The lookup rows are summed in
+ * 64-bit fixed point (2^-40 units, exact while |sum| < 2^22) and added onto the head's dE by one flush: every output is
+ * bit-deterministic and does not depend on the order in which rows arrive.
+ *   bsarec_lrurec_train_step is the above with train = 1 followed by Adam on both arrays, Adam's t advanced ONCE:
+ * adam_items->params / grads are E / dE with n = V d, adam_weights->params / grads the flat array and its gradient with
+ * n = bsarec_lrurec_weight_floats(cfg); grads are written, then read.  lr, beta1 and beta2 of the two must agree (one t and one
+ * pair of bias corrections serve both); shadow_bf16, grads2, grads2_n, n_grad_srcs and wimage_plan must be null / 0.
+ *   Launches, all on `stream`, one after the other: 11 + 28 N for a loss and its gradients (the step counter adds one when
+ * train != 0), then one Adam launch per array -- 70 for a training step at N = 2.  No allocation, no host synchronisation, no float
+ * atomics, static or launch-sized LDS: capturable, and a replay of a captured bsarec_lrurec_train_step is the NEXT step -- fresh
+ * masks, the next t.  The result does not depend on what the workspace holds on entry.
+ *   Workspace: bsarec_lrurec_workspace_bytes(cfg) bytes (host-only query, no HIP call).  In floats, with T = L B and T4 = T
+ * rounded up to 4: one [4] | xhat0 [T, d] | rstd0 [T4] | x_0 .. x_N [N + 1][T, d] | z [T, d] | per block: the workspace of
+ * bsarec_lru_fwd(train = 1), a [T, d], xhat_a [T, d], rstd_a [T4], u [T, 4d], xhat_f [T, d], rstd_f [T4] | dy, dz, dt [T, d] each |
+ * du [T, 4d] | da, dxl [T, d] each | dh [B, d] | the workspace of bsarec_ce_head_fwd | slabs of dW1 [ns][4d, d], of dW2
+ * [ns][d, 4d], of db1 [ns][4d], of db2 [ns][d] (ns split-K slices, a function of T) | LayerNorm partials [2 N + 1][2][nb][d]
+ * (nb <= 256) | the accumulator, V d 64-bit words.
+ *   Limits (else < 0 before any HIP call): cfg->lru inside the limits of bsarec_lru_workspace_bytes; 1 <= layers <=
+ * BSAREC_MAX_LAYERS; item_size >= 2; 0 <= dropout < 1 and ln_eps > 0 (NaN refused); every pointer non-null; the float arrays
+ * (Adam's four included) and the workspace 16-byte aligned, ids / answers / state 8-byte, loss_out 4-byte; workspace_bytes at
+ * least the queried size; adam_*->n as above.  ids and answers inside [0, V) are the caller's contract (an id outside is never
+ * dereferenced: its table row reads as zeros and its gradient row is dropped).  Outputs may not alias inputs, each other or the
+ * workspace. */
+typedef struct {
+    bsarec_lru_config_t lru;           /* batch B, seq_len L, width d: the limits of bsarec_lru_workspace_bytes */
+    int layers;                        /* N, 1 .. BSAREC_MAX_LAYERS */
+    int item_size;                     /* V >= 2 */
+    float dropout;                     /* p in [0, 1), NaN refused */
+    float ln_eps;                      /* > 0; 1e-12 in the model */
+} bsarec_lrurec_config_t;
+long bsarec_lrurec_weight_floats(const bsarec_lrurec_config_t *cfg);
+long bsarec_lrurec_workspace_bytes(const bsarec_lrurec_config_t *cfg);
+int bsarec_lrurec_loss_grad(const bsarec_lrurec_config_t *cfg, const float *item_emb, const float *weights,
+                            const int64_t *ids, const int64_t *answers, void *state, int train, float *loss_out,
+                            float *d_item_emb, float *dweights, void *workspace, long workspace_bytes, void *stream);
+int bsarec_lrurec_train_step(const bsarec_lrurec_config_t *cfg, const int64_t *ids, const int64_t *answers,
+                             const bsarec_adam_t *adam_items, const bsarec_adam_t *adam_weights, void *state,
+                             float *loss_out, void *workspace, long workspace_bytes, void *stream);
+
 /* Tag kernel launches of one id with hipEvents for in-process roofline timing (bench.py):
  * when set, every launch of kernel class `kclass` (see BSAREC_K_*) on the next calls of THIS plan is bracketed
  * by hipEventRecord on the launch stream; bsarec_profile_read returns the summed milliseconds and
