@@ -11,5 +11,6 @@ from .caser import CaserModel  # noqa: F401
 from .bert4rec import BERT4RecModel  # noqa: F401
 from .fearec import FEARecModel, FeaAttention  # noqa: F401
 from .lrurec import LRURecModel, LruLayer  # noqa: F401
+from .mamba4rec import Mamba4RecModel, MambaLayer  # noqa: F401
 
-__all__ = ["BSARecModel", "SASRecModel", "FMLPRecModel", "DuoRecModel", "GRU4RecModel", "CaserModel", "BERT4RecModel", "FEARecModel", "FeaAttention", "MODEL_DICT", "param_shapes", "LRURecModel", "LruLayer"]
+__all__ = ["BSARecModel", "SASRecModel", "FMLPRecModel", "DuoRecModel", "GRU4RecModel", "CaserModel", "BERT4RecModel", "FEARecModel", "FeaAttention", "MODEL_DICT", "param_shapes", "LRURecModel", "LruLayer", "Mamba4RecModel", "MambaLayer"]

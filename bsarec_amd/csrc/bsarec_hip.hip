@@ -27,6 +27,7 @@
 #include "caser_user.h"
 #include "fea_attn.h"
 #include "lru.h"
+#include "mamba.h"
 #include "lrurec_step.h"
 
 #include <hip/hip_runtime.h>
@@ -2756,6 +2757,198 @@ extern "C" int bsarec_lru_bwd(const bsarec_lru_config_t* cfg, const float* x, co
     RET(gru_tn(w + ws.g, 2 * d, x, 2 * d, d, T, slab, 2L * d * d, 0, w + ws.bpart, s));
     gru_sum(slab, T, 2L * d * d, dweights + wo.win, s);
     gru_sum(w + ws.bpart, T, 2 * d, dweights + wo.bin, s);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Selective state-space layer (mamba.h): plan-less, one linear chain on the caller's stream, no allocation
+// ---------------------------------------------------------------------------------------------
+static int mamba_check(const bsarec_mamba_config_t* c) {
+    if (!c) return -10;
+    if (c->batch < 1 || c->batch > 65536 || c->seq_len < 1 || c->seq_len > 256) return -10;
+    if (!row_dim_ok(c->width)) return -10;
+    if (c->expand < 1 || c->expand > 2) return -10;
+    if (c->d_state != 4 && c->d_state != 8 && c->d_state != 16 && c->d_state != 32) return -10;
+    if (c->d_conv < 2 || c->d_conv > 4) return -10;
+    if (c->dt_rank < 4 || c->dt_rank > 64 || c->dt_rank % 4) return -10;
+    return 0;
+}
+
+// offsets (floats) into the flat weight array: in_proj.weight [2 di][d] | conv1d.weight [di][K] | conv1d.bias [di] |
+// x_proj.weight [R + 2N][di] | dt_proj.weight [di][R] | dt_proj.bias [di] | A_log [di][N] | D [di] | out_proj.weight [d][di]
+struct MambaW { long win, wconv, bconv, wx, wdt, bdt, alog, dd, wout, total; };
+static MambaW mamba_weights(const bsarec_mamba_config_t& c) {
+    const long d = c.width, di = d * c.expand, N = c.d_state, K = c.d_conv, R = c.dt_rank;
+    MambaW w;
+    w.win = 0; w.wconv = w.win + 2 * di * d; w.bconv = w.wconv + di * K; w.wx = w.bconv + di; w.wdt = w.wx + (R + 2 * N) * di;
+    w.bdt = w.wdt + di * R; w.alog = w.bdt + di; w.dd = w.alog + di * N; w.wout = w.dd + di; w.total = w.wout + d * di;
+    return w;
+}
+
+// Workspace, in floats (every region a multiple of 4), T = B L: xz [T][2 di] | u [T][di] | delta [T][R] | bc [T][2N] |
+// dt [T][di] | y [T][di] | c [T][di] | s [T][di] | checkpoints [B][nck][di][N] | dy, du_scan, du_proj, ddt [T][di] each |
+// dxz [T][2 di] | dxdbl [T][R + 2N] | dB dC partials [slices][T][2N] | dA_log dD partials [G][di N + di] |
+// convolution partials [conv workgroups][di K + di] | slabs [ns][largest weight] | bias partials [ns][di]; everything behind y
+// in training only
+struct MambaWs {
+    long xz, u, delta, bc, dt, y, c, s, hck, dy, du1, du2, ddt, dxz, dxdbl, bcp, adp, cvp, slab, bpart, total, slab_floats;
+    int ns, nck, nslice, groups, conv_rows, conv_wgs;
+};
+static MambaWs mamba_ws(const bsarec_mamba_config_t& c, bool train) {
+    const long T = (long)c.batch * c.seq_len, d = c.width, di = d * c.expand, N = c.d_state, K = c.d_conv, R = c.dt_rank;
+    MambaWs w;
+    memset(&w, 0, sizeof(w));
+    int kc;
+    gru_split(T, &w.ns, &kc);
+    w.nck = cdiv(c.seq_len, MAMBA_CK) - 1;
+    w.nslice = cdiv((int)di, MAMBA_THREADS / (int)N);
+    w.groups = c.batch < 1024 ? c.batch : 1024;
+    w.conv_rows = cdiv(T, 1024L);                     // at most 1024 partial rows
+    w.conv_wgs = (int)cdiv(T, (long)w.conv_rows);
+    long off = 0;
+    w.xz = off; off += T * 2 * di;
+    w.u = off; off += T * di;
+    w.delta = off; off += T * R;
+    w.bc = off; off += T * 2 * N;
+    w.dt = off; off += T * di;
+    w.y = off; off += T * di;
+    if (train) {
+        w.c = off; off += T * di;
+        w.s = off; off += T * di;
+        w.hck = off; off += (long)c.batch * w.nck * di * N;
+        w.dy = off; off += T * di;
+        w.du1 = off; off += T * di;
+        w.du2 = off; off += T * di;
+        w.ddt = off; off += T * di;
+        w.dxz = off; off += T * 2 * di;
+        w.dxdbl = off; off += T * (R + 2 * N);
+        w.bcp = off; off += w.nslice * T * 2 * N;
+        w.adp = off; off += w.groups * (di * N + di);
+        w.cvp = off; off += w.conv_wgs * (di * K + di);
+        w.slab_floats = 2 * di * d;
+        if ((R + 2 * N) * di > w.slab_floats) w.slab_floats = (R + 2 * N) * di;
+        w.slab = off; off += w.ns * w.slab_floats;
+        w.bpart = off; off += w.ns * di;
+    }
+    w.total = off;
+    return w;
+}
+
+extern "C" long bsarec_mamba_weight_floats(const bsarec_mamba_config_t* cfg) {
+    if (mamba_check(cfg)) return -10;
+    return mamba_weights(*cfg).total;
+}
+
+extern "C" long bsarec_mamba_workspace_bytes(const bsarec_mamba_config_t* cfg, int train) {
+    if (mamba_check(cfg)) return -10;
+    return mamba_ws(*cfg, train != 0).total * (long)sizeof(float);
+}
+
+struct MambaSpan { const void* p; long bytes; };
+static bool mamba_overlap(const MambaSpan& a, const MambaSpan& b) {
+    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    return a0 < b0 + (uintptr_t)b.bytes && b0 < a0 + (uintptr_t)a.bytes;
+}
+// every pointer non-null and 16-byte aligned, the workspace large enough, and none of the first `nout` spans (the outputs)
+// overlapping any other span
+static int mamba_args(const bsarec_mamba_config_t* cfg, bool train, long workspace_bytes, const MambaSpan* spans, int n, int nout) {
+    RET(mamba_check(cfg));
+    for (int i = 0; i < n; ++i)
+        if (!aligned_to(spans[i].p, 16)) return -10;
+    if (workspace_bytes < mamba_ws(*cfg, train).total * (long)sizeof(float)) return -10;
+    for (int i = 0; i < nout; ++i)
+        for (int k = 0; k < n; ++k)
+            if (k != i && mamba_overlap(spans[i], spans[k])) return -10;
+    return 0;
+}
+
+#define MAMBA_DISPATCH(N, KERNEL, ...) \
+    switch (N) { \
+        case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break; \
+        case 8: hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__); break; \
+        case 16: hipLaunchKernelGGL(KERNEL<16>, __VA_ARGS__); break; \
+        default: hipLaunchKernelGGL(KERNEL<32>, __VA_ARGS__); break; \
+    }
+
+extern "C" int bsarec_mamba_fwd(const bsarec_mamba_config_t* cfg, const float* x, const int64_t* ids, const float* weights, int train,
+                                float* out, void* workspace, long workspace_bytes, void* stream) {
+    RET(mamba_check(cfg));
+    const bsarec_mamba_config_t& c = *cfg;
+    const int B = c.batch, L = c.seq_len, d = c.width, di = d * c.expand, N = c.d_state, K = c.d_conv, R = c.dt_rank;
+    const long T = (long)B * L, fb = sizeof(float);
+    const MambaW wo = mamba_weights(c);
+    const MambaSpan spans[] = {{out, T * d * fb}, {workspace, workspace_bytes}, {x, T * d * fb}, {weights, wo.total * fb}};
+    RET(mamba_args(cfg, train != 0, workspace_bytes, spans, 4, 2));
+    const MambaWs ws = mamba_ws(c, train != 0);
+    float* w = (float*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    RET(gru_nt(x, weights + wo.win, (int)T, 2 * di, d, gru_epi(w + ws.xz, 2 * di), s));
+    MambaConvP C;
+    memset(&C, 0, sizeof(C));
+    C.XZ = w + ws.xz; C.ids = ids; C.W = weights + wo.wconv; C.C = train ? w + ws.c : nullptr; C.U = w + ws.u;
+    C.T = T; C.L = L; C.di = di; C.K = K;
+    hipLaunchKernelGGL(mamba_conv_fwd_kernel, dim3((unsigned)cdiv(T * (di / 4), 256L)), dim3(256), 0, s, C);
+    RET(gru_nt(w + ws.u, weights + wo.wx, (int)T, R, di, gru_epi(w + ws.delta, R), s));
+    RET(gru_nt(w + ws.u, weights + wo.wx + (long)R * di, (int)T, 2 * N, di, gru_epi(w + ws.bc, 2 * N), s));
+    RET(gru_nt(w + ws.delta, weights + wo.wdt, (int)T, di, R, gru_epi(w + ws.dt, di, weights + wo.bdt), s));
+    MambaScanP P;
+    memset(&P, 0, sizeof(P));
+    P.XZ = w + ws.xz; P.U = w + ws.u; P.DTR = w + ws.dt; P.BC = w + ws.bc; P.Alog = weights + wo.alog; P.D = weights + wo.dd;
+    P.ids = ids; P.Y = w + ws.y; P.S = train ? w + ws.s : nullptr; P.HCK = train && ws.nck > 0 ? w + ws.hck : nullptr;
+    P.B = B; P.L = L; P.di = di; P.nck = ws.nck;
+    MAMBA_DISPATCH(N, mamba_scan_fwd_kernel, dim3(B, ws.nslice), dim3(MAMBA_THREADS), 0, s, P);
+    RET(gru_nt(w + ws.y, weights + wo.wout, (int)T, d, di, gru_epi(out, d), s));
+    return (int)hipGetLastError();
+}
+
+extern "C" int bsarec_mamba_bwd(const bsarec_mamba_config_t* cfg, const float* x, const int64_t* ids, const float* weights,
+                                const float* dout, void* workspace, long workspace_bytes, float* dx, float* dweights, void* stream) {
+    RET(mamba_check(cfg));
+    const bsarec_mamba_config_t& c = *cfg;
+    const int B = c.batch, L = c.seq_len, d = c.width, di = d * c.expand, N = c.d_state, K = c.d_conv, R = c.dt_rank, X = R + 2 * N;
+    const long T = (long)B * L, fb = sizeof(float);
+    const MambaW wo = mamba_weights(c);
+    const MambaSpan spans[] = {{dx, T * d * fb}, {dweights, wo.total * fb}, {workspace, workspace_bytes}, {x, T * d * fb},
+                               {weights, wo.total * fb}, {dout, T * d * fb}};
+    RET(mamba_args(cfg, true, workspace_bytes, spans, 6, 3));
+    const MambaWs ws = mamba_ws(c, true);
+    float* w = (float*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    float* slab = w + ws.slab;
+    // dy = dout . W_out;  dW_out = dout^T . y
+    RET(gru_nn(dout, weights + wo.wout, (int)T, di, d, gru_epi(w + ws.dy, di), s));
+    RET(gru_tn(dout, d, w + ws.y, d, di, T, slab, (long)d * di, 0, nullptr, s));
+    gru_sum(slab, T, (long)d * di, dweights + wo.wout, s);
+    MambaScanP P;
+    memset(&P, 0, sizeof(P));
+    P.XZ = w + ws.xz; P.U = w + ws.u; P.DTR = w + ws.dt; P.BC = w + ws.bc; P.Alog = weights + wo.alog; P.D = weights + wo.dd;
+    P.ids = ids; P.S = w + ws.s; P.HCK = w + ws.hck; P.DY = w + ws.dy; P.DU = w + ws.du1; P.DDT = w + ws.ddt; P.DXZ = w + ws.dxz;
+    P.BCP = w + ws.bcp; P.ADP = w + ws.adp; P.B = B; P.L = L; P.di = di; P.nck = ws.nck;
+    MAMBA_DISPATCH(N, mamba_scan_bwd_kernel, dim3(ws.groups, ws.nslice), dim3(MAMBA_THREADS), 0, s, P);
+    hipLaunchKernelGGL(mamba_rows_sum_kernel, dim3((di * N + di) / 4), dim3(256), 0, s, w + ws.adp, ws.groups, (long)di * N + di,
+                       dweights + wo.alog);
+    // dxdbl = [ddt . W_dt | dB | dC];  dW_dt = ddt^T . delta, db_dt = its column sums
+    RET(gru_nn(w + ws.ddt, weights + wo.wdt, (int)T, R, di, gru_epi(w + ws.dxdbl, X), s));
+    hipLaunchKernelGGL(mamba_bc_sum_kernel, dim3((unsigned)cdiv(T * (2 * N / 4), 256L)), dim3(256), 0, s, w + ws.bcp, ws.nslice, T,
+                       2 * N, w + ws.dxdbl, X, R);
+    RET(gru_tn(w + ws.ddt, di, w + ws.delta, di, R, T, slab, (long)di * R, 0, w + ws.bpart, s));
+    gru_sum(slab, T, (long)di * R, dweights + wo.wdt, s);
+    gru_sum(w + ws.bpart, T, di, dweights + wo.bdt, s);
+    // du_proj = dxdbl . W_x;  dW_x = dxdbl^T . u
+    RET(gru_nn(w + ws.dxdbl, weights + wo.wx, (int)T, di, X, gru_epi(w + ws.du2, di), s));
+    RET(gru_tn(w + ws.dxdbl, X, w + ws.u, X, di, T, slab, (long)X * di, 0, nullptr, s));
+    gru_sum(slab, T, (long)X * di, dweights + wo.wx, s);
+    MambaConvP C;
+    memset(&C, 0, sizeof(C));
+    C.XZ = w + ws.xz; C.ids = ids; C.W = weights + wo.wconv; C.C = w + ws.c; C.DU1 = w + ws.du1; C.DU2 = w + ws.du2;
+    C.DXZ = w + ws.dxz; C.part = w + ws.cvp; C.T = T; C.L = L; C.di = di; C.K = K; C.rows = ws.conv_rows;
+    hipLaunchKernelGGL(mamba_conv_bwd_kernel, dim3(ws.conv_wgs), dim3(256), 0, s, C);
+    hipLaunchKernelGGL(mamba_rows_sum_kernel, dim3((di * K + di) / 4), dim3(256), 0, s, w + ws.cvp, ws.conv_wgs, (long)di * K + di,
+                       dweights + wo.wconv);
+    // dx = dxz . W_in;  dW_in = dxz^T . x
+    RET(gru_nn(w + ws.dxz, weights + wo.win, (int)T, d, 2 * di, gru_epi(dx, d), s));
+    RET(gru_tn(w + ws.dxz, 2 * di, x, 2 * di, d, T, slab, 2L * di * d, 0, nullptr, s));
+    gru_sum(slab, T, 2L * di * d, dweights + wo.win, s);
     return (int)hipGetLastError();
 }
 

@@ -36,7 +36,8 @@ SIBLING_MODELS = {"bert4rec": BERT4RecModel}
 # key set, so the next sibling adds a key here
 from .fearec import FEARecModel
 from .lrurec import LRURecModel
-MODEL_REGISTRY = {"fearec": FEARecModel, "lrurec": LRURecModel}
+from .mamba4rec import Mamba4RecModel
+MODEL_REGISTRY = {"fearec": FEARecModel, "lrurec": LRURecModel, "mamba4rec": Mamba4RecModel}
 from .trainer import Trainer
 
 
@@ -82,6 +83,19 @@ def radius_value(text: str) -> float:
     if not 0.0 <= r < 1.0:                                                       # (NaN fails)
         raise argparse.ArgumentTypeError(f"{r} outside [0, 1)")
     return r
+
+
+def int_choice(what: str, allowed):
+    """--mamba_d_state / --mamba_d_conv / --mamba_expand / --mamba_dt_rank: an integer out of ``allowed``."""
+    def parse(text: str) -> int:
+        try:
+            v = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not an integer: {text!r}") from None
+        if v not in allowed:
+            raise argparse.ArgumentTypeError(f"{v}: expected {what}")
+        return v
+    return parse
 
 
 def bool_value(text: str) -> bool:
@@ -276,6 +290,15 @@ def parse_args(argv=None):
                    help="LRURec: step through autograd and torch.optim.Adam (default) or through the one-call HIP step "
                         "(lookup, LayerNorms, recurrent layers, feed-forward nets with Philox dropout, CE head, item-table "
                         "gradient and Adam in the library)")
+    # not reference-checked flags: the state-space layer of Mamba4Rec (--model_type Mamba4Rec).  Absent unless given
+    p.add_argument("--mamba_d_state", default=argparse.SUPPRESS, type=int_choice("4, 8, 16 or 32", (4, 8, 16, 32)),
+                   help="Mamba4Rec: states per channel, 4, 8, 16 or 32 (default 16)")
+    p.add_argument("--mamba_d_conv", default=argparse.SUPPRESS, type=int_choice("2..4", range(2, 5)),
+                   help="Mamba4Rec: taps of the causal depthwise convolution, 2..4 (default 4)")
+    p.add_argument("--mamba_expand", default=argparse.SUPPRESS, type=int_choice("1 or 2", (1, 2)),
+                   help="Mamba4Rec: d_inner / hidden_size, 1 or 2 (default 2)")
+    p.add_argument("--mamba_dt_rank", default=argparse.SUPPRESS, type=int_choice("a multiple of 4 in 4..64", range(4, 65, 4)),
+                   help="Mamba4Rec: rank of the step-size projection, a multiple of 4 in 4..64 (default 4 ceil(hidden_size / 64))")
     args = p.parse_args(argv)
     if not getattr(args, "lru_r_min", 0.8) < getattr(args, "lru_r_max", 0.99):
         p.error("--lru_r_min / --lru_r_max: expected 0 <= r_min < r_max < 1")

@@ -978,6 +978,42 @@ int bsarec_lru_fwd(const bsarec_lru_config_t *cfg, const float *x, const int64_t
 int bsarec_lru_bwd(const bsarec_lru_config_t *cfg, const float *x, const int64_t *ids, const float *weights, const float *dy,
                    void *workspace, long workspace_bytes, float *dx, float *dweights, void *stream);
 
+/* Selective state-space layer of the Mamba4Rec sibling model (csrc/mamba.h): with x [B, L, d] (d = width), d_inner = expand d,
+ * N = d_state, K = d_conv, R = dt_rank, ids [B, L] (int64, 0 is padding; a null pointer means no padding) and
+ * m_t = (ids[b, t] != 0),
+ *   [xs_t | z_t] = in_proj.weight x_t,
+ *   c_t[j] = conv1d.bias[j] + sum_{k<K} conv1d.weight[j, k] (m_s xs_s[j]), s = t - K + 1 + k, terms with s < 0 are 0,
+ *   u_t = silu(c_t),  [delta_t | B_t | C_t] = x_proj.weight u_t,  Delta_t = softplus(dt_proj.weight delta_t + dt_proj.bias),
+ *   A = -exp(A_log),
+ *   m_t = 1: h_t[j, n] = exp(Delta_t[j] A[j, n]) h_{t-1}[j, n] + Delta_t[j] B_t[n] u_t[j];  m_t = 0: h_t = h_{t-1};  h_{-1} = 0,
+ *   s_t[j] = sum_n C_t[n] h_t[j, n] + D[j] u_t[j],  y_t = m_t ? s_t silu(z_t) : 0,  out_t = out_proj.weight y_t, out [B, L, d].
+ * `weights` is ONE flat fp32 array, every tensor at a multiple of 4 floats: in_proj.weight [2 d_inner, d] | conv1d.weight
+ * [d_inner, K] | conv1d.bias [d_inner] | x_proj.weight [R + 2N, d_inner] | dt_proj.weight [d_inner, R] | dt_proj.bias [d_inner] |
+ * A_log [d_inner, N] | D [d_inner] | out_proj.weight [d, d_inner]; bsarec_mamba_weight_floats is their sum.  bsarec_mamba_bwd is
+ * the true derivative: every float of dx [B, L, d] and of dweights (the layout of weights) is overwritten.  It reads what
+ * bsarec_mamba_fwd(train = 1) left in the SAME workspace with the same cfg, ids and weights: the [B, L, .] activations and the
+ * state after every 8th step (never the state of every step).  train = 0 keeps nothing and gives the same out, bit for bit.
+ *   The products run in the GEMM core (v_mfma_f32, split-K slabs added in slice order, dt_proj.bias's gradient as column sums),
+ * the convolution and the scan in csrc/mamba.h.  Padding is a selection: the state is exactly 0 until a sequence's first item, a
+ * padded position gives out = 0 and dx = 0 whatever x holds there and adds nothing to any weight gradient.  Every sum has one
+ * order that is a function of the shape alone: no atomics, equal bits on every run, and a sequence's out and dx do not depend on
+ * the batch or on its place in it.  Launches, all on `stream`, one after the other: forward 7, backward 18.  No allocation, no
+ * host synchronisation, static LDS only: capturable.
+ *   Workspace: bsarec_mamba_workspace_bytes(cfg, train) bytes (host-only query, no HIP call); train != 0 asks for no less.
+ *   Limits (else < 0 before any HIP call, nothing written): 1 <= batch <= 65536, 1 <= seq_len <= 256, width in 4 .. 256 and a
+ * multiple of 4, expand 1 or 2, d_state 4, 8, 16 or 32, d_conv in 2 .. 4, dt_rank a multiple of 4 in 4 .. 64; every float
+ * pointer non-null and 16-byte aligned; workspace_bytes at least the queried size; no output (out; dx, dweights) overlapping an
+ * input, the workspace or the other output.  Inputs are assumed finite. */
+typedef struct {
+    int batch, seq_len, width, expand, d_state, d_conv, dt_rank;
+} bsarec_mamba_config_t;
+long bsarec_mamba_weight_floats(const bsarec_mamba_config_t *cfg);
+long bsarec_mamba_workspace_bytes(const bsarec_mamba_config_t *cfg, int train);
+int bsarec_mamba_fwd(const bsarec_mamba_config_t *cfg, const float *x, const int64_t *ids, const float *weights, int train,
+                     float *out, void *workspace, long workspace_bytes, void *stream);
+int bsarec_mamba_bwd(const bsarec_mamba_config_t *cfg, const float *x, const int64_t *ids, const float *weights, const float *dout,
+                     void *workspace, long workspace_bytes, float *dx, float *dweights, void *stream);
+
 /* One LRURec training step (csrc/lrurec_step.h): with E = item_emb [V, d], T = B L rows and N = layers blocks,
  *   x_0 = Drop_0(LN(E[ids])),
  *   per block k < N:  z = LRU_k(x_k, ids) (bsarec_lru_fwd),  a = LN(Drop_{1+2k}(z) + x_k),
