@@ -21,9 +21,9 @@ from torch import nn
 
 from . import _fused_step as FS
 from . import _lib as L
+from ._sibling import _FlatLayer, _Holder, _SiblingModel, _layout, _no_cpu
 
 CASER_NH = (4, 8, 16, 32)
-_NO_CPU = "bsarec_amd runs on MI355X only: move the model and its input to the GPU (there is no CPU fallback)"
 
 
 def caser_param_shapes(seq_len: int, width: int, n_h: int, n_v: int) -> "OrderedDict[str, tuple]":
@@ -37,64 +37,10 @@ def caser_param_shapes(seq_len: int, width: int, n_h: int, n_v: int) -> "Ordered
 
 def caser_layout(seq_len: int, width: int, n_h: int, n_v: int):
     """({name: (offset, numel, shape)}, total floats): every tensor starts at a multiple of 4 floats (16 bytes)."""
-    slices, off = OrderedDict(), 0
-    for name, shp in caser_param_shapes(seq_len, width, n_h, n_v).items():
-        off = (off + 3) // 4 * 4
-        n = math.prod(shp)
-        slices[name] = (off, n, shp)
-        off += n
-    return slices, (off + 3) // 4 * 4
+    return _layout(caser_param_shapes(seq_len, width, n_h, n_v), 4)
 
 
-class _CaserFn(torch.autograd.Function):
-    """The convolution block as one autograd node over bsarec_caser_fwd / bsarec_caser_bwd, both on the current stream.  The
-    workspace carries the winning window of every cell to the backward: it is taken from the block's pool per shape and goes
-    back after the backward.  ``params`` are the views of the block's flat weight tensor; their gradients are views of one flat
-    ``dweights``."""
-
-    @staticmethod
-    def forward(ctx, conv, x, *params):
-        cfg, nbytes = conv._config(x, 1)
-        key = (x.shape[0], True, x.device)
-        pool = conv._pool.setdefault(key, [])
-        ws = pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        x = conv._operand(x)
-        z = torch.empty((x.shape[0], conv.out_features), dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        L.check(L.load().bsarec_caser_fwd(cfg, x.data_ptr(), conv._flat.data_ptr(), 1, z.data_ptr(), ws.data_ptr(), nbytes, stream),
-                "bsarec_caser_fwd")
-        ctx.save_for_backward(x)
-        ctx.conv, ctx.key, ctx.ws, ctx.call = conv, key, ws, (cfg, nbytes, conv._flat)
-        return z
-
-    @staticmethod
-    def backward(ctx, gz):
-        (x,) = ctx.saved_tensors
-        cfg, nbytes, flat = ctx.call
-        conv = ctx.conv
-        if ctx.ws is None:
-            raise RuntimeError("caser: backward ran twice (the forward's winning windows are gone)")
-        g = conv._operand(gz)
-        dx = torch.empty_like(x)
-        dw = torch.empty_like(flat)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        L.check(L.load().bsarec_caser_bwd(cfg, x.data_ptr(), flat.data_ptr(), g.data_ptr(), ctx.ws.data_ptr(), nbytes,
-                                          dx.data_ptr(), dw.data_ptr(), stream), "bsarec_caser_bwd")
-        conv._pool[ctx.key].append(ctx.ws)
-        ctx.ws = None
-        return (None, dx) + tuple(dw[o:o + n].view(shp) for o, n, shp in conv._slices.values())
-
-
-class _Conv(nn.Module):
-    """Holder of one filter bank's ``weight`` / ``bias``: views of the block's flat tensor (the convolution runs in
-    bsarec_caser_fwd)."""
-
-    def __init__(self, weight, bias):
-        super().__init__()
-        self.weight, self.bias = weight, bias
-
-
-class CaserConv(nn.Module):
+class CaserConv(_FlatLayer):
     """x [B, L, d] -> z [B, n_v d + n_h L] on the HIP kernels:
       z[b, c d + j]             = sum_t conv_v.weight[c, 0, t, 0] x[b, t, j] + conv_v.bias[c]
       z[b, n_v d + i n_h + f]   = max(0, max_t (sum_{r <= i, j} conv_h.{i}.weight[f, 0, r, j] x[b, t + r, j] + conv_h.{i}.bias[f]))
@@ -104,7 +50,10 @@ class CaserConv(nn.Module):
     multiple of 4 floats); ``conv_v.weight`` / ``conv_v.bias`` / ``conv_h.{i}.weight`` / ``conv_h.{i}.bias`` are parameters that
     are views of it with torch's Conv2d shapes, so a module of ``nn.Conv2d``s under those names loads this state_dict, and the
     reverse, and an optimiser that updates them in place updates the array the kernels read.  Init is torch's Conv2d default,
-    U(-1 / sqrt(fan_in), 1 / sqrt(fan_in)) for weight and bias."""
+    U(-1 / sqrt(fan_in), 1 / sqrt(fan_in)) for weight and bias.  The workspace carries the winning window of every cell to the
+    backward."""
+
+    _tag, _kept = "caser", "winning windows"
 
     def __init__(self, seq_len: int, width: int, n_h: int = 16, n_v: int = 4):
         super().__init__()
@@ -118,88 +67,54 @@ class CaserConv(nn.Module):
             raise ValueError(f"Caser: hidden_size {width} outside 4..256 or not a multiple of 4")
         self.seq_len, self.width, self.n_h, self.n_v = seq_len, width, n_h, n_v
         self.out_features = n_v * width + n_h * seq_len
-        self._slices, self._numel = caser_layout(seq_len, width, n_h, n_v)
-        self._pool = {}                          # (B, train, device) -> free workspaces
-        self._flat = torch.zeros(self._numel, dtype=torch.float32)
-        views = [nn.Parameter(self._flat[o:o + n].view(shp)) for o, n, shp in self._slices.values()]
+        views = list(self._make_flat(caser_param_shapes(seq_len, width, n_h, n_v), 4).values())
         with torch.no_grad():
             for w, b in zip(views[0::2], views[1::2]):
                 bound = 1.0 / math.sqrt(w[0].numel())
                 w.uniform_(-bound, bound)
                 b.uniform_(-bound, bound)
-        self.conv_v = _Conv(views[0], views[1])
-        self.conv_h = nn.ModuleList(_Conv(w, b) for w, b in zip(views[2::2], views[3::2]))
+        self.conv_v = _Holder(views[0], views[1])
+        self.conv_h = nn.ModuleList(_Holder(w, b) for w, b in zip(views[2::2], views[3::2]))
 
     def flat_parameters(self):
-        """The parameters in the order of the flat array."""
+        """The parameters in the order of the flat array, as the filter banks hold them now (``load_state_dict(assign=True)``
+        puts new ones there)."""
         out = [self.conv_v.weight, self.conv_v.bias]
         for c in self.conv_h:
             out += [c.weight, c.bias]
         return out
 
-    def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
-        self.reflatten()
-        return out
-
-    def reflatten(self):
-        """Makes every parameter a view of one flat tensor again (after ``.to()`` / ``.cuda()`` gave each its own storage)."""
-        ps = self.flat_parameters()
-        base = self._flat
-        if all(p.device == base.device and p.data_ptr() == base.data_ptr() + 4 * o
-               for p, (o, n, shp) in zip(ps, self._slices.values())):
-            return
-        with torch.no_grad():
-            flat = torch.zeros(self._numel, dtype=torch.float32, device=ps[0].device)
-            for p, (o, n, shp) in zip(ps, self._slices.values()):
-                flat[o:o + n] = p.detach().reshape(-1).to(torch.float32)
-                p.data = flat[o:o + n].view(shp)
-                p.grad = None
-        self._flat = flat
-        self._pool = {}
-
-    def _config(self, x, train: int):
+    def _config(self, inputs, extra, train):
+        (x,) = inputs
         if x.dim() != 3 or x.shape[1] != self.seq_len or x.shape[2] != self.width:
             raise ValueError(f"caser: input must be [B, {self.seq_len}, {self.width}], got {tuple(x.shape)}")
         if not x.is_cuda:
-            raise RuntimeError(_NO_CPU)
-        self.reflatten()
-        if self._flat.device != x.device:
-            raise RuntimeError("caser: the weights and the input are on different devices")
+            raise _no_cpu()
+        self._weights_on(x)
         cfg = L.CaserConfig(x.shape[0], self.seq_len, self.width, self.n_h, self.n_v)
-        nbytes = L.load().bsarec_caser_workspace_bytes(cfg, train)
+        nbytes = L.load().bsarec_caser_workspace_bytes(cfg, int(train))
         if nbytes < 0:
             raise ValueError(f"caser: unsupported batch B = {x.shape[0]} (1 <= B <= 65536)")
         return cfg, nbytes
 
-    @staticmethod
-    def _operand(t):
-        t = t.detach().to(torch.float32).contiguous()
-        return t.clone() if t.data_ptr() % 16 != 0 else t
+    def _out_shape(self, x, extra):
+        return (x.shape[0], self.out_features)
+
+    def _fwd(self, cfg, inputs, extra, train, z, ws, nbytes, stream):
+        L.check(L.load().bsarec_caser_fwd(cfg, inputs[0].data_ptr(), self._flat.data_ptr(), train, z.data_ptr(), ws.data_ptr(),
+                                          nbytes, stream), "bsarec_caser_fwd")
+
+    def _bwd(self, cfg, inputs, extra, flat, g, ws, nbytes, grads, dw, stream):
+        L.check(L.load().bsarec_caser_bwd(cfg, inputs[0].data_ptr(), flat.data_ptr(), g.data_ptr(), ws.data_ptr(), nbytes,
+                                          grads[0].data_ptr(), dw.data_ptr(), stream), "bsarec_caser_bwd")
 
     def forward(self, x):
         """[B, L, d] -> [B, n_v d + n_h L].  Differentiable with respect to x and every parameter when autograd is recording;
         otherwise the train = 0 call, which keeps nothing."""
-        if not x.is_cuda:
-            raise RuntimeError(_NO_CPU)
-        params = self.flat_parameters()
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-            self.reflatten()
-            return _CaserFn.apply(self, x, *params)
-        cfg, nbytes = self._config(x, 0)
-        key = (x.shape[0], False, x.device)
-        pool = self._pool.setdefault(key, [])
-        ws = pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        xo = self._operand(x)
-        z = torch.empty((x.shape[0], self.out_features), dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        L.check(L.load().bsarec_caser_fwd(cfg, xo.data_ptr(), self._flat.data_ptr(), 0, z.data_ptr(), ws.data_ptr(), nbytes, stream),
-                "bsarec_caser_fwd")
-        pool.append(ws)                          # stream order: the next user of ws runs after this call
-        return z
+        return self._call((x,))
 
 
-class CaserModel(nn.Module):
+class CaserModel(_SiblingModel):
     """``bsarec_amd.main.MODEL_DICT['caser']`` (``--model_type Caser``).  Parameters (the state_dict keys, in this order): ``item_embeddings.weight`` [V, d],
     ``conv.conv_v.weight`` [n_v, 1, L, 1], ``conv.conv_v.bias`` [n_v], ``conv.conv_h.{i}.weight`` [n_h, 1, i + 1, d] and
     ``conv.conv_h.{i}.bias`` [n_h] for i < L, ``fc1.weight`` [d, n_v d + n_h L], ``fc1.bias`` [d]; d = hidden_size,
@@ -240,17 +155,16 @@ class CaserModel(nn.Module):
     needs_user_ids = False                       # True on an instance with caser_user: Trainer passes user_ids
     torch_optim = True
     kernel_family = "Caser"                      # Trainer's messages
+    model_name = "Caser"
 
     def __init__(self, args):
-        super().__init__()
-        self.args = args
+        super().__init__(args)
         mode = getattr(args, "caser_step", "torch")
         if mode not in ("torch", "fused"):
             raise ValueError(f"caser_step must be 'torch' or 'fused', got {mode!r}")
         self.caser_step = mode
         if mode == "fused":
             self.torch_optim = False                      # Trainer.iteration: the pairwise branch, model.train_step
-        self._fused = None                                # the fused step's buffers (_step_buffers)
         self._fc_flat = None                              # fused: fc1.weight [d, F] then fc1.bias [d]
         self._fc2_flat = None                             # fused with caser_user: fc2.weight [d, 2 d] then fc2.bias [d]
         self.caser_user = bool(getattr(args, "caser_user", False))
@@ -278,14 +192,11 @@ class CaserModel(nn.Module):
                 self.user_embeddings.weight.normal_(0.0, std)
                 self.fc2.weight.normal_(0.0, std)
                 self.fc2.bias.zero_()
-        self._seed, self._rank, self._gen = 42, 0, None
         self.reflatten()
 
     def _apply(self, fn, recurse=True):
         out = super()._apply(fn, recurse)
         self.reflatten()
-        self._gen = None
-        self._fused = None                                # with the Adam moments and the step state, as the workspace pool goes
         return out
 
     def reflatten(self):
@@ -317,29 +228,8 @@ class CaserModel(nn.Module):
         self._fused = None
         return flat
 
-    def _stream_seed(self):
-        return (self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF
-
-    def set_seed(self, seed: int, rank: int = 0):
-        """Seed of the dropout draws (rank-decorrelated): of the torch generator and of the fused step's device state, whose
-        step counter goes back to 0."""
-        self._seed, self._rank = int(seed), int(rank)
-        self._gen = None
-        if self._fused is not None:
-            self._fused["state"][0] = self._stream_seed()
-            self._fused["state"][1] = 0
-
-    def _generator(self, device):
-        if self._gen is None or self._gen.device != device:
-            self._gen = torch.Generator(device=device)
-            self._gen.manual_seed(self._stream_seed())
-        return self._gen
-
-    def _require_gpu(self, input_ids=None):
-        if self.item_embeddings.weight.device.type != "cuda" or (input_ids is not None and not input_ids.is_cuda):
-            raise RuntimeError("bsarec_amd runs on MI355X only: move the model and its input with .cuda() "
-                               "(there is no CPU fallback)")
-        if input_ids is not None and (input_ids.dim() != 2 or input_ids.shape[1] != self.conv.seq_len):
+    def _check_ids(self, input_ids):
+        if input_ids.dim() != 2 or input_ids.shape[1] != self.conv.seq_len:
             raise ValueError(f"Caser: input_ids must be [B, max_seq_length = {self.conv.seq_len}] (the filter bank is sized by it), "
                              f"got {tuple(input_ids.shape)}")
 
@@ -356,11 +246,7 @@ class CaserModel(nn.Module):
         return user_ids.to(device=input_ids.device, dtype=torch.int64).reshape(-1)
 
     def _state(self, input_ids, train: bool, users=None):
-        z = self.conv(self.item_embeddings(input_ids))
-        if train and self.p_drop > 0.0:
-            keep = torch.empty_like(z).bernoulli_(1.0 - self.p_drop, generator=self._generator(z.device))
-            z = z * keep * (1.0 / (1.0 - self.p_drop))
-        z1 = torch.relu(self.fc1(z))
+        z1 = torch.relu(self.fc1(self._drop(self.conv(self.item_embeddings(input_ids)), self.p_drop, train)))
         if not self.caser_user:
             return z1
         U = self.user_embeddings.num_embeddings
@@ -374,9 +260,6 @@ class CaserModel(nn.Module):
         users = self._users(user_ids, input_ids)
         self._require_gpu(input_ids)
         return self._state(input_ids, self.training, users)
-
-    def predict(self, input_ids, user_ids=None, all_sequence_output=False):
-        return self.forward(input_ids, user_ids, all_sequence_output)
 
     def last_hidden(self, input_ids, user_ids=None) -> torch.Tensor:
         """[B, d]: the eval-mode s (the bits of ``forward`` in eval mode), no gradient."""
@@ -420,11 +303,6 @@ class CaserModel(nn.Module):
             arrays += [("P", P), ("G", fc2)]
         self._fused = FS.buffers(self._fused, arrays, self._stream_seed())
         return self._fused
-
-    @property
-    def step_state(self) -> torch.Tensor:
-        """The fused step's device state, int64[8]: [0] the Philox seed, [1] the step counter of the dropout stream, [2] Adam's t."""
-        return self._step_buffers()["state"]
 
     def _slot(self, f, B: int):
         s = f["slots"].get(B)
@@ -509,7 +387,7 @@ class CaserModel(nn.Module):
         replay; ``args.caser_step_graph = False`` calls eagerly instead.  With ``caser_user`` the call is
         bsarec_caser_user_train_step (five arrays) and ``user_ids`` goes into a static buffer beside the ids."""
         if self.caser_step != "fused":
-            raise RuntimeError("Caser steps through calculate_loss / backward / torch.optim.Adam unless caser_step = 'fused'")
+            raise self._torch_steps(" unless caser_step = 'fused'")
         users = self._users(user_ids, input_ids)
         self._require_gpu(input_ids)
         f = self._step_buffers()

@@ -16,9 +16,9 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .model import _CatalogueCeFn, duorec_head_options, duorec_loss
+from ._sibling import _Encoder, _FeedForward, _KernelLayer, _LayerNorm, _SiblingModel, _act, _no_cpu
+from .model import duorec_head_options, duorec_loss
 
-_NO_CPU = "bsarec_amd runs on MI355X only: move the model and its input to the GPU (there is no CPU fallback)"
 FREDOM_TYPES = ("un", "su", "us_x")
 HIDDEN_ACTS = ("gelu", "relu", "swish", "tanh", "sigmoid")
 
@@ -51,44 +51,7 @@ def fea_topk(seq_len: int, factor: float = 1.0) -> int:
     return max(1, min(int(float(factor) * math.log(seq_len)), seq_len, 32))
 
 
-class _FeaAttnFn(torch.autograd.Function):
-    """The attention as one autograd node over bsarec_fea_attn_fwd / bsarec_fea_attn_bwd, both on the current stream.  The
-    workspace carries m, the chosen delays and their softmax to the backward: it is taken from the module's pool per shape and
-    goes back after the backward."""
-
-    @staticmethod
-    def forward(ctx, attn, train, q, k, v):
-        cfg, nbytes = attn._config(q, k, v, train)
-        key = (q.shape[0], bool(train), q.device)
-        pool = attn._pool.setdefault(key, [])
-        ws = pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-        q, k, v = attn._operand(q), attn._operand(k), attn._operand(v)
-        out = torch.empty_like(q)
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-        L.check(L.load().bsarec_fea_attn_fwd(cfg, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes,
-                                             stream), "bsarec_fea_attn_fwd")
-        ctx.save_for_backward(q, k, v)
-        ctx.attn, ctx.key, ctx.ws, ctx.call = attn, key, ws, (cfg, nbytes)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        q, k, v = ctx.saved_tensors
-        cfg, nbytes = ctx.call
-        attn = ctx.attn
-        if ctx.ws is None:
-            raise RuntimeError("fea_attn: backward ran twice (the forward's delays are gone)")
-        g = attn._operand(gout)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-        L.check(L.load().bsarec_fea_attn_bwd(cfg, q.data_ptr(), k.data_ptr(), v.data_ptr(), g.data_ptr(), ctx.ws.data_ptr(), nbytes,
-                                             dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), stream), "bsarec_fea_attn_bwd")
-        attn._pool[ctx.key].append(ctx.ws)
-        ctx.ws = None
-        return None, None, dq, dk, dv
-
-
-class FeaAttention(nn.Module):
+class FeaAttention(_KernelLayer):
     """q, k, v [B, L, D] -> out [B, L, D] on the HIP kernels, with F = L // 2 + 1 and the band lo <= f < hi:
       Qf[b, c, f] = sum_t q[b, t, c] e^{-2 pi i f t / L}  (Kf alike),   S[b, f] = sum_c Qf[b, c, f] conj(Kf[b, c, f])
       m[b, tau]   = 1 / (D L) sum_{f in band} w_f Re(S[b, f] e^{+2 pi i f tau / L});  w_f = 1 at f = 0 and at the Nyquist bin of
@@ -98,7 +61,10 @@ class FeaAttention(nn.Module):
       p[b, i]     = softmax_i(m[b, idx_i]),   out[b, t, c] = sum_i p[b, i] v[b, (t + idx_i) mod L, c]
     The head split plays no part (the correlation is averaged over heads and channels), and padding is not masked.  The
     backward is the true derivative with idx held fixed; nothing flows through the batch mean that only selects.  No
-    parameters.  ``forward(q, k, v, train=None)``: the mode follows ``self.training`` unless ``train`` says otherwise."""
+    parameters.  ``forward(q, k, v, train=None)``: the mode follows ``self.training`` unless ``train`` says otherwise.  The
+    workspace carries m, the chosen delays and their softmax to the backward."""
+
+    _tag, _kept = "fea_attn", "delays"
 
     def __init__(self, seq_len: int, width: int, lo: int, hi: int, topk: int):
         super().__init__()
@@ -111,7 +77,6 @@ class FeaAttention(nn.Module):
         if not 1 <= topk <= min(seq_len, 32):
             raise ValueError(f"FEARec: topk {topk} outside 1..{min(seq_len, 32)}")
         self.seq_len, self.width, self.lo, self.hi, self.topk = int(seq_len), int(width), int(lo), int(hi), int(topk)
-        self._pool = {}                          # (B, train, device) -> free workspaces
 
     def extra_repr(self):
         return f"seq_len={self.seq_len}, width={self.width}, band=[{self.lo}, {self.hi}), topk={self.topk}"
@@ -121,62 +86,35 @@ class FeaAttention(nn.Module):
         self._pool = {}
         return out
 
-    def _config(self, q, k, v, train):
+    def _config(self, inputs, mode, train):
+        q, k, v = inputs
         shape = (q.shape[0], self.seq_len, self.width) if q.dim() == 3 else None
         if shape is None or tuple(q.shape) != shape or tuple(k.shape) != shape or tuple(v.shape) != shape:
             raise ValueError(f"fea_attn: q, k and v must be [B, {self.seq_len}, {self.width}], got {tuple(q.shape)}, "
                              f"{tuple(k.shape)}, {tuple(v.shape)}")
         if not (q.is_cuda and k.is_cuda and v.is_cuda):
-            raise RuntimeError(_NO_CPU)
-        cfg = L.FeaAttnConfig(q.shape[0], self.seq_len, self.width, self.lo, self.hi, self.topk, int(bool(train)))
+            raise _no_cpu()
+        cfg = L.FeaAttnConfig(q.shape[0], self.seq_len, self.width, self.lo, self.hi, self.topk, int(mode))
         nbytes = L.load().bsarec_fea_attn_workspace_bytes(cfg)
         if nbytes < 0:
             raise ValueError(f"fea_attn: unsupported batch B = {q.shape[0]} (1 <= B <= 65536)")
         return cfg, nbytes
 
-    @staticmethod
-    def _operand(t):
-        t = t.detach().to(torch.float32).contiguous()
-        return t.clone() if t.data_ptr() % 16 != 0 else t
+    def _fwd(self, cfg, inputs, mode, train, out, ws, nbytes, stream):
+        q, k, v = inputs
+        L.check(L.load().bsarec_fea_attn_fwd(cfg, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes,
+                                             stream), "bsarec_fea_attn_fwd")
+
+    def _bwd(self, cfg, inputs, mode, flat, g, ws, nbytes, grads, dw, stream):
+        q, k, v = inputs
+        dq, dk, dv = grads
+        L.check(L.load().bsarec_fea_attn_bwd(cfg, q.data_ptr(), k.data_ptr(), v.data_ptr(), g.data_ptr(), ws.data_ptr(), nbytes,
+                                             dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), stream), "bsarec_fea_attn_bwd")
 
     def forward(self, q, k, v, train=None):
-        """Differentiable with respect to q, k and v when autograd is recording; otherwise the forward call alone."""
-        if not (q.is_cuda and k.is_cuda and v.is_cuda):
-            raise RuntimeError(_NO_CPU)
-        train = self.training if train is None else bool(train)
-        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-            return _FeaAttnFn.apply(self, train, q, k, v)
-        cfg, nbytes = self._config(q, k, v, train)
-        key = (q.shape[0], train, q.device)
-        pool = self._pool.setdefault(key, [])
-        ws = pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-        qo, ko, vo = self._operand(q), self._operand(k), self._operand(v)
-        out = torch.empty_like(qo)
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-        L.check(L.load().bsarec_fea_attn_fwd(cfg, qo.data_ptr(), ko.data_ptr(), vo.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                             nbytes, stream), "bsarec_fea_attn_fwd")
-        pool.append(ws)                          # stream order: the next user of ws runs after this call
-        return out
-
-
-class _LayerNorm(nn.Module):
-    """TF-style LayerNorm, eps inside the square root, biased variance (the reference's, oracle/bsarec_oracle.py)."""
-
-    def __init__(self, width: int, eps: float = 1e-12):
-        super().__init__()
-        self.weight, self.bias, self.eps = nn.Parameter(torch.ones(width)), nn.Parameter(torch.zeros(width)), eps
-
-    def forward(self, x):
-        u = x.mean(-1, keepdim=True)
-        xc = x - u
-        s = (xc * xc).mean(-1, keepdim=True)
-        return self.weight * (xc / torch.sqrt(s + self.eps)) + self.bias
-
-
-def _act(name: str):
-    if name == "gelu":                                    # the erf form, as the reference writes it
-        return lambda x: x * 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
-    return {"relu": torch.relu, "swish": lambda x: x * torch.sigmoid(x), "tanh": torch.tanh, "sigmoid": torch.sigmoid}[name]
+        """Differentiable with respect to q, k and v when autograd is recording; otherwise the forward call alone.  The mode
+        (``train``: delays shared by the batch) is the kernel's own flag and says nothing about a backward to come."""
+        return self._call((q, k, v), self.training if train is None else bool(train))
 
 
 class _FeaLayer(nn.Module):
@@ -190,13 +128,6 @@ class _FeaLayer(nn.Module):
         self.fea = attn
 
 
-class _FeedForward(nn.Module):
-    def __init__(self, d: int):
-        super().__init__()
-        self.dense_1, self.dense_2 = nn.Linear(d, 4 * d), nn.Linear(4 * d, d)
-        self.LayerNorm = _LayerNorm(d)
-
-
 class _Block(nn.Module):
     def __init__(self, d: int, heads: int, attn: FeaAttention):
         super().__init__()
@@ -204,13 +135,7 @@ class _Block(nn.Module):
         self.feed_forward = _FeedForward(d)
 
 
-class _Encoder(nn.Module):
-    def __init__(self, blocks):
-        super().__init__()
-        self.blocks = nn.ModuleList(blocks)
-
-
-class FEARecModel(nn.Module):
+class FEARecModel(_SiblingModel):
     """``bsarec_amd.main.MODEL_REGISTRY['fearec']`` (``--model_type FEARec``).  The module tree, the 4 + 16 N state_dict keys,
     their shapes and the init are SASRec's (``item_embeddings``, ``position_embeddings``, ``LayerNorm``,
     ``item_encoder.blocks.{i}.layer.{query,key,value,dense,LayerNorm}``, ``item_encoder.blocks.{i}.feed_forward.{dense_1,dense_2,
@@ -237,16 +162,11 @@ class FEARecModel(nn.Module):
     torch_optim = True
     full_logits = None                           # no dense-logits path: the rankings take last_hidden + catalogue_weight
     kernel_family = "FEARec"
+    model_name = "FEARec"
 
     def __init__(self, args):
-        super().__init__()
-        if getattr(args, "storage", None) == "bf16" or (getattr(args, "plan_options", None) or {}).get("storage", 0):
-            raise ValueError("FEARec: storage = 'bf16' does not apply (the FEARec kernels are fp32)")
-        if getattr(args, "train_negatives", 0):
-            raise ValueError("FEARec: train_negatives does not apply (the model has DuoRec's loss)")
-        if getattr(args, "train_lazy_adam", False):
-            raise ValueError("FEARec: train_lazy_adam does not apply (the model steps through torch.optim.Adam)")
-        self.args = args
+        super().__init__(args)
+        self._refuse_plan_options(args, "DuoRec's loss")
         d, Lq, N = int(args.hidden_size), int(args.max_seq_length), int(args.num_hidden_layers)
         heads = int(args.num_attention_heads)
         if d % heads != 0:
@@ -283,40 +203,15 @@ class FEARecModel(nn.Module):
                 if isinstance(m, nn.Linear):
                     m.bias.zero_()
         duorec_head_options(self, args)
-        self._ce_pool = {}                       # (B, V, d, device) -> free workspaces of bsarec_ce_head_*
-        self._seed, self._rank, self._gen, self._dft = 42, 0, None, {}
+        self._dft = {}
 
     def _apply(self, fn, recurse=True):
         out = super()._apply(fn, recurse)
-        self._gen, self._dft, self._ce_pool, self._nce_pool = None, {}, {}, {}
+        self._dft, self._nce_pool = {}, {}
         return out
 
-    def check_trainer(self, args, process_group):
-        """Called by Trainer before the first step."""
-        if process_group is not None:
-            raise ValueError("FEARec: single GPU only")
-
-    def set_seed(self, seed: int, rank: int = 0):
-        """Seed of the dropout draws (rank-decorrelated)."""
-        self._seed, self._rank, self._gen = int(seed), int(rank), None
-
-    def _generator(self, device):
-        if self._gen is None or self._gen.device != device:
-            self._gen = torch.Generator(device=device)
-            self._gen.manual_seed((self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF)
-        return self._gen
-
-    def _drop(self, x, p, train):
-        if not train or p <= 0.0:
-            return x
-        keep = torch.empty_like(x).bernoulli_(1.0 - p, generator=self._generator(x.device))
-        return x * keep * (1.0 / (1.0 - p))
-
-    def _require_gpu(self, input_ids=None):
-        if self.item_embeddings.weight.device.type != "cuda" or (input_ids is not None and not input_ids.is_cuda):
-            raise RuntimeError("bsarec_amd runs on MI355X only: move the model and its input with .cuda() "
-                               "(there is no CPU fallback)")
-        if input_ids is not None and (input_ids.dim() != 2 or input_ids.shape[1] != self.seq_len):
+    def _check_ids(self, input_ids):
+        if input_ids.dim() != 2 or input_ids.shape[1] != self.seq_len:
             raise ValueError(f"FEARec: input_ids must be [B, max_seq_length = {self.seq_len}] (the bands are sized by it), "
                              f"got {tuple(input_ids.shape)}")
 
@@ -352,28 +247,6 @@ class FEARecModel(nn.Module):
             outs.append(x)
         return outs
 
-    def forward(self, input_ids, user_ids=None, all_sequence_output=False):
-        """[B, L] ids -> the last layer's [B, L, d], or every layer's outputs as a list.  ``user_ids`` is ignored."""
-        self._require_gpu(input_ids)
-        outs = self._encode(input_ids, self.training)
-        return outs if all_sequence_output else outs[-1]
-
-    def predict(self, input_ids, user_ids=None, all_sequence_output=False):
-        return self.forward(input_ids, user_ids, all_sequence_output)
-
-    def last_hidden(self, input_ids) -> torch.Tensor:
-        """[B, d]: position L - 1 of the evaluation-mode output (per-sequence delays, no dropout), no gradient."""
-        self._require_gpu(input_ids)
-        with torch.no_grad():
-            return self._encode(input_ids, False)[-1][:, -1, :]
-
-    def catalogue_weight(self) -> torch.Tensor:
-        return self.item_embeddings.weight.detach()
-
-    def catalogue_ce(self, seq_output, answers) -> torch.Tensor:
-        """``F.cross_entropy(seq_output @ E.T, answers)`` as one HIP autograd node (bsarec_ce_head_fwd / _bwd)."""
-        return _CatalogueCeFn.apply(self, seq_output, self.item_embeddings.weight, answers)
-
     def _dft_pair(self, ref):
         """The ortho-normalised rfft along the sequence axis as two real [F, L] matrices (cos / -sin over sqrt(L)), built in
         fp64 from exactly reduced arguments."""
@@ -407,9 +280,3 @@ class FEARecModel(nn.Module):
             if self.fredom_type in ("su", "us_x"):
                 loss = loss + 0.1 * self.spectral_distance(views["seq"], views["sem"])
         return loss
-
-    def train_step(self, input_ids, answers, neg_answers=None, same_target=None):
-        raise RuntimeError("FEARec steps through calculate_loss / backward / torch.optim.Adam (Trainer does)")
-
-    def grad_step(self, input_ids, answers, neg_answers=None):
-        raise RuntimeError("FEARec steps through calculate_loss / backward / torch.optim.Adam (Trainer does)")

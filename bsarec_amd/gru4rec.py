@@ -20,6 +20,7 @@ from torch import nn
 
 from . import _fused_step as FS
 from . import _lib as L
+from ._sibling import _FlatLayer, _Holder, _SiblingModel, _no_cpu
 
 GRU_HIDDEN = (32, 64, 96, 128)
 
@@ -36,52 +37,15 @@ def gru_param_shapes(input_size: int, hidden_size: int, num_layers: int, out_siz
     return shapes
 
 
-class _GruFn(torch.autograd.Function):
-    """The GRU stack and its projection as one autograd node over bsarec_gru_fwd / bsarec_gru_bwd, both on the current stream.
-    The workspace carries the forward's activations to the backward: it is taken from the stack's pool per shape and goes
-    back after the backward.  ``params`` are the views of the stack's flat weight tensor; their gradients are views of one
-    flat ``dweights``."""
-
-    @staticmethod
-    def forward(ctx, stack, x, last_only, *params):
-        cfg, nbytes = stack._config(x)
-        lib = L.load()
-        key = (x.shape[0], x.shape[1], True, x.device)
-        pool = stack._pool.setdefault(key, [])
-        ws = pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        x = stack._operand(x)
-        out = torch.empty(stack._out_shape(x, last_only), dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        L.check(lib.bsarec_gru_fwd(cfg, x.data_ptr(), stack._flat.data_ptr(), 1, int(last_only), out.data_ptr(), ws.data_ptr(),
-                                   nbytes, stream), "bsarec_gru_fwd")
-        ctx.save_for_backward(x)
-        ctx.stack, ctx.key, ctx.ws, ctx.call = stack, key, ws, (cfg, nbytes, int(last_only), stack._flat)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        (x,) = ctx.saved_tensors
-        cfg, nbytes, last_only, flat = ctx.call
-        stack = ctx.stack
-        if ctx.ws is None:
-            raise RuntimeError("gru: backward ran twice (the forward's activations are gone)")
-        g = stack._operand(gout)
-        dx = torch.empty_like(x)
-        dw = torch.empty_like(flat)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        L.check(L.load().bsarec_gru_bwd(cfg, x.data_ptr(), flat.data_ptr(), last_only, g.data_ptr(), ctx.ws.data_ptr(), nbytes,
-                                        dx.data_ptr(), dw.data_ptr(), stream), "bsarec_gru_bwd")
-        stack._pool[ctx.key].append(ctx.ws)
-        ctx.ws = None
-        return (None, dx, None) + tuple(dw[o:o + n].view(shp) for o, n, shp in stack._slices.values())
-
-
-class GruStack(nn.Module):
+class GruStack(_FlatLayer):
     """``nn.GRU(input_size, hidden_size, num_layers, bias=False, batch_first=True)`` with h_0 = 0 and, when ``out_size`` is
     not 0, ``nn.Linear(hidden_size, out_size)`` on top, on the HIP kernels.  Owns ONE flat fp32 tensor in the layout of
     bsarec_gru_fwd's ``weights``; ``weight_ih_l{k}`` / ``weight_hh_l{k}`` are parameters that are views of it, so an optimiser
     that updates them in place updates the array the kernels read.  ``out_weight`` / ``out_bias`` are views of its tail: plain
-    attributes here, for the owner to register under its own names (GRU4RecModel: ``dense.weight`` / ``dense.bias``)."""
+    attributes here, for the owner to register under its own names (GRU4RecModel: ``dense.weight`` / ``dense.bias``).  The
+    workspace carries the forward's activations to the backward."""
+
+    _tag = "gru"
 
     def __init__(self, input_size: int, hidden_size: int, num_layers: int, out_size: int = 0):
         super().__init__()
@@ -93,25 +57,11 @@ class GruStack(nn.Module):
             if not (v == 0 and name == "output") and not (4 <= v <= 256 and v % 4 == 0):
                 raise ValueError(f"GRU stack: {name} size {v} outside 4..256 or not a multiple of 4")
         self.input_size, self.hidden_size, self.num_layers, self.out_size = input_size, hidden_size, num_layers, out_size
-        self._slices = OrderedDict()
-        off = 0
-        for name, shp in gru_param_shapes(input_size, hidden_size, num_layers, out_size).items():
-            n = math.prod(shp)
-            self._slices[name] = (off, n, shp)
-            off += n
-        self._numel = off
-        self._pool = {}                          # (B, L, train, device) -> free workspaces
-        self._flat = torch.zeros(off, dtype=torch.float32)
-        self._views = OrderedDict()
-        for name, (o, n, shp) in self._slices.items():
-            p = nn.Parameter(self._flat[o:o + n].view(shp))
-            self._views[name] = p
+        bound = 1.0 / math.sqrt(hidden_size)
+        for name, p in self._make_flat(gru_param_shapes(input_size, hidden_size, num_layers, out_size)).items():
             if name.startswith("weight_"):
                 self.register_parameter(name, p)
-        bound = 1.0 / math.sqrt(hidden_size)
-        with torch.no_grad():
-            for name, p in self._views.items():
-                if name.startswith("weight_"):
+                with torch.no_grad():
                     p.uniform_(-bound, bound)                 # torch's default for nn.GRU
 
     @property
@@ -123,80 +73,41 @@ class GruStack(nn.Module):
         return self._views.get("out_bias")
 
     def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
         with torch.no_grad():
             for name, p in self._views.items():
                 if not name.startswith("weight_"):           # registered by the owner: moved here too, so the views stay together
                     p.data = fn(p.data)
-        self.reflatten()
-        return out
+        return super()._apply(fn, recurse)
 
-    def flat_parameters(self):
-        """The parameters in the order of the flat array."""
-        return list(self._views.values())
-
-    def reflatten(self):
-        """Makes every parameter a view of one flat tensor again (after ``.to()`` / ``.cuda()`` gave each its own storage)."""
-        ps = self.flat_parameters()
-        base = self._flat
-        if all(p.device == base.device and p.data_ptr() == base.data_ptr() + 4 * o
-               for p, (o, n, shp) in zip(ps, self._slices.values())):
-            return
-        with torch.no_grad():
-            flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps])
-            for p, (o, n, shp) in zip(ps, self._slices.values()):
-                p.data = flat[o:o + n].view(shp)
-                p.grad = None
-        self._flat = flat
-        self._pool = {}
-
-    def _config(self, x):
+    def _config(self, inputs, last_only, train):
+        (x,) = inputs
         if x.dim() != 3 or x.shape[2] != self.input_size:
             raise ValueError(f"gru: input must be [B, L, {self.input_size}], got {tuple(x.shape)}")
         if not x.is_cuda:
-            raise RuntimeError("bsarec_amd runs on MI355X only: move the model and its input to the GPU "
-                               "(there is no CPU fallback)")
-        self.reflatten()
-        if self._flat.device != x.device:
-            raise RuntimeError("gru: the weights and the input are on different devices")
+            raise _no_cpu()
+        self._weights_on(x)
         cfg = L.GruConfig(x.shape[0], x.shape[1], self.input_size, self.hidden_size, self.num_layers, self.out_size)
-        nbytes = L.load().bsarec_gru_workspace_bytes(cfg, 1)
+        nbytes = L.load().bsarec_gru_workspace_bytes(cfg, int(train))
         if nbytes < 0:
             raise ValueError(f"gru: unsupported shape B = {x.shape[0]}, L = {x.shape[1]} (1 <= B <= 65536, 1 <= L <= 256)")
         return cfg, nbytes
-
-    @staticmethod
-    def _operand(t):
-        t = t.detach().to(torch.float32).contiguous()
-        return t.clone() if t.data_ptr() % 16 != 0 else t
 
     def _out_shape(self, x, last_only):
         w = self.out_size or self.hidden_size
         return (x.shape[0], w) if last_only else (x.shape[0], x.shape[1], w)
 
+    def _fwd(self, cfg, inputs, last_only, train, out, ws, nbytes, stream):
+        L.check(L.load().bsarec_gru_fwd(cfg, inputs[0].data_ptr(), self._flat.data_ptr(), train, int(last_only), out.data_ptr(),
+                                        ws.data_ptr(), nbytes, stream), "bsarec_gru_fwd")
+
+    def _bwd(self, cfg, inputs, last_only, flat, g, ws, nbytes, grads, dw, stream):
+        L.check(L.load().bsarec_gru_bwd(cfg, inputs[0].data_ptr(), flat.data_ptr(), int(last_only), g.data_ptr(), ws.data_ptr(),
+                                        nbytes, grads[0].data_ptr(), dw.data_ptr(), stream), "bsarec_gru_bwd")
+
     def forward(self, x, last_only: bool = False):
         """[B, L, input] -> [B, L, out] (``last_only``: [B, out], position L - 1).  Differentiable with respect to x and every
         parameter when autograd is recording; otherwise the train = 0 call, which keeps nothing."""
-        if not x.is_cuda:
-            raise RuntimeError("bsarec_amd runs on MI355X only: move the model and its input to the GPU "
-                               "(there is no CPU fallback)")
-        params = self.flat_parameters()
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-            self.reflatten()
-            return _GruFn.apply(self, x, bool(last_only), *params)
-        cfg, _ = self._config(x)
-        lib = L.load()
-        nbytes = lib.bsarec_gru_workspace_bytes(cfg, 0)
-        key = (x.shape[0], x.shape[1], False, x.device)
-        pool = self._pool.setdefault(key, [])
-        ws = pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        xo = self._operand(x)
-        out = torch.empty(self._out_shape(xo, last_only), dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        L.check(lib.bsarec_gru_fwd(cfg, xo.data_ptr(), self._flat.data_ptr(), 0, int(bool(last_only)), out.data_ptr(),
-                                   ws.data_ptr(), nbytes, stream), "bsarec_gru_fwd")
-        pool.append(ws)                          # stream order: the next user of ws runs after this call
-        return out
+        return self._call((x,), bool(last_only))
 
 
 GRU_LOSSES = ("bpr",) + tuple(L.GRU4REC_LOSSES)
@@ -231,15 +142,7 @@ def cand_scores_loss(r, cand, answers, loss: str, bpreg: float = 1.0):
     return torch.where(some, rows, torch.zeros_like(rows)).mean()
 
 
-class _Dense(nn.Module):
-    """Holder of ``dense.weight`` / ``dense.bias``: views of the stack's flat tensor (the projection runs in bsarec_gru_fwd)."""
-
-    def __init__(self, weight, bias):
-        super().__init__()
-        self.weight, self.bias = weight, bias
-
-
-class GRU4RecModel(nn.Module):
+class GRU4RecModel(_SiblingModel):
     """``MODEL_DICT['gru4rec']``.  Parameters (the state_dict keys, in this order): ``item_embeddings.weight`` [V, d],
     ``gru_layers.weight_ih_l{k}`` [3H, d or H] and ``gru_layers.weight_hh_l{k}`` [3H, H] for k < N, ``dense.weight`` [d, H],
     ``dense.bias`` [d]; d = hidden_size, H = gru_hidden_size (default 64), N = num_hidden_layers, V = item_size.  A model of
@@ -272,10 +175,10 @@ class GRU4RecModel(nn.Module):
     needs_negatives = True
     needs_same_target = False
     torch_optim = True
+    model_name = "GRU4Rec"
 
     def __init__(self, args):
-        super().__init__()
-        self.args = args
+        super().__init__(args)
         mode = getattr(args, "gru_step", "torch")
         if mode not in ("torch", "fused"):
             raise ValueError(f"gru_step must be 'torch' or 'fused', got {mode!r}")
@@ -296,63 +199,32 @@ class GRU4RecModel(nn.Module):
         self._head = None if loss == "bpr" else L.Gru4RecHead(L.GRU4REC_LOSSES[loss], L.GRU4REC_CANDIDATES[negatives], bpreg)
         if mode == "fused":
             self.torch_optim = False                      # Trainer.iteration: the pairwise branch, model.train_step
-        self._fused = None                                # the fused step's buffers (_step_buffers)
         d, H = int(args.hidden_size), int(getattr(args, "gru_hidden_size", 64))
         self.item_embeddings = nn.Embedding(int(args.item_size), d)
         self.gru_layers = GruStack(d, H, int(args.num_hidden_layers), d)
-        self.dense = _Dense(self.gru_layers.out_weight, self.gru_layers.out_bias)
+        self.dense = _Holder(self.gru_layers.out_weight, self.gru_layers.out_bias)     # the projection runs in bsarec_gru_fwd
         self.p_drop = float(args.hidden_dropout_prob)
         std = float(args.initializer_range)
         with torch.no_grad():
             self.item_embeddings.weight.normal_(0.0, std)
             self.dense.weight.normal_(0.0, std)
             self.dense.bias.zero_()
-        self._seed, self._rank, self._gen = 42, 0, None
 
     def _apply(self, fn, recurse=True):
         out = super()._apply(fn, recurse)
-        self.gru_layers.reflatten()
-        self._gen = None
-        self._fused = None                                # with the Adam moments and the step state, as the workspace pool goes
+        self.gru_layers.reflatten()                       # ``dense`` moved its two views after the stack had flattened itself
         return out
 
-    def _stream_seed(self):
-        return (self._seed ^ (self._rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF
-
-    def set_seed(self, seed: int, rank: int = 0):
-        """Seed of the dropout draws (rank-decorrelated): of the torch generator and of the fused step's device state, whose
-        step counter goes back to 0."""
-        self._seed, self._rank = int(seed), int(rank)
-        self._gen = None
-        if self._fused is not None:
-            self._fused["state"][0] = self._stream_seed()
-            self._fused["state"][1] = 0
-
-    def _generator(self, device):
-        if self._gen is None or self._gen.device != device:
-            self._gen = torch.Generator(device=device)
-            self._gen.manual_seed(self._stream_seed())
-        return self._gen
-
-    def _require_gpu(self, input_ids=None):
-        if self.item_embeddings.weight.device.type != "cuda" or (input_ids is not None and not input_ids.is_cuda):
-            raise RuntimeError("bsarec_amd runs on MI355X only: move the model and its input with .cuda() "
-                               "(there is no CPU fallback)")
+    def _check_ids(self, input_ids):
+        pass                                              # the stack checks its [B, L, d] input, the fused step its ids (_fill)
 
     def _embed(self, input_ids, train: bool):
-        x = self.item_embeddings(input_ids)
-        if train and self.p_drop > 0.0:
-            keep = torch.empty_like(x).bernoulli_(1.0 - self.p_drop, generator=self._generator(x.device))
-            x = x * keep * (1.0 / (1.0 - self.p_drop))
-        return x
+        return self._drop(self.item_embeddings(input_ids), self.p_drop, train)
 
     def forward(self, input_ids, user_ids=None, all_sequence_output=False):
         """[B, L] ids -> [B, L, d].  ``all_sequence_output`` is accepted and ignored."""
         self._require_gpu(input_ids)
         return self.gru_layers(self._embed(input_ids, self.training))
-
-    def predict(self, input_ids, user_ids=None, all_sequence_output=False):
-        return self.forward(input_ids, user_ids, all_sequence_output)
 
     def last_hidden(self, input_ids) -> torch.Tensor:
         """[B, d]: the eval-mode output at position L - 1 (the bits of ``forward`` in eval mode at that row), no gradient."""
@@ -387,11 +259,6 @@ class GRU4RecModel(nn.Module):
             raise RuntimeError("gru4rec: the item table and the GRU weights must be contiguous fp32 on one device")
         self._fused = FS.buffers(self._fused, [("E", E), ("W", flat)], self._stream_seed())
         return self._fused
-
-    @property
-    def step_state(self) -> torch.Tensor:
-        """The fused step's device state, int64[8]: [0] the Philox seed, [1] the step counter of the dropout stream, [2] Adam's t."""
-        return self._step_buffers()["state"]
 
     def _slot(self, f, B: int, Lq: int):
         s = f["slots"].get((B, Lq))
@@ -460,7 +327,7 @@ class GRU4RecModel(nn.Module):
         the device, and the capture is one linear chain on one stream, so it has no parallel branches to replay;
         ``args.gru_step_graph = False`` calls eagerly instead."""
         if self.gru_step != "fused":
-            raise RuntimeError("GRU4Rec steps through calculate_loss / backward / torch.optim.Adam (Trainer does)")
+            raise self._torch_steps()
         self._require_gpu(input_ids)
         f = self._step_buffers()
         s = self._fill(self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1])), input_ids, answers, neg_answers)
