@@ -1872,6 +1872,22 @@ extern "C" int bsarec_topk_seen(float* scores, long ld, int B, int V, const int6
 static bool row_dim_ok(int d) { return d >= 4 && d <= 256 && d % 4 == 0; }
 static bool aligned_to(const void* p, uintptr_t a) { return p && (uintptr_t)p % a == 0; }
 static bool col_range_ok(long col_base, int V) { return col_base >= 0 && col_base + V <= 0x7fffffffL; }
+// the pointers of an entry point: p16 aligned to 16 bytes, p8 to 8, p4 to 4, none null (aligned_to fails a null pointer)
+static int ptrs_check(std::initializer_list<const void*> p16, std::initializer_list<const void*> p8 = {},
+                      std::initializer_list<const void*> p4 = {}) {
+    for (const void* p : p16)
+        if (!aligned_to(p, 16)) return -10;
+    for (const void* p : p8)
+        if (!aligned_to(p, 8)) return -10;
+    for (const void* p : p4)
+        if (!aligned_to(p, 4)) return -10;
+    return 0;
+}
+// what the plan-less sequence layers share: B <= 65536 sequences of min_len .. 256 positions; a dropout rate in [0, 1)
+static bool seq_shape_ok(int batch, int seq_len, int min_len) {
+    return batch >= 1 && batch <= 65536 && seq_len >= min_len && seq_len <= 256;
+}
+static bool dropout_ok(float p) { return p >= 0.f && p < 1.f; }           // NaN fails both comparisons
 
 // A score-tile kernel's h tile is rows x (d + 4) floats: up to 133 KB of the 160 KB LDS (128 rows, d = 256), past the 64 KB a
 // launch gets without asking.  Once per process (`done` is the family's flag) every kernel's limit is raised to its largest tile.
@@ -2256,26 +2272,82 @@ extern "C" int bsarec_ce_head_range_bwd(const float* h, long ldh, const float* i
 }
 
 // ---------------------------------------------------------------------------------------------
-// GRU stack (gru.h): plan-less, everything on the caller's stream, no allocation
+// Dense products of the plan-less layers (the GRU stack, the LRU and Mamba layers, the LRURec step): fp32 products on 64 x 64
+// tiles of the GEMM core, on the caller's stream.  A weight gradient is a split-K product into slabs that the caller owns, and
+// one sum over the slabs.
 // ---------------------------------------------------------------------------------------------
-static int gru_check(const bsarec_gru_config_t* c) {
-    if (!c) return -10;
-    if (c->batch < 1 || c->batch > 65536 || c->seq_len < 1 || c->seq_len > 256) return -10;
-    if (!row_dim_ok(c->input_size)) return -10;
-    if (c->hidden_size != 32 && c->hidden_size != 64 && c->hidden_size != 96 && c->hidden_size != 128) return -10;
-    if (c->num_layers < 1 || c->num_layers > 4) return -10;
-    if (c->out_size != 0 && !row_dim_ok(c->out_size)) return -10;
-    return 0;
-}
-
 // split-K of a weight-gradient product over K rows: slices of >= 256 rows, 64 at the most; a function of K alone
-static void gru_split(long K, int* nsplit, int* kchunk) {
+static void split_k(long K, int* nsplit, int* kchunk) {
     long ns = (K + 255) / 256;
     ns = ns < 1 ? 1 : (ns > 64 ? 64 : ns);
     const long kc = rup((K + ns - 1) / ns, GEMM_BK);
     *kchunk = (int)kc;
     *nsplit = kc > 0 ? (int)((K + kc - 1) / kc) : 1;
     if (*nsplit < 1) *nsplit = 1;
+}
+// C (+ bias); P, Q != 0: row r = p Q + q of the product is stored at row q P + p
+static EpiGru dense_epi(float* C, long ldc, const float* bias = nullptr, int P = 0, int Q = 0) {
+    EpiGru e;
+    e.C = C; e.ldc = ldc; e.c_split = 0; e.bias = bias; e.P = P; e.Q = Q;
+    return e;
+}
+// C[M, N] = A[M, K] . W[N, K]^T through the epilogue e
+template <class Epi>
+static int dense_nt(const float* A, const float* W, int M, int N, int K, const Epi& e, hipStream_t s) {
+    GemmP g = gemm_defaults(M, N, K);
+    g.lda = K; g.ldb = K; g.A[0] = A; g.B[0] = W;
+    return launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_NONE, true);
+}
+// C[M, N] = A[M, K] . W[K, N] through the epilogue e
+template <class Epi>
+static int dense_nn(const float* A, const float* W, int M, int N, int K, const Epi& e, hipStream_t s) {
+    GemmP g = gemm_defaults(M, N, K);
+    g.lda = K; g.ldb = N; g.A[0] = A; g.B[0] = W;
+    return launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_NONE, true);
+}
+// out[M, N] = A[K, M]^T . Bm[K, N] in split-K slabs at slab + coff, M x Nfull each (the caller sums them); bpart: the column
+// sums of A per split, [ns][M]
+static int dense_tn(const float* A, long lda, const float* Bm, int M, int N, long K, float* slab, long slab_floats, long coff,
+                    float* bpart, hipStream_t s) {
+    int ns, kc;
+    split_k(K, &ns, &kc);
+    GemmP g = gemm_defaults(M, N, (int)K);
+    g.lda = lda; g.ldb = N; g.A[0] = A; g.B[0] = Bm; g.nsplit = ns; g.kchunk = kc;
+    EpiGru e = dense_epi(slab + coff, N);
+    e.c_split = slab_floats;
+    if (bpart) return launch_gemm<64, 64, 2, 2, true, true, XF_NONE, XF_NONE, true>(g, no_xform(), e, bpart, 1, s, BSAREC_K_NONE, true);
+    return launch_gemm<64, 64, 2, 2, true, true, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_NONE, true);
+}
+// out[floats] = the sum of the split_k(K) slabs of `floats` floats each
+static void slab_sum(const float* slab, long K, long floats, float* out, hipStream_t s) {
+    int ns, kc;
+    split_k(K, &ns, &kc);
+    hipLaunchKernelGGL(gru_slab_sum_kernel, dim3(cdiv(floats / 4, 256)), dim3(256), 0, s, slab, ns, floats / 4, out);
+}
+// The backward of Y[rows, out] = X[rows, in] . W[out, in]^T (+ b), four launches at the most, in this order:
+// dX = dY . W through dx_epi;  dW = dY^T . X summed over the split-K slabs;  db (null: none) = the column sums of dY.
+// slab holds split_k(rows) slabs of out x in floats, bpart (read only with db) as many of `out` floats; both are scratch
+static int linear_bwd(const float* dY, const float* X, const float* W, long rows, int out, int in, const EpiGru& dx_epi,
+                      float* slab, float* bpart, float* dW, float* db, hipStream_t s) {
+    const long wfloats = (long)out * in;
+    RET(dense_nn(dY, W, (int)rows, in, out, dx_epi, s));
+    RET(dense_tn(dY, out, X, out, in, rows, slab, wfloats, 0, db ? bpart : nullptr, s));
+    slab_sum(slab, rows, wfloats, dW, s);
+    if (db) slab_sum(bpart, rows, out, db, s);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// GRU stack (gru.h): plan-less, everything on the caller's stream, no allocation
+// ---------------------------------------------------------------------------------------------
+static int gru_check(const bsarec_gru_config_t* c) {
+    if (!c) return -10;
+    if (!seq_shape_ok(c->batch, c->seq_len, 1)) return -10;
+    if (!row_dim_ok(c->input_size)) return -10;
+    if (c->hidden_size != 32 && c->hidden_size != 64 && c->hidden_size != 96 && c->hidden_size != 128) return -10;
+    if (c->num_layers < 1 || c->num_layers > 4) return -10;
+    if (c->out_size != 0 && !row_dim_ok(c->out_size)) return -10;
+    return 0;
 }
 
 // Workspace, in floats (every region a multiple of 4): A / da [T][3H] | Y_k [T][H], k < NY | S_k [T][4H] | db_n [T][H] |
@@ -2291,7 +2363,7 @@ static GruWs gru_ws(const bsarec_gru_config_t& c, bool train) {
     memset(&w, 0, sizeof(w));
     for (long K : {T, T - c.batch, (long)c.batch}) {        // the K of every split-K product of the backward
         int ns, kc;
-        gru_split(K, &ns, &kc);
+        split_k(K, &ns, &kc);
         w.ns = std::max(w.ns, ns);
     }
     w.ny = train ? (int)N : (int)(N < 2 ? N : 2);
@@ -2338,41 +2410,6 @@ extern "C" long bsarec_gru_workspace_bytes(const bsarec_gru_config_t* cfg, int t
     return gru_ws(*cfg, train != 0).total * (long)sizeof(float);
 }
 
-static EpiGru gru_epi(float* C, long ldc, const float* bias = nullptr, int P = 0, int Q = 0) {
-    EpiGru e;
-    e.C = C; e.ldc = ldc; e.c_split = 0; e.bias = bias; e.P = P; e.Q = Q;
-    return e;
-}
-// C[M, N] = A[M, K] . W[N, K]^T (+ bias)
-static int gru_nt(const float* A, const float* W, int M, int N, int K, const EpiGru& e, hipStream_t s) {
-    GemmP g = gemm_defaults(M, N, K);
-    g.lda = K; g.ldb = K; g.A[0] = A; g.B[0] = W;
-    return launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_NONE, true);
-}
-// C[M, N] = A[M, K] . W[K, N]
-static int gru_nn(const float* A, const float* W, int M, int N, int K, const EpiGru& e, hipStream_t s) {
-    GemmP g = gemm_defaults(M, N, K);
-    g.lda = K; g.ldb = N; g.A[0] = A; g.B[0] = W;
-    return launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_NONE, true);
-}
-// out[M, N] = A[K, M]^T . Bm[K, N] in split-K slabs at slab + coff, M x Nfull each (the caller sums them); bpart: the column
-// sums of A per split, [ns][M]
-static int gru_tn(const float* A, long lda, const float* Bm, int M, int N, long K, float* slab, long slab_floats, long coff,
-                  float* bpart, hipStream_t s) {
-    int ns, kc;
-    gru_split(K, &ns, &kc);
-    GemmP g = gemm_defaults(M, N, (int)K);
-    g.lda = lda; g.ldb = N; g.A[0] = A; g.B[0] = Bm; g.nsplit = ns; g.kchunk = kc;
-    EpiGru e = gru_epi(slab + coff, N);
-    e.c_split = slab_floats;
-    if (bpart) return launch_gemm<64, 64, 2, 2, true, true, XF_NONE, XF_NONE, true>(g, no_xform(), e, bpart, 1, s, BSAREC_K_NONE, true);
-    return launch_gemm<64, 64, 2, 2, true, true, XF_NONE, XF_NONE, false>(g, no_xform(), e, nullptr, 1, s, BSAREC_K_NONE, true);
-}
-static void gru_sum(const float* slab, long K, long floats, float* out, hipStream_t s) {
-    int ns, kc;
-    gru_split(K, &ns, &kc);
-    hipLaunchKernelGGL(gru_slab_sum_kernel, dim3(cdiv(floats / 4, 256)), dim3(256), 0, s, slab, ns, floats / 4, out);
-}
 static void gru_swap(const float* src, float* dst, long P, long Q, int W, hipStream_t s) {
     hipLaunchKernelGGL(gru_swap_rows_kernel, dim3(cdiv(P * Q * (W / 4), 256)), dim3(256), 0, s, src, dst, P, Q, W / 4);
 }
@@ -2384,19 +2421,11 @@ static void gru_swap(const float* src, float* dst, long P, long Q, int W, hipStr
         default: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break; \
     }
 
-static int gru_args(const bsarec_gru_config_t* cfg, const float* x, const float* weights, const void* workspace, long workspace_bytes,
-                    bool train) {
-    RET(gru_check(cfg));
-    if (!x || !weights || !workspace) return -10;
-    if (!aligned_to(x, 16) || !aligned_to(weights, 16) || !aligned_to(workspace, 16)) return -10;
-    if (workspace_bytes < gru_ws(*cfg, train).total * (long)sizeof(float)) return -10;
-    return 0;
-}
-
 extern "C" int bsarec_gru_fwd(const bsarec_gru_config_t* cfg, const float* x, const float* weights, int train, int last_only,
                               float* out, void* workspace, long workspace_bytes, void* stream) {
-    RET(gru_args(cfg, x, weights, workspace, workspace_bytes, train != 0));
-    if (!out || !aligned_to(out, 16)) return -10;
+    RET(gru_check(cfg));
+    RET(ptrs_check({x, weights, out, workspace}));
+    if (workspace_bytes < gru_ws(*cfg, train != 0).total * (long)sizeof(float)) return -10;
     const bsarec_gru_config_t& c = *cfg;
     const int B = c.batch, L = c.seq_len, I = c.input_size, H = c.hidden_size, N = c.num_layers, O = c.out_size;
     const long T = (long)B * L;
@@ -2408,8 +2437,8 @@ extern "C" int bsarec_gru_fwd(const bsarec_gru_config_t* cfg, const float* x, co
     const float* y = nullptr;
     for (int k = 0; k < N; ++k) {
         // a = in . W_ih^T, time-major: x's rows (b, t) go through the row map, a layer output is time-major already
-        if (k == 0) RET(gru_nt(x, weights + wo.ih[0], (int)T, 3 * H, I, gru_epi(w + ws.a, 3 * H, nullptr, B, L), s));
-        else RET(gru_nt(y, weights + wo.ih[k], (int)T, 3 * H, H, gru_epi(w + ws.a, 3 * H), s));
+        if (k == 0) RET(dense_nt(x, weights + wo.ih[0], (int)T, 3 * H, I, dense_epi(w + ws.a, 3 * H, nullptr, B, L), s));
+        else RET(dense_nt(y, weights + wo.ih[k], (int)T, 3 * H, H, dense_epi(w + ws.a, 3 * H), s));
         GruFwdP P;
         P.A = w + ws.a; P.Whh = weights + wo.hh[k]; P.B = B; P.L = L;
         P.Y = w + ws.y + (long)(train ? k : (k & 1)) * T * H;
@@ -2419,8 +2448,8 @@ extern "C" int bsarec_gru_fwd(const bsarec_gru_config_t* cfg, const float* x, co
     }
     const float* ylast = y + (long)(L - 1) * B * H;
     if (O > 0) {
-        if (last_only) RET(gru_nt(ylast, weights + wo.out, B, O, H, gru_epi(out, O, weights + wo.bout), s));
-        else RET(gru_nt(y, weights + wo.out, (int)T, O, H, gru_epi(out, O, weights + wo.bout, L, B), s));
+        if (last_only) RET(dense_nt(ylast, weights + wo.out, B, O, H, dense_epi(out, O, weights + wo.bout), s));
+        else RET(dense_nt(y, weights + wo.out, (int)T, O, H, dense_epi(out, O, weights + wo.bout, L, B), s));
     } else {
         if (last_only) gru_swap(ylast, out, 1, B, H, s);
         else gru_swap(y, out, L, B, H, s);
@@ -2430,8 +2459,9 @@ extern "C" int bsarec_gru_fwd(const bsarec_gru_config_t* cfg, const float* x, co
 
 extern "C" int bsarec_gru_bwd(const bsarec_gru_config_t* cfg, const float* x, const float* weights, int last_only, const float* dout,
                               void* workspace, long workspace_bytes, float* dx, float* dweights, void* stream) {
-    RET(gru_args(cfg, x, weights, workspace, workspace_bytes, true));
-    if (!dout || !dx || !dweights || !aligned_to(dout, 16) || !aligned_to(dx, 16) || !aligned_to(dweights, 16)) return -10;
+    RET(gru_check(cfg));
+    RET(ptrs_check({x, weights, dout, workspace, dx, dweights}));
+    if (workspace_bytes < gru_ws(*cfg, true).total * (long)sizeof(float)) return -10;
     const bsarec_gru_config_t& c = *cfg;
     const int B = c.batch, L = c.seq_len, I = c.input_size, H = c.hidden_size, N = c.num_layers, O = c.out_size;
     const long T = (long)B * L;
@@ -2450,10 +2480,8 @@ extern "C" int bsarec_gru_bwd(const bsarec_gru_config_t* cfg, const float* x, co
         const float* yrows = ytop + (last_only ? (long)(L - 1) * B * H : 0);
         const long K = last_only ? B : T;
         if (!last_only) { gru_swap(dout, w + ws.dot, B, L, O, s); d = w + ws.dot; }
-        RET(gru_nn(d, weights + wo.out, (int)K, H, O, gru_epi(w + ws.dya, H), s));
-        RET(gru_tn(d, O, yrows, O, H, K, slab, (long)O * H, 0, w + ws.bpart, s));
-        gru_sum(slab, K, (long)O * H, dweights + wo.out, s);
-        gru_sum(w + ws.bpart, K, O, dweights + wo.bout, s);
+        RET(linear_bwd(d, yrows, weights + wo.out, K, O, H, dense_epi(w + ws.dya, H), slab, w + ws.bpart, dweights + wo.out,
+                       dweights + wo.bout, s));
     } else if (last_only) {
         dy = dout;
     } else {
@@ -2468,23 +2496,19 @@ extern "C" int bsarec_gru_bwd(const bsarec_gru_config_t* cfg, const float* x, co
         P.S = w + ws.s + (long)k * T * 4 * H; P.Y = yk; P.Whh = weights + wo.hh[k]; P.dY = dy;
         P.da = w + ws.a; P.dbn = w + ws.dbn; P.B = B; P.L = L; P.dy_last = (last_only && k == N - 1) ? 1 : 0;
         GRU_DISPATCH(H, gru_seq_bwd_kernel, grid, wg, 0, s, P);
-        // d(in) = da . W_ih: the layer below's dY, or dx through the row map
+        // d(in) = da . W_ih: the layer below's dY, or dx through the row map;  dW_ih = da^T . in over all T rows
+        const EpiGru din = k > 0 ? dense_epi(dy_next, H) : dense_epi(dx, I, nullptr, L, B);
+        RET(linear_bwd(P.da, in, weights + wo.ih[k], T, 3 * H, Ik, din, slab, nullptr, dweights + wo.ih[k], nullptr, s));
         if (k > 0) {
-            RET(gru_nn(P.da, weights + wo.ih[k], (int)T, H, 3 * H, gru_epi(dy_next, H), s));
             const float* t = dy_next;
             dy_next = (dy == dout) ? w + ws.dya : const_cast<float*>(dy);
             dy = t;
-        } else {
-            RET(gru_nn(P.da, weights + wo.ih[0], (int)T, I, 3 * H, gru_epi(dx, I, nullptr, L, B), s));
         }
-        // dW_ih = da^T . in over all T rows
-        RET(gru_tn(P.da, 3 * H, in, 3 * H, Ik, T, slab, 3L * H * Ik, 0, nullptr, s));
-        gru_sum(slab, T, 3L * H * Ik, dweights + wo.ih[k], s);
         // dW_hh = (da_r, da_z | db_n)[t >= 1]^T . y[t - 1]: rows 0 .. 2H from da, rows 2H .. 3H from db_n, over (L - 1) B rows
         const long K = T - B;
-        RET(gru_tn(P.da + 3L * B * H, 3 * H, yk, 2 * H, H, K, slab, 3L * H * H, 0, nullptr, s));
-        RET(gru_tn(P.dbn + (long)B * H, H, yk, H, H, K, slab, 3L * H * H, 2L * H * H, nullptr, s));
-        gru_sum(slab, K, 3L * H * H, dweights + wo.hh[k], s);
+        RET(dense_tn(P.da + 3L * B * H, 3 * H, yk, 2 * H, H, K, slab, 3L * H * H, 0, nullptr, s));
+        RET(dense_tn(P.dbn + (long)B * H, H, yk, H, H, K, slab, 3L * H * H, 2L * H * H, nullptr, s));
+        slab_sum(slab, K, 3L * H * H, dweights + wo.hh[k], s);
     }
     return (int)hipGetLastError();
 }
@@ -2494,7 +2518,7 @@ extern "C" int bsarec_gru_bwd(const bsarec_gru_config_t* cfg, const float* x, co
 // ---------------------------------------------------------------------------------------------
 static int caser_check(const bsarec_caser_config_t* c) {
     if (!c) return -10;
-    if (c->batch < 1 || c->batch > 65536 || c->seq_len < 1 || c->seq_len > 256) return -10;
+    if (!seq_shape_ok(c->batch, c->seq_len, 1)) return -10;
     if (!row_dim_ok(c->width)) return -10;
     if (c->n_h != 4 && c->n_h != 8 && c->n_h != 16 && c->n_h != 32) return -10;
     if (c->n_v < 1 || c->n_v > 16) return -10;
@@ -2528,18 +2552,11 @@ extern "C" long bsarec_caser_workspace_bytes(const bsarec_caser_config_t* cfg, i
     return caser_ws_bytes(*cfg, train != 0);
 }
 
-static int caser_args(const bsarec_caser_config_t* cfg, const float* x, const float* weights, const void* workspace, long workspace_bytes,
-                      bool train) {
-    RET(caser_check(cfg));
-    if (!aligned_to(x, 16) || !aligned_to(weights, 16) || !aligned_to(workspace, 16)) return -10;      // null fails too
-    if (workspace_bytes < caser_ws_bytes(*cfg, train)) return -10;
-    return 0;
-}
-
 extern "C" int bsarec_caser_fwd(const bsarec_caser_config_t* cfg, const float* x, const float* weights, int train, float* z,
                                 void* workspace, long workspace_bytes, void* stream) {
-    RET(caser_args(cfg, x, weights, workspace, workspace_bytes, train != 0));
-    if (!aligned_to(z, 16)) return -10;
+    RET(caser_check(cfg));
+    RET(ptrs_check({x, weights, z, workspace}));
+    if (workspace_bytes < caser_ws_bytes(*cfg, train != 0)) return -10;
     const bsarec_caser_config_t& c = *cfg;
     const CaserW wo = caser_weights(c);
     hipStream_t s = (hipStream_t)stream;
@@ -2556,8 +2573,9 @@ extern "C" int bsarec_caser_fwd(const bsarec_caser_config_t* cfg, const float* x
 
 extern "C" int bsarec_caser_bwd(const bsarec_caser_config_t* cfg, const float* x, const float* weights, const float* dz,
                                 void* workspace, long workspace_bytes, float* dx, float* dweights, void* stream) {
-    RET(caser_args(cfg, x, weights, workspace, workspace_bytes, true));
-    if (!aligned_to(dz, 16) || !aligned_to(dx, 16) || !aligned_to(dweights, 16)) return -10;
+    RET(caser_check(cfg));
+    RET(ptrs_check({x, weights, dz, workspace, dx, dweights}));
+    if (workspace_bytes < caser_ws_bytes(*cfg, true)) return -10;
     const bsarec_caser_config_t& c = *cfg;
     const CaserW wo = caser_weights(c);
     hipStream_t s = (hipStream_t)stream;
@@ -2577,7 +2595,7 @@ extern "C" int bsarec_caser_bwd(const bsarec_caser_config_t* cfg, const float* x
 // ---------------------------------------------------------------------------------------------
 static int fea_check(const bsarec_fea_attn_config_t* c) {
     if (!c) return -10;
-    if (c->batch < 1 || c->batch > 65536 || c->seq_len < 2 || c->seq_len > 256) return -10;
+    if (!seq_shape_ok(c->batch, c->seq_len, 2)) return -10;
     if (!row_dim_ok(c->width)) return -10;
     if (c->lo < 0 || c->lo >= c->hi || c->hi > c->seq_len / 2 + 1) return -10;
     if (c->topk < 1 || c->topk > 32 || c->topk > c->seq_len) return -10;
@@ -2615,8 +2633,7 @@ static FeaP fea_params(const bsarec_fea_attn_config_t& c, void* workspace) {
 extern "C" int bsarec_fea_attn_fwd(const bsarec_fea_attn_config_t* cfg, const float* q, const float* k, const float* v, float* out,
                                    void* workspace, long workspace_bytes, void* stream) {
     RET(fea_check(cfg));
-    if (!aligned_to(q, 16) || !aligned_to(k, 16) || !aligned_to(v, 16) || !aligned_to(out, 16) || !aligned_to(workspace, 16))
-        return -10;                                                                                        // null fails too
+    RET(ptrs_check({q, k, v, out, workspace}));
     if (workspace_bytes < fea_ws(*cfg).total * 4) return -10;
     const bsarec_fea_attn_config_t& c = *cfg;
     hipStream_t s = (hipStream_t)stream;
@@ -2633,9 +2650,7 @@ extern "C" int bsarec_fea_attn_bwd(const bsarec_fea_attn_config_t* cfg, const fl
                                    const float* dout, void* workspace, long workspace_bytes, float* dq, float* dk, float* dv,
                                    void* stream) {
     RET(fea_check(cfg));
-    if (!aligned_to(q, 16) || !aligned_to(k, 16) || !aligned_to(v, 16) || !aligned_to(dout, 16) || !aligned_to(workspace, 16) ||
-        !aligned_to(dq, 16) || !aligned_to(dk, 16) || !aligned_to(dv, 16))
-        return -10;
+    RET(ptrs_check({q, k, v, dout, workspace, dq, dk, dv}));
     if (workspace_bytes < fea_ws(*cfg).total * 4) return -10;
     const bsarec_fea_attn_config_t& c = *cfg;
     hipStream_t s = (hipStream_t)stream;
@@ -2652,7 +2667,7 @@ extern "C" int bsarec_fea_attn_bwd(const bsarec_fea_attn_config_t* cfg, const fl
 // ---------------------------------------------------------------------------------------------
 static int lru_check(const bsarec_lru_config_t* c) {
     if (!c) return -10;
-    if (c->batch < 1 || c->batch > 65536 || c->seq_len < 1 || c->seq_len > 256) return -10;
+    if (!seq_shape_ok(c->batch, c->seq_len, 1)) return -10;
     if (!row_dim_ok(c->width)) return -10;
     return 0;
 }
@@ -2675,7 +2690,7 @@ static LruWs lru_ws(const bsarec_lru_config_t& c, bool train) {
     LruWs w;
     memset(&w, 0, sizeof(w));
     int kc;
-    gru_split(T, &w.ns, &kc);
+    split_k(T, &w.ns, &kc);
     w.nwg = cdiv(c.batch, lru_geom(c.width).seqs);
     long off = 0;
     w.v = off; off += T * 2 * d;
@@ -2701,19 +2716,11 @@ extern "C" long bsarec_lru_workspace_bytes(const bsarec_lru_config_t* cfg, int t
     return lru_ws(*cfg, train != 0).total * (long)sizeof(float);
 }
 
-static int lru_args(const bsarec_lru_config_t* cfg, const float* x, const float* weights, const void* workspace, long workspace_bytes,
-                    bool train) {
-    RET(lru_check(cfg));
-    if (!x || !weights || !workspace) return -10;
-    if (!aligned_to(x, 16) || !aligned_to(weights, 16) || !aligned_to(workspace, 16)) return -10;
-    if (workspace_bytes < lru_ws(*cfg, train).total * (long)sizeof(float)) return -10;
-    return 0;
-}
-
 extern "C" int bsarec_lru_fwd(const bsarec_lru_config_t* cfg, const float* x, const int64_t* ids, const float* weights, int train,
                               float* y, void* workspace, long workspace_bytes, void* stream) {
-    RET(lru_args(cfg, x, weights, workspace, workspace_bytes, train != 0));
-    if (!y || !aligned_to(y, 16)) return -10;
+    RET(lru_check(cfg));
+    RET(ptrs_check({x, weights, y, workspace}));
+    if (workspace_bytes < lru_ws(*cfg, train != 0).total * (long)sizeof(float)) return -10;
     const bsarec_lru_config_t& c = *cfg;
     const int B = c.batch, L = c.seq_len, d = c.width;
     const long T = (long)B * L;
@@ -2722,18 +2729,19 @@ extern "C" int bsarec_lru_fwd(const bsarec_lru_config_t* cfg, const float* x, co
     float* w = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(lru_lambda_kernel, dim3(cdiv(d, 256)), dim3(256), 0, s, weights, w + ws.lam, d);
-    RET(gru_nt(x, weights + wo.win, (int)T, 2 * d, d, gru_epi(w + ws.v, 2 * d, weights + wo.bin), s));
+    RET(dense_nt(x, weights + wo.win, (int)T, 2 * d, d, dense_epi(w + ws.v, 2 * d, weights + wo.bin), s));
     LruFwdP P;
     P.V = w + ws.v; P.H = w + ws.h; P.ids = ids; P.lam = w + ws.lam; P.B = B; P.L = L; P.d = d; P.save_v = train != 0;
     hipLaunchKernelGGL(lru_scan_fwd_kernel, dim3(ws.nwg), dim3(LRU_THREADS), 0, s, P);
-    RET(gru_nt(w + ws.h, weights + wo.wout, (int)T, d, 2 * d, gru_epi(y, d, weights + wo.bout), s));
+    RET(dense_nt(w + ws.h, weights + wo.wout, (int)T, d, 2 * d, dense_epi(y, d, weights + wo.bout), s));
     return (int)hipGetLastError();
 }
 
 extern "C" int bsarec_lru_bwd(const bsarec_lru_config_t* cfg, const float* x, const int64_t* ids, const float* weights, const float* dy,
                               void* workspace, long workspace_bytes, float* dx, float* dweights, void* stream) {
-    RET(lru_args(cfg, x, weights, workspace, workspace_bytes, true));
-    if (!dy || !dx || !dweights || !aligned_to(dy, 16) || !aligned_to(dx, 16) || !aligned_to(dweights, 16)) return -10;
+    RET(lru_check(cfg));
+    RET(ptrs_check({x, weights, dy, workspace, dx, dweights}));
+    if (workspace_bytes < lru_ws(*cfg, true).total * (long)sizeof(float)) return -10;
     const bsarec_lru_config_t& c = *cfg;
     const int B = c.batch, L = c.seq_len, d = c.width;
     const long T = (long)B * L;
@@ -2744,19 +2752,15 @@ extern "C" int bsarec_lru_bwd(const bsarec_lru_config_t* cfg, const float* x, co
     float* slab = w + ws.slab;
     hipLaunchKernelGGL(lru_lambda_kernel, dim3(cdiv(d, 256)), dim3(256), 0, s, weights, w + ws.lam, d);
     // g = dy . W_out;  dW_out = dy^T . [Re h | Im h], db_out = its column sums
-    RET(gru_nn(dy, weights + wo.wout, (int)T, 2 * d, d, gru_epi(w + ws.g, 2 * d), s));
-    RET(gru_tn(dy, d, w + ws.h, d, 2 * d, T, slab, 2L * d * d, 0, w + ws.bpart, s));
-    gru_sum(slab, T, 2L * d * d, dweights + wo.wout, s);
-    gru_sum(w + ws.bpart, T, d, dweights + wo.bout, s);
+    RET(linear_bwd(dy, w + ws.h, weights + wo.wout, T, d, 2 * d, dense_epi(w + ws.g, 2 * d), slab, w + ws.bpart,
+                   dweights + wo.wout, dweights + wo.bout, s));
     LruBwdP P;
     P.G = w + ws.g; P.V = w + ws.v; P.H = w + ws.h; P.ids = ids; P.lam = w + ws.lam; P.part = w + ws.part; P.B = B; P.L = L; P.d = d;
     hipLaunchKernelGGL(lru_scan_bwd_kernel, dim3(ws.nwg), dim3(LRU_THREADS), 0, s, P);
     hipLaunchKernelGGL(lru_param_grad_kernel, dim3(d / 4), dim3(256), 0, s, w + ws.part, ws.nwg, weights, w + ws.lam, d, dweights);
     // dx = du . W_in;  dW_in = du^T . x, db_in = its column sums
-    RET(gru_nn(w + ws.g, weights + wo.win, (int)T, d, 2 * d, gru_epi(dx, d), s));
-    RET(gru_tn(w + ws.g, 2 * d, x, 2 * d, d, T, slab, 2L * d * d, 0, w + ws.bpart, s));
-    gru_sum(slab, T, 2L * d * d, dweights + wo.win, s);
-    gru_sum(w + ws.bpart, T, 2 * d, dweights + wo.bin, s);
+    RET(linear_bwd(w + ws.g, x, weights + wo.win, T, 2 * d, d, dense_epi(dx, d), slab, w + ws.bpart, dweights + wo.win,
+                   dweights + wo.bin, s));
     return (int)hipGetLastError();
 }
 
@@ -2765,7 +2769,7 @@ extern "C" int bsarec_lru_bwd(const bsarec_lru_config_t* cfg, const float* x, co
 // ---------------------------------------------------------------------------------------------
 static int mamba_check(const bsarec_mamba_config_t* c) {
     if (!c) return -10;
-    if (c->batch < 1 || c->batch > 65536 || c->seq_len < 1 || c->seq_len > 256) return -10;
+    if (!seq_shape_ok(c->batch, c->seq_len, 1)) return -10;
     if (!row_dim_ok(c->width)) return -10;
     if (c->expand < 1 || c->expand > 2) return -10;
     if (c->d_state != 4 && c->d_state != 8 && c->d_state != 16 && c->d_state != 32) return -10;
@@ -2799,7 +2803,7 @@ static MambaWs mamba_ws(const bsarec_mamba_config_t& c, bool train) {
     MambaWs w;
     memset(&w, 0, sizeof(w));
     int kc;
-    gru_split(T, &w.ns, &kc);
+    split_k(T, &w.ns, &kc);
     w.nck = cdiv(c.seq_len, MAMBA_CK) - 1;
     w.nslice = cdiv((int)di, MAMBA_THREADS / (int)N);
     w.groups = c.batch < 1024 ? c.batch : 1024;
@@ -2845,21 +2849,14 @@ extern "C" long bsarec_mamba_workspace_bytes(const bsarec_mamba_config_t* cfg, i
 }
 
 struct MambaSpan { const void* p; long bytes; };
-static bool mamba_overlap(const MambaSpan& a, const MambaSpan& b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + (uintptr_t)b.bytes && b0 < a0 + (uintptr_t)a.bytes;
-}
-// every pointer non-null and 16-byte aligned, the workspace large enough, and none of the first `nout` spans (the outputs)
-// overlapping any other span
-static int mamba_args(const bsarec_mamba_config_t* cfg, bool train, long workspace_bytes, const MambaSpan* spans, int n, int nout) {
-    RET(mamba_check(cfg));
-    for (int i = 0; i < n; ++i)
-        if (!aligned_to(spans[i].p, 16)) return -10;
-    if (workspace_bytes < mamba_ws(*cfg, train).total * (long)sizeof(float)) return -10;
+// whether one of the first `nout` spans (the outputs) overlaps any other span
+static bool spans_overlap(const MambaSpan* spans, int n, int nout) {
     for (int i = 0; i < nout; ++i)
-        for (int k = 0; k < n; ++k)
-            if (k != i && mamba_overlap(spans[i], spans[k])) return -10;
-    return 0;
+        for (int k = 0; k < n; ++k) {
+            const uintptr_t a0 = (uintptr_t)spans[i].p, b0 = (uintptr_t)spans[k].p;
+            if (k != i && a0 < b0 + (uintptr_t)spans[k].bytes && b0 < a0 + (uintptr_t)spans[i].bytes) return true;
+        }
+    return false;
 }
 
 #define MAMBA_DISPATCH(N, KERNEL, ...) \
@@ -2878,26 +2875,27 @@ extern "C" int bsarec_mamba_fwd(const bsarec_mamba_config_t* cfg, const float* x
     const long T = (long)B * L, fb = sizeof(float);
     const MambaW wo = mamba_weights(c);
     const MambaSpan spans[] = {{out, T * d * fb}, {workspace, workspace_bytes}, {x, T * d * fb}, {weights, wo.total * fb}};
-    RET(mamba_args(cfg, train != 0, workspace_bytes, spans, 4, 2));
     const MambaWs ws = mamba_ws(c, train != 0);
+    RET(ptrs_check({out, workspace, x, weights}));
+    if (workspace_bytes < ws.total * fb || spans_overlap(spans, 4, 2)) return -10;
     float* w = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
-    RET(gru_nt(x, weights + wo.win, (int)T, 2 * di, d, gru_epi(w + ws.xz, 2 * di), s));
+    RET(dense_nt(x, weights + wo.win, (int)T, 2 * di, d, dense_epi(w + ws.xz, 2 * di), s));
     MambaConvP C;
     memset(&C, 0, sizeof(C));
     C.XZ = w + ws.xz; C.ids = ids; C.W = weights + wo.wconv; C.C = train ? w + ws.c : nullptr; C.U = w + ws.u;
     C.T = T; C.L = L; C.di = di; C.K = K;
     hipLaunchKernelGGL(mamba_conv_fwd_kernel, dim3((unsigned)cdiv(T * (di / 4), 256L)), dim3(256), 0, s, C);
-    RET(gru_nt(w + ws.u, weights + wo.wx, (int)T, R, di, gru_epi(w + ws.delta, R), s));
-    RET(gru_nt(w + ws.u, weights + wo.wx + (long)R * di, (int)T, 2 * N, di, gru_epi(w + ws.bc, 2 * N), s));
-    RET(gru_nt(w + ws.delta, weights + wo.wdt, (int)T, di, R, gru_epi(w + ws.dt, di, weights + wo.bdt), s));
+    RET(dense_nt(w + ws.u, weights + wo.wx, (int)T, R, di, dense_epi(w + ws.delta, R), s));
+    RET(dense_nt(w + ws.u, weights + wo.wx + (long)R * di, (int)T, 2 * N, di, dense_epi(w + ws.bc, 2 * N), s));
+    RET(dense_nt(w + ws.delta, weights + wo.wdt, (int)T, di, R, dense_epi(w + ws.dt, di, weights + wo.bdt), s));
     MambaScanP P;
     memset(&P, 0, sizeof(P));
     P.XZ = w + ws.xz; P.U = w + ws.u; P.DTR = w + ws.dt; P.BC = w + ws.bc; P.Alog = weights + wo.alog; P.D = weights + wo.dd;
     P.ids = ids; P.Y = w + ws.y; P.S = train ? w + ws.s : nullptr; P.HCK = train && ws.nck > 0 ? w + ws.hck : nullptr;
     P.B = B; P.L = L; P.di = di; P.nck = ws.nck;
     MAMBA_DISPATCH(N, mamba_scan_fwd_kernel, dim3(B, ws.nslice), dim3(MAMBA_THREADS), 0, s, P);
-    RET(gru_nt(w + ws.y, weights + wo.wout, (int)T, d, di, gru_epi(out, d), s));
+    RET(dense_nt(w + ws.y, weights + wo.wout, (int)T, d, di, dense_epi(out, d), s));
     return (int)hipGetLastError();
 }
 
@@ -2910,15 +2908,15 @@ extern "C" int bsarec_mamba_bwd(const bsarec_mamba_config_t* cfg, const float* x
     const MambaW wo = mamba_weights(c);
     const MambaSpan spans[] = {{dx, T * d * fb}, {dweights, wo.total * fb}, {workspace, workspace_bytes}, {x, T * d * fb},
                                {weights, wo.total * fb}, {dout, T * d * fb}};
-    RET(mamba_args(cfg, true, workspace_bytes, spans, 6, 3));
     const MambaWs ws = mamba_ws(c, true);
+    RET(ptrs_check({dx, dweights, workspace, x, weights, dout}));
+    if (workspace_bytes < ws.total * fb || spans_overlap(spans, 6, 3)) return -10;
     float* w = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
     float* slab = w + ws.slab;
     // dy = dout . W_out;  dW_out = dout^T . y
-    RET(gru_nn(dout, weights + wo.wout, (int)T, di, d, gru_epi(w + ws.dy, di), s));
-    RET(gru_tn(dout, d, w + ws.y, d, di, T, slab, (long)d * di, 0, nullptr, s));
-    gru_sum(slab, T, (long)d * di, dweights + wo.wout, s);
+    RET(linear_bwd(dout, w + ws.y, weights + wo.wout, T, d, di, dense_epi(w + ws.dy, di), slab, nullptr, dweights + wo.wout,
+                   nullptr, s));
     MambaScanP P;
     memset(&P, 0, sizeof(P));
     P.XZ = w + ws.xz; P.U = w + ws.u; P.DTR = w + ws.dt; P.BC = w + ws.bc; P.Alog = weights + wo.alog; P.D = weights + wo.dd;
@@ -2928,16 +2926,14 @@ extern "C" int bsarec_mamba_bwd(const bsarec_mamba_config_t* cfg, const float* x
     hipLaunchKernelGGL(mamba_rows_sum_kernel, dim3((di * N + di) / 4), dim3(256), 0, s, w + ws.adp, ws.groups, (long)di * N + di,
                        dweights + wo.alog);
     // dxdbl = [ddt . W_dt | dB | dC];  dW_dt = ddt^T . delta, db_dt = its column sums
-    RET(gru_nn(w + ws.ddt, weights + wo.wdt, (int)T, R, di, gru_epi(w + ws.dxdbl, X), s));
+    // (dB | dC land in columns R .. X, the product in columns < R: the two writers of dxdbl do not meet)
     hipLaunchKernelGGL(mamba_bc_sum_kernel, dim3((unsigned)cdiv(T * (2 * N / 4), 256L)), dim3(256), 0, s, w + ws.bcp, ws.nslice, T,
                        2 * N, w + ws.dxdbl, X, R);
-    RET(gru_tn(w + ws.ddt, di, w + ws.delta, di, R, T, slab, (long)di * R, 0, w + ws.bpart, s));
-    gru_sum(slab, T, (long)di * R, dweights + wo.wdt, s);
-    gru_sum(w + ws.bpart, T, di, dweights + wo.bdt, s);
+    RET(linear_bwd(w + ws.ddt, w + ws.delta, weights + wo.wdt, T, di, R, dense_epi(w + ws.dxdbl, X), slab, w + ws.bpart,
+                   dweights + wo.wdt, dweights + wo.bdt, s));
     // du_proj = dxdbl . W_x;  dW_x = dxdbl^T . u
-    RET(gru_nn(w + ws.dxdbl, weights + wo.wx, (int)T, di, X, gru_epi(w + ws.du2, di), s));
-    RET(gru_tn(w + ws.dxdbl, X, w + ws.u, X, di, T, slab, (long)X * di, 0, nullptr, s));
-    gru_sum(slab, T, (long)X * di, dweights + wo.wx, s);
+    RET(linear_bwd(w + ws.dxdbl, w + ws.u, weights + wo.wx, T, X, di, dense_epi(w + ws.du2, di), slab, nullptr, dweights + wo.wx,
+                   nullptr, s));
     MambaConvP C;
     memset(&C, 0, sizeof(C));
     C.XZ = w + ws.xz; C.ids = ids; C.W = weights + wo.wconv; C.C = w + ws.c; C.DU1 = w + ws.du1; C.DU2 = w + ws.du2;
@@ -2946,9 +2942,7 @@ extern "C" int bsarec_mamba_bwd(const bsarec_mamba_config_t* cfg, const float* x
     hipLaunchKernelGGL(mamba_rows_sum_kernel, dim3((di * K + di) / 4), dim3(256), 0, s, w + ws.cvp, ws.conv_wgs, (long)di * K + di,
                        dweights + wo.wconv);
     // dx = dxz . W_in;  dW_in = dxz^T . x
-    RET(gru_nn(w + ws.dxz, weights + wo.win, (int)T, d, 2 * di, gru_epi(dx, d), s));
-    RET(gru_tn(w + ws.dxz, 2 * di, x, 2 * di, d, T, slab, 2L * di * d, 0, nullptr, s));
-    gru_sum(slab, T, 2L * di * d, dweights + wo.win, s);
+    RET(linear_bwd(w + ws.dxz, x, weights + wo.win, T, 2 * di, d, dense_epi(dx, d), slab, nullptr, dweights + wo.win, nullptr, s));
     return (int)hipGetLastError();
 }
 
@@ -3030,15 +3024,6 @@ static int pair_flush_tick(const PairStep& p) {
     return (int)hipGetLastError();
 }
 
-// the pointers of an entry point: p16 aligned to 16 bytes, p8 to 8, loss_out to 4, none null
-static int pair_ptrs_check(std::initializer_list<const void*> p16, std::initializer_list<const void*> p8, const float* loss_out) {
-    for (const void* p : p16)
-        if (!aligned_to(p, 16)) return -10;
-    for (const void* p : p8)
-        if (!aligned_to(p, 8)) return -10;
-    return aligned_to(loss_out, 4) ? 0 : -10;
-}
-
 // an Adam of a step: fp32 arrays only, one gradient source, 16-byte aligned, n floats
 struct StepAdam { const bsarec_adam_t* a; long n; };
 static int pair_adam_check(const bsarec_adam_t* a, long n) {
@@ -3075,7 +3060,7 @@ static int gru4rec_check(const bsarec_gru4rec_config_t* c) {
     RET(gru_check(&c->gru));
     if (c->gru.input_size != c->gru.out_size) return -10;
     if (c->item_size < 2) return -10;
-    if (!(c->dropout >= 0.f && c->dropout < 1.f)) return -10;          // NaN fails both comparisons
+    if (!dropout_ok(c->dropout)) return -10;
     return 0;
 }
 
@@ -3205,7 +3190,7 @@ static int gru4rec_loss_grad(const bsarec_gru4rec_config_t* cfg, const float* it
                              float* d_item_emb, float* dweights, void* workspace, long workspace_bytes,
                              const bsarec_adam_t* tick_adam, const bsarec_gru4rec_head_t* head, hipStream_t s) {
     RET(gru4rec_check(cfg));
-    RET(pair_ptrs_check({item_emb, weights, d_item_emb, dweights, workspace}, {ids, answers, neg_answers, state}, loss_out));
+    RET(ptrs_check({item_emb, weights, d_item_emb, dweights, workspace}, {ids, answers, neg_answers, state}, {loss_out}));
     if (workspace_bytes < gru4rec_ws(*cfg).total * (long)sizeof(float)) return -10;
     if (head) {
         RET(g4c_head_check(head, cfg->gru.batch));
@@ -3274,7 +3259,7 @@ static int lrurec_check(const bsarec_lrurec_config_t* c) {
     RET(lru_check(&c->lru));
     if (c->layers < 1 || c->layers > BSAREC_MAX_LAYERS) return -10;
     if (c->item_size < 2) return -10;
-    if (!(c->dropout >= 0.f && c->dropout < 1.f)) return -10;          // NaN fails both comparisons
+    if (!dropout_ok(c->dropout)) return -10;
     if (!(c->ln_eps > 0.f)) return -10;                                 // NaN fails it
     return 0;
 }
@@ -3301,7 +3286,7 @@ static LrrW lrurec_weights(const bsarec_lrurec_config_t& c) {
 //   dy [T][d] | dz [T][d] | dt [T][d] | du [T][4d] | da [T][d] | dxl [T][d] | dh [B][d] | the CE head's workspace |
 //   slabs of dW1 [ns][4d][d] | of dW2 [ns][d][4d] | of db1 [ns][4d] | of db2 [ns][d] | LayerNorm partials [2 N + 1][2][nb][d] |
 //   the fixed-point accumulator [V][d] of 64-bit words
-// ns: the split-K slices of a product over T rows (gru_split); nb blocks of rows_pb rows: the grid of ln_bwd_kernel
+// ns: the split-K slices of a product over T rows (split_k); nb blocks of rows_pb rows: the grid of ln_bwd_kernel
 struct LrrWs {
     long one, xhat0, rstd0, x, z, blk, blk_stride, dy, dz, dt, du, da, dxl, dh, ce, slab1, slab2, bp1, bp2, lnpart, acc, total;
     long b_a, b_xhat_a, b_rstd_a, b_u, b_xhat_f, b_rstd_f;        // inside a block's region, behind the LRU workspace at 0
@@ -3312,7 +3297,7 @@ static LrrWs lrurec_ws(const bsarec_lrurec_config_t& c) {
     const long B = c.lru.batch, T = B * c.lru.seq_len, d = c.lru.width, N = c.layers, T4 = rup(T, 4);
     LrrWs w;
     memset(&w, 0, sizeof(w));
-    gru_split(T, &w.ns, &w.kc);
+    split_k(T, &w.ns, &w.kc);
     w.nb = std::min(cdiv(T, 64), 256);
     w.rows_pb = (int)rup(cdiv(T, w.nb), 16);
     w.nb = cdiv(T, w.rows_pb);
@@ -3419,11 +3404,9 @@ static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const flo
             DISPATCH_LPR(d, hipLaunchKernelGGL(lrr_add_ln_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)), wg, 0, s, P));
         }
         {   // u = dense_1(a)
-            GemmP g = gemm_defaults((int)T, 4 * d, d);
-            g.lda = d; g.ldb = d; g.A[0] = bw + ws.b_a; g.B[0] = wk + wo.w1;
             auto e = epi_linear<true, false, false>(bw + ws.b_u, 4 * d);
             e.bias[0] = wk + wo.b1;
-            RET((launch_gemm<64, 64, 2, 2, false, false, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_NONE, true)));
+            RET(dense_nt(bw + ws.b_a, wk + wo.w1, (int)T, 4 * d, d, e, s));
         }
         {   // x_{k+1} = LN(Drop(dense_2(gelu(u))) + a)
             GemmP g = gemm_defaults((int)T, d, 4 * d);
@@ -3451,18 +3434,14 @@ static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const flo
         lrurec_ln_bwd<0>(ws, w, 2 + 2 * k, w + ws.dy, bw + ws.b_xhat_f, bw + ws.b_rstd_f, wk + wo.ff_ln,
                          lrurec_drop(c, state, tr, 2 + 2 * k), w + ws.dz, w + ws.dt, T, d, s);
         {   // du = (dt . W2) * gelu'(u)
-            GemmP g = gemm_defaults((int)T, 4 * d, d);
-            g.lda = d; g.ldb = 4 * d; g.A[0] = w + ws.dt; g.B[0] = wk + wo.w2;
             auto e = epi_linear<false, false, true>(w + ws.du, 4 * d);
             e.U = bw + ws.b_u; e.ldu = 4 * d; e.act = 0;
-            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_NONE, true)));
+            RET(dense_nn(w + ws.dt, wk + wo.w2, (int)T, 4 * d, d, e, s));
         }
         {   // da = du . W1 + dz
-            GemmP g = gemm_defaults((int)T, d, 4 * d);
-            g.lda = 4 * d; g.ldb = d; g.A[0] = w + ws.du; g.B[0] = wk + wo.w1;
             auto e = epi_linear<false, true, false>(w + ws.da, d);
             e.R = w + ws.dz; e.ldr = d;
-            RET((launch_gemm<64, 64, 2, 2, false, true, XF_NONE, XF_NONE, false>(g, nox, e, nullptr, 1, s, BSAREC_K_NONE, true)));
+            RET(dense_nn(w + ws.du, wk + wo.w1, (int)T, d, 4 * d, e, s));
         }
         {   // dW1 = du^T . a, dW2 = dt^T . gelu(u), db1 and db2 the column sums of du and dt: split-K slabs in one grouped launch
             GroupedTN G;
@@ -3486,10 +3465,10 @@ static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const flo
             G.tile0[2] = tiles; G.nprob = 2; G.act = 0;
             RET((launch_lds<gemm_grouped_tn_kernel<false, 64>>(dim3(tiles, ws.ns), dim3(GEMM_THREADS),
                                                                GemmSmem<64, 64, true, true, false>::BYTES, s, G)));
-            gru_sum(w + ws.slab1, T, 4L * d * d, dwk + wo.w1, s);
-            gru_sum(w + ws.bp1, T, 4L * d, dwk + wo.b1, s);
-            gru_sum(w + ws.slab2, T, 4L * d * d, dwk + wo.w2, s);
-            gru_sum(w + ws.bp2, T, d, dwk + wo.b2, s);
+            slab_sum(w + ws.slab1, T, 4L * d * d, dwk + wo.w1, s);
+            slab_sum(w + ws.bp1, T, 4L * d, dwk + wo.b1, s);
+            slab_sum(w + ws.slab2, T, 4L * d * d, dwk + wo.w2, s);
+            slab_sum(w + ws.bp2, T, d, dwk + wo.b2, s);
         }
         lrurec_ln_bwd<0>(ws, w, 1 + 2 * k, w + ws.da, bw + ws.b_xhat_a, bw + ws.b_rstd_a, wk + wo.lru_ln,
                          lrurec_drop(c, state, tr, 1 + 2 * k), w + ws.dz, w + ws.dt, T, d, s);
@@ -3523,7 +3502,7 @@ static int lrurec_loss_grad(const bsarec_lrurec_config_t* cfg, const float* item
                             const int64_t* answers, void* state, int train, float* loss_out, float* d_item_emb, float* dweights,
                             void* workspace, long workspace_bytes, const bsarec_adam_t* tick_adam, hipStream_t s) {
     RET(lrurec_check(cfg));
-    RET(pair_ptrs_check({item_emb, weights, d_item_emb, dweights, workspace}, {ids, answers, state}, loss_out));
+    RET(ptrs_check({item_emb, weights, d_item_emb, dweights, workspace}, {ids, answers, state}, {loss_out}));
     if (workspace_bytes < lrurec_ws(*cfg).total * (long)sizeof(float)) return -10;
     return lrurec_run(*cfg, item_emb, weights, ids, answers, state, train, loss_out, d_item_emb, dweights, workspace, tick_adam, s);
 }
@@ -3562,9 +3541,7 @@ extern "C" int bsarec_gru4rec_cand_head(const float* s, const float* item_emb, c
                                         int batch, int width, int item_size, const bsarec_gru4rec_head_t* head, float* loss_out,
                                         float* ds, float* dEc, void* workspace, long workspace_bytes, void* stream) {
     RET(g4c_alone_check(batch, width, item_size, head));
-    for (const void* p : {(const void*)s, (const void*)item_emb, (const void*)ds, (const void*)dEc, (const void*)workspace})
-        if (!aligned_to(p, 16)) return -10;
-    if (!aligned_to(answers, 8) || !aligned_to(neg_answers, 8) || !aligned_to(loss_out, 4)) return -10;
+    RET(ptrs_check({s, item_emb, ds, dEc, workspace}, {answers, neg_answers}, {loss_out}));
     if (workspace_bytes < bsarec_gru4rec_cand_head_workspace_bytes(batch, width, head)) return -10;
     const G4cWs g = g4c_ws(batch, head->candidates, width, 0);
     float* w = (float*)workspace;
@@ -3583,7 +3560,6 @@ extern "C" int bsarec_gru4rec_cand_head(const float* s, const float* item_emb, c
 static bool caser_fc_shape_ok(int B, int F, int d) {
     return B >= 1 && B <= 65536 && F >= 4 && F <= 12288 && F % 4 == 0 && row_dim_ok(d);
 }
-static bool dropout_ok(float p) { return p >= 0.f && p < 1.f; }           // NaN fails both comparisons
 
 extern "C" long bsarec_caser_fc_floats(const bsarec_caser_config_t* cfg) {
     if (caser_check(cfg)) return -10;
@@ -3623,9 +3599,7 @@ static void caser_fc_bwd_launch(const CaserFcP& P, hipStream_t s) {
 extern "C" int bsarec_caser_fc_fwd(int batch, int features, int width, const float* z, const float* fc, const void* state,
                                    int train, float dropout, float* s, void* workspace, long workspace_bytes, void* stream) {
     if (!caser_fc_shape_ok(batch, features, width) || !dropout_ok(dropout)) return -10;
-    for (const void* p : {(const void*)z, (const void*)fc, (const void*)s, (const void*)workspace})
-        if (!aligned_to(p, 16)) return -10;
-    if (!aligned_to(state, 8)) return -10;
+    RET(ptrs_check({z, fc, s, workspace}, {state}));
     if (workspace_bytes < bsarec_caser_fc_workspace_bytes(batch, features, width)) return -10;
     CaserFcP P = caser_fc_params(batch, features, width, z, fc, site0_drop(dropout, state, train != 0), (float*)workspace);
     P.s_out = s;
@@ -3637,10 +3611,7 @@ extern "C" int bsarec_caser_fc_bwd(int batch, int features, int width, const flo
                                    const float* ds, const void* state, int train, float dropout, float* dz, float* dfc,
                                    void* workspace, long workspace_bytes, void* stream) {
     if (!caser_fc_shape_ok(batch, features, width) || !dropout_ok(dropout)) return -10;
-    for (const void* p : {(const void*)z, (const void*)fc, (const void*)s, (const void*)ds, (const void*)dz, (const void*)dfc,
-                          (const void*)workspace})
-        if (!aligned_to(p, 16)) return -10;
-    if (!aligned_to(state, 8)) return -10;
+    RET(ptrs_check({z, fc, s, ds, dz, dfc, workspace}, {state}));
     if (workspace_bytes < bsarec_caser_fc_workspace_bytes(batch, features, width)) return -10;
     CaserFcP P = caser_fc_params(batch, features, width, z, fc, site0_drop(dropout, state, train != 0), (float*)workspace);
     P.s = s; P.ds = ds; P.dz = dz; P.dw = dfc;
@@ -3786,9 +3757,8 @@ static int caser_loss_grad(const bsarec_caser_step_config_t* cfg, const CaserUse
                            const int64_t* neg_answers, void* state, int train, float* loss_out, float* d_item_emb, float* dweights,
                            float* dfc, void* workspace, long workspace_bytes, const bsarec_adam_t* tick_adam, hipStream_t s) {
     RET(caser_step_check(cfg));
-    RET(pair_ptrs_check({item_emb, weights, fc, d_item_emb, dweights, dfc, workspace}, {ids, answers, neg_answers, state},
-                        loss_out));
-    if (u) RET(pair_ptrs_check({u->P, u->fc2, u->dP, u->dfc2}, {u->users}, loss_out));
+    RET(ptrs_check({item_emb, weights, fc, d_item_emb, dweights, dfc, workspace}, {ids, answers, neg_answers, state}, {loss_out}));
+    if (u) RET(ptrs_check({u->P, u->fc2, u->dP, u->dfc2}, {u->users}));
     if (workspace_bytes < (u ? u->ws.total : caser_step_ws(*cfg).total) * (long)sizeof(float)) return -10;
     return caser_run(*cfg, u, item_emb, weights, fc, ids, answers, neg_answers, state, train, loss_out, d_item_emb, dweights, dfc,
                      workspace, tick_adam, s);

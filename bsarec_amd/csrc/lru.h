@@ -8,7 +8,7 @@
 //   du_t = m_t gamma a_t;  z = lhat conj(lambda);  dnu_log = -exp(nu_log) Re z;  dtheta_log = exp(theta_log) Im z
 //
 // Every product (u, y, g, dx, the two weight gradients with the bias gradients as their column sums) goes through the GEMM core
-// as the GRU's do (gru_nt / gru_nn / gru_tn / gru_sum).  What is new here is the scan.  Every activation is [B][L][2d], real
+// as the GRU's do (dense_nt / dense_nn / dense_tn / slab_sum).  What is new here is the scan.  Every activation is [B][L][2d], real
 // half then imaginary half, in the rows' own order: no row map, no transposition.
 //
 // Scan kernels.  A workgroup of 256 threads owns SEQS sequences; a thread owns 4 adjacent channels (two 16-byte loads per step)

@@ -10,7 +10,7 @@
 //   dA_log[j][n] = A sum_t e_t h_{t-1} a_t Delta_t;  dD[j] = sum_t ds_t u_t;  dz_t = dy_t s_t silu'(z_t)
 //
 // Every product (in_proj, the two halves of x_proj, dt_proj, out_proj, their dX and split-K dW, dt_proj.bias's gradient as the
-// column sums of its dW product) goes through the GEMM core as the GRU's do (gru_nt / gru_nn / gru_tn / gru_sum).  dt_proj is a
+// column sums of its dW product) goes through the GEMM core as the GRU's do (dense_nt / dense_nn / dense_tn / slab_sum).  dt_proj is a
 // product too although its K = R may be 4: by count it is T di R multiply-adds, 1 / (2 d / R) of in_proj's, and a per-row dot
 // inside the scan would repeat it in each of the N lanes of a channel.  New here are the convolution and the scan.
 //

@@ -122,6 +122,7 @@ static long long buf[4096];                                       /* never deref
 static int bad = 0, cases = 0;
 static void neg(int rc, int line) { ++cases; if (rc >= 0) { printf("line %d returned %d\n", line, rc); ++bad; } }
 #define NEG(call) neg((int)(call), __LINE__)
+#define REFUSED(call) neg((int)(call) == -10 ? -10 : 0, __LINE__)   /* the code itself: BSAREC's invalid-argument return */
 #define FWD(c, q, k, v, o, ws, wsb) bsarec_fea_attn_fwd(c, q, k, v, o, ws, wsb, 0)
 #define BWD(c, q, k, v, g, ws, wsb, dq, dk, dv) bsarec_fea_attn_bwd(c, q, k, v, g, ws, wsb, dq, dk, dv, 0)
 int main(void) {
@@ -152,6 +153,8 @@ int main(void) {
     NEG(BWD(&ok, P16, P16, P16, P16, P16, w, P16, (float *)P4, P16));
     NEG(BWD(&ok, P16, P16, P16, P16, P16, w, P16, P16, (float *)P4));
     NEG(BWD(&ok, P16, P16, P16, P16, P16, w - 1, P16, P16, P16));
+    REFUSED(BWD(&ok, P4, P16, P16, P16, P16, w, P16, P16, P16));    REFUSED(BWD(&ok, P16, P4, P16, P16, P16, w, P16, P16, P16));
+    REFUSED(BWD(&ok, P16, P16, P4, P16, P16, w, P16, P16, P16));    REFUSED(BWD(&ok, P16, P16, P16, P16, (void *)P4, w, P16, P16, P16));
     printf("%d cases, %d bad, abi %d\n", cases, bad, bsarec_abi_version());
     return bad ? 1 : 0;
 }
@@ -171,7 +174,7 @@ def test_header_is_plain_c_and_every_limit_returns_negative_without_a_gpu(tmp_pa
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.strip().endswith("0 bad, abi 10"), r.stdout
-    assert int(r.stdout.split()[0]) == 13 * 3 + 3 + 13 + 14                          # every NEG line above ran
+    assert int(r.stdout.split()[0]) == 13 * 3 + 3 + 13 + 18                          # every NEG line above ran
 
 
 def _ns(**kw):
