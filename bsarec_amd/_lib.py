@@ -195,6 +195,11 @@ class MambaConfig(C.Structure):
                 ("d_conv", C.c_int), ("dt_rank", C.c_int)]
 
 
+class Mamba4RecConfig(C.Structure):
+    """bsarec_mamba4rec_config_t"""
+    _fields_ = [("mamba", MambaConfig), ("layers", C.c_int), ("item_size", C.c_int), ("dropout", C.c_float), ("ln_eps", C.c_float)]
+
+
 GRU4REC_CAND_MAX = 8192                        # BSAREC_GRU4REC_CAND_MAX: the most candidate columns of a GRU4Rec head
 GRU4REC_LOSSES = {"ce": 1, "top1": 2, "bpr_max": 3}                 # bsarec_gru4rec_head_t.loss
 GRU4REC_CANDIDATES = {"in_batch": 1, "in_batch+sampled": 2}         # bsarec_gru4rec_head_t.candidates
@@ -337,6 +342,12 @@ EXPORTS = {
     "bsarec_mamba_workspace_bytes": (C.c_long, [C.POINTER(MambaConfig), C.c_int]),
     "bsarec_mamba_fwd": (C.c_int, [C.POINTER(MambaConfig)] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
     "bsarec_mamba_bwd": (C.c_int, [C.POINTER(MambaConfig)] + [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 3),
+    "bsarec_mamba4rec_weight_floats": (C.c_long, [C.POINTER(Mamba4RecConfig)]),
+    "bsarec_mamba4rec_workspace_bytes": (C.c_long, [C.POINTER(Mamba4RecConfig)]),
+    "bsarec_mamba4rec_loss_grad": (C.c_int, [C.POINTER(Mamba4RecConfig)] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 +
+                                   [C.c_long, C.c_void_p]),
+    "bsarec_mamba4rec_train_step": (C.c_int, [C.POINTER(Mamba4RecConfig)] + [C.c_void_p] * 2 + [C.POINTER(Adam)] * 2 +
+                                    [C.c_void_p] * 3 + [C.c_long, C.c_void_p]),
     "bsarec_freq_layer_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_int,
                                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsarec_freq_layer_bwd_scratch_floats": (C.c_long, [C.c_int, C.c_int, C.c_int]),

@@ -6,7 +6,8 @@ their model classes have in common, once.
   ``_FlatLayer``    a ``_KernelLayer`` that owns ONE flat fp32 weight tensor whose slices are its parameters (``GruStack``,
                     ``CaserConv``, ``LruLayer``, ``MambaLayer``).
   ``_SiblingModel`` the models' plumbing: seed, generator and dropout, the device check, the catalogue head, the refusals.
-  ``_BlockModel``   the body that LRURec and Mamba4Rec share: embedding, LayerNorm, N blocks of (layer, feed-forward), CE loss.
+  ``_BlockModel``   the body that LRURec and Mamba4Rec share: embedding, LayerNorm, N blocks of (layer, feed-forward), CE loss,
+                    and the one-call training step of its "fused" mode (the flat weight array, the step buffers, the two calls).
 
 A layer writes its parameter shapes, registration and initial values, ``_config`` and the two C calls (``_fwd`` / ``_bwd``); a
 model writes its class attributes, its constructor, ``_encode`` (or its own ``forward`` / ``last_hidden``) and its loss."""
@@ -18,6 +19,8 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
+from . import _fused_step as FS
+from . import _lib as L
 from .model import _CatalogueCeFn
 
 
@@ -153,7 +156,7 @@ class _FlatLayer(_KernelLayer):
 
     def reflatten(self):
         """Makes every parameter a view of one flat tensor again (after ``.to()`` / ``.cuda()`` gave each its own storage).
-        ``_flat`` may itself be a slice of a larger array (LRURecModel with ``lru_step = "fused"``): the test compares addresses,
+        ``_flat`` may itself be a slice of a larger array (a ``_BlockModel`` in its fused mode): the test compares addresses,
         and ``data_ptr()`` of a slice is the address of its first element."""
         ps, base = self.flat_parameters(), self._flat
         if all(p.device == base.device and p.data_ptr() == base.data_ptr() + 4 * o
@@ -338,11 +341,25 @@ class _Block(nn.Module):
 class _BlockModel(_SiblingModel):
     """x = Dropout(LN(E[ids])); per block: z = layer(x, ids); a = LN(Dropout(z) + x); x = LN(Dropout(dense_2(gelu(dense_1(a)))) + a);
     the loss is the full-catalogue cross-entropy of the last position.  ``layer_attr`` names the layer inside a block (the
-    state_dict keys), ``make_layer(d, std)`` builds one."""
+    state_dict keys), ``make_layer(d, std)`` builds one.
+
+    ``args.<step_flag>`` ("torch", the default, or "fused") selects how the model steps; the mode is kept under the flag's name
+    (``model.lru_step``, ``model.mamba_step``).  In the fused mode ``train_step`` is ONE C call, the model owns ONE flat fp32
+    tensor in the layout of that call's ``weights``, every parameter but the item table is a view of it and each layer's
+    ``_flat`` a slice of it, and the instance sets ``torch_optim = False`` and ``own_train_step = True``.  A model supplies
+      step_flag                    the flag's name; ``args.<step_flag>_graph = False`` steps eagerly instead of replaying a graph
+      step_calls                   the prefix of its three C calls: ``<prefix>_workspace_bytes``, ``_loss_grad``, ``_train_step``
+      _param_shapes()              its ``*_param_shapes(width, layers, ...)``: the flat array under the state_dict keys
+      _step_config(B, L)           the config struct of the three calls"""
 
     layer_attr = ""
+    step_flag = ""
+    step_calls = ""
 
     def __init__(self, args, make_layer):
+        mode = getattr(args, self.step_flag, "torch")
+        if mode not in ("torch", "fused"):
+            raise ValueError(f"{self.step_flag} must be 'torch' or 'fused', got {mode!r}")
         super().__init__(args)
         self._refuse_plan_options(args, "the full-catalogue cross-entropy")
         d, N = int(args.hidden_size), int(args.num_hidden_layers)
@@ -362,6 +379,49 @@ class _BlockModel(_SiblingModel):
                     m.weight.normal_(0.0, std)
                 if isinstance(m, nn.Linear):
                     m.bias.zero_()
+        setattr(self, self.step_flag, mode)
+        if mode == "fused":
+            self.torch_optim, self.own_train_step = False, True
+        self._wflat = None                       # the fused mode: the flat weight array (reflatten)
+        self._wslices, _ = _layout(self._param_shapes())       # state_dict key -> (offset, floats, shape) in the flat array
+        self.reflatten()
+
+    def _is_fused(self) -> bool:
+        return getattr(self, self.step_flag) == "fused"
+
+    def _layers(self):
+        return [getattr(blk, self.layer_attr) for blk in self.item_encoder.blocks]
+
+    def _apply(self, fn, recurse=True):
+        out = super()._apply(fn, recurse)         # every layer has flattened itself again by now
+        self.reflatten()
+        return out
+
+    def flat_parameters(self):
+        """Every parameter but the item table, in the order of the flat weight array."""
+        named = dict(self.named_parameters())
+        return [named[k] for k in self._wslices]
+
+    def reflatten(self):
+        """The fused mode: makes every parameter but the item table a view of ONE flat tensor in the layout of the step's
+        ``weights`` and every layer's ``_flat`` a slice of it (at construction, and after ``.to()`` / ``.cuda()`` gave the
+        parameters storages of their own and the layers flattened themselves).  The values do not change.  A no-op in the
+        default mode."""
+        if not self._is_fused():
+            return
+        ps, base = self.flat_parameters(), self._wflat
+        if base is not None and all(p.device == base.device and p.data_ptr() == base.data_ptr() + 4 * o
+                                    for p, (o, n, shp) in zip(ps, self._wslices.values())):
+            return
+        with torch.no_grad():
+            flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps])
+            for p, (o, n, shp) in zip(ps, self._wslices.values()):
+                p.data = flat[o:o + n].view(shp)
+                p.grad = None
+        self._wflat, self._fused = flat, None
+        for k, layer in enumerate(self._layers()):
+            o = self._wslices[f"item_encoder.blocks.{k}.{self.layer_attr}.{next(iter(layer._slices))}"][0]
+            layer._flat, layer._pool = flat[o:o + layer._numel], {}
 
     def _encode(self, input_ids, train: bool):
         """Every layer's output, [x0, x1, .. xN]."""
@@ -380,3 +440,75 @@ class _BlockModel(_SiblingModel):
         """The full-catalogue cross-entropy of the last position: a 0-d tensor."""
         self._require_gpu(input_ids)
         return self.catalogue_ce(self.forward(input_ids)[:, -1, :], answers)
+
+    # ---- the fused step (<step_calls>_loss_grad / _train_step; host side: _fused_step.py) ----
+    def _step_buffers(self):
+        """What the fused step owns beside the parameters: the device step state (seed, step counter, Adam t), both gradient
+        arrays, the Adam moments of the item table ("E") and of the flat weight array ("W"), and per batch shape a workspace,
+        static id buffers and a captured graph.  Built on first use; dropped by ``.to()`` / ``reflatten()`` (a new parameter
+        storage)."""
+        if not self._is_fused():
+            raise self._torch_steps(f" (Trainer does); the one-call step needs {self.step_flag} = 'fused'")
+        self._require_gpu()
+        self.reflatten()
+        E, flat = self.item_embeddings.weight.data, self._wflat
+        if flat.device != E.device or not E.is_contiguous() or E.dtype != torch.float32:
+            raise RuntimeError(f"{self.model_name.lower()}: the item table and the flat weight array must be contiguous fp32 on "
+                               f"one device")
+        self._fused = FS.buffers(self._fused, [("E", E), ("W", flat)], self._stream_seed())
+        return self._fused
+
+    def _slot(self, f, B: int, Lq: int):
+        s = f["slots"].get((B, Lq))
+        if s is None:
+            cfg = self._step_config(B, Lq)
+            nbytes = getattr(L.load(), self.step_calls + "_workspace_bytes")(cfg)
+            if nbytes < 0:
+                raise ValueError(f"{self.model_name.lower()}: unsupported step shape B = {B}, L = {Lq}, N = {cfg.layers}, "
+                                 f"dropout = {self.p_hidden} (1 <= B <= 65536, 1 <= L <= 256, 1 <= N <= {L.MAX_LAYERS}, "
+                                 f"0 <= p < 1)")
+            s = FS.slot(f, (B, Lq), cfg, nbytes, (B, Lq))           # the slot's ``neg`` buffer stays unused
+        return s
+
+    def _fill(self, s, input_ids, answers):
+        self._require_gpu(input_ids)
+        s["ids"].copy_(input_ids)
+        s["ans"].copy_(answers.reshape(-1))
+        return s
+
+    def _loss_grad(self, f, s, train: bool):
+        name = self.step_calls + "_loss_grad"
+        L.check(getattr(L.load(), name)(s["cfg"], f["E"].data_ptr(), f["W"].data_ptr(), s["ids"].data_ptr(), s["ans"].data_ptr(),
+                                        f["state"].data_ptr(), int(train), s["loss"].data_ptr(), f["dE"].data_ptr(),
+                                        f["dW"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], FS.stream(f)), name)
+
+    def loss_and_grads(self, input_ids, answers, train: bool = False):
+        """The loss (0-d tensor) and {state_dict key: gradient} of one batch through the step's ``_loss_grad`` call, no update.
+        ``train``: draw the next dropout masks of the device stream (the step counter advances); else no dropout."""
+        f = self._step_buffers()
+        s = self._fill(self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1])), input_ids, answers)
+        self._loss_grad(f, s, train)
+        grads = OrderedDict([("item_embeddings.weight", f["dE"].clone())])
+        for name, (o, n, shp) in self._wslices.items():
+            grads[name] = f["dW"][o:o + n].view(shp).clone()
+        return s["loss"].clone(), grads
+
+    def _train_step(self, f, s):
+        items, weights = FS.adam_structs(f, self.args)
+        name = self.step_calls + "_train_step"
+        L.check(getattr(L.load(), name)(s["cfg"], s["ids"].data_ptr(), s["ans"].data_ptr(), items, weights, f["state"].data_ptr(),
+                                        s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"], FS.stream(f)), name)
+
+    def train_step(self, input_ids, answers, neg_answers=None, same_target=None):
+        """The fused mode: one optimisation step in one C call -- the step counter, lookup + LayerNorm + Philox dropout, the
+        blocks, the CE head, every gradient, Adam (``args.lr``, ``adam_beta1``, ``adam_beta2``, ``weight_decay``) on the item
+        table and on the flat weight array, in place.  Returns the mean loss as a 0-d device tensor (no host sync; the next step
+        overwrites it).  The call is captured once per batch shape over static id buffers and replayed -- the masks and Adam's t
+        advance on the device, and the capture is one linear chain on one stream, so it has no parallel branches to replay;
+        ``args.<step_flag>_graph = False`` calls eagerly instead.  ``neg_answers`` and ``same_target`` are ignored."""
+        if not self._is_fused():
+            raise self._torch_steps()
+        f = self._step_buffers()
+        s = self._fill(self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1])), input_ids, answers)
+        return FS.train_step(f, s, self.args, getattr(self.args, self.step_flag + "_graph", True), self._loss_grad,
+                             self._train_step)

@@ -3249,30 +3249,69 @@ extern "C" int bsarec_gru4rec_cand_train_step(const bsarec_gru4rec_config_t* cfg
 }
 
 // ---------------------------------------------------------------------------------------------
-// LRURec training step (lrurec_step.h): lookup + LayerNorm + dropout, N blocks of recurrent layer and feed-forward net, the CE head
-// at position L - 1, every gradient, Adam -- plan-less, one linear chain of launches on the caller's stream, no allocation, no
-// host synchronisation.  Launches: 11 + 28 N for a loss and its gradients (one more when train != 0: the step counter), and two
-// Adam launches behind them in a training step.
+// Block-model training step (lrurec_step.h), once for LRURec and Mamba4Rec: lookup + LayerNorm + dropout, N blocks of a sequence
+// layer and a feed-forward net, the CE head at position L - 1, every gradient, Adam -- plan-less, one linear chain of launches on
+// the caller's stream, no allocation, no host synchronisation.  The layer is a description (LrrLayer): its weight and train
+// workspace floats and its two calls.  Launches: 11 + N (21 + the layer's forward and backward) for a loss and its gradients
+// (one more when train != 0: the step counter), and two Adam launches behind them in a training step.
 // ---------------------------------------------------------------------------------------------
-static int lrurec_check(const bsarec_lrurec_config_t* c) {
+// the layer inside a block: z = fwd(x, ids, w) with train = 1, and its true derivative reading what fwd left in ws
+struct LrrLayer {
+    const void* cfg;
+    long weights, ws;                                       // floats of a block's weight array / of the train = 1 workspace
+    int (*fwd)(const void* cfg, const float* x, const int64_t* ids, const float* w, float* z, void* ws, long ws_bytes, hipStream_t s);
+    int (*bwd)(const void* cfg, const float* x, const int64_t* ids, const float* w, const float* dz, void* ws, long ws_bytes,
+               float* dx, float* dw, hipStream_t s);
+};
+// a checked step: the shape, and the layer
+struct LrrStep { int B, L, d, layers, item_size; float dropout, ln_eps; LrrLayer layer; };
+
+// what the two steps' configs share behind their layer's own check
+static int lrr_check(int layers, int item_size, float dropout, float ln_eps) {
+    if (layers < 1 || layers > BSAREC_MAX_LAYERS) return -10;
+    if (item_size < 2) return -10;
+    if (!dropout_ok(dropout)) return -10;
+    if (!(ln_eps > 0.f)) return -10;                                    // NaN fails it
+    return 0;
+}
+
+static int lrurec_step(const bsarec_lrurec_config_t* c, LrrStep* st) {
     if (!c) return -10;
     RET(lru_check(&c->lru));
-    if (c->layers < 1 || c->layers > BSAREC_MAX_LAYERS) return -10;
-    if (c->item_size < 2) return -10;
-    if (!dropout_ok(c->dropout)) return -10;
-    if (!(c->ln_eps > 0.f)) return -10;                                 // NaN fails it
+    RET(lrr_check(c->layers, c->item_size, c->dropout, c->ln_eps));
+    *st = {c->lru.batch, c->lru.seq_len, c->lru.width, c->layers, c->item_size, c->dropout, c->ln_eps,
+           {&c->lru, lru_weights(c->lru).total, lru_ws(c->lru, true).total,
+            [](const void* cfg, const float* x, const int64_t* ids, const float* w, float* z, void* ws, long n, hipStream_t s) {
+                return bsarec_lru_fwd((const bsarec_lru_config_t*)cfg, x, ids, w, 1, z, ws, n, s);
+            },
+            [](const void* cfg, const float* x, const int64_t* ids, const float* w, const float* dz, void* ws, long n, float* dx,
+               float* dw, hipStream_t s) { return bsarec_lru_bwd((const bsarec_lru_config_t*)cfg, x, ids, w, dz, ws, n, dx, dw, s); }}};
+    return 0;
+}
+
+static int mamba4rec_step(const bsarec_mamba4rec_config_t* c, LrrStep* st) {
+    if (!c) return -10;
+    RET(mamba_check(&c->mamba));
+    RET(lrr_check(c->layers, c->item_size, c->dropout, c->ln_eps));
+    *st = {c->mamba.batch, c->mamba.seq_len, c->mamba.width, c->layers, c->item_size, c->dropout, c->ln_eps,
+           {&c->mamba, mamba_weights(c->mamba).total, mamba_ws(c->mamba, true).total,
+            [](const void* cfg, const float* x, const int64_t* ids, const float* w, float* z, void* ws, long n, hipStream_t s) {
+                return bsarec_mamba_fwd((const bsarec_mamba_config_t*)cfg, x, ids, w, 1, z, ws, n, s);
+            },
+            [](const void* cfg, const float* x, const int64_t* ids, const float* w, const float* dz, void* ws, long n, float* dx,
+               float* dw, hipStream_t s) { return bsarec_mamba_bwd((const bsarec_mamba_config_t*)cfg, x, ids, w, dz, ws, n, dx, dw, s); }}};
     return 0;
 }
 
 // offsets (floats) into the flat weight array: LayerNorm.weight | LayerNorm.bias, then per block (`first` + k `stride`) the array
-// of bsarec_lru_fwd | lru.LayerNorm w, b | dense_1 w [4d][d], b [4d] | dense_2 w [d][4d], b [d] | feed_forward.LayerNorm w, b
-struct LrrW { long first, stride, lru_ln, w1, b1, w2, b2, ff_ln, total; };
-static LrrW lrurec_weights(const bsarec_lrurec_config_t& c) {
-    const long d = c.lru.width;
+// of the layer | its LayerNorm w, b | dense_1 w [4d][d], b [4d] | dense_2 w [d][4d], b [d] | feed_forward.LayerNorm w, b
+struct LrrW { long first, stride, layer_ln, w1, b1, w2, b2, ff_ln, total; };
+static LrrW lrr_weights(const LrrStep& c) {
+    const long d = c.d;
     LrrW w;
     w.first = 2 * d;
-    w.lru_ln = lru_weights(c.lru).total;
-    w.w1 = w.lru_ln + 2 * d; w.b1 = w.w1 + 4 * d * d;
+    w.layer_ln = c.layer.weights;
+    w.w1 = w.layer_ln + 2 * d; w.b1 = w.w1 + 4 * d * d;
     w.w2 = w.b1 + 4 * d; w.b2 = w.w2 + 4 * d * d;
     w.ff_ln = w.b2 + d; w.stride = w.ff_ln + 2 * d;
     w.total = w.first + c.layers * w.stride;
@@ -3281,7 +3320,7 @@ static LrrW lrurec_weights(const bsarec_lrurec_config_t& c) {
 
 // Workspace, in floats (every region a multiple of 4), T = B L, T4 = T rounded up to 4:
 //   one [4] | xhat0 [T][d] | rstd0 [T4] | x_0 .. x_N [N + 1][T][d] | z [T][d] |
-//   per block (`blk` + k `blk_stride`): the workspace of bsarec_lru_fwd(train = 1) | a [T][d] | xhat_a [T][d] | rstd_a [T4] |
+//   per block (`blk` + k `blk_stride`): the layer's workspace of train = 1 | a [T][d] | xhat_a [T][d] | rstd_a [T4] |
 //     u [T][4d] | xhat_f [T][d] | rstd_f [T4] |
 //   dy [T][d] | dz [T][d] | dt [T][d] | du [T][4d] | da [T][d] | dxl [T][d] | dh [B][d] | the CE head's workspace |
 //   slabs of dW1 [ns][4d][d] | of dW2 [ns][d][4d] | of db1 [ns][4d] | of db2 [ns][d] | LayerNorm partials [2 N + 1][2][nb][d] |
@@ -3289,27 +3328,27 @@ static LrrW lrurec_weights(const bsarec_lrurec_config_t& c) {
 // ns: the split-K slices of a product over T rows (split_k); nb blocks of rows_pb rows: the grid of ln_bwd_kernel
 struct LrrWs {
     long one, xhat0, rstd0, x, z, blk, blk_stride, dy, dz, dt, du, da, dxl, dh, ce, slab1, slab2, bp1, bp2, lnpart, acc, total;
-    long b_a, b_xhat_a, b_rstd_a, b_u, b_xhat_f, b_rstd_f;        // inside a block's region, behind the LRU workspace at 0
-    long lru_bytes, ce_bytes;
+    long b_a, b_xhat_a, b_rstd_a, b_u, b_xhat_f, b_rstd_f;        // inside a block's region, behind the layer's workspace at 0
+    long layer_bytes, ce_bytes;
     int ns, kc, nb, rows_pb;
 };
-static LrrWs lrurec_ws(const bsarec_lrurec_config_t& c) {
-    const long B = c.lru.batch, T = B * c.lru.seq_len, d = c.lru.width, N = c.layers, T4 = rup(T, 4);
+static LrrWs lrr_ws(const LrrStep& c) {
+    const long B = c.B, T = B * c.L, d = c.d, N = c.layers, T4 = rup(T, 4);
     LrrWs w;
     memset(&w, 0, sizeof(w));
     split_k(T, &w.ns, &w.kc);
     w.nb = std::min(cdiv(T, 64), 256);
     w.rows_pb = (int)rup(cdiv(T, w.nb), 16);
     w.nb = cdiv(T, w.rows_pb);
-    const long lru = lru_ws(c.lru, true).total, ce = ce_workspace_floats((int)B, c.item_size, (int)d);
-    w.lru_bytes = lru * (long)sizeof(float); w.ce_bytes = ce * (long)sizeof(float);
+    const long layer = c.layer.ws, ce = ce_workspace_floats((int)B, c.item_size, (int)d);
+    w.layer_bytes = layer * (long)sizeof(float); w.ce_bytes = ce * (long)sizeof(float);
     long off = 0;
     w.one = off; off += 4;
     w.xhat0 = off; off += T * d;
     w.rstd0 = off; off += T4;
     w.x = off; off += (N + 1) * T * d;
     w.z = off; off += T * d;
-    long b = lru;
+    long b = layer;
     w.b_a = b; b += T * d;
     w.b_xhat_a = b; b += T * d;
     w.b_rstd_a = b; b += T4;
@@ -3336,17 +3375,27 @@ static LrrWs lrurec_ws(const bsarec_lrurec_config_t& c) {
 }
 
 extern "C" long bsarec_lrurec_weight_floats(const bsarec_lrurec_config_t* cfg) {
-    if (lrurec_check(cfg)) return -10;
-    return lrurec_weights(*cfg).total;
+    LrrStep st;
+    return lrurec_step(cfg, &st) ? -10 : lrr_weights(st).total;
 }
 
 extern "C" long bsarec_lrurec_workspace_bytes(const bsarec_lrurec_config_t* cfg) {
-    if (lrurec_check(cfg)) return -10;
-    return lrurec_ws(*cfg).total * (long)sizeof(float);
+    LrrStep st;
+    return lrurec_step(cfg, &st) ? -10 : lrr_ws(st).total * (long)sizeof(float);
+}
+
+extern "C" long bsarec_mamba4rec_weight_floats(const bsarec_mamba4rec_config_t* cfg) {
+    LrrStep st;
+    return mamba4rec_step(cfg, &st) ? -10 : lrr_weights(st).total;
+}
+
+extern "C" long bsarec_mamba4rec_workspace_bytes(const bsarec_mamba4rec_config_t* cfg) {
+    LrrStep st;
+    return mamba4rec_step(cfg, &st) ? -10 : lrr_ws(st).total * (long)sizeof(float);
 }
 
 // dropout site `site` of a step; train = false: no mask, whatever p
-static DropP lrurec_drop(const bsarec_lrurec_config_t& c, const void* state, bool train, int site) {
+static DropP lrr_drop(const LrrStep& c, const void* state, bool train, int site) {
     DropP d = site0_drop(c.dropout, state, train);
     d.site = (uint32_t)site;
     return d;
@@ -3355,7 +3404,7 @@ static DropP lrurec_drop(const bsarec_lrurec_config_t& c, const void* state, boo
 // ln_bwd_kernel over the step's T rows, MODE 0 (y = LN(Drop(z) + res): dz and dt = dz times the mask) or MODE 2 (y = Drop(LN(e)):
 // dz = de); the d(gamma), d(beta) partials go to LayerNorm j's slot of the workspace
 template <int MODE>
-static void lrurec_ln_bwd(const LrrWs& ws, float* w, int j, const float* dy, const float* xhat, const float* rstd, const float* gamma,
+static void lrr_ln_bwd(const LrrWs& ws, float* w, int j, const float* dy, const float* xhat, const float* rstd, const float* gamma,
                           const DropP& drop, float* dz, float* dt, long T, int d, hipStream_t s) {
     LnBranch a;
     memset(&a, 0, sizeof(a));
@@ -3365,15 +3414,15 @@ static void lrurec_ln_bwd(const LrrWs& ws, float* w, int j, const float* dy, con
                                        ws.rows_pb));
 }
 
-// tick_adam: null, or the Adam whose t the step's closing block advances (bsarec_lrurec_train_step)
-static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const float* weights, const int64_t* ids,
+// tick_adam: null, or the Adam whose t the step's closing block advances (a *_train_step)
+static int lrr_run(const LrrStep& c, const float* E, const float* weights, const int64_t* ids,
                       const int64_t* answers, void* state, int train, float* loss_out, float* dE, float* dweights, void* workspace,
                       const bsarec_adam_t* tick_adam, hipStream_t s) {
-    const int B = c.lru.batch, L = c.lru.seq_len, d = c.lru.width, N = c.layers, V = c.item_size;
+    const int B = c.B, L = c.L, d = c.d, N = c.layers, V = c.item_size;
     const long T = (long)B * L, Td = T * d;
     const bool tr = train != 0;
-    const LrrWs ws = lrurec_ws(c);
-    const LrrW wo = lrurec_weights(c);
+    const LrrWs ws = lrr_ws(c);
+    const LrrW wo = lrr_weights(c);
     float* w = (float*)workspace;
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(w + ws.acc);
     const XformP nox = no_xform();
@@ -3387,7 +3436,7 @@ static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const flo
     if (tr) hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(1), 0, s, (uint64_t*)state, (long long*)nullptr, 0);
     {
         LrrEmbedP P;
-        P.E = E; P.ids = ids; P.gamma = weights; P.beta = weights + d; P.eps = c.ln_eps; P.drop = lrurec_drop(c, state, tr, 0);
+        P.E = E; P.ids = ids; P.gamma = weights; P.beta = weights + d; P.eps = c.ln_eps; P.drop = lrr_drop(c, state, tr, 0);
         P.T = T; P.d = d; P.V = V; P.x = X(0); P.xhat = w + ws.xhat0; P.rstd = w + ws.rstd0;
         P.acc = acc; P.acc_n2 = (long)V * d / 2; P.one = w + ws.one;
         DISPATCH_LPR(d, hipLaunchKernelGGL(lrr_embed_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)), wg, 0, s, P));
@@ -3395,11 +3444,11 @@ static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const flo
     for (int k = 0; k < N; ++k) {
         float* bw = blk(k);
         const float* wk = Wb(k);
-        RET(bsarec_lru_fwd(&c.lru, X(k), ids, wk, 1, w + ws.z, bw, ws.lru_bytes, s));
+        RET(c.layer.fwd(c.layer.cfg, X(k), ids, wk, w + ws.z, bw, ws.layer_bytes, s));
         {   // a = LN(Drop(z) + x)
             LrrAddLnP P;
-            P.z = w + ws.z; P.x = X(k); P.gamma = wk + wo.lru_ln; P.beta = wk + wo.lru_ln + d; P.eps = c.ln_eps;
-            P.drop = lrurec_drop(c, state, tr, 1 + 2 * k); P.T = T; P.d = d;
+            P.z = w + ws.z; P.x = X(k); P.gamma = wk + wo.layer_ln; P.beta = wk + wo.layer_ln + d; P.eps = c.ln_eps;
+            P.drop = lrr_drop(c, state, tr, 1 + 2 * k); P.T = T; P.d = d;
             P.a = bw + ws.b_a; P.xhat = bw + ws.b_xhat_a; P.rstd = bw + ws.b_rstd_a;
             DISPATCH_LPR(d, hipLaunchKernelGGL(lrr_add_ln_kernel<LPR>, dim3(std::min(cdiv(T, ROW_THREADS / LPR), 4096)), wg, 0, s, P));
         }
@@ -3412,7 +3461,7 @@ static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const flo
             GemmP g = gemm_defaults((int)T, d, 4 * d);
             g.lda = 4 * d; g.ldb = 4 * d; g.A[0] = bw + ws.b_u; g.B[0] = wk + wo.w2;
             EpiLN<false> e;
-            e.bias = wk + wo.b2; e.R = bw + ws.b_a; e.drop = lrurec_drop(c, state, tr, 2 + 2 * k);
+            e.bias = wk + wo.b2; e.R = bw + ws.b_a; e.drop = lrr_drop(c, state, tr, 2 + 2 * k);
             e.gamma = wk + wo.ff_ln; e.beta = wk + wo.ff_ln + d; e.eps = c.ln_eps;
             e.Y = X(k + 1); e.xhat = bw + ws.b_xhat_f; e.rstd = bw + ws.b_rstd_f;
             e.dsp = nullptr; e.alpha = 0.f; e.oma = 1.f;
@@ -3431,8 +3480,8 @@ static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const flo
         float* bw = blk(k);
         const float* wk = Wb(k);
         float* dwk = dweights + wo.first + (long)k * wo.stride;
-        lrurec_ln_bwd<0>(ws, w, 2 + 2 * k, w + ws.dy, bw + ws.b_xhat_f, bw + ws.b_rstd_f, wk + wo.ff_ln,
-                         lrurec_drop(c, state, tr, 2 + 2 * k), w + ws.dz, w + ws.dt, T, d, s);
+        lrr_ln_bwd<0>(ws, w, 2 + 2 * k, w + ws.dy, bw + ws.b_xhat_f, bw + ws.b_rstd_f, wk + wo.ff_ln,
+                         lrr_drop(c, state, tr, 2 + 2 * k), w + ws.dz, w + ws.dt, T, d, s);
         {   // du = (dt . W2) * gelu'(u)
             auto e = epi_linear<false, false, true>(w + ws.du, 4 * d);
             e.U = bw + ws.b_u; e.ldu = 4 * d; e.act = 0;
@@ -3470,17 +3519,17 @@ static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const flo
             slab_sum(w + ws.slab2, T, 4L * d * d, dwk + wo.w2, s);
             slab_sum(w + ws.bp2, T, d, dwk + wo.b2, s);
         }
-        lrurec_ln_bwd<0>(ws, w, 1 + 2 * k, w + ws.da, bw + ws.b_xhat_a, bw + ws.b_rstd_a, wk + wo.lru_ln,
-                         lrurec_drop(c, state, tr, 1 + 2 * k), w + ws.dz, w + ws.dt, T, d, s);
-        RET(bsarec_lru_bwd(&c.lru, X(k), ids, wk, w + ws.dt, bw, ws.lru_bytes, w + ws.dxl, dwk, s));
+        lrr_ln_bwd<0>(ws, w, 1 + 2 * k, w + ws.da, bw + ws.b_xhat_a, bw + ws.b_rstd_a, wk + wo.layer_ln,
+                         lrr_drop(c, state, tr, 1 + 2 * k), w + ws.dz, w + ws.dt, T, d, s);
+        RET(c.layer.bwd(c.layer.cfg, X(k), ids, wk, w + ws.dt, bw, ws.layer_bytes, w + ws.dxl, dwk, s));
         hipLaunchKernelGGL(lrr_add_kernel, flat_grid, wg, 0, s, w + ws.dxl, w + ws.dz, w + ws.dy, Td / 4);
     }
     // ---- the embedding: de = LNbwd(dy times the mask), every LayerNorm's parameter gradient, the lookup rows onto dE
-    lrurec_ln_bwd<2>(ws, w, 0, w + ws.dy, w + ws.xhat0, w + ws.rstd0, weights, lrurec_drop(c, state, tr, 0), w + ws.dz, nullptr, T, d, s);
+    lrr_ln_bwd<2>(ws, w, 0, w + ws.dy, w + ws.xhat0, w + ws.rstd0, weights, lrr_drop(c, state, tr, 0), w + ws.dz, nullptr, T, d, s);
     {
         LrrLnSumP P;
         P.part = w + ws.lnpart; P.nb = ws.nb; P.d = d; P.dw = dweights;
-        P.first = wo.first; P.stride = wo.stride; P.at_lru = wo.lru_ln; P.at_ff = wo.ff_ln;
+        P.first = wo.first; P.stride = wo.stride; P.at_layer = wo.layer_ln; P.at_ff = wo.ff_ln;
         hipLaunchKernelGGL(lrr_ln_sum_kernel, dim3(2 * N + 1), wg, 0, s, P);
     }
     {
@@ -3498,32 +3547,58 @@ static int lrurec_run(const bsarec_lrurec_config_t& c, const float* E, const flo
     return (int)hipGetLastError();
 }
 
-static int lrurec_loss_grad(const bsarec_lrurec_config_t* cfg, const float* item_emb, const float* weights, const int64_t* ids,
-                            const int64_t* answers, void* state, int train, float* loss_out, float* d_item_emb, float* dweights,
-                            void* workspace, long workspace_bytes, const bsarec_adam_t* tick_adam, hipStream_t s) {
-    RET(lrurec_check(cfg));
+static int lrr_loss_grad(const LrrStep& st, const float* item_emb, const float* weights, const int64_t* ids, const int64_t* answers,
+                         void* state, int train, float* loss_out, float* d_item_emb, float* dweights, void* workspace,
+                         long workspace_bytes, const bsarec_adam_t* tick_adam, hipStream_t s) {
     RET(ptrs_check({item_emb, weights, d_item_emb, dweights, workspace}, {ids, answers, state}, {loss_out}));
-    if (workspace_bytes < lrurec_ws(*cfg).total * (long)sizeof(float)) return -10;
-    return lrurec_run(*cfg, item_emb, weights, ids, answers, state, train, loss_out, d_item_emb, dweights, workspace, tick_adam, s);
+    if (workspace_bytes < lrr_ws(st).total * (long)sizeof(float)) return -10;
+    return lrr_run(st, item_emb, weights, ids, answers, state, train, loss_out, d_item_emb, dweights, workspace, tick_adam, s);
+}
+
+static int lrr_train_step(const LrrStep& st, const int64_t* ids, const int64_t* answers, const bsarec_adam_t* adam_items,
+                          const bsarec_adam_t* adam_weights, void* state, float* loss_out, void* workspace, long workspace_bytes,
+                          hipStream_t s) {
+    const StepAdam adams[] = {{adam_items, (long)st.item_size * st.d}, {adam_weights, lrr_weights(st).total}};
+    RET(pair_adams_check(adams));
+    RET(lrr_loss_grad(st, adam_items->params, adam_weights->params, ids, answers, state, 1, loss_out, adam_grads(adam_items),
+                      adam_grads(adam_weights), workspace, workspace_bytes, adam_items, s));
+    return pair_adams_launch(adams, state, s);
 }
 
 extern "C" int bsarec_lrurec_loss_grad(const bsarec_lrurec_config_t* cfg, const float* item_emb, const float* weights,
                                        const int64_t* ids, const int64_t* answers, void* state, int train, float* loss_out,
                                        float* d_item_emb, float* dweights, void* workspace, long workspace_bytes, void* stream) {
-    return lrurec_loss_grad(cfg, item_emb, weights, ids, answers, state, train, loss_out, d_item_emb, dweights, workspace,
-                            workspace_bytes, nullptr, (hipStream_t)stream);
+    LrrStep st;
+    RET(lrurec_step(cfg, &st));
+    return lrr_loss_grad(st, item_emb, weights, ids, answers, state, train, loss_out, d_item_emb, dweights, workspace,
+                         workspace_bytes, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int bsarec_lrurec_train_step(const bsarec_lrurec_config_t* cfg, const int64_t* ids, const int64_t* answers,
                                         const bsarec_adam_t* adam_items, const bsarec_adam_t* adam_weights, void* state,
                                         float* loss_out, void* workspace, long workspace_bytes, void* stream) {
-    RET(lrurec_check(cfg));
-    const StepAdam adams[] = {{adam_items, (long)cfg->item_size * cfg->lru.width}, {adam_weights, lrurec_weights(*cfg).total}};
-    RET(pair_adams_check(adams));
-    hipStream_t s = (hipStream_t)stream;
-    RET(lrurec_loss_grad(cfg, adam_items->params, adam_weights->params, ids, answers, state, 1, loss_out, adam_grads(adam_items),
-                         adam_grads(adam_weights), workspace, workspace_bytes, adam_items, s));
-    return pair_adams_launch(adams, state, s);
+    LrrStep st;
+    RET(lrurec_step(cfg, &st));
+    return lrr_train_step(st, ids, answers, adam_items, adam_weights, state, loss_out, workspace, workspace_bytes,
+                          (hipStream_t)stream);
+}
+
+extern "C" int bsarec_mamba4rec_loss_grad(const bsarec_mamba4rec_config_t* cfg, const float* item_emb, const float* weights,
+                                          const int64_t* ids, const int64_t* answers, void* state, int train, float* loss_out,
+                                          float* d_item_emb, float* dweights, void* workspace, long workspace_bytes, void* stream) {
+    LrrStep st;
+    RET(mamba4rec_step(cfg, &st));
+    return lrr_loss_grad(st, item_emb, weights, ids, answers, state, train, loss_out, d_item_emb, dweights, workspace,
+                         workspace_bytes, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int bsarec_mamba4rec_train_step(const bsarec_mamba4rec_config_t* cfg, const int64_t* ids, const int64_t* answers,
+                                           const bsarec_adam_t* adam_items, const bsarec_adam_t* adam_weights, void* state,
+                                           float* loss_out, void* workspace, long workspace_bytes, void* stream) {
+    LrrStep st;
+    RET(mamba4rec_step(cfg, &st));
+    return lrr_train_step(st, ids, answers, adam_items, adam_weights, state, loss_out, workspace, workspace_bytes,
+                          (hipStream_t)stream);
 }
 
 static int g4c_alone_check(int B, int d, int V, const bsarec_gru4rec_head_t* head) {

@@ -2,7 +2,8 @@
 // step needs between the pieces the library already has -- the recurrent layer (bsarec_lru_fwd / _bwd, lru.h), the feed-forward
 // products with their epilogues (launch_gemm with EpiLinear / EpiLN and the grouped TN launch, epilogues.h), the LayerNorm
 // backward (ln_bwd_kernel, kernels.h), the CE head (bsarec_ce_head_fwd / _bwd), the flush with the step's closing block
-// (pair_flush_kernel, pair_step.h) and Adam.  Their host side is the LRURec section of bsarec_hip.hip.  All fp32; a row of d floats
+// (pair_flush_kernel, pair_step.h) and Adam.  Their host side is the block-model step of bsarec_hip.hip, which runs the Mamba4Rec
+// step (bsarec_mamba4rec_*, the layer of mamba.h in the recurrent layer's place) through the same kernels.  All fp32; a row of d floats
 // is held by LPR lanes, a float4 per lane, as in kernels.h (d <= 256, d % 4 == 0).  With T = B L rows and E [V][d]:
 //   lrr_embed_kernel      x0[r, :] = Drop_0(LN(E[ids[r]])), xhat and rstd kept for the backward -- no position table; id 0 is an
 //                         ordinary row (nn.Embedding without padding_idx), an id outside [0, V) reads a zero row.  Its lanes also
@@ -128,16 +129,16 @@ __global__ void __launch_bounds__(ROW_THREADS) lrr_add_kernel(const float* __res
 
 // part: [2 N + 1][gamma | beta][nb][d], LayerNorm j's partials as ln_bwd_kernel wrote them (j = 0 the embedding's, 1 + 2 k block
 // k's behind the recurrent layer, 2 + 2 k its feed-forward's).  dw: the flat gradient; LayerNorm j's weight | bias stand at
-// offset 0 (j = 0), first + k stride + at_lru or + at_ff.
+// offset 0 (j = 0), first + k stride + at_layer or + at_ff.
 struct LrrLnSumP {
     const float* part; int nb, d;
-    float* dw; long first, stride, at_lru, at_ff;
+    float* dw; long first, stride, at_layer, at_ff;
 };
 
 __global__ void __launch_bounds__(ROW_THREADS) lrr_ln_sum_kernel(const LrrLnSumP P) {
     __shared__ f32x4 red[ROW_THREADS];
     const int j = blockIdx.x, k = (j - 1) >> 1;
-    float* out = P.dw + (j == 0 ? 0 : P.first + k * P.stride + ((j & 1) ? P.at_lru : P.at_ff));
+    float* out = P.dw + (j == 0 ? 0 : P.first + k * P.stride + ((j & 1) ? P.at_layer : P.at_ff));
     const int Q = P.d / 2, G = ROW_THREADS / Q;              // float4 columns of gamma | beta (<= 128), thread groups (>= 2)
     const int q = threadIdx.x % Q, grp = threadIdx.x / Q;
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;

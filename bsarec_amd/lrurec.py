@@ -11,8 +11,8 @@ parts of the state (``Re(C h)`` with the sign of the imaginary half absorbed int
 libbsarec_hip.so in both directions (bsarec_lru_fwd / bsarec_lru_bwd, csrc/lru.h) and the loss in the catalogue CE head
 (bsarec_ce_head_fwd / _bwd); on the default path the embedding lookup, the LayerNorms, the feed-forward net and the dropout are
 torch ops.  With ``lru_step = "fused"`` the whole training step -- those parts, the item-table gradient and Adam included -- is one
-C call (bsarec_lrurec_train_step, csrc/lrurec_step.h).  There is no CPU path.  The layer's and the model's plumbing is the
-siblings' shared shell (_sibling.py).
+C call (bsarec_lrurec_train_step, csrc/lrurec_step.h).  There is no CPU path.  The layer's and the model's plumbing, the
+fused mode's included, is the siblings' shared shell (_sibling.py).
 """
 from __future__ import annotations
 
@@ -21,7 +21,6 @@ from collections import OrderedDict
 
 import torch
 
-from . import _fused_step as FS
 from . import _lib as L
 from ._sibling import _BlockModel, _FeedForward, _FlatLayer, _Holder, _LayerNorm, _act, _layout  # noqa: F401
 
@@ -150,118 +149,16 @@ class LRURecModel(_BlockModel):
     kernel_family = "LRU"
     model_name = "LRURec"
     layer_attr = "lru"
+    step_flag = "lru_step"
+    step_calls = "bsarec_lrurec"
 
     def __init__(self, args):
-        mode = getattr(args, "lru_step", "torch")
-        if mode not in ("torch", "fused"):
-            raise ValueError(f"lru_step must be 'torch' or 'fused', got {mode!r}")
         r_min, r_max = float(getattr(args, "lru_r_min", 0.8)), float(getattr(args, "lru_r_max", 0.99))
         super().__init__(args, lambda d, std: LruLayer(d, r_min, r_max, std))
-        self.lru_step = mode
-        if mode == "fused":
-            self.torch_optim, self.own_train_step = False, True
-        self._wflat = None                       # lru_step = "fused": the flat weight array (reflatten)
-        # state_dict key -> (offset, floats, shape) in the flat weight array
-        self._wslices, _ = _layout(lrurec_param_shapes(int(args.hidden_size), int(args.num_hidden_layers)))
-        self.reflatten()
 
-    def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)         # every LruLayer has flattened itself again by now
-        self.reflatten()
-        return out
+    def _param_shapes(self):
+        return lrurec_param_shapes(self.LayerNorm.weight.shape[0], len(self.item_encoder.blocks))
 
-    def flat_parameters(self):
-        """Every parameter but the item table, in the order of the flat weight array."""
-        named = dict(self.named_parameters())
-        return [named[k] for k in self._wslices]
-
-    def reflatten(self):
-        """lru_step = "fused": makes every parameter but the item table a view of ONE flat tensor in the layout of
-        bsarec_lrurec_loss_grad's ``weights`` and every ``LruLayer._flat`` a slice of it (at construction, and after ``.to()`` /
-        ``.cuda()`` gave the parameters storages of their own and the layers flattened themselves).  The values do not change.
-        A no-op in the default mode."""
-        if self.lru_step != "fused":
-            return
-        ps, base = self.flat_parameters(), self._wflat
-        if base is not None and all(p.device == base.device and p.data_ptr() == base.data_ptr() + 4 * o
-                                    for p, (o, n, shp) in zip(ps, self._wslices.values())):
-            return
-        with torch.no_grad():
-            flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps])
-            for p, (o, n, shp) in zip(ps, self._wslices.values()):
-                p.data = flat[o:o + n].view(shp)
-                p.grad = None
-        self._wflat, self._fused = flat, None
-        for k, blk in enumerate(self.item_encoder.blocks):
-            o = self._wslices[f"item_encoder.blocks.{k}.lru.nu_log"][0]
-            blk.lru._flat, blk.lru._pool = flat[o:o + blk.lru._numel], {}
-
-    # ---- the fused step (lru_step = "fused"; bsarec_lrurec_loss_grad / bsarec_lrurec_train_step; host side: _fused_step.py) ----
-    def _step_buffers(self):
-        """What the fused step owns beside the parameters: the device step state (seed, step counter, Adam t), both gradient
-        arrays, the Adam moments of the item table ("E") and of the flat weight array ("W"), and per batch shape a workspace,
-        static id buffers and a captured graph.  Built on first use; dropped by ``.to()`` / ``reflatten()`` (a new parameter
-        storage)."""
-        if self.lru_step != "fused":
-            raise self._torch_steps(" (Trainer does); the one-call step needs lru_step = 'fused'")
-        self._require_gpu()
-        self.reflatten()
-        E, flat = self.item_embeddings.weight.data, self._wflat
-        if flat.device != E.device or not E.is_contiguous() or E.dtype != torch.float32:
-            raise RuntimeError("lrurec: the item table and the flat weight array must be contiguous fp32 on one device")
-        self._fused = FS.buffers(self._fused, [("E", E), ("W", flat)], self._stream_seed())
-        return self._fused
-
-    def _slot(self, f, B: int, Lq: int):
-        s = f["slots"].get((B, Lq))
-        if s is None:
-            cfg = L.LruRecConfig(L.LruConfig(B, Lq, self.LayerNorm.weight.shape[0]), len(self.item_encoder.blocks),
-                                 self.item_embeddings.num_embeddings, self.p_hidden, self.LayerNorm.eps)
-            nbytes = L.load().bsarec_lrurec_workspace_bytes(cfg)
-            if nbytes < 0:
-                raise ValueError(f"lrurec: unsupported step shape B = {B}, L = {Lq}, N = {cfg.layers}, dropout = {self.p_hidden} "
-                                 f"(1 <= B <= 65536, 1 <= L <= 256, 1 <= N <= {L.MAX_LAYERS}, 0 <= p < 1)")
-            s = FS.slot(f, (B, Lq), cfg, nbytes, (B, Lq))           # the slot's ``neg`` buffer stays unused
-        return s
-
-    def _fill(self, s, input_ids, answers):
-        self._require_gpu(input_ids)
-        s["ids"].copy_(input_ids)
-        s["ans"].copy_(answers.reshape(-1))
-        return s
-
-    def _loss_grad(self, f, s, train: bool):
-        L.check(L.load().bsarec_lrurec_loss_grad(s["cfg"], f["E"].data_ptr(), f["W"].data_ptr(), s["ids"].data_ptr(),
-                                                 s["ans"].data_ptr(), f["state"].data_ptr(), int(train), s["loss"].data_ptr(),
-                                                 f["dE"].data_ptr(), f["dW"].data_ptr(), s["ws"].data_ptr(), s["nbytes"],
-                                                 FS.stream(f)), "bsarec_lrurec_loss_grad")
-
-    def loss_and_grads(self, input_ids, answers, train: bool = False):
-        """The loss (0-d tensor) and {state_dict key: gradient} of one batch through bsarec_lrurec_loss_grad, no update.
-        ``train``: draw the next dropout masks of the device stream (the step counter advances); else no dropout."""
-        f = self._step_buffers()
-        s = self._fill(self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1])), input_ids, answers)
-        self._loss_grad(f, s, train)
-        grads = OrderedDict([("item_embeddings.weight", f["dE"].clone())])
-        for name, (o, n, shp) in self._wslices.items():
-            grads[name] = f["dW"][o:o + n].view(shp).clone()
-        return s["loss"].clone(), grads
-
-    def _train_step(self, f, s):
-        items, weights = FS.adam_structs(f, self.args)
-        L.check(L.load().bsarec_lrurec_train_step(s["cfg"], s["ids"].data_ptr(), s["ans"].data_ptr(), items, weights,
-                                                  f["state"].data_ptr(), s["loss"].data_ptr(), s["ws"].data_ptr(), s["nbytes"],
-                                                  FS.stream(f)), "bsarec_lrurec_train_step")
-
-    def train_step(self, input_ids, answers, neg_answers=None, same_target=None):
-        """lru_step = "fused": one optimisation step in one C call -- the step counter, lookup + LayerNorm + Philox dropout, the
-        blocks, the CE head, every gradient, Adam (``args.lr``, ``adam_beta1``, ``adam_beta2``, ``weight_decay``) on the item
-        table and on the flat weight array, in place.  Returns the mean loss as a 0-d device tensor (no host sync; the next step
-        overwrites it).  The call is captured once per batch shape over static id buffers and replayed -- the masks and Adam's t
-        advance on the device, and the capture is one linear chain on one stream, so it has no parallel branches to replay;
-        ``args.lru_step_graph = False`` calls eagerly instead.  ``neg_answers`` and ``same_target`` are ignored."""
-        if self.lru_step != "fused":
-            raise self._torch_steps()
-        f = self._step_buffers()
-        s = self._fill(self._slot(f, int(input_ids.shape[0]), int(input_ids.shape[1])), input_ids, answers)
-        return FS.train_step(f, s, self.args, getattr(self.args, "lru_step_graph", True), self._loss_grad, self._train_step)
+    def _step_config(self, B: int, Lq: int):
+        return L.LruRecConfig(L.LruConfig(B, Lq, self.LayerNorm.weight.shape[0]), len(self.item_encoder.blocks),
+                              self.item_embeddings.num_embeddings, self.p_hidden, self.LayerNorm.eps)

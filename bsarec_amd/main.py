@@ -299,6 +299,10 @@ def parse_args(argv=None):
                    help="Mamba4Rec: d_inner / hidden_size, 1 or 2 (default 2)")
     p.add_argument("--mamba_dt_rank", default=argparse.SUPPRESS, type=int_choice("a multiple of 4 in 4..64", range(4, 65, 4)),
                    help="Mamba4Rec: rank of the step-size projection, a multiple of 4 in 4..64 (default 4 ceil(hidden_size / 64))")
+    p.add_argument("--mamba_step", default=argparse.SUPPRESS, choices=("torch", "fused"),
+                   help="Mamba4Rec: step through autograd and torch.optim.Adam (default) or through the one-call HIP step "
+                        "(lookup, LayerNorms, state-space layers, feed-forward nets with Philox dropout, CE head, item-table "
+                        "gradient and Adam in the library)")
     args = p.parse_args(argv)
     if not getattr(args, "lru_r_min", 0.8) < getattr(args, "lru_r_max", 0.99):
         p.error("--lru_r_min / --lru_r_max: expected 0 <= r_min < r_max < 1")

@@ -11,8 +11,10 @@ one block too (the paper's code drops it at num_hidden_layers = 1), the loss is 
 already expands every prefix), and sequences are left-padded with the padding masked INSIDE the layer (the state is 0 until a
 sequence's first item; the paper's code lets the padding's embedding run through the recurrence).  The layer runs in
 libbsarec_hip.so in both directions (bsarec_mamba_fwd / bsarec_mamba_bwd, csrc/mamba.h) and the loss in the catalogue CE head
-(bsarec_ce_head_fwd / _bwd); the embedding lookup, the LayerNorms, the feed-forward net and the dropout are torch ops.  There
-is no CPU path.  The layer's and the model's plumbing is the siblings' shared shell (_sibling.py).
+(bsarec_ce_head_fwd / _bwd); on the default path the embedding lookup, the LayerNorms, the feed-forward net and the dropout are
+torch ops.  With ``mamba_step = "fused"`` the whole training step -- those parts, the item-table gradient and Adam included -- is
+one C call (bsarec_mamba4rec_train_step), built by the block-model driver that LRURec's step uses too.  There is no CPU path.
+The layer's and the model's plumbing, the fused mode's included, is the siblings' shared shell (_sibling.py).
 """
 from __future__ import annotations
 
@@ -36,6 +38,23 @@ def mamba_param_shapes(width: int, expand: int, d_state: int, d_conv: int, dt_ra
     return OrderedDict([("in_proj.weight", (2 * di, d)), ("conv1d.weight", (di, K)), ("conv1d.bias", (di,)),
                         ("x_proj.weight", (R + 2 * N, di)), ("dt_proj.weight", (di, R)), ("dt_proj.bias", (di,)),
                         ("A_log", (di, N)), ("D", (di,)), ("out_proj.weight", (d, di))])
+
+
+def mamba4rec_param_shapes(width: int, layers: int, expand: int, d_state: int, d_conv: int,
+                           dt_rank: int) -> "OrderedDict[str, tuple]":
+    """The tensors of bsarec_mamba4rec_loss_grad's flat weight array under their state_dict keys, in its order
+    (include/bsarec_hip.h): every parameter of Mamba4RecModel but the item table."""
+    d = int(width)
+    shapes = OrderedDict([("LayerNorm.weight", (d,)), ("LayerNorm.bias", (d,))])
+    for k in range(int(layers)):
+        blk = f"item_encoder.blocks.{k}."
+        for name, shp in mamba_param_shapes(d, expand, d_state, d_conv, dt_rank).items():
+            shapes[blk + "mamba." + name] = shp
+        shapes[blk + "mamba.LayerNorm.weight"] = shapes[blk + "mamba.LayerNorm.bias"] = (d,)
+        shapes[blk + "feed_forward.dense_1.weight"], shapes[blk + "feed_forward.dense_1.bias"] = (4 * d, d), (4 * d,)
+        shapes[blk + "feed_forward.dense_2.weight"], shapes[blk + "feed_forward.dense_2.bias"] = (d, 4 * d), (d,)
+        shapes[blk + "feed_forward.LayerNorm.weight"] = shapes[blk + "feed_forward.LayerNorm.bias"] = (d,)
+    return shapes
 
 
 class MambaLayer(_FlatLayer):
@@ -136,18 +155,46 @@ class Mamba4RecModel(_BlockModel):
     (4 ceil(d / 64)).
     Departures from the paper's code: the residual around the layer is kept at num_hidden_layers = 1 too, the loss is taken at
     the last position only, and sequences are left-padded with the padding masked inside the layer.
-    The model steps through calculate_loss / backward / torch.optim.Adam (``torch_optim``), on a single GPU."""
+
+    ``args.mamba_step`` selects how the model steps, single GPU either way:
+      "torch" (the default, also when absent): calculate_loss / backward / torch.optim.Adam (``torch_optim``); the dropout masks
+        are drawn from a torch generator seeded by ``set_seed``.
+      "fused": ``train_step`` is ONE C call (bsarec_mamba4rec_train_step: lookup, every LayerNorm, the state-space layers, the
+        feed-forward nets, the CE head, every gradient, Adam on the item table and on the flat weight array), replayed from a
+        hipGraph per batch shape unless ``args.mamba_step_graph`` is False.  The model then owns ONE flat fp32 tensor in the
+        layout of bsarec_mamba4rec_loss_grad's ``weights`` (``mamba4rec_param_shapes``); every parameter but the item table is a
+        view of it and each ``MambaLayer._flat`` a slice of it, so state_dict keys and shapes are those of the default mode and
+        checkpoints pass between the two.  The instance sets ``torch_optim = False`` and ``own_train_step = True``, which is
+        what Trainer.iteration routes by.  Its dropout masks are the library's Philox stream (site 0 on the embeddings, 1 + 2 k
+        and 2 + 2 k in block k; the step counter of the device state that ``set_seed`` seeds and resets).  The two streams have
+        the same distribution and DIFFERENT draws: the two modes do not train bit for bit alike at p > 0.
+    forward, predict, last_hidden, calculate_loss and evaluation are the same in both modes (torch-generator dropout in training
+    mode)."""
 
     needs_negatives = False
     needs_same_target = False
     torch_optim = True
-    own_train_step = False
+    own_train_step = False                       # mamba_step = "fused": Trainer.iteration calls train_step(input_ids, answers)
     full_logits = None                           # no dense-logits path: the rankings take last_hidden + catalogue_weight
     kernel_family = "Mamba"
     model_name = "Mamba4Rec"
     layer_attr = "mamba"
+    step_flag = "mamba_step"
+    step_calls = "bsarec_mamba4rec"
 
     def __init__(self, args):
         hyper = (int(getattr(args, "mamba_d_state", 16)), int(getattr(args, "mamba_d_conv", 4)),
                  int(getattr(args, "mamba_expand", 2)), getattr(args, "mamba_dt_rank", None))
         super().__init__(args, lambda d, std: MambaLayer(d, *hyper, std))
+
+    def _hyper(self):
+        m = self.item_encoder.blocks[0].mamba
+        return m.width, m.expand, m.d_state, m.d_conv, m.dt_rank
+
+    def _param_shapes(self):
+        d, *hyper = self._hyper()
+        return mamba4rec_param_shapes(d, len(self.item_encoder.blocks), *hyper)
+
+    def _step_config(self, B: int, Lq: int):
+        return L.Mamba4RecConfig(L.MambaConfig(B, Lq, *self._hyper()), len(self.item_encoder.blocks),
+                                 self.item_embeddings.num_embeddings, self.p_hidden, self.LayerNorm.eps)

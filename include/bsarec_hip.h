@@ -1075,6 +1075,58 @@ int bsarec_lrurec_train_step(const bsarec_lrurec_config_t *cfg, const int64_t *i
                              const bsarec_adam_t *adam_items, const bsarec_adam_t *adam_weights, void *state,
                              float *loss_out, void *workspace, long workspace_bytes, void *stream);
 
+/* One Mamba4Rec training step: the LRURec step above with the selective state-space layer inside a block.  The two steps run
+ * through ONE host driver (csrc/bsarec_hip.hip, "Block-model training step") that takes the layer as a description -- its weight
+ * floats, its train = 1 workspace floats, its forward and its backward call -- and the same six row kernels (csrc/lrurec_step.h).
+ * With E = item_emb [V, d], T = B L rows and N = layers blocks,
+ *   x_0 = Drop_0(LN(E[ids])),
+ *   per block k < N:  z = Mamba_k(x_k, ids) (bsarec_mamba_fwd),  a = LN(Drop_{1+2k}(z) + x_k),
+ *                     x_{k+1} = LN(Drop_{2+2k}(dense_2(gelu(dense_1(a)))) + a)       (4 d inner, the erf gelu),
+ *   loss = mean_b cross_entropy(x_N[b, L - 1] . E^T, answers_b)                      (bsarec_ce_head_fwd with ldh = L d).
+ *   `weights` is ONE flat fp32 array in the model's state_dict order -- but for A_log and D, which stay at their place in the
+ *   layer's array --, every tensor at a multiple of 4 floats:
+ *   LayerNorm.weight [d] | LayerNorm.bias [d], then per block the M = bsarec_mamba_weight_floats array of bsarec_mamba_fwd,
+ *   unchanged | mamba.LayerNorm.weight, .bias [d] | dense_1.weight [4d, d] | dense_1.bias [4d] | dense_2.weight [d, 4d] |
+ *   dense_2.bias [d] | feed_forward.LayerNorm.weight, .bias [d];  bsarec_mamba4rec_weight_floats is their sum,
+ *   2 d + N (M + 8 d d + 9 d).
+ *   Everything else is the contract of bsarec_lrurec_loss_grad / bsarec_lrurec_train_step word for word: id 0 an ordinary table
+ * row masked only inside the layer, the Philox dropout stream (element row d + c) and its sites 0, 1 + 2 k, 2 + 2 k, the device
+ * `state` u64[8], train != 0 advancing the step counter first and train = 0 drawing nothing and touching no counter, masks
+ * regenerated in the backward, the backward of a block with bsarec_mamba_bwd in the layer's place -- its dweights go straight
+ * into the block's slice of the flat gradient --, the lookup rows summed in 64-bit fixed point and added onto the head's dense dE
+ * by one flush, Adam's t advanced once in the closing block, the Adam structs (n = V d and n = bsarec_mamba4rec_weight_floats).
+ *   Launches, all on `stream`, one after the other: 11 + 38 N for a loss and its gradients -- per block 7 + 3 forward and
+ * 10 + 18 backward -- (the step counter adds one when train != 0), then one Adam launch per array: 14 + 38 N, 90 for a training
+ * step at N = 2.  No allocation, no host synchronisation, no float atomics, static or launch-sized LDS: capturable as one linear
+ * chain without parallel branches, and a replay of a captured bsarec_mamba4rec_train_step is the NEXT step.  The result does not
+ * depend on what the workspace holds on entry.
+ *   Workspace: bsarec_mamba4rec_workspace_bytes(cfg) bytes (host-only query, no HIP call).  In floats, with T = L B and T4 = T
+ * rounded up to 4: one [4] | xhat0 [T, d] | rstd0 [T4] | x_0 .. x_N [N + 1][T, d] | z [T, d] | per block: the whole workspace of
+ * bsarec_mamba_fwd(train = 1), its backward scratch included, a [T, d], xhat_a [T, d], rstd_a [T4], u [T, 4d], xhat_f [T, d],
+ * rstd_f [T4] | dy, dz, dt [T, d] each | du [T, 4d] | da, dxl [T, d] each | dh [B, d] | the workspace of bsarec_ce_head_fwd |
+ * slabs of dW1 [ns][4d, d], of dW2 [ns][d, 4d], of db1 [ns][4d], of db2 [ns][d] (ns split-K slices, a function of T) | LayerNorm
+ * partials [2 N + 1][2][nb][d] (nb <= 256) | the accumulator, V d 64-bit words.
+ *   Limits (else < 0 before any HIP call): cfg->mamba inside the limits of bsarec_mamba_workspace_bytes; the rest as for
+ * bsarec_lrurec_*: 1 <= layers <= BSAREC_MAX_LAYERS; item_size >= 2; 0 <= dropout < 1 and ln_eps > 0 (NaN refused); every pointer
+ * non-null; the float arrays (Adam's four included) and the workspace 16-byte aligned, ids / answers / state 8-byte, loss_out
+ * 4-byte; workspace_bytes at least the queried size; adam_*->n as above.  Outputs may not alias inputs, each other or the
+ * workspace. */
+typedef struct {
+    bsarec_mamba_config_t mamba;       /* B, L, d, expand, d_state, d_conv, dt_rank: the limits of bsarec_mamba_workspace_bytes */
+    int layers;                        /* N, 1 .. BSAREC_MAX_LAYERS */
+    int item_size;                     /* V >= 2 */
+    float dropout;                     /* p in [0, 1), NaN refused */
+    float ln_eps;                      /* > 0; 1e-12 in the model */
+} bsarec_mamba4rec_config_t;
+long bsarec_mamba4rec_weight_floats(const bsarec_mamba4rec_config_t *cfg);
+long bsarec_mamba4rec_workspace_bytes(const bsarec_mamba4rec_config_t *cfg);
+int bsarec_mamba4rec_loss_grad(const bsarec_mamba4rec_config_t *cfg, const float *item_emb, const float *weights,
+                               const int64_t *ids, const int64_t *answers, void *state, int train, float *loss_out,
+                               float *d_item_emb, float *dweights, void *workspace, long workspace_bytes, void *stream);
+int bsarec_mamba4rec_train_step(const bsarec_mamba4rec_config_t *cfg, const int64_t *ids, const int64_t *answers,
+                                const bsarec_adam_t *adam_items, const bsarec_adam_t *adam_weights, void *state,
+                                float *loss_out, void *workspace, long workspace_bytes, void *stream);
+
 /* Tag kernel launches of one id with hipEvents for in-process roofline timing (bench.py):
  * when set, every launch of kernel class `kclass` (see BSAREC_K_*) on the next calls of THIS plan is bracketed
  * by hipEventRecord on the launch stream; bsarec_profile_read returns the summed milliseconds and

@@ -8,7 +8,7 @@
 
 Three models of the same shape, everything allocated (and the graph captured) first; 20 warm-up and 200 timed steps, the three
 paths alternating step by step, an event pair around each step.  Per shape one JSON line: median / min / max milliseconds of
-each path and the ratios of the medians.  The host stays ahead of the device only as far as one step: an event pair is read
+each path, the ratios of the medians, and whether the replayed step's median lies below the torch step's minimum.  The host stays ahead of the device only as far as one step: an event pair is read
 back after every step, so a path that is bound by launching from the host shows that cost."""
 import argparse
 import json
@@ -26,7 +26,9 @@ def stats(ms):
     return {"median": round(float(np.median(t)), 4), "min": round(float(t.min()), 4), "max": round(float(t.max()), 4)}
 
 
-def main():
+def main(model_name="LRURecModel", flag="lru_step", tool="lrurec_step_time"):
+    """``model_name``: the block model to time; ``flag``: the name of its step flag; ``tool``: the name in the tool's messages
+    (tools/mamba4rec_step_time.py passes its own)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
@@ -38,19 +40,20 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[256, 1024])
     a = ap.parse_args()
     if not torch.cuda.is_available():
-        raise SystemExit("lrurec_step_time: no GPU (there is nothing to measure on a CPU)")
-    from bsarec_amd import LRURecModel
+        raise SystemExit(f"{tool}: no GPU (there is nothing to measure on a CPU)")
+    import bsarec_amd
+    Model = getattr(bsarec_amd, model_name)
     L, d, V, N = a.seq_len, a.hidden, a.items, a.layers
     for B in a.batches:
         def model(**kw):
             torch.manual_seed(B + N)
-            m = LRURecModel(argparse.Namespace(item_size=V, hidden_size=d, num_hidden_layers=N, max_seq_length=L,
-                                               hidden_dropout_prob=a.dropout, initializer_range=0.02, lr=1e-3, adam_beta1=0.9,
-                                               adam_beta2=0.999, weight_decay=0.0, **kw)).cuda()
+            m = Model(argparse.Namespace(item_size=V, hidden_size=d, num_hidden_layers=N, max_seq_length=L,
+                                         hidden_dropout_prob=a.dropout, initializer_range=0.02, lr=1e-3, adam_beta1=0.9,
+                                         adam_beta2=0.999, weight_decay=0.0, **kw)).cuda()
             m.train()
             m.set_seed(42)
             return m
-        mt, me, mg = model(), model(lru_step="fused", lru_step_graph=False), model(lru_step="fused")
+        mt, me, mg = model(), model(**{flag: "fused", flag + "_graph": False}), model(**{flag: "fused"})
         g = torch.Generator(device="cuda").manual_seed(B + N)
         ids = torch.randint(1, V, (B, L), device="cuda", generator=g)
         ans = torch.randint(1, V, (B,), device="cuda", generator=g)
@@ -88,6 +91,7 @@ def main():
         line.update({f"{k}_ms": stats(v) for k, v in ms.items()})
         line["eager_over_torch"] = round(med["eager"] / med["torch"], 3)
         line["graph_over_torch"] = round(med["graph"] / med["torch"], 3)
+        line["graph_median_below_torch_min"] = bool(med["graph"] < min(ms["torch"]))
         print(json.dumps(line), flush=True)
 
 
