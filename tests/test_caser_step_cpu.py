@@ -3,16 +3,13 @@ double on the twin model, the new symbols and their bindings, the header as plai
 return < 0 before any HIP call), the command-line flag and the model's mode switch."""
 import argparse
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-from conftest import ROOT  # noqa: E402
+import abi_cases as A  # noqa: E402
 import caser_step_ref as S  # noqa: E402
 from test_caser_cpu import Twin  # noqa: E402
 
@@ -83,23 +80,12 @@ NAMES = ("bsarec_caser_fc_floats", "bsarec_caser_fc_workspace_bytes", "bsarec_ca
 
 def test_symbols_are_exported_and_bound():
     from bsarec_amd import _lib
-    lib = _lib.load()
-    for name in NAMES:
-        assert name in _lib.EXPORTS
-        assert getattr(lib, name).argtypes == _lib.EXPORTS[name][1]
-        assert getattr(lib, name).restype == _lib.EXPORTS[name][0]
-    n = {k: len(_lib.EXPORTS[k][1]) for k in NAMES}
-    assert n["bsarec_caser_fc_fwd"] == 12 and n["bsarec_caser_fc_bwd"] == 15
-    assert n["bsarec_caser_loss_grad"] == 16 and n["bsarec_caser_train_step"] == 12
-    assert [f for f, _ in _lib.CaserStepConfig._fields_] == ["conv", "item_size", "dropout"]        # the eighth new name: the struct
-    assert C.sizeof(_lib.CaserStepConfig) == C.sizeof(_lib.CaserConfig) + 8
-    assert lib.bsarec_abi_version() == 10 and _lib.ABI_VERSION == 10
+    nargs = {"bsarec_caser_fc_fwd": 12, "bsarec_caser_fc_bwd": 15, "bsarec_caser_loss_grad": 16, "bsarec_caser_train_step": 12}
+    A.check_symbols(NAMES, nargs, _lib.CaserStepConfig, ["conv", "item_size", "dropout"],      # the eighth new name: the struct
+                    C.sizeof(_lib.CaserConfig) + 8)
 
 
 def test_header_block_is_plain_c99_and_links(tmp_path):
-    lib_dir = os.path.join(ROOT, "bsarec_amd")
-    if not os.path.exists(os.path.join(lib_dir, "libbsarec_hip.so")) or not shutil.which("gcc"):
-        pytest.skip("library or gcc missing")
     src = r"""
 #include "bsarec_hip.h"
 #include <stdio.h>
@@ -122,14 +108,7 @@ int main(void) {
     return (ff && fb && lg && ts && bsarec_abi_version() == 10 && ws > cws && cws > 0 && bad < 0) ? 0 : 1;
 }
 """
-    f = tmp_path / "host.c"
-    f.write_text(src)
-    exe = tmp_path / "host"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(f), "-o", str(exe),
-                    "-L", lib_dir, "-lbsarec_hip", f"-Wl,-rpath,{lib_dir}"], check=True, capture_output=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    ver, ws, cws, fc, fws, bad = (int(v) for v in r.stdout.split())
+    ver, ws, cws, fc, fws, bad = A.run_c99(tmp_path, src)
     Bq, Lq, d, Vq, Fq = 256, 50, 64, 3417, 4 * 64 + 16 * 50
     T = Bq * Lq
     assert ver == 10 and fc == d * Fq + d and fws == 4 * Bq * Fq
@@ -150,19 +129,9 @@ PTRS16 = {"bsarec_caser_loss_grad": ["item_emb", "weights", "fc", "d_item_emb", 
           "bsarec_caser_train_step": ["workspace"]}
 PTRS8 = ["ids", "answers", "neg_answers", "state"]
 ADAMS = ("adam_items", "adam_weights", "adam_fc")
-ADAM_PTRS = ["params", "grads", "exp_avg", "exp_avg_sq"]
-CASES = [(n, c) for n in ENTRY for c in BAD_CFG] + [(n, dict(cfg=None)) for n in ENTRY]
-CASES += [(n, {p: v}) for n in ENTRY for p in PTRS16[n] + PTRS8 for v in (None, "p+4")]
-CASES += [(n, dict(loss_out=v)) for n in ENTRY for v in (None, "p+2")]
-CASES += [(n, dict(workspace_bytes=v)) for n in ENTRY for v in (0, "short")]
-T = "bsarec_caser_train_step"
-CASES += [(T, {a: None}) for a in ADAMS]
-CASES += [(T, {f"{a}.{p}": v}) for a in ADAMS for p in ADAM_PTRS for v in (None, "p+4")]
-CASES += [(T, {f"{a}.n": v}) for a in ADAMS for v in ("n+4", "n-4", 0)]
-CASES += [(T, {f"{a}.{k}": v}) for a in ADAMS
-          for k, v in (("shadow_bf16", "p"), ("grads2", "p"), ("grads2_n", 4), ("n_grad_srcs", 1), ("wimage_plan", "p"))]
-CASES += [(T, {"adam_weights.lr": 2e-3}), (T, {"adam_fc.lr": 2e-3}), (T, {"adam_weights.beta1": 0.8}), (T, {"adam_fc.beta1": 0.8}),
-          (T, {"adam_items.beta2": 0.99}), (T, {"adam_fc.beta2": 0.99})]
+CASES = A.step_cases(ENTRY, BAD_CFG, PTRS16, PTRS8, ADAMS,
+                     hyper=[{"adam_weights.lr": 2e-3}, {"adam_fc.lr": 2e-3}, {"adam_weights.beta1": 0.8}, {"adam_fc.beta1": 0.8},
+                            {"adam_items.beta2": 0.99}, {"adam_fc.beta2": 0.99}])
 
 
 def _cfg(**kw):
@@ -172,8 +141,10 @@ def _cfg(**kw):
     return _lib.CaserStepConfig(_lib.CaserConfig(*[c[k] for k in CONV]), c["item_size"], c["dropout"])
 
 
-def _id(n, c):
-    return f"{n[13:]}-" + "-".join(f"{k}={v}" for k, v in c.items())
+SPEC = A.spec(GOOD, _cfg, ENTRY, PTRS16, PTRS8, need=lambda lib: lib.bsarec_caser_step_workspace_bytes(_cfg()),
+              adam_n=lambda lib: {"adam_items": GOOD["item_size"] * GOOD["width"],
+                                  "adam_weights": lib.bsarec_caser_weight_floats(_cfg().conv),
+                                  "adam_fc": lib.bsarec_caser_fc_floats(_cfg().conv)})
 
 
 def test_workspace_and_size_queries():
@@ -194,30 +165,9 @@ def test_workspace_and_size_queries():
         assert lib.bsarec_caser_fc_workspace_bytes(*shape) < 0, shape
 
 
-@pytest.mark.parametrize("name,change", CASES, ids=[_id(n, c) for n, c in CASES])
+@pytest.mark.parametrize("name,change", CASES, ids=A.ids(CASES, "bsarec_caser_"))
 def test_invalid_arguments_return_negative_without_a_gpu(name, change):
-    from bsarec_amd import _lib
-    lib = _lib.load()
-    buf = (C.c_byte * 4096)()
-    p = C.addressof(buf) + (-C.addressof(buf)) % 16           # a 16-byte aligned host address (never dereferenced)
-    need = lib.bsarec_caser_step_workspace_bytes(_cfg())
-    n = {"adam_items": GOOD["item_size"] * GOOD["width"], "adam_weights": lib.bsarec_caser_weight_floats(_cfg().conv),
-         "adam_fc": lib.bsarec_caser_fc_floats(_cfg().conv)}
-    adam = {a: _lib.Adam(p, p, p, p, n[a], 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, None, 0) for a in n}
-    kw = dict(cfg=_cfg(), item_emb=p, weights=p, fc=p, ids=p, answers=p, neg_answers=p, state=p, train=1, loss_out=p, d_item_emb=p,
-              dweights=p, dfc=p, workspace=p, workspace_bytes=need, stream=None, **adam)
-    for k, v in change.items():
-        if k in GOOD:
-            kw["cfg"] = _cfg(**change)
-        elif "." in k:
-            a, field = k.split(".")
-            v = {"p": p, "p+4": p + 4, "n+4": n[a] + 4, "n-4": n[a] - 4}.get(v, v) if isinstance(v, str) else v
-            if field == "n_grad_srcs":
-                adam[a].grad_srcs[0] = p
-            setattr(adam[a], field, v)
-        else:
-            kw[k] = {"p+4": p + 4, "p+2": p + 2, "short": need - 1}.get(v, v) if isinstance(v, str) else v
-    assert getattr(lib, name)(*[kw[k] for k in ENTRY[name]]) < 0
+    assert A.call(SPEC, name, change) < 0
 
 
 FC_FWD = ["batch", "features", "width", "z", "fc", "state", "train", "dropout", "s", "workspace", "workspace_bytes", "stream"]
@@ -235,7 +185,7 @@ FC_CASES += [(n, dict(state=v)) for n in FC_ENTRY for v in (None, "p+4")]
 FC_CASES += [(n, dict(workspace_bytes=v)) for n in FC_ENTRY for v in (0, "short")]
 
 
-@pytest.mark.parametrize("name,change", FC_CASES, ids=[_id(n, c) for n, c in FC_CASES])
+@pytest.mark.parametrize("name,change", FC_CASES, ids=A.ids(FC_CASES, "bsarec_caser_"))
 def test_invalid_fc_arguments_return_negative_without_a_gpu(name, change):
     from bsarec_amd import _lib
     lib = _lib.load()
@@ -262,12 +212,7 @@ def _args(**kw):
 
 
 def test_command_line_flag():
-    from bsarec_amd.main import parse_args
-    assert not hasattr(parse_args([]), "caser_step")               # absent unless given: the logged arguments stay as they were
-    assert parse_args(["--model_type", "Caser", "--caser_step", "fused"]).caser_step == "fused"
-    assert parse_args(["--caser_step", "torch"]).caser_step == "torch"
-    with pytest.raises(SystemExit):
-        parse_args(["--caser_step", "graph"])
+    A.check_flag("caser_step", "Caser")
 
 
 def test_mode_switch_and_fc1_views_on_the_host():

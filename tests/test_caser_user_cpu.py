@@ -4,16 +4,13 @@ and their bindings, the header as plain C, the argument limits of the entry poin
 model's refusals, the fc2 views and the command-line flag."""
 import argparse
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-from conftest import ROOT  # noqa: E402
+import abi_cases as A  # noqa: E402
 import caser_step_ref as S  # noqa: E402
 import caser_user_ref as UR  # noqa: E402
 from test_caser_cpu import TorchConv  # noqa: E402
@@ -235,22 +232,11 @@ NAMES = ("bsarec_caser_fc2_floats", "bsarec_caser_user_step_workspace_bytes", "b
 
 def test_symbols_are_exported_and_bound():
     from bsarec_amd import _lib
-    lib = _lib.load()
-    for name in NAMES:
-        assert name in _lib.EXPORTS
-        assert getattr(lib, name).argtypes == _lib.EXPORTS[name][1]
-        assert getattr(lib, name).restype == _lib.EXPORTS[name][0]
-    n = {k: len(_lib.EXPORTS[k][1]) for k in NAMES}
-    assert n["bsarec_caser_user_loss_grad"] == 21 and n["bsarec_caser_user_train_step"] == 15
-    assert [f for f, _ in _lib.CaserUserStepConfig._fields_] == ["step", "num_users"]
-    assert C.sizeof(_lib.CaserUserStepConfig) == C.sizeof(_lib.CaserStepConfig) + 4
-    assert lib.bsarec_abi_version() == 10 and _lib.ABI_VERSION == 10          # additive: the version stays
+    A.check_symbols(NAMES, {"bsarec_caser_user_loss_grad": 21, "bsarec_caser_user_train_step": 15}, _lib.CaserUserStepConfig,
+                    ["step", "num_users"], C.sizeof(_lib.CaserStepConfig) + 4)
 
 
 def test_header_block_is_plain_c99_and_links(tmp_path):
-    lib_dir = os.path.join(ROOT, "bsarec_amd")
-    if not os.path.exists(os.path.join(lib_dir, "libbsarec_hip.so")) or not shutil.which("gcc"):
-        pytest.skip("library or gcc missing")
     src = r"""
 #include "bsarec_hip.h"
 #include <stdio.h>
@@ -271,14 +257,7 @@ int main(void) {
     return (lg && ts && bsarec_abi_version() == 10 && ws > sws && sws > 0 && bad < 0) ? 0 : 1;
 }
 """
-    f = tmp_path / "host.c"
-    f.write_text(src)
-    exe = tmp_path / "host"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(f), "-o", str(exe),
-                    "-L", lib_dir, "-lbsarec_hip", f"-Wl,-rpath,{lib_dir}"], check=True, capture_output=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    ver, ws, sws, fc2, bad = (int(v) for v in r.stdout.split())
+    ver, ws, sws, fc2, bad = A.run_c99(tmp_path, src)
     Bq, d, Uq = 256, 64, 6040
     assert ver == 10 and fc2 == d * 2 * d + d
     assert ws == sws + 4 * (2 * Bq * d + Bq * d + Bq * d + 2 * Bq * d + 2 * Uq * d)      # x2 | s | ds | dx2 | the user accumulator
@@ -298,19 +277,11 @@ PTRS16 = {"bsarec_caser_user_loss_grad": ["item_emb", "user_emb", "weights", "fc
           "bsarec_caser_user_train_step": ["workspace"]}
 PTRS8 = ["ids", "users", "answers", "neg_answers", "state"]
 ADAMS = ("adam_items", "adam_users", "adam_weights", "adam_fc", "adam_fc2")
-ADAM_PTRS = ["params", "grads", "exp_avg", "exp_avg_sq"]
-CASES = [(n, c) for n in ENTRY for c in BAD_CFG] + [(n, dict(cfg=None)) for n in ENTRY]
-CASES += [(n, {p: v}) for n in ENTRY for p in PTRS16[n] + PTRS8 for v in (None, "p+4")]
-CASES += [(n, dict(loss_out=v)) for n in ENTRY for v in (None, "p+2")]
-CASES += [(n, dict(workspace_bytes=v)) for n in ENTRY for v in (0, "short", "item-only")]
-T = "bsarec_caser_user_train_step"
-CASES += [(T, {a: None}) for a in ADAMS]
-CASES += [(T, {f"{a}.{p}": v}) for a in ("adam_users", "adam_fc2") for p in ADAM_PTRS for v in (None, "p+4")]
-CASES += [(T, {f"{a}.n": v}) for a in ADAMS for v in ("n+4", "n-4", 0)]
-CASES += [(T, {f"{a}.{k}": v}) for a in ("adam_users", "adam_fc2")
-          for k, v in (("shadow_bf16", "p"), ("grads2", "p"), ("grads2_n", 4), ("n_grad_srcs", 1), ("wimage_plan", "p"))]
-CASES += [(T, {f"{a}.{k}": v}) for a in ADAMS[1:] for k, v in (("lr", 2e-3), ("beta1", 0.8), ("beta2", 0.99))]
-CASES += [(T, {"adam_items.lr": 2e-3})]
+# the three Adams of the item-only step are walked through in test_caser_step_cpu.py: here the two new ones, and every n
+CASES = A.step_cases(ENTRY, BAD_CFG, PTRS16, PTRS8, ADAMS, adams_in_full=("adam_users", "adam_fc2"),
+                     sizes=(0, "short", "item-only"),
+                     hyper=[{f"{a}.{k}": v} for a in ADAMS[1:] for k, v in (("lr", 2e-3), ("beta1", 0.8), ("beta2", 0.99))] +
+                     [{"adam_items.lr": 2e-3}])
 
 
 def _cfg(**kw):
@@ -321,8 +292,15 @@ def _cfg(**kw):
                                     c["num_users"])
 
 
-def _id(n, c):
-    return f"{n[18:]}-" + "-".join(f"{k}={v}" for k, v in c.items())
+def _adam_n(lib):
+    conv = _cfg().step.conv
+    return {"adam_items": GOOD["item_size"] * GOOD["width"], "adam_users": GOOD["num_users"] * GOOD["width"],
+            "adam_weights": lib.bsarec_caser_weight_floats(conv), "adam_fc": lib.bsarec_caser_fc_floats(conv),
+            "adam_fc2": lib.bsarec_caser_fc2_floats(conv)}
+
+
+SPEC = A.spec(GOOD, _cfg, ENTRY, PTRS16, PTRS8, need=lambda lib: lib.bsarec_caser_user_step_workspace_bytes(_cfg()), adam_n=_adam_n,
+              sizes=lambda lib: {"item-only": lib.bsarec_caser_step_workspace_bytes(_cfg().step)})
 
 
 def test_workspace_and_size_queries():
@@ -339,30 +317,6 @@ def test_workspace_and_size_queries():
     assert lib.bsarec_caser_fc2_floats(None) < 0 and lib.bsarec_caser_fc2_floats(_cfg(width=6).step.conv) < 0
 
 
-@pytest.mark.parametrize("name,change", CASES, ids=[_id(n, c) for n, c in CASES])
+@pytest.mark.parametrize("name,change", CASES, ids=A.ids(CASES, "bsarec_caser_user_"))
 def test_invalid_arguments_return_negative_without_a_gpu(name, change):
-    from bsarec_amd import _lib
-    lib = _lib.load()
-    buf = (C.c_byte * 4096)()
-    p = C.addressof(buf) + (-C.addressof(buf)) % 16           # a 16-byte aligned host address (never dereferenced)
-    need = lib.bsarec_caser_user_step_workspace_bytes(_cfg())
-    n = {"adam_items": GOOD["item_size"] * GOOD["width"], "adam_users": GOOD["num_users"] * GOOD["width"],
-         "adam_weights": lib.bsarec_caser_weight_floats(_cfg().step.conv), "adam_fc": lib.bsarec_caser_fc_floats(_cfg().step.conv),
-         "adam_fc2": lib.bsarec_caser_fc2_floats(_cfg().step.conv)}
-    adam = {a: _lib.Adam(p, p, p, p, n[a], 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, None, 0) for a in n}
-    kw = dict(cfg=_cfg(), item_emb=p, user_emb=p, weights=p, fc=p, fc2=p, ids=p, users=p, answers=p, neg_answers=p, state=p, train=1,
-              loss_out=p, d_item_emb=p, d_user_emb=p, dweights=p, dfc=p, dfc2=p, workspace=p, workspace_bytes=need, stream=None,
-              **adam)
-    for k, v in change.items():
-        if k in GOOD:
-            kw["cfg"] = _cfg(**change)
-        elif "." in k:
-            a, field = k.split(".")
-            v = {"p": p, "p+4": p + 4, "n+4": n[a] + 4, "n-4": n[a] - 4}.get(v, v) if isinstance(v, str) else v
-            if field == "n_grad_srcs":
-                adam[a].grad_srcs[0] = p
-            setattr(adam[a], field, v)
-        else:
-            sizes = {"p+4": p + 4, "p+2": p + 2, "short": need - 1, "item-only": lib.bsarec_caser_step_workspace_bytes(_cfg().step)}
-            kw[k] = sizes.get(v, v) if isinstance(v, str) else v
-    assert getattr(lib, name)(*[kw[k] for k in ENTRY[name]]) < 0
+    assert A.call(SPEC, name, change) < 0

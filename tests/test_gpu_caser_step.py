@@ -14,9 +14,6 @@ and, at shape 1, at the seven sets of weights of the three-step cases.  Shape 1 
 over the three steps there, nor at B = 17, where the first that does is 5629 (every Adam step moves every filter by about lr, so
 each set of weights is a fresh draw of 3,264 cells against the margin); so shape 1 has B = 17, one row past a 16-row tile."""
 import argparse
-import ast
-import functools
-import logging
 
 import numpy as np
 import pytest
@@ -24,6 +21,7 @@ import pytest
 from conftest import rel_l2
 import caser_ref as R
 import caser_step_ref as S
+import step_harness as H
 
 pytestmark = pytest.mark.gpu
 LOSS_GATE, OUT_GATE, GRAD_GATE = 5e-6, 2e-5, 2e-4
@@ -44,21 +42,9 @@ def _args(shape, p=0.0, **kw):
     return a
 
 
-@functools.lru_cache(maxsize=None)
 def _batch(shape):
-    """As test_gpu_gru4rec_step._batch: padding zeros in front, an answer and a negative equal to a looked-up id, a row whose
-    answer is its negative, a negative equal to another row's answer."""
-    import torch
     V, d, L, B, nh, nv = SHAPES[shape]
-    g = torch.Generator().manual_seed(11)
-    ids = torch.randint(1, V, (B, L), generator=g)
-    ids[:5, :max(1, min(7, L - 1))] = 0
-    pos = torch.randint(1, V, (B,), generator=g)
-    neg = torch.randint(1, V, (B,), generator=g)
-    pos[6], neg[7] = ids[6, -1], ids[7, -1]
-    neg[8] = pos[8]
-    neg[9] = pos[10]
-    return ids, pos, neg
+    return H.pairwise_batch(V, L, B)
 
 
 def _host_model(shape, p=0.0, seed=None, **kw):
@@ -82,10 +68,6 @@ def _model(shape, p=0.0, **kw):
     return m
 
 
-def _params(m):
-    return {k: v.detach().cpu().numpy().astype(np.float64) for k, v in m.state_dict().items()}
-
-
 def _mult(shape, p, seed, step):
     V, d, L, B, nh, nv = SHAPES[shape]
     return S.dropout_mult(B, nv * d + nh * L, p, seed, step)
@@ -96,14 +78,33 @@ def _assert_condition(params, ids, mult, what):
     assert cells == 0 and umin >= MARGIN, (what, cells, umin)             # a condition on the inputs, not a tolerance
 
 
-@functools.lru_cache(maxsize=None)
 def _reference(shape, p, seed, step):
-    """Loss, s and gradients of the reference at the model's initial weights, under the mask of (seed, step): computed once."""
-    ids, pos, neg = (t.numpy() for t in _batch(shape))
-    params = _params(_host_model(shape))
+    """Loss, s and gradients of the reference at the model's initial weights, under the mask of (seed, step)."""
+    ids, pos, neg = H.host(D, shape)
+    params = H.params64(_host_model(shape))
     mult = _mult(shape, p, seed, step)
     _assert_condition(params, ids, mult, (shape, p))
     return S.loss_and_grads(params, ids, pos, neg, mult)
+
+
+D = H.describe(stem="caser", name="Caser", flag="caser_step", seed=SEED, loss_gate=LOSS_GATE, grad_gate=GRAD_GATE,
+               vbl=lambda shape: (SHAPES[shape][0], SHAPES[shape][3], SHAPES[shape][2]), slot=lambda B, L: B,
+               args=_args, model=_model, batch=_batch, reference=_reference, mults=_mult,
+               train_step=lambda params, st, hb, mult: S.train_step(params, st, *hb, mult),
+               before_step=lambda params, hb, mult, what: _assert_condition(params, hb[0], mult, what),
+               eval_kw=dict(train=False),
+               adam_tag="caser fused adam",
+               moved=("item_embeddings.weight", "conv.conv_v.weight", "conv.conv_v.bias", "conv.conv_h.0.weight",
+                      "conv.conv_h.5.bias", "fc1.weight", "fc1.bias"),
+               main=dict(argv=["--max_seq_length", "12", "--hidden_size", "32", "--batch_size", "64"],
+                         synth=dict(n_users=120, n_items=200), tag="fused caser main.run"),
+               trainer=("test_gpu_caser_model", "fc1.weight"))
+
+
+def _line(errs):
+    worst = max((v, k) for k, v in errs.items() if k.startswith("conv.conv_h"))
+    return (f"E {errs['item_embeddings.weight']:.2e} conv_v {errs['conv.conv_v.weight']:.2e} / {errs['conv.conv_v.bias']:.2e} "
+            f"worst conv_h {worst[0]:.2e} ({worst[1]}) fc1 {errs['fc1.weight']:.2e} / {errs['fc1.bias']:.2e}")
 
 
 @pytest.mark.parametrize("p", [0.0, 0.5])
@@ -111,61 +112,29 @@ def _reference(shape, p, seed, step):
 def test_loss_and_grads_against_the_reference(shape, p):
     import torch
     V, d, L, B, nh, nv = SHAPES[shape]
-    m = _model(shape, p)
-    ids, pos, neg = (t.cuda() for t in _batch(shape))
-    loss, grads = m.loss_and_grads(ids, pos, neg, train=True)
-    st = m.step_state.cpu().tolist()
-    assert st[0] == SEED and st[1] == 1 and st[2] == 0        # the step counter advanced once, Adam's t did not
-    rloss, _, rgrads = _reference(shape, p, st[0], st[1])
+    m, call, loss, grads, (rloss, _, rgrads) = H.first_call(D, shape, p)
+    ids, pos, neg = call[0]
     assert list(grads) == list(m.state_dict()) == S.keys(L)
-    e_loss = abs(loss.item() - rloss) / abs(rloss)
-    errs = {}
-    for k, g in grads.items():
-        if not rgrads[k].any():
-            assert not g.any().item(), k                      # a bank none of whose cells passes: exactly zero
-            continue
-        errs[k] = rel_l2(g.cpu().numpy(), rgrads[k])
-    g = grads["item_embeddings.weight"].cpu().numpy()
     both = np.array([ids[6, -1].item(), ids[7, -1].item()])
-    e_both = rel_l2(g[both], rgrads["item_embeddings.weight"][both])
-    worst = max((v, k) for k, v in errs.items() if k.startswith("conv.conv_h"))
-    print(f"caser step shape {shape} p={p}: loss {loss.item():.7f} rel {e_loss:.2e} rows(lookup+head) {e_both:.2e} "
-          f"E {errs['item_embeddings.weight']:.2e} conv_v {errs['conv.conv_v.weight']:.2e} / {errs['conv.conv_v.bias']:.2e} "
-          f"worst conv_h {worst[0]:.2e} ({worst[1]}) fc1 {errs['fc1.weight']:.2e} / {errs['fc1.bias']:.2e}")
-    assert e_loss <= LOSS_GATE
-    for k, v in errs.items():
-        assert v <= GRAD_GATE, (k, v)
-    assert e_both <= GRAD_GATE
+    g = H.check_loss_and_grads(D, shape, p, loss, grads, rloss, rgrads, both, zero_banks=True, line=_line)
     touched = torch.unique(torch.cat([ids.reshape(-1), pos, neg])).cpu().numpy()
     rest = np.setdiff1d(np.arange(V), touched)
     assert not g[rest].any()                                  # exactly zero, every float written
     assert not rgrads["item_embeddings.weight"][rest].any()
-    # the same call again: the next mask at p > 0, the same bits at p = 0
-    loss2, grads2 = m.loss_and_grads(ids, pos, neg, train=True)
-    assert m.step_state[1].item() == 2 and m.step_state[2].item() == 0
-    same = all(torch.equal(grads[k], grads2[k]) for k in grads) and torch.equal(loss, loss2)
-    assert same == (p == 0.0)
-    if p > 0.0:
-        # train = 0 draws nothing and touches no counter: the bits of the p = 0 model
-        loss0, grads0 = m.loss_and_grads(ids, pos, neg, train=False)
-        assert m.step_state[1].item() == 2
-        lossz, gradsz = _model(shape, 0.0).loss_and_grads(ids, pos, neg, train=True)
-        assert torch.equal(loss0, lossz)
-        for k in grads0:
-            assert torch.equal(grads0[k], gradsz[k]), k
+    H.second_call_tail(D, m, shape, p, call, loss, grads)
 
 
 def test_state_of_the_step_against_the_reference():
     """s as the step forms it (read from the step's workspace region) at p = 0.5, and forward() in eval mode at p = 0."""
     import torch
     V, d, L, B, nh, nv = SHAPES[1]
-    ids, pos, neg = (t.cuda() for t in _batch(1))
+    (ids, pos, neg), _ = H.cuda(D, 1)
     m = _model(1, 0.0)
     m.eval()
     with torch.no_grad():
         s = m(ids)
     m.train()
-    e0 = rel_l2(s.cpu().numpy(), _reference(1, 0.0, SEED, 1)[1])
+    e0 = rel_l2(s.cpu().numpy(), H.reference(D, 1, 0.0, SEED, 1)[1])
     assert e0 <= OUT_GATE
     m = _model(1, 0.5)
     m.loss_and_grads(ids, pos, neg, train=True)
@@ -174,151 +143,40 @@ def test_state_of_the_step_against_the_reference():
     conv_floats = B * L * nh                                  # the convolution workspace of train = 1, a multiple of 4 ints
     off = conv_floats + B * L * d + 2 * B * F                 # | x | z | zd | s
     s5 = slot["ws"].view(torch.float32)[off:off + B * d].view(B, d).cpu().numpy()
-    s_r = _reference(1, 0.5, SEED, 1)[1]
+    s_r = H.reference(D, 1, 0.5, SEED, 1)[1]
     e5 = rel_l2(s5, s_r)
     print(f"caser step s: p=0 {e0:.2e} p=0.5 {e5:.2e} alive {(s_r > 0).mean():.2f}")
     assert e5 <= OUT_GATE and (s_r > 0).mean() > 0.2          # the ReLU is neither dead nor idle
 
 
 def test_a_row_whose_answer_is_its_negative_adds_exactly_nothing():
-    import torch
-    V, d, L, B, nh, nv = SHAPES[1]
-    m = _model(1)
-    ids, pos, neg = (t.clone() for t in _batch(1))
-    lone = int(np.setdiff1d(np.arange(1, V), torch.cat([ids.reshape(-1), pos, neg]).numpy())[0])
-    pos[8] = neg[8] = lone
-    _, grads = m.loss_and_grads(ids.cuda(), pos.cuda(), neg.cuda(), train=False)
-    assert not grads["item_embeddings.weight"][lone].any().item()
+    H.a_row_whose_answer_is_its_negative_adds_exactly_nothing(D)
 
 
 @pytest.mark.parametrize("p,wd", STEP_CASES)
 def test_three_train_steps_against_the_reference(p, wd):
-    import torch
     V, d, L, B, nh, nv = SHAPES[1]
-    m = _model(1, p, weight_decay=wd, caser_step_graph=False)
-    before = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    params = _params(m)
-    ids, pos, neg = _batch(1)
-    st = S.adam_state(lr=1e-3, weight_decay=wd)
-    losses = []
-    for step in range(1, 4):
-        mult = _mult(1, p, SEED, step)
-        _assert_condition(params, ids.numpy(), mult, (p, wd, step))
-        losses.append(m.train_step(ids.cuda(), pos.cuda(), neg.cuda()).item())
-        rl = S.train_step(params, st, ids.numpy(), pos.numpy(), neg.numpy(), mult)
-        print(f"caser fused adam p={p} wd={wd} step {step}: loss {losses[-1]:.7f} reference {rl:.7f}")
-    assert np.isfinite(losses).all()
-    state = m.step_state.cpu().tolist()
-    assert state[0] == SEED and state[1] == 3 and state[2] == 3
+    m = H.three_adam_steps(D, p, wd)
     flat, fc = m.conv._flat, m._fc_flat
     lay = {"conv." + n: o for n, o, _ in R.layout(L, d, nh, nv)[0]}
-    worst = (0.0, None)
     for k, q in m.named_parameters():
-        e = rel_l2(q.detach().cpu().numpy(), params[k])
-        worst = max(worst, (e, k))
-        assert e <= GRAD_GATE, (k, e)
         if k in lay:                                          # updated in place: still views of the flat arrays
             assert q.data_ptr() == flat.data_ptr() + 4 * lay[k], k
-    print(f"caser fused adam x3 p={p} wd={wd}: worst parameter {worst[0]:.2e} ({worst[1]})")
-    for k in ("item_embeddings.weight", "conv.conv_v.weight", "conv.conv_v.bias", "conv.conv_h.0.weight", "conv.conv_h.5.bias",
-              "fc1.weight", "fc1.bias"):
-        assert not torch.equal(m.state_dict()[k], before[k]), k                               # it moved
     assert m.fc1.weight.data_ptr() == fc.data_ptr() and m.fc1.bias.data_ptr() == fc.data_ptr() + 4 * m.fc1.weight.numel()
     assert fc.numel() == m.fc1.weight.numel() + d
 
 
-def _three_steps(m, poison=False):
-    import torch
-    V, d, L, B, nh, nv = SHAPES[1]
-    ids, pos, neg = (t.cuda() for t in _batch(1))
-    losses = []
-    for _ in range(3):
-        if poison:
-            m._slot(m._step_buffers(), B)["ws"].fill_(0xFF)   # NaN in every float, all ones in the accumulator, -1 in the windows
-        losses.append(m.train_step(ids, pos, neg).clone())
-    return torch.stack(losses), {k: v.detach().clone() for k, v in m.state_dict().items()}
-
-
 def test_determinism_with_a_poisoned_workspace():
-    import torch
-    la, pa = _three_steps(_model(1, 0.5, caser_step_graph=False))
-    lb, pb = _three_steps(_model(1, 0.5, caser_step_graph=False), poison=True)
-    assert torch.isfinite(la).all() and torch.equal(la, lb)
-    for k in pa:
-        assert torch.equal(pa[k], pb[k]), k
+    H.determinism_with_a_poisoned_workspace(D)
 
 
 def test_graph_replay_is_the_next_step():
-    import torch
-    mg = _model(1, 0.5)
-    lg, pg = _three_steps(mg)
-    le, pe = _three_steps(_model(1, 0.5, caser_step_graph=False))
-    assert mg._fused["slots"][SHAPES[1][3]]["graph"] is not None
-    assert torch.equal(lg, le) and len(set(lg.tolist())) == 3      # three different masks, three different t
-    for k in pg:
-        assert torch.equal(pg[k], pe[k]), k
-    assert mg.step_state.cpu().tolist()[1:3] == [3, 3]
+    H.graph_replay_is_the_next_step(D)
 
 
 def test_main_run_with_the_fused_step(monkeypatch):
-    import torch
-    from bsarec_amd import data as Dm, main as M
-
-    def no_optimiser(*a, **kw):
-        raise AssertionError("a torch optimiser was built for a fused Caser")
-    monkeypatch.setattr(torch.optim, "Adam", no_optimiser)
-    msgs = []
-
-    class Grab(logging.Handler):
-        def emit(self, rec):
-            msgs.append(rec.msg)
-    logger = logging.getLogger("caser_step_main")
-    logger.setLevel(logging.INFO)
-    logger.propagate = False
-    logger.addHandler(Grab())
-    seqs = Dm.synth_ml1m_like(seed=5, n_users=120, n_items=200)
-    args = M.parse_args(["--model_type", "Caser", "--caser_step", "fused", "--max_seq_length", "12", "--hidden_size", "32",
-                         "--batch_size", "64", "--epochs", "2", "--patience", "100"])
-    scores, info, epochs, secs = M.run(args, seqs, logger)
-    losses = [float(ast.literal_eval(m)["rec_loss"]) for m in msgs if isinstance(m, str) and "'rec_loss'" in m]
-    print(f"fused caser main.run: losses {losses} scores {scores}")
-    assert epochs == 2 and len(losses) == 2 and np.isfinite(losses).all()
-    assert losses[1] < losses[0]
-    assert len(scores) == 6 and np.isfinite(scores).all() and all(0.0 <= s <= 1.0 for s in scores)
+    H.main_run_with_the_fused_step(D, monkeypatch)
 
 
 def test_trainer_mode_switch_and_checkpoint_round_trip(tmp_path):
-    import torch
-    from bsarec_amd import CaserModel
-    from test_gpu_caser_model import _setup
-    with pytest.raises(ValueError, match="caser_step"):
-        CaserModel(_args(1, caser_step="bogus"))
-    default = CaserModel(_args(1, caser_step="torch")).cuda()
-    ids, pos, neg = (t.cuda() for t in _batch(1))
-    with pytest.raises(RuntimeError, match="torch.optim.Adam"):
-        default.train_step(ids, pos, neg)
-    seqs, args, model, tr = _setup(["--caser_step", "fused"])
-    assert model.caser_step == "fused" and model.torch_optim is False
-    tr.train(0)
-    assert getattr(tr, "_torch_opt", None) is None
-    assert model.step_state[2].item() > 0                     # Adam's t: the steps ran in the library
-    path = str(tmp_path / "caser_fused.pt")
-    before = {k: v.detach().clone() for k, v in model.state_dict().items()}
-    tr.save(path)
-    with torch.no_grad():
-        for q in model.parameters():
-            q.add_(1.0)
-    tr.load(path)
-    for k, v in model.state_dict().items():
-        assert torch.equal(v, before[k]), k
-    t = model.step_state[2].item()
-    tr.train(1)                                               # the step still updates the loaded arrays in place
-    assert model.step_state[2].item() > t
-    assert any(not torch.equal(v, before[k]) for k, v in model.state_dict().items())
-    # the default path still trains, through a torch optimiser
-    seqs, args, model, tr = _setup(["--caser_step", "torch"])
-    assert model.caser_step == "torch" and model.torch_optim is True
-    before = {k: v.detach().clone() for k, v in model.state_dict().items()}
-    post = tr.train(0)
-    assert np.isfinite(float(post["rec_loss"])) and getattr(tr, "_torch_opt", None) is not None
-    assert not torch.equal(model.state_dict()["fc1.weight"], before["fc1.weight"])
+    H.trainer_mode_switch_and_checkpoint_round_trip(D, tmp_path)

@@ -17,7 +17,6 @@ sets of weights of the three-step cases (shape 1: 1092; 286 seeds below it hold 
 At shape 4 seed 0 holds too, but its bank of height 2 passes nothing: seed 1 is the first at which, besides, every gradient
 tensor of the reference is non-zero."""
 import argparse
-import functools
 
 import numpy as np
 import pytest
@@ -25,6 +24,7 @@ import pytest
 from conftest import rel_l2
 import caser_ref as R
 import caser_user_ref as UR
+import step_harness as H
 
 pytestmark = pytest.mark.gpu
 LOSS_GATE, OUT_GATE, GRAD_GATE = 5e-6, 2e-5, 2e-4
@@ -46,22 +46,12 @@ def _args(shape, p=0.0, **kw):
     return a
 
 
-@functools.lru_cache(maxsize=None)
 def _batch(shape):
-    """As test_gpu_caser_step._batch -- padding zeros in front, an answer and a negative equal to a looked-up id, a row whose
-    answer is its negative, a negative equal to another row's answer -- with users that include 0, U - 1 and repeats."""
+    """The pairwise batch with users that include 0, U - 1 and repeats."""
     import torch
     V, U, d, L, B, nh, nv = SHAPES[shape]
-    g = torch.Generator().manual_seed(11)
-    ids = torch.randint(1, V, (B, L), generator=g)
-    ids[:5, :max(1, min(7, L - 1))] = 0
-    pos = torch.randint(1, V, (B,), generator=g)
-    neg = torch.randint(1, V, (B,), generator=g)
-    users = torch.randint(0, U, (B,), generator=g)
+    ids, users, pos, neg = H.pairwise_batch(V, L, B, U)
     if B > 10:
-        pos[6], neg[7] = ids[6, -1], ids[7, -1]
-        neg[8] = pos[8]
-        neg[9] = pos[10]
         users[0], users[1], users[2], users[5] = 0, U - 1, users[3], U - 1
         if U <= B - 6:
             users[6:6 + U] = torch.arange(U)                  # fewer users than rows: every one of them is named
@@ -70,7 +60,7 @@ def _batch(shape):
 
 def _users_outside(shape):
     """The users of the batch with two rows outside [0, U): one at U, one negative."""
-    users = _batch(shape)[1].clone()
+    users = H.batch(D, shape)[1].clone()
     users[3], users[11] = SHAPES[shape][1], -1
     return users
 
@@ -99,10 +89,6 @@ def _model(shape, p=0.0, **kw):
     return m
 
 
-def _params(m):
-    return {k: v.detach().cpu().numpy().astype(np.float64) for k, v in m.state_dict().items()}
-
-
 def _mult(shape, p, seed, step):
     V, U, d, L, B, nh, nv = SHAPES[shape]
     return UR.dropout_mult(B, nv * d + nh * L, p, seed, step)
@@ -113,16 +99,30 @@ def _assert_condition(params, ids, users, mult, what):
     assert cells == 0 and umin >= MARGIN, (what, cells, umin)             # a condition on the inputs, not a tolerance
 
 
-@functools.lru_cache(maxsize=None)
 def _reference(shape, p, seed, step, outside=False):
-    """Loss, (z1, x2, s) and gradients of the reference at the model's initial weights, under the mask of (seed, step): once."""
-    ids, users, pos, neg = (t.numpy() for t in _batch(shape))
+    """Loss, (z1, x2, s) and gradients of the reference at the model's initial weights, under the mask of (seed, step)."""
+    ids, users, pos, neg = H.host(D, shape)
     if outside:
         users = _users_outside(shape).numpy()
-    params = _params(_host_model(shape))
+    params = H.params64(_host_model(shape))
     mult = _mult(shape, p, seed, step)
     _assert_condition(params, ids, users, mult, (shape, p, outside))
     return UR.loss_and_grads(params, ids, users, pos, neg, mult)
+
+
+def _call(batch):
+    ids, users, pos, neg = batch
+    return (ids, pos, neg), dict(user_ids=users)
+
+
+D = H.describe(stem="caser_user", name="Caser", flag="caser_step", seed=SEED, loss_gate=LOSS_GATE,
+               grad_gate=GRAD_GATE, vbl=lambda shape: (SHAPES[shape][0], SHAPES[shape][4], SHAPES[shape][3]), slot=lambda B, L: B,
+               args=_args, model=_model, batch=_batch, reference=_reference, mults=_mult, call=_call,
+               train_step=lambda params, st, hb, mult: UR.train_step(params, st, *hb, mult),
+               before_step=lambda params, hb, mult, what: _assert_condition(params, hb[0], hb[1], mult, what),
+               eval_kw=dict(train=False), adam_tag="caser user fused adam",
+               moved=("item_embeddings.weight", "user_embeddings.weight", "conv.conv_v.weight", "conv.conv_h.0.weight",
+                      "conv.conv_h.5.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"))
 
 
 def _workspace_regions(m, shape):
@@ -192,31 +192,17 @@ def _compare(shape, p, m, users, loss, grads, ref, tag):
 def test_loss_and_grads_against_the_reference(shape, p):
     import torch
     V, U, d, L, B, nh, nv = SHAPES[shape]
-    m = _model(shape, p)
-    ids, users, pos, neg = (t.cuda() for t in _batch(shape))
+    m, call, loss, grads, ref = H.first_call(D, shape, p)
+    (ids, pos, neg), users = call[0], call[1]["user_ids"]
     if shape < 4:
         assert (users == 0).any() and (users == U - 1).any() and len(torch.unique(users)) < B
-    loss, grads = m.loss_and_grads(ids, pos, neg, train=True, user_ids=users)
-    st = m.step_state.cpu().tolist()
-    assert st[0] == SEED and st[1] == 1 and st[2] == 0        # the step counter advanced once, Adam's t did not
-    rest = _compare(shape, p, m, users, loss, grads, _reference(shape, p, st[0], st[1]), "grads")
+    rest = _compare(shape, p, m, users, loss, grads, ref, "grads")
     assert (len(rest) > 0) == (shape in (3, 4))               # more users than rows: untouched rows exist there
     touched = torch.unique(torch.cat([ids.reshape(-1), pos, neg])).cpu().numpy()
     gE = grads["item_embeddings.weight"].cpu().numpy()
     assert not gE[np.setdiff1d(np.arange(V), touched)].any()
-    # [B, 1] user ids are the same call; the same call again is the next mask at p > 0, the same bits at p = 0
-    loss2, grads2 = m.loss_and_grads(ids, pos, neg, train=True, user_ids=users.view(B, 1))
-    assert m.step_state[1].item() == 2 and m.step_state[2].item() == 0
-    same = all(torch.equal(grads[k], grads2[k]) for k in grads) and torch.equal(loss, loss2)
-    assert same == (p == 0.0)
-    if p > 0.0:
-        # train = 0 draws nothing and touches no counter: the bits of the p = 0 model
-        loss0, grads0 = m.loss_and_grads(ids, pos, neg, train=False, user_ids=users)
-        assert m.step_state[1].item() == 2
-        lossz, gradsz = _model(shape, 0.0).loss_and_grads(ids, pos, neg, train=True, user_ids=users)
-        assert torch.equal(loss0, lossz)
-        for k in grads0:
-            assert torch.equal(grads0[k], gradsz[k]), k
+    # [B, 1] user ids are the same call
+    H.second_call_tail(D, m, shape, p, call, loss, grads, again=dict(user_ids=users.view(B, 1)))
 
 
 def test_a_user_id_outside_the_table_gives_a_zero_half_and_adds_nothing():
@@ -224,10 +210,10 @@ def test_a_user_id_outside_the_table_gives_a_zero_half_and_adds_nothing():
     shape = 2
     V, U, d, L, B, nh, nv = SHAPES[shape]
     m = _model(shape, 0.5)
-    ids, _, pos, neg = (t.cuda() for t in _batch(shape))
+    (ids, pos, neg), _ = H.cuda(D, shape)
     users = _users_outside(shape).cuda()
     loss, grads = m.loss_and_grads(ids, pos, neg, train=True, user_ids=users)
-    _compare(shape, 0.5, m, users, loss, grads, _reference(shape, 0.5, SEED, 1, True), "outside")
+    _compare(shape, 0.5, m, users, loss, grads, H.reference(D, shape, 0.5, SEED, 1, True), "outside")
     _, x2, _ = _workspace_regions(m, shape)
     assert not x2[[3, 11], d:].any().item() and x2[0, d:].any().item()
     # every user outside: the whole half is zero and the user table gets exactly no gradient
@@ -251,90 +237,35 @@ def test_a_user_id_outside_the_table_gives_a_zero_half_and_adds_nothing():
 
 @pytest.mark.parametrize("p,wd", STEP_CASES)
 def test_three_train_steps_against_the_reference(p, wd):
-    import torch
     V, U, d, L, B, nh, nv = SHAPES[1]
-    m = _model(1, p, weight_decay=wd, caser_step_graph=False)
-    before = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    params = _params(m)
-    ids, users, pos, neg = _batch(1)
-    st = UR.adam_state(lr=1e-3, weight_decay=wd)
-    losses = []
-    for step in range(1, 4):
-        mult = _mult(1, p, SEED, step)
-        _assert_condition(params, ids.numpy(), users.numpy(), mult, (p, wd, step))
-        losses.append(m.train_step(ids.cuda(), pos.cuda(), neg.cuda(), user_ids=users.cuda()).item())
-        rl = UR.train_step(params, st, ids.numpy(), users.numpy(), pos.numpy(), neg.numpy(), mult)
-        print(f"caser user fused adam p={p} wd={wd} step {step}: loss {losses[-1]:.7f} reference {rl:.7f}")
-    assert np.isfinite(losses).all()
-    state = m.step_state.cpu().tolist()
-    assert state[0] == SEED and state[1] == 3 and state[2] == 3            # the counter and ONE t for the five arrays
+    m = H.three_adam_steps(D, p, wd)
     flat, fc, fc2 = m.conv._flat, m._fc_flat, m._fc2_flat
     lay = {"conv." + n: o for n, o, _ in R.layout(L, d, nh, nv)[0]}
-    worst = (0.0, None)
     for k, q in m.named_parameters():
-        e = rel_l2(q.detach().cpu().numpy(), params[k])
-        worst = max(worst, (e, k))
-        assert e <= GRAD_GATE, (k, e)
         if k in lay:                                          # updated in place: still views of the flat arrays
             assert q.data_ptr() == flat.data_ptr() + 4 * lay[k], k
-    print(f"caser user fused adam x3 p={p} wd={wd}: worst parameter {worst[0]:.2e} ({worst[1]})")
-    for k in ("item_embeddings.weight", "user_embeddings.weight", "conv.conv_v.weight", "conv.conv_h.0.weight",
-              "conv.conv_h.5.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"):
-        assert not torch.equal(m.state_dict()[k], before[k]), k                               # it moved
     assert m.fc1.weight.data_ptr() == fc.data_ptr() and m.fc1.bias.data_ptr() == fc.data_ptr() + 4 * m.fc1.weight.numel()
     assert m.fc2.weight.data_ptr() == fc2.data_ptr() and m.fc2.bias.data_ptr() == fc2.data_ptr() + 4 * m.fc2.weight.numel()
     assert fc2.numel() == 2 * d * d + d
     assert m.user_embeddings.weight.data_ptr() == m._fused["P"].data_ptr()
 
 
-def _three_steps(m, poison=False, users=None):
-    """Three train_steps on the batch of shape 1; ``users``: one user tensor per step (default: the batch's for all three)."""
-    import torch
-    V, U, d, L, B, nh, nv = SHAPES[1]
-    ids, u0, pos, neg = (t.cuda() for t in _batch(1))
-    losses = []
-    for i in range(3):
-        if poison:
-            m._slot(m._step_buffers(), B)["ws"].fill_(0xFF)   # NaN in every float, all ones in both accumulators
-        losses.append(m.train_step(ids, pos, neg, user_ids=u0 if users is None else users[i].cuda()).clone())
-    return torch.stack(losses), {k: v.detach().clone() for k, v in m.state_dict().items()}
-
-
 def test_determinism_with_a_poisoned_workspace():
-    import torch
-    la, pa = _three_steps(_model(1, 0.5, caser_step_graph=False))
-    lb, pb = _three_steps(_model(1, 0.5, caser_step_graph=False), poison=True)
-    assert torch.isfinite(la).all() and torch.equal(la, lb)
-    for k in pa:
-        assert torch.equal(pa[k], pb[k]), k
+    H.determinism_with_a_poisoned_workspace(D)
 
 
 def test_graph_replay_is_the_next_step():
-    import torch
-    mg = _model(1, 0.5)
-    lg, pg = _three_steps(mg)
-    le, pe = _three_steps(_model(1, 0.5, caser_step_graph=False))
-    assert mg._fused["slots"][SHAPES[1][4]]["graph"] is not None
-    assert torch.equal(lg, le) and len(set(lg.tolist())) == 3      # three different masks, three different t
-    for k in pg:
-        assert torch.equal(pg[k], pe[k]), k
-    assert mg.step_state.cpu().tolist()[1:3] == [3, 3]
+    H.graph_replay_is_the_next_step(D)
 
 
 def test_a_replay_reads_the_users_of_its_own_step():
     import torch
     V, U, d, L, B, nh, nv = SHAPES[1]
-    u0 = _batch(1)[1]
+    u0 = H.batch(D, 1)[1]
     u1 = (u0 + 3) % U                                             # other users in the static buffer for the second replay
     assert not torch.equal(u0, u1)
-    seq = [u0, u1, u0]
-    mg = _model(1, 0.5)
-    lg, pg = _three_steps(mg, users=seq)
-    assert mg._fused["slots"][B]["graph"] is not None
-    le, pe = _three_steps(_model(1, 0.5, caser_step_graph=False), users=seq)
-    assert torch.equal(lg, le)
-    for k in pg:
-        assert torch.equal(pg[k], pe[k]), k
-    ls, ps = _three_steps(_model(1, 0.5))                          # the same users three times: another result
+    a, _ = H.cuda(D, 1)
+    lg, pg = H.graph_replay_is_the_next_step(D, calls=[(a, dict(user_ids=u.cuda())) for u in (u0, u1, u0)])
+    ls, ps = H.three_steps(D, _model(1, 0.5))                      # the same users three times: another result
     assert torch.equal(ls[0], lg[0]) and not torch.equal(ls[1], lg[1])
     assert not torch.equal(ps["user_embeddings.weight"], pg["user_embeddings.weight"])

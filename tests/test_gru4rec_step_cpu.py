@@ -3,16 +3,13 @@ in double on the twin model, the new symbols and their bindings, the header as p
 points (they return < 0 before any HIP call), the command-line flag and the model's mode switch."""
 import argparse
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-from conftest import ROOT
+import abi_cases as A
 import gru4rec_step_ref as S
 
 V, D, H, N, L, B = 23, 8, 32, 2, 5, 6
@@ -77,21 +74,11 @@ NAMES = ("bsarec_gru4rec_workspace_bytes", "bsarec_gru4rec_loss_grad", "bsarec_g
 
 def test_symbols_are_exported_and_bound():
     from bsarec_amd import _lib
-    lib = _lib.load()
-    for name in NAMES:
-        assert name in _lib.EXPORTS
-        assert getattr(lib, name).argtypes == _lib.EXPORTS[name][1]
-        assert getattr(lib, name).restype == _lib.EXPORTS[name][0]
-    assert len(_lib.EXPORTS["bsarec_gru4rec_loss_grad"][1]) == 14 and len(_lib.EXPORTS["bsarec_gru4rec_train_step"][1]) == 11
-    assert [f for f, _ in _lib.Gru4RecConfig._fields_] == ["gru", "item_size", "dropout"]
-    assert C.sizeof(_lib.Gru4RecConfig) == C.sizeof(_lib.GruConfig) + 8
-    assert lib.bsarec_abi_version() == 10 and _lib.ABI_VERSION == 10
+    A.check_symbols(NAMES, {"bsarec_gru4rec_loss_grad": 14, "bsarec_gru4rec_train_step": 11}, _lib.Gru4RecConfig,
+                    ["gru", "item_size", "dropout"], C.sizeof(_lib.GruConfig) + 8)
 
 
 def test_header_block_is_plain_c99_and_links(tmp_path):
-    lib_dir = os.path.join(ROOT, "bsarec_amd")
-    if not os.path.exists(os.path.join(lib_dir, "libbsarec_hip.so")) or not shutil.which("gcc"):
-        pytest.skip("library or gcc missing")
     src = r"""
 #include "bsarec_hip.h"
 #include <stdio.h>
@@ -109,14 +96,7 @@ int main(void) {
     return (lg && ts && bsarec_abi_version() == 10 && ws > gws && gws > 0 && bad < 0) ? 0 : 1;
 }
 """
-    f = tmp_path / "host.c"
-    f.write_text(src)
-    exe = tmp_path / "host"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(f), "-o", str(exe),
-                    "-L", lib_dir, "-lbsarec_hip", f"-Wl,-rpath,{lib_dir}"], check=True, capture_output=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    ver, ws, gws, bad = (int(v) for v in r.stdout.split())
+    ver, ws, gws, bad = A.run_c99(tmp_path, src)
     T, Bq, d, Vq = 256 * 50, 256, 64, 3417
     assert ver == 10 and ws == gws + 4 * (2 * T * d + 2 * Bq * d + 2 * Bq + 2 * Vq * d)
 
@@ -134,18 +114,7 @@ ENTRY = {"bsarec_gru4rec_loss_grad": LOSS_GRAD, "bsarec_gru4rec_train_step": TRA
 PTRS16 = {"bsarec_gru4rec_loss_grad": ["item_emb", "weights", "d_item_emb", "dweights", "workspace"],
           "bsarec_gru4rec_train_step": ["workspace"]}
 PTRS8 = ["ids", "answers", "neg_answers", "state"]
-ADAM_PTRS = ["params", "grads", "exp_avg", "exp_avg_sq"]
-CASES = [(n, c) for n in ENTRY for c in BAD_CFG] + [(n, dict(cfg=None)) for n in ENTRY]
-CASES += [(n, {p: v}) for n in ENTRY for p in PTRS16[n] + PTRS8 for v in (None, "p+4")]
-CASES += [(n, dict(loss_out=v)) for n in ENTRY for v in (None, "p+2")]
-CASES += [(n, dict(workspace_bytes=v)) for n in ENTRY for v in (0, "short")]
-T = "bsarec_gru4rec_train_step"
-CASES += [(T, {a: None}) for a in ("adam_items", "adam_weights")]
-CASES += [(T, {f"{a}.{p}": v}) for a in ("adam_items", "adam_weights") for p in ADAM_PTRS for v in (None, "p+4")]
-CASES += [(T, {f"{a}.n": v}) for a in ("adam_items", "adam_weights") for v in ("n+4", "n-4", 0)]
-CASES += [(T, {f"{a}.{k}": v}) for a in ("adam_items", "adam_weights")
-          for k, v in (("shadow_bf16", "p"), ("grads2", "p"), ("grads2_n", 4), ("n_grad_srcs", 1), ("wimage_plan", "p"))]
-CASES += [(T, {"adam_weights.lr": 2e-3}), (T, {"adam_weights.beta1": 0.8}), (T, {"adam_items.beta2": 0.99})]
+CASES = A.step_cases(ENTRY, BAD_CFG, PTRS16, PTRS8)
 
 
 def _cfg(**kw):
@@ -156,8 +125,9 @@ def _cfg(**kw):
     return _lib.Gru4RecConfig(gru, c["item_size"], c["dropout"])
 
 
-def _id(n, c):
-    return f"{n[15:]}-" + "-".join(f"{k}={v}" for k, v in c.items())
+SPEC = A.spec(GOOD, _cfg, ENTRY, PTRS16, PTRS8, need=lambda lib: lib.bsarec_gru4rec_workspace_bytes(_cfg()),
+              adam_n=lambda lib: {"adam_items": GOOD["item_size"] * GOOD["input_size"],
+                                  "adam_weights": lib.bsarec_gru_weight_floats(_cfg().gru)})
 
 
 def test_workspace_query():
@@ -171,29 +141,9 @@ def test_workspace_query():
         assert lib.bsarec_gru4rec_workspace_bytes(_cfg(**change)) < 0, change
 
 
-@pytest.mark.parametrize("name,change", CASES, ids=[_id(n, c) for n, c in CASES])
+@pytest.mark.parametrize("name,change", CASES, ids=A.ids(CASES, "bsarec_gru4rec_"))
 def test_invalid_arguments_return_negative_without_a_gpu(name, change):
-    from bsarec_amd import _lib
-    lib = _lib.load()
-    buf = (C.c_byte * 4096)()
-    p = C.addressof(buf) + (-C.addressof(buf)) % 16           # a 16-byte aligned host address (never dereferenced)
-    need = lib.bsarec_gru4rec_workspace_bytes(_cfg())
-    n = {"adam_items": GOOD["item_size"] * GOOD["input_size"], "adam_weights": lib.bsarec_gru_weight_floats(_cfg().gru)}
-    adam = {a: _lib.Adam(p, p, p, p, n[a], 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, None, 0) for a in n}
-    kw = dict(cfg=_cfg(), item_emb=p, weights=p, ids=p, answers=p, neg_answers=p, state=p, train=1, loss_out=p, d_item_emb=p,
-              dweights=p, workspace=p, workspace_bytes=need, stream=None, **adam)
-    for k, v in change.items():
-        if k in GOOD:
-            kw["cfg"] = _cfg(**change)
-        elif "." in k:
-            a, field = k.split(".")
-            v = {"p": p, "p+4": p + 4, "n+4": n[a] + 4, "n-4": n[a] - 4}.get(v, v) if isinstance(v, str) else v
-            if field == "n_grad_srcs":
-                adam[a].grad_srcs[0] = p
-            setattr(adam[a], field, v)
-        else:
-            kw[k] = {"p+4": p + 4, "p+2": p + 2, "short": need - 1}.get(v, v) if isinstance(v, str) else v
-    assert getattr(lib, name)(*[kw[k] for k in ENTRY[name]]) < 0
+    assert A.call(SPEC, name, change) < 0
 
 
 def _args(**kw):
@@ -205,12 +155,7 @@ def _args(**kw):
 
 
 def test_command_line_flag():
-    from bsarec_amd.main import parse_args
-    assert not hasattr(parse_args([]), "gru_step")                 # absent unless given: the logged arguments stay as they were
-    assert parse_args(["--model_type", "GRU4Rec", "--gru_step", "fused"]).gru_step == "fused"
-    assert parse_args(["--gru_step", "torch"]).gru_step == "torch"
-    with pytest.raises(SystemExit):
-        parse_args(["--gru_step", "graph"])
+    A.check_flag("gru_step", "GRU4Rec")
 
 
 def test_mode_switch_on_the_host():
